@@ -67,7 +67,14 @@ def parse():
     ap.add_argument("--small-legs", action="store_true", help="those legs at a fraction of their size (tests)")
     ap.add_argument("--serial-prep", action="store_true",
                     help="keep the ICP target preparation on the main stream (default: side stream, next to the front end)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy, float32 / float64: the "
+                         "per-keyframe ICP results and point counts of the whole batch, and the CFAR masks, points and "
+                         "filtered clouds of a fixed sample of its frames (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_inputs(rank, batch):
@@ -328,6 +335,42 @@ def parity_check(kb, res, frames, srcs, tgts, guesses, det, fe, icp_mode, filter
                        % ("downsample+remove_outlier cloud, " if filters else "", picks)}
 
 
+DUMP_FRAMES = 8            # frames of the batch whose per-pixel / per-point outputs are dumped
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, kb, res, filters):
+    """The outputs of the last timed step, as a caller of KeyframeBatch receives them, written to path/<name>.npy.
+    Whole batch: ICP pose (float32, as computed), status, iterations, extracted and filtered point counts (int32 values,
+    stored as float64).  For DUMP_FRAMES frames drawn with a fixed seed: the 0/1 CFAR mask (float32), the float64 points
+    and the float32 filtered cloud; the variable-length clouds are concatenated, frame k's rows being
+    offsets[k]:offsets[k + 1].  -> total bytes written"""
+    n = len(res["status"])
+    # python ints: the batch's accessors turn j into a device address offset
+    picks = [int(j) for j in np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_FRAMES), replace=False))]
+    out = {"icp_T": np.asarray(res["T"], np.float32),
+           "icp_status": np.asarray(res["status"], np.float64),
+           "icp_iters": np.asarray(res["iters"], np.float64),
+           "point_counts": np.asarray(res["counts"], np.float64),
+           "sample_frames": np.asarray(picks, np.float64),
+           "sample_masks": np.stack([kb.mask(j) for j in picks]).astype(np.float32)}
+    pts = [np.asarray(kb.points(j), np.float64).reshape(-1, 2) for j in picks]
+    out["sample_points"] = np.concatenate(pts)
+    out["sample_points_offsets"] = np.cumsum([0] + [len(p) for p in pts]).astype(np.float64)
+    if filters:
+        out["cloud_counts"] = np.asarray(res["cloud_counts"], np.float64)
+        cl = [np.asarray(kb.cloud(j), np.float32).reshape(-1, 2) for j in picks]
+        out["sample_clouds"] = np.concatenate(cl)
+        out["sample_clouds_offsets"] = np.cumsum([0] + [len(c) for c in cl]).astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_MAX_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -446,6 +489,8 @@ def main():
     if rank == 0 and args.parity_jobs > 0:   # the timed step's own outputs, before anything overwrites them
         parity = parity_check(kb_last, res, frames, srcs, tgts, guesses, det, fe, args.icp_mode, not args.no_filters,
                               args.parity_jobs)
+    if rank == 0 and args.dump_outputs:      # also before the legs below reuse the batch's buffers
+        dump_outputs(args.dump_outputs, kb_last, res, not args.no_filters)
 
     out = None
     if rank == 0:

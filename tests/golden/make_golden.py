@@ -39,6 +39,7 @@ import ast
 import hashlib
 import json
 import os
+import re
 import sys
 import types
 
@@ -700,9 +701,46 @@ def bearings_for(n, aperture_deg=130.0):
     return np.round(np.linspace(-half, half, n)).astype(np.int16)
 
 
+def make_bindings():
+    """-> ref_bindings.json: the names the two pybind modules bind (cpp/cfar.cpp, cpp/pcl.cpp): module functions
+    (`m.def`) and every `.def`, methods of pcl's ICP class included, in source order"""
+    out = {}
+    for fname in ("cfar.cpp", "pcl.cpp"):
+        text = open(os.path.join(REF, "cpp", fname)).read()
+        out[fname] = {"m.def": re.findall(r'm\.def\("(\w+)"', text), ".def": re.findall(r'\.def\("(\w+)"', text)}
+    with open(os.path.join(HERE, "ref_bindings.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote ref_bindings.json")
+
+
+def make_cfar_ref_digest():
+    """-> cfar_ref_digest.json: digests of what the reference's own cfar.cpp (oracle/_ref) returns on the cases of
+    tests/test_reference_cfar.py"""
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))
+    import oracle
+    if not oracle.have_ref_cfar():
+        sys.exit("oracle/_ref/libcfar_ref.so missing: run `make -C oracle ref` first")
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_reference_cfar as t
+    out = {}
+    for alg in t.ALGS:
+        out.update(t.reference_digests(t.host_cases(alg) + t.full_size_cases(alg)))
+    with open(os.path.join(HERE, "cfar_ref_digest.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote cfar_ref_digest.json")
+
+
 def main():
     if not os.path.isdir(REF):
         sys.exit("reference tree not present; fixtures are committed, nothing to do")
+    if sys.argv[1:] == ["bindings"]:
+        make_bindings()
+        return
+    if sys.argv[1:] == ["cfar_digest"]:
+        make_cfar_ref_digest()
+        return
     if sys.argv[1:] == ["nssm"]:
         make_nssm_pieces()
         return
@@ -829,6 +867,8 @@ def main():
     make_ssm_session()
     make_nssm_session()
     make_feature_callback()
+    make_bindings()
+    make_cfar_ref_digest()
 
 
 if __name__ == "__main__":

@@ -115,3 +115,50 @@ def test_leg_checker_accepts_the_oracle_and_raises_on_a_wrong_pose_status_or_ite
     again = bench_legs.oracle_many(jobs * 4, {}, threads=8)
     for j, (r64, r32) in enumerate(again):
         assert r64[0] == ref[j % 4][0] and r64[2] == ref[j % 4][2] and np.array_equal(r64[1], ref[j % 4][1])
+
+
+class _IntIndexedBatch(_OracleBackedBatch):
+    """KeyframeBatch turns the frame index into a device address: ctypes takes a python int there, not a numpy one"""
+
+    def mask(self, j):
+        assert type(j) is int
+        return self.m[j]
+
+    def points(self, j):
+        assert type(j) is int
+        return self.p[j]
+
+    def cloud(self, j):
+        assert type(j) is int
+        return self.c[j]
+
+
+def test_dump_outputs_writes_the_step_outputs_as_float_arrays(tmp_path):
+    """bench.py --dump-outputs: every array float32 / float64, the whole batch's per-keyframe results, the sampled
+    frames' masks / points / clouds exactly as the batch hands them out, the same sample on every run, under 64 MB"""
+    det = CFAR(40, 10, 0.1, 10)
+    frames = bench.make_inputs(0, 2)[0]
+    res_, height_, rows_, width_, cols_, mx, my = build_maps(oculus_bearings(bench.COLS), 30.0 / bench.ROWS, bench.ROWS)
+    fe = SimpleNamespace(map_x=mx, map_y=my, rows=rows_, cols=cols_, width=width_, height=height_)
+    kb = _IntIndexedBatch(frames, det, fe)
+    res = {"T": np.stack([np.eye(3, dtype=np.float32)] * 2), "status": np.array([0, 1], np.int32),
+           "iters": np.array([30, 7], np.int32), "counts": np.array([len(p) for p in kb.p], np.int32),
+           "cloud_counts": np.array([len(c) for c in kb.c], np.int32)}
+    total = bench.dump_outputs(str(tmp_path / "a"), kb, res, True)
+    assert 0 < total <= 64 << 20
+    got = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in os.listdir(str(tmp_path / "a"))}
+    assert sum(a.nbytes for a in got.values()) == total
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert np.array_equal(got["icp_T"], res["T"]) and got["icp_T"].dtype == np.float32
+    for k in ("status", "iters"):
+        assert np.array_equal(got["icp_" + k], res[k])
+    assert np.array_equal(got["point_counts"], res["counts"]) and np.array_equal(got["cloud_counts"], res["cloud_counts"])
+    assert list(got["sample_frames"]) == [0, 1]
+    po, co = got["sample_points_offsets"].astype(int), got["sample_clouds_offsets"].astype(int)
+    for k, j in enumerate(got["sample_frames"].astype(int)):
+        assert np.array_equal(got["sample_masks"][k], kb.m[j])
+        assert np.array_equal(got["sample_points"][po[k]:po[k + 1]], kb.p[j])
+        assert np.array_equal(got["sample_clouds"][co[k]:co[k + 1]], kb.c[j])
+    bench.dump_outputs(str(tmp_path / "b"), kb, res, False)
+    assert sorted(os.listdir(str(tmp_path / "b"))) == sorted(f for f in os.listdir(str(tmp_path / "a")) if "cloud" not in f)
+    assert np.array_equal(np.load(str(tmp_path / "b" / "sample_points.npy")), got["sample_points"])

@@ -1,5 +1,6 @@
 """CPU: host logic -- ICP YAML parsing, the C-ABI surface, loud failure without a GPU,
 the job-farm sharding (incl. a 2-process gloo run)."""
+import json
 import os
 import re
 import subprocess
@@ -349,16 +350,16 @@ def test_shims_bind_every_name_the_reference_modules_define():
     assert accepts(pcl.ICP, 0)
     for name, n in (("loadFromYaml", 1), ("compute", 3), ("getCovariance", 0)):
         assert accepts(getattr(pcl.ICP(), name), n), name
-    # and the reference's own source names nothing else
-    ref = os.path.join("/root/reference/bruce_slam/src/bruce_slam/cpp")
-    if os.path.isdir(ref):     # (present in the build container only)
-        import re
-        for fname, mod in (("cfar.cpp", cfar), ("pcl.cpp", pcl)):
-            text = open(os.path.join(ref, fname)).read()
-            for name in re.findall(r'm\.def\("(\w+)"', text):
-                assert hasattr(mod, name), (fname, name)
-            for name in re.findall(r'\.def\("(\w+)"', text):
-                assert hasattr(mod, name) or hasattr(pcl.ICP, name), (fname, name)
+    # and the reference's own source names nothing else (tests/golden/ref_bindings.json: every m.def / .def name of the two
+    # files, recorded by tests/golden/make_golden.py)
+    bound = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_bindings.json")))
+    assert sorted(bound) == ["cfar.cpp", "pcl.cpp"]
+    for fname, mod in (("cfar.cpp", cfar), ("pcl.cpp", pcl)):
+        assert bound[fname]["m.def"] and bound[fname][".def"]
+        for name in bound[fname]["m.def"]:
+            assert hasattr(mod, name), (fname, name)
+        for name in bound[fname][".def"]:
+            assert hasattr(mod, name) or hasattr(pcl.ICP, name), (fname, name)
 
 
 def test_glibc_rand_restatement_and_density_filter_surface():
