@@ -76,6 +76,18 @@ void sfe_ctx_destroy(sfe_ctx *ctx);
 const char *sfe_last_error(sfe_ctx *ctx); /* ctx may be NULL: error of the last failed create */
 int sfe_sync(sfe_ctx *ctx);
 int sfe_device_name(sfe_ctx *ctx, char *buf, int cap);
+/* Launcher knob `name` of this context := value; the old value goes to *previous (may be NULL).  Every
+ * setting computes the same results: the knobs choose kernels and their launch shapes.  An unknown name,
+ * a value outside the knob's range or a fraction for an integer knob fails with SFE_ERR_ARG and changes
+ * nothing.  The names, defaults and ranges (LAB_NOTEBOOK.md, Appendix A):
+ *   cfar_os_gated (1), cfar_os_gated_min (40), cfar_os_pref (1), cfar_os_pref_x (80)     OS CFAR kernels
+ *   extract_rec_cap (0 = built-in), extract_capw (0 = built-in), extract_compact (1)    batched extraction
+ *   cost_many (1)                                                                       matching cost
+ *   sw_tiers, sw_tiny, sw_multi (1), sw_multi_g (0), sw_multi_min_src (8192),           strip-sweep ICP
+ *   sw_multi_share_min (1024), sw_cache, sw_rec (1), sw_budget (128), sw_budget_a (6),
+ *   sw_margin (15), sw_rtrips (4), sw_recm (8), sw_reck (3.0, a float), sw_strip_pts (96),
+ *   sw_union_iters (1), sw_union_max (768), icp_debug (0) */
+int sfe_tune(sfe_ctx *ctx, const char *name, double value, double *previous);
 
 /* device memory on the ctx's device, for resident pipelines (*_dev entry points) */
 int sfe_malloc(sfe_ctx *ctx, size_t bytes, void **dptr);

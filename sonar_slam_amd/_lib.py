@@ -4,6 +4,7 @@ Host code stays Python, exactly as in the reference (rospy nodes calling native 
 this module is the only place that touches the shared library.  There is NO CPU fallback:
 if the library or a gfx950 device is missing, every compute call raises.
 """
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -71,6 +72,7 @@ SIGNATURES = {
     "sfe_last_error": (C.c_char_p, [_vp]),
     "sfe_sync": (C.c_int, [_vp]),
     "sfe_device_name": (C.c_int, [_vp, C.c_char_p, C.c_int]),
+    "sfe_tune": (C.c_int, [_vp, C.c_char_p, C.c_double, C.POINTER(C.c_double)]),
     "sfe_malloc": (C.c_int, [_vp, C.c_size_t, C.POINTER(_vp)]),
     "sfe_free": (C.c_int, [_vp, _vp]),
     "sfe_memcpy_h2d": (C.c_int, [_vp, _vp, _vp, C.c_size_t]),
@@ -264,6 +266,24 @@ class Context(object):
         buf = C.create_string_buffer(256)
         self._check(self.lib.sfe_device_name(self.handle, buf, 256))
         return buf.value.decode()
+
+    def tune(self, name, value):
+        """set launcher knob `name` of this context (sfe_tune); returns its previous value"""
+        prev = C.c_double(0)
+        self._check(self.lib.sfe_tune(self.handle, name.encode(), float(value), C.byref(prev)))
+        return prev.value
+
+    @contextlib.contextmanager
+    def tuning(self, **knobs):
+        """``with ctx.tuning(sw_tiers=0, sw_tiny=0): ...`` -- the knobs set for the block, the previous values back after it"""
+        saved = []
+        try:
+            for name, value in knobs.items():
+                saved.append((name, self.tune(name, value)))
+            yield self
+        finally:
+            for name, value in reversed(saved):
+                self.tune(name, value)
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -1010,7 +1010,7 @@ static void launch_ring(sfe_ctx *ctx, int alg, const uint8_t *d_img, uint8_t *d_
     const int chunks = ((cols >> 2) + 63) / 64;
     const long long bpf = ((long long)tiles * chunks + 3) / 4;             // workgroups per frame
     const unsigned blocks = (unsigned)((((long long)n_frames + 7) / 8) * 8 * bpf); // frames padded to the 8 XCDs
-    static const int full_last = getenv("SFE_CFAR_FULL_LAST_TILE") ? 1 : 0; // A/B: the last tile as long as the others (rounds 1-4)
+    const int full_last = 0; // (1: the last tile as long as the others, rounds 1-4)
     if (alg == SFE_CFAR_SOCA)
         hipLaunchKernelGGL((cfar_u8_ring<T, G, SFE_CFAR_SOCA, D, BITS, THR>), dim3(blocks), dim3(256), 0, ctx->stream,
                            d_img, d_mask, rows, cols, n_frames, groups, tiles, chunks, out_frame_bytes, lut, d_thr, ta, full_last);
@@ -1040,8 +1040,6 @@ static CfarThrArith thr_arith_checked(sfe_ctx *ctx, int alg, int T, double tau)
         if (__builtin_memcmp(&want, &got, sizeof want) != 0)
             ta.on = 0; // (never seen: the kernels then read the table)
     }
-    if (getenv("SFE_CFAR_THR_TABLE"))
-        ta.on = 0; // A/B
     ctx->tha_alg = alg;
     ctx->tha_T = T;
     ctx->tha_tau = tau;
@@ -1106,9 +1104,9 @@ static int launch_os_gated(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int
     tab.c0 = 1;
     tab.m_le = 0;
     if (pref) {
-        // the level: what a pixel of a third of full scale is compared with (L[80]; SFE_CFAR_OS_PREF_X moves it).  Any level is
+        // the level: what a pixel of a third of full scale is compared with (L[80]; tuning cfar_os_pref_x moves it).  Any level is
         // exact; this one keeps both kinds of candidates rare on sonar images
-        const int xs = std::min(255, std::max(tab.xc, getenv("SFE_CFAR_OS_PREF_X") ? atoi(getenv("SFE_CFAR_OS_PREF_X")) : 80));
+        const int xs = std::min(255, std::max(tab.xc, ctx->tune.cfar_os_pref_x));
         const int l0 = xs <= 255 ? tab.L[xs] : -1;
         const bool ok = l0 >= 0 && l0 < 255 && 2 * T <= 127 && k + 1 <= 2 * T;
         if (applied)
@@ -1124,8 +1122,8 @@ static int launch_os_gated(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int
     const int tiles_y = (rows + OSG_TR - 1) / OSG_TR, tiles_x = (cols + OSG_TC - 1) / OSG_TC;
     const size_t smem = (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC + (size_t)OSG_TR * (OSG_TC / 8) + sizeof(unsigned short) * 4 * (OSG_LIST + 256) +
                         (pref ? (size_t)8 * 32 * 2 * 4 : 0);
-    const bool v16 = cols % 16 == 0 && (((uintptr_t)d_img | (uintptr_t)d_mask) & 15) == 0 && !getenv("SFE_CFAR_OSG_V4");
-    const int pv = !pref ? 0 : (T == 20 && !getenv("SFE_CFAR_OS_PREF_SLIDE")) ? 2 : 1;
+    const bool v16 = cols % 16 == 0 && (((uintptr_t)d_img | (uintptr_t)d_mask) & 15) == 0;
+    const int pv = !pref ? 0 : T == 20 ? 2 : 1;
     auto kernel = pv == 2 ? (v16 ? cfar_u8_os_gated<true, 2> : cfar_u8_os_gated<false, 2>)
                   : pv == 1 ? (v16 ? cfar_u8_os_gated<true, 1> : cfar_u8_os_gated<false, 1>)
                             : (v16 ? cfar_u8_os_gated<true, 0> : cfar_u8_os_gated<false, 0>);
@@ -1158,8 +1156,7 @@ static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int row
     const int ringR = 2 * (T + G) + 2;
     // (with a threshold map: when it can be computed, cfar_thr_arith, and not next to the bit-stream output)
     const CfarThrArith thr_ta = (d_thr && alg != SFE_CFAR_OS) ? thr_arith_checked(ctx, alg, T, tau) : CfarThrArith{0.0, 0.0, 1.0, 0};
-    static const bool no_ring_thr = getenv("SFE_CFAR_NO_RING_THR") != nullptr; // A/B
-    bool ring = (alg != SFE_CFAR_OS) && (!d_thr || (thr_ta.on && !d_bits && !no_ring_thr && reinterpret_cast<uintptr_t>(d_thr) % 16 == 0)) && (cols % 4 == 0) && cols >= 256 && rows >= ringR && (size_t)rows * cols < (1u << 30) &&
+    bool ring = (alg != SFE_CFAR_OS) && (!d_thr || (thr_ta.on && !d_bits && reinterpret_cast<uintptr_t>(d_thr) % 16 == 0)) && (cols % 4 == 0) && cols >= 256 && rows >= ringR && (size_t)rows * cols < (1u << 30) &&
                 ctx->cfar_variant != 1 &&
                 ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_mask)) % 4 == 0) &&
                 ring_window && build_lut(alg, T, tau, intensity_thr, &lut);
@@ -1247,10 +1244,9 @@ static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int row
         // window rows staged in LDS (R KiB per workgroup) unless the window is too tall for it
         const int R = 2 * (T + G) + 2;
         const size_t ring_bytes = (size_t)R * 1024;
-        static const bool no_lds = getenv("SFE_CFAR_NO_LDS_RING") != nullptr; // A/B
         // beyond two workgroups per CU (R > 80 rows = 80 KiB) the ring starves the CU of waves and re-reading the four
         // rows through the caches is faster (measured (80, 20): 15 % of HBM with the LDS ring, 25 % without)
-        const bool lds_ring = ring_bytes <= 80 * 1024 && !no_lds;
+        const bool lds_ring = ring_bytes <= 80 * 1024;
 #define SLIDE_LAUNCH(A, THRB)                                                                                          \
     do {                                                                                                               \
         if (lds_ring) {                                                                                                \
@@ -1281,18 +1277,17 @@ static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int row
         }
 #undef SLIDE_LAUNCH
     } else if (os_hist && !d_thr && aligned && (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC <= 96 * 1024 &&
-               intensity_thr >= (getenv("SFE_CFAR_OS_GATED_MIN") ? atoi(getenv("SFE_CFAR_OS_GATED_MIN")) : 40) &&
-               !getenv("SFE_CFAR_NO_OS_GATED")) {
+               ctx->tune.cfar_os_gated && intensity_thr >= ctx->tune.cfar_os_gated_min) {
         // OS behind a gate: only the pixels above it are looked at (cfar_u8_os_gated).  It pays when the gate removes most
         // pixels -- measured on 512 sonar frames, (Ntc 40, Ngc 10, k 10): gate 65 0.65 ms against the histogram kernel's
         // 1.65 ms; gate 20 (four pixels in ten pass) 1.84 against 1.65 -- so a low gate keeps the histogram kernel
-        // (feature.yaml ships 65; SFE_CFAR_OS_GATED_MIN moves the limit).
+        // (feature.yaml ships 65; tuning cfar_os_gated_min moves the limit).
         if (int rc = launch_os_gated(ctx, d_img, n_frames, rows, cols, T, G, k, tau, intensity_thr, d_mask))
             return rc;
     } else if (os_hist) {
         // no gate, or a low one: the pre-filtered candidate kernel (round 6) where it applies, else the sliding histogram
         bool done = false;
-        if (!d_thr && aligned && (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC <= 96 * 1024 && !getenv("SFE_CFAR_NO_OS_PREF"))
+        if (!d_thr && aligned && (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC <= 96 * 1024 && ctx->tune.cfar_os_pref)
             if (int rc = launch_os_gated(ctx, d_img, n_frames, rows, cols, T, G, k, tau, intensity_thr, d_mask, true, &done))
                 return rc;
         if (!done)
@@ -1314,8 +1309,7 @@ static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int row
 static bool ring_bits_applicable(const sfe_ctx *ctx, const uint8_t *d_img, int rows, int cols, int alg, int T, int G)
 {
     const bool ring_window = (T == 20 && G == 5) || (T == 16 && G == 4) || (T == 10 && G == 2) || (T == 8 && G == 1);
-    static const bool off = getenv("SFE_CFAR_NO_BITS") != nullptr; // A/B: byte kernel + mask_pack
-    return !off && ring_window && alg != SFE_CFAR_OS && cols % 32 == 0 && cols >= 256 && rows >= 2 * (T + G) + 2 &&
+    return ring_window && alg != SFE_CFAR_OS && cols % 32 == 0 && cols >= 256 && rows >= 2 * (T + G) + 2 &&
            (size_t)rows * cols < (1u << 30) && ctx->cfar_variant == 0 && reinterpret_cast<uintptr_t>(d_img) % 4 == 0;
 }
 

@@ -389,8 +389,7 @@ static int cost_launch(sfe_ctx *ctx, sfe_costgrid *g, const CostJob *d_jobs, int
                     : (lds ? matching_cost_kernel<false, true> : matching_cost_kernel<false, false>);
     if (lds)
         SFE_HIP(ctx, hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const bool no_many = getenv("SFE_COST_NO_MANY") != nullptr; // A/B (read per call): the 8-poses-per-workgroup kernel for every launch
-    if (lds && n_poses >= 32 && !no_many) {
+    if (lds && n_poses >= 32 && ctx->tune.cost_many) {
         // many poses per job: 64 per workgroup of 16 waves around one staged grid
         auto many = f64 ? matching_cost_many_kernel<true> : matching_cost_many_kernel<false>;
         SFE_HIP(ctx, hipFuncSetAttribute((const void *)many, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));

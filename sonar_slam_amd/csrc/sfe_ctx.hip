@@ -85,9 +85,74 @@ int sfe_pinned_end(sfe_ctx *ctx, hipStream_t s)
     return 0;
 }
 
+// sfe_tune: name -> field of sfe_tuning (an int or a float) and the values it accepts
+namespace {
+struct TuneKnob {
+    const char *name;
+    int sfe_tuning::*i;
+    float sfe_tuning::*f;
+    double lo, hi;
+};
+#define SFE_KNOB_I(n, lo, hi) {#n, &sfe_tuning::n, nullptr, lo, hi}
+#define SFE_KNOB_F(n, lo, hi) {#n, nullptr, &sfe_tuning::n, lo, hi}
+const TuneKnob g_knobs[] = {
+    SFE_KNOB_I(cfar_os_gated, 0, 1),
+    SFE_KNOB_I(cfar_os_gated_min, 0, 256),
+    SFE_KNOB_I(cfar_os_pref, 0, 1),
+    SFE_KNOB_I(cfar_os_pref_x, 0, 255),
+    SFE_KNOB_I(extract_rec_cap, 0, 8192), // (ME_THREADS x ME_RPT, sfe_remap.hip)
+    SFE_KNOB_I(extract_capw, 0, 1 << 20),
+    SFE_KNOB_I(extract_compact, 0, 1),
+    SFE_KNOB_I(cost_many, 0, 1),
+    SFE_KNOB_I(sw_tiers, 0, 1),
+    SFE_KNOB_I(sw_tiny, 0, 1),
+    SFE_KNOB_I(sw_multi, 0, 1),
+    SFE_KNOB_I(sw_multi_g, 0, 16), // (SW_MG_MAX, sfe_icp_sweep.h)
+    SFE_KNOB_I(sw_multi_min_src, 0, 1 << 30),
+    SFE_KNOB_I(sw_multi_share_min, 1, 1 << 30),
+    SFE_KNOB_I(sw_cache, 0, 1),
+    SFE_KNOB_I(sw_rec, 0, 1),
+    SFE_KNOB_I(sw_budget, 1, 65535),
+    SFE_KNOB_I(sw_budget_a, 1, 65535),
+    SFE_KNOB_I(sw_margin, 0, 255),
+    SFE_KNOB_I(sw_rtrips, 1, 255),
+    SFE_KNOB_I(sw_recm, 1, 100),
+    SFE_KNOB_F(sw_reck, 0, 1000),
+    SFE_KNOB_I(sw_strip_pts, 1, 1 << 20),
+    SFE_KNOB_I(sw_union_iters, 0, 255),
+    SFE_KNOB_I(sw_union_max, 0, 65535),
+    SFE_KNOB_I(icp_debug, 0, 1),
+};
+#undef SFE_KNOB_I
+#undef SFE_KNOB_F
+} // namespace
+
 extern "C" {
 
 const char *sfe_version(void) { return "sonarfe 0.1 (gfx950)"; }
+
+int sfe_tune(sfe_ctx *ctx, const char *name, double value, double *previous)
+{
+    if (!ctx)
+        return SFE_ERR_ARG;
+    SFE_ARG(ctx, name);
+    for (const TuneKnob &k : g_knobs) {
+        if (strcmp(k.name, name) != 0)
+            continue;
+        if (!(value >= k.lo && value <= k.hi))
+            return sfe_set_err(ctx, SFE_ERR_ARG, "sfe_tune: %s = %g is outside [%g, %g]", name, value, k.lo, k.hi);
+        if (k.i && value != (double)(int)value)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "sfe_tune: %s takes an integer, not %g", name, value);
+        if (previous)
+            *previous = k.i ? (double)(ctx->tune.*k.i) : (double)(ctx->tune.*k.f);
+        if (k.i)
+            ctx->tune.*k.i = (int)value;
+        else
+            ctx->tune.*k.f = (float)value;
+        return 0;
+    }
+    return sfe_set_err(ctx, SFE_ERR_ARG, "sfe_tune: unknown knob \"%s\"", name);
+}
 
 int sfe_device_count(int *count)
 {

@@ -294,10 +294,7 @@ struct SweepShared {
         break;                                                                                   \
     }
 #define SW_NQ 8         // results fetched per lane and batch in the census / quantile / reduction loops
-#define SW_BUDGET_A 6   // first pass (own strip): walk trips (4 candidates each) before a query is handed on
-#define SW_BUDGET 128   // second pass (all strips): trips + strips before a query is handed to the cooperative tier
-#define SW_CAP_MARGIN 15 // percent
-#define SW_ROUND_TRIPS 4 // second pass: walk trips between two chances to move on to the next strip
+// (the search budgets, the cap margin and the trips per round are tuning: sfe_tuning in sfe_internal.h)
 #define SW_NONE (-1)
 // an unfinished / suspended (inexact) query is stored as pos = -2 - bpos (<= -2; bpos = 0: nothing met
 // yet): the target it holds bounds its next search and doubles as the next iteration's witness
@@ -315,9 +312,8 @@ struct SweepShared {
 // the clouds have converged (a few mm per iteration against neighbour distances of centimetres) almost every query
 // takes this path: the iteration costs a transform, one distance and the census.  Decisions and results are those of
 // the full search: the skip needs a strict gap (1e-5 relative, two orders above the fp32 rounding of the distances).
+// (m and the factor on the last step's movement: tuning sw_recm / sw_reck)
 #define SW_REC_MIN_ITER 12
-#define SW_REC_KAPPA 3.0f
-#define SW_REC_MARGIN 8 // percent: the search radius grows by 8 %, ~17 % more candidates
 
 struct SweepQ { // per-job views of the per-query scratch (the transformed query itself is never stored: whoever needs
                 // it again recomputes it from the source point, two affine maps with wave-uniform coefficients)

@@ -11,15 +11,6 @@
 // host side: job tables, scratch, the prep / split / loop launches.  jobs4 = n_jobs x (src_start, n_src, tgt_start,
 // n_tgt) in points.
 // ---------------------------------------------------------------------------------------------
-namespace {
-int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
-} // namespace
-
 int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
                          const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
                          int32_t *d_iters)
@@ -41,38 +32,25 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     std::vector<int> pids_nrm; // ... and those whose normals take a kernel of their own
     std::map<std::pair<int, int>, int> seen; // many guesses on one pair share one prep
     long long toff = 0, qoff = 0, koff = 0, goff = 0;
-    // (knobs are read per call, not once per process: the tests switch them between calls)
-    // tiers (A/B: SFE_SW_TIERS=0 sends every job to the 1024-thread kernels)
-    const int tiers_on = env_int("SFE_SW_TIERS", 1);
-    const int t0_src = env_int("SFE_SW_T0_SRC", 384), t1_src = env_int("SFE_SW_T1_SRC", 2048);
-    // LDS share of a 1024-thread workgroup: two per CU when the batch has more jobs than CUs, else the whole CU
-    const int force_wide = env_int("SFE_SW_WIDE", -1); // A/B: 1 = one 128-VGPR workgroup per CU
-    const int force_share = env_int("SFE_SW_SHARE_KB", 0); // A/B: LDS per workgroup
-    const bool no_ldsq = getenv("SFE_SW_NO_LDSQ") != nullptr; // A/B
-    // A/B: 0 = never split a job; sfe_icp_set_tuning bit 4 = the same per context (a device shared with another
-    // context / process cannot promise that all shares of a job are resident together: ADVICE r3)
-    const int multi_on = (ctx->icp_variant & 16) ? 0 : env_int("SFE_SW_MULTI", 1);
-    const int multi_min_src = env_int("SFE_SW_MULTI_MIN_SRC", 8192);
-    const int multi_share_min = env_int("SFE_SW_MULTI_SHARE_MIN", 1024); // fewest queries worth a workgroup
-    const int multi_force = env_int("SFE_SW_MULTI_G", 0);     // A/B: shares per job
-    // ~96 points per strip on average (measured optimum 96-128 on 5000-point clouds: fewer queries need a
-    // second strip, a little more to walk in each), one strip (= a plain x sweep) for small clouds
-    const int strip_pts = std::max(1, env_int("SFE_SW_STRIP_PTS", 96));
-    // clouds of a few hundred points: the exhaustive one-wave kernel (A/B: SFE_SW_TINY=0)
-    const int tiny_on = env_int("SFE_SW_TINY", 1);
-    const long long tiny_pairs = env_int("SFE_SW_TINY_PAIRS", (p->use_diff_checker || p->max_iter < SW_REC_MIN_ITER)
-                                                                    ? SW_TINY_PAIRS_SHORT : SW_TINY_PAIRS_LONG);
+    const sfe_tuning &tu = ctx->tune; // (tuning sw_tiers = 0 sends every job to the 1024-thread kernels)
+    // large jobs shared by several workgroups unless tuning sw_multi = 0 or sfe_icp_set_tuning bit 4 (a device shared
+    // with another context / process cannot promise that all shares of a job are resident together: ADVICE r3)
+    const bool multi_on = tu.sw_multi && !(ctx->icp_variant & 16);
+    // ~96 points per strip on average (tuning sw_strip_pts; measured optimum 96-128 on 5000-point clouds: fewer queries need
+    // a second strip, a little more to walk in each), one strip (= a plain x sweep) for small clouds
+    const int strip_pts = tu.sw_strip_pts;
+    // clouds of a few hundred points: the exhaustive one-wave kernel (tuning sw_tiny)
+    const long long tiny_pairs = (p->use_diff_checker || p->max_iter < SW_REC_MIN_ITER) ? SW_TINY_PAIRS_SHORT : SW_TINY_PAIRS_LONG;
     auto is_tiny = [&](int n_src, int n_tgt) {
-        return tiny_on && n_src <= SW_TINY_MAX && n_tgt <= SW_TINY_MAX && (long long)n_src * n_tgt <= tiny_pairs;
+        return tu.sw_tiny && n_src <= SW_TINY_MAX && n_tgt <= SW_TINY_MAX && (long long)n_src * n_tgt <= tiny_pairs;
     };
 
     // The small workgroups buy throughput (many jobs per CU), not latency: ONE scan match of 200 points is done sooner by
     // 256 threads (one slice of queries per pass) than by 64 (four slices, one after the other).  So the one-wave tier is
     // only used when the call brings enough such jobs to fill the device with them (the live node's single scan
     // match takes the four-wave kernel).
-    const int t0_min_jobs = env_int("SFE_SW_T0_MIN_JOBS", 2 * ctx->n_cu), t1_min_jobs = env_int("SFE_SW_T1_MIN_JOBS", 1);
-    auto fits0 = [&](int n_src, int n_tgt) { return tiers_on && n_src <= std::min(t0_src, 4096) && n_tgt <= SW_T0_TCAP; };
-    auto fits1 = [&](int n_src, int n_tgt) { return tiers_on && n_src <= std::min(t1_src, 8192) && n_tgt <= SW_T1_TCAP; };
+    auto fits0 = [&](int n_src, int n_tgt) { return tu.sw_tiers && n_src <= 384 && n_tgt <= SW_T0_TCAP; };
+    auto fits1 = [&](int n_src, int n_tgt) { return tu.sw_tiers && n_src <= 2048 && n_tgt <= SW_T1_TCAP; };
     int n_fit0 = 0, n_fit1 = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const int32_t *q = jobs4 + 4 * (size_t)j;
@@ -81,19 +59,18 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
         else if (fits1(q[1], q[3]))
             ++n_fit1;
     }
-    const bool use_t0 = n_fit0 >= t0_min_jobs;
-    const bool use_t1 = n_fit1 + (use_t0 ? 0 : n_fit0) >= std::max(1, t1_min_jobs);
+    const bool use_t0 = n_fit0 >= 2 * ctx->n_cu;
+    const bool use_t1 = n_fit1 + (use_t0 ? 0 : n_fit0) >= 1;
     // ... and with only a few small jobs in the call the four-wave kernel takes those of at most one slice of queries
     // (measured, one scan match alone: 200 points 261 us with 256 threads, 282 with 1024, 464 with 64; 1000 points 508 us
     // with 256 threads, 341 with 1024)
     const bool few_small = n_fit0 + n_fit1 < 2 * ctx->n_cu;
-    const int t1_few_src = env_int("SFE_SW_T1_FEW_SRC", 320);
     // first pass: sizes -> how many big jobs there are (decides `wide` and whether big jobs are split)
     int n_big = 0, n_t2 = 0;
     auto tier_of = [&](int n_src, int n_tgt) {
         if (use_t0 && fits0(n_src, n_tgt))
             return 0;
-        if (use_t1 && fits1(n_src, n_tgt) && (!few_small || n_src <= t1_few_src))
+        if (use_t1 && fits1(n_src, n_tgt) && (!few_small || n_src <= 320))
             return 1;
         return 2;
     };
@@ -101,19 +78,20 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
         const int32_t *q = jobs4 + 4 * (size_t)j;
         if (!is_tiny(q[1], q[3]) && tier_of(q[1], q[3]) == 2) {
             ++n_t2;
-            if (q[3] > SW_TCAP && q[1] >= multi_min_src)
+            if (q[3] > SW_TCAP && q[1] >= tu.sw_multi_min_src)
                 ++n_big;
         }
     }
-    const bool wide = force_wide >= 0 ? force_wide != 0 : n_t2 <= ctx->n_cu;
-    const size_t lds_share = (force_share > 0 ? force_share : (wide ? 160 : 80)) * (size_t)1024;
+    // LDS share of a 1024-thread workgroup: two per CU when the batch has more jobs than CUs, else the whole CU
+    const bool wide = n_t2 <= ctx->n_cu;
+    const size_t lds_share = (wide ? 160 : 80) * (size_t)1024;
     // Shares per big job: all workgroups of the launch must be resident at once (one 128-VGPR workgroup per CU) -- only
     // when the 1024-thread jobs of this call are the big ones alone and G x n_big fits the CUs
     int mg = 1;
     if (multi_on && n_big > 0 && n_big == n_t2 && wide) {
         mg = std::min(SW_MG_MAX, ctx->n_cu / n_big);
-        if (multi_force > 0)
-            mg = std::min(std::min(multi_force, SW_MG_MAX), std::max(1, ctx->n_cu / n_big));
+        if (tu.sw_multi_g > 0) // (tuning: shares per job)
+            mg = std::min(tu.sw_multi_g, std::max(1, ctx->n_cu / n_big));
     }
     constexpr size_t ctl_q = sweep_ctl_bytes<ICP_THREADS, false, true>(); // (the largest control block of the LDS_Q builds)
     int q_tmax = 0, q_smax = 0, t0_tmax = 0, t0_smax = 0, t1_tmax = 0, t1_smax = 0, tiny_tmax = 0, tiny_smax = 0;
@@ -136,7 +114,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
             prep_tier.push_back(pt);
             prep_need.push_back(0);
             // (targets sorted in HBM scratch get their normals from icp_sweep_normals_kernel: pad_ = 1)
-            const int nrm_later = (q[3] > SW_TCAP && p->minimizer == 1 && env_int("SFE_SW_NORMALS_SPLIT", 1)) ? 1 : 0;
+            const int nrm_later = (q[3] > SW_TCAP && p->minimizer == 1) ? 1 : 0;
             if (nrm_later)
                 pids_nrm.push_back((int)preps.size());
             preps.push_back({q[2], q[3], n_strips, nrm_later, toff, koff, goff});
@@ -150,8 +128,8 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
         if (!tiny || p->minimizer == 1)
             prep_need[(size_t)it->second] = 1;
         int shares = 1;
-        if (tier == 2 && mg > 1 && q[3] > SW_TCAP && q[1] >= multi_min_src)
-            shares = std::max(1, std::min(mg, (int)q[1] / std::max(1, multi_share_min)));
+        if (tier == 2 && mg > 1 && q[3] > SW_TCAP && q[1] >= tu.sw_multi_min_src)
+            shares = std::max(1, std::min(mg, (int)q[1] / tu.sw_multi_share_min));
         const int rec0 = (int)jobs.size();
         for (int g = 0; g < shares; ++g) // (the shares of a split job: the split kernel fills in their clouds)
             jobs.push_back({q[0], q[1], q[3], it->second, pr.off, qoff, j, g, shares, shares > 1 ? n_sync : 0});
@@ -174,7 +152,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
             t1_tmax = std::max(t1_tmax, (int)q[3]);
             t1_smax = std::max(t1_smax, (int)q[1]);
         } else {
-            const bool fits_q = !no_ldsq && q[3] <= SW_TCAP &&
+            const bool fits_q = q[3] <= SW_TCAP &&
                                 ctl_q + 8 * (size_t)(q[3] + SW_PAD) + 6 * (size_t)q[1] + 16 <= lds_share;
             if (fits_q) {
                 ids_q.push_back(rec0);
@@ -283,7 +261,6 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
                                                                           d_stgt, d_perm, d_snrm, d_mean, d_gkeys, d_tab, d_grid))
                 return rc;
         if (np2) {
-            const bool gtail = env_int("SFE_SW_PREP_GTAIL", 1) != 0; // (0: the witness grid in LDS of its own, one workgroup per CU: A/B)
             // (the list capacity the kernel is built for: the smallest of 8 / 10 / 12 / 16 that holds normals_knn)
             const int km = p->minimizer != 1 ? 8 : p->normals_knn <= 8 ? 8 : p->normals_knn <= 10 ? 10 : p->normals_knn <= 12 ? 12 : ICP_KMAX;
             auto go = [&](auto gt, auto kmf) {
@@ -293,7 +270,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
             };
             using std::integral_constant;
             // (lists of 12 / 16 neighbours do not fit 64 registers: 184 / 541 spills; those keep one workgroup per CU)
-            if (int rc = !gtail || km > 10 ? go(std::false_type{}, integral_constant<int, 0>{})
+            if (int rc = km > 10 ? go(std::false_type{}, integral_constant<int, 0>{})
                          : km == 8          ? go(std::true_type{}, integral_constant<int, 8>{})
                                             : go(std::true_type{}, integral_constant<int, 10>{}))
                 return rc;
@@ -318,22 +295,19 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
         SFE_HIP(ctx, hipEventRecord(ctx->ev_prep, ps));
         SFE_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_prep, 0));
     }
-    static const bool debug = getenv("SFE_ICP_DEBUG") != nullptr;
-    // bit 0: witness / clearance cache (0: A/B without it); bits 8..15: walk trips per second-pass round
-    // bit 1: the cap of a repeated round comes from the queries' upper bounds (0: grows 4x)
-    // bit 2: grid witnesses in the first iteration (0: A/B without them)
-    const int sw_cache = (env_int("SFE_SW_CACHE", 1) & 1) | (env_int("SFE_SW_GRID", 1) ? 4 : 0) |
-                         (env_int("SFE_SW_GRID_SKIP", 1) ? 8 : 0) | // bit 3: witnessed queries skip round 0
-                         (env_int("SFE_SW_REC", 1) ? 16 : 0) |      // bit 4: clearance records
-                         (env_int("SFE_SW_TRIAGE", 1) ? 32 : 0) |   // bit 5: ... with triage passes
-                         (env_int("SFE_SW_GRID_DEFER", 1) ? 64 : 0) | // bit 6: first iteration: queries without a witness wait for round 1
-                         (env_int("SFE_SW_UNBOUNDED_COOP", 1) ? 128 : 0) | // bit 7: later passes: unbounded queries -> cooperative tier
-                         (env_int("SFE_SW_LEAN_TRIAGE", 1) ? (1 << 25) : 0) |  // bit 25: the triage pass as a loop of its own
-                         (env_int("SFE_SW_PREDICT_Q", 1) ? (1 << 26) : 0) |    // bit 26: steady state: the trimmed quantile looked for around the previous one
-                         (env_int("SFE_SW_JUMP", 1) ? 2 : 0) |
-                         // bits 16..23: margin (percent) of the next iteration's cap over this iteration's limit
-                         (std::max(0, std::min(255, env_int("SFE_SW_MARGIN", SW_CAP_MARGIN))) << 16) |
-                         (std::max(1, std::min(255, env_int("SFE_SW_RTRIPS", SW_ROUND_TRIPS))) << 8);
+    const bool debug = tu.icp_debug != 0;
+    const int sw_cache = tu.sw_cache |       // bit 0: witness / clearance cache
+                         2 |                 // bit 1: the cap of a repeated round comes from the queries' upper bounds (else grows 4x)
+                         4 |                 // bit 2: grid witnesses in the first iteration
+                         8 |                 // bit 3: witnessed queries skip round 0
+                         (tu.sw_rec ? 16 : 0) | // bit 4: clearance records
+                         32 |                // bit 5: ... with triage passes
+                         64 |                // bit 6: first iteration: queries without a witness wait for round 1
+                         128 |               // bit 7: later passes: unbounded queries -> cooperative tier
+                         (tu.sw_rtrips << 8) | // bits 8..15: walk trips per second-pass round
+                         (tu.sw_margin << 16) | // bits 16..23: margin (percent) of the next iteration's cap over this iteration's limit
+                         (1 << 25) |         // bit 25: the triage pass as a loop of its own
+                         (1 << 26);          // bit 26: steady state: the trimmed quantile looked for around the previous one
     int *d_dbg = nullptr;
     if (debug) {
         d_dbg = (int *)sfe_scratch(ctx, 22, sizeof(int) * 8);
@@ -368,8 +342,8 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     a.d_iters = d_iters;
     a.d_prof = d_prof;
     a.d_dbg = d_dbg;
-    a.sw_budget = env_int("SFE_SW_BUDGET", SW_BUDGET);
-    a.sw_budget_a = env_int("SFE_SW_BUDGET_A", SW_BUDGET_A);
+    a.sw_budget = tu.sw_budget;
+    a.sw_budget_a = tu.sw_budget_a;
     a.sw_cache = sw_cache;
     // union scan of the first iterations: bits 0..7 = iterations that use it, bits 8..23 = most points of a union window.
     // Measured (1024 jobs of 5000 x 5000, search cycles of workgroup 0 per iteration, walks -> union): iteration 0
@@ -377,13 +351,12 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     // from grid witnesses, ~0.9 m) are wide enough for the union of 64 neighbours' windows (~400 points) to beat the
     // private walks; from the second iteration on a query's old neighbour bounds it to a few dozen candidates.  Whole
     // launch: p2plane30 8.78-8.87 -> 8.64-8.76 ms, shipped chain 4.07 -> 3.93-4.00 ms per 1024 jobs.
-    a.sw_cache2 = std::max(0, std::min(255, env_int("SFE_SW_UNION_ITERS", 1))) |
-                  (std::max(0, std::min(65535, env_int("SFE_SW_UNION_MAX", 768))) << 8);
+    a.sw_cache2 = tu.sw_union_iters | (tu.sw_union_max << 8);
     // margin of the clearance records: a search looks this fraction further (in radius) than it has to ...
-    a.sw_m = 0.01f * (float)std::max(1, std::min(100, env_int("SFE_SW_RECM", SW_REC_MARGIN)));
+    a.sw_m = 0.01f * (float)tu.sw_recm;
     // ... plus sw_kappa x the largest movement of the last step (the steps shrink geometrically once ICP converges: a
     // few times the last one covers all that are still to come)
-    a.sw_kappa = getenv("SFE_SW_RECK") ? (float)atof(getenv("SFE_SW_RECK")) : SW_REC_KAPPA;
+    a.sw_kappa = tu.sw_reck;
     a.d_sync = d_sync;
     // The build with clearance records carries more per-lane state (the 64-VGPR budget makes every register count:
     // the same chain runs ~10 % slower in it until the records start to hit), so it only takes chains that are set to
@@ -416,13 +389,10 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     if (n_t1) { // four waves per job, 128 VGPRs, up to 4 jobs per CU
         const int tc = t1_tmax + SW_PAD, qc = (t1_smax + 3) & ~3;
         const size_t body = 8 * (size_t)tc + 6 * (size_t)qc;
-        const int t1_minw = env_int("SFE_SW_T1_MINW", 4); // A/B: 8 = 64 VGPRs, up to 8 jobs per CU
         if (d_prof && !rec_build)
             rc = sweep_launch_loop<SW_T1_NT, 4, true, true, true, false, false>(a, n_t1, ids, body, tc, qc);
-        else if (t1_minw == 8 && !rec_build)
-            rc = sweep_launch_loop<SW_T1_NT, 8, true, true, false, false, false>(a, n_t1, ids, body, tc, qc);
         else
-        rc = rec_build ? sweep_launch_loop<SW_T1_NT, 4, true, true, false, true, false>(a, n_t1, ids, body, tc, qc)
+            rc = rec_build ? sweep_launch_loop<SW_T1_NT, 4, true, true, false, true, false>(a, n_t1, ids, body, tc, qc)
                        : sweep_launch_loop<SW_T1_NT, 4, true, true, false, false, false>(a, n_t1, ids, body, tc, qc);
         if (rc)
             return rc;

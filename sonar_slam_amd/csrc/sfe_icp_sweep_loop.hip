@@ -1735,7 +1735,6 @@ SW_LOOP_INST(ICP_THREADS, 8, true, true, false, true, false)
 SW_LOOP_INST(SW_T0_NT, 4, true, true, false, true, false)
 SW_LOOP_INST(SW_T0_NT, 4, true, true, false, false, false)
 SW_LOOP_INST(SW_T1_NT, 4, true, true, true, false, false)
-SW_LOOP_INST(SW_T1_NT, 8, true, true, false, false, false)
 SW_LOOP_INST(SW_T1_NT, 4, true, true, false, true, false)
 SW_LOOP_INST(SW_T1_NT, 4, true, true, false, false, false)
 SW_LOOP_INST(ICP_THREADS, 4, true, true, false, false, false)

@@ -12,6 +12,41 @@
 #define SFE_NSCRATCH 64
 #define SFE_ICP_PROF_N 96 // values sfe_icp_get_profile hands back
 
+// Launcher knobs of one context, set by name with sfe_tune (the name -> field / range table is in sfe_ctx.hip).  The
+// member initialisers are the shipped defaults; every setting computes the same results.
+struct sfe_tuning {
+    // CFAR, OS (sfe_cfar.hip)
+    int cfar_os_gated = 1;      // behind a gate of at least cfar_os_gated_min: the candidates-only kernel (0: histogram)
+    int cfar_os_gated_min = 40; //   (gate 65: 0.65 ms per 512 frames against the histogram's 1.65; gate 20: 1.84 against 1.65)
+    int cfar_os_pref = 1;       // below it: the pre-filtered candidate kernel where it applies (0: sliding histogram)
+    int cfar_os_pref_x = 80;    //   its level: L[x] for a pixel of about a third of full scale
+    // extraction (sfe_remap.hip)
+    int extract_rec_cap = 0;    // record slots per workgroup region of the record path (0: ME_THREADS x ME_RPT)
+    int extract_capw = 0;       // canvas words a frame of the record path may fill (0: 4096)
+    int extract_compact = 1;    // inverse map in its 4-byte entries (0: the 8-byte entries of round 3)
+    // matching cost (sfe_cost.hip)
+    int cost_many = 1;          // 32+ poses per job: 64 per workgroup around one staged grid (0: 8 per workgroup)
+    // strip-sweep ICP (sfe_icp_sweep.hip)
+    int sw_tiers = 1;           // one-wave / four-wave workgroups for small jobs (0: every job on 1024 threads)
+    int sw_tiny = 1;            // clouds of a few hundred points: the exhaustive one-wave kernel
+    int sw_multi = 1;           // large jobs shared by several workgroups (sfe_icp_set_tuning bit 4 also turns it off)
+    int sw_multi_g = 0;         //   shares per job (0: as many as the CUs allow, at most SW_MG_MAX)
+    int sw_multi_min_src = 8192; //  fewest queries of a job that is shared
+    int sw_multi_share_min = 1024; // fewest queries worth a share
+    int sw_cache = 1;           // witness / clearance cache
+    int sw_rec = 1;             // clearance records (long fixed-count chains only)
+    int sw_budget = 128;        // second pass (all strips): trips + strips before a query goes to the cooperative tier
+    int sw_budget_a = 6;        // first pass (own strip): walk trips (4 candidates each) before a query is handed on
+    int sw_margin = 15;         // percent: the next iteration's cap over this iteration's limit
+    int sw_rtrips = 4;          // second pass: walk trips between two chances to move on to the next strip
+    int sw_recm = 8;            // percent: clearance records search this much further (radius; ~17 % more candidates)
+    float sw_reck = 3.0f;       //   ... plus this many times the largest movement of the last step
+    int sw_strip_pts = 96;      // target points per strip
+    int sw_union_iters = 1;     // first iterations that scan the union of a wave's windows
+    int sw_union_max = 768;     //   ... of at most this many points
+    int icp_debug = 0;          // watchdogs of the sweep kernel reported on stderr (synchronises every call)
+};
+
 struct sfe_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -62,6 +97,7 @@ struct sfe_ctx {
     // (-1: none; anything else that writes those slots resets it)
     int staged_frames = -1;
     long long staged_cap = 0;
+    sfe_tuning tune;
 };
 
 struct sfe_geom {

@@ -542,7 +542,7 @@ __global__ __launch_bounds__(256) void extract_clean_queued_kernel(unsigned long
 // is the (t - offset)-th set bit of that row's words in column order (= np.nonzero order); then metres in fp64,
 // operation by operation.  The general form: it stores the first `cap` points of a frame whatever its count.  With
 // ovf_list it only serves the frames queued there (frames above the capacity, which the word form leaves alone:
-// normally none, the kernel then ends at once); A/B against the word form with SFE_EXPAND_POINTS=1.
+// normally none, the kernel then ends at once).
 __global__ __launch_bounds__(256) void extract_expand_kernel(const unsigned long long *__restrict__ bitmap,
                                                              const int32_t *__restrict__ row_off,
                                                              const int32_t *__restrict__ frame_count,
@@ -1225,7 +1225,7 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
                        float2 *d_p32 = nullptr, CfBBox *d_bbox = nullptr, bool want64 = true)
 {
     const int crows = g->cart_rows, wpr = g->words_per_row;
-    static const int chunk = getenv("SFE_EXTRACT_CHUNK") ? std::max(1, atoi(getenv("SFE_EXTRACT_CHUNK"))) : 1024; // frames per pass: bounds the bitmap scratch (0.25 MB per frame), fewer passes = fewer launches
+    const int chunk = 1024; // frames per pass: bounds the bitmap scratch (0.25 MB per frame), fewer passes = fewer launches
     const size_t bm_bytes = (size_t)chunk * crows * wpr * sizeof(unsigned long long);
     unsigned long long *d_bm = (unsigned long long *)sfe_scratch(ctx, 39, bm_bytes); // (a slot of its own: its contents outlive the call, see self_clean)
     int32_t *d_rcnt = (int32_t *)sfe_scratch(ctx, 5, (size_t)chunk * crows * 4);
@@ -1241,11 +1241,9 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
     SFE_HIP(ctx, hipFuncSetAttribute((const void *)extract_bits_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      g->lds_bytes));
     // word form of the expansion: a list of the non-empty bitmap words per frame (at most one per stored point)
-    static const bool points_form = getenv("SFE_EXPAND_POINTS") != nullptr; // A/B: lane-per-point expansion
-    static const bool nosc = getenv("SFE_NO_SELF_CLEAN") != nullptr;         // A/B: memset of the bitmap per batch
     const long long words_pf = (long long)crows * wpr;
     const size_t tab_bytes = ((size_t)crows + g->cart_cols) * sizeof(double);
-    const bool use_words = !points_form && cap > 0 && std::min(words_pf, cap) <= (1ll << 24) && cap < (1ll << 31) &&
+    const bool use_words = cap > 0 && std::min(words_pf, cap) <= (1ll << 24) && cap < (1ll << 31) &&
                            wpr <= 64 && crows < 32768 && tab_bytes <= 144 * 1024 && g->d_ytab && g->d_xtab;
     const int list_cap = use_words ? (int)std::min(words_pf, cap) : 0;
     int4 *d_wlist = nullptr;
@@ -1261,10 +1259,10 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes));
     }
     // record path (round 5; default for bit-stream batches): no canvas bitmap for the frames that fit its capacities
-    const int rec_cap_env = getenv("SFE_EXTRACT_REC_CAP") ? atoi(getenv("SFE_EXTRACT_REC_CAP")) : 0; // (read per call: the tests
-    const int capw_env = getenv("SFE_EXTRACT_CAPW") ? atoi(getenv("SFE_EXTRACT_CAPW")) : 0;         //  force the hand-back with them)
-    const int rec_cap = std::max(1, std::min(ME_THREADS * ME_RPT, rec_cap_env > 0 ? rec_cap_env : ME_THREADS * ME_RPT));
-    const int capw = (int)std::max<long long>(1, std::min<long long>(capw_env > 0 ? capw_env : 4096, std::min(words_pf, std::max<long long>(cap, 1))));
+    // (tuning extract_rec_cap / extract_capw: the tests force the hand-back with them)
+    const int rec_cap = ctx->tune.extract_rec_cap > 0 ? ctx->tune.extract_rec_cap : ME_THREADS * ME_RPT;
+    const int capw = (int)std::max<long long>(1, std::min<long long>(ctx->tune.extract_capw > 0 ? ctx->tune.extract_capw : 4096,
+                                                                     std::min(words_pf, std::max<long long>(cap, 1))));
     const bool me_narrow = words_pf < 65536 && cap < 65536;
     const size_t me_lds = tab_bytes + (size_t)capw * 8 + ((size_t)(words_pf + 31) / 32) * 8 + ((size_t)capw * 2 + 1) * (me_narrow ? 2 : 4) + 16;
     const bool records = use_words && d_bits_in && ctx->extract_variant == 0 && g->d_inv_off != nullptr &&
@@ -1298,7 +1296,7 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
         // with a capacity: extract_expand_words_kernel clears the words it expands, extract_clean_queued_kernel the
         // frames without a list): the memset is only needed when the scratch is new or another path (or a failed
         // call) has left bits behind.
-        const bool self_clean = gather && d_bits_in && use_words && cap > 0 && !nosc;
+        const bool self_clean = gather && d_bits_in && use_words && cap > 0;
         const size_t bm_need = (size_t)nf * crows * wpr * sizeof(unsigned long long);
         if (!self_clean)
             clean_bytes = 0; // (this pass leaves its bits in the bitmap)
@@ -1309,8 +1307,6 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
                 clean_bytes = std::max(clean_bytes, bm_need);
             // workgroups per frame: enough of them to fill the device with a few frames, few enough that a
             // workgroup's list holds several rounds of 256 set pixels when there are many
-            static const int sg_slices = getenv("SFE_SG_SLICES") ? atoi(getenv("SFE_SG_SLICES")) : 0;
-            static const int sg_piece_env = getenv("SFE_SG_PIECE") ? std::min(8, std::max(0, atoi(getenv("SFE_SG_PIECE")))) : -1;
             // 8192 workgroups per 512 frames measured best (16: 0.259 ms per 512 frames, 8: 0.274, 4: 0.36 -- a workgroup's
             // rounds of 256 set pixels wait for their loads one after the other), in pieces of 1024 words when the frame
             // has that many per workgroup (64 rows of 512 beams: a canvas word collects its bits from neighbouring rows,
@@ -1321,15 +1317,14 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
             // returning atomic, 2 % of the frames handed back; profiles/r05_extract_records_stats.txt.
             // Measured: 256 frames per launch 59.1 us with 32 workgroups per frame, 72.7 with 64; 512 frames 0.147 ms with 16, 0.165
             // with 32; 1024 frames 0.256 ms with 16.  So: 8192 workgroups per launch, but between 16 and 32 per frame for batches.)
-            int slices = sg_slices > 0 ? sg_slices : std::max(2, std::min(64, 8192 / std::max(nf, 1)));
-            if (sg_slices <= 0 && records && nf >= 64)
+            int slices = std::max(2, std::min(64, 8192 / std::max(nf, 1)));
+            if (records && nf >= 64)
                 slices = std::max(16, std::min(32, slices));
             slices = (int)std::max<long long>(1, std::min<long long>(slices, (nwords + 63) / 64));
-            int sg_piece = sg_piece_env >= 0 ? sg_piece_env : 4;
-            while (sg_piece_env < 0 && sg_piece > 0 && (nwords >> (6 + sg_piece)) < slices)
+            int sg_piece = 4;
+            while (sg_piece > 0 && (nwords >> (6 + sg_piece)) < slices)
                 --sg_piece;
-            const bool no_compact = getenv("SFE_EXTRACT_NO_COMPACT") != nullptr; // A/B: the 8-byte entries of round 3 (read per call)
-            const bool c4 = g->d_inv_c4 && !no_compact;
+            const bool c4 = g->d_inv_c4 && ctx->tune.extract_compact;
             const int32_t *p_off = c4 ? reinterpret_cast<const int32_t *>(g->d_inv_ob) : g->d_inv_off;
             const uint2 *p_ent = c4 ? reinterpret_cast<const uint2 *>(g->d_inv_c4) : g->d_inv_lut;
             d_ovf_flag = nullptr;
@@ -1390,10 +1385,9 @@ static int extract_dev(sfe_ctx *ctx, sfe_geom *g, const uint8_t *d_mask, int n_f
             long long *rc_f = d_rc ? d_rc + (size_t)f0 * cap * 2 : nullptr;
             double *pts_f = d_pts ? d_pts + (size_t)f0 * cap * 2 : nullptr;
             if (use_words) {
-                static const int expand_wg_env = getenv("SFE_EXPAND_WG") ? std::max(1, atoi(getenv("SFE_EXPAND_WG"))) : 0;
                 // a workgroup first fetches the two metre tables (23 KB for config A): about a thousand workgroups
                 // per launch, all resident at once (8 per frame measured 69 us per 512 frames, 2 per frame 53)
-                const int expand_wg = expand_wg_env ? expand_wg_env : std::max(1, std::min(EXPAND_WG, 1024 / std::max(nf, 1)));
+                const int expand_wg = std::max(1, std::min(EXPAND_WG, 1024 / std::max(nf, 1)));
                 hipLaunchKernelGGL(extract_expand_words_kernel, dim3(expand_wg, nf), dim3(256), tab_bytes, ctx->stream,
                                    d_wlist, d_wlist_n, list_cap, rc_f, pts_f, cap, crows, g->cart_cols, g->d_ytab, g->d_xtab,
                                    self_clean ? d_bm : nullptr, wpr, (const int32_t *)d_ovf_flag);

@@ -138,11 +138,13 @@ def _chunk_slab(jobs4, lo_col, n_col):
     return lo, hi
 
 
-def _hip_compute(device, params_dict):
-    """the product backend of a farm worker: one sfe_ctx on `device`, chunks of the job table through
-    sfe_icp_compute_jobs (no CPU fallback: without the library or a gfx950 device this raises)"""
+def _hip_compute(device, params_dict, tuning=None):
+    """the product backend of a farm worker: one sfe_ctx on `device` (launcher knobs `tuning`: sfe_tune), chunks of the
+    job table through sfe_icp_compute_jobs (no CPU fallback: without the library or a gfx950 device this raises)"""
     from . import _lib, pcl
     ctx = _lib.Context(device)
+    for name, value in (tuning or {}).items():
+        ctx.tune(name, value)
     icp = pcl.ICP(ctx)
     icp.setParams(_lib.IcpParams(**params_dict))
 
@@ -161,14 +163,14 @@ def _hip_compute(device, params_dict):
     return ctx.name(), run
 
 
-def _farm_worker(device, params_dict, backend, conn):
+def _farm_worker(device, params_dict, tuning, backend, conn):
     """Persistent worker: create the backend once, then serve ("run", shm name, layout, chunk) requests until
     ("stop",).  Every failure is reported to the parent, never swallowed."""
     shm = None
     try:
         os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] = os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         if backend is None:
-            name, run = _hip_compute(device, params_dict)
+            name, run = _hip_compute(device, params_dict, tuning)
         else:  # test hook: "module:function" -> (name, run) like _hip_compute
             mod, fn = backend.split(":")
             name, run = getattr(importlib.import_module(mod), fn)(device, params_dict)
@@ -221,9 +223,9 @@ class _Worker(object):
 class IcpFarm(object):
     """Farm (source, target, [guesses]) jobs over ``devices`` (default: every visible GPU): job j -> worker
     j mod G.  The worker processes start on the first ``run`` (or ``start()``) and live until ``close()``;
-    use it as a context manager."""
+    use it as a context manager.  ``tuning``: launcher knobs (``Context.tuning``) set in every worker's context."""
 
-    def __init__(self, params, devices=None, chunk=CHUNK, _backend=None):
+    def __init__(self, params, devices=None, chunk=CHUNK, tuning=None, _backend=None):
         from . import _lib
         self.params = params
         if devices is None:
@@ -232,6 +234,9 @@ class IcpFarm(object):
             raise _lib.SonarFEError("IcpFarm: no HIP device visible; there is no CPU fallback")
         self.devices = list(devices)
         self.chunk = int(chunk)
+        self.tuning = dict(tuning or {})
+        if self.tuning and _backend is not None:
+            raise ValueError("IcpFarm: tuning applies to the HIP backend only")
         self._backend = _backend
         self._workers = []
         self._seq = 0           # request number, echoed by the worker: a stale reply can never answer a newer request
@@ -242,7 +247,7 @@ class IcpFarm(object):
         ctxm = mp.get_context("spawn")      # a HIP context does not survive fork()
         for dev in self.devices:
             parent, child = ctxm.Pipe()
-            p = ctxm.Process(target=_farm_worker, args=(dev, self.params.as_dict(), self._backend, child), daemon=True)
+            p = ctxm.Process(target=_farm_worker, args=(dev, self.params.as_dict(), self.tuning, self._backend, child), daemon=True)
             p.start()
             child.close()
             self._workers.append(_Worker(p, parent, dev))

@@ -7,7 +7,6 @@ kernels on the context's stream (no host round trip between the stages) and ``re
 downloads the small per-job outputs.  This is the unit bench.py times and the farm shards.
 """
 import ctypes as _C
-import os
 
 import numpy as np
 
@@ -43,8 +42,6 @@ class KeyframeBatch(object):
         if self.bit_masks and self.cols % 32:
             raise ValueError("bit_masks needs polar_cols % 32 == 0")
         self.wpf = (self.rows * self.cols + 31) // 32 + 1      # SFE_BITS_WORDS
-        if staged is None and os.environ.get("SONARFE_STAGED") == "0":     # A/B inside one GPU call (tools/ab_stage.sh)
-            staged = False
         self.staged = (self.bit_masks and self.cap <= 65536) if staged is None else bool(staged)
         if self.staged and not (self.bit_masks and self.cap <= 65536):
             raise ValueError("staged needs bit masks and max_points <= 65536")

@@ -12,14 +12,13 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(autouse=True, params=["default", "entries8"])
-def extraction_build(request, monkeypatch):
+def extraction_build(request, ctx):
     """Every test of this module runs twice: with the 4-byte inverse-map entries of round 4 (default) and with round 3's
     8-byte entries, which stay as the fallback for geometries whose candidates span more than 127 canvas rows or columns
-    (DESIGN 5.2).  The knob is read per call (extract_dev).  (The fused kernel, the second-level flags and round 2's
+    (DESIGN 5.2).  The knob is the context's tuning extract_compact (sfe_tune).  (The fused kernel, the second-level flags and round 2's
     row-block kernel ran here until round 5: measured slower, removed, profiles/r05_pruned_variants.txt.)"""
-    if request.param == "entries8":
-        monkeypatch.setenv("SFE_EXTRACT_NO_COMPACT", "1")
-    return request.param
+    with ctx.tuning(**({"extract_compact": 0} if request.param == "entries8" else {})):
+        yield request.param
 
 
 def _geom(ctx, beams, ranges, res):
@@ -149,9 +148,9 @@ def test_resident_cloud_filters_equal_the_per_cloud_api_and_the_oracle(ctx, ship
 
 
 @pytest.mark.parametrize("points64", [False, True])
-def test_staged_hand_over_with_frames_that_leave_the_record_path(ctx, shipped_cfar, points64, monkeypatch):
+def test_staged_hand_over_with_frames_that_leave_the_record_path(ctx, shipped_cfar, points64):
     """The staged extraction when frames do not fit the record path's per-frame capacities (forced here by shrinking them:
-    SFE_EXTRACT_REC_CAP / SFE_EXTRACT_CAPW are read per call): those frames go through the canvas kernels, land as float64
+    tuning extract_rec_cap / extract_capw): those frames go through the canvas kernels, land as float64
     and are cast by extract_stage_fallback_kernel; the others are staged by the merge kernel itself.  Same clouds as the
     unstaged path and the oracle either way, and points(j) is the float64 cloud in both modes."""
     import oracle
@@ -174,29 +173,26 @@ def test_staged_hand_over_with_frames_that_leave_the_record_path(ctx, shipped_cf
     want_cl = [ref.cloud(j) for j in range(len(frames))]
     ref.free()
     n_rec = sorted(len(p) for p in want_pts)
-    for env in ({}, {"SFE_EXTRACT_REC_CAP": "1500"}, {"SFE_EXTRACT_CAPW": "200"}, {"SFE_EXTRACT_REC_CAP": "1"}):
-        for k in ("SFE_EXTRACT_REC_CAP", "SFE_EXTRACT_CAPW"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        kb = KeyframeBatch(ctx, fe.geometry, (th, gh, tau), "SOCA", 65, None, len(frames), max_points=16384, staged=True,
-                           points64=points64)
-        kb.upload_frames(frames)
-        kb.run_cfar()
-        kb.run_extract()
-        kb.run_filter(0.5, 1.0, 5)
-        ctx.sync()
-        for j in range(len(frames)):
-            assert np.array_equal(kb.cloud(j), want_cl[j]), (env, j)
-            assert np.array_equal(kb.points(j), want_pts[j]), (env, j)
-            o = oracle.remove_outlier(oracle.downsample(want_pts[j].astype(np.float32), 0.5), 1.0, 5) if len(want_pts[j]) else want_cl[j]
-            assert np.array_equal(kb.cloud(j), np.asarray(o, np.float32).reshape(-1, 2)), (env, j)
-        kb.run_filter(0.25, 0.6, 3)                  # the staged clouds serve a second filter call
-        ctx.sync()
-        for j in (1, 3):
-            o = oracle.remove_outlier(oracle.downsample(want_pts[j].astype(np.float32), 0.25), 0.6, 3)
-            assert np.array_equal(kb.cloud(j), o), (env, j)
-        kb.free()
+    for env in ({}, {"extract_rec_cap": 1500}, {"extract_capw": 200}, {"extract_rec_cap": 1}):
+        with ctx.tuning(**env):
+            kb = KeyframeBatch(ctx, fe.geometry, (th, gh, tau), "SOCA", 65, None, len(frames), max_points=16384, staged=True,
+                               points64=points64)
+            kb.upload_frames(frames)
+            kb.run_cfar()
+            kb.run_extract()
+            kb.run_filter(0.5, 1.0, 5)
+            ctx.sync()
+            for j in range(len(frames)):
+                assert np.array_equal(kb.cloud(j), want_cl[j]), (env, j)
+                assert np.array_equal(kb.points(j), want_pts[j]), (env, j)
+                o = oracle.remove_outlier(oracle.downsample(want_pts[j].astype(np.float32), 0.5), 1.0, 5) if len(want_pts[j]) else want_cl[j]
+                assert np.array_equal(kb.cloud(j), np.asarray(o, np.float32).reshape(-1, 2)), (env, j)
+            kb.run_filter(0.25, 0.6, 3)                  # the staged clouds serve a second filter call
+            ctx.sync()
+            for j in (1, 3):
+                o = oracle.remove_outlier(oracle.downsample(want_pts[j].astype(np.float32), 0.25), 0.6, 3)
+                assert np.array_equal(kb.cloud(j), o), (env, j)
+            kb.free()
     assert n_rec[0] == 0 and n_rec[-1] > 3000
 
 
@@ -359,8 +355,8 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
 
     def batch(idx, cap, variant=0, env=None):
         kb = KeyframeBatch(ctx, fe.geometry, (th, gh, tau), "SOCA", 65, None, len(idx), max_points=cap, bit_masks=True)
+        restore = [(k, ctx.tune(k, v)) for k, v in (env or {}).items()]
         try:
-            os.environ.update(env or {})
             ctx._check(ctx.lib.sfe_extract_set_tuning(ctx.handle, variant))
             kb.upload_frames(frames[idx])
             kb.run_cfar()
@@ -372,8 +368,8 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
                 if counts[k] <= cap:
                     assert np.array_equal(kb.points(k), oracle.px_to_m(want[j], fe.rows, fe.cols, fe.width, fe.height)), j
         finally:
-            for key in env or {}:
-                del os.environ[key]
+            for k, v in restore:
+                ctx.tune(k, v)
             ctx._check(ctx.lib.sfe_extract_set_tuning(ctx.handle, 0))
             kb.free()
 
@@ -388,10 +384,10 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
     # round 5: the record path (no canvas for the frames that fit) hands frames back to the canvas kernels when they exceed its
     # capacities -- the record list, the compact word array -- frame by frame inside one batch; and the canvas path alone
     words = sorted(len(np.unique(w[:, 0] * 4096 + w[:, 1] // 64)) for w in want)
-    batch(list(range(6)), big, env={"SFE_EXTRACT_CAPW": str((words[2] + words[3]) // 2)})    # half of the frames handed back
+    batch(list(range(6)), big, env={"extract_capw": (words[2] + words[3]) // 2})    # half of the frames handed back
     batch([3, 2, 1], big)
-    batch(list(range(6)), big, env={"SFE_EXTRACT_REC_CAP": "64"})                             # every frame handed back
-    batch(list(range(6)), small, env={"SFE_EXTRACT_CAPW": str(words[4] + 1)})                 # both kinds of overflow
+    batch(list(range(6)), big, env={"extract_rec_cap": 64})                                   # every frame handed back
+    batch(list(range(6)), small, env={"extract_capw": words[4] + 1})                      # both kinds of overflow
     batch([0, 5, 2], big, variant=2)    # the canvas path for every frame
     batch([5, 0], big)
 

@@ -17,18 +17,22 @@ TOL_TIGHT = 1e-6
 TOL_REF = 1e-4
 
 
+ONE_SIZE = dict(sw_tiers=0, sw_multi=0, sw_tiny=0)
+
+
 @pytest.fixture(autouse=True, params=["tiers", "one-size"])
-def job_tiers(request, monkeypatch):
+def job_tiers(request, ctx):
     """Every test of this module runs twice: with the launcher's job classes (the exhaustive one-wave kernel for clouds
     of a few hundred points, one-wave / four-wave workgroups of the strip sweep up to ~2000 points, 1024 threads beyond;
     large many-to-one jobs split over several workgroups) and with every job on the 1024-thread sweep kernels, unsplit
-    (what round 2 shipped).  The knobs are read
-    per call (sfe_icp_sweep_launch)."""
-    if request.param == "one-size":
-        monkeypatch.setenv("SFE_SW_TIERS", "0")
-        monkeypatch.setenv("SFE_SW_MULTI", "0")
-        monkeypatch.setenv("SFE_SW_TINY", "0")
-    return request.param
+    (what round 2 shipped).  The knobs are the context's tuning (sfe_tune); the farm tests hand them to their workers
+    (_farm_tuning)."""
+    with ctx.tuning(**(ONE_SIZE if request.param == "one-size" else {})):
+        yield request.param
+
+
+def _farm_tuning(job_tiers):
+    return ONE_SIZE if job_tiers == "one-size" else None
 
 
 def _pose_diff(Ta, Tb):
@@ -313,7 +317,7 @@ def test_hires_many_to_one_batch_sweep_equals_brute_force(ctx, job_tiers):
 
 
 @pytest.mark.parametrize("shares", [0, 2, 3, 16])
-def test_split_job_takes_the_decisions_of_the_unsplit_one(ctx, monkeypatch, shares):
+def test_split_job_takes_the_decisions_of_the_unsplit_one(ctx, shares):
     """A job shared by several workgroups (sfe_icp_sweep.hip, MULTI): 30-iteration chains of both minimisers and the
     shipped chain with its differential stop, 3 guesses on one 20 000 x 12 000 pair; any number of shares (0 = the
     launcher's choice) must reproduce status and iteration count of the unsplit run and its pose to 1e-6.  The source
@@ -326,33 +330,28 @@ def test_split_job_takes_the_decisions_of_the_unsplit_one(ctx, monkeypatch, shar
                for dx, dy, dt in rng.normal(0, [0.3, 0.3, 0.05], (3, 3))]
     for over in (dict(minimizer=1, max_iter=30, use_diff_checker=0), dict(minimizer=0, max_iter=30, use_diff_checker=0), {}):
         p = icp_config.shipped_params(**over)
-        monkeypatch.setenv("SFE_SW_MULTI", "0")
-        ref = _icp(p, ctx).compute_batch(src, tgt, guesses)
-        monkeypatch.setenv("SFE_SW_MULTI", "1")
-        monkeypatch.setenv("SFE_SW_TIERS", "1")
-        if shares:
-            monkeypatch.setenv("SFE_SW_MULTI_G", str(shares))
-        got = _icp(p, ctx).compute_batch(src, tgt, guesses)
+        with ctx.tuning(sw_multi=0):
+            ref = _icp(p, ctx).compute_batch(src, tgt, guesses)
+        with ctx.tuning(sw_multi=1, sw_tiers=1, sw_multi_g=shares):
+            got = _icp(p, ctx).compute_batch(src, tgt, guesses)
         assert got[0] == ref[0] and all(m == "success" for m in got[0]), (over, got[0])
         assert np.array_equal(got[2], ref[2]), (over, got[2], ref[2])
         assert max(_pose_diff(x, y) for x, y in zip(got[1], ref[1])) < TOL_TIGHT
 
 
-def test_split_job_with_empty_shares(ctx, monkeypatch):
+def test_split_job_with_empty_shares(ctx):
     """all queries in two thin bands of strips: most of the 16 shares get no query at all and still take part in
     every exchange"""
     src, tgt, guess, _ = synth.scan_pair(seed=42, n_src=9000, n_tgt=9000)
     big_t = np.concatenate([tgt, tgt + np.float32(0.013)]).astype(np.float32)
     keep = (np.abs(src[:, 1] - np.median(src[:, 1])) < 0.4) | (src[:, 1] > np.quantile(src[:, 1], 0.97))
     band = np.concatenate([src[keep]] * 6)[:8800].astype(np.float32)
-    monkeypatch.setenv("SFE_SW_MULTI_MIN_SRC", "4096")
-    monkeypatch.setenv("SFE_SW_MULTI_SHARE_MIN", "64")
     p = icp_config.shipped_params(minimizer=1, max_iter=10, use_diff_checker=0)
-    monkeypatch.setenv("SFE_SW_MULTI", "0")
-    ref = _icp(p, ctx).compute_batch(band, big_t, [guess])
-    monkeypatch.setenv("SFE_SW_MULTI", "1")
-    monkeypatch.setenv("SFE_SW_TIERS", "1")
-    got = _icp(p, ctx).compute_batch(band, big_t, [guess])
+    with ctx.tuning(sw_multi_min_src=4096, sw_multi_share_min=64):
+        with ctx.tuning(sw_multi=0):
+            ref = _icp(p, ctx).compute_batch(band, big_t, [guess])
+        with ctx.tuning(sw_multi=1, sw_tiers=1):
+            got = _icp(p, ctx).compute_batch(band, big_t, [guess])
     assert got[0] == ref[0] and np.array_equal(got[2], ref[2])
     assert _pose_diff(got[1][0], ref[1][0]) < TOL_TIGHT
 
@@ -494,7 +493,7 @@ def _sweep_vs_brute(ctx, p, src, tgt, guesses):
     return same, a, b
 
 
-def test_sweep_iteration_cache_at_the_maxdist_boundary(ctx, monkeypatch):
+def test_sweep_iteration_cache_at_the_maxdist_boundary(ctx):
     """From the second iteration on the sweep reuses what the previous iteration knew: the old
     neighbour as a witness, and for queries without any target within maxDist a clearance that
     proves "still none" while the query has moved less than it.  Source points are placed in a thin
@@ -521,9 +520,9 @@ def test_sweep_iteration_cache_at_the_maxdist_boundary(ctx, monkeypatch):
             p = IcpParams(matcher_max_dist=md, use_max_dist_filter=1, max_dist_filter=1.0, use_trimmed_filter=1,
                           trim_ratio=0.7, minimizer=mz, max_iter=25, use_diff_checker=0, min_diff_rot=0.001,
                           min_diff_trans=0.01, smooth_len=3, normals_knn=10)
-            for cache in ("1", "0"):
-                monkeypatch.setenv("SFE_SW_CACHE", cache)
-                same, x, y = _sweep_vs_brute(ctx, p, src, tgt, guesses)
+            for cache in (1, 0):
+                with ctx.tuning(sw_cache=cache):
+                    same, x, y = _sweep_vs_brute(ctx, p, src, tgt, guesses)
                 assert same, (md, mz, cache, x[0], y[0], x[2], y[2])
                 assert all(m == "success" for m in x[0]) and (x[2] == 25).all()
             st, To, ito = oracle.icp(src, tgt, guesses[0], oracle.shipped_icp_params(
@@ -600,7 +599,7 @@ def test_side_stream_preparation_returns_the_same_results(ctx):
         kb.free()
 
 
-def test_compute_pairs_and_the_farm_equal_single_calls(ctx):
+def test_compute_pairs_and_the_farm_equal_single_calls(ctx, job_tiers):
     """ICP.compute_pairs (many independent pairs per launch) and farm.IcpFarm (one worker process per
     device, chunks of pairs per launch) return what one ICP.compute per pair returns"""
     from sonar_slam_amd.farm import IcpFarm
@@ -612,7 +611,7 @@ def test_compute_pairs_and_the_farm_equal_single_calls(ctx):
     for (m1, T1), m2, T2 in zip(single, msgs, T):
         assert m1 == m2 and np.array_equal(T1, T2)
     jobs = [(s, t, [g, g @ synth.pose_matrix(0.1, 0.0, 0.01).astype(np.float32)]) for s, t, g, _ in pairs[:4]]
-    out = IcpFarm(p, devices=[ctx.device]).run(jobs)
+    out = IcpFarm(p, devices=[ctx.device], tuning=_farm_tuning(job_tiers)).run(jobs)
     assert len(out) == 4
     for (s, t, gs), (m, Tf, itf) in zip(jobs, out):
         mb, Tb, itb = icp.compute_batch(s, t, gs)
@@ -669,7 +668,7 @@ def test_knn_density_and_max_density_filter():
 
 
 @pytest.mark.parametrize("mz", [0, 1])
-def test_clearance_records_over_long_chains_equal_brute_force(ctx, mz, monkeypatch):
+def test_clearance_records_over_long_chains_equal_brute_force(ctx, mz):
     """Chains with a fixed count of >= 12 iterations run the build with clearance records (a converged query whose old
     neighbour is provably still the nearest is not searched again).  70 iterations: past convergence (every query
     settled by its record), past the 64 iterations the records can number, with duplicated targets (ties never get a
@@ -686,8 +685,8 @@ def test_clearance_records_over_long_chains_equal_brute_force(ctx, mz, monkeypat
     same, a, b = _sweep_vs_brute(ctx, p, src, tgt, guesses)
     assert same, (a[0], b[0], a[2], b[2])
     assert list(a[2]) == [70] * len(guesses)
-    monkeypatch.setenv("SFE_SW_REC", "0")
-    off = _with_variant(ctx, 0, lambda: _icp(p, ctx).compute_batch(src, tgt, guesses))
+    with ctx.tuning(sw_rec=0):
+        off = _with_variant(ctx, 0, lambda: _icp(p, ctx).compute_batch(src, tgt, guesses))
     assert off[0] == a[0] and np.array_equal(off[1], a[1]) and np.array_equal(off[2], a[2])
 
 
@@ -731,7 +730,7 @@ def test_clearance_records_far_from_the_origin(ctx, offset):
             assert _pose_diff(T, To) <= tol, (offset, mz, _pose_diff(T, To))
 
 
-def test_two_real_farm_workers_on_one_device(ctx):
+def test_two_real_farm_workers_on_one_device(ctx, job_tiers):
     """IcpFarm with two REAL HIP worker processes (two contexts on the one GPU, devices=[0, 0]): two
     batches on the same workers, a bad job between them (ADVICE r2's scenario: nothing may stay in flight), results
     equal to single calls in this process."""
@@ -743,7 +742,7 @@ def test_two_real_farm_workers_on_one_device(ctx):
     def jobs_of(sel):
         return [(pairs[i][0], pairs[i][1], [pairs[i][2], pairs[i][2] @ synth.pose_matrix(0.08, 0.0, 0.01).astype(np.float32)])
                 for i in sel]
-    with IcpFarm(p, devices=[ctx.device, ctx.device], chunk=3) as f:
+    with IcpFarm(p, devices=[ctx.device, ctx.device], chunk=3, tuning=_farm_tuning(job_tiers)) as f:
         pids = None
         for sel in (range(5), range(9)):
             jobs = jobs_of(sel)
@@ -762,7 +761,7 @@ def test_two_real_farm_workers_on_one_device(ctx):
                     f.run(bad)
 
 
-def test_four_real_farm_workers_on_one_device(ctx):
+def test_four_real_farm_workers_on_one_device(ctx, job_tiers):
     """The farm with several REAL HIP workers: four worker processes, four contexts on this box's one
     GPU (devices=[0] * 4), fewer jobs than workers and more; results equal to single calls here.  Four, not the target
     node's eight: with this process, at most five processes hold the shared device (the dealing to eight workers is
@@ -771,7 +770,7 @@ def test_four_real_farm_workers_on_one_device(ctx):
     p = icp_config.shipped_params()
     pairs = [synth.scan_pair(seed=500 + i, n_src=260 + 31 * i, n_tgt=300 + 17 * i) for i in range(6)]
     icp = _icp(p, ctx)
-    with IcpFarm(p, devices=[ctx.device] * 4, chunk=4) as f:
+    with IcpFarm(p, devices=[ctx.device] * 4, chunk=4, tuning=_farm_tuning(job_tiers)) as f:
         assert len(f._workers) == 4 and len(set(w.proc.pid for w in f._workers)) == 4
         for n in (3, 19):
             jobs = [(pairs[j % 6][0], pairs[j % 6][1], [pairs[j % 6][2]]) for j in range(n)]

@@ -114,6 +114,17 @@ def test_product_never_imports_the_oracle():
                 assert not re.search(r'#include\s+"[^"]*oracle', txt), f  # never compiled in
 
 
+def test_product_reads_no_tuning_from_the_environment():
+    """Kernel choices are per-context tuning (sfe_tune / Context.tuning): a stray environment variable must not change
+    what the library or the package runs."""
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "sonar_slam_amd")):
+        for f in files:
+            txt = open(os.path.join(dirpath, f)).read() if f.endswith((".py", ".hip", ".h", ".cpp")) else ""
+            if f.endswith((".hip", ".h", ".cpp")):
+                assert not re.search(r"\bgetenv\s*\(", txt), f
+            assert not re.search(r"""(environ|getenv)[^\n]{0,12}["'](SFE_|SONARFE_STAGED)""", txt), f
+
+
 def test_shard_and_scatter_back():
     for n, w in [(10, 3), (7, 8), (0, 2), (16, 4)]:
         shards = [farm.shard(n, r, w) for r in range(w)]

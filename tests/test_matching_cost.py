@@ -113,11 +113,8 @@ def test_gpu_many_poses_per_launch_equal_the_oracle_and_the_small_kernel(ctx):
             T6 = np.array([np.asarray(tp.between(sp.compose(mc.Pose2(*x))).matrix()).astype(np.float32)[:2].reshape(-1) for x in X])
             want = oracle.matching_cost(grid, src, T6, geo["xmin"], geo["ymin"], 0.05, f64_points=f64)
             got = sub.batch(X)
-            os.environ["SFE_COST_NO_MANY"] = "1"
-            try:
+            with ctx.tuning(cost_many=0):
                 small = sub.batch(X)
-            finally:
-                del os.environ["SFE_COST_NO_MANY"]
             assert np.array_equal(got, want) and np.array_equal(small, want) and (want < -200).any(), (f64, P)
         sub.grid.close()
     # ties: resolution 2^-4, the source points on k + 0.5 cells of the target's grid, the identity as one of the poses

@@ -58,13 +58,10 @@ def main():
                       flush=True)
                 if alg == "OS" and not want_thr:
                     # cfar.os() of the drop-in has NO gate (and feature.yaml's threshold can be low): the pre-filtered candidate
-                    # kernel of round 6 against the sliding histogram of rounds 2-5 (SFE_CFAR_NO_OS_PREF=1), same launch
+                    # kernel of round 6 against the sliding histogram of rounds 2-5 (tuning cfar_os_pref = 0), same launch
                     for gate in (-1, 20):
                         for pref in (True, False):
-                            if pref:
-                                os.environ.pop("SFE_CFAR_NO_OS_PREF", None)
-                            else:
-                                os.environ["SFE_CFAR_NO_OS_PREF"] = "1"
+                            ctx.tune("cfar_os_pref", 1 if pref else 0)
 
                             def launch_g():
                                 ctx._check(ctx.lib.sfe_cfar_u8_batch_dev(ctx.handle, d_in.ptr, a.frames, rows, cols, _lib.ALG[alg], th, gh,
@@ -74,7 +71,7 @@ def main():
                             print("%-10s %-5s %-8s %9.3f %9.0f %6.1f%%   %s" % (
                                 w, alg, "gate %d" % gate, ms, gb, gb / 80.0,
                                 "pre-filtered candidates (cfar_u8_os_gated<PREF>)" if pref else "sliding histogram (cfar_u8_os)"), flush=True)
-                    os.environ.pop("SFE_CFAR_NO_OS_PREF", None)
+                    ctx.tune("cfar_os_pref", 1)
 
 
 if __name__ == "__main__":

@@ -35,11 +35,11 @@ def bit_stream_batch(ctx, rng, fe, ranges, beams):
     cap = int(rng.choice([max(sizes[-1], 1) + 3, max(sizes[len(sizes) // 2], 1), 1 + sizes[-1] // 3 + 5]))
     env = {}
     if rng.random() < 0.5:
-        env = {str(rng.choice(["SFE_EXTRACT_CAPW", "SFE_EXTRACT_REC_CAP"])): str(int(rng.choice([1, 7, 60, 300, 1500])))}
+        env = {str(rng.choice(["extract_capw", "extract_rec_cap"])): int(rng.choice([1, 7, 60, 300, 1500]))}
     d_bits, d_pts, d_cnt = ctx.alloc(bits.nbytes), ctx.alloc(nf * cap * 16), ctx.alloc(nf * 4)
     bad = 0
+    restore = [(k, ctx.tune(k, v)) for k, v in env.items()]
     try:
-        os.environ.update(env)
         d_bits.upload(bits)
         ctx._check(ctx.lib.sfe_extract_points_bits_batch_dev(ctx.handle, fe.geometry.handle, d_bits.ptr, nf, cap, d_pts.ptr, d_cnt.ptr))
         ctx.sync()
@@ -53,8 +53,8 @@ def bit_stream_batch(ctx, rng, fe, ranges, beams):
                 print("MISMATCH bit stream: beams %d ranges %d frame %d of %d, %d points, cap %d, env %r"
                       % (beams, ranges, f, nf, len(want[f]), cap, env), flush=True)
     finally:
-        for key in env:
-            del os.environ[key]
+        for k, v in restore:
+            ctx.tune(k, v)
         for b in (d_bits, d_pts, d_cnt):
             b.free()
     return nf, bad

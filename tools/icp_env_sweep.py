@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""One-knob-at-a-time sweep of the ICP launcher's environment knobs (read per call: DESIGN appendix in LAB_NOTEBOOK.md) on the
+"""One-knob-at-a-time sweep of the ICP launcher's tuning knobs (sfe_tune: Appendix A of LAB_NOTEBOOK.md) on the
 bench's 4096 scan pairs, 30-iteration point-to-plane chain: ms per launch (loop + preparation), the default measured again
 between the groups.  Every setting returns identical results; this only re-checks the tuning after a kernel change.
 usage: python tools/icp_env_sweep.py [NAME=v1,v2,... ...]"""
@@ -14,8 +14,8 @@ from sonar_slam_amd.feature_extraction import FeatureExtraction, SonarPing, ocul
 from sonar_slam_amd.pipeline import KeyframeBatch  # noqa: E402
 
 B = int(os.environ.get("SWEEP_BATCH", "4096"))
-groups = sys.argv[1:] or ["SFE_SW_MARGIN=10,25", "SFE_SW_RECM=6,12", "SFE_SW_RECK=2,4", "SFE_SW_BUDGET_A=4,8", "SFE_SW_RTRIPS=3,6",
-                          "SFE_SW_BUDGET=64,256", "SFE_SW_UNION_MAX=512,1024", "SFE_SW_UNION_ITERS=0,2", "SFE_SW_STRIP_PTS=64,128"]
+groups = sys.argv[1:] or ["sw_margin=10,25", "sw_recm=6,12", "sw_reck=2,4", "sw_budget_a=4,8", "sw_rtrips=3,6",
+                          "sw_budget=64,256", "sw_union_max=512,1024", "sw_union_iters=0,2", "sw_strip_pts=64,128"]
 ctx = _lib.default_context()
 det = CFAR(40, 10, 0.1, 10)
 fe = FeatureExtraction(ctx)
@@ -43,7 +43,6 @@ print("default                    %.3f ms" % timed(), flush=True)
 for g in groups:
     name, vals = g.split("=")
     for v in vals.split(","):
-        os.environ[name] = v
-        print("%-18s %-7s %.3f ms" % (name, v, timed()), flush=True)
-    del os.environ[name]
+        with ctx.tuning(**{name: float(v)}):
+            print("%-18s %-7s %.3f ms" % (name, v, timed()), flush=True)
     print("default                    %.3f ms" % timed(), flush=True)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Sweep the search budgets of the ICP loop kernel (env SFE_SW_BUDGET_A / SFE_SW_BUDGET / SFE_SW_RTRIPS) on the bench
+"""Sweep the search budgets of the ICP loop kernel (tuning sw_budget_a / sw_budget / sw_rtrips) on the bench
 scan pairs: `python tools/icp_knobs.py 6,128,4 6,256,4 ...` (first pass trips, second pass budget, trips per round)."""
 import ctypes
 import os
@@ -43,9 +43,9 @@ if len(sys.argv) > 1:  # e.g. "4,24 6,24 8,40"
 for combo in combos:
     refill, budget = combo[:2]
     rtrips = combo[2] if len(combo) > 2 else 4
-    os.environ["SFE_SW_BUDGET_A"] = str(refill)
-    os.environ["SFE_SW_BUDGET"] = str(budget)
-    os.environ["SFE_SW_RTRIPS"] = str(rtrips)
+    ctx.tune("sw_budget_a", refill)
+    ctx.tune("sw_budget", budget)
+    ctx.tune("sw_rtrips", rtrips)
     line = "budget A %2d B %3d R %d:" % (refill, budget, rtrips)
     for mode, kb in kbs.items():
         ms = timed(kb.run_icp, 3)

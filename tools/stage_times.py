@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Per-stage HIP-event timing of the keyframe pipeline (CFAR / extract / ICP) for quick A/B."""
+"""Per-stage HIP-event timing of the keyframe pipeline (CFAR / extract / ICP) for quick A/B.
+usage: python tools/stage_times.py [--unstaged] [--tune NAME=VALUE ...]   (tuning names: sfe_tune, LAB_NOTEBOOK Appendix A)"""
 import argparse
 import os
 import sys
@@ -21,8 +22,13 @@ def main():
     ap.add_argument("--p2plane-only", action="store_true", help="skip the shipped chain (counter passes)")
     ap.add_argument("--max-iter", type=int, default=30, help="iterations of the forced point-to-plane chain")
     ap.add_argument("--max-points", type=int, default=32768, help="point capacity per frame (the bench's)")
+    ap.add_argument("--unstaged", action="store_true", help="extraction -> filters through float64 points (KeyframeBatch staged=False)")
+    ap.add_argument("--tune", action="append", default=[], metavar="NAME=VALUE", help="launcher knob of the context (repeatable)")
     a = ap.parse_args()
     ctx = _lib.default_context()
+    for kv in a.tune:
+        name, value = kv.split("=")
+        ctx.tune(name, float(value))
     det = CFAR(40, 10, 0.1, 10)
     fe = FeatureExtraction(ctx)
     fe.Ntc, fe.Ngc, fe.Pfa, fe.rank, fe.alg, fe.threshold = 40, 10, 0.1, 10, "SOCA", 65
@@ -41,7 +47,8 @@ def main():
                     ("reference", icp_config.shipped_params())):
         if a.p2plane_only and mode != "p2plane30":
             continue
-        kb = KeyframeBatch(ctx, fe.geometry, det.params["SOCA"], "SOCA", 65, p, a.batch, max_points=a.max_points)
+        kb = KeyframeBatch(ctx, fe.geometry, det.params["SOCA"], "SOCA", 65, p, a.batch, max_points=a.max_points,
+                           staged=False if a.unstaged else None)
         kb.upload_frames(frames)
         kb.upload_scan_pairs(srcs, tgts, guesses)
         if mode == "p2plane30":
