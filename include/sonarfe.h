@@ -285,6 +285,17 @@ int sfe_icp_set_tuning(sfe_ctx *ctx, int variant);
  * handed to the cooperative tier, [11] queries handed to the second pass, [12] cooperative trips.
  * [16 + 2i], [17 + 2i]: search cycles and (cap bits << 32 | exact matches) of iteration i < 32. */
 int sfe_icp_get_profile(sfe_ctx *ctx, int enable, long long *cycles16);
+/* test hook: the kernel the launcher gave each job of the last ICP call on this context, and the CU count its tier
+ * rules used.  route may be NULL with n_jobs == 0 (just n_cu); SFE_ERR_ARG if n_jobs differs from that call's job count. */
+#define SFE_ICP_ROUTE_TINY 0    /* one wave per job, exhaustive search (clouds of a few hundred points) */
+#define SFE_ICP_ROUTE_T0 1      /* strip sweep, one-wave workgroups (many small jobs in the call) */
+#define SFE_ICP_ROUTE_T1 2      /* strip sweep, four-wave workgroups */
+#define SFE_ICP_ROUTE_Q 3       /* strip sweep, 1024 threads, target and per-query results in LDS */
+#define SFE_ICP_ROUTE_LDS 4     /* ... target in LDS, per-query results in HBM scratch */
+#define SFE_ICP_ROUTE_GLB 5     /* ... target in HBM scratch */
+#define SFE_ICP_ROUTE_SPLIT 6   /* ... the job shared by several workgroups */
+#define SFE_ICP_ROUTE_BRUTE 7   /* brute-force tile scan (sfe_icp_set_tuning bit 2) */
+int sfe_icp_last_routes(sfe_ctx *ctx, int32_t *route, int n_jobs, int32_t *n_cu);
 /* independent jobs, device-resident: clouds concatenated, job j uses
  * src[src_off[j]..src_off[j+1]) and tgt[tgt_off[j]..tgt_off[j+1]) (offsets in points, host
  * arrays of n_jobs+1), guess d_guess9 + 9*j; outputs d_T9 (9 floats), d_status, d_iters per job */

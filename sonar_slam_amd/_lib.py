@@ -17,6 +17,16 @@ LIB_PATH = os.environ.get("SONARFE_LIB") or os.path.join(_HERE, "libsonarfe.so")
 
 SFE_ERR_CAP = -4
 
+# the kernel the ICP launcher gave a job (SFE_ICP_ROUTE_* in include/sonarfe.h; Context.icp_routes)
+ICP_ROUTE_TINY = 0    # one wave per job, exhaustive search
+ICP_ROUTE_T0 = 1      # strip sweep, one-wave workgroups
+ICP_ROUTE_T1 = 2      # strip sweep, four-wave workgroups
+ICP_ROUTE_Q = 3       # strip sweep, 1024 threads, target and per-query results in LDS
+ICP_ROUTE_LDS = 4     # ... target in LDS, per-query results in HBM scratch
+ICP_ROUTE_GLB = 5     # ... target in HBM scratch
+ICP_ROUTE_SPLIT = 6   # ... the job shared by several workgroups
+ICP_ROUTE_BRUTE = 7   # brute-force tile scan (sfe_icp_set_tuning bit 2)
+
 ALG = {"CA": 0, "SOCA": 1, "GOCA": 2, "OS": 3}
 
 ICP_STATUS_MESSAGES = {
@@ -125,6 +135,7 @@ SIGNATURES = {
                                        _f32p, _i32p, _i32p]),
     "sfe_icp_set_tuning": (C.c_int, [_vp, C.c_int]),
     "sfe_icp_get_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
+    "sfe_icp_last_routes": (C.c_int, [_vp, _i32p, C.c_int, _i32p]),
     "sfe_icp_batch_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _vp, _i32p, _vp, C.c_int,
                                     _vp, _vp, _vp]),
     "sfe_icp_jobs_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _vp, _i32p, _vp, C.c_int, _vp, _vp, _vp]),
@@ -284,6 +295,19 @@ class Context(object):
         finally:
             for name, value in reversed(saved):
                 self.tune(name, value)
+
+    @property
+    def n_cu(self):
+        """the CU count the ICP launcher's tier rules use"""
+        n = C.c_int32(0)
+        self._check(self.lib.sfe_icp_last_routes(self.handle, None, 0, C.byref(n)))
+        return n.value
+
+    def icp_routes(self, n):
+        """ICP_ROUTE_* of each of the `n` jobs of the last ICP call on this context (int32 [n])"""
+        out = np.zeros(n, np.int32)
+        self._check(self.lib.sfe_icp_last_routes(self.handle, ptr(out, C.c_int32), int(n), None))
+        return out
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)

@@ -748,6 +748,7 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
         if (rc != 1)
             return rc;
     }
+    ctx->icp_routes.assign((size_t)n_jobs, (int8_t)SFE_ICP_ROUTE_BRUTE);
     IcpJob *d_jobs = (IcpJob *)sfe_scratch(ctx, 4, sizeof(IcpJob) * (size_t)n_jobs);
     float *d_nn_d2 = (float *)sfe_scratch(ctx, 5, sizeof(float) * (size_t)soff);
     int *d_nn_idx = (int *)sfe_scratch(ctx, 6, sizeof(int) * (size_t)soff);

@@ -232,12 +232,17 @@ __device__ __forceinline__ long long sw_uniform_ll(long long v)
     return (long long)(((unsigned long long)hi << 32) | lo);
 }
 
+// The error minimiser's sums are added in the order of a 1024-thread workgroup whatever NT is (sfe_icp_sweep_loop.hip,
+// D): one role per wave of that workgroup, each with its nine fp64 partial sums (the pair count goes through xr)
+#define SW_SUM_ROLES (ICP_THREADS / 64)
+#define SW_SUM_NA 9
+
 // control block of a job; the LDS-resident variant places the sorted target right behind it.  The profile counters
 // and the transform history of the clearance records only take room in the builds that use them (the small-job tiers
 // run many workgroups per CU: every KB of control block is a job less per CU).
 template <int NT, bool PROF, bool REC>
 struct SweepShared {
-    double red[(NT / 64) * 10 + 10 > 16 * 5 ? (NT / 64) * 10 + 10 : 16 * 5]; // (16 x 5: the canonical order of the sums, below)
+    double red[SW_SUM_ROLES * SW_SUM_NA]; // the partial sums of every role, role-major (the canonical order of the sums)
     double acc[10];  // the reduced error-minimiser sums (read by the solving lane)
     unsigned hist[256], hist0[256];
     unsigned sel_prefix, sel_k;

@@ -96,6 +96,8 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     constexpr size_t ctl_q = sweep_ctl_bytes<ICP_THREADS, false, true>(); // (the largest control block of the LDS_Q builds)
     int q_tmax = 0, q_smax = 0, t0_tmax = 0, t0_smax = 0, t1_tmax = 0, t1_smax = 0, tiny_tmax = 0, tiny_smax = 0;
     int n_sync = 0;
+    ctx->icp_routes.resize((size_t)n_jobs); // the class of every job, for sfe_icp_last_routes
+    int8_t *route = ctx->icp_routes.data();
     for (int j = 0; j < n_jobs; ++j) {
         const int32_t *q = jobs4 + 4 * (size_t)j;
         const auto key = std::make_pair((int)q[2], (int)q[3]);
@@ -139,16 +141,20 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
             for (int g = 0; g < shares; ++g)
                 ids_multi.push_back(rec0 + g);
             ++n_sync;
+            route[j] = SFE_ICP_ROUTE_SPLIT;
         } else if (tiny) {
             ids_tiny.push_back(rec0);
+            route[j] = SFE_ICP_ROUTE_TINY;
             tiny_tmax = std::max(tiny_tmax, (int)q[3]);
             tiny_smax = std::max(tiny_smax, (int)q[1]);
         } else if (tier == 0) {
             ids_t0.push_back(rec0);
+            route[j] = SFE_ICP_ROUTE_T0;
             t0_tmax = std::max(t0_tmax, (int)q[3]);
             t0_smax = std::max(t0_smax, (int)q[1]);
         } else if (tier == 1) {
             ids_t1.push_back(rec0);
+            route[j] = SFE_ICP_ROUTE_T1;
             t1_tmax = std::max(t1_tmax, (int)q[3]);
             t1_smax = std::max(t1_smax, (int)q[1]);
         } else {
@@ -156,10 +162,12 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
                                 ctl_q + 8 * (size_t)(q[3] + SW_PAD) + 6 * (size_t)q[1] + 16 <= lds_share;
             if (fits_q) {
                 ids_q.push_back(rec0);
+                route[j] = SFE_ICP_ROUTE_Q;
                 q_tmax = std::max(q_tmax, (int)q[3]);
                 q_smax = std::max(q_smax, (int)q[1]);
             } else {
                 (q[3] <= SW_TCAP ? ids_lds : ids_glb).push_back(rec0);
+                route[j] = q[3] <= SW_TCAP ? SFE_ICP_ROUTE_LDS : SFE_ICP_ROUTE_GLB;
             }
         }
     }
@@ -170,6 +178,8 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     int t_cap = q_tmax + SW_PAD, q_cap = (q_smax + 3) & ~3;
     if (!ids_q.empty() && ctl_q + 8 * (size_t)t_cap + 6 * (size_t)q_cap > lds_share) {
         ids_lds.insert(ids_lds.end(), ids_q.begin(), ids_q.end()); // odd mix of shapes: keep the results in HBM
+        for (int r : ids_q)
+            route[jobs[(size_t)r].out] = SFE_ICP_ROUTE_LDS;
         std::sort(ids_lds.begin(), ids_lds.end());
         ids_q.clear();
     }
@@ -468,6 +478,18 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
                                     ctx->stream));
         SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return 0;
+}
+
+extern "C" int sfe_icp_last_routes(sfe_ctx *ctx, int32_t *route, int n_jobs, int32_t *n_cu)
+{
+    if (!ctx)
+        return SFE_ERR_ARG;
+    SFE_ARG(ctx, n_jobs >= 0 && (route || n_jobs == 0) && (n_jobs == 0 || n_jobs == (int)ctx->icp_routes.size()));
+    for (int j = 0; j < n_jobs; ++j)
+        route[j] = ctx->icp_routes[(size_t)j];
+    if (n_cu)
+        *n_cu = ctx->n_cu;
     return 0;
 }
 

@@ -65,6 +65,8 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
 {
     static_assert(LDS_TGT || !LDS_Q, "LDS_Q needs the LDS-resident target layout");
     static_assert(!MULTI || !PROF, "the profile build runs whole jobs");
+    // (the predicted quantile of the clearance-record passes counts the workgroup's own queries, with no exchange)
+    static_assert(!MULTI || !REC, "split jobs run without clearance records");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     using Shared = SweepShared<NT, PROF, REC>;
     Shared &S = *reinterpret_cast<Shared *>(smem_raw);
@@ -1450,7 +1452,9 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
         // as the other kernels; tools/icp_soak.py found such jobs at 6 in 100 000 before.)
         {
             asm volatile("; SUMS_BEGIN"); // (markers in the ISA, nothing else: tools/icp_isa.sh cuts the region between them)
-            constexpr int NA = 9;
+            constexpr int NA = SW_SUM_NA;
+            static_assert(sizeof(S.red) / sizeof(S.red[0]) == SW_SUM_ROLES * NA && sizeof(S.xr) / sizeof(S.xr[0]) >= SW_SUM_ROLES,
+                          "one slot per role and sum");
             // kept pair?  (called wave-uniformly; counts the kept pairs of the wave on the way)
             auto kept = [&](int i, bool in, int &id, unsigned &cnt) -> bool {
                 float d = 0.0f;
@@ -1464,7 +1468,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 cnt += (unsigned)__popcll(__ballot(ok));
                 return ok;
             };
-            const int roles = min(16, (ns + 63) >> 6); // (the waves beyond hold no query: their totals are 0.0)
+            const int roles = min(SW_SUM_ROLES, (ns + 63) >> 6); // (the waves beyond hold no query: their totals are 0.0)
             for (int w0 = tid >> 6; w0 < roles; w0 += NT / 64) { // (NT == 1024: every wave plays itself)
                 double a[NA] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
                 unsigned cnt = 0;

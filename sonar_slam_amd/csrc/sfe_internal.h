@@ -92,6 +92,7 @@ struct sfe_ctx {
     int extract_variant = 0;     // 0 = inverse map for binary masks, records instead of a canvas for bit-stream batches (default); 1 = dense pass only; 2 = inverse map through the canvas bitmap always (A/B)
     int icp_prof = 0;            // debug: per-phase cycle counts of workgroup 0 of the sweep kernel
     long long icp_prof_host[SFE_ICP_PROF_N] = {0};
+    std::vector<int8_t> icp_routes; // SFE_ICP_ROUTE_* of every job of the last ICP call (sfe_icp_last_routes)
     int n_cu = 256;
     // clouds left in the staging slots by sfe_extract_points_bits_staged_dev, waiting for sfe_cloud_filter_staged_dev
     // (-1: none; anything else that writes those slots resets it)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
-from sonar_slam_amd import icp_config, pcl, synth
+from sonar_slam_amd import _lib, icp_config, pcl, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -358,8 +358,10 @@ def test_split_job_with_empty_shares(ctx):
 
 def test_small_job_tiers_in_one_batch_equal_brute_force_and_the_oracle(ctx, job_tiers):
     """the job shapes bruce_slam produces (slam.py:769,1032: clouds of 10^2..10^3 points) side by side in one device
-    batch: one-wave, four-wave and 1024-thread workgroups, one launch each; bit-identical to the brute-force kernel,
-    a sample against the oracle"""
+    batch: the tiny kernel, four-wave and 1024-thread workgroups, one launch each; bit-identical to the brute-force
+    kernel, a sample against the oracle.  74 jobs are fewer than 2 x CUs small jobs, so the one-wave sweep tier stays
+    off and the four-wave one only takes jobs of at most 320 source points (test_gpu_icp_tiers runs both tiers at the
+    batch sizes that select them)."""
     from sonar_slam_amd.CFAR import CFAR
     from sonar_slam_amd.feature_extraction import FeatureExtraction, SonarPing, oculus_bearings
     from sonar_slam_amd.pipeline import KeyframeBatch
@@ -379,8 +381,14 @@ def test_small_job_tiers_in_one_batch_equal_brute_force_and_the_oracle(ctx, job_
             kb = KeyframeBatch(ctx, fe.geometry, CFAR(40, 10, 0.1, 10).params["SOCA"], "SOCA", 65, p, len(pairs))
             kb.upload_scan_pairs([q[0] for q in pairs], [q[1] for q in pairs], [q[2] for q in pairs])
             _with_variant(ctx, variant, lambda: (kb.run_icp(), ctx.sync()))
+            if variant == 0:
+                routes = set(ctx.icp_routes(len(pairs)))
             out[variant] = kb.results()
             kb.free()
+        if job_tiers == "tiers":
+            assert {_lib.ICP_ROUTE_TINY, _lib.ICP_ROUTE_T1, _lib.ICP_ROUTE_Q} <= routes, (routes, over)
+        else:
+            assert routes <= {_lib.ICP_ROUTE_Q, _lib.ICP_ROUTE_LDS, _lib.ICP_ROUTE_GLB}, (routes, over)
         for k in ("T", "status", "iters"):
             assert np.array_equal(out[0][k], out[4][k], equal_nan=True), (k, over)
         for j in (0, 7, 41, 50, 64, 66, 70):
@@ -454,12 +462,13 @@ def test_sweep_vs_brute_force_fuzz(ctx):
     assert 0 < n_fail < 200      # the fuzz reaches both the success and the failure paths
 
 
-def test_rank_deficient_jobs_come_out_the_same_from_every_kernel(ctx):
+def test_rank_deficient_jobs_come_out_the_same_from_every_kernel(ctx, job_tiers):
     """A few hundred source points on a target of 2..7 points (duplicates among them): every inlier is matched to one or
     two points, the point-to-point system is rank-deficient, its sums are rounding noise and the closed-form solve amplifies
     them without bound -- the last bit of an fp64 sum decides the pose.  Every build adds the mean and the minimiser's
-    sums in the order of a 1024-thread workgroup, so the one-wave kernels still equal the brute-force kernel bit for bit
-    (tools/icp_soak.py found 7 such batches in 113 000 scan matches before that)."""
+    sums in the order of a 1024-thread workgroup, so the tiny kernel (these jobs with the job tiers on) and the 1024-thread
+    sweep (with them off) still equal the brute-force kernel bit for bit (tools/icp_soak.py found 7 such batches in
+    113 000 scan matches before that).  The sweep's one-wave and four-wave builds get such jobs in test_gpu_icp_tiers."""
     from sonar_slam_amd._lib import IcpParams
     rng = np.random.default_rng(4711)
     for rep in range(6):
@@ -481,6 +490,8 @@ def test_rank_deficient_jobs_come_out_the_same_from_every_kernel(ctx):
                       use_diff_checker=int(rng.integers(0, 2)), min_diff_rot=0.001, min_diff_trans=0.01,
                       smooth_len=int(rng.integers(1, 4)), normals_knn=10)
         a = _with_variant(ctx, 0, lambda: _icp(p, ctx).compute_pairs(srcs, tgts, gs))
+        want = _lib.ICP_ROUTE_TINY if job_tiers == "tiers" else _lib.ICP_ROUTE_Q
+        assert (ctx.icp_routes(len(srcs)) == want).all(), rep
         b = _with_variant(ctx, 4, lambda: _icp(p, ctx).compute_pairs(srcs, tgts, gs))
         assert a[0] == b[0] and np.array_equal(a[2], b[2]), rep
         assert np.array_equal(a[1], b[1], equal_nan=True), rep

@@ -85,6 +85,14 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.sfe_version()
 
 
+def test_icp_route_codes_match_header():
+    hdr = open(os.path.join(ROOT, "include", "sonarfe.h")).read()
+    codes = dict(re.findall(r"#define SFE_ICP_ROUTE_([A-Z0-9]+) (\d+)", hdr))
+    assert len(codes) == 8
+    assert {n: int(v) for n, v in codes.items()} == {n[len("ICP_ROUTE_"):]: getattr(_lib, n)
+                                                       for n in dir(_lib) if n.startswith("ICP_ROUTE_")}
+
+
 def test_params_struct_matches_header():
     hdr = open(os.path.join(ROOT, "include", "sonarfe.h")).read()
     body = hdr[hdr.index("typedef struct sfe_icp_params {"):hdr.index("} sfe_icp_params;")]
