@@ -67,6 +67,8 @@ typedef struct sfe_geom sfe_geom;
 #define SFE_ICP_NAN_TRANS 4  /* "abs translation norm not a number" */
 #define SFE_ICP_SINGULAR 5   /* point-to-plane normal system not positive definite */
 #define SFE_ICP_SPLIT_TIMEOUT 6 /* *_dev entry points only: the workgroups sharing one large job were not resident together (sfe_icp_set_tuning bit 4) */
+#define SFE_ICP_DPF_EMPTY 7     /* *_chain entry points: the job's reading or reference has no point left after its data-point filters */
+#define SFE_ICP_DPF_DEPTH 8     /* *_chain entry points: an OctreeGridDataPointsFilter stage needs a tree deeper than 24 levels */
 
 /* ---- library / context ------------------------------------------------- */
 const char *sfe_version(void);
@@ -260,6 +262,49 @@ int sfe_icp_compute_pairs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
 int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
                          int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
                          int32_t *status, int32_t *iters);
+/* Data-point filters of a libpointmatcher ICP chain (readingDataPointsFilters / referenceDataPointsFilters), 2-D.
+ * A stage keeps a point (x, y) when
+ *   SFE_DPF_MAX_DIST     dim -1: sqrtf(x*x + y*y) < |f[0]|, dim 0 / 1: x / y < f[0]           (maxDist = f[0])
+ *   SFE_DPF_MIN_DIST     dim -1: sqrtf(x*x + y*y) > |f[0]|, dim 0 / 1: |x| / |y| > |f[0]|     (minDist = f[0])
+ *   SFE_DPF_BOUNDING_BOX (xMin < x < xMax && yMin < y < yMax) != remove_inside, f = xMin xMax yMin yMax (zMin zMax unused)
+ *   SFE_DPF_OCTREE_GRID  OctreeGridDataPointsFilter {maxSizeByNode = f[0] > 0, samplingMethod: 3 (medoid),
+ *                        maxPointByNode: 1}: exactly sfe_downsample(cloud, f[0]); clouds of <= 65536 points
+ * (every product / sum rounded to float, correctly rounded sqrtf).  Kept points keep their order.  A
+ * SurfaceNormalDataPointsFilter keeps every point and has no code here: it is sfe_icp_params.normals_knn. */
+#define SFE_DPF_MAX_DIST 0
+#define SFE_DPF_MIN_DIST 1
+#define SFE_DPF_BOUNDING_BOX 2
+#define SFE_DPF_OCTREE_GRID 3
+#define SFE_DPF_MAX_STAGES 8 /* stages per side of a chain */
+typedef struct sfe_icp_dpf {
+    int kind;          /* SFE_DPF_* */
+    int dim;           /* MAX_DIST / MIN_DIST: -1 (norm), 0 (x), 1 (y) */
+    int remove_inside; /* BOUNDING_BOX */
+    float f[6];        /* the stage's thresholds, see above */
+} sfe_icp_dpf;
+/* Runs n_stages stages in order over n_clouds device-resident clouds, cloud c = d_pts[off[c] .. off[c+1]) (off: host,
+ * n_clouds + 1 entries, in points).  The survivors of cloud c go to d_out back to back (cloud c after the survivors of
+ * clouds 0 .. c-1; d_out holds off[n_clouds] points), their number to counts_out[c] (host; -1: an octree stage needed a
+ * tree deeper than 24 levels, no points written).  One stream synchronisation. */
+int sfe_icp_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_stages, const float *d_pts,
+                              const int32_t *off, int n_clouds, float *d_out, int32_t *counts_out);
+/* sfe_icp_compute_guesses / _pairs / _jobs with a chain's data-point filters: the reading stages run once on every
+ * distinct source cloud (slice) of the call, the reference stages once on every distinct target cloud, each in its own
+ * frame before any guess is applied; ICP then runs on the filtered clouds (routes chosen by the filtered sizes).  A job
+ * whose filtered reading or reference is empty reports SFE_ICP_DPF_EMPTY, one whose octree is too deep
+ * SFE_ICP_DPF_DEPTH, both with T = the guess and 0 iterations (sfe_icp_last_routes: -1); the other jobs are unaffected.
+ * With no stages on either side these are the plain entry points. */
+int sfe_icp_compute_guesses_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                                  const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src, const float *tgt, int n_tgt,
+                                  const float *guesses9, int n_guesses, float *T_out9, int32_t *status, int32_t *iters);
+int sfe_icp_compute_pairs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                                const sfe_icp_dpf *rf, int n_rf, const float *src, const int32_t *src_off, const float *tgt,
+                                const int32_t *tgt_off, const float *guesses9, int n_jobs, float *T_out9, int32_t *status,
+                                int32_t *iters);
+int sfe_icp_compute_jobs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                               const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts, const float *tgt,
+                               int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
+                               int32_t *status, int32_t *iters);
 /* A-B knob for the ICP kernels.  bit 2: 0 = strip-sweep exact NN search (default; targets beyond 8192
  * points are walked through L2 instead of LDS), 1 = brute-force tile scan for everything.
  * Brute-force only: bit 0: 0 = packed fp32 NN loop, 1 = scalar fp32; bit 1: 0 = 64-VGPR build,

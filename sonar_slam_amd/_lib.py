@@ -37,7 +37,16 @@ ICP_STATUS_MESSAGES = {
     4: "abs translation norm not a number",
     5: "point-to-plane system not positive definite",
     6: "internal: the workgroups sharing one job were not resident together (sfe_icp_set_tuning bit 4)",
+    7: "data-point filters left the reading or the reference without a point",
+    8: "OctreeGridDataPointsFilter: the octree would be deeper than 24 levels",
 }
+
+# data-point filter stages of an ICP chain (SFE_DPF_* in include/sonarfe.h; icp_config.parse_icp_chain)
+DPF_MAX_DIST = 0
+DPF_MIN_DIST = 1
+DPF_BOUNDING_BOX = 2
+DPF_OCTREE_GRID = 3
+DPF_MAX_STAGES = 8
 
 
 class SonarFEError(RuntimeError):
@@ -64,6 +73,20 @@ class IcpParams(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class IcpDpf(C.Structure):
+    """Mirror of ``struct sfe_icp_dpf`` (include/sonarfe.h): one data-point filter stage."""
+
+    _fields_ = [
+        ("kind", C.c_int),
+        ("dim", C.c_int),
+        ("remove_inside", C.c_int),
+        ("f", C.c_float * 6),
+    ]
+
+    def __repr__(self):
+        return "IcpDpf(kind=%d, dim=%d, remove_inside=%d, f=%r)" % (self.kind, self.dim, self.remove_inside, list(self.f))
 
 
 _u8p = C.POINTER(C.c_uint8)
@@ -133,6 +156,14 @@ SIGNATURES = {
                                         _f32p, _i32p, _i32p]),
     "sfe_icp_compute_jobs": (C.c_int, [_vp, C.POINTER(IcpParams), _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int,
                                        _f32p, _i32p, _i32p]),
+    "sfe_icp_filter_clouds_dev": (C.c_int, [_vp, C.POINTER(IcpDpf), C.c_int, _vp, _i32p, C.c_int, _vp, _i32p]),
+    "sfe_icp_compute_guesses_chain": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpDpf), C.c_int, C.POINTER(IcpDpf),
+                                                C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp_compute_pairs_chain": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpDpf), C.c_int, C.POINTER(IcpDpf),
+                                              C.c_int, _f32p, _i32p, _f32p, _i32p, _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp_compute_jobs_chain": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpDpf), C.c_int, C.POINTER(IcpDpf),
+                                             C.c_int, _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int, _f32p, _i32p,
+                                             _i32p]),
     "sfe_icp_set_tuning": (C.c_int, [_vp, C.c_int]),
     "sfe_icp_get_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "sfe_icp_last_routes": (C.c_int, [_vp, _i32p, C.c_int, _i32p]),

@@ -783,6 +783,14 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
     return 0;
 }
 
+// the launch above for the data-point filter chain (sfe_icp_dpf.hip), which builds its job table on filtered pools
+int sfe_icp_launch_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
+                        const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
+                        int32_t *d_iters)
+{
+    return icp_launch(ctx, p, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
+}
+
 // A job that was shared by several workgroups reports SFE_ICP_SPLIT_TIMEOUT when its shares were not resident
 // together (the device is shared with another context or process; sfe_icp_sweep.hip "split jobs").  The host-pointer
 // entry points see the statuses and run the call once more with splitting off, so the caller never meets status 6.

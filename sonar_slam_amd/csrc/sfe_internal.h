@@ -9,7 +9,7 @@
 
 #include "../../include/sonarfe.h"
 
-#define SFE_NSCRATCH 64
+#define SFE_NSCRATCH 72
 #define SFE_ICP_PROF_N 96 // values sfe_icp_get_profile hands back
 
 // Launcher knobs of one context, set by name with sfe_tune (the name -> field / range table is in sfe_ctx.hip).  The

@@ -4,7 +4,13 @@
 The file is accepted byte for byte.  Supported modules (anything else is rejected loudly --
 silently ignoring a filter would change the pose):
 
-    readingDataPointsFilters / referenceDataPointsFilters : must be empty
+    readingDataPointsFilters / referenceDataPointsFilters (``parse_icp_chain`` only; ``parse_icp_yaml``
+                       refuses any), at most MAX_STAGES per side, 2-D:
+                       MaxDistDataPointsFilter {dim: -1|0|1, maxDist}, MinDistDataPointsFilter {dim, minDist},
+                       BoundingBoxDataPointsFilter {xMin, xMax, yMin, yMax, zMin, zMax, removeInside},
+                       OctreeGridDataPointsFilter {maxSizeByNode, samplingMethod: 3, maxPointByNode: 1, buildParallel},
+                       SurfaceNormalDataPointsFilter {knn, epsilon: 0, keep*} -- last reference stage of a
+                       point-to-plane chain only, where it is ``normals_knn``
     matcher            KDTreeMatcher {knn: 1, epsilon: 0, maxDist}
     outlierFilters     MaxDistOutlierFilter {maxDist}, TrimmedDistOutlierFilter {ratio}
     errorMinimizer     PointToPointErrorMinimizer | PointToPlaneErrorMinimizer {force2D: 1}
@@ -13,10 +19,30 @@ silently ignoring a filter would change the pose):
                                                                smoothLength}
     inspector          NullInspector
     logger             NullLogger
+
+Data-point filters, restated from libpointmatcher's published ICP::compute / computeWithTransformedReference and
+the filters' sources (UNPINNED, like the rest of pcl.cpp's third-party behaviour; tools/pin_thirdparty.py writes
+the fixture that would pin them):
+  * the reading filters run once on the reading in its own frame, before the guess is applied; the reference
+    filters once on the reference in its own frame; the reference mean used for centring is that of the FILTERED
+    reference.  So ICP with a chain is ICP on the filtered clouds.  (Should the library turn out to centre on the
+    unfiltered mean, only float rounding differs: the centring cancels out of the solved transformation.)
+  * stages run in the order listed and keep the relative order of the points they keep.
+  * MaxDist keeps a point when dim -1: sqrtf(x*x + y*y) < |maxDist|, dim 0 / 1: x / y < maxDist (signed);
+    MinDist when dim -1: the norm > |minDist|, dim 0 / 1: |x| / |y| > |minDist| (every product / sum in float);
+    BoundingBox when (xMin < x < xMax and yMin < y < yMax) != removeInside (defaults +-1, removeInside 1);
+    OctreeGrid {samplingMethod: 3, maxPointByNode: 1} is ``pcl.downsample(cloud, maxSizeByNode)``.
+  * refused: the random filters (RandomSampling, MaxPointCount, MaxDensity: not reproducible), OctreeGrid with
+    another sampling method (libpointmatcher's default 0, FirstPoint, is not restated) or maxPointByNode != 1,
+    dim >= 2 (3-D), a SurfaceNormal with epsilon != 0 or maxDist, or anywhere but the last reference stage of a
+    point-to-plane chain, unknown parameter names, readingStepDataPointsFilters.
 """
 import yaml
 
-from ._lib import IcpParams
+from ._lib import (DPF_BOUNDING_BOX, DPF_MAX_DIST, DPF_MAX_STAGES, DPF_MIN_DIST, DPF_OCTREE_GRID, IcpDpf,
+                   IcpParams)
+
+MAX_STAGES = DPF_MAX_STAGES     # data-point filter stages per side of a chain
 
 
 class IcpConfigError(ValueError):
@@ -42,8 +68,7 @@ def _single(node, what):
     raise IcpConfigError("cannot parse %s entry: %r" % (what, node))
 
 
-def parse_icp_yaml(text):
-    """YAML text -> IcpParams."""
+def _load(text):
     doc = yaml.safe_load(text) or {}
     known = {"readingDataPointsFilters", "referenceDataPointsFilters", "matcher", "outlierFilters",
              "errorMinimizer", "transformationCheckers", "inspector", "logger",
@@ -51,10 +76,20 @@ def parse_icp_yaml(text):
     for key in doc:
         if key not in known:
             raise IcpConfigError("unknown ICP chain section %r" % key)
+    return doc
+
+
+def parse_icp_yaml(text):
+    """YAML text -> IcpParams.  Refuses any data-point filter (``parse_icp_chain`` takes them)."""
+    doc = _load(text)
     for key in ("readingDataPointsFilters", "referenceDataPointsFilters", "readingStepDataPointsFilters"):
         if doc.get(key):
-            raise IcpConfigError("%s are not supported (the shipped icp.yaml has none)" % key)
+            raise IcpConfigError("%s are not supported by parse_icp_yaml (parse_icp_chain takes them)" % key)
+    return _params(doc)
 
+
+def _params(doc):
+    """the sections other than the data-point filters -> IcpParams"""
     p = dict(matcher_max_dist=float("inf"), use_max_dist_filter=0, max_dist_filter=0.0,
              use_trimmed_filter=0, trim_ratio=1.0, minimizer=0, max_iter=40, use_diff_checker=0,
              min_diff_rot=0.001, min_diff_trans=0.01, smooth_len=3, normals_knn=10)
@@ -116,3 +151,134 @@ def parse_icp_yaml(text):
             if name != ok:
                 raise IcpConfigError("unsupported %s %r" % (key, name))
     return IcpParams(**p)
+
+
+class SurfaceNormalStage(object):
+    """SurfaceNormalDataPointsFilter as the last reference stage of a point-to-plane chain: keeps every point; its
+    ``knn`` is the chain's ``normals_knn`` (the neighbours, the point itself included, of the PCA normals)."""
+
+    def __init__(self, knn):
+        self.knn = int(knn)
+
+    def __repr__(self):
+        return "SurfaceNormalStage(knn=%d)" % self.knn
+
+    def __eq__(self, other):
+        return isinstance(other, SurfaceNormalStage) and other.knn == self.knn
+
+
+class IcpChain(object):
+    """A parsed ICP chain: ``params`` (IcpParams), ``reading`` and ``reference`` (lists of data-point filter stages:
+    ``IcpDpf`` structures, and on the reference side possibly a final ``SurfaceNormalStage``)."""
+
+    def __init__(self, params, reading=(), reference=()):
+        self.params = params
+        self.reading = list(reading)
+        self.reference = list(reference)
+
+    @staticmethod
+    def device_stages(stages):
+        """the stages the device runs (SurfaceNormal keeps every point and is ``normals_knn``) ->
+        (ctypes array of IcpDpf or None, count)"""
+        dev = [s for s in stages if isinstance(s, IcpDpf)]
+        if not dev:
+            return None, 0
+        arr = (IcpDpf * len(dev))()
+        for i, st in enumerate(dev):
+            arr[i] = st
+        return arr, len(dev)
+
+    def has_filters(self):
+        return any(isinstance(s, IcpDpf) for s in self.reading + self.reference)
+
+
+_RANDOM = {"RandomSamplingDataPointsFilter", "MaxPointCountDataPointsFilter", "MaxDensityDataPointsFilter"}
+
+
+def _known_params(name, fp, allowed):
+    unknown = set(fp) - set(allowed)
+    if unknown:
+        raise IcpConfigError("%s: unsupported parameters %r" % (name, sorted(unknown)))
+
+
+def _dim(name, fp):
+    dim = int(fp.get("dim", -1))
+    if dim >= 2:
+        raise IcpConfigError("%s: dim %d is a 3-D axis (the sonar clouds are 2-D)" % (name, dim))
+    if dim < -1:
+        raise IcpConfigError("%s: dim %d is not -1, 0 or 1" % (name, dim))
+    return dim
+
+
+def _stage(name, fp):
+    """one YAML data-point filter entry -> IcpDpf or SurfaceNormalStage (defaults: libpointmatcher's)"""
+    if name in _RANDOM:
+        raise IcpConfigError("%s draws random numbers: results would not be reproducible" % name)
+    st = IcpDpf()
+    if name == "MaxDistDataPointsFilter":
+        _known_params(name, fp, ("dim", "maxDist"))
+        st.kind, st.dim, st.f[0] = DPF_MAX_DIST, _dim(name, fp), float(fp.get("maxDist", 1.0))
+    elif name == "MinDistDataPointsFilter":
+        _known_params(name, fp, ("dim", "minDist"))
+        st.kind, st.dim, st.f[0] = DPF_MIN_DIST, _dim(name, fp), float(fp.get("minDist", 1.0))
+    elif name == "BoundingBoxDataPointsFilter":
+        keys = ("xMin", "xMax", "yMin", "yMax", "zMin", "zMax")
+        _known_params(name, fp, keys + ("removeInside",))
+        st.kind, st.dim = DPF_BOUNDING_BOX, -1
+        st.remove_inside = 1 if int(fp.get("removeInside", 1)) else 0
+        for i, k in enumerate(keys):
+            st.f[i] = float(fp.get(k, -1.0 if k.endswith("Min") else 1.0))
+    elif name == "OctreeGridDataPointsFilter":
+        _known_params(name, fp, ("maxSizeByNode", "samplingMethod", "maxPointByNode", "buildParallel"))
+        if int(fp.get("samplingMethod", 0)) != 3:
+            raise IcpConfigError("%s needs samplingMethod: 3 (medoid); libpointmatcher's default 0 (FirstPoint) and the "
+                                 "other methods are not restated" % name)
+        if int(fp.get("maxPointByNode", 1)) != 1:
+            raise IcpConfigError("%s: maxPointByNode must be 1" % name)
+        size = float(fp.get("maxSizeByNode", 0.0))
+        if not size > 0.0:
+            raise IcpConfigError("%s: maxSizeByNode must be given and > 0 (got %r)" % (name, size))
+        st.kind, st.dim, st.f[0] = DPF_OCTREE_GRID, -1, size
+    elif name == "SurfaceNormalDataPointsFilter":
+        _known_params(name, fp, ("knn", "epsilon", "keepNormals", "keepDensities", "keepEigenValues",
+                                 "keepEigenVectors", "maxDist"))
+        if "maxDist" in fp:
+            raise IcpConfigError("%s: maxDist is not supported (the normals use the knn nearest points)" % name)
+        if float(fp.get("epsilon", 0)) != 0:
+            raise IcpConfigError("%s: epsilon must be 0 (exact neighbour search)" % name)
+        knn = int(fp.get("knn", 5))
+        if not 2 <= knn <= 16:
+            raise IcpConfigError("%s: knn %d outside [2, 16]" % (name, knn))
+        return SurfaceNormalStage(knn)
+    else:
+        raise IcpConfigError("unsupported data-point filter %r" % name)
+    return st
+
+
+def parse_icp_chain(text):
+    """YAML text -> IcpChain: the IcpParams of ``parse_icp_yaml`` plus the reading and reference data-point filters."""
+    doc = _load(text)
+    if doc.get("readingStepDataPointsFilters"):
+        raise IcpConfigError("readingStepDataPointsFilters are not supported")
+    sides = {}
+    for key in ("readingDataPointsFilters", "referenceDataPointsFilters"):
+        nodes = doc.get(key) or []
+        if not isinstance(nodes, list):
+            nodes = [nodes]
+        if len(nodes) > MAX_STAGES:
+            raise IcpConfigError("%s: %d stages, at most %d" % (key, len(nodes), MAX_STAGES))
+        sides[key] = [_stage(*_single(node, key)) for node in nodes]
+    params = _params(doc)
+    reading, reference = sides["readingDataPointsFilters"], sides["referenceDataPointsFilters"]
+    if any(isinstance(s, SurfaceNormalStage) for s in reading):
+        raise IcpConfigError("SurfaceNormalDataPointsFilter in readingDataPointsFilters: only the last reference stage "
+                             "of a point-to-plane chain is supported")
+    for i, s in enumerate(reference):
+        if isinstance(s, SurfaceNormalStage):
+            if i != len(reference) - 1:
+                raise IcpConfigError("SurfaceNormalDataPointsFilter must be the last referenceDataPointsFilters stage")
+            if params.minimizer != 1:
+                raise IcpConfigError("SurfaceNormalDataPointsFilter is only supported in a point-to-plane chain "
+                                     "(PointToPlaneErrorMinimizer), where it sets the normals")
+            params.normals_knn = s.knn
+    return IcpChain(params, reading, reference)

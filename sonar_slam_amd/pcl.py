@@ -13,6 +13,8 @@ Same names and call signatures as ``PYBIND11_MODULE(pcl, m)``
 
 Extension (not in the reference): ``ICP.compute_batch(source, target, guesses)`` runs the
 many-guesses-one-pair loop of SLAM.compute_icp_with_cov (slam.py:346-358) in one launch.
+``ICP.loadFromYaml`` also takes the data-point filters of a chain (``icp_config.parse_icp_chain``); they run on the
+device in front of the ICP launch of ``compute`` / ``compute_batch`` / ``compute_pairs`` / ``compute_jobs``.
 """
 import ctypes as _C
 import os as _os
@@ -222,6 +224,7 @@ class ICP(object):
         self._ctx = ctx
         # PM::ICP() starts without a chain (pcl.cpp:185); the SLAM node always calls loadFromYaml next (slam.py:99)
         self.params = None
+        self.chain = None   # icp_config.IcpChain: params + the data-point filters (empty after setParams)
 
     def loadFromYaml(self, filename, strict=None):
         """pcl.cpp:187-197.  A file that cannot be opened makes the reference print a message and fall back to
@@ -242,18 +245,36 @@ class ICP(object):
         except (IOError, OSError) as e:
             if not strict:
                 print("Failed to load %s. Use default configuration." % filename)      # pcl.cpp:192, verbatim
-                self.params = _cfg.shipped_params()
+                self.setParams(_cfg.shipped_params())
                 return
             raise RuntimeError("ICP.loadFromYaml: cannot open %s (%s).  The reference would print 'Failed to load ... Use "
                                "default configuration.' and run libpointmatcher's setDefault() chain (random sampling + "
                                "surface normals), which this front end does not provide: fix the path, install a "
                                "chain with setParams(), or pass strict=False / set SONARFE_YAML_FALLBACK=shipped to "
                                "carry on with the chain of the shipped config/icp.yaml" % (filename, e))
-        self.params = _cfg.parse_icp_yaml(text)
+        self.setChain(_cfg.parse_icp_chain(text))
 
     def setParams(self, params):
-        """Extension: install an ``IcpParams`` directly."""
+        """Extension: install an ``IcpParams`` directly (a chain without data-point filters)."""
         self.params = params
+        self.chain = _cfg.IcpChain(params)
+
+    def setChain(self, chain):
+        """Extension: install an ``icp_config.IcpChain`` (what ``loadFromYaml`` parses): its reading filters run once
+        on every distinct source cloud of a call, its reference filters once on every distinct target cloud, on the
+        device and before any guess is applied; ICP then runs on the filtered clouds.  A job left with an empty cloud
+        reports status 7, one whose octree stage would need more than 24 levels status 8 (T = the guess)."""
+        self.params = chain.params
+        self.chain = chain
+
+    def _stages(self):
+        """(reading array, n, reference array, n) of the device stages, or None for a chain without filters"""
+        ch = self.chain
+        if ch is None or not ch.has_filters():
+            return None
+        rd, n_rd = ch.device_stages(ch.reading)
+        rf, n_rf = ch.device_stages(ch.reference)
+        return rd, n_rd, rf, n_rf
 
     def _chain(self):
         if self.params is None:
@@ -289,11 +310,18 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
+        stages = self._stages()
         with ctx.lock:
-            ctx._check(ctx.lib.sfe_icp_compute_guesses(
-                ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src),
-                _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            if stages is None:
+                ctx._check(ctx.lib.sfe_icp_compute_guesses(
+                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src),
+                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            else:
+                ctx._check(ctx.lib.sfe_icp_compute_guesses_chain(
+                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), len(src),
+                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
         msgs = [_L.ICP_STATUS_MESSAGES.get(int(s), "ICP failure %d" % s) for s in st]
         return msgs, T, it
 
@@ -321,11 +349,18 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
+        stages = self._stages()
         with ctx.lock:
-            ctx._check(ctx.lib.sfe_icp_compute_pairs(
-                ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
-                _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            if stages is None:
+                ctx._check(ctx.lib.sfe_icp_compute_pairs(
+                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
+                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            else:
+                ctx._check(ctx.lib.sfe_icp_compute_pairs_chain(
+                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
+                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
         msgs = [_L.ICP_STATUS_MESSAGES.get(int(s), "ICP failure %d" % s) for s in st]
         return msgs, T, it
 
@@ -348,11 +383,18 @@ class ICP(object):
             st, T, it = out
         if n and ((jobs4[:, 1] <= 0).any() or (jobs4[:, 3] <= 0).any()):
             raise RuntimeError("ICP.compute_jobs: empty point cloud (libpointmatcher would throw)")
+        stages = self._stages()
         with ctx.lock:
-            ctx._check(ctx.lib.sfe_icp_compute_jobs(
-                ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt),
-                _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32),
-                _L.ptr(it, _C.c_int32)))
+            if stages is None:
+                ctx._check(ctx.lib.sfe_icp_compute_jobs(
+                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt),
+                    _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32),
+                    _L.ptr(it, _C.c_int32)))
+            else:
+                ctx._check(ctx.lib.sfe_icp_compute_jobs_chain(
+                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float),
+                    len(tgt), _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
         return st, T, it
 
     def getCovariance(self):

@@ -15,6 +15,9 @@ them is in the build image or on the GPU box, so `oracle/` restates their publis
   * `from bruce_slam import pcl` -> tests/golden/thirdparty_pcl.npz: downsample (both overloads), remove_outlier, match, and
                                     ICP().loadFromYaml(icp.yaml as shipped).compute on scan pairs that succeed, on the two
                                     failure classes (messages and the guess returned, pcl.cpp:203,207-210), on 1-point clouds
+                                 -> tests/golden/thirdparty_pcl_dpf.npz: ICP().loadFromYaml(chain).compute with each supported
+                                    data-point filter and the libpointmatcher form of the point-to-plane chain (DPF_CHAINS;
+                                    read by tests/test_gpu_icp_dpf_pin.py)
 
 Each file holds the INPUTS next to the libraries' outputs (a fixture is data), the library versions, and is committed by
 whoever ran this.  `tests/test_golden.py::test_oracle_matches_the_real_*` compare the oracle with them and are skipped while
@@ -162,8 +165,67 @@ def pin_pcl():
     return "wrote thirdparty_pcl.npz"
 
 
+# ICP chains with data-point filters (icp_config.parse_icp_chain): (name, readingDataPointsFilters entries,
+# referenceDataPointsFilters entries, point-to-plane?) spliced into the shipped icp.yaml
+DPF_CHAINS = [
+    ("reading_maxdist", "  - MaxDistDataPointsFilter:\n      maxDist: 15\n", "", False),
+    ("reference_maxdist_y", "", "  - MaxDistDataPointsFilter:\n      dim: 1\n      maxDist: 8\n", False),
+    ("reading_mindist", "  - MinDistDataPointsFilter:\n      minDist: 2\n", "", False),
+    ("reference_box", "", "  - BoundingBoxDataPointsFilter:\n      xMin: -3\n      xMax: 3\n      yMin: -3\n"
+                          "      yMax: 3\n      removeInside: 1\n", False),
+    ("both_octree", "  - OctreeGridDataPointsFilter:\n      maxSizeByNode: 0.3\n      samplingMethod: 3\n",
+     "  - OctreeGridDataPointsFilter:\n      maxSizeByNode: 0.2\n      samplingMethod: 3\n", False),
+    ("point_to_plane_normals", "", "  - SurfaceNormalDataPointsFilter:\n      knn: 10\n      epsilon: 0\n"
+                                   "      keepNormals: 1\n", True),
+]
+
+
+def dpf_chain_yaml(shipped, reading, reference, point_to_plane):
+    y = shipped.replace("readingDataPointsFilters:\n", "readingDataPointsFilters:\n" + reading, 1).replace(
+        "referenceDataPointsFilters:\n", "referenceDataPointsFilters:\n" + reference, 1)
+    if point_to_plane:
+        y = y.replace("  PointToPointErrorMinimizer\n", "").replace(
+            "  # PointToPlaneErrorMinimizer:\n  #   force2D: 1", "  PointToPlaneErrorMinimizer:\n    force2D: 1")
+    icp_config.parse_icp_chain(y)       # (a chain this repo's parser refuses is not worth pinning)
+    return y
+
+
+def pin_pcl_dpf():
+    """tests/golden/thirdparty_pcl_dpf.npz: ICP().loadFromYaml(chain).compute for every chain of DPF_CHAINS on three scan
+    pairs; the fixture holds the chains' YAML, the inputs and the outputs (tests/test_gpu_icp_dpf_pin.py reads it)"""
+    import tempfile
+    pcl = thirdparty.real_pcl()
+    if pcl is None:
+        return "bruce_slam.pcl does not import here: thirdparty_pcl_dpf.npz not written"
+    yaml_path = find_icp_yaml(pcl)
+    if yaml_path is None:
+        return "icp.yaml not found (pass --icp-yaml=PATH): thirdparty_pcl_dpf.npz not written"
+    shipped = open(yaml_path).read()
+    d = {"versions": np.array(json.dumps({"bruce_slam.pcl": getattr(pcl, "__file__", "?"), "numpy": np.__version__}))}
+    for k in range(3):
+        src, tgt, guess, _ = synth.scan_pair(seed=700 + k, n_src=1500, n_tgt=1400)
+        d.update({"src%d" % k: src, "tgt%d" % k: tgt, "guess%d" % k: guess})
+    names = []
+    for name, reading, reference, p2plane in DPF_CHAINS:
+        y = dpf_chain_yaml(shipped, reading, reference, p2plane)
+        with tempfile.NamedTemporaryFile("w", suffix=".yaml", delete=False) as fh:
+            fh.write(y)
+        icp = pcl.ICP()
+        icp.loadFromYaml(fh.name)
+        os.unlink(fh.name)
+        d["yaml_" + name] = np.array(y)
+        for k in range(3):
+            msg, T = icp.compute(d["src%d" % k], d["tgt%d" % k], d["guess%d" % k])
+            d["msg_%s_%d" % (name, k)] = np.array(msg)
+            d["T_%s_%d" % (name, k)] = np.asarray(T, np.float32)
+        names.append(name)
+    d["chains"] = np.array(json.dumps(names))
+    np.savez_compressed(os.path.join(GOLDEN, "thirdparty_pcl_dpf.npz"), **d)
+    return "wrote thirdparty_pcl_dpf.npz"
+
+
 def main():
-    for line in (pin_cv2(), pin_pcl()):
+    for line in (pin_cv2(), pin_pcl(), pin_pcl_dpf()):
         print(line)
 
 
