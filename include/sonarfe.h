@@ -69,6 +69,7 @@ typedef struct sfe_geom sfe_geom;
 #define SFE_ICP_SPLIT_TIMEOUT 6 /* *_dev entry points only: the workgroups sharing one large job were not resident together (sfe_icp_set_tuning bit 4) */
 #define SFE_ICP_DPF_EMPTY 7     /* *_chain entry points: the job's reading or reference has no point left after its data-point filters */
 #define SFE_ICP_DPF_DEPTH 8     /* *_chain entry points: an OctreeGridDataPointsFilter stage needs a tree deeper than 24 levels */
+#define SFE_ICP_BOUND 9         /* *_chain_ext entry points: "limit out of bounds" (BoundTransformationChecker) */
 
 /* ---- library / context ------------------------------------------------- */
 const char *sfe_version(void);
@@ -305,6 +306,39 @@ int sfe_icp_compute_jobs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_
                                const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts, const float *tgt,
                                int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
                                int32_t *status, int32_t *iters);
+/* The outlier filters and transformation checker of a chain that sfe_icp_params has no field for (all zero: none of
+ * them).  d2 is the matcher's float squared distance; a pair is kept only if every listed filter keeps it:
+ *   MinDistOutlierFilter     d2 >= minDist * minDist (the square in float)
+ *   MedianDistOutlierFilter  d2 <= factor * median (a float product), median = the (unsigned)(n * 0.5f)-th smallest (0-based)
+ *                            of the n finite d2 -- the trimmed filter's quantile; none finite: SFE_ICP_NO_OUTLIER
+ * BoundTransformationChecker on the accumulated T_iter (reference-mean frame, identity at the start): out of bounds when
+ * acosf(T00) > max_rotation_norm (a NaN never is) or sqrtf(tx*tx + ty*ty) > max_translation_norm; the job then reports
+ * SFE_ICP_BOUND with T = the guess.  The checkers run in the listed order: Bound is skipped on the iteration at which a
+ * Counter listed before it reaches its limit (bound_order bit 0), and a Differential NaN status wins over Bound's only
+ * when the Differential checker is listed first (bit 1). */
+typedef struct sfe_icp_outliers {
+    int use_min_dist;           /* MinDistOutlierFilter listed */
+    float min_dist;             /*   .minDist (>= 0) */
+    int use_median;             /* MedianDistOutlierFilter listed */
+    float median_factor;        /*   .factor (finite, > 0) */
+    int use_bound;              /* BoundTransformationChecker listed */
+    float max_rotation_norm;    /*   .maxRotationNorm (finite, > 0) */
+    float max_translation_norm; /*   .maxTranslationNorm (finite, > 0) */
+    int bound_order;            /*   bit 0: CounterTransformationChecker listed before it, bit 1: Differential* listed before it */
+} sfe_icp_outliers;
+/* The *_chain entry points with those settings too; o == NULL is exactly the *_chain call. */
+int sfe_icp_compute_guesses_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                      const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                      int n_src, const float *tgt, int n_tgt, const float *guesses9, int n_guesses,
+                                      float *T_out9, int32_t *status, int32_t *iters);
+int sfe_icp_compute_pairs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                    const int32_t *src_off, const float *tgt, const int32_t *tgt_off, const float *guesses9,
+                                    int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
+int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                   const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                   int n_src_pts, const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses9,
+                                   int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
 /* A-B knob for the ICP kernels.  bit 2: 0 = strip-sweep exact NN search (default; targets beyond 8192
  * points are walked through L2 instead of LDS), 1 = brute-force tile scan for everything.
  * Brute-force only: bit 0: 0 = packed fp32 NN loop, 1 = scalar fp32; bit 1: 0 = 64-VGPR build,

@@ -39,7 +39,9 @@ ICP_STATUS_MESSAGES = {
     6: "internal: the workgroups sharing one job were not resident together (sfe_icp_set_tuning bit 4)",
     7: "data-point filters left the reading or the reference without a point",
     8: "OctreeGridDataPointsFilter: the octree would be deeper than 24 levels",
+    9: "limit out of bounds",
 }
+ICP_BOUND = 9   # SFE_ICP_BOUND: BoundTransformationChecker stopped the job
 
 # data-point filter stages of an ICP chain (SFE_DPF_* in include/sonarfe.h; icp_config.parse_icp_chain)
 DPF_MAX_DIST = 0
@@ -87,6 +89,36 @@ class IcpDpf(C.Structure):
 
     def __repr__(self):
         return "IcpDpf(kind=%d, dim=%d, remove_inside=%d, f=%r)" % (self.kind, self.dim, self.remove_inside, list(self.f))
+
+
+class IcpOutliers(C.Structure):
+    """Mirror of ``struct sfe_icp_outliers`` (include/sonarfe.h): the outlier filters and the checker of a chain that
+    ``IcpParams`` has no field for (MinDist, MedianDist, Bound); all zero = none of them."""
+
+    _fields_ = [
+        ("use_min_dist", C.c_int),
+        ("min_dist", C.c_float),
+        ("use_median", C.c_int),
+        ("median_factor", C.c_float),
+        ("use_bound", C.c_int),
+        ("max_rotation_norm", C.c_float),
+        ("max_translation_norm", C.c_float),
+        ("bound_order", C.c_int),
+    ]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+    def any(self):
+        return bool(self.use_min_dist or self.use_median or self.use_bound)
+
+    def __eq__(self, other):
+        return isinstance(other, IcpOutliers) and self.as_dict() == other.as_dict()
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "IcpOutliers(%s)" % ", ".join("%s=%r" % kv for kv in self.as_dict().items())
 
 
 _u8p = C.POINTER(C.c_uint8)
@@ -164,6 +196,15 @@ SIGNATURES = {
     "sfe_icp_compute_jobs_chain": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpDpf), C.c_int, C.POINTER(IcpDpf),
                                              C.c_int, _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int, _f32p, _i32p,
                                              _i32p]),
+    "sfe_icp_compute_guesses_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                    C.c_int, C.POINTER(IcpDpf), C.c_int, _f32p, C.c_int, _f32p, C.c_int,
+                                                    _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp_compute_pairs_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                  C.c_int, C.POINTER(IcpDpf), C.c_int, _f32p, _i32p, _f32p, _i32p, _f32p,
+                                                  C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp_compute_jobs_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                 C.c_int, C.POINTER(IcpDpf), C.c_int, _f32p, C.c_int, _f32p, C.c_int, _i32p,
+                                                 _f32p, C.c_int, _f32p, _i32p, _i32p]),
     "sfe_icp_set_tuning": (C.c_int, [_vp, C.c_int]),
     "sfe_icp_get_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "sfe_icp_last_routes": (C.c_int, [_vp, _i32p, C.c_int, _i32p]),

@@ -138,7 +138,47 @@ struct IcpShared {
     float hist_c[ICP_MAX_HIST], hist_s[ICP_MAX_HIST], hist_x[ICP_MAX_HIST], hist_y[ICP_MAX_HIST];
 };
 
-template <int MINW>
+// k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns) by radix select on the float bit patterns: the loop of the
+// trimmed quantile in icp_job_kernel, for the median of its OX builds (called by the whole workgroup)
+__device__ __forceinline__ float job_select_kth(IcpShared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
+{
+    if (tid == 0) {
+        S.sel_k = k_sel;
+        S.sel_prefix = 0;
+    }
+    __syncthreads();
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256)
+            S.hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = S.sel_prefix;
+        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int i = tid; i < ns; i += ICP_THREADS) {
+            const float d = nn_d2[i];
+            if (d != INFINITY) {
+                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
+                if ((u & himask) == prefix)
+                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned k = S.sel_k, b = 0;
+            for (; b < 256; ++b) {
+                const unsigned h = S.hist[b];
+                if (k < h)
+                    break;
+                k -= h;
+            }
+            S.sel_k = k;
+            S.sel_prefix = prefix | (b << shift);
+        }
+        __syncthreads();
+    }
+    return __uint_as_float(S.sel_prefix);
+}
+
+template <int MINW, bool OX>
 __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_params P, int nn_variant,
                                                               const IcpJob *__restrict__ jobs,
                                                               const float2 *__restrict__ src_all,
@@ -148,8 +188,12 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
                                                               int *__restrict__ nn_idx_all,
                                                               float2 *__restrict__ nrm_all,
                                                               float *__restrict__ T_out, int *__restrict__ status_out,
-                                                              int *__restrict__ iters_out)
+                                                              int *__restrict__ iters_out, sfe_icp_outliers O_arg)
 {
+    // OX: the build for chains with MinDist / MedianDist / Bound (sfe_icp_outliers).  Their code sits in `if constexpr (OX)`
+    // blocks: the other builds compile to the device code they had before the modules existed.
+    const sfe_icp_outliers O = OX ? O_arg : sfe_icp_outliers{};
+
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     IcpShared &S = *reinterpret_cast<IcpShared *>(smem_raw);
 
@@ -319,6 +363,7 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
 
     const float r2_match = f_mul(P.matcher_max_dist, P.matcher_max_dist);
     const float r2_filter = f_mul(P.max_dist_filter, P.max_dist_filter);
+    const float min2 = OX ? f_mul(O.min_dist, O.min_dist) : 0.0f;
 
     while (true) {
         float Ti[9];
@@ -469,6 +514,20 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
         __syncthreads();
         if (fail)
             break;
+        // ---- MedianDistOutlierFilter limit (OX builds): factor x the median, the same radix select at rank icp_median_rank ----
+        float med_limit = INFINITY;
+        if constexpr (OX) {
+            if (O.use_median) {
+                if (nfin == 0) {
+                    if (tid == 0)
+                        S.flag_status = SFE_ICP_NO_OUTLIER; // "no outlier to filter"
+                    break;
+                }
+                // (the barrier above: every wave has read the trimmed limit out of S.sel_prefix, which this select resets)
+                med_limit = f_mul(O.median_factor, job_select_kth(S, nn_d2, ns, tid, icp_median_rank(nfin)));
+                __syncthreads(); // (... and the median out of it before anything else writes it)
+            }
+        }
 
         // ---- error minimiser: accumulate over kept pairs ----
         double acc[10];
@@ -478,8 +537,10 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
         for (int i = tid; i < ns; i += ICP_THREADS) {
             const int id = nn_idx[i];
             const float d = nn_d2[i];
-            const bool ok = id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) &&
-                            (!P.use_trimmed_filter || d <= limit);
+            bool ok = id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) &&
+                      (!P.use_trimmed_filter || d <= limit);
+            if constexpr (OX)
+                ok = ok && icp_ox_keep(O, min2, med_limit, d);
             if (!ok)
                 continue;
             const float2 s = src[i];
@@ -526,7 +587,7 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
         // ---- solve, compose, check (thread 0) ----
         if (tid == 0) {
             int status, iterate;
-            icp_solve_and_check(P, acc, Ti, S.Ti, chk, status, iterate);
+            icp_solve_and_check<OX>(P, O, acc, Ti, S.Ti, chk, status, iterate);
             S.flag_status = status;
             S.flag_iterate = (status == SFE_ICP_OK) ? iterate : 0;
         }
@@ -764,21 +825,17 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
         if (int rc = sfe_pinned_end(ctx, ctx->stream))
             return rc;
     }
-    // occupancy A/B: bit 1 of the tuning variant selects the 128-VGPR build (1 workgroup per CU)
+    // occupancy A/B: bit 1 of the tuning variant selects the 128-VGPR build (1 workgroup per CU); OX: the build for
+    // chains with MinDist / MedianDist / Bound
     const int nnv = ctx->icp_variant & 1;
-    if (!(ctx->icp_variant & 2)) { // default: 64-VGPR build, two workgroups per CU (measured 7 % faster)
-        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp_job_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)sizeof(IcpShared)));
-        hipLaunchKernelGGL(icp_job_kernel<8>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(IcpShared), ctx->stream, *p, nnv,
-                           d_jobs, (const float2 *)d_src, (const float2 *)d_tgt, d_guess9, d_nn_d2, d_nn_idx, d_nrm,
-                           d_T9, d_status, d_iters);
-    } else {
-        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp_job_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)sizeof(IcpShared)));
-        hipLaunchKernelGGL(icp_job_kernel<4>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(IcpShared), ctx->stream, *p, nnv,
-                           d_jobs, (const float2 *)d_src, (const float2 *)d_tgt, d_guess9, d_nn_d2, d_nn_idx, d_nrm,
-                           d_T9, d_status, d_iters);
-    }
+    const sfe_icp_outliers &ox = ctx->icp_ox;
+    const bool with_ox = ox.use_min_dist || ox.use_median || ox.use_bound;
+    auto kernel = !(ctx->icp_variant & 2) ? (with_ox ? icp_job_kernel<8, true> : icp_job_kernel<8, false>) // default: 64-VGPR build, two workgroups per CU (measured 7 % faster)
+                                          : (with_ox ? icp_job_kernel<4, true> : icp_job_kernel<4, false>);
+    SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(IcpShared)));
+    hipLaunchKernelGGL(kernel, dim3(n_jobs), dim3(ICP_THREADS), sizeof(IcpShared), ctx->stream, *p, nnv, d_jobs,
+                       (const float2 *)d_src, (const float2 *)d_tgt, d_guess9, d_nn_d2, d_nn_idx, d_nrm, d_T9, d_status, d_iters,
+                       ox);
     SFE_LAUNCH_CHECK(ctx);
     return 0;
 }

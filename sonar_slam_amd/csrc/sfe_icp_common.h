@@ -152,13 +152,33 @@ struct IcpCheck {
     int nhist, counter, iters;
 };
 
+// MedianDistOutlierFilter: rank (0-based) of the median among the nfin finite distances -- Matches::getDistsQuantile(0.5)
+// as the trimmed quantile is taken: values.size() * 0.5 in float, truncated
+__device__ __forceinline__ unsigned icp_median_rank(unsigned nfin) { return (unsigned)f_mul((float)nfin, 0.5f); }
+
+// kept by MinDist (d >= minDist^2) and by the median filter (d <= its limit)?
+__device__ __forceinline__ bool icp_ox_keep(const sfe_icp_outliers &O, float min2, float med_limit, float d)
+{
+    return (!O.use_min_dist || d >= min2) && (!O.use_median || d <= med_limit);
+}
+
+// BoundTransformationChecker on T_iter: rotation acosf(T00) (NaN when |T00| > 1: never out of bounds), translation
+// sqrtf(tx*tx + ty*ty) in float
+__device__ __forceinline__ bool icp_bound_out(const sfe_icp_outliers &O, const float (&T)[9])
+{
+    const float rot = acosf(T[0]);
+    const float tr = sqrtf(f_add(f_mul(T[2], T[2]), f_mul(T[5], T[5])));
+    return rot > O.max_rotation_norm || tr > O.max_translation_norm;
+}
+
 // One lane: error minimiser solve (closed-form weighted Kabsch, or Cholesky of the 2-D
 // point-to-plane normal equations) from the reduced sums `acc`, T_iter = T_step * T_iter, then
-// the Counter / Differential transformation checkers (libpointmatcher order).  Ti = current
-// T_iter (registers), Ti_lds = where the new one goes.
-__device__ __forceinline__ void icp_solve_and_check(const sfe_icp_params &P, const double (&acc)[10],
-                                                    const float (&Ti)[9], float *Ti_lds, IcpCheck &C, int &status,
-                                                    int &iterate)
+// the Counter / Differential transformation checkers (libpointmatcher order) and, where listed, the Bound checker in
+// its place of the list (sfe_icp_outliers; OX builds only).  Ti = current T_iter (registers), Ti_lds = where the new one goes.
+template <bool OX>
+__device__ __forceinline__ void icp_solve_and_check(const sfe_icp_params &P, const sfe_icp_outliers &O,
+                                                    const double (&acc)[10], const float (&Ti)[9], float *Ti_lds,
+                                                    IcpCheck &C, int &status, int &iterate)
 {
     float *hist_c = C.hist_c, *hist_s = C.hist_s, *hist_x = C.hist_x, *hist_y = C.hist_y;
     int &nhist = C.nhist, &counter = C.counter, &iters = C.iters;
@@ -220,6 +240,16 @@ __device__ __forceinline__ void icp_solve_and_check(const sfe_icp_params &P, con
             Ti_lds[i] = Tn[i];
         ++iters;
         ++counter;
+        // Bound: not evaluated when a Counter listed before it has just reached its limit; its status ends the job at
+        // once unless a Differential checker listed before it runs first (whose NaN status then wins)
+        bool out = false;
+        if constexpr (OX) {
+            out = O.use_bound && !((O.bound_order & 1) && counter >= P.max_iter) && icp_bound_out(O, Tn);
+            if (out && !(O.bound_order & 2)) {
+                status = SFE_ICP_BOUND;
+                return;
+            }
+        }
         if (counter >= P.max_iter) {
             iterate = 0; // CounterTransformationChecker: MaxNumIterationsReached
         } else if (P.use_diff_checker) {
@@ -260,6 +290,10 @@ __device__ __forceinline__ void icp_solve_and_check(const sfe_icp_params &P, con
                 else if (isnan(tsum))
                     status = SFE_ICP_NAN_TRANS;
             }
+        }
+        if constexpr (OX) {
+            if (out && status == SFE_ICP_OK)
+                status = SFE_ICP_BOUND;
         }
     }
 }

@@ -438,6 +438,26 @@ static int dpf_icp_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf
     return 0;
 }
 
+// ---- the *_chain_ext entry points: the chain's outlier filters and checker beyond sfe_icp_params, installed on the
+// context for the one call (every ICP kernel the call launches takes them by value) ----
+template <class F>
+static int icp_with_outliers(sfe_ctx *ctx, const sfe_icp_outliers *o, F call)
+{
+    if (!o)
+        return call();
+    if (!ctx)
+        return SFE_ERR_ARG;
+    SFE_ARG(ctx, !o->use_min_dist || o->min_dist >= 0.0f);
+    SFE_ARG(ctx, !o->use_median || (std::isfinite(o->median_factor) && o->median_factor > 0.0f));
+    SFE_ARG(ctx, !o->use_bound || (std::isfinite(o->max_rotation_norm) && o->max_rotation_norm > 0.0f &&
+                                   std::isfinite(o->max_translation_norm) && o->max_translation_norm > 0.0f));
+    SFE_ARG(ctx, !o->use_bound || (o->bound_order >= 0 && o->bound_order <= 3));
+    ctx->icp_ox = *o;
+    const int rc = call();
+    ctx->icp_ox = sfe_icp_outliers{};
+    return rc;
+}
+
 extern "C" {
 
 int sfe_icp_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_stages, const float *d_pts,
@@ -564,6 +584,39 @@ int sfe_icp_compute_guesses_chain(sfe_ctx *ctx, const sfe_icp_params *p, const s
     }
     return sfe_icp_compute_jobs_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, jobs4.data(), guesses9,
                                       n_guesses, T_out9, status, iters);
+}
+
+int sfe_icp_compute_guesses_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                      const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                      int n_src, const float *tgt, int n_tgt, const float *guesses9, int n_guesses,
+                                      float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_with_outliers(ctx, o, [&] {
+        return sfe_icp_compute_guesses_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, guesses9, n_guesses,
+                                             T_out9, status, iters);
+    });
+}
+
+int sfe_icp_compute_pairs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                    const int32_t *src_off, const float *tgt, const int32_t *tgt_off, const float *guesses9,
+                                    int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_with_outliers(ctx, o, [&] {
+        return sfe_icp_compute_pairs_chain(ctx, p, rd, n_rd, rf, n_rf, src, src_off, tgt, tgt_off, guesses9, n_jobs,
+                                           T_out9, status, iters);
+    });
+}
+
+int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                   const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                   int n_src_pts, const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses9,
+                                   int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_with_outliers(ctx, o, [&] {
+        return sfe_icp_compute_jobs_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9,
+                                          n_jobs, T_out9, status, iters);
+    });
 }
 
 } // extern "C"

@@ -52,7 +52,7 @@ __device__ __forceinline__ int sweep_resolve_tie(const TV &T, const StripTab &ta
 // icp_split_kernel).  Every share runs the whole loop on its own queries; what an iteration decides from ALL queries --
 // the census of a search round, the histograms of the radix select, the sums of the error minimiser -- is exchanged
 // through the job's sync area (xreduce below) and every share takes the same decisions and solves the same system.
-template <int NT, int MINW, bool LDS_TGT, bool LDS_Q, bool PROF, bool REC, bool MULTI>
+template <int NT, int MINW, bool LDS_TGT, bool LDS_Q, bool PROF, bool REC, bool MULTI, bool OX>
 __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, MINW))) void icp_sweep_kernel(
     sfe_icp_params P, const SweepJob *__restrict__ jobs, const int *__restrict__ job_ids, const float2 *__restrict__ src_all,
     const float *__restrict__ guess_all, const float2 *__restrict__ stgt_all, const int *__restrict__ perm_all,
@@ -61,8 +61,12 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     float *__restrict__ nn_d2_all,
     int *__restrict__ nn_pos_all, float *__restrict__ T_out, int *__restrict__ status_out,
     int *__restrict__ iters_out, long long *prof, int *dbg, int sw_budget, int sw_budget_a, int sw_cache, int t_cap, int q_cap, int sort_chunk, float sw_m, float sw_kappa,
-    unsigned long long *__restrict__ sync_all, int sw_cache2)
+    unsigned long long *__restrict__ sync_all, int sw_cache2, sfe_icp_outliers O_arg)
 {
+    // OX: the build for chains with MinDist / MedianDist / Bound (sfe_icp_outliers).  Their code sits in `if constexpr (OX)`
+    // blocks: the other builds compile to the device code they had before the modules existed.
+    const sfe_icp_outliers O = OX ? O_arg : sfe_icp_outliers{};
+
     static_assert(LDS_TGT || !LDS_Q, "LDS_Q needs the LDS-resident target layout");
     static_assert(!MULTI || !PROF, "the profile build runs whole jobs");
     // (the predicted quantile of the clearance-record passes counts the workgroup's own queries, with no exchange)
@@ -328,7 +332,14 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     const float W2 = sw_uniform(fmaxf(r2m_up, f_mul(r2_match, 1.1025f)));
     const float md_hi = sw_uniform(f_mul(P.matcher_max_dist, 1.00001f));
     // no pair beyond Cmax can get weight 1
-    const float Cmax = sw_uniform(P.use_max_dist_filter ? fminf(r2_filter, r2_match) : r2_match);
+    float Cmax = sw_uniform(P.use_max_dist_filter ? fminf(r2_filter, r2_match) : r2_match);
+    const float min2 = OX ? sw_uniform(f_mul(O.min_dist, O.min_dist)) : 0.0f;
+    if constexpr (OX) {
+        // ... except that a median filter with a factor below 1 needs the exact median even where it lies beyond MaxDist
+        // (its limit can then still fall inside MaxDist): its searches go up to the matcher's maxDist
+        if (O.use_median && O.median_factor < 1.0f)
+            Cmax = sw_uniform(r2_match);
+    }
     float Cinit;
     {
         const float h = 8.0f * tab.ext_x / (float)nt; // a few point spacings of a cloud spread along x
@@ -338,6 +349,10 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
         Cinit = sw_uniform(Cinit);
     }
     float Cnext = sw_uniform(P.use_trimmed_filter ? Cinit : Cmax); // cap the next iteration starts with
+    if constexpr (OX) {
+        if (O.use_median) // (an order statistic decides the weights: the searches start capped)
+            Cnext = sw_uniform(Cinit);
+    }
     SW_PROF(0);
 
     const int sw_rtrips = (sw_cache >> 8) & 255;
@@ -506,6 +521,9 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
         float C = Cnext;
         unsigned nfin = 0, nexact = 0, ksel = 0;
         bool limit_inf = false;
+        unsigned kmed = 0;      // (OX) the median's rank,
+        bool med_known = false; //   and the median once the census of a median-only chain has taken it (below)
+        float med = INFINITY;
         // The census of the iteration -- queries without a match, true neighbours within the cap, and the histogram
         // of the top byte of their distances (= the first pass of the radix select) -- is tallied where a query is
         // settled: `none` and `exact` are final for the iteration, so every query is counted once, in whatever round
@@ -1320,11 +1338,33 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 } else {
                     done = nsusp == 0;
                 }
+                if constexpr (OX) {
+                    if (O.use_median && nfin > 0) { // the round settles the larger of the two ranks
+                        kmed = icp_median_rank(nfin);
+                        done = nexact > (P.use_trimmed_filter ? max(ksel, kmed) : kmed);
+                    }
+                }
                 // queries that took a grid witness instead of searching are suspended WITHOUT the guarantee "neighbour
                 // beyond the cap" the other suspended ones carry: the round that searches them must follow, whatever
                 // the census says (they exist only in round 0 of the first iteration, and only while C < Cmax)
                 if (round == 0 && grid_skipped && nsusp != 0)
                     done = false;
+                // A median filter keeps every pair with d2 <= factor * median, which can lie beyond the cap.  Once the
+                // round has settled the median (nexact > kmed: it is the kmed-th exact distance, and a later round only
+                // adds distances beyond this cap, so it stays), a round whose cap is below that limit searches the
+                // suspended queries once more with the limit as the cap.  (A trimmed filter listed too bounds every kept
+                // pair by its own quantile, which is within the cap already.)
+                float c_med = 0.0f;
+                if constexpr (OX) {
+                    if (done && O.use_median && !P.use_trimmed_filter && !med_known && nsusp != 0 && C < Cmax) {
+                        med = select_kth(kmed, false, false);
+                        med_known = true;
+                        c_med = sw_uniform(f_mul(O.median_factor, med));
+                        if (c_med > C)
+                            done = false;
+                        __syncthreads(); // (S.sel_prefix was read by every wave)
+                    }
+                }
                 if (!done && (C >= Cmax || nsusp == 0)) {
                     // the k-th finite distance exceeds MaxDist^2 (or every neighbour is already known)
                     limit_inf = C >= Cmax && nsusp != 0;
@@ -1332,7 +1372,19 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 }
                 if (done)
                     break;
-                if (P.use_trimmed_filter && sw_jump) {
+                bool c_set = false; // (OX) the next cap is set by the median's re-search or its rank
+                if constexpr (OX) {
+                    if (O.use_median && c_med > C) {
+                        C = sw_uniform(fminf(c_med, Cmax));
+                        c_set = true;
+                    } else if (O.use_median && sw_jump) { // (the jump below, at the larger rank)
+                        const float uk = select_kth(P.use_trimmed_filter ? max(ksel, kmed) : kmed, true, false);
+                        C = sw_uniform(fminf(fmaxf(uk, C), Cmax));
+                        c_set = true;
+                    }
+                }
+                if (c_set) {
+                } else if (P.use_trimmed_filter && sw_jump) {
                     // Every finite query holds an upper bound U of its neighbour's distance (exact ones the distance
                     // itself).  The k-th smallest U is >= the k-th smallest distance, so with C = that value the next
                     // round is the last one: at least k+1 queries have their neighbour within C.
@@ -1356,12 +1408,19 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
         // ---- C: TrimmedDistOutlierFilter limit: exact order statistic by radix select ----
         float limit = INFINITY;
         bool fail = false;
+        // the trimmed quantile lies beyond the searched cap (with a median filter of a larger rank the round may have
+        // stopped at Cmax with this one settled)
+        bool trim_inf = limit_inf;
+        if constexpr (OX) {
+            if (O.use_median)
+                trim_inf = limit_inf && nexact <= ksel;
+        }
         if (P.use_trimmed_filter) {
             if (nfin == 0) {
                 fail = true; // "no outlier to filter"
                 if (tid == 0)
                     S.flag_status = SFE_ICP_NO_OUTLIER;
-            } else if (!limit_inf && predict) {
+            } else if (!trim_inf && predict) {
                 // Steady state (round 6): the k-th smallest exact d2 is almost where it was one iteration ago.  ONE pass over the
                 // results counts the values below a window of +-2^17 ulps (0.8 .. 1.6 %) around the previous limit and collects
                 // those inside it (a few dozen of 4000); when the rank falls into the window -- it does, once the clouds have
@@ -1425,17 +1484,46 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 } else {
                     limit = select_kth(ksel, false, false);
                 }
-            } else if (!limit_inf) {
+            } else if (!trim_inf) {
                 limit = select_kth(ksel, false, true);
             }
         }
         __syncthreads();
         if (fail)
             break;
+        // ---- MedianDistOutlierFilter limit: factor * the median (radix select, or the census's).  Beyond the searched
+        // cap (limit_inf with nexact <= kmed) the median exceeds Cmax; Cmax is MaxDist^2 only when factor >= 1, so the
+        // limit is then above every pair MaxDist keeps. ----
+        float med_limit = INFINITY;
+        if constexpr (OX) {
+            if (O.use_median) {
+                if (nfin == 0) {
+                    if (tid == 0)
+                        S.flag_status = SFE_ICP_NO_OUTLIER; // "no outlier to filter"
+                    break;
+                }
+                if (!(limit_inf && nexact <= kmed)) {
+                    if (!med_known)
+                        med = select_kth(kmed, false, false);
+                    med_limit = sw_uniform(f_mul(O.median_factor, med));
+                } else {
+                    med = INFINITY;
+                }
+                __syncthreads();
+            }
+        }
         limit_prev = limit;
         // the next iteration's cap: this limit plus a margin (the clouds keep moving a little: without it about
         // every fourth converged iteration finds one match too few inside the cap and has to search twice)
         Cnext = sw_uniform(P.use_trimmed_filter ? fminf(fmaxf(limit * sw_margin, Cinit * 0.0625f), Cmax) : Cmax);
+        if constexpr (OX) {
+            // with a median filter: from what the weights needed -- the median too, and its limit when no trimmed filter
+            // bounds the kept pairs -- not from the trimmed limit alone
+            if (O.use_median) {
+                const float need = P.use_trimmed_filter ? fmaxf(limit, med) : fmaxf(med, med_limit);
+                Cnext = sw_uniform(fminf(fmaxf(need * sw_margin, Cinit * 0.0625f), Cmax));
+            }
+        }
         SW_PROF(3);
         SW_STAMP(6);
 
@@ -1463,8 +1551,10 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                     id = Pz(i);
                     d = Dz(i);
                 }
-                const bool ok = in && id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) &&
-                                (!P.use_trimmed_filter || d <= limit);
+                bool ok = in && id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) &&
+                          (!P.use_trimmed_filter || d <= limit);
+                if constexpr (OX)
+                    ok = ok && icp_ox_keep(O, min2, med_limit, d);
                 cnt += (unsigned)__popcll(__ballot(ok));
                 return ok;
             };
@@ -1550,7 +1640,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
             for (int i = 0; i < 10; ++i)
                 acc[i] = S.acc[i];
             IcpCheck chk = {S.hist_c, S.hist_s, S.hist_x, S.hist_y, S.chk_n[0], S.chk_n[1], S.chk_n[2]};
-            icp_solve_and_check(P, acc, Ti, S.Ti, chk, status, iterate);
+            icp_solve_and_check<OX>(P, O, acc, Ti, S.Ti, chk, status, iterate);
             S.chk_n[0] = chk.nhist;
             S.chk_n[1] = chk.counter;
             S.chk_n[2] = chk.iters;
@@ -1719,13 +1809,15 @@ template <int NT, int MINW, bool LDS_TGT, bool LDS_Q, bool PROF, bool REC, bool 
 int sweep_launch_loop(const SweepLaunchArgs &a, int n, const int *d_ids, size_t body, int t_cap, int q_cap)
 {
     sfe_ctx *ctx = a.ctx;
-    auto kernel = icp_sweep_kernel<NT, MINW, LDS_TGT, LDS_Q, PROF, REC, MULTI>;
+    const sfe_icp_outliers &ox = ctx->icp_ox;
+    auto kernel = (ox.use_min_dist || ox.use_median || ox.use_bound) ? icp_sweep_kernel<NT, MINW, LDS_TGT, LDS_Q, PROF, REC, MULTI, true>
+                                                                     : icp_sweep_kernel<NT, MINW, LDS_TGT, LDS_Q, PROF, REC, MULTI, false>;
     const size_t smem = sweep_ctl_bytes<NT, PROF, REC>() + body;
     SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(kernel, dim3(n), dim3(NT), smem, ctx->stream, *a.p, a.d_jobs, d_ids, a.d_src, a.d_guess9, a.d_stgt,
                        a.d_perm, a.d_snrm, a.d_mean, a.d_tab, a.d_grid, a.d_qst, a.d_qwl, a.d_qssrc, a.d_nn_d2, a.d_nn_pos,
                        a.d_T9, a.d_status, a.d_iters, a.d_prof, a.d_dbg, a.sw_budget, a.sw_budget_a, a.sw_cache, t_cap, q_cap,
-                       pow2_floor(body / 8), a.sw_m, a.sw_kappa, a.d_sync, a.sw_cache2);
+                       pow2_floor(body / 8), a.sw_m, a.sw_kappa, a.d_sync, a.sw_cache2, ox);
     SFE_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1769,11 +1861,13 @@ int sweep_launch_tiny(sfe_ctx *ctx, const sfe_icp_params *p, int n, const SweepJ
                       const float *d_mean, const StripTab *d_tab, float *d_T9, int32_t *d_status, int32_t *d_iters, int tiny_tmax,
                       int tiny_smax)
 {
+    const sfe_icp_outliers &ox = ctx->icp_ox;
+    auto kernel = (ox.use_min_dist || ox.use_median || ox.use_bound) ? icp_tiny_kernel<true> : icp_tiny_kernel<false>;
     const int tc = ((tiny_tmax + SW_TINY_CH - 1) / SW_TINY_CH + 1) * SW_TINY_CH, qc = (tiny_smax + 3) & ~3; // (whole chunks + one of padding)
     const size_t smem = ((sizeof(TinyShared) + 15) & ~(size_t)15) + sizeof(float2) * (size_t)tc * (p->minimizer == 1 ? 2 : 1) +
                         6 * (size_t)qc;
-    hipLaunchKernelGGL(icp_tiny_kernel, dim3(n), dim3(SW_TINY_NT), smem, ctx->stream, *p, d_jobs, d_ids, d_preps, d_src, d_tgt,
-                       d_guess9, d_perm, d_snrm, d_mean, d_tab, d_T9, d_status, d_iters, tc, qc);
+    hipLaunchKernelGGL(kernel, dim3(n), dim3(SW_TINY_NT), smem, ctx->stream, *p, d_jobs, d_ids, d_preps, d_src, d_tgt,
+                       d_guess9, d_perm, d_snrm, d_mean, d_tab, d_T9, d_status, d_iters, tc, qc, ox);
     SFE_LAUNCH_CHECK(ctx);
     return 0;
 }

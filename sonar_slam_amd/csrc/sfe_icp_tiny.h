@@ -36,14 +36,66 @@ struct TinyShared {
     unsigned sel_k, sel_prefix;
 };
 
+// k_sel-th smallest (0-based) finite distance of s_d2[0 .. ns) by radix select on the float bit patterns: the loop of the
+// trimmed quantile below, for the median of the OX builds (called by the whole wave)
+__device__ __forceinline__ float tiny_select_kth(TinyShared &S, const float *s_d2, int ns, int lane, unsigned k_sel)
+{
+    unsigned prefix = 0;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+            S.hist[4 * lane + b] = 0;
+        __syncthreads();
+        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int i = lane; i < ns; i += SW_TINY_NT) {
+            const float d = s_d2[i];
+            if (d != INFINITY) {
+                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
+                if ((u & himask) == prefix)
+                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
+            }
+        }
+        __syncthreads();
+        const unsigned h0 = S.hist[4 * lane], h1 = S.hist[4 * lane + 1], h2 = S.hist[4 * lane + 2], h3 = S.hist[4 * lane + 3];
+        const unsigned tot = h0 + h1 + h2 + h3;
+        const unsigned incl = wave_inclusive_scan(tot), excl = incl - tot;
+        if (k_sel >= excl && k_sel < incl) { // exactly one lane
+            unsigned r = k_sel - excl, b = 4 * lane;
+            if (r >= h0) {
+                r -= h0;
+                ++b;
+                if (r >= h1) {
+                    r -= h1;
+                    ++b;
+                    if (r >= h2) {
+                        r -= h2;
+                        ++b;
+                    }
+                }
+            }
+            S.sel_k = r;
+            S.sel_prefix = prefix | (b << shift);
+        }
+        __syncthreads();
+        k_sel = S.sel_k;
+        prefix = S.sel_prefix;
+    }
+    return __uint_as_float(prefix);
+}
+
 // dynamic LDS behind TinyShared: [tgt: t_cap float2][nrm: t_cap float2 (point-to-plane)][d2: q_cap float][idx: q_cap int16]
+template <bool OX>
 __global__ __launch_bounds__(SW_TINY_NT, 4) void icp_tiny_kernel(
     sfe_icp_params P, const SweepJob *__restrict__ jobs, const int *__restrict__ job_ids, const SweepPrep *__restrict__ preps,
     const float2 *__restrict__ src_all, const float2 *__restrict__ tgt_all, const float *__restrict__ guess_all,
     const int *__restrict__ perm_all, const float2 *__restrict__ snrm_all, const float *__restrict__ mean_all,
     const StripTab *__restrict__ tab_all, float *__restrict__ T_out, int *__restrict__ status_out, int *__restrict__ iters_out,
-    int t_cap, int q_cap)
+    int t_cap, int q_cap, sfe_icp_outliers O_arg)
 {
+    // OX: the build for chains with MinDist / MedianDist / Bound (sfe_icp_outliers).  Their code sits in `if constexpr (OX)`
+    // blocks: the other build compiles to the device code it had before the modules existed.
+    const sfe_icp_outliers O = OX ? O_arg : sfe_icp_outliers{};
+
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     TinyShared &S = *reinterpret_cast<TinyShared *>(smem_raw);
     float2 *s_tgt = reinterpret_cast<float2 *>(smem_raw + ((sizeof(TinyShared) + 15) & ~(size_t)15));
@@ -123,6 +175,7 @@ __global__ __launch_bounds__(SW_TINY_NT, 4) void icp_tiny_kernel(
     __syncthreads(); // (one wave: orders the LDS writes above, costs nothing)
     const float r2_match = sw_uniform(f_mul(P.matcher_max_dist, P.matcher_max_dist));
     const float r2_filter = sw_uniform(f_mul(P.max_dist_filter, P.max_dist_filter));
+    const float min2 = OX ? sw_uniform(f_mul(O.min_dist, O.min_dist)) : 0.0f;
     auto xform = [&](const float (&Ti)[9], float2 sp) { // cur = Ti * (T0 * src): the two roundings of every ICP kernel here
         const float rx = affine1(T0[0], T0[1], T0[2], sp.x, sp.y);
         const float ry = affine1(T0[3], T0[4], T0[5], sp.x, sp.y);
@@ -245,6 +298,18 @@ __global__ __launch_bounds__(SW_TINY_NT, 4) void icp_tiny_kernel(
             }
             limit = sw_uniform(__uint_as_float(prefix));
         }
+        // ---- MedianDistOutlierFilter limit (OX builds): factor x the median, the same radix select at rank icp_median_rank ----
+        float med_limit = INFINITY;
+        if constexpr (OX) {
+            if (O.use_median) {
+                if (nfin == 0) { // "no outlier to filter"
+                    if (lane == 0)
+                        S.flag_status = SFE_ICP_NO_OUTLIER;
+                    break;
+                }
+                med_limit = sw_uniform(f_mul(O.median_factor, tiny_select_kth(S, s_d2, ns, lane, icp_median_rank(nfin))));
+            }
+        }
         // ---- error minimiser: sums over the kept pairs, fp64, in the order of the 1024-thread kernels (query i = their
         // thread i, 64 consecutive queries = one of their waves: the wave's fixed tree, then the waves left to right).
         // The sums of a rank-deficient problem (a target of three points) are rounding noise that the solve amplifies
@@ -261,7 +326,9 @@ __global__ __launch_bounds__(SW_TINY_NT, 4) void icp_tiny_kernel(
                 t[k] = 0.0;
             const int id = i < ns ? (int)s_idx[i] : -1;
             const float d = i < ns ? s_d2[i] : INFINITY;
-            const bool ok = id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit);
+            bool ok = id >= 0 && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit);
+            if constexpr (OX)
+                ok = ok && icp_ox_keep(O, min2, med_limit, d);
             if (ok) {
                 const float2 p = xform(Ti, src[i]);
                 const double px = p.x, py = p.y;
@@ -302,7 +369,7 @@ __global__ __launch_bounds__(SW_TINY_NT, 4) void icp_tiny_kernel(
         // ---- solve, compose, check (one lane) ----
         if (lane == 0) {
             int status, iterate;
-            icp_solve_and_check(P, acc, Ti, S.Ti, chk, status, iterate);
+            icp_solve_and_check<OX>(P, O, acc, Ti, S.Ti, chk, status, iterate);
             S.flag_status = status;
             S.flag_iterate = (status == SFE_ICP_OK) ? iterate : 0;
         }

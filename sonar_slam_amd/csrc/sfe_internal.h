@@ -93,6 +93,8 @@ struct sfe_ctx {
     int icp_prof = 0;            // debug: per-phase cycle counts of workgroup 0 of the sweep kernel
     long long icp_prof_host[SFE_ICP_PROF_N] = {0};
     std::vector<int8_t> icp_routes; // SFE_ICP_ROUTE_* of every job of the last ICP call (sfe_icp_last_routes)
+    // the outlier filters / checker of the *_chain_ext call in progress (all zero outside one): every ICP kernel takes it
+    sfe_icp_outliers icp_ox = {};
     int n_cu = 256;
     // clouds left in the staging slots by sfe_extract_points_bits_staged_dev, waiting for sfe_cloud_filter_staged_dev
     // (-1: none; anything else that writes those slots resets it)

@@ -12,13 +12,21 @@ silently ignoring a filter would change the pose):
                        SurfaceNormalDataPointsFilter {knn, epsilon: 0, keep*} -- last reference stage of a
                        point-to-plane chain only, where it is ``normals_knn``
     matcher            KDTreeMatcher {knn: 1, epsilon: 0, maxDist}
-    outlierFilters     MaxDistOutlierFilter {maxDist}, TrimmedDistOutlierFilter {ratio}
+    outlierFilters     MaxDistOutlierFilter {maxDist}, TrimmedDistOutlierFilter {ratio}; with ``parse_icp_chain``
+                       also MinDistOutlierFilter {minDist}, MedianDistOutlierFilter {factor}, NullOutlierFilter
+                       (each at most once, any order; the weights are the product of the filters')
     errorMinimizer     PointToPointErrorMinimizer | PointToPlaneErrorMinimizer {force2D: 1}
     transformationCheckers  CounterTransformationChecker {maxIterationCount},
                             DifferentialTransformationChecker {minDiffRotErr, minDiffTransErr,
-                                                               smoothLength}
+                                                               smoothLength};
+                            with ``parse_icp_chain`` also BoundTransformationChecker {maxRotationNorm,
+                                                               maxTranslationNorm} (its place in the list is kept)
     inspector          NullInspector
     logger             NullLogger
+
+The outlier filters and the checker only ``parse_icp_chain`` takes live in ``IcpChain.outliers`` (``IcpOutliers``, the
+mirror of ``sfe_icp_outliers``; its comment in include/sonarfe.h states their rules), not in ``IcpParams``: the farm,
+store, chained and replay paths keep running chains without them.
 
 Data-point filters, restated from libpointmatcher's published ICP::compute / computeWithTransformedReference and
 the filters' sources (UNPINNED, like the rest of pcl.cpp's third-party behaviour; tools/pin_thirdparty.py writes
@@ -37,10 +45,12 @@ the fixture that would pin them):
     dim >= 2 (3-D), a SurfaceNormal with epsilon != 0 or maxDist, or anywhere but the last reference stage of a
     point-to-plane chain, unknown parameter names, readingStepDataPointsFilters.
 """
+import math
+
 import yaml
 
 from ._lib import (DPF_BOUNDING_BOX, DPF_MAX_DIST, DPF_MAX_STAGES, DPF_MIN_DIST, DPF_OCTREE_GRID, IcpDpf,
-                   IcpParams)
+                   IcpOutliers, IcpParams)
 
 MAX_STAGES = DPF_MAX_STAGES     # data-point filter stages per side of a chain
 
@@ -88,8 +98,20 @@ def parse_icp_yaml(text):
     return _params(doc)
 
 
-def _params(doc):
-    """the sections other than the data-point filters -> IcpParams"""
+# modules only parse_icp_chain takes (their settings go to IcpChain.outliers)
+_CHAIN_ONLY = {"MinDistOutlierFilter", "MedianDistOutlierFilter", "NullOutlierFilter", "BoundTransformationChecker"}
+
+
+def _positive(name, key, v):
+    v = float(v)
+    if not (math.isfinite(v) and v > 0.0):
+        raise IcpConfigError("%s: %s must be finite and > 0 (got %r)" % (name, key, v))
+    return v
+
+
+def _params(doc, ox=None):
+    """the sections other than the data-point filters -> IcpParams; ``ox`` (an IcpOutliers to fill: parse_icp_chain)
+    takes the modules of _CHAIN_ONLY, without it they are refused"""
     p = dict(matcher_max_dist=float("inf"), use_max_dist_filter=0, max_dist_filter=0.0,
              use_trimmed_filter=0, trim_ratio=1.0, minimizer=0, max_iter=40, use_diff_checker=0,
              min_diff_rot=0.001, min_diff_trans=0.01, smooth_len=3, normals_knn=10)
@@ -107,18 +129,31 @@ def _params(doc):
             raise IcpConfigError("unsupported KDTreeMatcher parameters %r" % sorted(unknown))
         p["matcher_max_dist"] = float(mp.get("maxDist", float("inf")))
 
+    listed = set()
     for node in doc.get("outlierFilters") or []:
         name, fp = _single(node, "outlierFilters")
+        if name in _CHAIN_ONLY and ox is None:
+            raise IcpConfigError("%s is not supported by parse_icp_yaml (parse_icp_chain takes it)" % name)
+        if name in listed:
+            raise IcpConfigError("%s listed twice" % name)
+        listed.add(name)
         if name == "MaxDistOutlierFilter":
-            if p["use_max_dist_filter"]:
-                raise IcpConfigError("MaxDistOutlierFilter listed twice")
             p["use_max_dist_filter"] = 1
             p["max_dist_filter"] = float(fp.get("maxDist", 1.0))
         elif name == "TrimmedDistOutlierFilter":
-            if p["use_trimmed_filter"]:
-                raise IcpConfigError("TrimmedDistOutlierFilter listed twice")
             p["use_trimmed_filter"] = 1
             p["trim_ratio"] = float(fp.get("ratio", 0.85))
+        elif name == "MinDistOutlierFilter":
+            _known_params(name, fp, ("minDist",))
+            v = float(fp.get("minDist", 1.0))
+            if not v >= 0.0:
+                raise IcpConfigError("%s: minDist must be >= 0 (got %r)" % (name, v))
+            ox.use_min_dist, ox.min_dist = 1, v
+        elif name == "MedianDistOutlierFilter":
+            _known_params(name, fp, ("factor",))
+            ox.use_median, ox.median_factor = 1, _positive(name, "factor", fp.get("factor", 3.0))
+        elif name == "NullOutlierFilter":
+            _known_params(name, fp, ())      # keeps every pair
         else:
             raise IcpConfigError("unsupported outlier filter %r" % name)
 
@@ -133,11 +168,25 @@ def _params(doc):
         else:
             raise IcpConfigError("unsupported error minimizer %r" % name)
 
+    seen_counter = seen_diff = False
     for node in doc.get("transformationCheckers") or []:
         name, cp = _single(node, "transformationCheckers")
+        if name in _CHAIN_ONLY and ox is None:
+            raise IcpConfigError("%s is not supported by parse_icp_yaml (parse_icp_chain takes it)" % name)
         if name == "CounterTransformationChecker":
+            seen_counter = True
             p["max_iter"] = int(cp.get("maxIterationCount", 40))
+        elif name == "BoundTransformationChecker":
+            if ox.use_bound:
+                raise IcpConfigError("%s listed twice" % name)
+            _known_params(name, cp, ("maxRotationNorm", "maxTranslationNorm"))
+            ox.use_bound = 1
+            ox.max_rotation_norm = _positive(name, "maxRotationNorm", cp.get("maxRotationNorm", 1.0))
+            ox.max_translation_norm = _positive(name, "maxTranslationNorm", cp.get("maxTranslationNorm", 1.0))
+            # where it runs among the others: after a Counter / a Differential listed before it
+            ox.bound_order = (1 if seen_counter else 0) | (2 if seen_diff else 0)
         elif name == "DifferentialTransformationChecker":
+            seen_diff = True
             p["use_diff_checker"] = 1
             p["min_diff_rot"] = float(cp.get("minDiffRotErr", 0.001))
             p["min_diff_trans"] = float(cp.get("minDiffTransErr", 0.001))
@@ -169,12 +218,14 @@ class SurfaceNormalStage(object):
 
 class IcpChain(object):
     """A parsed ICP chain: ``params`` (IcpParams), ``reading`` and ``reference`` (lists of data-point filter stages:
-    ``IcpDpf`` structures, and on the reference side possibly a final ``SurfaceNormalStage``)."""
+    ``IcpDpf`` structures, and on the reference side possibly a final ``SurfaceNormalStage``), ``outliers``
+    (IcpOutliers: MinDist / MedianDist outlier filters and the Bound checker; all zero when none is listed)."""
 
-    def __init__(self, params, reading=(), reference=()):
+    def __init__(self, params, reading=(), reference=(), outliers=None):
         self.params = params
         self.reading = list(reading)
         self.reference = list(reference)
+        self.outliers = outliers if outliers is not None else IcpOutliers()
 
     @staticmethod
     def device_stages(stages):
@@ -256,7 +307,8 @@ def _stage(name, fp):
 
 
 def parse_icp_chain(text):
-    """YAML text -> IcpChain: the IcpParams of ``parse_icp_yaml`` plus the reading and reference data-point filters."""
+    """YAML text -> IcpChain: the IcpParams of ``parse_icp_yaml`` plus the reading and reference data-point filters and
+    the outlier filters / checker of ``IcpChain.outliers``."""
     doc = _load(text)
     if doc.get("readingStepDataPointsFilters"):
         raise IcpConfigError("readingStepDataPointsFilters are not supported")
@@ -268,7 +320,8 @@ def parse_icp_chain(text):
         if len(nodes) > MAX_STAGES:
             raise IcpConfigError("%s: %d stages, at most %d" % (key, len(nodes), MAX_STAGES))
         sides[key] = [_stage(*_single(node, key)) for node in nodes]
-    params = _params(doc)
+    outliers = IcpOutliers()
+    params = _params(doc, outliers)
     reading, reference = sides["readingDataPointsFilters"], sides["referenceDataPointsFilters"]
     if any(isinstance(s, SurfaceNormalStage) for s in reading):
         raise IcpConfigError("SurfaceNormalDataPointsFilter in readingDataPointsFilters: only the last reference stage "
@@ -281,4 +334,4 @@ def parse_icp_chain(text):
                 raise IcpConfigError("SurfaceNormalDataPointsFilter is only supported in a point-to-plane chain "
                                      "(PointToPlaneErrorMinimizer), where it sets the normals")
             params.normals_knn = s.knn
-    return IcpChain(params, reading, reference)
+    return IcpChain(params, reading, reference, outliers)

@@ -263,7 +263,9 @@ class ICP(object):
         """Extension: install an ``icp_config.IcpChain`` (what ``loadFromYaml`` parses): its reading filters run once
         on every distinct source cloud of a call, its reference filters once on every distinct target cloud, on the
         device and before any guess is applied; ICP then runs on the filtered clouds.  A job left with an empty cloud
-        reports status 7, one whose octree stage would need more than 24 levels status 8 (T = the guess)."""
+        reports status 7, one whose octree stage would need more than 24 levels status 8 (T = the guess).  Its
+        ``outliers`` (MinDist / MedianDist outlier filters, BoundTransformationChecker) run inside the ICP loop; a job
+        the Bound checker stops reports status 9, "limit out of bounds" (T = the guess)."""
         self.params = chain.params
         self.chain = chain
 
@@ -275,6 +277,11 @@ class ICP(object):
         rd, n_rd = ch.device_stages(ch.reading)
         rf, n_rf = ch.device_stages(ch.reference)
         return rd, n_rd, rf, n_rf
+
+    def _outliers(self):
+        """the chain's ``IcpOutliers`` (MinDist / MedianDist / Bound), or None when it lists none of them"""
+        ch = self.chain
+        return ch.outliers if ch is not None and ch.outliers.any() else None
 
     def _chain(self):
         if self.params is None:
@@ -310,11 +317,17 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
-        stages = self._stages()
+        stages, ox = self._stages(), self._outliers()
         with ctx.lock:
-            if stages is None:
+            if stages is None and ox is None:
                 ctx._check(ctx.lib.sfe_icp_compute_guesses(
                     ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src),
+                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            elif ox is not None:
+                ctx._check(ctx.lib.sfe_icp_compute_guesses_chain_ext(
+                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
+                    _L.ptr(src, _C.c_float), len(src),
                     _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
                     _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
             else:
@@ -349,11 +362,17 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
-        stages = self._stages()
+        stages, ox = self._stages(), self._outliers()
         with ctx.lock:
-            if stages is None:
+            if stages is None and ox is None:
                 ctx._check(ctx.lib.sfe_icp_compute_pairs(
                     ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
+                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            elif ox is not None:
+                ctx._check(ctx.lib.sfe_icp_compute_pairs_chain_ext(
+                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
+                    _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
                     _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
                     _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
             else:
@@ -383,13 +402,19 @@ class ICP(object):
             st, T, it = out
         if n and ((jobs4[:, 1] <= 0).any() or (jobs4[:, 3] <= 0).any()):
             raise RuntimeError("ICP.compute_jobs: empty point cloud (libpointmatcher would throw)")
-        stages = self._stages()
+        stages, ox = self._stages(), self._outliers()
         with ctx.lock:
-            if stages is None:
+            if stages is None and ox is None:
                 ctx._check(ctx.lib.sfe_icp_compute_jobs(
                     ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt),
                     _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32),
                     _L.ptr(it, _C.c_int32)))
+            elif ox is not None:
+                ctx._check(ctx.lib.sfe_icp_compute_jobs_chain_ext(
+                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
+                    _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float),
+                    len(tgt), _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
             else:
                 ctx._check(ctx.lib.sfe_icp_compute_jobs_chain(
                     ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float),
