@@ -222,10 +222,13 @@ def test_tiny_kernel_limits(ctx, chain):
     _check_oracle(p, picks, srcs, tgts, jobs, gs, got, chain)
 
 
-def test_every_job_class_in_one_call(ctx):
-    """Tiny, one-wave, four-wave and 1024-thread jobs (queries in LDS, target in LDS with the per-query results in HBM,
-    target in HBM) side by side in one call that holds 2 x CUs small jobs, so that both small tiers are live."""
-    p = icp_config.shipped_params(**P2P_REC)
+BIG_ROUTES = [L.ICP_ROUTE_Q, L.ICP_ROUTE_Q, L.ICP_ROUTE_LDS, L.ICP_ROUTE_LDS, L.ICP_ROUTE_GLB, L.ICP_ROUTE_GLB]
+
+
+def _every_class_batch(ctx):
+    """2 x CUs + 64 small jobs (tiny, one-wave and four-wave shapes) and the six 1024-thread jobs of BIG_ROUTES behind
+    them -> (srcs, tgts, jobs, guesses, n = the number of small jobs, n0 = the number of tiny and one-wave pairs, which
+    come first among the distinct pairs)"""
     rng = np.random.default_rng(35)
     sizes = [(int(a), int(b)) for a, b in zip(rng.integers(60, 300, 12), rng.integers(60, 300, 12))]      # tiny
     sizes += [(int(a), int(b)) for a, b in zip(rng.integers(330, 385, 12), rng.integers(400, 513, 12))]   # one wave
@@ -241,11 +244,19 @@ def test_every_job_class_in_one_call(ctx):
     jobs += j1
     gs += g1 + [q[2] for q in pairs[n_small:]]
     jobs += [(n_small + i, n_small + i) for i in range(len(big))]
+    return srcs, tgts, jobs, gs, n, n0
+
+
+def test_every_job_class_in_one_call(ctx):
+    """Tiny, one-wave, four-wave and 1024-thread jobs (queries in LDS, target in LDS with the per-query results in HBM,
+    target in HBM) side by side in one call that holds 2 x CUs small jobs, so that both small tiers are live."""
+    p = icp_config.shipped_params(**P2P_REC)
+    srcs, tgts, jobs, gs, n, n0 = _every_class_batch(ctx)
     got = _run(ctx, p, srcs, tgts, jobs, gs)
     r = list(got[3])
     shapes = [(len(srcs[a]), len(tgts[b])) for a, b in jobs]
     assert r[:n] == _small_routes(shapes, p, ctx.n_cu)[:n]
-    assert r[n:] == [L.ICP_ROUTE_Q, L.ICP_ROUTE_Q, L.ICP_ROUTE_LDS, L.ICP_ROUTE_LDS, L.ICP_ROUTE_GLB, L.ICP_ROUTE_GLB]
+    assert r[n:] == BIG_ROUTES
     for route in (L.ICP_ROUTE_TINY, L.ICP_ROUTE_T0, L.ICP_ROUTE_T1):
         assert r[:n].count(route) >= 8, route
     _same(got, _run(ctx, p, srcs, tgts, jobs, gs, **ONE_SIZE), "one-size")
