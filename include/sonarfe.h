@@ -478,6 +478,15 @@ int sfe_icp_store_jobs_dev(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_stor
                            const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status, int32_t *d_iters);
 int sfe_icp_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store *s, const int32_t *pairs,
                           const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
+/* sfe_icp_store_compute with a whole chain: o (may be NULL) as in sfe_icp_compute_jobs_chain_ext, rd / rf the reading
+ * / reference data-point filter stages.  The pairs are refused as sfe_icp_store_compute refuses them.  No stage: the
+ * sfe_icp_store_compute call under o.  With stages they read the store's pool in place, every distinct handle of a side
+ * filtered once per call; results as sfe_icp_compute_jobs_chain_ext's (statuses 7, 8 and 9 with T = the guess).  The
+ * octree stage rewrites the staging slots of sfe_extract_points_bits_staged_dev. */
+int sfe_icp_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf,
+                                    sfe_cloud_store *s, const int32_t *pairs, const float *guesses9, int n_jobs,
+                                    float *T_out9, int32_t *status, int32_t *iters);
 /* SLAM.get_overlap (slam.py:389-424) for n_jobs (source, target) pairs: the source moved by T6[j*6 ..] (the estimated
  * pose's matrix as float32), pcl.match(target, source, 1, max_dist), counts_out[j] = matched points (host) */
 int sfe_cloud_store_overlap(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *pairs, const float *T6, int n_jobs,

@@ -225,6 +225,9 @@ SIGNATURES = {
     "sfe_cloud_store_get_points": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_int, C.c_float, C.c_int, _i64p, _i32p]),
     "sfe_icp_store_jobs_dev": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _vp, C.c_int, _vp, _vp, _vp]),
     "sfe_icp_store_compute": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp_store_compute_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                  C.c_int, C.POINTER(IcpDpf), C.c_int, _vp, _i32p, _f32p, C.c_int, _f32p,
+                                                  _i32p, _i32p]),
     "sfe_cloud_store_overlap": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, C.c_int, _i32p]),
     "sfe_feature_extract_ping_store": (C.c_int, [_vp, _vp, _vp, C.c_int64, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_double, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int64, C.c_int,

@@ -31,6 +31,7 @@ import math
 import numpy as np
 
 from . import _lib as _L
+from . import icp_config as _cfg
 from . import store as _store
 
 
@@ -134,7 +135,8 @@ class SessionBatch(object):
         from .pipeline import KeyframeBatch
         self.ctx, self.S, self.K = ctx, int(n_sessions), int(n_steps)
         self.icp_params = icp_params
-        self.kb = KeyframeBatch(ctx, geometry, cfar_params, alg, intensity_thr, icp_params, self.S, max_points=max_points)
+        self.kb = KeyframeBatch(ctx, geometry, cfar_params, alg, intensity_thr, self._kb_params(), self.S,
+                                max_points=max_points)
         self.frame_bytes = self.kb.rows * self.kb.cols
         self._kb_img = self.kb.d_img                     # (kept for free(): the batch's own frame buffer is unused)
         self.d_frames = ctx.alloc(self.K * self.S * self.frame_bytes)
@@ -159,6 +161,24 @@ class SessionBatch(object):
                            "replayed": 0, "replay_fallbacks": 0, "transforms_s": 0.0, "table_s": 0.0, "grids_s": 0.0}
         self.reset()
 
+    @property
+    def icp_params(self):
+        """the chain of the scan matches: an ``IcpParams`` or an ``icp_config.IcpChain`` (its data-point filters and
+        outlier filters / checker run through ``store.icp``); assignable between runs"""
+        return self._icp
+
+    @icp_params.setter
+    def icp_params(self, params_or_chain):
+        if not isinstance(params_or_chain, (_L.IcpParams, _cfg.IcpChain)):
+            raise TypeError("SessionBatch: icp_params must be an IcpParams or an icp_config.IcpChain, got %s"
+                            % type(params_or_chain).__name__)
+        self._icp = params_or_chain
+
+    def _kb_params(self):
+        """what KeyframeBatch takes: the IcpParams of the chain"""
+        p = self._icp
+        return p.params if isinstance(p, _cfg.IcpChain) else p
+
     def upload_frames(self, k, frames):
         """pings of step k: [S x rows x cols] uint8"""
         frames = np.ascontiguousarray(frames, np.uint8)
@@ -174,7 +194,7 @@ class SessionBatch(object):
             return self.kb.cap
         old = self.kb
         old.d_img = self._kb_img
-        self.kb = KeyframeBatch(self.ctx, old.geom, (old.train_hs, old.guard_hs, old.tau), "SOCA", 0, self.icp_params, self.S,
+        self.kb = KeyframeBatch(self.ctx, old.geom, (old.train_hs, old.guard_hs, old.tau), "SOCA", 0, self._kb_params(), self.S,
                                 max_points=8192)
         self.kb.alg, self.kb.k, self.kb.intensity_thr = old.alg, old.k, old.intensity_thr
         self._kb_img = self.kb.d_img
@@ -193,6 +213,8 @@ class SessionBatch(object):
         kb.d_img = _View(self.d_frames, k * S * self.frame_bytes)
         kb.run_cfar()
         kb.run_extract()
+        # (nothing between these two: run_filter reads the staging slots run_extract filled, and an octree stage of a
+        #  chain's ICP rewrites them -- the scan matches below come after it)
         kb.run_filter(self.resolution, self.outlier_radius, self.outlier_min_points)
         src_h = kb.store_clouds(store, stamps=np.arange(S) * self.K + k)
         self.handles[:, k] = src_h

@@ -619,4 +619,35 @@ int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const 
     });
 }
 
+// The chain over store handles: the stages read the store's pool in place (both sides, every distinct handle of a side
+// once), the job table is rebuilt on the filtered pools like sfe_icp_compute_jobs_chain's.
+int sfe_icp_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf,
+                                    sfe_cloud_store *s, const int32_t *pairs, const float *guesses9, int n_jobs,
+                                    float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_with_outliers(ctx, o, [&]() -> int {
+        if (n_rd == 0 && n_rf == 0)
+            return sfe_icp_store_compute(ctx, p, s, pairs, guesses9, n_jobs, T_out9, status, iters);
+        if (int rc = sfe_use(ctx))
+            return rc;
+        SFE_ARG(ctx, p && s && sfe_store_ctx(s) == ctx && n_jobs >= 0 &&
+                         (n_jobs == 0 || (pairs && guesses9 && T_out9 && status)));
+        if (int rc = dpf_check(ctx, rd, n_rd))
+            return rc;
+        if (int rc = dpf_check(ctx, rf, n_rf))
+            return rc;
+        if (n_jobs == 0)
+            return 0;
+        std::vector<int32_t> jobs4;
+        if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
+            return rc;
+        SfeStoreView v;
+        if (int rc = sfe_store_view(s, &v))
+            return rc;
+        const float *pool = (const float *)v.d_pool;
+        return dpf_icp_jobs(ctx, p, rd, n_rd, rf, n_rf, pool, pool, jobs4.data(), guesses9, n_jobs, T_out9, status, iters);
+    });
+}
+
 } // extern "C"

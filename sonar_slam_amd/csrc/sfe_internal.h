@@ -177,6 +177,9 @@ struct SfeStoreView {
     int n_slots;
 };
 int sfe_store_view(sfe_cloud_store *s, SfeStoreView *v);
+// n_jobs (source, target) handle pairs -> the ICP job table over the store's pool, refused like sfe_icp_store_compute
+// refuses them (a handle outside the store, an empty or failed cloud); syncs the host mirror of the slot table first
+extern "C" int sfe_store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4);
 
 // sfe_downsample.hip: pcl.downsample with indices on a device-resident cloud of any size (rank sort in global memory)
 struct SfeDsHeader {

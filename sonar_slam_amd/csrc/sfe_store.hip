@@ -1070,8 +1070,8 @@ int sfe_cloud_store_match_keys(sfe_ctx *ctx, sfe_cloud_store *s, int32_t source,
     return 0;
 }
 
-// jobs over handles -> the job table of the ICP launcher (sizes from the mirrored slot table)
-static int store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4)
+// jobs over handles -> the job table of the ICP launcher (sizes from the mirrored slot table; sfe_internal.h)
+int sfe_store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4)
 {
     sfe_ctx *ctx = s->ctx;
     if (int rc = store_sync_meta(s))
@@ -1103,7 +1103,7 @@ int sfe_icp_store_jobs_dev(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_stor
     if (n_jobs == 0)
         return 0;
     std::vector<int32_t> jobs4;
-    if (int rc = store_jobs4(s, pairs, n_jobs, jobs4))
+    if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
         return rc;
     return sfe_icp_jobs_dev(ctx, p, (const float *)s->d_pool, (const float *)s->d_pool, jobs4.data(), d_guess9, n_jobs, d_T9,
                             d_status, d_iters);
@@ -1118,7 +1118,7 @@ int sfe_icp_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store
     if (n_jobs == 0)
         return 0;
     std::vector<int32_t> jobs4;
-    if (int rc = store_jobs4(s, pairs, n_jobs, jobs4))
+    if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
         return rc;
     const size_t b_g = sizeof(float) * 9 * (size_t)n_jobs, b_out = (sizeof(float) * 9 + 2 * sizeof(int32_t)) * (size_t)n_jobs;
     float *d_g = (float *)sfe_scratch(ctx, 2, b_g);

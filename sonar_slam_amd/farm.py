@@ -138,15 +138,25 @@ def _chunk_slab(jobs4, lo_col, n_col):
     return lo, hi
 
 
+def is_chain_dict(params_dict):
+    """True for what ``IcpChain.as_dict()`` makes, False for ``IcpParams.as_dict()``"""
+    return "params" in params_dict
+
+
 def _hip_compute(device, params_dict, tuning=None):
     """the product backend of a farm worker: one sfe_ctx on `device` (launcher knobs `tuning`: sfe_tune), chunks of the
-    job table through sfe_icp_compute_jobs (no CPU fallback: without the library or a gfx950 device this raises)"""
-    from . import _lib, pcl
+    job table through pcl.ICP.compute_jobs (no CPU fallback: without the library or a gfx950 device this raises).
+    ``params_dict``: ``IcpParams.as_dict()``, or ``IcpChain.as_dict()`` for a chain farm (installed with setChain; its
+    filters run per cloud, so rebasing the job table per chunk changes nothing)"""
+    from . import _lib, icp_config, pcl
     ctx = _lib.Context(device)
     for name, value in (tuning or {}).items():
         ctx.tune(name, value)
     icp = pcl.ICP(ctx)
-    icp.setParams(_lib.IcpParams(**params_dict))
+    if is_chain_dict(params_dict):
+        icp.setChain(icp_config.IcpChain.from_dict(params_dict))
+    else:
+        icp.setParams(_lib.IcpParams(**params_dict))
 
     def run(v, chunk):
         n = len(v["jobs4"])
@@ -171,7 +181,7 @@ def _farm_worker(device, params_dict, tuning, backend, conn):
         os.environ["HSA_ENABLE_IPC_MODE_LEGACY"] = os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         if backend is None:
             name, run = _hip_compute(device, params_dict, tuning)
-        else:  # test hook: "module:function" -> (name, run) like _hip_compute
+        else:  # test hook: "module:function" -> (name, run) like _hip_compute; it gets the same params_dict
             mod, fn = backend.split(":")
             name, run = getattr(importlib.import_module(mod), fn)(device, params_dict)
         conn.send(("ready", name))
@@ -223,10 +233,16 @@ class _Worker(object):
 class IcpFarm(object):
     """Farm (source, target, [guesses]) jobs over ``devices`` (default: every visible GPU): job j -> worker
     j mod G.  The worker processes start on the first ``run`` (or ``start()``) and live until ``close()``;
-    use it as a context manager.  ``tuning``: launcher knobs (``Context.tuning``) set in every worker's context."""
+    use it as a context manager.  ``tuning``: launcher knobs (``Context.tuning``) set in every worker's context.
+
+    ``params``: an ``IcpParams`` (workers receive ``params.as_dict()``) or an ``icp_config.IcpChain`` (workers receive
+    ``chain.as_dict()`` and install it with ``setChain``).  A ``_backend`` hook ``fn(device, params_dict)`` gets that
+    same dict: ``farm.is_chain_dict`` tells the two apart, ``IcpChain.from_dict`` rebuilds the chain."""
 
     def __init__(self, params, devices=None, chunk=CHUNK, tuning=None, _backend=None):
-        from . import _lib
+        from . import _lib, icp_config
+        if not isinstance(params, (_lib.IcpParams, icp_config.IcpChain)):
+            raise TypeError("IcpFarm: expected an IcpParams or an icp_config.IcpChain, got %s" % type(params).__name__)
         self.params = params
         if devices is None:
             devices = list(range(_lib.device_count()))

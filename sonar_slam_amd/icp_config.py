@@ -25,8 +25,9 @@ silently ignoring a filter would change the pose):
     logger             NullLogger
 
 The outlier filters and the checker only ``parse_icp_chain`` takes live in ``IcpChain.outliers`` (``IcpOutliers``, the
-mirror of ``sfe_icp_outliers``; its comment in include/sonarfe.h states their rules), not in ``IcpParams``: the farm,
-store, chained and replay paths keep running chains without them.
+mirror of ``sfe_icp_outliers``; its comment in include/sonarfe.h states their rules), not in ``IcpParams``.  Every
+route ICP takes runs the whole chain: ``pcl.ICP``, ``store.CloudStore.icp``, ``replay.FrontEnd``,
+``chained.SessionBatch`` and ``farm.IcpFarm`` all accept an ``IcpChain`` (the farm sends ``IcpChain.as_dict()``).
 
 Data-point filters, restated from libpointmatcher's published ICP::compute / computeWithTransformedReference and
 the filters' sources (UNPINNED, like the rest of pcl.cpp's third-party behaviour; tools/pin_thirdparty.py writes
@@ -241,6 +242,50 @@ class IcpChain(object):
 
     def has_filters(self):
         return any(isinstance(s, IcpDpf) for s in self.reading + self.reference)
+
+    def has_modules(self):
+        """True when the chain lists anything ``IcpParams`` cannot carry: a data-point filter the device runs, or an
+        outlier filter / checker of ``outliers``"""
+        return self.has_filters() or self.outliers.any()
+
+    def as_dict(self):
+        """plain, picklable values (what a farm worker receives); ``IcpChain.from_dict`` rebuilds the chain exactly"""
+        return {"params": self.params.as_dict(), "reading": [_stage_dict(s) for s in self.reading],
+                "reference": [_stage_dict(s) for s in self.reference], "outliers": self.outliers.as_dict()}
+
+    @staticmethod
+    def from_dict(d):
+        return IcpChain(IcpParams(**d["params"]), [_stage_of(x) for x in d["reading"]],
+                        [_stage_of(x) for x in d["reference"]], IcpOutliers(**d["outliers"]))
+
+    def __eq__(self, other):
+        return isinstance(other, IcpChain) and self.as_dict() == other.as_dict()
+
+    def __ne__(self, other):
+        return not self == other
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "IcpChain(%r)" % (self.as_dict(),)
+
+
+def _stage_dict(st):
+    if isinstance(st, SurfaceNormalStage):
+        return {"stage": "SurfaceNormal", "knn": st.knn}
+    return {"stage": "dpf", "kind": st.kind, "dim": st.dim, "remove_inside": st.remove_inside, "f": list(st.f)}
+
+
+def _stage_of(d):
+    if d["stage"] == "SurfaceNormal":
+        return SurfaceNormalStage(d["knn"])
+    if d["stage"] != "dpf":
+        raise IcpConfigError("unknown chain stage %r" % (d["stage"],))
+    st = IcpDpf()
+    st.kind, st.dim, st.remove_inside = d["kind"], d["dim"], d["remove_inside"]
+    for i, v in enumerate(d["f"]):
+        st.f[i] = v
+    return st
 
 
 _RANDOM = {"RandomSamplingDataPointsFilter", "MaxPointCountDataPointsFilter", "MaxDensityDataPointsFilter"}

@@ -131,7 +131,15 @@ class FrontEnd(object):
         self.shgo_replay = shgo_replay      # FrontEnd.shgo: replay of shgo's decisions from one table of costs (shgo_fast.py)
         self.store = store          # CloudStore: keyframe clouds stay on the device (feed_handle)
         self.icp = pcl.ICP(ctx)
-        self.icp.setParams(icp_params if icp_params is not None else icp_config.shipped_params())
+        if icp_params is None:
+            icp_params = icp_config.shipped_params()
+        if isinstance(icp_params, icp_config.IcpChain):
+            self.icp.setChain(icp_params)
+        elif isinstance(icp_params, _L.IcpParams):
+            self.icp.setParams(icp_params)
+        else:
+            raise TypeError("FrontEnd: icp_params must be an IcpParams or an icp_config.IcpChain, got %s"
+                            % type(icp_params).__name__)
         self.backend = backend or ChainBackend()
         self.keyframe_duration = keyframe_duration
         self.keyframe_translation = keyframe_translation
@@ -198,10 +206,21 @@ class FrontEnd(object):
             all_points.append(Keyframe.transform_points(self.keyframes[key].points, transf))
         return pcl.downsample(np.concatenate(all_points), self.point_resolution)
 
+    def _store_chain(self):
+        """the chain installed on ``self.icp`` (``loadFromYaml`` / ``setChain`` / ``setParams``, also after construction),
+        for ``store.icp``: the store path runs what ``self.icp.compute`` would"""
+        params = self.icp._chain()          # (the "compute before loadFromYaml / setParams" error)
+        chain = self.icp.chain
+        if chain is None:
+            return params
+        if chain.params is not params:      # (ICP.params replaced by hand: pcl.ICP runs it with the chain's modules)
+            chain = icp_config.IcpChain(params, chain.reading, chain.reference, chain.outliers)
+        return chain
+
     def compute_icp(self, source_points, target_points, guess):
         """slam.py:294-323"""
         if self.store is not None:
-            T, st, _ = self.store.icp(self.icp._chain(), [(source_points.handle, target_points.handle)],
+            T, st, _ = self.store.icp(self._store_chain(), [(source_points.handle, target_points.handle)],
                                       [pcl.ICP._guess(guess.matrix())])
             message, T = _L.ICP_STATUS_MESSAGES.get(int(st[0]), "ICP failure %d" % st[0]), T[0]
             x, y = T[:2, 2]
@@ -224,7 +243,7 @@ class FrontEnd(object):
         if not len(guesses):
             return "Too few samples for covariance computation", None, None, None
         if self.store is not None:
-            Ts, st, _ = self.store.icp(self.icp._chain(), [(source_points.handle, target_points.handle)] * len(guesses),
+            Ts, st, _ = self.store.icp(self._store_chain(), [(source_points.handle, target_points.handle)] * len(guesses),
                                        [pcl.ICP._guess(g.matrix()) for g in guesses])
             ok = np.asarray(st) == 0
         else:

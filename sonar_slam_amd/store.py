@@ -12,6 +12,7 @@ import ctypes as _C
 import numpy as np
 
 from . import _lib as _L
+from . import icp_config as _cfg
 
 NEGATE_Y = 1        # SFE_STORE_NEGATE_Y: store (x, -y), what slam_ros.py:170 makes of the feature message
 F32_POINTS = 2      # SFE_STORE_F32_POINTS: transform like numpy does for float32 keyframe clouds (sgemm)
@@ -108,17 +109,38 @@ class CloudStore(object):
                 float(resolution), int(flags), None if st is None else _L.ptr(st, _C.c_int64), _L.ptr(out, _C.c_int32)))
         return out
 
-    def icp(self, params, pairs, guesses):
+    def icp(self, params_or_chain, pairs, guesses):
         """SLAM.compute_icp over handles: pairs [n x 2] = (source, target), guesses [n x 3 x 3]
-        -> (T [n x 3 x 3] float32, status [n], iterations [n])"""
+        -> (T [n x 3 x 3] float32, status [n], iterations [n]).
+
+        ``params_or_chain``: an ``IcpParams``, or an ``icp_config.IcpChain`` -- its data-point filters then run on the
+        stored clouds in place (every distinct handle of a side once per call) and its outlier filters / checker inside
+        the ICP loop, bit for bit what ``pcl.ICP`` with ``setChain`` computes on the same clouds (statuses 7, 8 and 9
+        included).  A chain with neither is its ``params``."""
+        chain = None
+        if isinstance(params_or_chain, _cfg.IcpChain):
+            chain, params = params_or_chain, params_or_chain.params
+        else:
+            params = params_or_chain
+        if not isinstance(params, _L.IcpParams):
+            raise TypeError("CloudStore.icp: expected an IcpParams or an icp_config.IcpChain, got %s"
+                            % type(params_or_chain).__name__)
         pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         n = len(pairs)
         g = np.ascontiguousarray(np.asarray(guesses, np.float32).reshape(n, 9))
         T, st, it = np.zeros((n, 3, 3), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
         with self.ctx.lock:
-            self.ctx._check(self.ctx.lib.sfe_icp_store_compute(
-                self.ctx.handle, _C.byref(params), self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(g, _C.c_float), n,
-                _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            if chain is None or not chain.has_modules():
+                self.ctx._check(self.ctx.lib.sfe_icp_store_compute(
+                    self.ctx.handle, _C.byref(params), self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(g, _C.c_float), n,
+                    _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+            else:
+                rd, n_rd = chain.device_stages(chain.reading)
+                rf, n_rf = chain.device_stages(chain.reference)
+                ox = _C.byref(chain.outliers) if chain.outliers.any() else None
+                self.ctx._check(self.ctx.lib.sfe_icp_store_compute_chain_ext(
+                    self.ctx.handle, _C.byref(params), ox, rd, n_rd, rf, n_rf, self.handle, _L.ptr(pairs, _C.c_int32),
+                    _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
         return T, st, it
 
     def overlap(self, pairs, T6, max_dist, flags=0):
