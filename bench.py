@@ -12,6 +12,11 @@ FeatureExtraction.callback), and B scan pairs (5000 x 5000 points) through the 3
 2-D point-to-plane ICP (BASELINE.json configs[1]).  Every rank owns one GPU and its own B jobs
 (weak scaling, no data-path collective; torch.distributed/gloo is control plane only: barrier
 and the max-over-ranks time).  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline figure needs: set-up, warm-up, the timed steps, --dump-outputs if given,
+and the line (`value`, `ms_per_step` and `config`).  --full adds everything else the bench measures or checks, as it did
+before the option existed: the CPU baseline, the oracle parity sample of the timed batch, per-stage times, rooflines and
+the counted ICP utilisation, the legs of tools/bench_legs.py, live latency and the farm leg.
 """
 import argparse
 import json
@@ -38,16 +43,19 @@ def parse():
                     help="keyframes per step per GPU (512 = one scan match per workgroup slot of the 256 CUs: every job's "
                          "tail is exposed; with several times more the dispatcher refills slots as jobs finish: -15 %% per job at 2048, "
                          "-19 %% at 4096)")
-    ap.add_argument("--cfar-frames", type=int, default=1024, help="frames per launch for the CFAR roofline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline figure as well: CPU baseline, parity sample, "
+                         "per-stage times and rooflines, legs, live latency, farm (the options below marked --full)")
+    ap.add_argument("--cfar-frames", type=int, default=1024, help="frames per launch for the CFAR roofline leg (--full)")
     ap.add_argument("--inflight", type=int, default=1,
                     help="keyframe batches in flight per GPU: consecutive steps alternate between this many resident "
                          "batches, each on its own context (stream + scratch), so the front end and the ICP preparation "
                          "of step k+1 fill the CUs the iteration kernel of step k leaves idle (default 1 = one batch, serial; "
                          "measured on MI355X: 114.6 k keyframes/s with 1, 116.3 k with 2, 118.9 k with 3)")
-    ap.add_argument("--cfar-launches", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cfar-launches", type=int, default=20, help="launches per timing of the CFAR roofline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (--full)")
     ap.add_argument("--cpu-keyframes", type=int, default=0,
-                    help="CPU-baseline keyframes per host core (0 = about 10 s of work per core)")
+                    help="CPU-baseline keyframes per host core (0 = about 10 s of work per core; --full)")
     ap.add_argument("--icp-mode", choices=["p2plane30", "reference"], default="p2plane30")
     ap.add_argument("--no-filters", action="store_true", help="leave pcl.downsample / remove_outlier out of the step")
     ap.add_argument("--max-points", type=int, default=32768,
@@ -55,16 +63,18 @@ def parse():
                          "19 122): the 8-rank launch of round 6 found rank 3 raising at the 16384 of rounds 1-5.  The resident "
                          "filters pick their sort per frame, so the capacity only sizes buffers")
     ap.add_argument("--parity-jobs", type=int, default=64,
-                    help="keyframes of the timed batch re-computed by the oracle after the timed region (0 = skip)")
-    ap.add_argument("--no-farm", action="store_true", help="skip the BASELINE configs[3] leg (job farm on this device)")
-    ap.add_argument("--farm-jobs", type=int, default=10000)
-    ap.add_argument("--no-latency", action="store_true", help="skip the live single-ping / single-scan-match latency leg")
+                    help="keyframes of the timed batch re-computed by the oracle after the timed region (0 = skip; --full)")
+    ap.add_argument("--no-farm", action="store_true", help="skip the BASELINE configs[3] leg (job farm on this device; --full)")
+    ap.add_argument("--farm-jobs", type=int, default=10000, help="jobs of the farm leg (--full)")
+    ap.add_argument("--no-latency", action="store_true",
+                    help="skip the live single-ping / single-scan-match latency leg (--full)")
     ap.add_argument("--distinct-frames", type=int, default=256,
                     help="distinct synthetic pings behind the batch's frames (tiled to --batch); beyond the first 32 they are "
                          "screened on the device, untimed: a ping with more points than the batch's capacity is left out")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the legs beyond the timed step: reference_chain, real_size, configs4_hires, float_oracle, stream_frames")
-    ap.add_argument("--small-legs", action="store_true", help="those legs at a fraction of their size (tests)")
+                    help="skip the legs beyond the timed step: reference_chain, real_size, configs4_hires, float_oracle, "
+                         "stream_frames (--full)")
+    ap.add_argument("--small-legs", action="store_true", help="those legs at a fraction of their size (tests; --full)")
     ap.add_argument("--serial-prep", action="store_true",
                     help="keep the ICP target preparation on the main stream (default: side stream, next to the front end)")
     ap.add_argument("--dump-outputs", metavar="DIR",
@@ -393,7 +403,7 @@ def main():
     det = CFAR(40, 10, 0.1, 10)                      # feature.yaml:3-7
     frames, srcs, tgts, guesses = make_inputs(rank, args.batch)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # contract: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # contract: rank 0 at N=1 only
         # before any HIP call: the worker processes are forked and must not inherit a live GPU context
         from types import SimpleNamespace
         from sonar_slam_amd.feature_extraction import build_maps
@@ -485,8 +495,9 @@ def main():
         dt = float(t[0])
     res = kb_last.results()
     ok = int((res["status"] == 0).sum())
+    iters_total = int(res["iters"].sum())
     parity = None
-    if rank == 0 and args.parity_jobs > 0:   # the timed step's own outputs, before anything overwrites them
+    if args.full and rank == 0 and args.parity_jobs > 0:   # the timed step's own outputs, before anything overwrites them
         parity = parity_check(kb_last, res, frames, srcs, tgts, guesses, det, fe, args.icp_mode, not args.no_filters,
                               args.parity_jobs)
     if rank == 0 and args.dump_outputs:      # also before the legs below reuse the batch's buffers
@@ -494,6 +505,23 @@ def main():
 
     out = None
     if rank == 0:
+        value = args.batch * args.steps * world / dt
+        out = {
+            "metric": "keyframes/sec (CFAR+ICP) on 512x1024 sonar, 5k-pt pairs",
+            "value": value, "unit": "keyframes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "u8 (CFAR, integer-exact) + f32/f64-accumulate (ICP)", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[1]: %d keyframes/step/GPU = 1024x512 SOCA-CFAR(Ntc40,Ngc10)+gate65"
+                                   " -> remap+nonzero+px2m%s -> 5000x5000-pt ICP (%s)"
+                                   % (args.batch, "" if args.no_filters else " -> downsample 0.5 -> remove_outlier 1.0/5",
+                                      args.icp_mode),
+                       "batch_per_gpu": args.batch, "distinct_frames": n_distinct, "screened_out_pings": n_screened, "icp_mode": args.icp_mode, "parallelism": "job farm x%d" % world,
+                       "icp_prep_stream": "main" if args.serial_prep else "side", "batches_in_flight": n_inflight,
+                       "icp_converged_jobs": ok, "mean_icp_iters": iters_total / float(args.batch),
+                       "mean_points_per_frame": float(res["counts"].mean()),
+                       "max_points_per_frame": int(res["counts"].max()), "points_capacity": kb.cap,
+                       "full": args.full}}
+    if rank == 0 and args.full:
         # ---- per-stage time and rooflines, HIP events on the stream the kernels run on ----
         def timed(fn, reps):
             fn()
@@ -509,7 +537,6 @@ def main():
         pt_bytes = 8.0 if (kb.staged and not kb.points64) else 16.0
         extract_bytes = float(args.batch) * ROWS * COLS / (8.0 if kb.bit_masks else 1.0) + pt_bytes * float(res["counts"].sum())
         ms_icp_b = timed(kb.run_icp, 2)
-        iters_total = int(res["iters"].sum())
         icp_kernel = icp_utilisation(ctx, kb, ms_icp_b, iters_total, args.batch)
 
         # CFAR roofline leg: a batch larger than the 256 MiB Infinity Cache, one kernel per launch
@@ -593,21 +620,7 @@ def main():
             except (OSError, KeyError, ValueError):
                 pass
 
-        value = args.batch * args.steps * world / dt
-        out = {
-            "metric": "keyframes/sec (CFAR+ICP) on 512x1024 sonar, 5k-pt pairs",
-            "value": value, "unit": "keyframes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8 (CFAR, integer-exact) + f32/f64-accumulate (ICP)", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[1]: %d keyframes/step/GPU = 1024x512 SOCA-CFAR(Ntc40,Ngc10)+gate65"
-                                   " -> remap+nonzero+px2m%s -> 5000x5000-pt ICP (%s)"
-                                   % (args.batch, "" if args.no_filters else " -> downsample 0.5 -> remove_outlier 1.0/5",
-                                      args.icp_mode),
-                       "batch_per_gpu": args.batch, "distinct_frames": n_distinct, "screened_out_pings": n_screened, "icp_mode": args.icp_mode, "parallelism": "job farm x%d" % world,
-                       "icp_prep_stream": "main" if args.serial_prep else "side", "batches_in_flight": n_inflight,
-                       "icp_converged_jobs": ok, "mean_icp_iters": iters_total / float(args.batch),
-                       "mean_points_per_frame": float(res["counts"].mean()),
-                       "max_points_per_frame": int(res["counts"].max()), "points_capacity": kb.cap},
+        out.update({
             # achieved / frac are priced on the bytes that cross the pins.  The kernel of the timed step
             # stores its detections as bits: per pixel it reads 1 B and writes 1 bit, so ITS algorithmic bytes are 1.125 B
             # per pixel (measured traffic = 1.03 x that), and at that figure it is limited by VALU issue, not by
@@ -670,7 +683,7 @@ def main():
                                  "note": "algorithmic bytes = the R*B detections (bits when CFAR hands over bit streams) + `point_bytes` per point per frame (16: float64 pairs; 8: the float32 pairs of the staged hand-over to the filters); the kernels are "
                                          "bound by gathers into the inverse remap table (10 MB of 4-byte entries, four candidates per 16-byte read), not "
                                          "by streaming"},
-        }
+        })
         out["roofline"]["extract_frac"] = out["roofline_extract"]["frac"]      # (flat copies: see the note at `chained` below)
         if filters_bytes is not None:
             out["roofline"]["filters_frac"] = filters_bytes / (ms_filter_b * 1e-3) / 1e9 / HBM_PEAK_GBS

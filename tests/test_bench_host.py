@@ -21,6 +21,14 @@ def test_inputs_have_the_baseline_shapes():
     assert not np.array_equal(frames, f2) and not np.array_equal(srcs[0], s2[0])
 
 
+def test_full_is_off_unless_asked_for(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse()
+    assert not a.full and (a.steps, a.warmup) == (3, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full
+
+
 def test_usable_cores_is_sane():
     n = bench.usable_cores()
     assert 1 <= n <= (os.cpu_count() or 1)

@@ -5,7 +5,7 @@ as its brute-force scan, tests/test_oracle_pipeline.py; 0.3 s per 20k x 20k x 30
               (the NSSM batch of slam.py:346-358 at slam.yaml's cov_samples = 30)
   configs[3]  the job farm: a few hundred independent 5 000 x 5 000 scan matches through farm.IcpFarm
               (persistent worker, shared-memory job blocks), every one against the oracle
-  configs[1]  bench.py end to end with its own parity sample, and the 2-rank launch on one device
+  configs[1]  bench.py --full end to end with its own parity sample, and the 2-rank launch on one device
 
 Tolerances.  Against the oracle with fp64 sums (same discrete decisions): identical status and iteration counts, pose
 within 1e-6 (point-to-point) / 1e-4 (point-to-plane).  Against the oracle in float (PointMatcher<float>): 1e-4 m / rad
@@ -141,10 +141,11 @@ def test_resident_batch_refuses_a_frame_above_its_point_capacity(ctx):
     big.free()
 
 
-def _bench(extra, env=None, launcher=(), legs=False):
+def _bench(extra, env=None, launcher=(), legs=False, full=True):
     cmd = [sys.executable] + list(launcher) + [os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
                                                "--batch", "16", "--cfar-frames", "64", "--cfar-launches", "2",
-                                               "--no-cpu-baseline"] + ([] if legs else ["--no-legs"]) + extra
+                                               "--no-cpu-baseline"] + ([] if legs else ["--no-legs"]) + \
+        (["--full"] if full else []) + extra
     e = dict(os.environ)
     e.update(env or {})
     r = subprocess.run(cmd, cwd=ROOT, env=e, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -163,12 +164,15 @@ def test_bench_line_carries_its_own_parity_sample():
 
 
 def test_bench_dumps_what_its_last_timed_step_computed(tmp_path):
-    """--dump-outputs: float32 / float64 arrays of the last timed step, under 64 MB; the sampled frames' masks, points
-    and filtered clouds are the oracle's on the bench's own inputs, the counts agree with them"""
+    """--dump-outputs of a plain run: float32 / float64 arrays of the last timed step, under 64 MB; the sampled frames'
+    masks, points and filtered clouds are the oracle's on the bench's own inputs, the counts agree with them.  The plain
+    line carries the headline figure and `config`, and leaves every leg and check to --full"""
     import bench
     d = str(tmp_path / "dump")
-    out = _bench(["--gpus", "1", "--parity-jobs", "2", "--no-latency", "--no-farm", "--dump-outputs", d])
+    out = _bench(["--gpus", "1", "--parity-jobs", "2", "--no-latency", "--no-farm", "--dump-outputs", d], full=False)
     assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert abs(out["value"] - 16 * 2 / (out["ms_per_step"] * 2e-3)) < 1e-6 * out["value"] and out["config"]["full"] is False
+    assert not {"parity_check", "roofline", "icp_kernel", "stage_ms_per_step", "cpu_baseline"} & set(out)
     got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
     assert all(a.dtype in (np.float32, np.float64) for a in got.values())
     assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
