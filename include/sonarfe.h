@@ -610,6 +610,49 @@ int sfe_shgo_sobol_replay(int n_vertices, const int32_t *nn_off, const int32_t *
 int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_xycs, int n_sessions, const double *delta_xycs,
                                 int n_deltas, float *T6_out);
 
+/* ---- replaces: the log-odds occupancy grid of bruce_slam/mapping.py (method 1: add_keyframe, update_pose, fit_grid,
+ * inc_grid / dec_grid, adjust_bounds, get_occupancy_grid1); sonar_slam_amd/mapping.py is the host side.  One sfe_map per
+ * Mapping owns the device state: the float32 grid [rows x cols], the sonar_xy table of every geometry, and per keyframe slot
+ * its polar log-odds image and its current cell list (r, c, l in ascending r * cols + c).  Entry points take host pointers.
+ *   sfe_map_geometry: sonar_xy [img_rows * img_cols][2] float32 (mapping.py:158-163) -> geometry id.
+ *   sfe_map_set_logodds: a ready log-odds image [img_rows * img_cols] for `slot` (created for `geom` on first use).
+ *   sfe_map_measure: n keyframes at once: slot / geometry, hits [2 * hit_off[n]] (row, col of the downsampled image; keyframe b
+ *     owns [hit_off[b], hit_off[b + 1])), hrhc[2 b] = hr, hc (hr < 0: no points, all miss_prob), its float32 kernel
+ *     (2 hr + 1) x (2 hc + 1) at ktab + k_off[b], div[b] = kernel[hr, hc] / hit_prob; logit of miss32 / hit32 as the host
+ *     computes it.  sfe_map_measure_stages reads keyframe b of the last call: hit mask, the image before logit, first hits.
+ *   sfe_map_fit_bounds: per keyframe {min r, max r, min c, max c} of its pixels fitted with pose4 = {cos, sin, x, y} at
+ *     origin2 = {y0, x0} (one synchronisation).
+ *   sfe_map_grow: pad the grid by rows on top / bottom and columns left / right (existing cells keep their values).
+ *   sfe_map_refit: fit, deduplicate (first pixel per cell) and apply n keyframes in order: for each, subtract its current
+ *     list if dec[b], then add the new one.  mm = the bounds sfe_map_fit_bounds gave at the same origin, shift2 = {rows,
+ *     cols} added to the fitted cells to reach the grid's current coordinates.  Enqueue only; a slot at most once per call.
+ *   sfe_map_cells / sfe_map_logodds / sfe_map_read_grid: read back (which = 1: the grid of the last sfe_map_frames call);
+ *     sfe_map_shape -> {rows, cols, rows grown on top, columns grown on the left}.
+ *   sfe_map_frames: a fresh grid, the listed slots added in list order.  sfe_map_render: rows r0..r1 x cols c0..c1 of a grid
+ *     -> int8(clip(100 expit(v), 0, 100)), resized INTER_NEAREST to out_h x out_w with source index floor(i * inv) when
+ *     resize != 0. */
+typedef struct sfe_map sfe_map;
+int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out);
+void sfe_map_destroy(sfe_map *m);
+int sfe_map_geometry(sfe_map *m, const float *sonar_xy, int img_rows, int img_cols, int *id_out);
+int sfe_map_set_logodds(sfe_map *m, int slot, int geom, const float *logodds);
+int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geoms, const int32_t *hit_off,
+                    const int32_t *hits, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
+                    const double *div, float miss32, float logit_miss, float hit32, float logit_hit);
+int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out);
+int sfe_map_fit_bounds(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
+                       double resolution, int32_t *mm_out);
+int sfe_map_grow(sfe_map *m, int top, int bottom, int left, int right);
+int sfe_map_refit(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2, double resolution,
+                  const int32_t *mm, const int32_t *shift2, const uint8_t *dec);
+int sfe_map_cells(sfe_map *m, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out);
+int sfe_map_logodds(sfe_map *m, int slot, float *out, int cap);
+int sfe_map_shape(sfe_map *m, int32_t *rows_cols_grow4);
+int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap);
+int sfe_map_frames(sfe_map *m, int n, const int32_t *slots);
+int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
+                   int8_t *occ_out);
+
 #ifdef __cplusplus
 }
 #endif

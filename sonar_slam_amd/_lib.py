@@ -251,6 +251,24 @@ SIGNATURES = {
     "sfe_cloud_store_set_selection": (C.c_int, [_vp, _vp, C.c_int32, _u8p, C.c_int]),
     "sfe_cloud_store_compact_selected": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, _i32p]),
     "sfe_cloud_store_match_keys": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_int32, C.c_float, C.c_int, C.c_int, _i32p, _i32p]),
+    "sfe_map_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "sfe_map_destroy": (None, [_vp]),
+    "sfe_map_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_map_set_logodds": (C.c_int, [_vp, C.c_int, C.c_int, _f32p]),
+    "sfe_map_measure": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, C.c_int, _f64p,
+                                  C.c_float, C.c_float, C.c_float, C.c_float]),
+    "sfe_map_measure_stages": (C.c_int, [_vp, C.c_int, _u8p, _f32p, _i32p]),
+    "sfe_map_fit_bounds": (C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, C.c_double, _i32p]),
+    "sfe_map_grow": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sfe_map_refit": (C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, C.c_double, _i32p, _i32p, _u8p]),
+    "sfe_map_cells": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _f32p, C.c_int,
+                                C.POINTER(C.c_int)]),
+    "sfe_map_logodds": (C.c_int, [_vp, C.c_int, _f32p, C.c_int]),
+    "sfe_map_shape": (C.c_int, [_vp, _i32p]),
+    "sfe_map_read_grid": (C.c_int, [_vp, C.c_int, _f32p, C.c_longlong]),
+    "sfe_map_frames": (C.c_int, [_vp, C.c_int, _i32p]),
+    "sfe_map_render": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+                                 C.POINTER(C.c_int8)]),
 }
 
 _lib = None

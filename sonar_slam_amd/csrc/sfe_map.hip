@@ -1,0 +1,839 @@
+// Log-odds occupancy map of bruce_slam's mapping.py (method 1) on the device: the polar measurement image of a keyframe,
+// the fit of its pixels to grid cells, and the ordered add / subtract of its cells on a float32 grid (sonar_slam_amd/mapping.py
+// is the host side: control flow, growth decisions, everything O(keyframes)).
+//
+// State of one map (sfe_map): the grid [rows x cols] float32, the sonar_xy table of every geometry, and per keyframe slot its
+// polar log-odds image and its cell list (r, c uint16 + l float32, ascending r * cols + c).  Cell lists are double-buffered:
+// a refit writes the new list next to the old one, subtracts the old, adds the new, and flips.  Growth pads the grid and
+// bumps two counters; a list keeps the counters it was written at, and its cells are shifted by the difference when read.
+#include <climits>
+#include <cstring>
+
+#include "sfe_internal.h"
+
+namespace {
+
+constexpr int MAP_THREADS = 256;
+constexpr int COMPACT_THREADS = 1024;
+constexpr int32_t EMPTY_SLOT = INT_MAX;
+
+struct MapGeom {
+    float2 *d_xy = nullptr;
+    int img_rows = 0, img_cols = 0;
+};
+
+struct MapSlot {
+    int geom = -1;
+    float *d_logodds = nullptr;
+    uint16_t *d_r[2] = {nullptr, nullptr}, *d_c[2] = {nullptr, nullptr};
+    float *d_l[2] = {nullptr, nullptr};
+    int cur = 0;             // which buffer holds the current list
+    int has_cells = 0;
+    int base_r = 0, base_c = 0; // growth counters when the current list was written
+};
+
+// per keyframe of a measurement batch
+struct MeasJob {
+    int32_t slot_px;   // pixels of its image
+    int32_t img_rows, img_cols;
+    int32_t hit_off, n_hits; // its hits in the batch's hit table
+    int32_t hr, hc;    // kernel half sizes
+    int32_t k_off;     // its float32 kernel in the batch's kernel table ((2hr+1) x (2hc+1), row-major)
+    int64_t px_off;    // its pixels in the batch scratch (mask / probabilities)
+    double div;        // kernel[hr, hc] / hit_prob (float64, mapping.py:212)
+    float *logodds;    // the slot's image
+};
+
+// per keyframe of a fit batch
+struct FitJob {
+    const float2 *xy;
+    int32_t n_px;
+    double c, s, tx, ty;   // rotation and translation (host cos / sin of the pose's theta)
+    double y0, x0;         // grid origin at the time of the fit
+    int32_t wr0, wc0, wh, ww; // cell window = [wr0, wr0 + wh) x [wc0, wc0 + ww) in fit coordinates
+    int32_t sr, sc;        // shift of the fitted cells into the grid's current coordinates
+    int64_t win_off;       // its window in the slot scratch
+    const float *logodds;
+    uint16_t *out_r, *out_c;
+    float *out_l;
+    int32_t *out_n;
+};
+
+} // namespace
+
+struct sfe_map {
+    sfe_ctx *ctx = nullptr;
+    int rows = 0, cols = 0;
+    float *d_grid = nullptr;
+    float *d_frames = nullptr; // the grid of the last frames= render
+    int frames_rows = 0, frames_cols = 0;
+    int grow_r = 0, grow_c = 0;
+    std::vector<MapGeom> geoms;
+    std::vector<MapSlot> slots;
+    int32_t *d_counts = nullptr; // [slot][2]: cell count of each list buffer
+    int counts_cap = 0;
+    struct Buf {
+        void *p = nullptr;
+        size_t cap = 0;
+    } buf[6];
+    int last_meas_n = 0;
+    std::vector<MeasJob> last_meas;
+};
+
+namespace {
+
+void *map_buf(sfe_map *m, int i, size_t bytes)
+{
+    auto &b = m->buf[i];
+    if (b.cap >= bytes && b.p)
+        return b.p;
+    if (b.p) {
+        (void)hipStreamSynchronize(m->ctx->stream);
+        (void)hipFree(b.p);
+        b.p = nullptr;
+        b.cap = 0;
+    }
+    size_t cap = bytes + bytes / 4 + 256;
+    if (hipMalloc(&b.p, cap) != hipSuccess) {
+        b.p = nullptr;
+        return nullptr;
+    }
+    b.cap = cap;
+    return b.p;
+}
+
+// --- measurement (mapping.py:170-228) ---------------------------------------------------------------------------------
+__global__ void map_hits_kernel(const MeasJob *jobs, const int32_t *hits, uint8_t *mask)
+{
+    const MeasJob j = jobs[blockIdx.y];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < j.n_hits; i += gridDim.x * blockDim.x) {
+        const int r = hits[2 * (j.hit_off + i)], c = hits[2 * (j.hit_off + i) + 1];
+        if (r >= 0 && r < j.img_rows && c >= 0 && c < j.img_cols)
+            mask[j.px_off + (int64_t)r * j.img_cols + c] = 1;
+    }
+}
+
+// cv2.filter2D(mask, CV_32F, kernel, BORDER_CONSTANT) as a direct sum in the kernel's row-major order: the image holds 0 and 1,
+// so only the hits inside the window add (their coefficient, exactly), in that order; then / div in float64 and the clip.
+__global__ void map_filter_kernel(const MeasJob *jobs, const float *ktab, const uint8_t *mask, float *prob, float hit32)
+{
+    const MeasJob j = jobs[blockIdx.y];
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= j.slot_px)
+        return;
+    const int y = p / j.img_cols, x = p - y * j.img_cols;
+    const int kw = 2 * j.hc + 1;
+    const uint8_t *m = mask + j.px_off;
+    const float *k = ktab + j.k_off;
+    float s = 0.0f;
+    for (int i = 0; i <= 2 * j.hr; ++i) {
+        const int yy = y + i - j.hr;
+        if (yy < 0 || yy >= j.img_rows)
+            continue;
+        for (int jj = 0; jj < kw; ++jj) {
+            const int xx = x + jj - j.hc;
+            if (xx >= 0 && xx < j.img_cols && m[(int64_t)yy * j.img_cols + xx])
+                s = __fadd_rn(s, k[i * kw + jj]);
+        }
+    }
+    float v = (float)__ddiv_rn((double)s, j.div);
+    v = v < 0.5f ? 0.5f : v;     // np.clip(mask, 0.5, hit_prob) = minimum(maximum(mask, 0.5), hit_prob)
+    v = v > hit32 ? hit32 : v;
+    prob[j.px_off + p] = v;
+}
+
+__device__ __forceinline__ float map_logit(float v, float miss32, float logit_miss, float hit32, float logit_hit)
+{
+    if (v == miss32)
+        return logit_miss;
+    if (v == hit32)
+        return logit_hit;
+    const double d = (double)v;
+    return (float)log(__ddiv_rn(d, __dsub_rn(1.0, d)));
+}
+
+// per column: the first row > 0.5 (np.argmax; 0 for no hit and for a hit in row 0 alike, and then the whole column is a miss),
+// the rows above it set to miss_prob, then logit.  A keyframe without points (hr < 0) is all miss_prob.
+__global__ void map_columns_kernel(const MeasJob *jobs, float *prob, int32_t *first_hits, float miss32, float logit_miss,
+                                   float hit32, float logit_hit, int64_t fh_stride)
+{
+    const MeasJob j = jobs[blockIdx.y];
+    const int col = blockIdx.x * blockDim.x + threadIdx.x;
+    if (col >= j.img_cols)
+        return;
+    float *pc = prob + j.px_off + col;
+    int fh = j.img_rows;
+    if (j.hr >= 0) {
+        fh = 0;
+        for (int r = 0; r < j.img_rows; ++r)
+            if (pc[(int64_t)r * j.img_cols] > 0.5f) {
+                fh = r;
+                break;
+            }
+        if (fh == 0)
+            fh = j.img_rows;
+    }
+    first_hits[blockIdx.y * fh_stride + col] = fh;
+    for (int r = 0; r < j.img_rows; ++r) {
+        const int64_t o = (int64_t)r * j.img_cols;
+        float v = r < fh ? miss32 : pc[o];
+        pc[o] = v;
+        j.logodds[o + col] = map_logit(v, miss32, logit_miss, hit32, logit_hit);
+    }
+}
+
+// --- fit (mapping.py:466-499) -----------------------------------------------------------------------------------------
+// xy = R.dot(sonar_xy.T).T + t in float64: this image's dgemm accumulates over k with a fused multiply-add,
+// fma(R[i][1], y, fl(R[i][0] * x)), then the translation is added (pinned by tests/golden/mapping_session.npz); then
+// round((v - origin) / resolution) half to even.
+__device__ __forceinline__ void map_cell(const FitJob &j, float2 p, double res, int &r, int &c)
+{
+    const double X = (double)p.x, Y = (double)p.y;
+    const double gx = __dadd_rn(__fma_rn(-j.s, Y, __dmul_rn(j.c, X)), j.tx);
+    const double gy = __dadd_rn(__fma_rn(j.c, Y, __dmul_rn(j.s, X)), j.ty);
+    r = (int)rint(__ddiv_rn(__dsub_rn(gy, j.y0), res));
+    c = (int)rint(__ddiv_rn(__dsub_rn(gx, j.x0), res));
+}
+
+__device__ __forceinline__ int wave_min(int v)
+{
+    for (int o = 32; o > 0; o >>= 1)
+        v = min(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ int wave_max(int v)
+{
+    for (int o = 32; o > 0; o >>= 1)
+        v = max(v, __shfl_xor(v, o));
+    return v;
+}
+
+// per keyframe: min / max of r and c over its pixels -> mm[4 b .. 4 b + 3] (initialised to INT_MAX / INT_MIN by the host)
+__global__ void map_bounds_kernel(const FitJob *jobs, double res, int32_t *mm)
+{
+    const FitJob j = jobs[blockIdx.y];
+    int rlo = INT_MAX, rhi = INT_MIN, clo = INT_MAX, chi = INT_MIN;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < j.n_px; p += gridDim.x * blockDim.x) {
+        int r, c;
+        map_cell(j, j.xy[p], res, r, c);
+        rlo = min(rlo, r), rhi = max(rhi, r), clo = min(clo, c), chi = max(chi, c);
+    }
+    rlo = wave_min(rlo), rhi = wave_max(rhi), clo = wave_min(clo), chi = wave_max(chi);
+    if ((threadIdx.x & 63) == 0 && rlo != INT_MAX) {
+        int32_t *o = mm + 4 * blockIdx.y;
+        atomicMin(o + 0, rlo);
+        atomicMax(o + 1, rhi);
+        atomicMin(o + 2, clo);
+        atomicMax(o + 3, chi);
+    }
+}
+
+// np.unique(r * cols + c, return_index=True): the first pixel of every cell.  The window of a 30 m fan at 0.2 m is up to about
+// 300 x 300 cells, more than 160 KB of LDS holds as 32-bit slots, so it lives in HBM: one int per cell, the smallest pixel
+// index wins (integer atomicMin: the same winner whatever the order).
+__global__ void map_scatter_kernel(const FitJob *jobs, double res, int32_t *win)
+{
+    const FitJob j = jobs[blockIdx.y];
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= j.n_px)
+        return;
+    int r, c;
+    map_cell(j, j.xy[p], res, r, c);
+    r -= j.wr0, c -= j.wc0;
+    if (r < 0 || r >= j.wh || c < 0 || c >= j.ww)
+        return;   // cannot happen: the window is the bounds of these same cells
+    atomicMin(win + j.win_off + (int64_t)r * j.ww + c, p);
+}
+
+// one workgroup per keyframe walks its window in row-major order (= ascending r * cols + c) and writes the occupied cells
+__global__ __launch_bounds__(COMPACT_THREADS) void map_compact_kernel(const FitJob *jobs, const int32_t *win)
+{
+    __shared__ int wave_tot[COMPACT_THREADS / 64];
+    __shared__ int carry_s;
+    const FitJob j = jobs[blockIdx.x];
+    const int64_t n = (int64_t)j.wh * j.ww;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int carry = 0;
+    for (int64_t base = 0; base < n; base += COMPACT_THREADS) {
+        const int64_t i = base + threadIdx.x;
+        const int32_t v = i < n ? win[j.win_off + i] : EMPTY_SLOT;
+        const bool on = v != EMPTY_SLOT;
+        const unsigned long long bal = __ballot(on);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0)
+            wave_tot[wave] = __popcll(bal);
+        __syncthreads();
+        int off = carry;
+        int tot = 0;
+        for (int w = 0; w < COMPACT_THREADS / 64; ++w) {
+            off += w < wave ? wave_tot[w] : 0;
+            tot += wave_tot[w];
+        }
+        if (on && v >= 0 && v < j.n_px) {
+            const int k = off + before;
+            const int rr = (int)(i / j.ww), cc = (int)(i - (int64_t)rr * j.ww);
+            j.out_r[k] = (uint16_t)(j.wr0 + rr + j.sr);
+            j.out_c[k] = (uint16_t)(j.wc0 + cc + j.sc);
+            j.out_l[k] = j.logodds[v];
+        }
+        carry += tot;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        carry_s = carry;
+        *j.out_n = carry_s;
+    }
+}
+
+// --- apply (inc_grid / dec_grid): one keyframe's cells are unique, so its scatter has no conflicts; keyframes go in order
+__global__ void map_apply_kernel(float *grid, int rows, int cols, const uint16_t *r, const uint16_t *c, const float *l,
+                                 const int32_t *n, int dr, int dc, int sub)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= *n)
+        return;
+    const int rr = (int)r[i] + dr, cc = (int)c[i] + dc;
+    if (rr < 0 || rr >= rows || cc < 0 || cc >= cols)
+        return;   // cannot happen: every cell lies inside the grown grid
+    float *g = grid + (int64_t)rr * cols + cc;
+    *g = sub ? __fsub_rn(*g, l[i]) : __fadd_rn(*g, l[i]);
+}
+
+__global__ void map_pad_kernel(const float *src, int rows, int cols, float *dst, int dcols, int top, int left)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)rows * cols)
+        return;
+    const int r = (int)(i / cols), c = (int)(i - (int64_t)r * cols);
+    dst[(int64_t)(r + top) * dcols + c + left] = src[i];
+}
+
+// --- render (get_occupancy_grid1, mapping.py:306-355): crop, expit, INTER_NEAREST, int8(clip(100 p, 0, 100))
+__global__ void map_render_kernel(const float *grid, int cols, int r0, int c0, int h, int w, int oh, int ow, double inv,
+                                  int resize, int8_t *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)oh * ow)
+        return;
+    const int y = (int)(i / ow), x = (int)(i - (int64_t)y * ow);
+    int sy = y, sx = x;
+    if (resize) {
+        sy = min((int)floor(__dmul_rn((double)y, inv)), h - 1);
+        sx = min((int)floor(__dmul_rn((double)x, inv)), w - 1);
+    }
+    const double v = (double)grid[(int64_t)(r0 + sy) * cols + c0 + sx];
+    const float p = (float)__ddiv_rn(1.0, __dadd_rn(1.0, exp(-v)));
+    float q = __fmul_rn(100.0f, p);
+    q = q < 0.0f ? 0.0f : (q > 100.0f ? 100.0f : q);
+    out[i] = (int8_t)(int)q;
+}
+
+int map_grid_alloc(sfe_map *m, float **d, size_t n)
+{
+    if (hipMalloc((void **)d, n * sizeof(float)) != hipSuccess)
+        return sfe_set_err(m->ctx, SFE_ERR_HIP, "map grid allocation of %zu cells failed", n);
+    SFE_HIP(m->ctx, hipMemsetAsync(*d, 0, n * sizeof(float), m->ctx->stream));
+    return 0;
+}
+
+int map_counts(sfe_map *m)
+{
+    if (m->counts_cap >= (int)m->slots.size())
+        return 0;
+    int cap = (int)m->slots.size() * 2 + 64;
+    int32_t *d = nullptr;
+    SFE_HIP(m->ctx, hipMalloc((void **)&d, sizeof(int32_t) * 2 * cap));
+    SFE_HIP(m->ctx, hipMemsetAsync(d, 0, sizeof(int32_t) * 2 * cap, m->ctx->stream));
+    if (m->d_counts) {
+        SFE_HIP(m->ctx, hipMemcpyAsync(d, m->d_counts, sizeof(int32_t) * 2 * m->counts_cap, hipMemcpyDeviceToDevice,
+                                       m->ctx->stream));
+        SFE_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
+        (void)hipFree(m->d_counts);
+    }
+    m->d_counts = d;
+    m->counts_cap = cap;
+    return 0;
+}
+
+// the slot, created for geometry g (or checked against it)
+int map_slot(sfe_map *m, int slot, int g)
+{
+    SFE_ARG(m->ctx, slot >= 0 && g >= 0 && g < (int)m->geoms.size());
+    if (slot >= (int)m->slots.size())
+        m->slots.resize(slot + 1);
+    if (int rc = map_counts(m))
+        return rc;
+    MapSlot &s = m->slots[slot];
+    if (s.d_logodds) {
+        SFE_ARG(m->ctx, s.geom == g);
+        return 0;
+    }
+    const size_t n = (size_t)m->geoms[g].img_rows * m->geoms[g].img_cols;
+    s.geom = g;
+    SFE_HIP(m->ctx, hipMalloc((void **)&s.d_logodds, n * sizeof(float)));
+    for (int b = 0; b < 2; ++b) {
+        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_r[b], n * sizeof(uint16_t)));
+        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_c[b], n * sizeof(uint16_t)));
+        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_l[b], n * sizeof(float)));
+    }
+    return 0;
+}
+
+template <class T>
+T *map_upload(sfe_map *m, int i, const T *h, size_t n)
+{
+    T *d = (T *)map_buf(m, i, sizeof(T) * (n ? n : 1));
+    if (!d)
+        return nullptr;
+    if (n && hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, m->ctx->stream) != hipSuccess)
+        return nullptr;
+    return d;
+}
+
+} // namespace
+
+extern "C" {
+
+int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, out != nullptr && rows > 0 && cols > 0 && (long long)rows * cols < (1LL << 31));
+    sfe_map *m = new sfe_map();
+    m->ctx = ctx;
+    m->rows = rows, m->cols = cols;
+    if (int rc = map_grid_alloc(m, &m->d_grid, (size_t)rows * cols)) {
+        delete m;
+        return rc;
+    }
+    *out = m;
+    return 0;
+}
+
+void sfe_map_destroy(sfe_map *m)
+{
+    if (!m)
+        return;
+    if (sfe_use(m->ctx) == 0)
+        (void)hipStreamSynchronize(m->ctx->stream);
+    (void)hipFree(m->d_grid);
+    (void)hipFree(m->d_frames);
+    (void)hipFree(m->d_counts);
+    for (auto &g : m->geoms)
+        (void)hipFree(g.d_xy);
+    for (auto &s : m->slots) {
+        (void)hipFree(s.d_logodds);
+        for (int b = 0; b < 2; ++b) {
+            (void)hipFree(s.d_r[b]);
+            (void)hipFree(s.d_c[b]);
+            (void)hipFree(s.d_l[b]);
+        }
+    }
+    for (auto &b : m->buf)
+        (void)hipFree(b.p);
+    delete m;
+}
+
+int sfe_map_geometry(sfe_map *m, const float *sonar_xy, int img_rows, int img_cols, int *id_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    if (int rc = sfe_use(m->ctx))
+        return rc;
+    SFE_ARG(m->ctx, sonar_xy && id_out && img_rows > 0 && img_cols > 0 && (long long)img_rows * img_cols < (1 << 30));
+    MapGeom g;
+    g.img_rows = img_rows, g.img_cols = img_cols;
+    const size_t n = (size_t)img_rows * img_cols;
+    SFE_HIP(m->ctx, hipMalloc((void **)&g.d_xy, n * sizeof(float2)));
+    SFE_HIP(m->ctx, hipMemcpy(g.d_xy, sonar_xy, n * sizeof(float2), hipMemcpyHostToDevice));
+    m->geoms.push_back(g);
+    *id_out = (int)m->geoms.size() - 1;
+    return 0;
+}
+
+int sfe_map_set_logodds(sfe_map *m, int slot, int geom, const float *logodds)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    if (int rc = sfe_use(m->ctx))
+        return rc;
+    SFE_ARG(m->ctx, logodds != nullptr);
+    if (int rc = map_slot(m, slot, geom))
+        return rc;
+    const MapGeom &g = m->geoms[geom];
+    SFE_HIP(m->ctx, hipMemcpyAsync(m->slots[slot].d_logodds, logodds, sizeof(float) * (size_t)g.img_rows * g.img_cols,
+                                   hipMemcpyHostToDevice, m->ctx->stream));
+    SFE_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
+    return 0;
+}
+
+int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geoms, const int32_t *hit_off,
+                    const int32_t *hits, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
+                    const double *div, float miss32, float logit_miss, float hit32, float logit_hit)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && geoms && hit_off && hrhc && k_off && div)) && n_ktab >= 0);
+    if (n == 0)
+        return 0;
+    std::vector<MeasJob> jobs(n);
+    int64_t px = 0;
+    int max_px = 0, max_cols = 0;
+    for (int b = 0; b < n; ++b) {
+        if (int rc = map_slot(m, slots[b], geoms[b]))
+            return rc;
+        const MapGeom &g = m->geoms[geoms[b]];
+        MeasJob &j = jobs[b];
+        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
+        j.hit_off = hit_off[b];
+        j.n_hits = hit_off[b + 1] - hit_off[b];
+        j.hr = hrhc[2 * b], j.hc = hrhc[2 * b + 1];
+        j.k_off = k_off[b];
+        // hr < 0: no points at all, the image is all miss_prob (mapping.py:224-225)
+        SFE_ARG(ctx, j.n_hits >= 0 && j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
+        if (j.hr < 0)
+            SFE_ARG(ctx, j.n_hits == 0);
+        else
+            SFE_ARG(ctx, j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab);
+        j.div = div[b];
+        j.px_off = px;
+        j.logodds = m->slots[slots[b]].d_logodds;
+        px += j.slot_px;
+        max_px = max(max_px, j.slot_px);
+        max_cols = max(max_cols, j.img_cols);
+    }
+    const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
+    SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
+    MeasJob *d_jobs = map_upload(m, 0, jobs.data(), jobs.size());
+    int32_t *d_hits = map_upload(m, 1, hits, 2 * (size_t)(n_hit_tot - 1));
+    float *d_k = map_upload(m, 2, ktab, (size_t)n_ktab);
+    uint8_t *d_mask = (uint8_t *)map_buf(m, 3, (size_t)px);
+    float *d_prob = (float *)map_buf(m, 4, sizeof(float) * (size_t)px);
+    int32_t *d_fh = (int32_t *)map_buf(m, 5, sizeof(int32_t) * (size_t)n * max_cols);
+    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map measurement scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
+    const unsigned ny = (unsigned)n;
+    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
+                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
+                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
+    m->last_meas = jobs;
+    m->last_meas_n = max_cols;
+    return 0;
+}
+
+int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, b >= 0 && b < (int)m->last_meas.size());
+    const MeasJob &j = m->last_meas[b];
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (hits_out)
+        SFE_HIP(ctx, hipMemcpy(hits_out, (uint8_t *)m->buf[3].p + j.px_off, (size_t)j.slot_px, hipMemcpyDeviceToHost));
+    if (prob_out)
+        SFE_HIP(ctx, hipMemcpy(prob_out, (float *)m->buf[4].p + j.px_off, sizeof(float) * j.slot_px, hipMemcpyDeviceToHost));
+    if (first_hits_out)
+        SFE_HIP(ctx, hipMemcpy(first_hits_out, (int32_t *)m->buf[5].p + (int64_t)b * m->last_meas_n,
+                               sizeof(int32_t) * j.img_cols, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// pose4 per keyframe: {cos, sin, x, y}; origin2: {y0, x0}
+static int map_fit_jobs(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
+                        std::vector<FitJob> &jobs, int &max_px)
+{
+    jobs.assign(n, FitJob());
+    max_px = 0;
+    for (int b = 0; b < n; ++b) {
+        SFE_ARG(m->ctx, slots[b] >= 0 && slots[b] < (int)m->slots.size() && m->slots[slots[b]].d_logodds);
+        const MapSlot &s = m->slots[slots[b]];
+        const MapGeom &g = m->geoms[s.geom];
+        FitJob &j = jobs[b];
+        j.xy = g.d_xy;
+        j.n_px = g.img_rows * g.img_cols;
+        j.c = pose4[4 * b], j.s = pose4[4 * b + 1], j.tx = pose4[4 * b + 2], j.ty = pose4[4 * b + 3];
+        j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1];
+        j.logodds = s.d_logodds;
+        max_px = max(max_px, j.n_px);
+    }
+    return 0;
+}
+
+int sfe_map_fit_bounds(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
+                       double resolution, int32_t *mm_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && pose4 && origin2 && mm_out)) && resolution > 0);
+    if (n == 0)
+        return 0;
+    std::vector<FitJob> jobs;
+    int max_px;
+    if (int rc = map_fit_jobs(m, n, slots, pose4, origin2, jobs, max_px))
+        return rc;
+    std::vector<int32_t> mm(4 * (size_t)n);
+    for (int b = 0; b < n; ++b)
+        mm[4 * b] = INT_MAX, mm[4 * b + 1] = INT_MIN, mm[4 * b + 2] = INT_MAX, mm[4 * b + 3] = INT_MIN;
+    FitJob *d_jobs = map_upload(m, 0, jobs.data(), jobs.size());
+    int32_t *d_mm = map_upload(m, 1, mm.data(), mm.size());
+    if (!d_jobs || !d_mm)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit scratch allocation / upload failed");
+    const unsigned gx = (unsigned)min((max_px + MAP_THREADS - 1) / MAP_THREADS, 64);
+    hipLaunchKernelGGL(map_bounds_kernel, dim3(gx, (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution,
+                       d_mm);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipMemcpyAsync(mm_out, d_mm, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sfe_map_grow(sfe_map *m, int top, int bottom, int left, int right)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, top >= 0 && bottom >= 0 && left >= 0 && right >= 0);
+    if (top + bottom + left + right == 0)
+        return 0;
+    const int nr = m->rows + top + bottom, nc = m->cols + left + right;
+    SFE_ARG(ctx, (long long)nr * nc < (1LL << 31) && nr <= 65536 && nc <= 65536);
+    float *d = nullptr;
+    if (int rc = map_grid_alloc(m, &d, (size_t)nr * nc))
+        return rc;
+    const int64_t n = (int64_t)m->rows * m->cols;
+    hipLaunchKernelGGL(map_pad_kernel, dim3((unsigned)((n + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
+                       ctx->stream, m->d_grid, m->rows, m->cols, d, nc, top, left);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(m->d_grid);
+    m->d_grid = d;
+    m->rows = nr, m->cols = nc;
+    m->grow_r += top, m->grow_c += left;
+    return 0;
+}
+
+int sfe_map_refit(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2, double resolution,
+                  const int32_t *mm, const int32_t *shift2, const uint8_t *dec)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && pose4 && origin2 && mm && shift2 && dec)) && resolution > 0);
+    if (n == 0)
+        return 0;
+    std::vector<FitJob> jobs;
+    int max_px;
+    if (int rc = map_fit_jobs(m, n, slots, pose4, origin2, jobs, max_px))
+        return rc;
+    int64_t win = 0;
+    for (int b = 0; b < n; ++b) {
+        FitJob &j = jobs[b];
+        MapSlot &s = m->slots[slots[b]];
+        for (int a = 0; a < b; ++a)
+            SFE_ARG(ctx, slots[a] != slots[b]); // one refit per slot and call: its other buffer takes the new list
+        SFE_ARG(ctx, mm[4 * b] <= mm[4 * b + 1] && mm[4 * b + 2] <= mm[4 * b + 3]);
+        j.wr0 = mm[4 * b], j.wh = mm[4 * b + 1] - mm[4 * b] + 1;
+        j.wc0 = mm[4 * b + 2], j.ww = mm[4 * b + 3] - mm[4 * b + 2] + 1;
+        j.sr = shift2[2 * b], j.sc = shift2[2 * b + 1];
+        // every cell inside the grid as it stands now (the caller grew it first)
+        SFE_ARG(ctx, j.wr0 + j.sr >= 0 && j.wr0 + j.sr + j.wh <= m->rows && j.wc0 + j.sc >= 0 &&
+                         j.wc0 + j.sc + j.ww <= m->cols);
+        SFE_ARG(ctx, (int64_t)j.wh * j.ww < (1LL << 30));
+        SFE_ARG(ctx, !dec[b] || s.has_cells);
+        j.win_off = win;
+        win += (int64_t)j.wh * j.ww;
+        const int nb = 1 - s.cur;
+        j.out_r = s.d_r[nb], j.out_c = s.d_c[nb], j.out_l = s.d_l[nb];
+        j.out_n = m->d_counts + 2 * slots[b] + nb;
+    }
+    // the job table through pinned staging: the call only enqueues (no synchronisation per batch)
+    FitJob *d_jobs = (FitJob *)map_buf(m, 0, sizeof(FitJob) * jobs.size());
+    int32_t *d_win = (int32_t *)map_buf(m, 1, sizeof(int32_t) * (size_t)win);
+    if (!d_jobs || !d_win)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit scratch allocation failed");
+    void *pin = sfe_pinned_begin(ctx, sizeof(FitJob) * jobs.size());
+    if (!pin)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit: pinned staging failed");
+    memcpy(pin, jobs.data(), sizeof(FitJob) * jobs.size());
+    SFE_HIP(ctx, hipMemcpyAsync(d_jobs, pin, sizeof(FitJob) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = sfe_pinned_end(ctx, ctx->stream))
+        return rc;
+    SFE_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d_win, EMPTY_SLOT, (size_t)win, ctx->stream));
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
+                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)n), dim3(COMPACT_THREADS), 0, ctx->stream, d_jobs, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    // the float32 history of every cell as the reference writes it: for each keyframe in call order, dec then inc
+    for (int b = 0; b < n; ++b) {
+        MapSlot &s = m->slots[slots[b]];
+        const unsigned nblk = (unsigned)((jobs[b].n_px + MAP_THREADS - 1) / MAP_THREADS);
+        if (dec[b]) {
+            const int o = s.cur;
+            hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_grid, m->rows, m->cols,
+                               s.d_r[o], s.d_c[o], s.d_l[o], m->d_counts + 2 * slots[b] + o, m->grow_r - s.base_r,
+                               m->grow_c - s.base_c, 1);
+            SFE_LAUNCH_CHECK(ctx);
+        }
+        const int nb = 1 - s.cur;
+        hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_grid, m->rows, m->cols,
+                           s.d_r[nb], s.d_c[nb], s.d_l[nb], m->d_counts + 2 * slots[b] + nb, 0, 0, 0);
+        SFE_LAUNCH_CHECK(ctx);
+        s.cur = nb;
+        s.has_cells = 1;
+        s.base_r = m->grow_r, s.base_c = m->grow_c;
+    }
+    return 0;
+}
+
+int sfe_map_cells(sfe_map *m, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, slot >= 0 && slot < (int)m->slots.size() && m->slots[slot].has_cells && n_out);
+    const MapSlot &s = m->slots[slot];
+    int32_t n = 0;
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(&n, m->d_counts + 2 * slot + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
+    *n_out = n;
+    if (n > cap)
+        return sfe_set_err(ctx, SFE_ERR_CAP, "map cells: %d cells, room for %d", n, cap);
+    if (r_out)
+        SFE_HIP(ctx, hipMemcpy(r_out, s.d_r[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    if (c_out)
+        SFE_HIP(ctx, hipMemcpy(c_out, s.d_c[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    if (l_out)
+        SFE_HIP(ctx, hipMemcpy(l_out, s.d_l[s.cur], sizeof(float) * n, hipMemcpyDeviceToHost));
+    // the growth since the list was written (uint16 arithmetic, as the reference's keyframe.r += inc_r)
+    for (int i = 0; r_out && i < n; ++i)
+        r_out[i] = (uint16_t)(r_out[i] + (m->grow_r - s.base_r));
+    for (int i = 0; c_out && i < n; ++i)
+        c_out[i] = (uint16_t)(c_out[i] + (m->grow_c - s.base_c));
+    return 0;
+}
+
+int sfe_map_logodds(sfe_map *m, int slot, float *out, int cap)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, slot >= 0 && slot < (int)m->slots.size() && m->slots[slot].d_logodds && out);
+    const MapGeom &g = m->geoms[m->slots[slot].geom];
+    SFE_ARG(ctx, cap >= g.img_rows * g.img_cols);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(out, m->slots[slot].d_logodds, sizeof(float) * g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sfe_map_shape(sfe_map *m, int32_t *rows_cols_grow4)
+{
+    if (!m || !rows_cols_grow4)
+        return SFE_ERR_ARG;
+    rows_cols_grow4[0] = m->rows, rows_cols_grow4[1] = m->cols;
+    rows_cols_grow4[2] = m->grow_r, rows_cols_grow4[3] = m->grow_c;
+    return 0;
+}
+
+// which = 0: the map's grid; 1: the grid of the last sfe_map_frames call
+int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    const float *src = which ? m->d_frames : m->d_grid;
+    const long long n = which ? (long long)m->frames_rows * m->frames_cols : (long long)m->rows * m->cols;
+    SFE_ARG(ctx, out && src && cap >= n);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(out, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// get_occupancy_grid1(frames=...): a fresh zero grid, the listed slots' cells added in list order
+int sfe_map_frames(sfe_map *m, int n, const int32_t *slots)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || slots));
+    if (m->frames_rows != m->rows || m->frames_cols != m->cols) {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(m->d_frames);
+        m->d_frames = nullptr;
+        if (int rc = map_grid_alloc(m, &m->d_frames, (size_t)m->rows * m->cols))
+            return rc;
+        m->frames_rows = m->rows, m->frames_cols = m->cols;
+    } else
+        SFE_HIP(ctx, hipMemsetAsync(m->d_frames, 0, sizeof(float) * (size_t)m->rows * m->cols, ctx->stream));
+    for (int b = 0; b < n; ++b) {
+        SFE_ARG(ctx, slots[b] >= 0 && slots[b] < (int)m->slots.size() && m->slots[slots[b]].has_cells);
+        const MapSlot &s = m->slots[slots[b]];
+        const MapGeom &g = m->geoms[s.geom];
+        const unsigned nblk = (unsigned)((g.img_rows * g.img_cols + MAP_THREADS - 1) / MAP_THREADS);
+        hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_frames, m->rows, m->cols,
+                           s.d_r[s.cur], s.d_c[s.cur], s.d_l[s.cur], m->d_counts + 2 * slots[b] + s.cur,
+                           m->grow_r - s.base_r, m->grow_c - s.base_c, 0);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    return 0;
+}
+
+int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
+                   int8_t *occ_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    const float *src = which ? m->d_frames : m->d_grid;
+    SFE_ARG(ctx, src && (!which || (m->frames_rows == m->rows && m->frames_cols == m->cols)));
+    const int h = r1 - r0 + 1, w = c1 - c0 + 1;
+    SFE_ARG(ctx, out_h >= 0 && out_w >= 0 && (out_h * (long long)out_w == 0 || occ_out));
+    if ((long long)out_h * out_w == 0)
+        return 0;
+    SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && h > 0 && w > 0 && r1 < m->rows && c1 < m->cols);
+    SFE_ARG(ctx, resize || (out_h == h && out_w == w));
+    SFE_ARG(ctx, !resize || inv > 0);
+    const int64_t n = (int64_t)out_h * out_w;
+    int8_t *d = (int8_t *)map_buf(m, 2, (size_t)n);
+    if (!d)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map render scratch allocation failed");
+    hipLaunchKernelGGL(map_render_kernel, dim3((unsigned)((n + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
+                       ctx->stream, src, m->cols, r0, c0, h, w, out_h, out_w, inv, resize, d);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+} // extern "C"
