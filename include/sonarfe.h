@@ -517,6 +517,27 @@ int sfe_cloud_store_compact_selected(sfe_ctx *ctx, sfe_cloud_store *s, int32_t h
  * every source point; key_counts_out[k] = matches whose target carries key k, *overlap_out their number */
 int sfe_cloud_store_match_keys(sfe_ctx *ctx, sfe_cloud_store *s, int32_t source, const float *T6, int32_t target, float max_dist,
                                int flags, int n_keys, int32_t *key_counts_out, int32_t *overlap_out);
+/* The four calls above for n_jobs clouds at once, one launch per stage (chained.SessionBatch runs the loop-closure search of
+ * all its sessions in lock-step).  Job by job the results equal the single-job calls bit for bit -- those are the n = 1 case.
+ *   get_points_keys_many: job j = handles / T6 / keys [job_off[j], job_off[j + 1]) (job_off[0] = 0), its own downsample,
+ *     its own new slot handles_out[j] (stamps: n_jobs entries or NULL).
+ *   fov_select_many: job j = keyed cloud handles[j] against frames [frame_off[j], frame_off[j + 1]) of Tinv6 / range_bound /
+ *     bearing_bound; key_counts_out[j * n_keys ..], n_selected_out[j], n_ambiguous_out[j].  Every cloud keeps its own
+ *     selection (sfe_cloud_store_set_selection replaces one of them).
+ *   compact_selected_many: handles_out[j] = the selected points of handles[j] (stamps: n_jobs entries or NULL).
+ *   match_keys_many: job j = sources[j] under T6[j * 6 ..] against the keyed targets[j]; key_counts_out[j * n_keys ..],
+ *     overlap_out[j]. */
+int sfe_cloud_store_get_points_keys_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, const float *T6,
+                                         const int32_t *keys, const int32_t *job_off, int n_jobs, float resolution, int flags,
+                                         const int64_t *stamps, int32_t *handles_out);
+int sfe_cloud_store_fov_select_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n_jobs, const float *Tinv6,
+                                    const double *range_bound, const double *bearing_bound, const int32_t *frame_off,
+                                    int n_keys, int32_t *key_counts_out, int32_t *n_selected_out, int32_t *n_ambiguous_out);
+int sfe_cloud_store_compact_selected_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n_jobs,
+                                          const int64_t *stamps, int32_t *handles_out);
+int sfe_cloud_store_match_keys_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *sources, const float *T6,
+                                    const int32_t *targets, int n_jobs, float max_dist, int flags, int n_keys,
+                                    int32_t *key_counts_out, int32_t *overlap_out);
 /* bounding boxes of n clouds: bbox_out[i*4 ..] = {min x, min y, max x, max y} (float32 min / max: what np.min / np.max
  * of the cloud give, slam.py:506-507) */
 int sfe_cloud_store_bbox(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n, float *bbox_out);

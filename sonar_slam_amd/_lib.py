@@ -251,6 +251,13 @@ SIGNATURES = {
     "sfe_cloud_store_set_selection": (C.c_int, [_vp, _vp, C.c_int32, _u8p, C.c_int]),
     "sfe_cloud_store_compact_selected": (C.c_int, [_vp, _vp, C.c_int32, C.c_int64, _i32p]),
     "sfe_cloud_store_match_keys": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_int32, C.c_float, C.c_int, C.c_int, _i32p, _i32p]),
+    "sfe_cloud_store_get_points_keys_many": (C.c_int, [_vp, _vp, _i32p, _f32p, _i32p, _i32p, C.c_int, C.c_float, C.c_int, _i64p,
+                                                       _i32p]),
+    "sfe_cloud_store_fov_select_many": (C.c_int, [_vp, _vp, _i32p, C.c_int, _f32p, _f64p, _f64p, _i32p, C.c_int, _i32p, _i32p,
+                                                  _i32p]),
+    "sfe_cloud_store_compact_selected_many": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i64p, _i32p]),
+    "sfe_cloud_store_match_keys_many": (C.c_int, [_vp, _vp, _i32p, _f32p, _i32p, C.c_int, C.c_float, C.c_int, C.c_int, _i32p,
+                                                  _i32p]),
     "sfe_map_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "sfe_map_destroy": (None, [_vp]),
     "sfe_map_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),

@@ -25,6 +25,22 @@ takes is the cost function: the target grids of all S sessions are built in one 
 same Sobol set for every session, since the bounds are the odometry sigmas -- are scored for all sessions in one more
 (``matching_cost.batch_store``), and each session's shgo then runs on that table; the handful of further points its
 local minimiser asks for (finite-difference neighbours) are scored one call each.
+
+``nssm_enable=True`` (off by default here; FrontEnd's other ``nssm_*`` arguments and defaults) adds the loop-closure search
+(slam.py:839-1087) of every session after its scan match, in ``FrontEnd._feed``'s order -- marginal covariance, append, search
+-- and with FrontEnd's own host decisions (replay.fov_bounds, nssm_pose_bounds, initial_transforms, robust_covariance,
+large_transformation).  Sessions leave it at different gates; each stage is one call over the sessions still searching:
+
+    source clouds, refined targets, target moved to its keyframe                 sfe_cloud_store_get_points
+    keyed global targets (own downsample each)                                    sfe_cloud_store_get_points_keys_many
+    field-of-view gate / compaction                                               sfe_cloud_store_fov_select_many / compact_selected_many
+    shgo(100, 5) candidates + finite-difference points of all sessions            sfe_costgrid_create_store + sfe_matching_cost_store
+    target-key refinement                                                         sfe_cloud_store_match_keys_many
+    <= 30 guesses per session / overlaps                                          sfe_icp_store_compute / sfe_cloud_store_overlap
+
+On the host, per session: shgo_fast.replay_multi (scipy.optimize.shgo after a FALLBACK or with shgo_replay=False), the numpy
+gate of a session whose device gate reports undecided points, MinCovDet.  ``rec["nssm"][s]`` is FrontEnd's ``rec["nssm"]``
+bit for bit (None: no search), ``loops[s]`` its loop factors; every cloud of a step's searches is dropped at its end.
 """
 import math
 
@@ -131,9 +147,27 @@ class SessionBatch(object):
                  max_points=16384, resolution=0.5, outlier_radius=1.0, outlier_min_points=5, point_resolution=0.5,
                  point_noise=0.5, ssm_min_points=50, ssm_max_translation=3.0, ssm_max_rotation=np.deg2rad(30),
                  ssm_target_frames=3, store_points=None, initialization=False, initialization_params=(50, 1, 0.01),
-                 odom_sigmas=(0.2, 0.2, 0.02), shgo_workers=1, shgo_replay=True):
+                 odom_sigmas=(0.2, 0.2, 0.02), shgo_workers=1, shgo_replay=True, nssm_enable=False, nssm_initialization=True,
+                 nssm_initialization_params=(100, 5, 0.01), nssm_min_st_sep=8, nssm_min_points=50, nssm_max_translation=10.0,
+                 nssm_max_rotation=np.deg2rad(60), nssm_source_frames=5, nssm_cov_samples=30, oculus_max_range=30.0,
+                 oculus_horizontal_aperture=np.radians(130.0), mcd_random_state=None):
         from .pipeline import KeyframeBatch
+        from .replay import ChainBackend
         self.ctx, self.S, self.K = ctx, int(n_sessions), int(n_steps)
+        # loop-closure search (replay.FrontEnd's arguments of the same names, its defaults but for nssm_enable: off here, so that a
+        # batch built without it runs, sizes and records exactly what it did before the search existed)
+        assert nssm_source_frames < nssm_min_st_sep                                           # slam.py:158
+        assert nssm_cov_samples == 0 or nssm_cov_samples < nssm_initialization_params[0] * nssm_initialization_params[1]
+        self.nssm_enable, self.nssm_initialization = bool(nssm_enable), nssm_initialization
+        self.nssm_initialization_params = tuple(nssm_initialization_params)
+        self.nssm_min_st_sep, self.nssm_min_points = nssm_min_st_sep, nssm_min_points
+        self.nssm_max_translation, self.nssm_max_rotation = nssm_max_translation, nssm_max_rotation
+        self.nssm_source_frames, self.nssm_cov_samples = nssm_source_frames, nssm_cov_samples
+        self.oculus_max_range, self.oculus_horizontal_aperture = oculus_max_range, oculus_horizontal_aperture
+        self.mcd_random_state = mcd_random_state
+        self.icp_odom_sigmas = np.array([0.1, 0.1, 0.01])        # slam.yaml: icp_odom_sigmas (replay.FrontEnd's)
+        self._cov_backend = ChainBackend()                       # its marginal_covariance: what FrontEnd's keyframes get
+        self.nssm_stats = {"searches": 0, "device_s": 0.0, "shgo_s": 0.0, "mcd_s": 0.0, "host_s": 0.0}
         self.icp_params = icp_params
         self.kb = KeyframeBatch(ctx, geometry, cfar_params, alg, intensity_thr, self._kb_params(), self.S,
                                 max_points=max_points)
@@ -144,9 +178,12 @@ class SessionBatch(object):
         self.point_resolution, self.point_noise = point_resolution, point_noise
         self.ssm_min_points, self.ssm_max_translation = ssm_min_points, ssm_max_translation
         self.ssm_max_rotation, self.ssm_target_frames = ssm_max_rotation, ssm_target_frames
-        # keyframe clouds of K steps + the targets of one step (3 keyframes each before the downsample shrinks them)
-        pts = store_points or int(self.S * (self.K + 4) * 2048)
-        self.store = _store.CloudStore(ctx, capacity_points=pts, max_clouds=self.S * (self.K + 2))
+        # keyframe clouds of K steps + the targets of one step (3 keyframes each before the downsample shrinks them); with the
+        # loop-closure search also its scratch clouds of one step: the source (nssm_source_frames keyframes), the keyed global
+        # target and its compaction (all older keyframes each), the compaction moved to the target and the refined target
+        pts = store_points or int(self.S * (self.K + 4 + (self.nssm_source_frames + 4 * self.K if self.nssm_enable else 0)) * 2048)
+        self.store = _store.CloudStore(ctx, capacity_points=pts,
+                                       max_clouds=self.S * (self.K + 2 + (self.NSSM_CLOUDS if self.nssm_enable else 0)))
         dr = np.asarray(dr_poses, np.float64).reshape(self.S, self.K, 3)
         self.dr = [Pose2Batch(dr[:, k, 0], dr[:, k, 1], dr[:, k, 2]) for k in range(self.K)]
         self.max_raw = 0
@@ -201,11 +238,15 @@ class SessionBatch(object):
         old.free()
         return self.kb.cap
 
+    NSSM_CLOUDS = 5     # clouds one session's loop-closure search holds at once (source, keyed target, compaction, 2 targets)
+
     def reset(self):
         self.store.truncate(0)
         self.handles = np.full((self.S, self.K), -1, np.int32)      # keyframe k of session s -> store handle
         self.poses = [None] * self.K                                # Pose2Batch per step (every ping is a keyframe)
         self.records = []
+        self.covs = [[None] * self.K for _ in range(self.S)]        # marginal covariance per keyframe (loop-closure search)
+        self.loops = [[] for _ in range(self.S)]                    # ("loop", target_key, source_key, transform, cov) per session
 
     def step(self, k):
         """-> dict of per-session arrays: status codes, sizes, transforms, overlaps, poses"""
@@ -226,6 +267,7 @@ class SessionBatch(object):
             self._check_counts(rec["n_source"], k)
             rec["pose"] = self.poses[0].xytheta()
             self.records.append(rec)
+            self._after_keyframe(k, rec)
             return rec
         # frame.update(current_keyframe.pose.compose(dr_odom))              slam_ros.py:181-184
         prev = self.poses[k - 1]
@@ -241,9 +283,11 @@ class SessionBatch(object):
             T6[:, j] = prev.between(self.poses[key]).T6()
         n_keep = len(store)
         try:
-            return self._scan_match_step(k, rec, src_h, th, T6, prev, pose)
+            rec = self._scan_match_step(k, rec, src_h, th, T6, prev, pose)
         finally:
             store.truncate(n_keep)                                          # the targets are dropped, the keyframes stay
+        self._after_keyframe(k, rec)
+        return rec
 
     def _scan_match_step(self, k, rec, src_h, th, T6, prev, pose):
         S, store = self.S, self.store
@@ -339,11 +383,13 @@ class SessionBatch(object):
         return self._plan if self._plan.checked else None
 
     def warm_up(self):
-        """Build and self-check the shgo replay NOW instead of inside the first step (a few seconds of scipy.optimize.shgo on
-        random step functions), and say in the log whether it is active for the installed scipy.  -> shgo_fast.status()"""
+        """Build and self-check the shgo replays NOW instead of inside the first steps (a few seconds of scipy.optimize.shgo on
+        random step functions), and say in the log whether they are active for the installed scipy.  -> shgo_fast.status()"""
         from . import shgo_fast
         pose_stds = np.array([self.odom_sigmas]).T
         self._replay_plan(5.0 * np.c_[-pose_stds, pose_stds])
+        if self.nssm_enable and self.nssm_initialization and self.shgo_replay and self.nssm_initialization_params[1] > 1:
+            shgo_fast.multi_checked(*self.nssm_initialization_params)
         return shgo_fast.status()
 
     def _global_init(self, idx, src_h, tgt_h, pose, prev):
@@ -443,6 +489,281 @@ class SessionBatch(object):
             grids.close()
         est = src_pose.compose(Pose2Batch(xs[:, 0], xs[:, 1], xs[:, 2]))
         return ok, est, xs, fs
+
+    # -- loop-closure search (slam.py:839-1087) of every session, after its keyframe is appended (slam_ros.py:207) --
+    def _pose(self, k, s):
+        """keyframe k of session s as a pose2.Pose2 with the bits of the batch's pose (what FrontEnd's keyframe holds)"""
+        from .pose2 import Pose2
+        p = self.poses[k]
+        return Pose2(float(p.x[s]), float(p.y[s]), _cs=(float(p.c[s]), float(p.s[s])))
+
+    def _after_keyframe(self, k, rec):
+        """FrontEnd._feed after the scan match: the keyframe's marginal covariance (ChainBackend.marginal_covariance, kind from
+        the scan match's status), then the search -> rec["nssm"] = [S entries: FrontEnd's rec["nssm"], or None: no search]"""
+        if not self.nssm_enable:
+            return
+        import time
+        for s in range(self.S):
+            kind = "prior" if k == 0 else ("icp" if rec["status"][s] == SUCCESS else "odometry")
+            self.covs[s][k] = self._cov_backend.marginal_covariance(k, self.covs[s][k - 1] if k else None, kind)
+        rec["nssm"] = [None] * self.S
+        if k == 0 or k + 1 < self.nssm_min_st_sep:              # (FrontEnd: current_frame is None / shorter than the exclusion zone)
+            return
+        n_keep = len(self.store)
+        t0 = time.perf_counter()
+        try:
+            rec["nssm"] = self._nssm_search(k)
+        finally:
+            self.store.truncate(n_keep)                         # every cloud the searches built is dropped again
+        self.nssm_stats["searches"] += self.S
+        self.nssm_stats["host_s"] += time.perf_counter() - t0
+
+    def _made(self, handles, k, what):
+        """counts of clouds the search just built; a store too small for them fails here (-3: pool full), never silently"""
+        n = self.store.counts(handles)
+        bad = np.nonzero(n < 0)[0]
+        if len(bad):
+            raise _L.SonarFEError("step %d: the loop-closure search's %s cloud was not stored (count %d: -1 octree deeper than 24 "
+                                  "levels, -3 store full: raise store_points)" % (k, what, int(n[bad[0]])))
+        return n
+
+    def _nssm_search(self, k):
+        """FrontEnd._nssm for every session at keyframe k, one device call per stage over the sessions still searching; the
+        host decisions are FrontEnd's own functions"""
+        import time
+        from . import pcl
+        from .replay import FrontEnd, fov_bounds, icp_result, large_transformation, robust_covariance
+        S, store, P, st = self.S, self.store, self._pose, self.nssm_stats
+        F32 = _store.F32_POINTS
+        K, source_key = k + 1, k
+        recs = [{"source_key": source_key} for _ in range(S)]
+        source_frames = list(range(source_key, source_key - self.nssm_source_frames, -1))
+        target_frames = list(range(K - self.nssm_min_st_sep))
+        source_pose = [P(k - 1, s) for s in range(S)]               # slam.py:854: the frame of the PREVIOUS callback
+
+        def done(s, status):
+            recs[s]["status"] = status
+
+        t = time.perf_counter()
+        # source = get_points(source_frames, source_key)
+        T6 = np.array([[_store.pose_T6(P(k, s).between(P(f, s))) for f in source_frames] for s in range(S)], np.float32)
+        src_h = store.get_points(self.handles[:, source_frames], T6, self.point_resolution)
+        n_src = self._made(src_h, k, "source")
+        act = []
+        for s in range(S):
+            recs[s]["n_source"] = int(n_src[s])
+            if n_src[s] < self.nssm_min_points:
+                done(s, "NOT_ENOUGH_POINTS")
+            else:
+                act.append(s)
+        # keyed global target, field-of-view gate (slam.py:873-904)
+        G = store.get_points_keys_many([self.handles[s, target_frames] for s in act],
+                                       [[_store.pose_T6(P(f, s)) for f in target_frames] for s in act],
+                                       [target_frames] * len(act), self.point_resolution)
+        self._made(G, k, "keyed target")
+        bounds = [fov_bounds([P(f, s) for f in source_frames], [self.covs[s][f] for f in source_frames], self.oculus_max_range,
+                             self.oculus_horizontal_aperture) for s in act]
+        hist, n_sel, n_amb = store.fov_select_many(G, [[_store.pose_T6(p) for p in b[0]] for b in bounds], [b[1] for b in bounds],
+                                                   [b[2] for b in bounds], K)
+        st["device_s"] += time.perf_counter() - t
+        gate = []
+        for j, s in enumerate(act):
+            h, ns = hist[j], int(n_sel[j])
+            if n_amb[j]:        # a bearing within float32 rounding of its bound: numpy decides, for this session alone
+                Tinv, rb, bb = bounds[j]
+                sel = FrontEnd._fov_numpy(store.read(G[j]), Tinv, rb, bb)
+                store.set_selection(G[j], sel)
+                h = np.bincount(store.read_keys(G[j])[sel], minlength=K).astype(np.int32)
+                ns = int(sel.sum())
+            r = recs[s]
+            r["fov_ambiguous"] = int(n_amb[j])
+            frames1 = np.nonzero(h)[0].astype(np.int32)
+            counts = h[frames1]
+            r["n_target_global"] = ns
+            frames1, counts = frames1[counts > 10], counts[counts > 10]
+            if len(frames1) == 0 or ns < self.nssm_min_points:
+                done(s, "NOT_ENOUGH_POINTS")
+                continue
+            r["target_key_fov"] = int(frames1[np.argmax(counts)])
+            gate.append((j, s, ns))
+        if not gate:
+            return recs
+        t = time.perf_counter()
+        # target_points[sel] moved to the target keyframe (slam.py:898-905)
+        C = store.compact_selected_many([G[j] for j, _, _ in gate])
+        self._made(C, k, "compacted target")
+        tkey = {s: recs[s]["target_key_fov"] for _, s, _ in gate}
+        tl = store.get_points(C[:, None], np.array([[_store.pose_T6(P(tkey[s], s).inverse())] for _, s, _ in gate], np.float32),
+                              0.0, flags=F32)
+        self._made(tl, k, "target")
+        st["device_s"] += time.perf_counter() - t
+        cur = [dict(s=s, C=int(C[i]), tl=int(tl[i]), n=ns, target_key=tkey[s], target_pose=P(tkey[s], s),
+                    est=source_pose[s], samples=None) for i, (_, s, ns) in enumerate(gate)]
+        if self.nssm_initialization:
+            cur = self._nssm_init(k, cur, recs, src_h, K, target_frames)
+        for c in cur:
+            recs[c["s"]]["target_key"], recs[c["s"]]["n_target"] = c["target_key"], c["n"]
+        # ICPResult (slam_objects.py:247-300): the guesses of every session in one store.icp call
+        pairs, guesses, owner = [], [], []
+        with_cov = self.nssm_initialization and self.nssm_cov_samples > 0
+        for i, c in enumerate(cur):
+            c["initial"] = c["target_pose"].between(c["est"])
+            if with_cov:
+                g = FrontEnd.initial_transforms(c["samples"], c["target_pose"], limit=self.nssm_cov_samples)
+                recs[c["s"]]["n_guesses"] = len(g)
+            else:
+                g = [c["initial"]]
+            pairs += [(src_h[c["s"]], c["tl"])] * len(g)
+            guesses += [pcl.ICP._guess(x.matrix()) for x in g]
+            owner += [i] * len(g)
+        t = time.perf_counter()
+        if pairs:
+            Ts, sts, _ = store.icp(self.icp_params, pairs, guesses)
+        st["device_s"] += time.perf_counter() - t
+        owner = np.array(owner, np.int64)
+        ok_cur = []
+        for i, c in enumerate(cur):
+            r, mine = recs[c["s"]], np.nonzero(owner == i)[0]
+            if with_cov:
+                t = time.perf_counter()
+                if len(mine):
+                    message, odom, cov_icp, samples = robust_covariance(Ts[mine], sts[mine] == 0, self.mcd_random_state,
+                                                                        self.icp_odom_sigmas)
+                else:
+                    message = "Too few samples for covariance computation"
+                st["mcd_s"] += time.perf_counter() - t
+                r["icp"] = message
+                if message != "success":
+                    done(c["s"], "NOT_CONVERGED")
+                    continue
+                r["n_converged"], r["sample_transforms"], r["cov"] = len(samples), samples, cov_icp
+            else:
+                message, odom = icp_result(Ts[mine[0]], sts[mine[0]])
+                cov_icp = None
+                r["icp"] = message
+                if message != "success":
+                    done(c["s"], "NOT_CONVERGED")
+                    continue
+            r["transform"] = (odom.x(), odom.y(), odom.theta())
+            if large_transformation(c["initial"], odom, self.nssm_max_translation, self.nssm_max_rotation):   # slam.py:1066-1077
+                done(c["s"], "LARGE_TRANSFORMATION")
+                continue
+            c["odom"], c["cov"] = odom, cov_icp
+            ok_cur.append(c)
+        t = time.perf_counter()
+        ov = store.overlap([(src_h[c["s"]], c["tl"]) for c in ok_cur], [_store.pose_T6(c["odom"]) for c in ok_cur],
+                           self.point_noise, flags=F32) if ok_cur else []
+        st["device_s"] += time.perf_counter() - t
+        for c, o in zip(ok_cur, ov):
+            r = recs[c["s"]]
+            r["overlap"] = int(o)
+            if o < self.nssm_min_points:
+                done(c["s"], "NOT_ENOUGH_OVERLAP")
+                continue
+            done(c["s"], "SUCCESS")
+            self.loops[c["s"]].append(("loop", c["target_key"], source_key, c["odom"], c["cov"]))   # -> PCM + ISAM2: back end
+        return recs
+
+    def _nssm_init(self, k, cur, recs, src_h, K, target_frames):
+        """slam.py:922-999 for the sessions `cur`: shgo over the matching cost (the candidates of every session and their
+        finite-difference points scored in one launch, shgo_fast.replay_multi per session; scipy.optimize.shgo itself where the
+        replay is off or reports FALLBACK), then the target key refined by the matches (one launch) and the refined targets
+        (one get_points call) -> the sessions still searching"""
+        import time
+        from . import matching_cost as mc
+        from . import shgo_fast
+        from .pose2 import Pose2
+        from .replay import FrontEnd, nssm_pose_bounds
+        store, P, st, params = self.store, self._pose, self.nssm_stats, self.nssm_initialization_params
+        source_frames_last = k - self.nssm_source_frames + 1
+        for c in cur:
+            c["bounds"] = nssm_pose_bounds(self.covs[c["s"]][source_frames_last])
+            np.linalg.inv(self.covs[c["s"]][k])                  # slam.py:529 (the subroutine inverts the source's covariance)
+        multi = self.shgo_replay and params[1] > 1 and shgo_fast.multi_checked(params[0], params[1], params[2])
+        results = [None] * len(cur)
+        if multi:
+            t = time.perf_counter()
+            grids = mc._StoreGrids(store, [c["tl"] for c in cur], self.point_noise)
+            try:
+                cands, T6 = [], []
+                for c in cur:
+                    draws, cand, fd = shgo_fast.multi_candidates(c["bounds"], params[0], params[1])
+                    cands.append((draws, cand, fd))
+                    T6.append(mc._sample_poses(self.ctx.lib, c["est"], c["target_pose"], np.concatenate([cand, fd.reshape(-1, 3)]))[0])
+                costs = grids.cost([src_h[c["s"]] for c in cur], np.array(T6), f64_points=False).astype(np.int64)
+            finally:
+                grids.close()
+            st["device_s"] += time.perf_counter() - t
+            t = time.perf_counter()
+            for i, c in enumerate(cur):
+                draws, cand, fd = cands[i]
+                M = len(cand)
+                cost, fd_cost = costs[i, :M], costs[i, M:].reshape(M, 3)
+                sta, x, fun, vertices, minimised = self._replay_multi(c["bounds"], params[0], params[1], draws, cand, cost, fd_cost)
+                if sta == shgo_fast.FALLBACK:
+                    continue
+                X = np.concatenate([cand[vertices], cand[minimised], fd[minimised].reshape(-1, 3)])
+                _, poses = mc._sample_poses(self.ctx.lib, c["est"], c["target_pose"], X)
+                c["samples"] = list(np.c_[poses, np.concatenate([cost[vertices], cost[minimised],
+                                                                  fd_cost[minimised].reshape(-1)]).astype(np.float64)])
+                results[i] = (sta == shgo_fast.OK, x, np.int64(fun), True,
+                              None if sta == shgo_fast.OK else "Failed to find a feasible minimizer point. Lowest sampling point = %s" % fun)
+            st["shgo_s"] += time.perf_counter() - t
+        t = time.perf_counter()
+        for i, c in enumerate(cur):
+            if results[i] is not None:
+                continue
+            # FrontEnd's own call on this session alone, over its handles: after a FALLBACK of the replay scipy.optimize.shgo
+            # (where FrontEnd.shgo goes then), otherwise what FrontEnd.shgo does with these parameters
+            sub, samples = mc.get_matching_cost_subroutine1_store(store, int(src_h[c["s"]]), c["est"], c["tl"], c["target_pose"],
+                                                                  self.covs[c["s"]][k], point_noise=self.point_noise, f64_points=False)
+            try:
+                res = FrontEnd.shgo(sub, c["bounds"], params, replay=self.shgo_replay and not multi)
+            finally:
+                sub.grid.close()
+            c["samples"] = samples
+            results[i] = (bool(res.success), res.x, res.fun, bool(res.get("replayed", False)), str(res.message))
+        st["shgo_s"] += time.perf_counter() - t
+        nxt = []
+        for i, c in enumerate(cur):
+            r = recs[c["s"]]
+            success, x, fun, replayed, message = results[i]
+            r["init_replayed"] = replayed
+            if not success:
+                r["status"], r["init_message"] = "INITIALIZATION_FAILURE", message
+                continue
+            r["init_x"], r["init_cost"] = tuple(float(v) for v in x), float(fun)
+            c["est"] = c["est"].compose(Pose2(*x))
+            c["samples"] = np.array(c["samples"])
+            nxt.append(c)
+        if not nxt:
+            return nxt
+        t = time.perf_counter()
+        # refine the target key: the keyframe most of the matched target points came from (slam.py:975-999)
+        hist1, overlap = store.match_keys_many([src_h[c["s"]] for c in nxt], [_store.pose_T6(c["est"]) for c in nxt],
+                                               [c["C"] for c in nxt], self.point_noise, K, flags=_store.F32_POINTS)
+        cur, nxt = nxt, []
+        for i, c in enumerate(cur):
+            recs[c["s"]]["overlap_global"] = int(overlap[i])
+            if overlap[i] == 0:
+                recs[c["s"]]["status"] = "NOT_ENOUGH_OVERLAP"
+                continue
+            c["target_key"] = int(np.argmax(hist1[i]))
+            c["target_pose"] = P(c["target_key"], c["s"])
+            nxt.append(c)
+        if nxt:
+            T6 = np.array([[_store.pose_T6(c["target_pose"].between(P(f, c["s"]))) for f in target_frames] for c in nxt], np.float32)
+            th = store.get_points(np.array([self.handles[c["s"], target_frames] for c in nxt], np.int32), T6, self.point_resolution)
+            n = self._made(th, k, "refined target")
+            for c, h, m in zip(nxt, th, n):
+                c["tl"], c["n"] = int(h), int(m)
+        st["device_s"] += time.perf_counter() - t
+        return nxt
+
+    @staticmethod
+    def _replay_multi(*args):
+        from . import shgo_fast
+        return shgo_fast.replay_multi(*args)
 
     def _check_raw(self, k):
         """a ping with more detections than the batch's point capacity would be truncated silently"""

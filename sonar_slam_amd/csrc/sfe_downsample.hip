@@ -16,6 +16,7 @@
 // LDS): N is a few thousand, the pass is a few microseconds, and it is trivially exact/stable.
 #include "sfe_internal.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 
@@ -23,10 +24,32 @@ typedef SfeDsHeader DsHeader; // {cx, cy, radius, levels, n_seg}: sfe_internal.h
 
 #define DS_MAX_LEVELS 31
 
-__global__ __launch_bounds__(1024) void ds_bbox_kernel(const float2 *__restrict__ pts, int n, float max_size,
-                                                       DsHeader *__restrict__ hdr)
+// Many jobs per launch (sfe_ds_run_dev_many): job j's points sit at pts + j * stride, its n at DsJobs::n(j); its keys,
+// sorted keys and sorted indices at the same offsets, its run starts at seg_start + j * (stride + 1), its header at hdr + j,
+// its medoids / their (job-local) indices at out + j * stride.  blockIdx.y is the job.  One job (sfe_ds_run_dev) is n = 1,
+// stride = n: the layout and the arithmetic of the single-cloud chain.
+struct DsJobs {
+    const int32_t *tab_n; // [n_jobs] points per job (device), or nullptr: every job has `one` points
+    int one;
+    int stride;
+    __device__ __forceinline__ int n(int j) const { return tab_n ? tab_n[j] : one; }
+};
+
+__global__ __launch_bounds__(1024) void ds_bbox_kernel(const float2 *__restrict__ pts_, DsJobs J, float max_size,
+                                                       DsHeader *__restrict__ hdr_)
 {
     __shared__ float s_mn[2][16], s_mx[2][16];
+    const int j = blockIdx.y, n = J.n(j);
+    const float2 *pts = pts_ + (size_t)j * J.stride;
+    DsHeader *hdr = hdr_ + j;
+    if (n == 0) { // (an empty job of a many-job call: no leaves)
+        if (threadIdx.x == 0) {
+            hdr->cx = hdr->cy = hdr->radius = 0.0f;
+            hdr->levels = 0;
+            hdr->n_seg = 0;
+        }
+        return;
+    }
     float mnx = INFINITY, mny = INFINITY, mxx = -INFINITY, mxy = -INFINITY;
     for (int i = threadIdx.x; i < n; i += 1024) {
         const float2 p = pts[i];
@@ -76,14 +99,16 @@ __global__ __launch_bounds__(1024) void ds_bbox_kernel(const float2 *__restrict_
     }
 }
 
-__global__ __launch_bounds__(256) void ds_key_kernel(const float2 *__restrict__ pts, int n,
-                                                     const DsHeader *__restrict__ hdr,
-                                                     unsigned long long *__restrict__ keys)
+__global__ __launch_bounds__(256) void ds_key_kernel(const float2 *__restrict__ pts_, DsJobs J,
+                                                     const DsHeader *__restrict__ hdr_,
+                                                     unsigned long long *__restrict__ keys_)
 {
+    const int j = blockIdx.y, n = J.n(j);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n)
         return;
-    const float2 p = pts[i];
+    const DsHeader *hdr = hdr_ + j;
+    const float2 p = pts_[(size_t)j * J.stride + i];
     float cx = hdr->cx, cy = hdr->cy, r = hdr->radius;
     const int L = hdr->levels;
     unsigned long long key = 0;
@@ -95,40 +120,50 @@ __global__ __launch_bounds__(256) void ds_key_kernel(const float2 *__restrict__ 
         cy = cy + (by ? hr : -hr);
         r = hr;
     }
-    keys[i] = key;
+    keys_[(size_t)j * J.stride + i] = key;
 }
 
 // rank of (key_i, i) among all points = position in the stable sort; scatter index and key there
-__global__ __launch_bounds__(256) void ds_rank_kernel(const unsigned long long *__restrict__ keys, int n,
-                                                      int *__restrict__ sorted_idx,
-                                                      unsigned long long *__restrict__ sorted_key)
+__global__ __launch_bounds__(256) void ds_rank_kernel(const unsigned long long *__restrict__ keys_, DsJobs J,
+                                                      int *__restrict__ sorted_idx_,
+                                                      unsigned long long *__restrict__ sorted_key_)
 {
     __shared__ unsigned long long s_k[2048];
+    const int j = blockIdx.y, n = J.n(j);
+    if (blockIdx.x * 256 >= n) // (the whole block: a job smaller than the largest of the call)
+        return;
+    const size_t base = (size_t)j * J.stride;
+    const unsigned long long *keys = keys_ + base;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const unsigned long long ki = (i < n) ? keys[i] : 0ull;
     int rank = 0;
     for (int tb = 0; tb < n; tb += 2048) {
         const int tn = min(2048, n - tb);
         __syncthreads();
-        for (int j = threadIdx.x; j < tn; j += 256)
-            s_k[j] = keys[tb + j];
+        for (int q = threadIdx.x; q < tn; q += 256)
+            s_k[q] = keys[tb + q];
         __syncthreads();
-        for (int j = 0; j < tn; ++j) {
-            const unsigned long long kj = s_k[j];
-            rank += (kj < ki) || (kj == ki && tb + j < i);
+        for (int q = 0; q < tn; ++q) {
+            const unsigned long long kj = s_k[q];
+            rank += (kj < ki) || (kj == ki && tb + q < i);
         }
     }
     if (i < n) {
-        sorted_idx[rank] = i;
-        sorted_key[rank] = ki;
+        sorted_idx_[base + rank] = i;
+        sorted_key_[base + rank] = ki;
     }
 }
 
-// one workgroup: mark the first position of every run of equal keys, list the run starts
-__global__ __launch_bounds__(1024) void ds_segment_kernel(const unsigned long long *__restrict__ sorted_key, int n,
-                                                          int *__restrict__ seg_start, DsHeader *__restrict__ hdr)
+// one workgroup per job: mark the first position of every run of equal keys, list the run starts (+ counts[j] = their
+// number when the caller wants the sizes as an array: the store's append reads them there)
+__global__ __launch_bounds__(1024) void ds_segment_kernel(const unsigned long long *__restrict__ sorted_key_, DsJobs J,
+                                                          int *__restrict__ seg_start_, DsHeader *__restrict__ hdr_,
+                                                          int32_t *__restrict__ counts)
 {
     __shared__ int s_part[1024];
+    const int j = blockIdx.y, n = J.n(j);
+    const unsigned long long *sorted_key = sorted_key_ + (size_t)j * J.stride;
+    int *seg_start = seg_start_ + (size_t)j * ((size_t)J.stride + 1);
     const int per = (n + 1023) / 1024;
     const int b = threadIdx.x * per, e = min(b + per, n);
     int c = 0;
@@ -147,21 +182,28 @@ __global__ __launch_bounds__(1024) void ds_segment_kernel(const unsigned long lo
         if ((r == 0) || (sorted_key[r] != sorted_key[r - 1]))
             seg_start[s++] = r;
     if (threadIdx.x == 1023) {
-        hdr->n_seg = s_part[1023];
+        hdr_[j].n_seg = s_part[1023];
         seg_start[s_part[1023]] = n; // sentinel
+        if (counts)
+            counts[j] = s_part[1023];
     }
 }
 
 // one thread per leaf: float centroid in original order, first point at minimum distance
-__global__ __launch_bounds__(256) void ds_medoid_kernel(const float2 *__restrict__ pts,
-                                                        const int *__restrict__ sorted_idx,
-                                                        const int *__restrict__ seg_start,
-                                                        const DsHeader *__restrict__ hdr, float2 *__restrict__ out,
-                                                        int *__restrict__ out_idx)
+__global__ __launch_bounds__(256) void ds_medoid_kernel(const float2 *__restrict__ pts_, DsJobs J,
+                                                        const int *__restrict__ sorted_idx_,
+                                                        const int *__restrict__ seg_start_,
+                                                        const DsHeader *__restrict__ hdr_, float2 *__restrict__ out_,
+                                                        int *__restrict__ out_idx_)
 {
+    const int j = blockIdx.y;
     const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= hdr->n_seg)
+    if (s >= hdr_[j].n_seg)
         return;
+    const size_t base = (size_t)j * J.stride;
+    const float2 *pts = pts_ + base;
+    const int *sorted_idx = sorted_idx_ + base;
+    const int *seg_start = seg_start_ + (size_t)j * ((size_t)J.stride + 1);
     const int r0 = seg_start[s], r1 = seg_start[s + 1];
     float sx = 0.0f, sy = 0.0f;
     for (int r = r0; r < r1; ++r) {
@@ -186,37 +228,52 @@ __global__ __launch_bounds__(256) void ds_medoid_kernel(const float2 *__restrict
             bi = id;
         }
     }
-    out[s] = pts[bi];
-    out_idx[s] = bi;
+    out_[base + s] = pts[bi];
+    out_idx_[base + s] = bi;
 }
 
-// The chain above on a cloud that is already on the device (sfe_store.hip: targets beyond the resident filter's capacity,
-// and the descriptor overload of pcl.downsample, which needs the indices).  Enqueue only: d_out / d_out_idx hold the
-// medoids and their indices into d_pts, d_hdr->n_seg their number.  Scratch slots 1-4.
-int sfe_ds_run_dev(sfe_ctx *ctx, const float *d_pts_, int n, float resolution, float *d_out_, int32_t *d_out_idx,
-                   SfeDsHeader *d_hdr_)
+// The chain above on clouds that are already on the device (sfe_store.hip: targets beyond the resident filter's capacity,
+// and the descriptor overload of pcl.downsample, which needs the indices), n_jobs of them per launch: job j = d_n[j]
+// points at d_pts + j * stride (d_n may be nullptr for one job of n_max points).  Enqueue only: d_out / d_out_idx + j *
+// stride hold job j's medoids and their indices into its points, d_hdr[j].n_seg (and d_counts[j], if given) their number.
+// Scratch slots 1-4.
+int sfe_ds_run_dev_many(sfe_ctx *ctx, const float *d_pts_, int n_jobs, const int32_t *d_n, int n_max, int stride,
+                        float resolution, float *d_out_, int32_t *d_out_idx, SfeDsHeader *d_hdr_, int32_t *d_counts)
 {
     const float2 *d_pts = (const float2 *)d_pts_;
     float2 *d_out = (float2 *)d_out_;
     DsHeader *d_hdr = (DsHeader *)d_hdr_;
+    if (n_jobs <= 0)
+        return 0;
     char buf[64];
     snprintf(buf, sizeof buf, "%f", (double)resolution); // pcl.cpp:134: std::to_string(float)
     const float max_size = strtof(buf, nullptr);
-    unsigned long long *d_keys = (unsigned long long *)sfe_scratch(ctx, 1, 8 * (size_t)n);
-    unsigned long long *d_skeys = (unsigned long long *)sfe_scratch(ctx, 2, 8 * (size_t)n);
-    int *d_sidx = (int *)sfe_scratch(ctx, 3, 4 * (size_t)n);
-    int *d_seg = (int *)sfe_scratch(ctx, 4, 4 * ((size_t)n + 1));
+    const size_t tot = (size_t)n_jobs * (size_t)stride;
+    unsigned long long *d_keys = (unsigned long long *)sfe_scratch(ctx, 1, 8 * tot);
+    unsigned long long *d_skeys = (unsigned long long *)sfe_scratch(ctx, 2, 8 * tot);
+    int *d_sidx = (int *)sfe_scratch(ctx, 3, 4 * tot);
+    int *d_seg = (int *)sfe_scratch(ctx, 4, 4 * (tot + (size_t)n_jobs));
     if (!d_keys || !d_skeys || !d_sidx || !d_seg)
         return SFE_ERR_HIP;
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ds_bbox_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_pts, n, max_size, d_hdr);
-    hipLaunchKernelGGL(ds_key_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_pts, n, d_hdr, d_keys);
-    hipLaunchKernelGGL(ds_rank_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_keys, n, d_sidx, d_skeys);
-    hipLaunchKernelGGL(ds_segment_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_skeys, n, d_seg, d_hdr);
-    hipLaunchKernelGGL(ds_medoid_kernel, dim3(nb), dim3(256), 0, ctx->stream, d_pts, d_sidx, d_seg, d_hdr, d_out,
-                       d_out_idx);
+    const DsJobs J{d_n, n_max, stride};
+    const unsigned nb = (unsigned)std::max((n_max + 255) / 256, 1);
+    hipLaunchKernelGGL(ds_bbox_kernel, dim3(1, n_jobs), dim3(1024), 0, ctx->stream, d_pts, J, max_size, d_hdr);
+    hipLaunchKernelGGL(ds_key_kernel, dim3(nb, n_jobs), dim3(256), 0, ctx->stream, d_pts, J, (const DsHeader *)d_hdr, d_keys);
+    hipLaunchKernelGGL(ds_rank_kernel, dim3(nb, n_jobs), dim3(256), 0, ctx->stream, (const unsigned long long *)d_keys, J, d_sidx,
+                       d_skeys);
+    hipLaunchKernelGGL(ds_segment_kernel, dim3(1, n_jobs), dim3(1024), 0, ctx->stream, (const unsigned long long *)d_skeys, J,
+                       d_seg, d_hdr, d_counts);
+    hipLaunchKernelGGL(ds_medoid_kernel, dim3(nb, n_jobs), dim3(256), 0, ctx->stream, d_pts, J, (const int *)d_sidx,
+                       (const int *)d_seg, (const DsHeader *)d_hdr, d_out, d_out_idx);
     SFE_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+// one cloud: the n = 1 case of the above
+int sfe_ds_run_dev(sfe_ctx *ctx, const float *d_pts, int n, float resolution, float *d_out, int32_t *d_out_idx,
+                   SfeDsHeader *d_hdr)
+{
+    return sfe_ds_run_dev_many(ctx, d_pts, 1, nullptr, n, n, resolution, d_out, d_out_idx, d_hdr, nullptr);
 }
 
 extern "C" {

@@ -189,6 +189,8 @@ struct SfeDsHeader {
 };
 int sfe_ds_run_dev(sfe_ctx *ctx, const float *d_pts, int n, float resolution, float *d_out, int32_t *d_out_idx,
                    SfeDsHeader *d_hdr);
+int sfe_ds_run_dev_many(sfe_ctx *ctx, const float *d_pts, int n_jobs, const int32_t *d_n, int n_max, int stride,
+                        float resolution, float *d_out, int32_t *d_out_idx, SfeDsHeader *d_hdr, int32_t *d_counts);
 
 static inline int sfe_use(sfe_ctx *ctx)
 {

@@ -33,13 +33,13 @@ struct sfe_cloud_store {
     int32_t *d_cnt = nullptr; // [max_clouds] points (< 0: the producer failed, see SFE_STORE_*)
     int64_t *d_top = nullptr; // [1] points in use
     // loop-closure search (NSSM, slam.py:839-1001): a key (the keyframe a point came from) per pool point, filled for the
-    // clouds the keyed entry points produce; a selection byte per point of the cloud the last fov_select looked at
+    // clouds the keyed entry points produce; a selection byte per pool point, filled for the clouds fov_select /
+    // set_selection looked at (many clouds can hold a selection at once: the many-job gate of chained.SessionBatch)
     int32_t *d_key = nullptr; // [capacity], allocated on first use
-    uint8_t *d_sel = nullptr;
-    size_t sel_cap = 0;
-    int32_t sel_handle = -1, sel_count = 0; // the cloud the selection was made for, and its size then (a handle alone can
-                                            // be reused by a larger cloud after a truncate)
-    std::vector<uint8_t> keyed;             // per slot: built by a keyed entry point (the key pool holds ITS keys)
+    uint8_t *d_sel = nullptr; // [capacity], allocated on first use
+    std::vector<int32_t> sel_n; // per slot: the cloud's size when its selection was made, -1 none (a handle alone
+                                // can be reused by a larger cloud after a truncate; truncate drops the dropped slots' entries)
+    std::vector<uint8_t> keyed; // per slot: built by a keyed entry point (the key pool holds ITS keys)
     // host mirror of the slot table: entries < n_synced are valid
     std::vector<int64_t> stamp, off;
     std::vector<int32_t> cnt;
@@ -312,31 +312,40 @@ __global__ __launch_bounds__(256) void store_concat_kernel(const float2 *__restr
             hi = mid - 1;
     }
     const StoreSeg sg = seg[lo];
-    out[i] = store_transform<F64>(pool[sg.src + (i - sg.dst)], sg.T[0], sg.T[1], sg.T[2], sg.T[3], sg.T[4], sg.T[5]);
+    const long long r = i - sg.dst;
+    if (r < 0 || r >= sg.n) // (the gap behind a job shorter than the stride of a many-job concatenation)
+        return;
+    out[i] = store_transform<F64>(pool[sg.src + r], sg.T[0], sg.T[1], sg.T[2], sg.T[3], sg.T[4], sg.T[5]);
     if (out_key)
         out_key[i] = sg.key;
 }
 
-// keys of the medoids: key[s] = cat_key[idx[s]]
+// keys of the medoids of job blockIdx.y: key[s] = cat_key[idx[s]] (its medoids' indices are job-local; the job's data
+// starts at j * stride)
 __global__ __launch_bounds__(256) void store_pick_keys_kernel(const int32_t *__restrict__ cat_key, const int32_t *__restrict__ idx,
-                                                              const int32_t *__restrict__ n, int32_t *__restrict__ out)
+                                                              const int32_t *__restrict__ n, int stride, int32_t *__restrict__ out)
 {
+    const int j = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < *n)
-        out[i] = cat_key[idx[i]];
+    const size_t base = (size_t)j * stride;
+    if (i < n[j])
+        out[base + i] = cat_key[base + idx[base + i]];
 }
 
-// the keys of a freshly committed slot go next to its points (the slot's offset is known on the device only)
-__global__ __launch_bounds__(256) void store_commit_keys_kernel(const int32_t *__restrict__ keys, const int64_t *__restrict__ off,
-                                                                const int32_t *__restrict__ cnt, int slot,
-                                                                int32_t *__restrict__ key_pool)
+// the keys of freshly committed slots go next to their points (a slot's offset is known on the device only): slot
+// first + blockIdx.y takes the keys at keys + blockIdx.y * stride
+__global__ __launch_bounds__(256) void store_commit_keys_kernel(const int32_t *__restrict__ keys, int stride,
+                                                                const int64_t *__restrict__ off, const int32_t *__restrict__ cnt,
+                                                                int first, int32_t *__restrict__ key_pool)
 {
+    const int slot = first + (int)blockIdx.y;
     const long long o = off[slot];
     const int n = cnt[slot];
     if (o < 0)
         return;
+    const int32_t *k = keys + (size_t)blockIdx.y * stride;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256)
-        key_pool[o + i] = keys[i];
+        key_pool[o + i] = k[i];
 }
 
 // Field-of-view gate (slam.py:875-899) for every point of one cloud against n_src source frames:
@@ -348,20 +357,35 @@ __global__ __launch_bounds__(256) void store_commit_keys_kernel(const int32_t *_
 // further from the bound than a float32 result can be from the true angle; a point that no frame selects for certain
 // and some frame leaves undecided is counted in *n_ambiguous, and the host then takes the numpy path for this cloud
 // (sfe_cloud_store_set_selection).  In practice: never (a bound hit to 1e-6 relative).
+// Many clouds per launch: job blockIdx.y = the cloud at pool offset off (its keys and selection bytes at the same offset)
+// against frames [f0, f1); its counters at counters + 2 j, its histogram at hist + j * n_keys.
 struct FovFrame {
     float T[6];
     double range_bound, bearing_bound;
 };
-__global__ __launch_bounds__(256) void store_fov_kernel(const float2 *__restrict__ pts, const int32_t *__restrict__ keys, int n,
-                                                        const FovFrame *__restrict__ frames, int n_frames, int n_keys,
-                                                        uint8_t *__restrict__ sel, int32_t *__restrict__ hist,
-                                                        int32_t *__restrict__ counters /* [0] selected, [1] ambiguous */)
+struct FovJob {
+    long long off;
+    int n, f0, f1;
+};
+__global__ __launch_bounds__(256) void store_fov_kernel(const float2 *__restrict__ pool, const int32_t *__restrict__ key_pool,
+                                                        const FovJob *__restrict__ jobs, const FovFrame *__restrict__ frames,
+                                                        int n_keys, uint8_t *__restrict__ sel_pool, int32_t *__restrict__ hist_,
+                                                        int32_t *__restrict__ counters_ /* [j][0] selected, [j][1] ambiguous */)
 {
+    const int j = blockIdx.y;
+    const FovJob jb = jobs[j];
+    if (blockIdx.x * 256 >= jb.n) // (the whole block: a cloud smaller than the largest of the call)
+        return;
+    const float2 *pts = pool + jb.off;
+    const int32_t *keys = key_pool + jb.off;
+    uint8_t *sel = sel_pool + jb.off;
+    int32_t *hist = hist_ + (size_t)j * n_keys, *counters = counters_ + 2 * (size_t)j;
+    const int n = jb.n;
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool yes = false, maybe = false;
     if (i < n) {
         const float2 p = pts[i];
-        for (int f = 0; f < n_frames; ++f) {
+        for (int f = jb.f0; f < jb.f1; ++f) {
             const FovFrame fr = frames[f];
             const float2 q = store_transform<false>(p, fr.T[0], fr.T[1], fr.T[2], fr.T[3], fr.T[4], fr.T[5]);
             // sqrtf, not __fsqrt_rn: the intrinsic lowers to a bare v_sqrt_f32 (1 ulp), sqrtf to the correctly rounded
@@ -392,13 +416,27 @@ __global__ __launch_bounds__(256) void store_fov_kernel(const float2 *__restrict
     }
 }
 
-// selected points of a cloud, order kept, with their keys: one workgroup, chunks of 1024 with a running base
-__global__ __launch_bounds__(1024) void store_compact_kernel(const float2 *__restrict__ pts, const int32_t *__restrict__ keys,
-                                                             const uint8_t *__restrict__ sel, int n, float2 *__restrict__ out,
-                                                             int32_t *__restrict__ out_key, int32_t *__restrict__ n_out)
+// selected points of a cloud, order kept, with their keys: one workgroup per cloud (job blockIdx.x: the cloud at pool
+// offset off, written to out + j * stride, its size to n_out[j]), chunks of 1024 with a running base
+struct CompactJob {
+    long long off;
+    int n;
+};
+__global__ __launch_bounds__(1024) void store_compact_kernel(const float2 *__restrict__ pool, const int32_t *__restrict__ key_pool,
+                                                             const uint8_t *__restrict__ sel_pool, const CompactJob *__restrict__ jobs,
+                                                             int stride, float2 *__restrict__ out_, int32_t *__restrict__ out_key_,
+                                                             int32_t *__restrict__ n_out_)
 {
     __shared__ int s_wave[16];
     __shared__ int s_base;
+    const int j = blockIdx.x;
+    const CompactJob jb = jobs[j];
+    const float2 *pts = pool + jb.off;
+    const int32_t *keys = key_pool + jb.off;
+    const uint8_t *sel = sel_pool + jb.off;
+    float2 *out = out_ + (size_t)j * stride;
+    int32_t *out_key = out_key_ + (size_t)j * stride, *n_out = n_out_ + j;
+    const int n = jb.n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0)
         s_base = 0;
@@ -433,17 +471,31 @@ __global__ __launch_bounds__(1024) void store_compact_kernel(const float2 *__res
 
 // get_overlap(source under a pose, target, return_indices=True) + the keys of the matched targets (slam.py:977-985):
 // pcl.match's neighbour = nearest target, lowest index among equals, within the radius; hist[key of it] += 1.
+// Many pairs per launch: job blockIdx.y = source at soff (ns points) under T against the keyed target at toff (nt);
+// its overlap at overlap[j], its histogram at hist + j * n_keys.
+struct MatchKeysJob {
+    long long soff, toff;
+    int ns, nt;
+    float T[6];
+};
 template <bool F64>
-__global__ __launch_bounds__(256) void store_match_keys_kernel(const float2 *__restrict__ src, int ns, const float2 *__restrict__ tgt,
-                                                               const int32_t *__restrict__ tkey, int nt, const float *__restrict__ T6,
-                                                               float r2, int n_keys, int32_t *__restrict__ hist,
-                                                               int32_t *__restrict__ overlap)
+__global__ __launch_bounds__(256) void store_match_keys_kernel(const float2 *__restrict__ pool, const int32_t *__restrict__ key_pool,
+                                                               const MatchKeysJob *__restrict__ jobs, float r2, int n_keys,
+                                                               int32_t *__restrict__ hist_, int32_t *__restrict__ overlap_)
 {
     __shared__ float2 s_ref[2048];
+    const int j = blockIdx.y;
+    const MatchKeysJob jb = jobs[j];
+    const int ns = jb.ns, nt = jb.nt;
+    if (blockIdx.x * 256 >= ns) // (the whole block: a source smaller than the largest of the call)
+        return;
+    const float2 *src = pool + jb.soff, *tgt = pool + jb.toff;
+    const int32_t *tkey = key_pool + jb.toff;
+    int32_t *hist = hist_ + (size_t)j * n_keys, *overlap = overlap_ + j;
     const int i = blockIdx.x * 256 + threadIdx.x;
     float2 q = make_float2(0.0f, 0.0f);
     if (i < ns)
-        q = store_transform<F64>(src[i], T6[0], T6[1], T6[2], T6[3], T6[4], T6[5]);
+        q = store_transform<F64>(src[i], jb.T[0], jb.T[1], jb.T[2], jb.T[3], jb.T[4], jb.T[5]);
     float best = INFINITY;
     int bi = -1;
     for (int tb = 0; tb < nt; tb += 2048) {
@@ -560,95 +612,125 @@ static int store_key_pool(sfe_cloud_store *s)
     return 0;
 }
 
-// One target cloud of ANY size, optionally with keys (the descriptor overload of pcl.downsample, pcl.cpp:143-159): the
-// concatenation is built in scratch, downsampled by the rank-sort chain of sfe_downsample.hip (indices come for free), and
-// appended as one new slot (+ its keys).  Enqueue only.
-static int store_get_points_big(sfe_cloud_store *s, const int32_t *handles, const float *T6, const int32_t *keys, int m,
-                                float resolution, int flags, int64_t stamp, int32_t *handle_out)
+// Target clouds of ANY size, optionally with keys (the descriptor overload of pcl.downsample, pcl.cpp:143-159), n_jobs of
+// them per call: job j = clouds handles[job_off[j] .. job_off[j + 1]) under their T6, tagged with their keys.  The
+// concatenations are built in scratch, job j at j * stride (stride = the largest job), downsampled by the rank-sort chain of
+// sfe_downsample.hip (indices come for free) in one launch per stage, and appended as n_jobs new slots (+ their keys).
+// One job is the n = 1 case: stride = its size, the single-cloud layout.  Enqueue only (the slot table must be synced).
+static int store_get_points_many(sfe_cloud_store *s, const int32_t *handles, const float *T6, const int32_t *keys,
+                                 const int32_t *job_off, int n_jobs, float resolution, int flags, const int64_t *stamps,
+                                 int32_t *handles_out)
 {
     sfe_ctx *ctx = s->ctx;
+    if (n_jobs <= 0)
+        return 0;
     std::vector<StoreSeg> segs;
-    long long total = 0;
-    for (int k = 0; k < m; ++k) {
-        const int h = handles[k];
-        if (h < 0)
-            continue;
-        if (h >= s->n_slots)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: cloud %d named, the store holds %d", h, s->n_slots);
-        if (s->cnt[h] < 0)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: cloud %d was not stored (count %d: -1 octree too deep, -3 pool full)",
-                               h, s->cnt[h]);
-        if (s->cnt[h] == 0)
-            continue;
-        StoreSeg sg;
-        sg.src = s->off[h];
-        sg.dst = total;
-        sg.n = s->cnt[h];
-        sg.key = keys ? keys[k] : 0;
-        memcpy(sg.T, T6 + 6 * (size_t)k, sizeof sg.T);
-        segs.push_back(sg);
-        total += sg.n;
+    std::vector<int32_t> job_n((size_t)n_jobs, 0);
+    long long stride = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (job_off[j + 1] < job_off[j])
+            return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: job %d has a negative number of clouds", j);
+        long long tot = 0;
+        for (int k = job_off[j]; k < job_off[j + 1]; ++k) {
+            const int h = handles[k];
+            if (h < 0)
+                continue;
+            if (h >= s->n_slots)
+                return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: cloud %d named, the store holds %d", h, s->n_slots);
+            if (s->cnt[h] < 0)
+                return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: cloud %d was not stored (count %d: -1 octree too deep, -3 pool full)",
+                                   h, s->cnt[h]);
+            tot += s->cnt[h];
+        }
+        if (tot >= (1ll << 31) - 1)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: %lld points in one target cloud", tot);
+        job_n[(size_t)j] = (int32_t)tot;
+        stride = std::max(stride, tot);
     }
-    if (total >= (1ll << 31) - 1)
-        return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: %lld points in one target cloud", total);
+    stride = std::max(stride, 1ll);
+    if ((long long)n_jobs * stride >= (1ll << 31) - 1)
+        return sfe_set_err(ctx, SFE_ERR_ARG, "get_points: %d jobs of up to %lld points in one call", n_jobs, stride);
+    for (int j = 0; j < n_jobs; ++j) {
+        long long dst = (long long)j * stride;
+        for (int k = job_off[j]; k < job_off[j + 1]; ++k) {
+            const int h = handles[k];
+            if (h < 0 || s->cnt[h] == 0)
+                continue;
+            StoreSeg sg;
+            sg.src = s->off[h];
+            sg.dst = dst;
+            sg.n = s->cnt[h];
+            sg.key = keys ? keys[k] : 0;
+            memcpy(sg.T, T6 + 6 * (size_t)k, sizeof sg.T);
+            segs.push_back(sg);
+            dst += sg.n;
+        }
+    }
     if (keys)
         if (int rc = store_key_pool(s))
             return rc;
-    const int n = (int)total;
-    const size_t cap = (size_t)std::max(n, 1);
+    const int n_max = (int)*std::max_element(job_n.begin(), job_n.end());
+    const size_t cap = (size_t)n_jobs * (size_t)stride;
     float2 *d_cat = (float2 *)sfe_scratch(ctx, 53, sizeof(float2) * cap);
     int32_t *d_catkey = keys ? (int32_t *)sfe_scratch(ctx, 54, sizeof(int32_t) * cap) : nullptr;
     float2 *d_out = (float2 *)sfe_scratch(ctx, 55, sizeof(float2) * cap);
     int32_t *d_oidx = (int32_t *)sfe_scratch(ctx, 56, sizeof(int32_t) * cap);
     int32_t *d_okey = keys ? (int32_t *)sfe_scratch(ctx, 57, sizeof(int32_t) * cap) : nullptr;
-    SfeDsHeader *d_hdr = (SfeDsHeader *)sfe_scratch(ctx, 58, sizeof(SfeDsHeader));
-    if (!d_cat || !d_out || !d_oidx || !d_hdr || (keys && (!d_catkey || !d_okey)))
+    SfeDsHeader *d_hdr = (SfeDsHeader *)sfe_scratch(ctx, 58, sizeof(SfeDsHeader) * (size_t)n_jobs);
+    int32_t *d_n = (int32_t *)sfe_scratch(ctx, 60, sizeof(int32_t) * 2 * (size_t)n_jobs); // [sizes in | sizes out]
+    if (!d_cat || !d_out || !d_oidx || !d_hdr || !d_n || (keys && (!d_catkey || !d_okey)))
         return SFE_ERR_HIP;
+    int32_t *d_cnt_out = d_n + n_jobs;
     const float2 *d_final = d_out;
     const int32_t *d_final_key = d_okey;
-    SFE_HIP(ctx, hipMemsetAsync(d_hdr, 0, sizeof(SfeDsHeader), ctx->stream)); // (n_seg = 0: an empty target)
-    if (n > 0) {
-        const size_t b_seg = sizeof(StoreSeg) * segs.size();
-        StoreSeg *h_seg = (StoreSeg *)sfe_pinned_begin(ctx, b_seg);
+    SFE_HIP(ctx, hipMemsetAsync(d_cnt_out, 0, sizeof(int32_t) * (size_t)n_jobs, ctx->stream)); // (an empty target)
+    if (n_max > 0) {
+        const size_t b_seg = sizeof(StoreSeg) * segs.size(), b_n = sizeof(int32_t) * (size_t)n_jobs;
+        char *h_up = (char *)sfe_pinned_begin(ctx, b_seg + b_n);
         StoreSeg *d_seg = (StoreSeg *)sfe_scratch(ctx, 59, b_seg);
-        if (!h_seg || !d_seg)
+        if (!h_up || !d_seg)
             return SFE_ERR_HIP;
-        memcpy(h_seg, segs.data(), b_seg);
-        SFE_HIP(ctx, hipMemcpyAsync(d_seg, h_seg, b_seg, hipMemcpyHostToDevice, ctx->stream));
+        memcpy(h_up, segs.data(), b_seg);
+        memcpy(h_up + b_seg, job_n.data(), b_n);
+        SFE_HIP(ctx, hipMemcpyAsync(d_seg, h_up, b_seg, hipMemcpyHostToDevice, ctx->stream));
+        SFE_HIP(ctx, hipMemcpyAsync(d_n, h_up + b_seg, b_n, hipMemcpyHostToDevice, ctx->stream));
         if (int rc = sfe_pinned_end(ctx, ctx->stream))
             return rc;
         auto cat = (flags & SFE_STORE_F32_POINTS) ? store_concat_kernel<false> : store_concat_kernel<true>;
-        hipLaunchKernelGGL(cat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const float2 *)s->d_pool,
-                           (const StoreSeg *)d_seg, (int)segs.size(), (long long)n, d_cat, d_catkey);
+        hipLaunchKernelGGL(cat, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, (const float2 *)s->d_pool,
+                           (const StoreSeg *)d_seg, (int)segs.size(), (long long)cap, d_cat, d_catkey);
         SFE_LAUNCH_CHECK(ctx);
         if (resolution > 0.0f) {
-            if (int rc = sfe_ds_run_dev(ctx, (const float *)d_cat, n, resolution, (float *)d_out, d_oidx, d_hdr))
+            if (int rc = sfe_ds_run_dev_many(ctx, (const float *)d_cat, n_jobs, n_jobs > 1 ? d_n : nullptr, n_max, (int)stride,
+                                             resolution, (float *)d_out, d_oidx, d_hdr, d_cnt_out))
                 return rc;
             if (keys) {
-                hipLaunchKernelGGL(store_pick_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (const int32_t *)d_catkey, (const int32_t *)d_oidx, (const int32_t *)&d_hdr->n_seg, d_okey);
+                hipLaunchKernelGGL(store_pick_keys_kernel, dim3((unsigned)((n_max + 255) / 256), n_jobs), dim3(256), 0, ctx->stream,
+                                   (const int32_t *)d_catkey, (const int32_t *)d_oidx, (const int32_t *)d_cnt_out, (int)stride,
+                                   d_okey);
                 SFE_LAUNCH_CHECK(ctx);
             }
         } else { // no downsample (SLAM.get_points never asks for this; kept for symmetry with the batched entry point)
-            SFE_HIP(ctx, hipMemcpyAsync(&d_hdr->n_seg, &n, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+            SFE_HIP(ctx, hipMemcpyAsync(d_cnt_out, d_n, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToDevice, ctx->stream));
             d_final = d_cat;
             d_final_key = d_catkey;
         }
     }
-    int32_t h_new = -1;
-    if (int rc = sfe_store_append_dev(s, &stamp, (const float *)d_final, (const int32_t *)&d_hdr->n_seg, 1, (int64_t)cap, 0, &h_new))
+    const int first = s->n_slots;
+    if (int rc = sfe_store_append_dev(s, stamps, (const float *)d_final, (const int32_t *)d_cnt_out, n_jobs, (int64_t)stride, 0,
+                                      handles_out))
         return rc;
-    if (keys && n > 0) {
-        hipLaunchKernelGGL(store_commit_keys_kernel, dim3(64), dim3(256), 0, ctx->stream, d_final_key, (const int64_t *)s->d_off,
-                           (const int32_t *)s->d_cnt, (int)h_new, s->d_key);
+    if (keys && n_max > 0) {
+        hipLaunchKernelGGL(store_commit_keys_kernel, dim3(64, n_jobs), dim3(256), 0, ctx->stream, d_final_key, (int)stride,
+                           (const int64_t *)s->d_off, (const int32_t *)s->d_cnt, first, s->d_key);
         SFE_LAUNCH_CHECK(ctx);
     }
-    if (keys && h_new >= 0) { // (an empty keyed cloud is keyed too: it has no keys to be wrong about)
-        if ((int32_t)s->keyed.size() <= h_new)
-            s->keyed.resize((size_t)h_new + 1, 0);
-        s->keyed[(size_t)h_new] = 1;
+    if (keys) { // (an empty keyed cloud is keyed too: it has no keys to be wrong about)
+        if ((int32_t)s->keyed.size() < s->n_slots)
+            s->keyed.resize((size_t)s->n_slots, 0);
+        for (int j = 0; j < n_jobs; ++j)
+            s->keyed[(size_t)(first + j)] = 1;
     }
-    *handle_out = h_new;
     return 0;
 }
 
@@ -795,8 +877,8 @@ int sfe_cloud_store_truncate(sfe_ctx *ctx, sfe_cloud_store *s, int32_t n_slots)
     SFE_LAUNCH_CHECK(ctx);
     s->n_slots = n_slots;
     s->n_synced = std::min(s->n_synced, n_slots);
-    if (s->sel_handle >= n_slots) // the cloud the selection belonged to is gone: its slot may come back as another cloud
-        s->sel_handle = -1;
+    if ((int32_t)s->sel_n.size() > n_slots) // the clouds the selections belonged to are gone: their slots may come back as others
+        s->sel_n.resize((size_t)n_slots);
     if ((int32_t)s->keyed.size() > n_slots)
         s->keyed.resize((size_t)n_slots);
     return 0;
@@ -832,11 +914,10 @@ int sfe_cloud_store_get_points(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *
     if (resolution > 0.0f && cap > CF_MAX_CAP) {
         // beyond the resident filter's capacity (16 index bits in its sort key): every job of the call, in order, through
         // the rank-sort path that knows no size limit (the NSSM target of a long session, slam.py:999)
-        for (int j = 0; j < n_jobs; ++j)
-            if (int rc = store_get_points_big(s, handles + (size_t)j * m, T6 + (size_t)j * m * 6, nullptr, m, resolution, flags,
-                                              stamps ? stamps[j] : 0, handles_out + j))
-                return rc;
-        return 0;
+        std::vector<int32_t> job_off((size_t)n_jobs + 1);
+        for (int j = 0; j <= n_jobs; ++j)
+            job_off[(size_t)j] = j * m;
+        return store_get_points_many(s, handles, T6, nullptr, job_off.data(), n_jobs, resolution, flags, stamps, handles_out);
     }
     const size_t nh = (size_t)n_jobs * m;
     const size_t b_tab = nh * (sizeof(int32_t) + 6 * sizeof(float));
@@ -870,12 +951,25 @@ int sfe_cloud_store_get_points(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *
 int sfe_cloud_store_get_points_keys(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, const float *T6,
                                     const int32_t *keys, int m, float resolution, int flags, int64_t stamp, int32_t *handle_out)
 {
+    const int32_t off[2] = {0, m};
+    SFE_ARG(ctx, m >= 0 && handle_out);
+    return sfe_cloud_store_get_points_keys_many(ctx, s, handles, T6, keys, off, 1, resolution, flags, &stamp, handle_out);
+}
+
+// the same for n_jobs keyed targets at once (chained.SessionBatch): job j = handles / T6 / keys [job_off[j], job_off[j + 1])
+int sfe_cloud_store_get_points_keys_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, const float *T6,
+                                         const int32_t *keys, const int32_t *job_off, int n_jobs, float resolution, int flags,
+                                         const int64_t *stamps, int32_t *handles_out)
+{
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, s && s->ctx == ctx && m >= 0 && handle_out && (m == 0 || (handles && T6 && keys)));
+    SFE_ARG(ctx, s && s->ctx == ctx && n_jobs >= 0 && (n_jobs == 0 || (job_off && handles_out)));
+    if (n_jobs == 0)
+        return 0;
+    SFE_ARG(ctx, job_off[0] == 0 && job_off[n_jobs] >= 0 && (job_off[n_jobs] == 0 || (handles && T6 && keys)));
     if (int rc = store_sync_meta(s))
         return rc;
-    return store_get_points_big(s, handles, T6, keys, m, resolution, flags, stamp, handle_out);
+    return store_get_points_many(s, handles, T6, keys, job_off, n_jobs, resolution, flags, stamps, handles_out);
 }
 
 static int store_keyed_cloud(sfe_cloud_store *s, int32_t handle, const char *what)
@@ -909,21 +1003,24 @@ int sfe_cloud_store_read_keys(sfe_ctx *ctx, sfe_cloud_store *s, int32_t handle, 
     return 0;
 }
 
-static int store_sel_buffer(sfe_cloud_store *s, size_t n)
+// the selection pool (a byte per pool point) and the record that `handle` holds a selection of its current size
+static int store_sel_pool(sfe_cloud_store *s)
 {
-    if (s->d_sel && s->sel_cap >= n)
-        return 0;
     if (s->d_sel)
-        (void)hipFree(s->d_sel);
-    s->d_sel = nullptr;
-    s->sel_cap = 0;
-    const size_t want = n + n / 4 + 4096;
-    if (hipMalloc((void **)&s->d_sel, want) != hipSuccess) {
+        return 0;
+    if (hipMalloc((void **)&s->d_sel, (size_t)std::max<int64_t>(s->capacity, 1)) != hipSuccess) {
         s->d_sel = nullptr;
-        return sfe_set_err(s->ctx, SFE_ERR_HIP, "cloud store: allocating the selection buffer (%zu) failed", want);
+        return sfe_set_err(s->ctx, SFE_ERR_HIP, "cloud store: allocating the selection pool (%lld points) failed",
+                           (long long)s->capacity);
     }
-    s->sel_cap = want;
     return 0;
+}
+
+static void store_mark_selected(sfe_cloud_store *s, int32_t handle)
+{
+    if ((int32_t)s->sel_n.size() < s->n_slots)
+        s->sel_n.resize((size_t)s->n_slots, -1);
+    s->sel_n[(size_t)handle] = s->cnt[handle];
 }
 
 // slam.py:875-899 + :902: frames = n_frames x {Tinv[6] float32 of pose.inverse().matrix(), range_bound, bearing_bound};
@@ -932,45 +1029,77 @@ int sfe_cloud_store_fov_select(sfe_ctx *ctx, sfe_cloud_store *s, int32_t handle,
                                const double *bearing_bound, int n_frames, int n_keys, int32_t *key_counts_out,
                                int32_t *n_selected_out, int32_t *n_ambiguous_out)
 {
+    const int32_t off[2] = {0, n_frames};
+    SFE_ARG(ctx, n_frames >= 0);
+    return sfe_cloud_store_fov_select_many(ctx, s, &handle, 1, Tinv6, range_bound, bearing_bound, off, n_keys, key_counts_out,
+                                           n_selected_out, n_ambiguous_out);
+}
+
+// the gate for n_jobs keyed clouds in one launch: job j = handles[j] against frames [frame_off[j], frame_off[j + 1]);
+// key_counts_out[j * n_keys ..], n_selected_out[j], n_ambiguous_out[j]
+int sfe_cloud_store_fov_select_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n_jobs, const float *Tinv6,
+                                    const double *range_bound, const double *bearing_bound, const int32_t *frame_off,
+                                    int n_keys, int32_t *key_counts_out, int32_t *n_selected_out, int32_t *n_ambiguous_out)
+{
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, s && s->ctx == ctx && n_frames >= 0 && n_keys >= 0 && n_selected_out && n_ambiguous_out &&
-                     (n_frames == 0 || (Tinv6 && range_bound && bearing_bound)) && (n_keys == 0 || key_counts_out));
-    if (int rc = store_keyed_cloud(s, handle, "fov_select"))
+    SFE_ARG(ctx, s && s->ctx == ctx && n_jobs >= 0 && n_keys >= 0);
+    if (n_jobs == 0)
+        return 0;
+    SFE_ARG(ctx, handles && frame_off && n_selected_out && n_ambiguous_out && frame_off[0] == 0 && (n_keys == 0 || key_counts_out));
+    const int n_frames = frame_off[n_jobs];
+    SFE_ARG(ctx, n_frames >= 0 && (n_frames == 0 || (Tinv6 && range_bound && bearing_bound)));
+    for (int j = 0; j < n_jobs; ++j) {
+        SFE_ARG(ctx, frame_off[j + 1] >= frame_off[j]);
+        if (int rc = store_keyed_cloud(s, handles[j], "fov_select"))
+            return rc;
+    }
+    if (int rc = store_sel_pool(s))
         return rc;
-    const int n = s->cnt[handle];
-    if (int rc = store_sel_buffer(s, (size_t)std::max(n, 1)))
-        return rc;
-    s->sel_handle = handle;
-    s->sel_count = n;
-    const size_t b_fr = sizeof(FovFrame) * (size_t)std::max(n_frames, 1), b_out = sizeof(int32_t) * ((size_t)n_keys + 2);
-    FovFrame *h_fr = (FovFrame *)sfe_pinned_begin(ctx, b_fr);
-    FovFrame *d_fr = (FovFrame *)sfe_scratch(ctx, 59, b_fr);
+    int n_max = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        n_max = std::max(n_max, s->cnt[handles[j]]);
+        store_mark_selected(s, handles[j]);
+    }
+    const size_t b_fr = sizeof(FovFrame) * (size_t)std::max(n_frames, 1), b_job = sizeof(FovJob) * (size_t)n_jobs;
+    const size_t n_out = 2 * (size_t)n_jobs + (size_t)n_jobs * (size_t)n_keys, b_out = sizeof(int32_t) * n_out;
+    char *h_up = (char *)sfe_pinned_begin(ctx, b_fr + b_job);
+    char *d_up = (char *)sfe_scratch(ctx, 59, b_fr + b_job);
     int32_t *d_out = (int32_t *)sfe_scratch(ctx, 60, b_out);
     int32_t *h_out = (int32_t *)sfe_pinned_io(ctx, 3, b_out);
-    if (!h_fr || !d_fr || !d_out || !h_out)
+    if (!h_up || !d_up || !d_out || !h_out)
         return SFE_ERR_HIP;
+    FovFrame *h_fr = (FovFrame *)h_up;
+    FovJob *h_job = (FovJob *)(h_up + b_fr);
     for (int f = 0; f < n_frames; ++f) {
         memcpy(h_fr[f].T, Tinv6 + 6 * (size_t)f, sizeof h_fr[f].T);
         h_fr[f].range_bound = range_bound[f];
         h_fr[f].bearing_bound = bearing_bound[f];
     }
-    SFE_HIP(ctx, hipMemcpyAsync(d_fr, h_fr, b_fr, hipMemcpyHostToDevice, ctx->stream));
+    for (int j = 0; j < n_jobs; ++j) {
+        h_job[j].off = s->off[handles[j]];
+        h_job[j].n = s->cnt[handles[j]];
+        h_job[j].f0 = frame_off[j];
+        h_job[j].f1 = frame_off[j + 1];
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(d_up, h_up, b_fr + b_job, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = sfe_pinned_end(ctx, ctx->stream))
         return rc;
     SFE_HIP(ctx, hipMemsetAsync(d_out, 0, b_out, ctx->stream));
-    if (n > 0) {
-        hipLaunchKernelGGL(store_fov_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const float2 *)(s->d_pool + s->off[handle]), (const int32_t *)(s->d_key + s->off[handle]), n,
-                           (const FovFrame *)d_fr, n_frames, n_keys, s->d_sel, d_out + 2, d_out);
+    if (n_max > 0) {
+        hipLaunchKernelGGL(store_fov_kernel, dim3((unsigned)((n_max + 255) / 256), n_jobs), dim3(256), 0, ctx->stream,
+                           (const float2 *)s->d_pool, (const int32_t *)s->d_key, (const FovJob *)(d_up + b_fr),
+                           (const FovFrame *)d_up, n_keys, s->d_sel, d_out + 2 * (size_t)n_jobs, d_out);
         SFE_LAUNCH_CHECK(ctx);
     }
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *n_selected_out = h_out[0];
-    *n_ambiguous_out = h_out[1];
+    for (int j = 0; j < n_jobs; ++j) {
+        n_selected_out[j] = h_out[2 * j];
+        n_ambiguous_out[j] = h_out[2 * j + 1];
+    }
     if (n_keys)
-        memcpy(key_counts_out, h_out + 2, sizeof(int32_t) * (size_t)n_keys);
+        memcpy(key_counts_out, h_out + 2 * (size_t)n_jobs, sizeof(int32_t) * (size_t)n_jobs * (size_t)n_keys);
     return 0;
 }
 
@@ -983,12 +1112,11 @@ int sfe_cloud_store_set_selection(sfe_ctx *ctx, sfe_cloud_store *s, int32_t hand
     if (int rc = store_keyed_cloud(s, handle, "set_selection"))
         return rc;
     SFE_ARG(ctx, n == s->cnt[handle]);
-    if (int rc = store_sel_buffer(s, (size_t)std::max(n, 1)))
+    if (int rc = store_sel_pool(s))
         return rc;
-    s->sel_handle = handle;
-    s->sel_count = n;
+    store_mark_selected(s, handle);
     if (n) {
-        SFE_HIP(ctx, hipMemcpyAsync(s->d_sel, sel, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+        SFE_HIP(ctx, hipMemcpyAsync(s->d_sel + s->off[handle], sel, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
         SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (pageable source)
     }
     return 0;
@@ -997,36 +1125,57 @@ int sfe_cloud_store_set_selection(sfe_ctx *ctx, sfe_cloud_store *s, int32_t hand
 // target_points[sel], target_keys[sel] (slam.py:898-899) as a new slot with keys
 int sfe_cloud_store_compact_selected(sfe_ctx *ctx, sfe_cloud_store *s, int32_t handle, int64_t stamp, int32_t *handle_out)
 {
+    SFE_ARG(ctx, handle_out);
+    return sfe_cloud_store_compact_selected_many(ctx, s, &handle, 1, &stamp, handle_out);
+}
+
+// the same for n_jobs clouds in one launch (a workgroup per cloud) -> n_jobs new keyed slots
+int sfe_cloud_store_compact_selected_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n_jobs,
+                                          const int64_t *stamps, int32_t *handles_out)
+{
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, s && s->ctx == ctx && handle_out);
-    if (int rc = store_keyed_cloud(s, handle, "compact_selected"))
-        return rc;
-    if (s->sel_handle != handle || s->sel_count != s->cnt[handle])
-        return sfe_set_err(ctx, SFE_ERR_ARG, "compact_selected: cloud %d has no selection (the last one was made for cloud %d of %d "
-                           "points)", handle, s->sel_handle, s->sel_count);
-    const int n = s->cnt[handle];
-    const size_t cap = (size_t)std::max(n, 1);
+    SFE_ARG(ctx, s && s->ctx == ctx && n_jobs >= 0 && (n_jobs == 0 || (handles && handles_out)));
+    if (n_jobs == 0)
+        return 0;
+    int stride = 1;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t h = handles[j];
+        if (int rc = store_keyed_cloud(s, h, "compact_selected"))
+            return rc;
+        if (!s->d_sel || h >= (int32_t)s->sel_n.size() || s->sel_n[(size_t)h] != s->cnt[h])
+            return sfe_set_err(ctx, SFE_ERR_ARG, "compact_selected: cloud %d of %d points has no selection (none was made for it "
+                               "at its current size)", h, s->cnt[h]);
+        stride = std::max(stride, s->cnt[h]);
+    }
+    const size_t cap = (size_t)n_jobs * (size_t)stride, b_job = sizeof(CompactJob) * (size_t)n_jobs;
     float2 *d_out = (float2 *)sfe_scratch(ctx, 55, sizeof(float2) * cap);
     int32_t *d_okey = (int32_t *)sfe_scratch(ctx, 57, sizeof(int32_t) * cap);
-    int32_t *d_n = (int32_t *)sfe_scratch(ctx, 58, sizeof(SfeDsHeader));
-    if (!d_out || !d_okey || !d_n)
+    int32_t *d_n = (int32_t *)sfe_scratch(ctx, 58, sizeof(int32_t) * (size_t)n_jobs);
+    CompactJob *h_job = (CompactJob *)sfe_pinned_begin(ctx, b_job);
+    CompactJob *d_job = (CompactJob *)sfe_scratch(ctx, 59, b_job);
+    if (!d_out || !d_okey || !d_n || !h_job || !d_job)
         return SFE_ERR_HIP;
-    hipLaunchKernelGGL(store_compact_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float2 *)(s->d_pool + s->off[handle]),
-                       (const int32_t *)(s->d_key + s->off[handle]), (const uint8_t *)s->d_sel, n, d_out, d_okey, d_n);
-    SFE_LAUNCH_CHECK(ctx);
-    int32_t h_new = -1;
-    if (int rc = sfe_store_append_dev(s, &stamp, (const float *)d_out, d_n, 1, (int64_t)cap, 0, &h_new))
-        return rc;
-    hipLaunchKernelGGL(store_commit_keys_kernel, dim3(64), dim3(256), 0, ctx->stream, (const int32_t *)d_okey,
-                       (const int64_t *)s->d_off, (const int32_t *)s->d_cnt, (int)h_new, s->d_key);
-    SFE_LAUNCH_CHECK(ctx);
-    if (h_new >= 0) {
-        if ((int32_t)s->keyed.size() <= h_new)
-            s->keyed.resize((size_t)h_new + 1, 0);
-        s->keyed[(size_t)h_new] = 1;
+    for (int j = 0; j < n_jobs; ++j) {
+        h_job[j].off = s->off[handles[j]];
+        h_job[j].n = s->cnt[handles[j]];
     }
-    *handle_out = h_new;
+    SFE_HIP(ctx, hipMemcpyAsync(d_job, h_job, b_job, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = sfe_pinned_end(ctx, ctx->stream))
+        return rc;
+    hipLaunchKernelGGL(store_compact_kernel, dim3(n_jobs), dim3(1024), 0, ctx->stream, (const float2 *)s->d_pool,
+                       (const int32_t *)s->d_key, (const uint8_t *)s->d_sel, (const CompactJob *)d_job, stride, d_out, d_okey, d_n);
+    SFE_LAUNCH_CHECK(ctx);
+    const int first = s->n_slots;
+    if (int rc = sfe_store_append_dev(s, stamps, (const float *)d_out, d_n, n_jobs, (int64_t)stride, 0, handles_out))
+        return rc;
+    hipLaunchKernelGGL(store_commit_keys_kernel, dim3(64, n_jobs), dim3(256), 0, ctx->stream, (const int32_t *)d_okey, stride,
+                       (const int64_t *)s->d_off, (const int32_t *)s->d_cnt, first, s->d_key);
+    SFE_LAUNCH_CHECK(ctx);
+    if ((int32_t)s->keyed.size() < s->n_slots)
+        s->keyed.resize((size_t)s->n_slots, 0);
+    for (int j = 0; j < n_jobs; ++j)
+        s->keyed[(size_t)(first + j)] = 1;
     return 0;
 }
 
@@ -1034,43 +1183,63 @@ int sfe_cloud_store_compact_selected(sfe_ctx *ctx, sfe_cloud_store *s, int32_t h
 int sfe_cloud_store_match_keys(sfe_ctx *ctx, sfe_cloud_store *s, int32_t source, const float *T6, int32_t target, float max_dist,
                                int flags, int n_keys, int32_t *key_counts_out, int32_t *overlap_out)
 {
+    return sfe_cloud_store_match_keys_many(ctx, s, &source, T6, &target, 1, max_dist, flags, n_keys, key_counts_out, overlap_out);
+}
+
+// the same for n_jobs (source, T6[j * 6 ..], keyed target) triples in one launch: key_counts_out[j * n_keys ..], overlap_out[j]
+int sfe_cloud_store_match_keys_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *sources, const float *T6,
+                                    const int32_t *targets, int n_jobs, float max_dist, int flags, int n_keys,
+                                    int32_t *key_counts_out, int32_t *overlap_out)
+{
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, s && s->ctx == ctx && T6 && overlap_out && n_keys >= 0 && (n_keys == 0 || key_counts_out));
-    if (int rc = store_keyed_cloud(s, target, "match_keys"))
-        return rc;
-    if (source < 0 || source >= s->n_slots || s->cnt[source] < 0)
-        return sfe_set_err(ctx, SFE_ERR_ARG, "match_keys: source cloud %d does not exist or was not stored", source);
-    const int ns = s->cnt[source], nt = s->cnt[target];
-    const size_t b_out = sizeof(int32_t) * ((size_t)n_keys + 1);
-    float *h_T = (float *)sfe_pinned_begin(ctx, 6 * sizeof(float));
-    float *d_T = (float *)sfe_scratch(ctx, 59, 6 * sizeof(float));
+    SFE_ARG(ctx, s && s->ctx == ctx && n_jobs >= 0 && n_keys >= 0);
+    if (n_jobs == 0)
+        return 0;
+    SFE_ARG(ctx, sources && targets && T6 && overlap_out && (n_keys == 0 || key_counts_out));
+    int ns_max = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        if (int rc = store_keyed_cloud(s, targets[j], "match_keys"))
+            return rc;
+        const int32_t src = sources[j];
+        if (src < 0 || src >= s->n_slots || s->cnt[src] < 0)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "match_keys: source cloud %d does not exist or was not stored", src);
+        ns_max = std::max(ns_max, s->cnt[src]);
+    }
+    const size_t b_job = sizeof(MatchKeysJob) * (size_t)n_jobs;
+    const size_t b_out = sizeof(int32_t) * ((size_t)n_jobs + (size_t)n_jobs * (size_t)n_keys);
+    MatchKeysJob *h_job = (MatchKeysJob *)sfe_pinned_begin(ctx, b_job);
+    MatchKeysJob *d_job = (MatchKeysJob *)sfe_scratch(ctx, 59, b_job);
     int32_t *d_out = (int32_t *)sfe_scratch(ctx, 60, b_out);
     int32_t *h_out = (int32_t *)sfe_pinned_io(ctx, 3, b_out);
-    if (!h_T || !d_T || !d_out || !h_out)
+    if (!h_job || !d_job || !d_out || !h_out)
         return SFE_ERR_HIP;
-    memcpy(h_T, T6, 6 * sizeof(float));
-    SFE_HIP(ctx, hipMemcpyAsync(d_T, h_T, 6 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    for (int j = 0; j < n_jobs; ++j) {
+        h_job[j].soff = s->off[sources[j]];
+        h_job[j].toff = s->off[targets[j]];
+        h_job[j].ns = s->cnt[sources[j]];
+        h_job[j].nt = s->cnt[targets[j]];
+        memcpy(h_job[j].T, T6 + 6 * (size_t)j, sizeof h_job[j].T);
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(d_job, h_job, b_job, hipMemcpyHostToDevice, ctx->stream));
     if (int rc = sfe_pinned_end(ctx, ctx->stream))
         return rc;
     SFE_HIP(ctx, hipMemsetAsync(d_out, 0, b_out, ctx->stream));
-    if (ns > 0) {
+    if (ns_max > 0) {
         auto mk = (flags & SFE_STORE_F32_POINTS) ? store_match_keys_kernel<false> : store_match_keys_kernel<true>;
-        hipLaunchKernelGGL(mk, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const float2 *)(s->d_pool + s->off[source]), ns, (const float2 *)(s->d_pool + s->off[target]),
-                           (const int32_t *)(s->d_key + s->off[target]), nt, (const float *)d_T, max_dist * max_dist, n_keys,
-                           d_out + 1, d_out);
+        hipLaunchKernelGGL(mk, dim3((unsigned)((ns_max + 255) / 256), n_jobs), dim3(256), 0, ctx->stream, (const float2 *)s->d_pool,
+                           (const int32_t *)s->d_key, (const MatchKeysJob *)d_job, max_dist * max_dist, n_keys,
+                           d_out + n_jobs, d_out);
         SFE_LAUNCH_CHECK(ctx);
     }
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *overlap_out = h_out[0];
+    memcpy(overlap_out, h_out, sizeof(int32_t) * (size_t)n_jobs);
     if (n_keys)
-        memcpy(key_counts_out, h_out + 1, sizeof(int32_t) * (size_t)n_keys);
+        memcpy(key_counts_out, h_out + n_jobs, sizeof(int32_t) * (size_t)n_jobs * (size_t)n_keys);
     return 0;
 }
 
-// jobs over handles -> the job table of the ICP launcher (sizes from the mirrored slot table; sfe_internal.h)
 int sfe_store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4)
 {
     sfe_ctx *ctx = s->ctx;

@@ -116,6 +116,65 @@ class ChainBackend(object):
         return add if prev_cov is None else prev_cov + add
 
 
+def icp_result(T, status):
+    """what SLAM.compute_icp (slam.py:294-323) makes of one ICP result over handles: (message, Pose2 from the float32 matrix)"""
+    message = _L.ICP_STATUS_MESSAGES.get(int(status), "ICP failure %d" % status)
+    x, y = T[:2, 2]
+    return message, Pose2(x, y, np.arctan2(T[1, 0], T[0, 0]))
+
+
+def robust_covariance(Ts, ok, random_state, icp_odom_sigmas):
+    """The MinCovDet step of compute_icp_with_cov (slam.py:346-387) on the transforms of the guesses [n x 3 x 3] and which of
+    them converged [n] -> (message, centre Pose2, cov 3 x 3, converged transforms [n x 3] float32)"""
+    from sklearn.covariance import MinCovDet
+    Ts = np.asarray(Ts, np.float32)[np.asarray(ok, bool)]
+    # x, y = T[:2, 2]; theta = np.arctan2(T[1, 0], T[0, 0]) on the float32 matrix; np.array of tuples of np.float32 scalars
+    # STAYS float32 (slam.py:352-361), and MinCovDet then takes its location as a float32 mean (its covariance in double):
+    # pinned by tests/golden/nssm_pieces.npz -- rounds 1-5 cast to float64 here and were 6e-8 off the reference's centre
+    xyt = np.c_[Ts[:, 0, 2], Ts[:, 1, 2], np.arctan2(Ts[:, 1, 0], Ts[:, 0, 0])].astype(np.float32) if len(Ts) else np.zeros((0, 3), np.float32)
+    if len(xyt) < 5:
+        return "Too few samples for covariance computation", None, None, None
+    try:
+        est = MinCovDet(store_precision=False, support_fraction=0.8, random_state=random_state).fit(xyt)
+    except ValueError:
+        return "Failed to calculate covariance", None, None, None
+    centre = Pose2(float(est.location_[0]), float(est.location_[1]), float(est.location_[2]))
+    cov = est.covariance_
+    R = np.asarray(centre.matrix())[:2, :2]                     # m.rotation().matrix()
+    cov[:2, :] = R.T.dot(cov[:2, :])                            # slam.py:378-380
+    cov[:, :2] = cov[:, :2].dot(R)
+    floor = np.diag(icp_odom_sigmas) ** 2                       # never more confident than the configured sigmas
+    if np.linalg.det(cov) < np.linalg.det(floor):
+        cov = floor
+    return "success", centre, cov, xyt
+
+
+def fov_bounds(poses, covs, oculus_max_range, oculus_horizontal_aperture):
+    """slam.py:879-888 for the source frames' poses and marginal covariances -> (inverse poses, range bounds, bearing bounds)"""
+    Tinv, rb, bb = [], [], []
+    for pose, cov in zip(poses, covs):
+        translation_std = np.sqrt(np.max(np.linalg.eigvals(cov[:2, :2])))
+        rotation_std = np.sqrt(cov[2, 2])
+        rb.append(translation_std * 5.0 + oculus_max_range)                    # slam.py:885-888
+        bb.append(rotation_std * 5.0 + oculus_horizontal_aperture * 0.5)
+        Tinv.append(pose.inverse())
+    return Tinv, rb, bb
+
+
+def nssm_pose_bounds(cov):
+    """slam.py:929-932: shgo's bounds of the loop-closure search from the covariance the gate's loop left behind"""
+    translation_std = np.sqrt(np.max(np.linalg.eigvals(cov[:2, :2])))
+    rotation_std = np.sqrt(cov[2, 2])
+    pose_stds = np.array([[translation_std, translation_std, rotation_std]]).T
+    return 5.0 * np.c_[-pose_stds, pose_stds]
+
+
+def large_transformation(initial_transform, estimated, max_translation, max_rotation):
+    """slam.py:786-792 / :1066-1077: the estimate strays too far from where the search began"""
+    delta = initial_transform.between(estimated)
+    return bool(np.linalg.norm(np.array([delta.x(), delta.y()])) > max_translation or abs(delta.theta()) > max_rotation)
+
+
 class FrontEnd(object):
     """The sequential-scan-matching half of ``SLAM`` (slam.py), parameters from config/slam.yaml."""
 
@@ -222,9 +281,7 @@ class FrontEnd(object):
         if self.store is not None:
             T, st, _ = self.store.icp(self._store_chain(), [(source_points.handle, target_points.handle)],
                                       [pcl.ICP._guess(guess.matrix())])
-            message, T = _L.ICP_STATUS_MESSAGES.get(int(st[0]), "ICP failure %d" % st[0]), T[0]
-            x, y = T[:2, 2]
-            return message, Pose2(x, y, np.arctan2(T[1, 0], T[0, 0]))
+            return icp_result(T[0], st[0])
         source_points = np.array(source_points, np.float32)
         target_points = np.array(target_points, np.float32)
         message, T = self.icp.compute(source_points, target_points, guess.matrix())
@@ -239,7 +296,6 @@ class FrontEnd(object):
         ``sfe_icp_store_compute`` over handles: the target is prepared once) instead of a timed Python loop of
         ``compute`` calls (the 2 s budget of :346-358 is never in reach).
         -> (message, centre Pose2, cov 3 x 3, converged transforms [n x 3]); the messages are the reference's."""
-        from sklearn.covariance import MinCovDet
         if not len(guesses):
             return "Too few samples for covariance computation", None, None, None
         if self.store is not None:
@@ -250,26 +306,7 @@ class FrontEnd(object):
             msgs, Ts, _ = self.icp.compute_batch(np.asarray(source_points, np.float32), np.asarray(target_points, np.float32),
                                                  [g.matrix() for g in guesses])
             ok = np.array([m == "success" for m in msgs], bool)
-        Ts = np.asarray(Ts, np.float32)[ok]
-        # x, y = T[:2, 2]; theta = np.arctan2(T[1, 0], T[0, 0]) on the float32 matrix; np.array of tuples of np.float32 scalars
-        # STAYS float32 (slam.py:352-361), and MinCovDet then takes its location as a float32 mean (its covariance in double):
-        # pinned by tests/golden/nssm_pieces.npz -- rounds 1-5 cast to float64 here and were 6e-8 off the reference's centre
-        xyt = np.c_[Ts[:, 0, 2], Ts[:, 1, 2], np.arctan2(Ts[:, 1, 0], Ts[:, 0, 0])].astype(np.float32) if len(Ts) else np.zeros((0, 3), np.float32)
-        if len(xyt) < 5:
-            return "Too few samples for covariance computation", None, None, None
-        try:
-            est = MinCovDet(store_precision=False, support_fraction=0.8, random_state=self.mcd_random_state).fit(xyt)
-        except ValueError:
-            return "Failed to calculate covariance", None, None, None
-        centre = self._as_pose(est.location_)
-        cov = est.covariance_
-        R = np.asarray(centre.matrix())[:2, :2]                     # m.rotation().matrix()
-        cov[:2, :] = R.T.dot(cov[:2, :])                            # slam.py:378-380
-        cov[:, :2] = cov[:, :2].dot(R)
-        floor = np.diag(self.icp_odom_sigmas) ** 2                  # never more confident than the configured sigmas
-        if np.linalg.det(cov) < np.linalg.det(floor):
-            cov = floor
-        return "success", centre, cov, xyt
+        return robust_covariance(Ts, ok, self.mcd_random_state, self.icp_odom_sigmas)
 
     @staticmethod
     def _as_pose(xytheta):
@@ -453,15 +490,8 @@ class FrontEnd(object):
         return pcl.downsample(all_points[:, :2], all_points[:, (2,)], self.point_resolution)
 
     def _fov_bounds(self, source_frames):
-        Tinv, rb, bb = [], [], []
-        for f in source_frames:
-            pose, cov = self.keyframes[f].pose, self.keyframes[f].cov
-            translation_std = np.sqrt(np.max(np.linalg.eigvals(cov[:2, :2])))
-            rotation_std = np.sqrt(cov[2, 2])
-            rb.append(translation_std * 5.0 + self.oculus_max_range)                    # slam.py:885-888
-            bb.append(rotation_std * 5.0 + self.oculus_horizontal_aperture * 0.5)
-            Tinv.append(pose.inverse())
-        return Tinv, rb, bb
+        return fov_bounds([self.keyframes[f].pose for f in source_frames], [self.keyframes[f].cov for f in source_frames],
+                          self.oculus_max_range, self.oculus_horizontal_aperture)
 
     @staticmethod
     def _fov_numpy(target_points, Tinv, rb, bb):
@@ -535,11 +565,7 @@ class FrontEnd(object):
         cov = self.keyframes[source_key].cov
         estimated_source_pose, pose_samples = source_pose, None
         if self.nssm_initialization:
-            c = self.keyframes[source_frames[-1]].cov       # slam.py:929: `cov` is what the gate's loop left behind
-            translation_std = np.sqrt(np.max(np.linalg.eigvals(c[:2, :2])))
-            rotation_std = np.sqrt(c[2, 2])
-            pose_stds = np.array([[translation_std, translation_std, rotation_std]]).T
-            pose_bounds = 5.0 * np.c_[-pose_stds, pose_stds]
+            pose_bounds = nssm_pose_bounds(self.keyframes[source_frames[-1]].cov)   # slam.py:929: the gate loop's last `cov`
             subroutine, pose_samples = self.matching_cost_subroutine(source_points, source_pose, target_local, target_pose, cov,
                                                                      f64_source=False)
             try:
@@ -592,8 +618,7 @@ class FrontEnd(object):
                 rec["status"] = "NOT_CONVERGED"
                 return
         rec["transform"] = (odom.x(), odom.y(), odom.theta())
-        delta = initial_transform.between(odom)                                 # slam.py:1066-1077
-        if (np.linalg.norm(np.array([delta.x(), delta.y()])) > self.nssm_max_translation or abs(delta.theta()) > self.nssm_max_rotation):
+        if large_transformation(initial_transform, odom, self.nssm_max_translation, self.nssm_max_rotation):   # slam.py:1066-1077
             rec["status"] = "LARGE_TRANSFORMATION"
             return
         overlap = self.get_overlap(source_points, target_local, odom, f32_source=True)

@@ -228,6 +228,76 @@ class CloudStore(object):
                 int(n_keys), _L.ptr(hist, _C.c_int32), _C.byref(ov)))
         return hist, ov.value
 
+    # -- the same for many clouds at once (chained.SessionBatch: the search of every session in lock-step) --
+    def get_points_keys_many(self, handles, T6, keys, resolution, flags=0, stamps=None):
+        """``get_points_keys`` for n_jobs keyed targets in one call: handles / T6 / keys are lists (one entry per job) of
+        what ``get_points_keys`` takes -> new handles [n_jobs]"""
+        n_jobs = len(handles)
+        m = np.array([len(h) for h in handles], np.int32)
+        off = np.ascontiguousarray(np.r_[0, np.cumsum(m)], np.int32)
+        hs = np.ascontiguousarray(np.concatenate([np.asarray(h, np.int32).reshape(-1) for h in handles]) if n_jobs else
+                                  np.zeros(0), np.int32)
+        T = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float32).reshape(-1, 6) for t in T6]) if n_jobs else
+                                 np.zeros((0, 6)), np.float32).reshape(-1, 6)
+        ks = np.ascontiguousarray(np.concatenate([np.asarray(k, np.int32).reshape(-1) for k in keys]) if n_jobs else
+                                  np.zeros(0), np.int32)
+        assert len(hs) == len(T) == len(ks) == off[-1]
+        st = None if stamps is None else np.ascontiguousarray(stamps, np.int64).reshape(n_jobs)
+        out = np.full(n_jobs, -1, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_get_points_keys_many(
+                self.ctx.handle, self.handle, _L.ptr(hs, _C.c_int32), _L.ptr(T, _C.c_float), _L.ptr(ks, _C.c_int32),
+                _L.ptr(off, _C.c_int32), n_jobs, float(resolution), int(flags), None if st is None else _L.ptr(st, _C.c_int64),
+                _L.ptr(out, _C.c_int32)))
+        return out
+
+    def fov_select_many(self, handles, Tinv6, range_bounds, bearing_bounds, n_keys):
+        """``fov_select`` for n_jobs keyed clouds in one launch: Tinv6 / range_bounds / bearing_bounds are lists (one entry per
+        job, any number of frames each) -> (per-key counts [n_jobs x n_keys], selected [n_jobs], undecided [n_jobs])"""
+        h = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        n_jobs = len(h)
+        nf = np.array([len(np.asarray(r).reshape(-1)) for r in range_bounds], np.int32)
+        off = np.ascontiguousarray(np.r_[0, np.cumsum(nf)], np.int32)
+        cat = (lambda xs, dt, w: np.ascontiguousarray(np.concatenate([np.asarray(x, dt).reshape(-1, w) for x in xs]) if n_jobs else
+                                                     np.zeros((0, w)), dt))
+        T, rb, bb = cat(Tinv6, np.float32, 6), cat(range_bounds, np.float64, 1), cat(bearing_bounds, np.float64, 1)
+        assert len(T) == len(rb) == len(bb) == off[-1] and len(nf) == n_jobs
+        hist = np.zeros((n_jobs, int(n_keys)), np.int32)
+        n_sel, n_amb = np.zeros(n_jobs, np.int32), np.zeros(n_jobs, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_fov_select_many(
+                self.ctx.handle, self.handle, _L.ptr(h, _C.c_int32), n_jobs, _L.ptr(T, _C.c_float), _L.ptr(rb, _C.c_double),
+                _L.ptr(bb, _C.c_double), _L.ptr(off, _C.c_int32), int(n_keys), _L.ptr(hist, _C.c_int32),
+                _L.ptr(n_sel, _C.c_int32), _L.ptr(n_amb, _C.c_int32)))
+        return hist, n_sel, n_amb
+
+    def compact_selected_many(self, handles, stamps=None):
+        """``compact_selected`` for n_jobs clouds in one launch -> new keyed handles [n_jobs]"""
+        h = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        st = None if stamps is None else np.ascontiguousarray(stamps, np.int64).reshape(len(h))
+        out = np.full(len(h), -1, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_compact_selected_many(
+                self.ctx.handle, self.handle, _L.ptr(h, _C.c_int32), len(h), None if st is None else _L.ptr(st, _C.c_int64),
+                _L.ptr(out, _C.c_int32)))
+        return out
+
+    def match_keys_many(self, sources, T6, targets, max_dist, n_keys, flags=0):
+        """``match_keys`` for n_jobs (source, T6 [6], keyed target) triples in one launch -> (per-key counts [n_jobs x n_keys],
+        overlaps [n_jobs])"""
+        src = np.ascontiguousarray(sources, np.int32).reshape(-1)
+        tgt = np.ascontiguousarray(targets, np.int32).reshape(-1)
+        n_jobs = len(src)
+        assert len(tgt) == n_jobs
+        T6 = np.ascontiguousarray(T6, np.float32).reshape(n_jobs, 6)
+        hist = np.zeros((n_jobs, int(n_keys)), np.int32)
+        ov = np.zeros(n_jobs, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_match_keys_many(
+                self.ctx.handle, self.handle, _L.ptr(src, _C.c_int32), _L.ptr(T6, _C.c_float), _L.ptr(tgt, _C.c_int32), n_jobs,
+                float(max_dist), int(flags), int(n_keys), _L.ptr(hist, _C.c_int32), _L.ptr(ov, _C.c_int32)))
+        return hist, ov
+
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:
             self.ctx.lib.sfe_cloud_store_destroy(self.handle)
