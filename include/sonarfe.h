@@ -349,8 +349,8 @@ int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const 
  * bit 4: never share one large job between several workgroups.  Sharing (jobs of >= 8192 queries on a target beyond
  * 8192 points, when the call holds nothing else and shares x jobs <= CUs) needs every share resident at the same
  * time, which only a device this context has to itself can promise; a share that waits 0.5 s for the others gives up
- * and the job reports SFE_ICP_SPLIT_TIMEOUT.  The host-pointer entry points (sfe_icp_compute*) then run the call again
- * with this bit set, so their callers never see that status; callers of the enqueue-only *_dev entry points that
+ * and the job reports SFE_ICP_SPLIT_TIMEOUT.  The host-pointer entry points (sfe_icp_compute*) then launch the call once
+ * more without sharing, so their callers never see that status; callers of the enqueue-only *_dev entry points that
  * share the device set the bit themselves or repeat the call with it when they read status 6.
  * All variants return identical results. */
 int sfe_icp_set_tuning(sfe_ctx *ctx, int variant);

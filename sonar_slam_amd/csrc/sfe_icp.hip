@@ -786,8 +786,60 @@ static int check_params(sfe_ctx *ctx, const sfe_icp_params *p)
     return 0;
 }
 
-// jobs4: host array n_jobs x 4 = (src_start, n_src, tgt_start, n_tgt) in points
-static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
+int sfe_icp_check_outliers(sfe_ctx *ctx, const sfe_icp_outliers *o)
+{
+    if (!o)
+        return 0;
+    if (!ctx)
+        return SFE_ERR_ARG;
+    SFE_ARG(ctx, !o->use_min_dist || o->min_dist >= 0.0f);
+    SFE_ARG(ctx, !o->use_median || (std::isfinite(o->median_factor) && o->median_factor > 0.0f));
+    SFE_ARG(ctx, !o->use_bound || (std::isfinite(o->max_rotation_norm) && o->max_rotation_norm > 0.0f &&
+                                   std::isfinite(o->max_translation_norm) && o->max_translation_norm > 0.0f));
+    SFE_ARG(ctx, !o->use_bound || (o->bound_order >= 0 && o->bound_order <= 3));
+    return 0;
+}
+
+// ---- job tables: n_jobs x 4 = (src_start, n_src, tgt_start, n_tgt) in points, on the host ----
+static std::vector<int32_t> jobs4_offsets(const int32_t *src_off, const int32_t *tgt_off, int n_jobs)
+{
+    std::vector<int32_t> jobs4(4 * (size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        jobs4[4 * j] = src_off[j];
+        jobs4[4 * j + 1] = src_off[j + 1] - src_off[j];
+        jobs4[4 * j + 2] = tgt_off[j];
+        jobs4[4 * j + 3] = tgt_off[j + 1] - tgt_off[j];
+    }
+    return jobs4;
+}
+
+static std::vector<int32_t> jobs4_one_pair(int n_src, int n_tgt, int n_jobs)
+{
+    std::vector<int32_t> jobs4(4 * (size_t)n_jobs);
+    for (int j = 0; j < n_jobs; ++j) {
+        jobs4[4 * j] = 0;
+        jobs4[4 * j + 1] = n_src;
+        jobs4[4 * j + 2] = 0;
+        jobs4[4 * j + 3] = n_tgt;
+    }
+    return jobs4;
+}
+
+// refuses a job that is empty or lies outside pools of n_src_pts / n_tgt_pts points
+static int check_jobs4(sfe_ctx *ctx, const int32_t *jobs4, int n_jobs, int n_src_pts, int n_tgt_pts)
+{
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t *q = jobs4 + 4 * (size_t)j;
+        if (q[0] < 0 || q[1] <= 0 || q[2] < 0 || q[3] <= 0 || (long long)q[0] + q[1] > n_src_pts ||
+            (long long)q[2] + q[3] > n_tgt_pts)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "ICP job %d (%d+%d, %d+%d) is empty or lies outside the clouds (%d, %d points)",
+                               j, q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
+    }
+    return 0;
+}
+
+// one launch of a job table over device pools; enqueue only
+static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &call, const float *d_src, const float *d_tgt,
                       const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
                       int32_t *d_iters)
 {
@@ -805,7 +857,7 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
         noff += q[3];
     }
     if (!(ctx->icp_variant & 4)) { // default: strip-sweep search (sfe_icp_sweep.hip), same results
-        const int rc = sfe_icp_sweep_launch(ctx, p, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
+        const int rc = sfe_icp_sweep_launch(ctx, p, call, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
         if (rc != 1)
             return rc;
     }
@@ -828,7 +880,7 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
     // occupancy A/B: bit 1 of the tuning variant selects the 128-VGPR build (1 workgroup per CU); OX: the build for
     // chains with MinDist / MedianDist / Bound
     const int nnv = ctx->icp_variant & 1;
-    const sfe_icp_outliers &ox = ctx->icp_ox;
+    const sfe_icp_outliers &ox = call.ox;
     const bool with_ox = ox.use_min_dist || ox.use_median || ox.use_bound;
     auto kernel = !(ctx->icp_variant & 2) ? (with_ox ? icp_job_kernel<8, true> : icp_job_kernel<8, false>) // default: 64-VGPR build, two workgroups per CU (measured 7 % faster)
                                           : (with_ox ? icp_job_kernel<4, true> : icp_job_kernel<4, false>);
@@ -840,33 +892,136 @@ static int icp_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
     return 0;
 }
 
-// the launch above for the data-point filter chain (sfe_icp_dpf.hip), which builds its job table on filtered pools
-int sfe_icp_launch_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
-                        const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
-                        int32_t *d_iters)
+// A job that was shared by several workgroups reports SFE_ICP_SPLIT_TIMEOUT when its shares were not resident together (the
+// device is shared with another context or process; sfe_icp_sweep.hip "split jobs").  Every entry point with host results
+// ends here: the statuses are seen, and the table is launched once more with sharing off (the clouds and the guesses are
+// still on the device), so the caller never meets status 6.
+int sfe_icp_run_host(sfe_ctx *ctx, const sfe_icp_params *p, IcpCall call, const float *d_src, const float *d_tgt,
+                     const int32_t *jobs4, const float *guesses9, const float *d_guess9, int n_jobs, float *T_out9,
+                     int32_t *status, int32_t *iters)
 {
-    return icp_launch(ctx, p, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
+    // pinned blocks both ways, the results in one: [T | status | iterations]
+    const size_t b_g = sizeof(float) * 9 * (size_t)n_jobs, b_st = sizeof(int32_t) * (size_t)n_jobs, b_out = b_g + 2 * b_st;
+    char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
+    char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
+    if (!d_out || !h_out)
+        return SFE_ERR_HIP;
+    if (!d_guess9) {
+        float *d_g = (float *)sfe_scratch(ctx, 2, b_g);
+        void *h_g = sfe_pinned_io(ctx, 2, b_g);
+        if (!d_g || !h_g)
+            return SFE_ERR_HIP;
+        memcpy(h_g, guesses9, b_g);
+        SFE_HIP(ctx, hipMemcpyAsync(d_g, h_g, b_g, hipMemcpyHostToDevice, ctx->stream));
+        d_guess9 = d_g;
+    }
+    int32_t *d_st = (int32_t *)(d_out + b_g);
+    for (;;) {
+        if (int rc = icp_launch(ctx, p, call, d_src, d_tgt, jobs4, d_guess9, n_jobs, (float *)d_out, d_st, d_st + n_jobs))
+            return rc;
+        SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
+        SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        memcpy(T_out9, h_out, b_g);
+        memcpy(status, h_out + b_g, b_st);
+        if (iters)
+            memcpy(iters, h_out + b_g + b_st, b_st);
+        if (call.unsplit || (ctx->icp_variant & 16) ||
+            std::find(status, status + n_jobs, (int32_t)SFE_ICP_SPLIT_TIMEOUT) == status + n_jobs)
+            return 0;
+        call.unsplit = true;
+    }
 }
 
-// A job that was shared by several workgroups reports SFE_ICP_SPLIT_TIMEOUT when its shares were not resident
-// together (the device is shared with another context or process; sfe_icp_sweep.hip "split jobs").  The host-pointer
-// entry points see the statuses and run the call once more with splitting off, so the caller never meets status 6.
-static bool icp_any_split_timeout(const int32_t *status, int n)
+// ---- one function per shape of the host-pointer entry points: params, the outlier settings or none, the data-point
+// filter stages of either side or none ----
+static int icp_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd,
+                    const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts, const float *tgt, int n_tgt_pts,
+                    const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
 {
-    for (int j = 0; j < n; ++j)
-        if (status[j] == SFE_ICP_SPLIT_TIMEOUT)
-            return true;
-    return false;
+    const bool chain = n_rd != 0 || n_rf != 0;
+    if (int rc = sfe_icp_check_outliers(ctx, o))
+        return rc;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, (p || !chain) && n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
+                     (n_jobs == 0 || (src && tgt && jobs4 && guesses9 && T_out9 && status)));
+    if (int rc = sfe_icp_dpf_check(ctx, rd, n_rd))
+        return rc;
+    if (int rc = sfe_icp_dpf_check(ctx, rf, n_rf))
+        return rc;
+    if (n_jobs == 0)
+        return 0;
+    if (int rc = check_jobs4(ctx, jobs4, n_jobs, n_src_pts, n_tgt_pts))
+        return rc;
+    float *d_src = (float *)sfe_scratch(ctx, 0, sizeof(float) * 2 * (size_t)std::max(n_src_pts, 1));
+    float *d_tgt = (float *)sfe_scratch(ctx, 1, sizeof(float) * 2 * (size_t)std::max(n_tgt_pts, 1));
+    if (!d_src || !d_tgt)
+        return SFE_ERR_HIP;
+    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, sizeof(float) * 2 * (size_t)n_src_pts, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, sizeof(float) * 2 * (size_t)n_tgt_pts, hipMemcpyHostToDevice, ctx->stream));
+    IcpCall call;
+    if (o)
+        call.ox = *o;
+    if (chain)
+        return sfe_icp_dpf_run_host(ctx, p, call, rd, n_rd, rf, n_rf, d_src, d_tgt, jobs4, guesses9, n_jobs, T_out9, status,
+                                    iters);
+    return sfe_icp_run_host(ctx, p, call, d_src, d_tgt, jobs4, guesses9, nullptr, n_jobs, T_out9, status, iters);
 }
-#define ICP_RETRY_UNSPLIT(call)                                                                  \
-    do {                                                                                         \
-        if (!(ctx->icp_variant & 16) && icp_any_split_timeout(status, n_retry_)) {               \
-            ctx->icp_variant |= 16;                                                              \
-            const int rc_ = (call);                                                              \
-            ctx->icp_variant &= ~16;                                                             \
-            return rc_;                                                                          \
-        }                                                                                        \
-    } while (0)
+
+static int icp_pairs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd,
+                     const sfe_icp_dpf *rf, int n_rf, const float *src, const int32_t *src_off, const float *tgt,
+                     const int32_t *tgt_off, const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    if (int rc = sfe_icp_check_outliers(ctx, o))
+        return rc;
+    if (!ctx)
+        return SFE_ERR_ARG;
+    SFE_ARG(ctx, n_jobs >= 0 && (n_jobs == 0 || (src_off && tgt_off)));
+    const std::vector<int32_t> jobs4 = jobs4_offsets(src_off, tgt_off, n_jobs);
+    return icp_jobs(ctx, p, o, rd, n_rd, rf, n_rf, src, n_jobs ? src_off[n_jobs] : 0, tgt, n_jobs ? tgt_off[n_jobs] : 0,
+                    jobs4.data(), guesses9, n_jobs, T_out9, status, iters);
+}
+
+static int icp_guesses(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd,
+                       const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src, const float *tgt, int n_tgt,
+                       const float *guesses9, int n_guesses, float *T_out9, int32_t *status, int32_t *iters)
+{
+    if (int rc = sfe_icp_check_outliers(ctx, o))
+        return rc;
+    if (n_rd != 0 || n_rf != 0) { // a chain with stages: n_guesses jobs on the one pair
+        if (!ctx)
+            return SFE_ERR_ARG;
+        SFE_ARG(ctx, n_guesses >= 0);
+        const std::vector<int32_t> jobs4 = jobs4_one_pair(n_src, n_tgt, n_guesses);
+        return icp_jobs(ctx, p, o, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, jobs4.data(), guesses9, n_guesses, T_out9,
+                        status, iters);
+    }
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, src && tgt && guesses9 && T_out9 && status && n_src >= 0 && n_tgt >= 0 && n_guesses >= 0);
+    if (n_guesses == 0)
+        return 0;
+    if (n_src == 0 || n_tgt == 0)
+        return sfe_set_err(ctx, SFE_ERR_ARG, "ICP needs non-empty clouds (n_src=%d, n_tgt=%d)", n_src, n_tgt);
+    // one pinned block up ([source | target | guesses]) and sfe_icp_run_host's one block down: the live node calls this once
+    // per scan match with clouds of 10^2..10^3 points, where the copies and their latencies are the cost
+    const size_t b_src = sizeof(float) * 2 * (size_t)n_src, b_tgt = sizeof(float) * 2 * (size_t)n_tgt;
+    const size_t b_g = sizeof(float) * 9 * (size_t)n_guesses, b_in = b_src + b_tgt + b_g;
+    char *d_in = (char *)sfe_scratch(ctx, 0, b_in);
+    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_in);
+    if (!d_in || !h_in)
+        return SFE_ERR_HIP;
+    memcpy(h_in, src, b_src);
+    memcpy(h_in + b_src, tgt, b_tgt);
+    memcpy(h_in + b_src + b_tgt, guesses9, b_g);
+    SFE_HIP(ctx, hipMemcpyAsync(d_in, h_in, b_in, hipMemcpyHostToDevice, ctx->stream));
+    IcpCall call;
+    if (o)
+        call.ox = *o;
+    const std::vector<int32_t> jobs4 = jobs4_one_pair(n_src, n_tgt, n_guesses);
+    return sfe_icp_run_host(ctx, p, call, (const float *)d_in, (const float *)(d_in + b_src), jobs4.data(), nullptr,
+                            (const float *)(d_in + b_src + b_tgt), n_guesses, T_out9, status, iters);
+}
 
 extern "C" {
 
@@ -888,14 +1043,8 @@ int sfe_icp_batch_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src,
     SFE_ARG(ctx, d_src && d_tgt && src_off && tgt_off && d_guess9 && d_T9 && d_status && d_iters && n_jobs >= 0);
     if (n_jobs == 0)
         return 0;
-    std::vector<int32_t> jobs4(4 * (size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        jobs4[4 * j] = src_off[j];
-        jobs4[4 * j + 1] = src_off[j + 1] - src_off[j];
-        jobs4[4 * j + 2] = tgt_off[j];
-        jobs4[4 * j + 3] = tgt_off[j + 1] - tgt_off[j];
-    }
-    return icp_launch(ctx, p, d_src, d_tgt, jobs4.data(), d_guess9, n_jobs, d_T9, d_status, d_iters);
+    const std::vector<int32_t> jobs4 = jobs4_offsets(src_off, tgt_off, n_jobs);
+    return icp_launch(ctx, p, IcpCall{}, d_src, d_tgt, jobs4.data(), d_guess9, n_jobs, d_T9, d_status, d_iters);
 }
 
 int sfe_icp_jobs_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt, const int32_t *jobs4,
@@ -906,130 +1055,82 @@ int sfe_icp_jobs_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, 
     SFE_ARG(ctx, d_src && d_tgt && jobs4 && d_guess9 && d_T9 && d_status && d_iters && n_jobs >= 0);
     if (n_jobs == 0)
         return 0;
-    return icp_launch(ctx, p, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
+    return icp_launch(ctx, p, IcpCall{}, d_src, d_tgt, jobs4, d_guess9, n_jobs, d_T9, d_status, d_iters);
 }
 
+// ---- the host-pointer entry points: plain, _chain (data-point filter stages) and _chain_ext (stages and the outlier
+// settings beyond sfe_icp_params) of each shape ----
 int sfe_icp_compute_guesses(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src, const float *tgt,
                             int n_tgt, const float *guesses9, int n_guesses, float *T_out9, int32_t *status,
                             int32_t *iters)
 {
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, src && tgt && guesses9 && T_out9 && status && n_src >= 0 && n_tgt >= 0 && n_guesses >= 0);
-    if (n_guesses == 0)
-        return 0;
-    if (n_src == 0 || n_tgt == 0)
-        return sfe_set_err(ctx, SFE_ERR_ARG, "ICP needs non-empty clouds (n_src=%d, n_tgt=%d)", n_src, n_tgt);
-    // one pinned block up ([source | target | guesses]), one down ([T | status | iterations]): the live node calls this
-    // once per scan match with clouds of 10^2..10^3 points, where the copies and their latencies are the cost
-    const size_t b_src = sizeof(float) * 2 * (size_t)n_src, b_tgt = sizeof(float) * 2 * (size_t)n_tgt;
-    const size_t b_g = sizeof(float) * 9 * (size_t)n_guesses, b_in = b_src + b_tgt + b_g;
-    const size_t b_out = (sizeof(float) * 9 + 2 * sizeof(int32_t)) * (size_t)n_guesses;
-    char *d_in = (char *)sfe_scratch(ctx, 0, b_in);
-    char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
-    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_in);
-    char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
-    if (!d_in || !d_out || !h_in || !h_out)
-        return SFE_ERR_HIP;
-    memcpy(h_in, src, b_src);
-    memcpy(h_in + b_src, tgt, b_tgt);
-    memcpy(h_in + b_src + b_tgt, guesses9, b_g);
-    SFE_HIP(ctx, hipMemcpyAsync(d_in, h_in, b_in, hipMemcpyHostToDevice, ctx->stream));
-    float *d_src = (float *)d_in, *d_tgt = (float *)(d_in + b_src), *d_g = (float *)(d_in + b_src + b_tgt);
-    float *d_T = (float *)d_out;
-    int32_t *d_st = (int32_t *)(d_out + sizeof(float) * 9 * (size_t)n_guesses);
-    std::vector<int32_t> jobs4(4 * (size_t)n_guesses);
-    for (int j = 0; j < n_guesses; ++j) {
-        jobs4[4 * j] = 0;
-        jobs4[4 * j + 1] = n_src;
-        jobs4[4 * j + 2] = 0;
-        jobs4[4 * j + 3] = n_tgt;
-    }
-    if (int rc = icp_launch(ctx, p, d_src, d_tgt, jobs4.data(), d_g, n_guesses, d_T, d_st, d_st + n_guesses))
-        return rc;
-    SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(T_out9, h_out, sizeof(float) * 9 * (size_t)n_guesses);
-    memcpy(status, h_out + sizeof(float) * 9 * (size_t)n_guesses, sizeof(int32_t) * (size_t)n_guesses);
-    if (iters)
-        memcpy(iters, h_out + (sizeof(float) * 9 + sizeof(int32_t)) * (size_t)n_guesses, sizeof(int32_t) * (size_t)n_guesses);
-    const int n_retry_ = n_guesses;
-    ICP_RETRY_UNSPLIT(sfe_icp_compute_guesses(ctx, p, src, n_src, tgt, n_tgt, guesses9, n_guesses, T_out9, status, iters));
-    return 0;
+    return icp_guesses(ctx, p, nullptr, nullptr, 0, nullptr, 0, src, n_src, tgt, n_tgt, guesses9, n_guesses, T_out9, status,
+                       iters);
+}
+
+int sfe_icp_compute_guesses_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                                  const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src, const float *tgt, int n_tgt,
+                                  const float *guesses9, int n_guesses, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_guesses(ctx, p, nullptr, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, guesses9, n_guesses, T_out9, status, iters);
+}
+
+int sfe_icp_compute_guesses_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                      const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                      int n_src, const float *tgt, int n_tgt, const float *guesses9, int n_guesses,
+                                      float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_guesses(ctx, p, o, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, guesses9, n_guesses, T_out9, status, iters);
 }
 
 int sfe_icp_compute_pairs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, const int32_t *src_off,
                           const float *tgt, const int32_t *tgt_off, const float *guesses9, int n_jobs, float *T_out9,
                           int32_t *status, int32_t *iters)
 {
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n_jobs >= 0 && (n_jobs == 0 || (src && tgt && src_off && tgt_off && guesses9 && T_out9 && status)));
-    if (n_jobs == 0)
-        return 0;
-    const size_t ns = (size_t)src_off[n_jobs], nt = (size_t)tgt_off[n_jobs];
-    float *d_src = (float *)sfe_scratch(ctx, 0, sizeof(float) * 2 * std::max<size_t>(ns, 1));
-    float *d_tgt = (float *)sfe_scratch(ctx, 1, sizeof(float) * 2 * std::max<size_t>(nt, 1));
-    float *d_g = (float *)sfe_scratch(ctx, 2, sizeof(float) * 9 * (size_t)n_jobs);
-    float *d_T = (float *)sfe_scratch(ctx, 3, sizeof(float) * 9 * (size_t)n_jobs);
-    int32_t *d_st = (int32_t *)sfe_scratch(ctx, 8, sizeof(int32_t) * 2 * (size_t)n_jobs);
-    if (!d_src || !d_tgt || !d_g || !d_T || !d_st)
-        return SFE_ERR_HIP;
-    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, sizeof(float) * 2 * ns, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, sizeof(float) * 2 * nt, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_g, guesses9, sizeof(float) * 9 * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = sfe_icp_batch_dev(ctx, p, d_src, src_off, d_tgt, tgt_off, d_g, n_jobs, d_T, d_st, d_st + n_jobs))
-        return rc;
-    SFE_HIP(ctx, hipMemcpyAsync(T_out9, d_T, sizeof(float) * 9 * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(status, d_st, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-    if (iters)
-        SFE_HIP(ctx, hipMemcpyAsync(iters, d_st + n_jobs, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int n_retry_ = n_jobs;
-    ICP_RETRY_UNSPLIT(sfe_icp_compute_pairs(ctx, p, src, src_off, tgt, tgt_off, guesses9, n_jobs, T_out9, status, iters));
-    return 0;
+    return icp_pairs(ctx, p, nullptr, nullptr, 0, nullptr, 0, src, src_off, tgt, tgt_off, guesses9, n_jobs, T_out9, status,
+                     iters);
+}
+
+int sfe_icp_compute_pairs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                                const sfe_icp_dpf *rf, int n_rf, const float *src, const int32_t *src_off, const float *tgt,
+                                const int32_t *tgt_off, const float *guesses9, int n_jobs, float *T_out9, int32_t *status,
+                                int32_t *iters)
+{
+    return icp_pairs(ctx, p, nullptr, rd, n_rd, rf, n_rf, src, src_off, tgt, tgt_off, guesses9, n_jobs, T_out9, status, iters);
+}
+
+int sfe_icp_compute_pairs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                    const int32_t *src_off, const float *tgt, const int32_t *tgt_off, const float *guesses9,
+                                    int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_pairs(ctx, p, o, rd, n_rd, rf, n_rf, src, src_off, tgt, tgt_off, guesses9, n_jobs, T_out9, status, iters);
 }
 
 int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
                          int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
                          int32_t *status, int32_t *iters)
 {
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
-                     (n_jobs == 0 || (src && tgt && jobs4 && guesses9 && T_out9 && status)));
-    if (n_jobs == 0)
-        return 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int32_t *q = jobs4 + 4 * (size_t)j;
-        if (q[0] < 0 || q[1] < 0 || q[2] < 0 || q[3] < 0 || (long long)q[0] + q[1] > n_src_pts ||
-            (long long)q[2] + q[3] > n_tgt_pts)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "ICP job %d (%d+%d, %d+%d) lies outside the clouds (%d, %d points)", j,
-                               q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
-    }
-    float *d_src = (float *)sfe_scratch(ctx, 0, sizeof(float) * 2 * (size_t)std::max(n_src_pts, 1));
-    float *d_tgt = (float *)sfe_scratch(ctx, 1, sizeof(float) * 2 * (size_t)std::max(n_tgt_pts, 1));
-    float *d_g = (float *)sfe_scratch(ctx, 2, sizeof(float) * 9 * (size_t)n_jobs);
-    float *d_T = (float *)sfe_scratch(ctx, 3, sizeof(float) * 9 * (size_t)n_jobs);
-    int32_t *d_st = (int32_t *)sfe_scratch(ctx, 8, sizeof(int32_t) * 2 * (size_t)n_jobs);
-    if (!d_src || !d_tgt || !d_g || !d_T || !d_st)
-        return SFE_ERR_HIP;
-    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, sizeof(float) * 2 * (size_t)n_src_pts, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, sizeof(float) * 2 * (size_t)n_tgt_pts, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_g, guesses9, sizeof(float) * 9 * (size_t)n_jobs, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = icp_launch(ctx, p, d_src, d_tgt, jobs4, d_g, n_jobs, d_T, d_st, d_st + n_jobs))
-        return rc;
-    SFE_HIP(ctx, hipMemcpyAsync(T_out9, d_T, sizeof(float) * 9 * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(status, d_st, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToHost, ctx->stream));
-    if (iters)
-        SFE_HIP(ctx, hipMemcpyAsync(iters, d_st + n_jobs, sizeof(int32_t) * (size_t)n_jobs, hipMemcpyDeviceToHost,
-                                    ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int n_retry_ = n_jobs;
-    ICP_RETRY_UNSPLIT(sfe_icp_compute_jobs(ctx, p, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9, n_jobs, T_out9, status,
-                                           iters));
-    return 0;
+    return icp_jobs(ctx, p, nullptr, nullptr, 0, nullptr, 0, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9, n_jobs, T_out9,
+                    status, iters);
+}
+
+int sfe_icp_compute_jobs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
+                               const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts, const float *tgt,
+                               int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
+                               int32_t *status, int32_t *iters)
+{
+    return icp_jobs(ctx, p, nullptr, rd, n_rd, rf, n_rf, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9, n_jobs, T_out9,
+                    status, iters);
+}
+
+int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                   const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
+                                   int n_src_pts, const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses9,
+                                   int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return icp_jobs(ctx, p, o, rd, n_rd, rf, n_rf, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9, n_jobs, T_out9, status,
+                    iters);
 }
 
 int sfe_icp_compute(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src, const float *tgt, int n_tgt,

@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void dpf_pack_kernel(const float2 *__restrict_
         o[i] = s[i];
 }
 
-static int dpf_check(sfe_ctx *ctx, const sfe_icp_dpf *st, int n)
+int sfe_icp_dpf_check(sfe_ctx *ctx, const sfe_icp_dpf *st, int n)
 {
     SFE_ARG(ctx, n >= 0 && n <= SFE_DPF_MAX_STAGES && (n == 0 || st));
     for (int i = 0; i < n; ++i) {
@@ -337,16 +337,11 @@ static void dpf_slices(const int32_t *jobs4, int n_jobs, int col, DpfSlices &s)
     s.kept.assign(s.n.size(), 0);
 }
 
-// sfe_icp.hip
-int sfe_icp_launch_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
-                        const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
-                        int32_t *d_iters);
-
 // The chain on a job table over device pools (d_src / d_tgt hold the clouds, jobs4 validated), guesses on the host;
 // results to the host.
-static int dpf_icp_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf,
-                        int n_rf, const float *d_src, const float *d_tgt, const int32_t *jobs4, const float *guesses9,
-                        int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+int sfe_icp_dpf_run_host(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &call, const sfe_icp_dpf *rd, int n_rd,
+                         const sfe_icp_dpf *rf, int n_rf, const float *d_src, const float *d_tgt, const int32_t *jobs4,
+                         const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
 {
     DpfSlices S, R;
     dpf_slices(jobs4, n_jobs, 0, S);
@@ -394,37 +389,11 @@ static int dpf_icp_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf
     const int m = (int)idx.size();
     std::vector<int8_t> routes((size_t)n_jobs, (int8_t)-1);
     if (m > 0) {
-        float *d_g = (float *)sfe_scratch(ctx, 2, sizeof(float) * 9 * (size_t)m);
-        float *d_T = (float *)sfe_scratch(ctx, 3, sizeof(float) * 9 * (size_t)m);
-        int32_t *d_st = (int32_t *)sfe_scratch(ctx, 8, sizeof(int32_t) * 2 * (size_t)m);
-        if (!d_g || !d_T || !d_st)
-            return SFE_ERR_HIP;
         std::vector<float> T((size_t)m * 9);
         std::vector<int32_t> st((size_t)m * 2);
-        SFE_HIP(ctx, hipMemcpyAsync(d_g, g.data(), sizeof(float) * 9 * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        bool unsplit = false; // this call set sfe_icp_set_tuning bit 4 for its second pass
-        for (int pass = 0; pass < 2; ++pass) {
-            const int rc = sfe_icp_launch_jobs(ctx, p, fsrc, ftgt, jobs.data(), d_g, m, d_T, d_st, d_st + m);
-            if (rc) {
-                if (unsplit)
-                    ctx->icp_variant &= ~16;
-                return rc;
-            }
-            SFE_HIP(ctx, hipMemcpyAsync(T.data(), d_T, sizeof(float) * 9 * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-            SFE_HIP(ctx, hipMemcpyAsync(st.data(), d_st, sizeof(int32_t) * 2 * (size_t)m, hipMemcpyDeviceToHost,
-                                        ctx->stream));
-            SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            // a shared job whose workgroups were not resident together: once more without sharing (sfe_icp.hip)
-            bool again = false;
-            for (int k = 0; k < m && pass == 0 && !(ctx->icp_variant & 16); ++k)
-                again |= st[k] == SFE_ICP_SPLIT_TIMEOUT;
-            if (!again)
-                break;
-            ctx->icp_variant |= 16;
-            unsplit = true;
-        }
-        if (unsplit)
-            ctx->icp_variant &= ~16;
+        if (int rc = sfe_icp_run_host(ctx, p, call, fsrc, ftgt, jobs.data(), g.data(), nullptr, m, T.data(), st.data(),
+                                      st.data() + m))
+            return rc;
         for (int k = 0; k < m; ++k) {
             const int j = idx[k];
             memcpy(T_out9 + 9 * (size_t)j, T.data() + 9 * (size_t)k, sizeof(float) * 9);
@@ -438,26 +407,6 @@ static int dpf_icp_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf
     return 0;
 }
 
-// ---- the *_chain_ext entry points: the chain's outlier filters and checker beyond sfe_icp_params, installed on the
-// context for the one call (every ICP kernel the call launches takes them by value) ----
-template <class F>
-static int icp_with_outliers(sfe_ctx *ctx, const sfe_icp_outliers *o, F call)
-{
-    if (!o)
-        return call();
-    if (!ctx)
-        return SFE_ERR_ARG;
-    SFE_ARG(ctx, !o->use_min_dist || o->min_dist >= 0.0f);
-    SFE_ARG(ctx, !o->use_median || (std::isfinite(o->median_factor) && o->median_factor > 0.0f));
-    SFE_ARG(ctx, !o->use_bound || (std::isfinite(o->max_rotation_norm) && o->max_rotation_norm > 0.0f &&
-                                   std::isfinite(o->max_translation_norm) && o->max_translation_norm > 0.0f));
-    SFE_ARG(ctx, !o->use_bound || (o->bound_order >= 0 && o->bound_order <= 3));
-    ctx->icp_ox = *o;
-    const int rc = call();
-    ctx->icp_ox = sfe_icp_outliers{};
-    return rc;
-}
-
 extern "C" {
 
 int sfe_icp_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_stages, const float *d_pts,
@@ -466,7 +415,7 @@ int sfe_icp_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_sta
     if (int rc = sfe_use(ctx))
         return rc;
     SFE_ARG(ctx, n_clouds >= 0 && (n_clouds == 0 || (off && d_pts && d_out && counts_out)));
-    if (int rc = dpf_check(ctx, stages, n_stages))
+    if (int rc = sfe_icp_dpf_check(ctx, stages, n_stages))
         return rc;
     if (n_clouds == 0)
         return 0;
@@ -509,145 +458,6 @@ int sfe_icp_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_sta
                        (const int *)(d_tab + 16 * nc), (float2 *)d_out, (const long long *)(d_tab + 8 * nc));
     SFE_LAUNCH_CHECK(ctx);
     return 0;
-}
-
-int sfe_icp_compute_jobs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
-                               const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts, const float *tgt,
-                               int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
-                               int32_t *status, int32_t *iters)
-{
-    if (n_rd == 0 && n_rf == 0)
-        return sfe_icp_compute_jobs(ctx, p, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9, n_jobs, T_out9, status,
-                                    iters);
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, p && n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
-                     (n_jobs == 0 || (src && tgt && jobs4 && guesses9 && T_out9 && status)));
-    if (int rc = dpf_check(ctx, rd, n_rd))
-        return rc;
-    if (int rc = dpf_check(ctx, rf, n_rf))
-        return rc;
-    if (n_jobs == 0)
-        return 0;
-    for (int j = 0; j < n_jobs; ++j) {
-        const int32_t *q = jobs4 + 4 * (size_t)j;
-        if (q[0] < 0 || q[1] <= 0 || q[2] < 0 || q[3] <= 0 || (long long)q[0] + q[1] > n_src_pts ||
-            (long long)q[2] + q[3] > n_tgt_pts)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "ICP job %d (%d+%d, %d+%d) is empty or lies outside the clouds (%d, %d points)",
-                               j, q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
-    }
-    float *d_src = (float *)sfe_scratch(ctx, 0, sizeof(float) * 2 * (size_t)std::max(n_src_pts, 1));
-    float *d_tgt = (float *)sfe_scratch(ctx, 1, sizeof(float) * 2 * (size_t)std::max(n_tgt_pts, 1));
-    if (!d_src || !d_tgt)
-        return SFE_ERR_HIP;
-    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, sizeof(float) * 2 * (size_t)n_src_pts, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, sizeof(float) * 2 * (size_t)n_tgt_pts, hipMemcpyHostToDevice, ctx->stream));
-    return dpf_icp_jobs(ctx, p, rd, n_rd, rf, n_rf, d_src, d_tgt, jobs4, guesses9, n_jobs, T_out9, status, iters);
-}
-
-int sfe_icp_compute_pairs_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
-                                const sfe_icp_dpf *rf, int n_rf, const float *src, const int32_t *src_off, const float *tgt,
-                                const int32_t *tgt_off, const float *guesses9, int n_jobs, float *T_out9, int32_t *status,
-                                int32_t *iters)
-{
-    if (n_rd == 0 && n_rf == 0)
-        return sfe_icp_compute_pairs(ctx, p, src, src_off, tgt, tgt_off, guesses9, n_jobs, T_out9, status, iters);
-    if (!ctx)
-        return SFE_ERR_ARG;
-    SFE_ARG(ctx, n_jobs >= 0 && (n_jobs == 0 || (src_off && tgt_off)));
-    std::vector<int32_t> jobs4(4 * (size_t)n_jobs);
-    for (int j = 0; j < n_jobs; ++j) {
-        jobs4[4 * j] = src_off[j];
-        jobs4[4 * j + 1] = src_off[j + 1] - src_off[j];
-        jobs4[4 * j + 2] = tgt_off[j];
-        jobs4[4 * j + 3] = tgt_off[j + 1] - tgt_off[j];
-    }
-    return sfe_icp_compute_jobs_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_jobs ? src_off[n_jobs] : 0, tgt,
-                                      n_jobs ? tgt_off[n_jobs] : 0, jobs4.data(), guesses9, n_jobs, T_out9, status, iters);
-}
-
-int sfe_icp_compute_guesses_chain(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_dpf *rd, int n_rd,
-                                  const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src, const float *tgt, int n_tgt,
-                                  const float *guesses9, int n_guesses, float *T_out9, int32_t *status, int32_t *iters)
-{
-    if (n_rd == 0 && n_rf == 0)
-        return sfe_icp_compute_guesses(ctx, p, src, n_src, tgt, n_tgt, guesses9, n_guesses, T_out9, status, iters);
-    if (!ctx)
-        return SFE_ERR_ARG;
-    SFE_ARG(ctx, n_guesses >= 0);
-    std::vector<int32_t> jobs4(4 * (size_t)n_guesses);
-    for (int j = 0; j < n_guesses; ++j) {
-        jobs4[4 * j] = 0;
-        jobs4[4 * j + 1] = n_src;
-        jobs4[4 * j + 2] = 0;
-        jobs4[4 * j + 3] = n_tgt;
-    }
-    return sfe_icp_compute_jobs_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, jobs4.data(), guesses9,
-                                      n_guesses, T_out9, status, iters);
-}
-
-int sfe_icp_compute_guesses_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
-                                      const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
-                                      int n_src, const float *tgt, int n_tgt, const float *guesses9, int n_guesses,
-                                      float *T_out9, int32_t *status, int32_t *iters)
-{
-    return icp_with_outliers(ctx, o, [&] {
-        return sfe_icp_compute_guesses_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src, tgt, n_tgt, guesses9, n_guesses,
-                                             T_out9, status, iters);
-    });
-}
-
-int sfe_icp_compute_pairs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
-                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
-                                    const int32_t *src_off, const float *tgt, const int32_t *tgt_off, const float *guesses9,
-                                    int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
-{
-    return icp_with_outliers(ctx, o, [&] {
-        return sfe_icp_compute_pairs_chain(ctx, p, rd, n_rd, rf, n_rf, src, src_off, tgt, tgt_off, guesses9, n_jobs,
-                                           T_out9, status, iters);
-    });
-}
-
-int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
-                                   const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
-                                   int n_src_pts, const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses9,
-                                   int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
-{
-    return icp_with_outliers(ctx, o, [&] {
-        return sfe_icp_compute_jobs_chain(ctx, p, rd, n_rd, rf, n_rf, src, n_src_pts, tgt, n_tgt_pts, jobs4, guesses9,
-                                          n_jobs, T_out9, status, iters);
-    });
-}
-
-// The chain over store handles: the stages read the store's pool in place (both sides, every distinct handle of a side
-// once), the job table is rebuilt on the filtered pools like sfe_icp_compute_jobs_chain's.
-int sfe_icp_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
-                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf,
-                                    sfe_cloud_store *s, const int32_t *pairs, const float *guesses9, int n_jobs,
-                                    float *T_out9, int32_t *status, int32_t *iters)
-{
-    return icp_with_outliers(ctx, o, [&]() -> int {
-        if (n_rd == 0 && n_rf == 0)
-            return sfe_icp_store_compute(ctx, p, s, pairs, guesses9, n_jobs, T_out9, status, iters);
-        if (int rc = sfe_use(ctx))
-            return rc;
-        SFE_ARG(ctx, p && s && sfe_store_ctx(s) == ctx && n_jobs >= 0 &&
-                         (n_jobs == 0 || (pairs && guesses9 && T_out9 && status)));
-        if (int rc = dpf_check(ctx, rd, n_rd))
-            return rc;
-        if (int rc = dpf_check(ctx, rf, n_rf))
-            return rc;
-        if (n_jobs == 0)
-            return 0;
-        std::vector<int32_t> jobs4;
-        if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
-            return rc;
-        SfeStoreView v;
-        if (int rc = sfe_store_view(s, &v))
-            return rc;
-        const float *pool = (const float *)v.d_pool;
-        return dpf_icp_jobs(ctx, p, rd, n_rd, rf, n_rf, pool, pool, jobs4.data(), guesses9, n_jobs, T_out9, status, iters);
-    });
 }
 
 } // extern "C"

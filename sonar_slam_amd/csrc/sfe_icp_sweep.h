@@ -375,6 +375,7 @@ struct SweepLaunchArgs {
     int sw_budget, sw_budget_a, sw_cache, sw_cache2;
     float sw_m, sw_kappa;
     unsigned long long *d_sync;
+    sfe_icp_outliers ox; // IcpCall::ox
 };
 
 // bytes of the control block of one instantiation (the dynamic LDS behind it is 16-byte aligned)
@@ -406,7 +407,7 @@ int sweep_launch_split(sfe_ctx *ctx, hipStream_t ps, int n_split, SweepJob *d_jo
 int sweep_launch_tiny(sfe_ctx *ctx, const sfe_icp_params *p, int n, const SweepJob *d_jobs, const int *d_ids, const SweepPrep *d_preps,
                       const float2 *d_src, const float2 *d_tgt, const float *d_guess9, const int *d_perm, const float2 *d_snrm,
                       const float *d_mean, const StripTab *d_tab, float *d_T9, int32_t *d_status, int32_t *d_iters, int tiny_tmax,
-                      int tiny_smax);
+                      int tiny_smax, const sfe_icp_outliers &ox);
 // limits of the one-wave kernel the host side sorts jobs by (sfe_icp_tiny.h)
 #define SW_TINY_MAX 512        // most points of either cloud
 #define SW_TINY_PAIRS_SHORT 400000

@@ -11,7 +11,7 @@
 // host side: job tables, scratch, the prep / split / loop launches.  jobs4 = n_jobs x (src_start, n_src, tgt_start,
 // n_tgt) in points.
 // ---------------------------------------------------------------------------------------------
-int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
+int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &call, const float *d_src, const float *d_tgt,
                          const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
                          int32_t *d_iters)
 {
@@ -33,9 +33,10 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     std::map<std::pair<int, int>, int> seen; // many guesses on one pair share one prep
     long long toff = 0, qoff = 0, koff = 0, goff = 0;
     const sfe_tuning &tu = ctx->tune; // (tuning sw_tiers = 0 sends every job to the 1024-thread kernels)
-    // large jobs shared by several workgroups unless tuning sw_multi = 0 or sfe_icp_set_tuning bit 4 (a device shared
-    // with another context / process cannot promise that all shares of a job are resident together: ADVICE r3)
-    const bool multi_on = tu.sw_multi && !(ctx->icp_variant & 16);
+    // large jobs shared by several workgroups unless tuning sw_multi = 0, sfe_icp_set_tuning bit 4 or the call is the
+    // unsplit second run (a device shared with another context / process cannot promise that all shares of a job are
+    // resident together: ADVICE r3)
+    const bool multi_on = tu.sw_multi && !(ctx->icp_variant & 16) && !call.unsplit;
     // ~96 points per strip on average (tuning sw_strip_pts; measured optimum 96-128 on 5000-point clouds: fewer queries need
     // a second strip, a little more to walk in each), one strip (= a plain x sweep) for small clouds
     const int strip_pts = tu.sw_strip_pts;
@@ -368,6 +369,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     // few times the last one covers all that are still to come)
     a.sw_kappa = tu.sw_reck;
     a.d_sync = d_sync;
+    a.ox = call.ox;
     // The build with clearance records carries more per-lane state (the 64-VGPR budget makes every register count:
     // the same chain runs ~10 % slower in it until the records start to hit), so it only takes chains that are set to
     // run many iterations: a fixed count (no differential checker) of at least SW_REC_MIN_ITER -- and only the builds
@@ -383,7 +385,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_s
     if (n_tiny) { // one wave per job, everything in LDS (sfe_icp_tiny.h)
         if ((rc = sweep_launch_tiny(ctx, p, n_tiny, d_jobs, ids, d_preps, (const float2 *)d_src, (const float2 *)d_tgt, d_guess9,
                                     (const int *)d_perm, (const float2 *)d_snrm, (const float *)d_mean, (const StripTab *)d_tab, d_T9,
-                                    d_status, d_iters, tiny_tmax, tiny_smax)))
+                                    d_status, d_iters, tiny_tmax, tiny_smax, call.ox)))
             return rc;
         ids += n_tiny;
     }

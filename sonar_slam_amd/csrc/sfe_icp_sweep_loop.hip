@@ -1809,7 +1809,7 @@ template <int NT, int MINW, bool LDS_TGT, bool LDS_Q, bool PROF, bool REC, bool 
 int sweep_launch_loop(const SweepLaunchArgs &a, int n, const int *d_ids, size_t body, int t_cap, int q_cap)
 {
     sfe_ctx *ctx = a.ctx;
-    const sfe_icp_outliers &ox = ctx->icp_ox;
+    const sfe_icp_outliers &ox = a.ox;
     auto kernel = (ox.use_min_dist || ox.use_median || ox.use_bound) ? icp_sweep_kernel<NT, MINW, LDS_TGT, LDS_Q, PROF, REC, MULTI, true>
                                                                      : icp_sweep_kernel<NT, MINW, LDS_TGT, LDS_Q, PROF, REC, MULTI, false>;
     const size_t smem = sweep_ctl_bytes<NT, PROF, REC>() + body;
@@ -1859,9 +1859,8 @@ int sweep_launch_split(sfe_ctx *ctx, hipStream_t ps, int n_split, SweepJob *d_jo
 int sweep_launch_tiny(sfe_ctx *ctx, const sfe_icp_params *p, int n, const SweepJob *d_jobs, const int *d_ids, const SweepPrep *d_preps,
                       const float2 *d_src, const float2 *d_tgt, const float *d_guess9, const int *d_perm, const float2 *d_snrm,
                       const float *d_mean, const StripTab *d_tab, float *d_T9, int32_t *d_status, int32_t *d_iters, int tiny_tmax,
-                      int tiny_smax)
+                      int tiny_smax, const sfe_icp_outliers &ox)
 {
-    const sfe_icp_outliers &ox = ctx->icp_ox;
     auto kernel = (ox.use_min_dist || ox.use_median || ox.use_bound) ? icp_tiny_kernel<true> : icp_tiny_kernel<false>;
     const int tc = ((tiny_tmax + SW_TINY_CH - 1) / SW_TINY_CH + 1) * SW_TINY_CH, qc = (tiny_smax + 3) & ~3; // (whole chunks + one of padding)
     const size_t smem = ((sizeof(TinyShared) + 15) & ~(size_t)15) + sizeof(float2) * (size_t)tc * (p->minimizer == 1 ? 2 : 1) +

@@ -29,7 +29,7 @@ struct sfe_tuning {
     // strip-sweep ICP (sfe_icp_sweep.hip)
     int sw_tiers = 1;           // one-wave / four-wave workgroups for small jobs (0: every job on 1024 threads)
     int sw_tiny = 1;            // clouds of a few hundred points: the exhaustive one-wave kernel
-    int sw_multi = 1;           // large jobs shared by several workgroups (sfe_icp_set_tuning bit 4 also turns it off)
+    int sw_multi = 1;           // large jobs shared by several workgroups (off too under sfe_icp_set_tuning bit 4 and in IcpCall::unsplit's retry)
     int sw_multi_g = 0;         //   shares per job (0: as many as the CUs allow, at most SW_MG_MAX)
     int sw_multi_min_src = 8192; //  fewest queries of a job that is shared
     int sw_multi_share_min = 1024; // fewest queries worth a share
@@ -93,8 +93,6 @@ struct sfe_ctx {
     int icp_prof = 0;            // debug: per-phase cycle counts of workgroup 0 of the sweep kernel
     long long icp_prof_host[SFE_ICP_PROF_N] = {0};
     std::vector<int8_t> icp_routes; // SFE_ICP_ROUTE_* of every job of the last ICP call (sfe_icp_last_routes)
-    // the outlier filters / checker of the *_chain_ext call in progress (all zero outside one): every ICP kernel takes it
-    sfe_icp_outliers icp_ox = {};
     int n_cu = 256;
     // clouds left in the staging slots by sfe_extract_points_bits_staged_dev, waiting for sfe_cloud_filter_staged_dev
     // (-1: none; anything else that writes those slots resets it)
@@ -153,10 +151,33 @@ void *sfe_pinned_io(sfe_ctx *ctx, int slot, size_t bytes);
                                __LINE__);                                                        \
     } while (0)
 
+// What one ICP call carries beyond sfe_icp_params, handed from the entry point down to every launch (nothing of a call
+// lives on the context).
+struct IcpCall {
+    sfe_icp_outliers ox = {}; // outlier filters / checker of a *_chain_ext call (all zero: none); the kernels take it by value
+    bool unsplit = false;     // no job shared by several workgroups: the second run after SFE_ICP_SPLIT_TIMEOUT
+};
+
 // sfe_icp_sweep.hip: 0 = launched, 1 = a target exceeds the LDS capacity (use the brute-force kernel), < 0 = error
-int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt,
+int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &call, const float *d_src, const float *d_tgt,
                          const int32_t *jobs4, const float *d_guess9, int n_jobs, float *d_T9, int32_t *d_status,
                          int32_t *d_iters);
+
+// sfe_icp.hip: the argument checks of a call's outlier settings (o == nullptr: none, passes)
+int sfe_icp_check_outliers(sfe_ctx *ctx, const sfe_icp_outliers *o);
+// ... one call with host guesses and host results on device pools and a validated job table (n_jobs x (src_start, n_src,
+// tgt_start, n_tgt) in points): stages the guesses (or takes them where they are: d_guess9 != nullptr), launches, brings
+// T / status / iterations back (one copy, one synchronisation) and, if a job reports SFE_ICP_SPLIT_TIMEOUT while sharing
+// was on, launches once more unsplit.  iters may be nullptr.
+int sfe_icp_run_host(sfe_ctx *ctx, const sfe_icp_params *p, IcpCall call, const float *d_src, const float *d_tgt,
+                     const int32_t *jobs4, const float *guesses9, const float *d_guess9, int n_jobs, float *T_out9,
+                     int32_t *status, int32_t *iters);
+// sfe_icp_dpf.hip: the argument checks of a data-point filter chain, and sfe_icp_run_host behind the chain's filters: every
+// distinct slice of the job table filtered once, the job table rebuilt on the filtered pools
+int sfe_icp_dpf_check(sfe_ctx *ctx, const sfe_icp_dpf *st, int n);
+int sfe_icp_dpf_run_host(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &call, const sfe_icp_dpf *rd, int n_rd,
+                         const sfe_icp_dpf *rf, int n_rf, const float *d_src, const float *d_tgt, const int32_t *jobs4,
+                         const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
 
 // sfe_store.hip: append n_frames clouds ([f][cap] float2 + counts[f], device) to a store; enqueue only
 struct sfe_cloud_store;
@@ -177,9 +198,6 @@ struct SfeStoreView {
     int n_slots;
 };
 int sfe_store_view(sfe_cloud_store *s, SfeStoreView *v);
-// n_jobs (source, target) handle pairs -> the ICP job table over the store's pool, refused like sfe_icp_store_compute
-// refuses them (a handle outside the store, an empty or failed cloud); syncs the host mirror of the slot table first
-extern "C" int sfe_store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4);
 
 // sfe_downsample.hip: pcl.downsample with indices on a device-resident cloud of any size (rank sort in global memory)
 struct SfeDsHeader {

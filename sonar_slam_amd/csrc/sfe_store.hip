@@ -1240,7 +1240,9 @@ int sfe_cloud_store_match_keys_many(sfe_ctx *ctx, sfe_cloud_store *s, const int3
     return 0;
 }
 
-int sfe_store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4)
+// n_jobs (source, target) handle pairs -> the ICP job table over the store's pool; refuses a handle outside the store and
+// an empty or failed cloud; syncs the host mirror of the slot table first
+static int store_jobs4(sfe_cloud_store *s, const int32_t *pairs, int n_jobs, std::vector<int32_t> &jobs4)
 {
     sfe_ctx *ctx = s->ctx;
     if (int rc = store_sync_meta(s))
@@ -1272,64 +1274,54 @@ int sfe_icp_store_jobs_dev(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_stor
     if (n_jobs == 0)
         return 0;
     std::vector<int32_t> jobs4;
-    if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
+    if (int rc = store_jobs4(s, pairs, n_jobs, jobs4))
         return rc;
     return sfe_icp_jobs_dev(ctx, p, (const float *)s->d_pool, (const float *)s->d_pool, jobs4.data(), d_guess9, n_jobs, d_T9,
                             d_status, d_iters);
 }
 
-int sfe_icp_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store *s, const int32_t *pairs,
-                          const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+// Scan matches over store handles with host guesses and results.  With data-point filter stages they read the store's
+// pool in place (both sides, every distinct handle of a side once) and the job table is rebuilt on the filtered pools.
+static int store_icp(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd,
+                     const sfe_icp_dpf *rf, int n_rf, sfe_cloud_store *s, const int32_t *pairs, const float *guesses9,
+                     int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
 {
+    if (int rc = sfe_icp_check_outliers(ctx, o))
+        return rc;
     if (int rc = sfe_use(ctx))
         return rc;
     SFE_ARG(ctx, p && s && s->ctx == ctx && n_jobs >= 0 && (n_jobs == 0 || (pairs && guesses9 && T_out9 && status)));
+    if (int rc = sfe_icp_dpf_check(ctx, rd, n_rd))
+        return rc;
+    if (int rc = sfe_icp_dpf_check(ctx, rf, n_rf))
+        return rc;
     if (n_jobs == 0)
         return 0;
     std::vector<int32_t> jobs4;
-    if (int rc = sfe_store_jobs4(s, pairs, n_jobs, jobs4))
+    if (int rc = store_jobs4(s, pairs, n_jobs, jobs4))
         return rc;
-    const size_t b_g = sizeof(float) * 9 * (size_t)n_jobs, b_out = (sizeof(float) * 9 + 2 * sizeof(int32_t)) * (size_t)n_jobs;
-    float *d_g = (float *)sfe_scratch(ctx, 2, b_g);
-    char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
-    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_g);
-    char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
-    if (!d_g || !d_out || !h_in || !h_out)
-        return SFE_ERR_HIP;
-    const int was_unsplit = ctx->icp_variant & 16;
-    int rc = 0;
-    for (int attempt = 0;; ++attempt) {
-        memcpy(h_in, guesses9, b_g);
-        float *d_T = (float *)d_out;
-        int32_t *d_st = (int32_t *)(d_out + sizeof(float) * 9 * (size_t)n_jobs);
-        if (hipMemcpyAsync(d_g, h_in, b_g, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-            rc = sfe_set_err(ctx, SFE_ERR_HIP, "scan match over the store: upload of the guesses failed");
-            break;
-        }
-        if ((rc = sfe_icp_jobs_dev(ctx, p, (const float *)s->d_pool, (const float *)s->d_pool, jobs4.data(), d_g, n_jobs, d_T,
-                                   d_st, d_st + n_jobs)))
-            break;
-        if (hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            rc = sfe_set_err(ctx, SFE_ERR_HIP, "scan match over the store: download of the results failed");
-            break;
-        }
-        memcpy(T_out9, h_out, sizeof(float) * 9 * (size_t)n_jobs);
-        memcpy(status, h_out + sizeof(float) * 9 * (size_t)n_jobs, sizeof(int32_t) * (size_t)n_jobs);
-        if (iters)
-            memcpy(iters, h_out + (sizeof(float) * 9 + sizeof(int32_t)) * (size_t)n_jobs, sizeof(int32_t) * (size_t)n_jobs);
-        // a job shared by several workgroups whose shares were not resident together: once more, unsplit (sonarfe.h,
-        // sfe_icp_set_tuning bit 4)
-        bool timeout = false;
-        for (int j = 0; j < n_jobs; ++j)
-            timeout |= status[j] == SFE_ICP_SPLIT_TIMEOUT;
-        if (!timeout || attempt == 1 || was_unsplit)
-            break;
-        ctx->icp_variant |= 16;
-    }
-    if (!was_unsplit)
-        ctx->icp_variant &= ~16;
-    return rc;
+    IcpCall call;
+    if (o)
+        call.ox = *o;
+    const float *pool = (const float *)s->d_pool;
+    if (n_rd != 0 || n_rf != 0)
+        return sfe_icp_dpf_run_host(ctx, p, call, rd, n_rd, rf, n_rf, pool, pool, jobs4.data(), guesses9, n_jobs, T_out9,
+                                    status, iters);
+    return sfe_icp_run_host(ctx, p, call, pool, pool, jobs4.data(), guesses9, nullptr, n_jobs, T_out9, status, iters);
+}
+
+int sfe_icp_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store *s, const int32_t *pairs,
+                          const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
+{
+    return store_icp(ctx, p, nullptr, nullptr, 0, nullptr, 0, s, pairs, guesses9, n_jobs, T_out9, status, iters);
+}
+
+int sfe_icp_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o,
+                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf,
+                                    sfe_cloud_store *s, const int32_t *pairs, const float *guesses9, int n_jobs,
+                                    float *T_out9, int32_t *status, int32_t *iters)
+{
+    return store_icp(ctx, p, o, rd, n_rd, rf, n_rf, s, pairs, guesses9, n_jobs, T_out9, status, iters);
 }
 
 int sfe_cloud_store_overlap(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *pairs, const float *T6, int n_jobs,

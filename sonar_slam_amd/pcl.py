@@ -289,6 +289,21 @@ class ICP(object):
                                "default chain either, pcl.cpp:185)")
         return self.params
 
+    def _call(self, ctx, shape, clouds, g, n, T, st, it):
+        """One host-pointer ICP call of ``shape`` ("guesses", "pairs", "jobs"; ``clouds`` = its cloud arguments).  The
+        chain picks the entry point: no stages and no outliers -> the plain one; outliers -> ``_chain_ext``; stages
+        only -> ``_chain``."""
+        stages, ox = self._stages(), self._outliers()
+        name, extra = "sfe_icp_compute_" + shape, ()
+        if ox is not None:
+            name, extra = name + "_chain_ext", (_C.byref(ox),) + (stages or (None, 0, None, 0))
+        elif stages is not None:
+            name, extra = name + "_chain", stages
+        args = (ctx.handle, _C.byref(self.params)) + tuple(extra) + tuple(clouds) + (
+            _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32))
+        with ctx.lock:
+            ctx._check(getattr(ctx.lib, name)(*args))
+
     @staticmethod
     def _guess(guess):
         g = _np.asarray(guess, _np.float32)
@@ -306,7 +321,7 @@ class ICP(object):
     def compute_batch(self, source, target, guesses):
         """Many initial guesses on one cloud pair in one launch.
         -> (messages [n], T [n x 3 x 3] float32, iterations [n])"""
-        params = self._chain()
+        self._chain()
         ctx = self._ctx or _L.default_context()
         src = _cloud(source, "ICP.compute(source)")
         tgt = _cloud(target, "ICP.compute(target)")
@@ -317,31 +332,14 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
-        stages, ox = self._stages(), self._outliers()
-        with ctx.lock:
-            if stages is None and ox is None:
-                ctx._check(ctx.lib.sfe_icp_compute_guesses(
-                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src),
-                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
-            elif ox is not None:
-                ctx._check(ctx.lib.sfe_icp_compute_guesses_chain_ext(
-                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
-                    _L.ptr(src, _C.c_float), len(src),
-                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
-            else:
-                ctx._check(ctx.lib.sfe_icp_compute_guesses_chain(
-                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), len(src),
-                    _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+        self._call(ctx, "guesses", (_L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt)), g, n, T, st, it)
         msgs = [_L.ICP_STATUS_MESSAGES.get(int(s), "ICP failure %d" % s) for s in st]
         return msgs, T, it
 
     def compute_pairs(self, sources, targets, guesses):
         """Many independent (source, target, guess) scan matches in ONE launch (extension; the job
         farm's unit).  -> (messages [n], T [n x 3 x 3] float32, iterations [n])"""
-        params = self._chain()
+        self._chain()
         ctx = self._ctx or _L.default_context()
         n = len(sources)
         if not (len(targets) == n and len(guesses) == n):
@@ -362,24 +360,8 @@ class ICP(object):
         T = _np.zeros((n, 3, 3), _np.float32)
         st = _np.zeros(n, _np.int32)
         it = _np.zeros(n, _np.int32)
-        stages, ox = self._stages(), self._outliers()
-        with ctx.lock:
-            if stages is None and ox is None:
-                ctx._check(ctx.lib.sfe_icp_compute_pairs(
-                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
-                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
-            elif ox is not None:
-                ctx._check(ctx.lib.sfe_icp_compute_pairs_chain_ext(
-                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
-                    _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
-                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
-            else:
-                ctx._check(ctx.lib.sfe_icp_compute_pairs_chain(
-                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32),
-                    _L.ptr(tgt, _C.c_float), _L.ptr(to, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+        self._call(ctx, "pairs", (_L.ptr(src, _C.c_float), _L.ptr(so, _C.c_int32), _L.ptr(tgt, _C.c_float),
+                                  _L.ptr(to, _C.c_int32)), g, n, T, st, it)
         msgs = [_L.ICP_STATUS_MESSAGES.get(int(s), "ICP failure %d" % s) for s in st]
         return msgs, T, it
 
@@ -389,7 +371,7 @@ class ICP(object):
         tgt_start, n_tgt) in points, guesses9 = n x 9.  Jobs may share clouds; jobs naming the same target slice
         share its preparation.  -> (status int32 [n], T [n x 3 x 3] float32, iterations int32 [n]); the three
         arrays may be handed in preallocated (``out=(status, T, iters)``, e.g. views of shared memory)."""
-        params = self._chain()
+        self._chain()
         ctx = self._ctx or _L.default_context()
         src = _cloud(src_all, "ICP.compute_jobs(src_all)")
         tgt = _cloud(tgt_all, "ICP.compute_jobs(tgt_all)")
@@ -402,24 +384,8 @@ class ICP(object):
             st, T, it = out
         if n and ((jobs4[:, 1] <= 0).any() or (jobs4[:, 3] <= 0).any()):
             raise RuntimeError("ICP.compute_jobs: empty point cloud (libpointmatcher would throw)")
-        stages, ox = self._stages(), self._outliers()
-        with ctx.lock:
-            if stages is None and ox is None:
-                ctx._check(ctx.lib.sfe_icp_compute_jobs(
-                    ctx.handle, _C.byref(params), _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt),
-                    _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32),
-                    _L.ptr(it, _C.c_int32)))
-            elif ox is not None:
-                ctx._check(ctx.lib.sfe_icp_compute_jobs_chain_ext(
-                    ctx.handle, _C.byref(params), _C.byref(ox), *(stages or (None, 0, None, 0)),
-                    _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float),
-                    len(tgt), _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
-            else:
-                ctx._check(ctx.lib.sfe_icp_compute_jobs_chain(
-                    ctx.handle, _C.byref(params), *stages, _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float),
-                    len(tgt), _L.ptr(jobs4, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
-                    _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+        self._call(ctx, "jobs", (_L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt),
+                                 _L.ptr(jobs4, _C.c_int32)), g, n, T, st, it)
         return st, T, it
 
     def getCovariance(self):

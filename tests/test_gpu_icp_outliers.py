@@ -329,3 +329,31 @@ def test_bound_listed_after_counter_skips_the_last_iteration(ctx):
         assert (int(b[0][0]), int(b[2][0])) == (L.ICP_BOUND, k), b[:3]
         _check_ref(p, after, [0], [src], [tgt], [(0, 0)], [guess], a, ("after", variant))
         _check_ref(p, first, [0], [src], [tgt], [(0, 0)], [guess], b, ("first", variant))
+
+
+def test_nothing_of_one_call_survives_into_the_next():
+    """The outlier settings and the unsplit retry travel with the call, not on the context: after a ``*_chain_ext`` call
+    with MedianDist that is refused with SFE_ERR_ARG (a job outside its pool), a plain ``sfe_icp_compute_jobs`` and a
+    ``*_chain_ext`` call give bit for bit what the same calls give on a context that has seen nothing else"""
+    p, ox = icp_config.shipped_params(use_trimmed_filter=0), _ox(use_median=1, median_factor=2.0)
+    pairs = [synth.scan_pair(seed=5200 + i, n_src=a, n_tgt=b) for i, (a, b) in enumerate([(150, 180), (700, 900), (2600, 2600)])]
+    srcs, tgts, gs = [q[0] for q in pairs], [q[1] for q in pairs], [q[2] for q in pairs]
+    jobs = [(i, i) for i in range(len(pairs))]
+
+    def calls(c):
+        return [_jobs(c, p, o, srcs, tgts, jobs, gs)[:3] for o in (None, ox, None)]
+
+    used, fresh = L.Context(0), L.Context(0)
+    try:
+        sp, tp = _pool(srcs)[0], _pool(tgts)[0]
+        beyond = np.array([[0, len(sp) + 1, 0, len(tgts[0])]], np.int32)
+        with pytest.raises(L.SonarFEError, match="libsonarfe error -1:"):
+            _icp(used, p, ox).compute_jobs(sp, tp, beyond, np.asarray(gs[0], np.float32).reshape(1, 9))
+        got, want = calls(used), calls(fresh)
+    finally:
+        used.close()
+        fresh.close()
+    for k, what in enumerate(("plain after the refused call", "chain_ext", "plain after chain_ext")):
+        _same(got[k], want[k], what)
+    _same(want[0], want[2], "plain twice")
+    assert not np.array_equal(want[0][1], want[1][1]), "MedianDist{2} left every pose as it was: the chain_ext call shows nothing"
