@@ -459,6 +459,11 @@ int sfe_cloud_store_meta(sfe_ctx *ctx, sfe_cloud_store *s, int32_t first, int32_
                          int32_t *counts);
 /* the points of one cloud, for whoever needs them on the host (the PointCloud2 of publish_features, rviz, mapping) */
 int sfe_cloud_store_read(sfe_ctx *ctx, sfe_cloud_store *s, int32_t handle, float *out, int cap, int *n_out);
+/* the points of n clouds back to back in `out` (room for cap points): one copy per cloud, one synchronisation at the end (the
+ * copies land in pageable memory, so the runtime may stage each of them); counts_out[i] as
+ * sfe_cloud_store_read's n_out (<= 0: nothing written for that cloud) */
+int sfe_cloud_store_read_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n, float *out, long long cap,
+                              int32_t *counts_out);
 /* release every slot >= n_slots */
 int sfe_cloud_store_truncate(sfe_ctx *ctx, sfe_cloud_store *s, int32_t n_slots);
 /* SLAM.get_points(frames, ref_frame) for n_jobs target clouds at once (slam.py:229-292): job j takes the clouds
@@ -673,6 +678,71 @@ int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap);
 int sfe_map_frames(sfe_map *m, int n, const int32_t *slots);
 int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
                    int8_t *occ_out);
+
+/* ---- S occupancy maps that advance together (sonar_slam_amd/mapping.py: MapBatch; chained.SessionBatch's maps).  One
+ * sfe_mapset owns the state of n_maps maps, each exactly what an sfe_map of its own would hold after the same calls: the
+ * float32 grids (each with its own rows, columns and growth counters), one table of sonar_xy geometries shared by all maps,
+ * and for every (map, slot) its polar log-odds image and its double-buffered cell list.  Every stage is one call over any
+ * subset of the maps; a keyframe is named by (map, slot).  Entry points take host pointers.
+ *
+ * Memory: the arena is allocated once, at creation, for n_maps * max_keyframes slots of max_px pixels each and is never
+ * reallocated: per keyframe max_px * 20 bytes (float32 log-odds 4 B, two cell lists of uint16 r + uint16 c + float32 l = 8 B
+ * each, per pixel) + 8 bytes of counts; 2.1 MB at the 105 k pixels of a 1024 x 512 ping at the shipped skips.  A slot >=
+ * max_keyframes or a geometry of more than max_px pixels is refused with SFE_ERR_CAP before anything changes.  Only this
+ * arena is fixed.  Grids are reallocated when they grow, a frames grid when its map's shape changed, and the grow-only scratch
+ * (job tables, measurement mask and image, render output, fit windows) when a call needs more than any before it, each with a
+ * stream synchronisation.  The fit windows of one refit call lie back to back, 4 bytes per cell of every listed keyframe's
+ * bounding box (about 360 KB for a 30 m fan at 0.2 m), and are kept: a caller with very many keyframes bounds that by the
+ * number of keyframes it lists per call.
+ *   sfe_mapset_create: every map starts as a zero grid [rows x cols].
+ *   sfe_mapset_geometry: as sfe_map_geometry, for all maps (the caller stores equal tables once).
+ *   sfe_mapset_set_logodds: n ready log-odds images, back to back in `logodds`, image b for (maps[b], slots[b]) of geometry
+ *     geoms[b].  One synchronisation.
+ *   sfe_mapset_measure: sfe_map_measure over (map, slot) jobs: all hits in one upload.  One synchronisation.
+ *     sfe_mapset_measure_stages reads job b of the last call.
+ *   sfe_mapset_fit_bounds: as sfe_map_fit_bounds; keyframe b carries its own pose and its own map's origin.  One synchronisation.
+ *   sfe_mapset_grow: pad map maps[b] by grow4[4 b ..] = {top, bottom, left, right} (each map at most once per call); a map
+ *     with four zeros costs nothing; one synchronisation for all the maps that grew.
+ *   sfe_mapset_refit: fit and deduplicate all n keyframes in one pass (each keyframe's window is sized by its own bounds),
+ *     then the ordered applies.  The keyframes of one map are applied in the order they are listed (subtract the current list
+ *     if dec[b], then add the new one); maps are independent, so the i-th apply of every map runs in one launch: K refits per
+ *     map cost 2 K launches (K without dec), however many maps take part.  Enqueue only; a (map, slot) at most once per call.
+ *   sfe_mapset_cells / _logodds / _read_grid / _shape: read back one map's or one keyframe's state, as the sfe_map calls.
+ *   sfe_mapset_apply_launches: the apply launches (rounds) the set has made since it was created, refit and frames alike.
+ *   sfe_mapset_frames: for map maps[b] a fresh grid with slots[slot_off[b] .. slot_off[b + 1]) added in list order (rounds as
+ *     in refit).  Enqueue only.
+ *   sfe_mapset_render: n images in one launch and one read-back: job b renders box4[4 b ..] = {r0, r1, c0, c1} of map maps[b]'s
+ *     grid (which[b] = 1: its frames grid) to out_hw[2 b ..] = {out_h, out_w} at occ_out + out_off[b]; `total` bytes in all.
+ *     inv / resize as sfe_map_render.
+ * sfe_remove_outlier_many: sfe_remove_outlier's decision for n_clouds clouds in one launch: cloud c = pts[off[c] .. off[c + 1])
+ *   (points), keep_out[i] = 1 for the points that stay.  One synchronisation. */
+typedef struct sfe_mapset sfe_mapset;
+int sfe_mapset_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyframes, int max_px, sfe_mapset **out);
+void sfe_mapset_destroy(sfe_mapset *ms);
+int sfe_mapset_geometry(sfe_mapset *ms, const float *sonar_xy, int img_rows, int img_cols, int *id_out);
+int sfe_mapset_set_logodds(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                           const float *logodds);
+int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                       const int32_t *hit_off, const int32_t *hits, const int32_t *hrhc, const int32_t *k_off,
+                       const float *ktab, int n_ktab, const double *div, float miss32, float logit_miss, float hit32,
+                       float logit_hit);
+int sfe_mapset_measure_stages(sfe_mapset *ms, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out);
+int sfe_mapset_fit_bounds(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4,
+                          const double *origin2, double resolution, int32_t *mm_out);
+int sfe_mapset_grow(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *grow4);
+int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4,
+                     const double *origin2, double resolution, const int32_t *mm, const int32_t *shift2, const uint8_t *dec);
+int sfe_mapset_cells(sfe_mapset *ms, int map, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out);
+int sfe_mapset_logodds(sfe_mapset *ms, int map, int slot, float *out, int cap);
+int sfe_mapset_shape(sfe_mapset *ms, int map, int32_t *rows_cols_grow4);
+int sfe_mapset_apply_launches(sfe_mapset *ms, long long *n_out);
+int sfe_mapset_read_grid(sfe_mapset *ms, int map, int which, float *out, long long cap);
+int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int32_t *slot_off, const int32_t *slots);
+int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *which, const int32_t *box4,
+                      const int32_t *out_hw, const double *inv, const int32_t *resize, const long long *out_off,
+                      int8_t *occ_out, long long total);
+int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,
+                            uint8_t *keep_out);
 
 #ifdef __cplusplus
 }

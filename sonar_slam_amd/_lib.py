@@ -258,6 +258,7 @@ SIGNATURES = {
     "sfe_cloud_store_compact_selected_many": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i64p, _i32p]),
     "sfe_cloud_store_match_keys_many": (C.c_int, [_vp, _vp, _i32p, _f32p, _i32p, C.c_int, C.c_float, C.c_int, C.c_int, _i32p,
                                                   _i32p]),
+    "sfe_cloud_store_read_many": (C.c_int, [_vp, _vp, _i32p, C.c_int, _f32p, C.c_longlong, _i32p]),
     "sfe_map_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "sfe_map_destroy": (None, [_vp]),
     "sfe_map_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
@@ -276,6 +277,26 @@ SIGNATURES = {
     "sfe_map_frames": (C.c_int, [_vp, C.c_int, _i32p]),
     "sfe_map_render": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                  C.POINTER(C.c_int8)]),
+    "sfe_mapset_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "sfe_mapset_destroy": (None, [_vp]),
+    "sfe_mapset_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_mapset_set_logodds": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _f32p]),
+    "sfe_mapset_measure": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, C.c_int, _f64p,
+                                     C.c_float, C.c_float, C.c_float, C.c_float]),
+    "sfe_mapset_measure_stages": (C.c_int, [_vp, C.c_int, _u8p, _f32p, _i32p]),
+    "sfe_mapset_fit_bounds": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f64p, _f64p, C.c_double, _i32p]),
+    "sfe_mapset_grow": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
+    "sfe_mapset_refit": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f64p, _f64p, C.c_double, _i32p, _i32p, _u8p]),
+    "sfe_mapset_cells": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _f32p, C.c_int,
+                                   C.POINTER(C.c_int)]),
+    "sfe_mapset_logodds": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_int]),
+    "sfe_mapset_shape": (C.c_int, [_vp, C.c_int, _i32p]),
+    "sfe_mapset_apply_launches": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
+    "sfe_mapset_read_grid": (C.c_int, [_vp, C.c_int, C.c_int, _f32p, C.c_longlong]),
+    "sfe_mapset_frames": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p]),
+    "sfe_mapset_render": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong),
+                                    C.POINTER(C.c_int8), C.c_longlong]),
+    "sfe_remove_outlier_many": (C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_double, C.c_int, _u8p]),
 }
 
 _lib = None

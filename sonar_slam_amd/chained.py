@@ -150,7 +150,7 @@ class SessionBatch(object):
                  odom_sigmas=(0.2, 0.2, 0.02), shgo_workers=1, shgo_replay=True, nssm_enable=False, nssm_initialization=True,
                  nssm_initialization_params=(100, 5, 0.01), nssm_min_st_sep=8, nssm_min_points=50, nssm_max_translation=10.0,
                  nssm_max_rotation=np.deg2rad(60), nssm_source_frames=5, nssm_cov_samples=30, oculus_max_range=30.0,
-                 oculus_horizontal_aperture=np.radians(130.0), mcd_random_state=None):
+                 oculus_horizontal_aperture=np.radians(130.0), mcd_random_state=None, mapping=None):
         from .pipeline import KeyframeBatch
         from .replay import ChainBackend
         self.ctx, self.S, self.K = ctx, int(n_sessions), int(n_steps)
@@ -194,6 +194,18 @@ class SessionBatch(object):
         # shgo_replay: sonar_slam_amd/shgo_fast.py -- what shgo decides after its sampling stage, replayed for all sessions from
         # one table of costs; scipy.optimize.shgo itself only for the sessions the replay reports as undecidable
         self.shgo_replay, self._plan = bool(shgo_replay), None
+        # mapping: None (no map: the batch allocates, runs and records what it did before maps existed), or a dict: `ping` (what
+        # Mapping.add_keyframe reads of a ping: num_ranges, range_resolution, bearings), optionally `max_pixels`, and Mapping's
+        # settings -> self.maps, a mapping.MapBatch that step(k) feeds keyframe k of every session
+        self.maps, self._map_ping = None, None
+        if mapping is not None:
+            from .mapping import MapBatch
+            mapping = dict(mapping)
+            if "ping" not in mapping:
+                raise ValueError("SessionBatch: mapping needs a `ping` (num_ranges, range_resolution, bearings)")
+            self._map_ping = mapping.pop("ping")
+            self.maps = MapBatch(ctx, self.S, self.K, **mapping)
+            self.maps.configure()
         self.init_stats = {"shgo_s": 0.0, "cost_calls": 0, "table_hits": 0, "speculated": 0, "speculation_failed": 0,
                            "replayed": 0, "replay_fallbacks": 0, "transforms_s": 0.0, "table_s": 0.0, "grids_s": 0.0}
         self.reset()
@@ -247,6 +259,8 @@ class SessionBatch(object):
         self.records = []
         self.covs = [[None] * self.K for _ in range(self.S)]        # marginal covariance per keyframe (loop-closure search)
         self.loops = [[] for _ in range(self.S)]                    # ("loop", target_key, source_key, transform, cov) per session
+        if self.maps is not None and any(len(v.keyframes) for v in self.maps.maps):
+            self.maps.reset()
 
     def step(self, k):
         """-> dict of per-session arrays: status codes, sizes, transforms, overlaps, poses"""
@@ -268,6 +282,7 @@ class SessionBatch(object):
             rec["pose"] = self.poses[0].xytheta()
             self.records.append(rec)
             self._after_keyframe(k, rec)
+            self._map_keyframe(k)
             return rec
         # frame.update(current_keyframe.pose.compose(dr_odom))              slam_ros.py:181-184
         prev = self.poses[k - 1]
@@ -287,7 +302,16 @@ class SessionBatch(object):
         finally:
             store.truncate(n_keep)                                          # the targets are dropped, the keyframes stay
         self._after_keyframe(k, rec)
+        self._map_keyframe(k)
         return rec
+
+    def _map_keyframe(self, k):
+        """keyframe k of every session into its occupancy map: the cloud stored for the ping, the pose just recorded (pose
+        corrections are the caller's: ``self.maps.update_poses``)"""
+        if self.maps is None:
+            return
+        clouds = self.store.read_many(self.handles[:, k])
+        self.maps.add_keyframes(range(self.S), [k] * self.S, [self._pose(k, s) for s in range(self.S)], self._map_ping, clouds)
 
     def _scan_match_step(self, k, rec, src_h, th, T6, prev, pose):
         S, store = self.S, self.store
@@ -794,6 +818,8 @@ class SessionBatch(object):
         self.kb.free()
         self.d_frames.free()
         self.store.close()
+        if self.maps is not None:
+            self.maps.close()
 
 
 PRIOR, SUCCESS, NOT_ENOUGH_POINTS, NOT_CONVERGED, LARGE_TRANSFORMATION, NOT_ENOUGH_OVERLAP, INITIALIZATION_FAILURE = range(7)

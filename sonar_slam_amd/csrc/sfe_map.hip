@@ -22,6 +22,11 @@ struct MapGeom {
     int img_rows = 0, img_cols = 0;
 };
 
+struct MapBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
 struct MapSlot {
     int geom = -1;
     float *d_logodds = nullptr;
@@ -72,23 +77,20 @@ struct sfe_map {
     std::vector<MapSlot> slots;
     int32_t *d_counts = nullptr; // [slot][2]: cell count of each list buffer
     int counts_cap = 0;
-    struct Buf {
-        void *p = nullptr;
-        size_t cap = 0;
-    } buf[6];
+    MapBuf buf[6];
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
 };
 
 namespace {
 
-void *map_buf(sfe_map *m, int i, size_t bytes)
+// grow-only device scratch
+void *buf_get(sfe_ctx *ctx, MapBuf &b, size_t bytes)
 {
-    auto &b = m->buf[i];
     if (b.cap >= bytes && b.p)
         return b.p;
     if (b.p) {
-        (void)hipStreamSynchronize(m->ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
         (void)hipFree(b.p);
         b.p = nullptr;
         b.cap = 0;
@@ -100,6 +102,11 @@ void *map_buf(sfe_map *m, int i, size_t bytes)
     }
     b.cap = cap;
     return b.p;
+}
+
+void *map_buf(sfe_map *m, int i, size_t bytes)
+{
+    return buf_get(m->ctx, m->buf[i], bytes);
 }
 
 // --- measurement (mapping.py:170-228) ---------------------------------------------------------------------------------
@@ -832,6 +839,816 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
                        ctx->stream, src, m->cols, r0, c0, h, w, out_h, out_w, inv, resize, d);
     SFE_LAUNCH_CHECK(ctx);
     SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+} // extern "C"
+
+// ======================================================================================================================
+// sfe_mapset: S maps that advance together.  The kernels above run unchanged over (map, slot) jobs -- their job tables
+// carry pointers, so a job does not know which map it belongs to; what is new is the arena, the apply rounds and the
+// many-map render.
+//
+// Arena: fixed at creation for n_maps * max_keyframes slots of max_px pixels each.  Slot (map, k) owns
+//   logodds  float32 [max_px]
+//   r, c     uint16  [2][max_px] each   (the double-buffered cell list)
+//   l        float32 [2][max_px]
+// = 20 bytes per pixel, 20 * max_px bytes per keyframe (2.1 MB at the 105 k pixels of a 1024 x 512 ping at the shipped
+// skips), plus 8 bytes of counts.  Nothing is reallocated afterwards: a slot >= max_keyframes or an image of more than max_px
+// pixels is refused (SFE_ERR_CAP) before any state changes.  Grids are per map and grow on their own.
+namespace {
+
+struct SetSlot {
+    int geom = -1; // -1: unused
+    int cur = 0, has_cells = 0;
+    int base_r = 0, base_c = 0;
+};
+
+struct SetMap {
+    int rows = 0, cols = 0;
+    float *d_grid = nullptr, *d_frames = nullptr;
+    int frames_rows = 0, frames_cols = 0;
+    int grow_r = 0, grow_c = 0;
+};
+
+// one ordered add / subtract of a cell list on its map's grid
+struct ApplyJob {
+    float *grid;
+    int32_t rows, cols;
+    const uint16_t *r, *c;
+    const float *l;
+    const int32_t *n;
+    int32_t dr, dc; // growth since the list was written
+    int32_t sub;
+    int32_t n_px; // upper bound of *n (the pixels of its image)
+};
+
+struct RenderJob {
+    const float *grid;
+    int32_t cols, r0, c0, h, w, oh, ow, resize;
+    double inv;
+    int64_t out_off;
+};
+
+// One round: job blockIdx.y is the next apply of one map, so no two jobs of a launch share a grid, and the cells of a list are
+// unique: plain loads and stores, every cell written by one thread.  One pass, 8 B read + 4 B read-modify-write per cell.
+__global__ __launch_bounds__(MAP_THREADS) void mapset_apply_kernel(const ApplyJob *jobs)
+{
+    const ApplyJob j = jobs[blockIdx.y];
+    const int n = min(*j.n, j.n_px);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int rr = (int)j.r[i] + j.dr, cc = (int)j.c[i] + j.dc;
+        if (rr < 0 || rr >= j.rows || cc < 0 || cc >= j.cols)
+            continue; // cannot happen: every cell lies inside the grown grid
+        float *g = j.grid + (int64_t)rr * j.cols + cc;
+        *g = j.sub ? __fsub_rn(*g, j.l[i]) : __fadd_rn(*g, j.l[i]);
+    }
+}
+
+// map_render_kernel for many maps: job blockIdx.y writes its out_h x out_w image at out + out_off
+__global__ __launch_bounds__(MAP_THREADS) void mapset_render_kernel(const RenderJob *jobs, int8_t *out)
+{
+    const RenderJob j = jobs[blockIdx.y];
+    const int64_t n = (int64_t)j.oh * j.ow;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int y = (int)(i / j.ow), x = (int)(i - (int64_t)y * j.ow);
+        int sy = y, sx = x;
+        if (j.resize) {
+            sy = min((int)floor(__dmul_rn((double)y, j.inv)), j.h - 1);
+            sx = min((int)floor(__dmul_rn((double)x, j.inv)), j.w - 1);
+        }
+        const double v = (double)j.grid[(int64_t)(j.r0 + sy) * j.cols + j.c0 + sx];
+        const float p = (float)__ddiv_rn(1.0, __dadd_rn(1.0, exp(-v)));
+        float q = __fmul_rn(100.0f, p);
+        q = q < 0.0f ? 0.0f : (q > 100.0f ? 100.0f : q);
+        out[j.out_off + i] = (int8_t)(int)q;
+    }
+}
+
+// pcl.remove_outlier's decision (radius_count_kernel of sfe_icp.hip, the same float32 arithmetic) for many clouds: cloud
+// blockIdx.y = pts[off[y] .. off[y + 1]); keep iff more than min_points points (itself included) lie within the radius
+__global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__restrict__ pts, const int32_t *__restrict__ off,
+                                                                float r2, int min_points, uint8_t *__restrict__ keep)
+{
+    __shared__ float2 s_p[2048];
+    const int base = off[blockIdx.y], n = off[blockIdx.y + 1] - base;
+    if ((int)(blockIdx.x * 256) >= n)
+        return; // the whole block at once
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float px = 0, py = 0;
+    if (i < n) {
+        const float2 p = pts[base + i];
+        px = p.x;
+        py = p.y;
+    }
+    int cnt = 0;
+    for (int tb = 0; tb < n; tb += 2048) {
+        const int tn = min(2048, n - tb);
+        __syncthreads();
+        for (int j = threadIdx.x; j < tn; j += 256)
+            s_p[j] = pts[base + tb + j];
+        __syncthreads();
+        for (int j = 0; j < tn; ++j) {
+            const float2 t = s_p[j];
+            const float dx = __fadd_rn(px, -t.x), dy = __fadd_rn(py, -t.y);
+            cnt += __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= r2;
+        }
+    }
+    if (i < n)
+        keep[base + i] = cnt > min_points;
+}
+
+} // namespace
+
+struct sfe_mapset {
+    sfe_ctx *ctx = nullptr;
+    int n_maps = 0, max_kf = 0, max_px = 0;
+    std::vector<SetMap> maps;
+    std::vector<MapGeom> geoms;
+    std::vector<SetSlot> slots; // [map * max_kf + slot]
+    float *d_logodds = nullptr, *d_l = nullptr;
+    uint16_t *d_r = nullptr, *d_c = nullptr;
+    int32_t *d_counts = nullptr; // [map * max_kf + slot][2]
+    MapBuf buf[6];
+    int last_meas_n = 0;
+    std::vector<MeasJob> last_meas;
+    long long apply_launches = 0; // launches of mapset_apply_kernel so far
+};
+
+namespace {
+
+inline size_t set_idx(const sfe_mapset *ms, int map, int slot) { return (size_t)map * ms->max_kf + slot; }
+inline float *set_logodds(sfe_mapset *ms, size_t idx) { return ms->d_logodds + idx * ms->max_px; }
+inline uint16_t *set_r(sfe_mapset *ms, size_t idx, int b) { return ms->d_r + (2 * idx + b) * ms->max_px; }
+inline uint16_t *set_c(sfe_mapset *ms, size_t idx, int b) { return ms->d_c + (2 * idx + b) * ms->max_px; }
+inline float *set_l(sfe_mapset *ms, size_t idx, int b) { return ms->d_l + (2 * idx + b) * ms->max_px; }
+
+int set_grid_alloc(sfe_mapset *ms, float **d, size_t n)
+{
+    if (hipMalloc((void **)d, n * sizeof(float)) != hipSuccess)
+        return sfe_set_err(ms->ctx, SFE_ERR_HIP, "map set grid allocation of %zu cells failed", n);
+    SFE_HIP(ms->ctx, hipMemsetAsync(*d, 0, n * sizeof(float), ms->ctx->stream));
+    return 0;
+}
+
+// may (map, slot) take an image of geometry g?  Checks only.
+int set_slot_check(sfe_mapset *ms, int map, int slot, int g)
+{
+    sfe_ctx *ctx = ms->ctx;
+    SFE_ARG(ctx, map >= 0 && map < ms->n_maps && slot >= 0 && g >= 0 && g < (int)ms->geoms.size());
+    if (slot >= ms->max_kf)
+        return sfe_set_err(ctx, SFE_ERR_CAP, "map set: keyframe slot %d of map %d, room for %d keyframes per map", slot, map,
+                           ms->max_kf);
+    const SetSlot &s = ms->slots[set_idx(ms, map, slot)];
+    SFE_ARG(ctx, s.geom < 0 || s.geom == g);
+    return 0;
+}
+
+// a used (map, slot)
+int set_slot_used(sfe_mapset *ms, int map, int slot)
+{
+    SFE_ARG(ms->ctx, map >= 0 && map < ms->n_maps && slot >= 0 && slot < ms->max_kf &&
+                         ms->slots[set_idx(ms, map, slot)].geom >= 0);
+    return 0;
+}
+
+// a job table through pinned staging: enqueue only
+template <class T>
+T *set_stage(sfe_mapset *ms, int i, const std::vector<T> &jobs)
+{
+    sfe_ctx *ctx = ms->ctx;
+    const size_t bytes = sizeof(T) * jobs.size();
+    T *d = (T *)buf_get(ctx, ms->buf[i], bytes ? bytes : 1);
+    if (!d || !bytes)
+        return d;
+    void *pin = sfe_pinned_begin(ctx, bytes);
+    if (!pin)
+        return nullptr;
+    memcpy(pin, jobs.data(), bytes);
+    if (hipMemcpyAsync(d, pin, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        return nullptr;
+    if (sfe_pinned_end(ctx, ctx->stream))
+        return nullptr;
+    return d;
+}
+
+template <class T>
+T *set_upload(sfe_mapset *ms, int i, const T *h, size_t n)
+{
+    T *d = (T *)buf_get(ms->ctx, ms->buf[i], sizeof(T) * (n ? n : 1));
+    if (!d)
+        return nullptr;
+    if (n && hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, ms->ctx->stream) != hipSuccess)
+        return nullptr;
+    return d;
+}
+
+int set_fit_jobs(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4, const double *origin2,
+                 std::vector<FitJob> &jobs, int &max_px)
+{
+    jobs.assign(n, FitJob());
+    max_px = 0;
+    for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_used(ms, maps[b], slots[b]))
+            return rc;
+        const size_t idx = set_idx(ms, maps[b], slots[b]);
+        const MapGeom &g = ms->geoms[ms->slots[idx].geom];
+        FitJob &j = jobs[b];
+        j.xy = g.d_xy;
+        j.n_px = g.img_rows * g.img_cols;
+        j.c = pose4[4 * b], j.s = pose4[4 * b + 1], j.tx = pose4[4 * b + 2], j.ty = pose4[4 * b + 3];
+        j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1];
+        j.logodds = set_logodds(ms, idx);
+        max_px = max(max_px, j.n_px);
+    }
+    return 0;
+}
+
+// rounds of applies: round i holds the i-th apply of every map that has one; a launch per round
+int set_run_rounds(sfe_mapset *ms, int buf, const std::vector<std::vector<ApplyJob>> &rounds)
+{
+    sfe_ctx *ctx = ms->ctx;
+    std::vector<ApplyJob> flat;
+    for (const auto &r : rounds)
+        flat.insert(flat.end(), r.begin(), r.end());
+    if (flat.empty())
+        return 0;
+    ApplyJob *d = set_stage(ms, buf, flat);
+    if (!d)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: apply job table upload failed");
+    size_t off = 0;
+    for (const auto &r : rounds) {
+        int px = 1;
+        for (const auto &j : r)
+            px = max(px, j.n_px);
+        hipLaunchKernelGGL(mapset_apply_kernel, dim3((unsigned)((px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)r.size()),
+                           dim3(MAP_THREADS), 0, ctx->stream, d + off);
+        SFE_LAUNCH_CHECK(ctx);
+        ++ms->apply_launches;
+        off += r.size();
+    }
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+int sfe_mapset_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyframes, int max_px, sfe_mapset **out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, out != nullptr && n_maps > 0 && n_maps <= 4096 && rows > 0 && cols > 0 && (long long)rows * cols < (1LL << 31));
+    SFE_ARG(ctx, max_keyframes > 0 && max_px > 0 && max_px < (1 << 30));
+    SFE_ARG(ctx, (long long)n_maps * max_keyframes < (1LL << 28));
+    sfe_mapset *ms = new sfe_mapset();
+    ms->ctx = ctx;
+    ms->n_maps = n_maps, ms->max_kf = max_keyframes, ms->max_px = max_px;
+    ms->maps.resize(n_maps);
+    const size_t n_slots = (size_t)n_maps * max_keyframes, px = n_slots * (size_t)max_px;
+    ms->slots.resize(n_slots);
+    bool ok = hipMalloc((void **)&ms->d_logodds, px * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&ms->d_l, 2 * px * sizeof(float)) == hipSuccess &&
+              hipMalloc((void **)&ms->d_r, 2 * px * sizeof(uint16_t)) == hipSuccess &&
+              hipMalloc((void **)&ms->d_c, 2 * px * sizeof(uint16_t)) == hipSuccess &&
+              hipMalloc((void **)&ms->d_counts, 2 * n_slots * sizeof(int32_t)) == hipSuccess &&
+              hipMemsetAsync(ms->d_counts, 0, 2 * n_slots * sizeof(int32_t), ctx->stream) == hipSuccess;
+    int rc = ok ? 0
+                : sfe_set_err(ctx, SFE_ERR_HIP, "map set: arena of %d maps x %d keyframes x %d pixels (%zu bytes) failed",
+                              n_maps, max_keyframes, max_px, px * 20);
+    for (int m = 0; m < n_maps && !rc; ++m) {
+        ms->maps[m].rows = rows, ms->maps[m].cols = cols;
+        rc = set_grid_alloc(ms, &ms->maps[m].d_grid, (size_t)rows * cols);
+    }
+    if (rc) {
+        sfe_mapset_destroy(ms);
+        return rc;
+    }
+    *out = ms;
+    return 0;
+}
+
+void sfe_mapset_destroy(sfe_mapset *ms)
+{
+    if (!ms)
+        return;
+    if (sfe_use(ms->ctx) == 0)
+        (void)hipStreamSynchronize(ms->ctx->stream);
+    for (auto &m : ms->maps) {
+        (void)hipFree(m.d_grid);
+        (void)hipFree(m.d_frames);
+    }
+    for (auto &g : ms->geoms)
+        (void)hipFree(g.d_xy);
+    (void)hipFree(ms->d_logodds);
+    (void)hipFree(ms->d_l);
+    (void)hipFree(ms->d_r);
+    (void)hipFree(ms->d_c);
+    (void)hipFree(ms->d_counts);
+    for (auto &b : ms->buf)
+        (void)hipFree(b.p);
+    delete ms;
+}
+
+int sfe_mapset_geometry(sfe_mapset *ms, const float *sonar_xy, int img_rows, int img_cols, int *id_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, sonar_xy && id_out && img_rows > 0 && img_cols > 0 && (long long)img_rows * img_cols < (1 << 30));
+    if ((long long)img_rows * img_cols > ms->max_px)
+        return sfe_set_err(ctx, SFE_ERR_CAP, "map set: a %d x %d image, room for %d pixels per keyframe", img_rows, img_cols,
+                           ms->max_px);
+    MapGeom g;
+    g.img_rows = img_rows, g.img_cols = img_cols;
+    const size_t n = (size_t)img_rows * img_cols;
+    SFE_HIP(ctx, hipMalloc((void **)&g.d_xy, n * sizeof(float2)));
+    SFE_HIP(ctx, hipMemcpy(g.d_xy, sonar_xy, n * sizeof(float2), hipMemcpyHostToDevice));
+    ms->geoms.push_back(g);
+    *id_out = (int)ms->geoms.size() - 1;
+    return 0;
+}
+
+int sfe_mapset_set_logodds(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                           const float *logodds)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && slots && geoms && logodds)));
+    for (int b = 0; b < n; ++b)
+        if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+    size_t off = 0;
+    for (int b = 0; b < n; ++b) {
+        const MapGeom &g = ms->geoms[geoms[b]];
+        const size_t px = (size_t)g.img_rows * g.img_cols, idx = set_idx(ms, maps[b], slots[b]);
+        SFE_HIP(ctx, hipMemcpyAsync(set_logodds(ms, idx), logodds + off, sizeof(float) * px, hipMemcpyHostToDevice,
+                                    ctx->stream));
+        ms->slots[idx].geom = geoms[b];
+        off += px;
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                       const int32_t *hit_off, const int32_t *hits, const int32_t *hrhc, const int32_t *k_off,
+                       const float *ktab, int n_ktab, const double *div, float miss32, float logit_miss, float hit32,
+                       float logit_hit)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && slots && geoms && hit_off && hrhc && k_off && div)) && n_ktab >= 0);
+    if (n == 0)
+        return 0;
+    std::vector<MeasJob> jobs(n);
+    int64_t px = 0;
+    int max_px = 0, max_cols = 0;
+    for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+        const MapGeom &g = ms->geoms[geoms[b]];
+        MeasJob &j = jobs[b];
+        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
+        j.hit_off = hit_off[b];
+        j.n_hits = hit_off[b + 1] - hit_off[b];
+        j.hr = hrhc[2 * b], j.hc = hrhc[2 * b + 1];
+        j.k_off = k_off[b];
+        SFE_ARG(ctx, j.n_hits >= 0 && j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
+        if (j.hr < 0)
+            SFE_ARG(ctx, j.n_hits == 0);
+        else
+            SFE_ARG(ctx, j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab);
+        j.div = div[b];
+        j.px_off = px;
+        j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
+        px += j.slot_px;
+        max_px = max(max_px, j.slot_px);
+        max_cols = max(max_cols, j.img_cols);
+    }
+    const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
+    SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
+    MeasJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
+    int32_t *d_hits = set_upload(ms, 1, hits, 2 * (size_t)(n_hit_tot - 1));
+    float *d_k = set_upload(ms, 2, ktab, (size_t)n_ktab);
+    uint8_t *d_mask = (uint8_t *)buf_get(ctx, ms->buf[3], (size_t)px);
+    float *d_prob = (float *)buf_get(ctx, ms->buf[4], sizeof(float) * (size_t)px);
+    int32_t *d_fh = (int32_t *)buf_get(ctx, ms->buf[5], sizeof(int32_t) * (size_t)n * max_cols);
+    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set measurement scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
+    const unsigned ny = (unsigned)n;
+    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
+                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
+                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
+    for (int b = 0; b < n; ++b)
+        ms->slots[set_idx(ms, maps[b], slots[b])].geom = geoms[b];
+    ms->last_meas = jobs;
+    ms->last_meas_n = max_cols;
+    return 0;
+}
+
+int sfe_mapset_measure_stages(sfe_mapset *ms, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, b >= 0 && b < (int)ms->last_meas.size());
+    const MeasJob &j = ms->last_meas[b];
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (hits_out)
+        SFE_HIP(ctx, hipMemcpy(hits_out, (uint8_t *)ms->buf[3].p + j.px_off, (size_t)j.slot_px, hipMemcpyDeviceToHost));
+    if (prob_out)
+        SFE_HIP(ctx, hipMemcpy(prob_out, (float *)ms->buf[4].p + j.px_off, sizeof(float) * j.slot_px, hipMemcpyDeviceToHost));
+    if (first_hits_out)
+        SFE_HIP(ctx, hipMemcpy(first_hits_out, (int32_t *)ms->buf[5].p + (int64_t)b * ms->last_meas_n,
+                               sizeof(int32_t) * j.img_cols, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sfe_mapset_fit_bounds(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4,
+                          const double *origin2, double resolution, int32_t *mm_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && slots && pose4 && origin2 && mm_out)) && resolution > 0);
+    if (n == 0)
+        return 0;
+    SFE_ARG(ctx, n <= 65535);
+    std::vector<FitJob> jobs;
+    int max_px;
+    if (int rc = set_fit_jobs(ms, n, maps, slots, pose4, origin2, jobs, max_px))
+        return rc;
+    std::vector<int32_t> mm(4 * (size_t)n);
+    for (int b = 0; b < n; ++b)
+        mm[4 * b] = INT_MAX, mm[4 * b + 1] = INT_MIN, mm[4 * b + 2] = INT_MAX, mm[4 * b + 3] = INT_MIN;
+    FitJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
+    int32_t *d_mm = set_upload(ms, 1, mm.data(), mm.size());
+    if (!d_jobs || !d_mm)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set fit scratch allocation / upload failed");
+    const unsigned gx = (unsigned)min((max_px + MAP_THREADS - 1) / MAP_THREADS, 64);
+    hipLaunchKernelGGL(map_bounds_kernel, dim3(gx, (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution,
+                       d_mm);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipMemcpyAsync(mm_out, d_mm, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sfe_mapset_grow(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *grow4)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && grow4)));
+    for (int b = 0; b < n; ++b) {
+        const int32_t *g = grow4 + 4 * b;
+        SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps && g[0] >= 0 && g[1] >= 0 && g[2] >= 0 && g[3] >= 0);
+        for (int a = 0; a < b; ++a)
+            SFE_ARG(ctx, maps[a] != maps[b]);
+        const SetMap &m = ms->maps[maps[b]];
+        const long long nr = (long long)m.rows + g[0] + g[1], nc = (long long)m.cols + g[2] + g[3];
+        SFE_ARG(ctx, nr * nc < (1LL << 31) && nr <= 65536 && nc <= 65536);
+    }
+    std::vector<float *> old;
+    for (int b = 0; b < n; ++b) {
+        const int32_t *g = grow4 + 4 * b;
+        if (g[0] + g[1] + g[2] + g[3] == 0)
+            continue;
+        SetMap &m = ms->maps[maps[b]];
+        const int nr = m.rows + g[0] + g[1], nc = m.cols + g[2] + g[3];
+        float *d = nullptr;
+        if (int rc = set_grid_alloc(ms, &d, (size_t)nr * nc))
+            return rc;
+        const int64_t cells = (int64_t)m.rows * m.cols;
+        hipLaunchKernelGGL(map_pad_kernel, dim3((unsigned)((cells + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
+                           ctx->stream, m.d_grid, m.rows, m.cols, d, nc, g[0], g[2]);
+        SFE_LAUNCH_CHECK(ctx);
+        old.push_back(m.d_grid);
+        m.d_grid = d;
+        m.rows = nr, m.cols = nc;
+        m.grow_r += g[0], m.grow_c += g[2];
+    }
+    if (!old.empty()) {
+        SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // one for all the maps that grew
+        for (float *p : old)
+            (void)hipFree(p);
+    }
+    return 0;
+}
+
+int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4,
+                     const double *origin2, double resolution, const int32_t *mm, const int32_t *shift2, const uint8_t *dec)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && slots && pose4 && origin2 && mm && shift2 && dec)) && resolution > 0);
+    if (n == 0)
+        return 0;
+    SFE_ARG(ctx, n <= 65535);
+    std::vector<FitJob> jobs;
+    int max_px;
+    if (int rc = set_fit_jobs(ms, n, maps, slots, pose4, origin2, jobs, max_px))
+        return rc;
+    int64_t win = 0;
+    std::vector<uint8_t> seen(ms->slots.size(), 0);
+    for (int b = 0; b < n; ++b) {
+        FitJob &j = jobs[b];
+        const size_t idx = set_idx(ms, maps[b], slots[b]);
+        const SetSlot &s = ms->slots[idx];
+        const SetMap &m = ms->maps[maps[b]];
+        SFE_ARG(ctx, !seen[idx]); // one refit per slot and call: its other buffer takes the new list
+        seen[idx] = 1;
+        SFE_ARG(ctx, mm[4 * b] <= mm[4 * b + 1] && mm[4 * b + 2] <= mm[4 * b + 3]);
+        j.wr0 = mm[4 * b], j.wh = mm[4 * b + 1] - mm[4 * b] + 1;
+        j.wc0 = mm[4 * b + 2], j.ww = mm[4 * b + 3] - mm[4 * b + 2] + 1;
+        j.sr = shift2[2 * b], j.sc = shift2[2 * b + 1];
+        // every cell inside its map's grid as it stands now (the caller grew it first)
+        SFE_ARG(ctx, j.wr0 + j.sr >= 0 && j.wr0 + j.sr + j.wh <= m.rows && j.wc0 + j.sc >= 0 && j.wc0 + j.sc + j.ww <= m.cols);
+        SFE_ARG(ctx, (int64_t)j.wh * j.ww < (1LL << 30));
+        SFE_ARG(ctx, !dec[b] || s.has_cells);
+        j.win_off = win; // each keyframe's own window, back to back: the largest map sizes nothing
+        win += (int64_t)j.wh * j.ww;
+        const int nb = 1 - s.cur;
+        j.out_r = set_r(ms, idx, nb), j.out_c = set_c(ms, idx, nb), j.out_l = set_l(ms, idx, nb);
+        j.out_n = ms->d_counts + 2 * idx + nb;
+    }
+    SFE_ARG(ctx, win < (1LL << 40));
+    FitJob *d_jobs = set_stage(ms, 0, jobs);
+    int32_t *d_win = (int32_t *)buf_get(ctx, ms->buf[1], sizeof(int32_t) * (size_t)win);
+    if (!d_jobs || !d_win)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set fit scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d_win, EMPTY_SLOT, (size_t)win, ctx->stream));
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
+                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)n), dim3(COMPACT_THREADS), 0, ctx->stream, d_jobs, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    // the float32 history of every cell as the reference writes it, per map: for each of its keyframes in call order, dec
+    // then inc.  Maps do not share cells, so the i-th apply of every map goes into round i.
+    std::vector<std::vector<ApplyJob>> rounds;
+    std::vector<int> seq(ms->n_maps, 0);
+    for (int b = 0; b < n; ++b) {
+        const size_t idx = set_idx(ms, maps[b], slots[b]);
+        SetSlot &s = ms->slots[idx];
+        SetMap &m = ms->maps[maps[b]];
+        ApplyJob a;
+        a.grid = m.d_grid, a.rows = m.rows, a.cols = m.cols, a.n_px = jobs[b].n_px;
+        for (int pass = dec[b] ? 0 : 1; pass < 2; ++pass) {
+            const int o = pass ? 1 - s.cur : s.cur;
+            a.r = set_r(ms, idx, o), a.c = set_c(ms, idx, o), a.l = set_l(ms, idx, o);
+            a.n = ms->d_counts + 2 * idx + o;
+            a.dr = pass ? 0 : m.grow_r - s.base_r, a.dc = pass ? 0 : m.grow_c - s.base_c;
+            a.sub = pass ? 0 : 1;
+            const int round = seq[maps[b]]++;
+            if (round >= (int)rounds.size())
+                rounds.resize(round + 1);
+            rounds[round].push_back(a);
+        }
+        s.cur = 1 - s.cur;
+        s.has_cells = 1;
+        s.base_r = m.grow_r, s.base_c = m.grow_c;
+    }
+    return set_run_rounds(ms, 2, rounds);
+}
+
+int sfe_mapset_cells(sfe_mapset *ms, int map, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (int rc = set_slot_used(ms, map, slot))
+        return rc;
+    const size_t idx = set_idx(ms, map, slot);
+    const SetSlot &s = ms->slots[idx];
+    const SetMap &m = ms->maps[map];
+    SFE_ARG(ctx, s.has_cells && n_out);
+    int32_t n = 0;
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(&n, ms->d_counts + 2 * idx + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
+    *n_out = n;
+    if (n > cap)
+        return sfe_set_err(ctx, SFE_ERR_CAP, "map set cells: %d cells, room for %d", n, cap);
+    if (r_out)
+        SFE_HIP(ctx, hipMemcpy(r_out, set_r(ms, idx, s.cur), sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    if (c_out)
+        SFE_HIP(ctx, hipMemcpy(c_out, set_c(ms, idx, s.cur), sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    if (l_out)
+        SFE_HIP(ctx, hipMemcpy(l_out, set_l(ms, idx, s.cur), sizeof(float) * n, hipMemcpyDeviceToHost));
+    for (int i = 0; r_out && i < n; ++i)
+        r_out[i] = (uint16_t)(r_out[i] + (m.grow_r - s.base_r));
+    for (int i = 0; c_out && i < n; ++i)
+        c_out[i] = (uint16_t)(c_out[i] + (m.grow_c - s.base_c));
+    return 0;
+}
+
+int sfe_mapset_logodds(sfe_mapset *ms, int map, int slot, float *out, int cap)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (int rc = set_slot_used(ms, map, slot))
+        return rc;
+    const size_t idx = set_idx(ms, map, slot);
+    const MapGeom &g = ms->geoms[ms->slots[idx].geom];
+    SFE_ARG(ctx, out && cap >= g.img_rows * g.img_cols);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(out, set_logodds(ms, idx), sizeof(float) * g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sfe_mapset_shape(sfe_mapset *ms, int map, int32_t *rows_cols_grow4)
+{
+    if (!ms || !rows_cols_grow4 || map < 0 || map >= ms->n_maps)
+        return SFE_ERR_ARG;
+    const SetMap &m = ms->maps[map];
+    rows_cols_grow4[0] = m.rows, rows_cols_grow4[1] = m.cols;
+    rows_cols_grow4[2] = m.grow_r, rows_cols_grow4[3] = m.grow_c;
+    return 0;
+}
+
+int sfe_mapset_apply_launches(sfe_mapset *ms, long long *n_out)
+{
+    if (!ms || !n_out)
+        return SFE_ERR_ARG;
+    *n_out = ms->apply_launches;
+    return 0;
+}
+
+int sfe_mapset_read_grid(sfe_mapset *ms, int map, int which, float *out, long long cap)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, map >= 0 && map < ms->n_maps);
+    const SetMap &m = ms->maps[map];
+    const float *src = which ? m.d_frames : m.d_grid;
+    const long long n = which ? (long long)m.frames_rows * m.frames_cols : (long long)m.rows * m.cols;
+    SFE_ARG(ctx, out && src && cap >= n);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SFE_HIP(ctx, hipMemcpy(out, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int32_t *slot_off, const int32_t *slots)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n_maps >= 0 && (n_maps == 0 || (maps && slot_off)) && (n_maps == 0 || slot_off[0] == 0));
+    for (int b = 0; b < n_maps; ++b) {
+        SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps && slot_off[b + 1] >= slot_off[b]);
+        SFE_ARG(ctx, slot_off[b + 1] == slot_off[b] || slots);
+        for (int a = 0; a < b; ++a)
+            SFE_ARG(ctx, maps[a] != maps[b]);
+        for (int i = slot_off[b]; i < slot_off[b + 1]; ++i) {
+            if (int rc = set_slot_used(ms, maps[b], slots[i]))
+                return rc;
+            SFE_ARG(ctx, ms->slots[set_idx(ms, maps[b], slots[i])].has_cells);
+        }
+    }
+    std::vector<std::vector<ApplyJob>> rounds;
+    for (int b = 0; b < n_maps; ++b) {
+        SetMap &m = ms->maps[maps[b]];
+        if (m.frames_rows != m.rows || m.frames_cols != m.cols) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(m.d_frames);
+            m.d_frames = nullptr;
+            m.frames_rows = m.frames_cols = 0;
+            if (int rc = set_grid_alloc(ms, &m.d_frames, (size_t)m.rows * m.cols))
+                return rc;
+            m.frames_rows = m.rows, m.frames_cols = m.cols;
+        } else
+            SFE_HIP(ctx, hipMemsetAsync(m.d_frames, 0, sizeof(float) * (size_t)m.rows * m.cols, ctx->stream));
+        for (int i = slot_off[b]; i < slot_off[b + 1]; ++i) {
+            const size_t idx = set_idx(ms, maps[b], slots[i]);
+            const SetSlot &s = ms->slots[idx];
+            const MapGeom &g = ms->geoms[s.geom];
+            ApplyJob a;
+            a.grid = m.d_frames, a.rows = m.rows, a.cols = m.cols, a.n_px = g.img_rows * g.img_cols;
+            a.r = set_r(ms, idx, s.cur), a.c = set_c(ms, idx, s.cur), a.l = set_l(ms, idx, s.cur);
+            a.n = ms->d_counts + 2 * idx + s.cur;
+            a.dr = m.grow_r - s.base_r, a.dc = m.grow_c - s.base_c, a.sub = 0;
+            const int round = i - slot_off[b];
+            if (round >= (int)rounds.size())
+                rounds.resize(round + 1);
+            rounds[round].push_back(a);
+        }
+    }
+    return set_run_rounds(ms, 2, rounds);
+}
+
+int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *which, const int32_t *box4,
+                      const int32_t *out_hw, const double *inv, const int32_t *resize, const long long *out_off,
+                      int8_t *occ_out, long long total)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && total >= 0 && (n == 0 || (maps && which && box4 && out_hw && inv && resize && out_off)));
+    SFE_ARG(ctx, n <= 65535 && (total == 0 || occ_out));
+    std::vector<RenderJob> jobs;
+    int64_t max_out = 0;
+    for (int b = 0; b < n; ++b) {
+        SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps);
+        const SetMap &m = ms->maps[maps[b]];
+        RenderJob j;
+        j.grid = which[b] ? m.d_frames : m.d_grid;
+        SFE_ARG(ctx, j.grid && (!which[b] || (m.frames_rows == m.rows && m.frames_cols == m.cols)));
+        const int r0 = box4[4 * b], r1 = box4[4 * b + 1], c0 = box4[4 * b + 2], c1 = box4[4 * b + 3];
+        j.oh = out_hw[2 * b], j.ow = out_hw[2 * b + 1];
+        SFE_ARG(ctx, j.oh >= 0 && j.ow >= 0);
+        const int64_t cells = (int64_t)j.oh * j.ow;
+        if (cells == 0)
+            continue;
+        j.cols = m.cols, j.r0 = r0, j.c0 = c0, j.h = r1 - r0 + 1, j.w = c1 - c0 + 1;
+        j.resize = resize[b], j.inv = inv[b], j.out_off = out_off[b];
+        SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && j.h > 0 && j.w > 0 && r1 < m.rows && c1 < m.cols);
+        SFE_ARG(ctx, j.resize || (j.oh == j.h && j.ow == j.w));
+        SFE_ARG(ctx, !j.resize || j.inv > 0);
+        SFE_ARG(ctx, j.out_off >= 0 && j.out_off + cells <= total);
+        max_out = max(max_out, cells);
+        jobs.push_back(j);
+    }
+    if (jobs.empty())
+        return 0;
+    RenderJob *d_jobs = set_stage(ms, 0, jobs);
+    int8_t *d = (int8_t *)buf_get(ctx, ms->buf[1], (size_t)total);
+    if (!d_jobs || !d)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set render scratch allocation / upload failed");
+    const unsigned gx = (unsigned)std::min<int64_t>((max_out + MAP_THREADS - 1) / MAP_THREADS, 1 << 20);
+    hipLaunchKernelGGL(mapset_render_kernel, dim3(gx, (unsigned)jobs.size()), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d);
+    SFE_LAUNCH_CHECK(ctx);
+    // (bytes of `total` no job covers are whatever the scratch held: the offsets are the caller's)
+    SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,
+                            uint8_t *keep_out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n_clouds >= 0 && n_clouds <= 65535 && (n_clouds == 0 || off));
+    if (n_clouds == 0)
+        return 0;
+    int max_n = 0;
+    SFE_ARG(ctx, off[0] == 0);
+    for (int c = 0; c < n_clouds; ++c) {
+        SFE_ARG(ctx, off[c + 1] >= off[c]);
+        max_n = max(max_n, off[c + 1] - off[c]);
+    }
+    const int n = off[n_clouds];
+    if (n == 0)
+        return 0;
+    SFE_ARG(ctx, pts && keep_out);
+    float *d_pts = (float *)sfe_scratch(ctx, 0, sizeof(float) * 2 * (size_t)n);
+    uint8_t *d_keep = (uint8_t *)sfe_scratch(ctx, 2, (size_t)n);
+    int32_t *d_off = (int32_t *)sfe_scratch(ctx, 1, sizeof(int32_t) * ((size_t)n_clouds + 1));
+    if (!d_pts || !d_keep || !d_off)
+        return SFE_ERR_HIP;
+    SFE_HIP(ctx, hipMemcpyAsync(d_pts, pts, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_off, off, sizeof(int32_t) * ((size_t)n_clouds + 1), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(radius_count_many_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)n_clouds), dim3(256), 0,
+                       ctx->stream, (const float2 *)d_pts, d_off, (float)(radius * radius), min_points, d_keep);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipMemcpyAsync(keep_out, d_keep, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
 }

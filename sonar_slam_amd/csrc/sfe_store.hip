@@ -860,6 +860,37 @@ int sfe_cloud_store_read(sfe_ctx *ctx, sfe_cloud_store *s, int32_t handle, float
     return 0;
 }
 
+int sfe_cloud_store_read_many(sfe_ctx *ctx, sfe_cloud_store *s, const int32_t *handles, int n, float *out, long long cap,
+                              int32_t *counts_out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, s && s->ctx == ctx && n >= 0 && cap >= 0 && (n == 0 || (handles && counts_out)) && (cap == 0 || out));
+    if (n == 0)
+        return 0;
+    if (int rc = store_sync_meta(s))
+        return rc;
+    long long tot = 0;
+    for (int i = 0; i < n; ++i) {
+        SFE_ARG(ctx, handles[i] >= 0 && handles[i] < s->n_slots);
+        counts_out[i] = s->cnt[handles[i]];
+        tot += counts_out[i] > 0 ? counts_out[i] : 0;
+    }
+    if (tot > cap)
+        return sfe_set_err(ctx, SFE_ERR_CAP, "cloud store: %d clouds hold %lld points, the buffer holds %lld", n, tot, cap);
+    long long at = 0;
+    for (int i = 0; i < n; ++i) {
+        const int c = counts_out[i];
+        if (c <= 0)
+            continue;
+        SFE_HIP(ctx, hipMemcpyAsync(out + 2 * at, s->d_pool + s->off[handles[i]], sizeof(float2) * (size_t)c,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+        at += c;
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
 int sfe_cloud_store_truncate(sfe_ctx *ctx, sfe_cloud_store *s, int32_t n_slots)
 {
     if (int rc = sfe_use(ctx))

@@ -11,6 +11,7 @@ Extensions: ``update_poses(keys, poses)`` (the loop of update_pose calls, batche
 ``add_keyframe_logodds(key, pose, ping, logodds)`` (a ready polar log-odds image instead of points).  Refused:
 method 2 (``get_occupancy_grid2``) and the intensity grid.  INTEGRATION.md lists the deviations.
 """
+import contextlib
 import ctypes as C
 import math
 import types
@@ -98,13 +99,7 @@ class Submap(object):
 
     def _cells(self):
         m = self._m
-        n = int(np.prod(m._geom_shape[self.geom]))
-        r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
-        got = C.c_int(0)
-        m._check(m._lib.sfe_map_cells(m._h, self._slot, r.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                      c.ctypes.data_as(C.POINTER(C.c_uint16)), _L.ptr(l, C.c_float), n, C.byref(got)))
-        k = got.value
-        return r[:k].copy(), c[:k].copy(), l[:k].copy()
+        return m._read_cells(self._slot, int(np.prod(m._geom_shape[self.geom])))
 
     @property
     def r(self):
@@ -121,10 +116,7 @@ class Submap(object):
     @property
     def logodds(self):
         m = self._m
-        n = int(np.prod(m._geom_shape[self.geom]))
-        out = np.zeros(n, np.float32)
-        m._check(m._lib.sfe_map_logodds(m._h, self._slot, _L.ptr(out, C.c_float), n))
-        return out
+        return m._read_logodds(self._slot, int(np.prod(m._geom_shape[self.geom])))
 
     def cell_box(self):
         """(rmin, rmax, cmin, cmax) of its cells in the grid's current coordinates"""
@@ -180,7 +172,7 @@ class Mapping(object):
 
         self._h = None
         self._geom = -1               # geometry of the next keyframe
-        self._geom_shape = []
+        self._geom_shape = {}         # geometry id -> image shape
         self._grow = [0, 0]           # rows grown on top, columns grown on the left (sfe_map_shape)
 
     # ---- configuration ---------------------------------------------------------------------------------------------
@@ -209,6 +201,16 @@ class Mapping(object):
         self.configure()
 
     def configure(self):
+        self._configure_host()
+        self.close()
+        if self.ctx is None:
+            self.ctx = _L.default_context()
+        self._lib = self.ctx.lib
+        h = C.c_void_p()
+        self._check(self._lib.sfe_map_create(self.ctx.handle, self.rows, self.cols, C.byref(h)))
+        self._h = h
+
+    def _configure_host(self):
         if self.pub_intensity:
             raise NotImplementedError("Mapping.configure: pub_intensity=True (the intensity grid) is not implemented")
         self.hit_logodds = logit(self.hit_prob)
@@ -225,16 +227,9 @@ class Mapping(object):
         self.cmin = xs.shape[0] - 1
         self.inc_r = int(self.inc / self.resolution)
         self.inc_c = int(self.inc / self.resolution)
-        self.close()
-        if self.ctx is None:
-            self.ctx = _L.default_context()
-        self._lib = self.ctx.lib
-        h = C.c_void_p()
-        self._check(self._lib.sfe_map_create(self.ctx.handle, self.rows, self.cols, C.byref(h)))
-        self._h = h
         self._grow = [0, 0]
         self._geom = -1
-        self._geom_shape = []
+        self._geom_shape = {}
         self.keyframes = []
         self.oculus = _Oculus()
 
@@ -252,6 +247,29 @@ class Mapping(object):
     def _check(self, rc):
         return self.ctx._check(rc)
 
+    # ---- the device calls of one map (MapBatch's per-session views answer these from the shared map set) -------------
+    def _new_slot(self):
+        # the slot of a keyframe is its index in self.keyframes (missed keys leave their slot unused)
+        return len(self.keyframes)
+
+    def _register_geometry(self, sonar_xy, shape):
+        gid = C.c_int(0)
+        self._check(self._lib.sfe_map_geometry(self._h, _L.ptr(sonar_xy, C.c_float), shape[0], shape[1], C.byref(gid)))
+        return gid.value
+
+    def _read_cells(self, slot, n):
+        r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
+        got = C.c_int(0)
+        self._check(self._lib.sfe_map_cells(self._h, slot, r.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                            c.ctypes.data_as(C.POINTER(C.c_uint16)), _L.ptr(l, C.c_float), n, C.byref(got)))
+        k = got.value
+        return r[:k].copy(), c[:k].copy(), l[:k].copy()
+
+    def _read_logodds(self, slot, n):
+        out = np.zeros(n, np.float32)
+        self._check(self._lib.sfe_map_logodds(self._h, slot, _L.ptr(out, C.c_float), n))
+        return out
+
     # ---- the reference's methods -----------------------------------------------------------------------------------
     def pose_changed(self, pose, new_pose):
         dp = pose.between(new_pose)
@@ -260,7 +278,7 @@ class Mapping(object):
         return dt > self.min_translation or dr > self.min_rotation
 
     def _new_keyframe(self, pose, ping):
-        kf = Submap(self, len(self.keyframes))
+        kf = Submap(self, self._new_slot())
         kf.k = len(self.keyframes)
         kf.pose = pose
         if self.oculus.configure(ping):
@@ -272,13 +290,9 @@ class Mapping(object):
             X, Y = np.cos(B) * R, np.sin(B) * R
             kf.sonar_xy = np.ascontiguousarray(np.c_[X.ravel(), Y.ravel()].astype(np.float32))
             self.oculus_image_size = X.shape
-            gid = C.c_int(0)
-            self._check(self._lib.sfe_map_geometry(self._h, _L.ptr(kf.sonar_xy, C.c_float), X.shape[0], X.shape[1],
-                                                    C.byref(gid)))
-            self._geom = gid.value
-            self._geom_shape.append(X.shape)
+            self._geom = self._register_geometry(kf.sonar_xy, X.shape)
+            self._geom_shape[self._geom] = X.shape
         kf.geom = self._geom
-        # the slot of a keyframe is its index in self.keyframes (missed keys leave their slot unused)
         return kf
 
     def _hits(self, points):
@@ -288,6 +302,10 @@ class Mapping(object):
         if self.outlier_filter_min_points > 1:
             points = pcl.remove_outlier(points[:, :2], self.outlier_filter_radius, self.outlier_filter_min_points,
                                         ctx=self.ctx)
+        return self._hit_indices(points)
+
+    def _hit_indices(self, points):
+        """the hits of filtered points: elementwise in the points, so many clouds of one geometry may go through at once"""
         o = self.oculus
         c = o.b2c(np.arctan2(points[:, 1], points[:, 0]))
         c = np.clip(np.int32(np.round(c)), 0, o.num_bearings - 1)
@@ -298,14 +316,18 @@ class Mapping(object):
         hits = np.c_[r // self.oculus_r_skip, c // self.oculus_c_skip].astype(np.int32)
         return hits, hr, hc
 
-    def _measure(self, slot, geom, hits, hr, hc):
+    def _measure_args(self, hits, hr, hc):
+        """-> (hits int32 [n x 2], the float32 kernel table, div) of one keyframe's measurement"""
         if hr >= 0:
             kernel = gaussian_kernel(2 * hr + 1).dot(gaussian_kernel(2 * hc + 1).T)
             ktab = np.ascontiguousarray(kernel.astype(np.float32).ravel())
             div = kernel[hr, hc] / self.hit_prob
         else:
             hits, ktab, div = np.zeros((0, 2), np.int32), np.zeros(1, np.float32), 1.0
-        hits = np.ascontiguousarray(hits, np.int32)
+        return np.ascontiguousarray(hits, np.int32), ktab, div
+
+    def _measure(self, slot, geom, hits, hr, hc):
+        hits, ktab, div = self._measure_args(hits, hr, hc)
         hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
         arr = lambda v, t: np.ascontiguousarray(np.array(v, t))
         self._check(self._lib.sfe_map_measure(
@@ -373,20 +395,11 @@ class Mapping(object):
         if group:
             self._fit(group, dec=True)
 
-    def _fit(self, group, dec):
-        """fit_grid + adjust_bounds + dec_grid / inc_grid of `group` in order (mapping.py:466-582)"""
-        n = len(group)
-        slots = np.array([kf._slot for kf in group], np.int32)
-        pose4 = np.zeros((n, 4), np.float64)
-        for i, kf in enumerate(group):
-            yaw = kf.pose.theta()
-            pose4[i] = np.cos(yaw), np.sin(yaw), kf.pose.x(), kf.pose.y()
-        origin = np.zeros((n, 2), np.float64)
-        origin[:] = self.y0, self.x0
-        mm = self._bounds(slots, pose4, origin)
-        shift = np.zeros((n, 2), np.int64)
-        grow = [0, 0, 0, 0]       # top, bottom, left, right (cells)
-        for i in range(n):
+    def _adjust(self, mm, shift, grow, origin, start):
+        """adjust_bounds and inc_grid's box for keyframes start.. of a fit group, from their bounds `mm`; fills shift / grow.
+        -> the index of the first keyframe whose bounds must be taken again (the origin moved: origin[i:] is updated), or n"""
+        n = len(mm)
+        for i in range(start, n):
             r0, r1, c0, c1 = (int(v) for v in mm[i])
             top = left = 0
             # adjust_bounds: while the cells leave the grid, grow by inc on that side
@@ -426,9 +439,28 @@ class Mapping(object):
             self.rmin, self.rmax = min(self.rmin, r0), max(self.rmax, r1)
             self.cmin, self.cmax = min(self.cmin, c0), max(self.cmax, c1)
             if (top or left) and i + 1 < n:
-                # the keyframes after this one are fitted at the new origin
                 origin[i + 1:] = self.y0, self.x0
-                mm[i + 1:] = self._bounds(slots[i + 1:], pose4[i + 1:], origin[i + 1:])
+                return i + 1
+        return n
+
+    def _fit(self, group, dec):
+        """fit_grid + adjust_bounds + dec_grid / inc_grid of `group` in order (mapping.py:466-582)"""
+        n = len(group)
+        slots = np.array([kf._slot for kf in group], np.int32)
+        pose4 = np.zeros((n, 4), np.float64)
+        for i, kf in enumerate(group):
+            yaw = kf.pose.theta()
+            pose4[i] = np.cos(yaw), np.sin(yaw), kf.pose.x(), kf.pose.y()
+        origin = np.zeros((n, 2), np.float64)
+        origin[:] = self.y0, self.x0
+        mm = self._bounds(slots, pose4, origin)
+        shift = np.zeros((n, 2), np.int64)
+        grow = [0, 0, 0, 0]       # top, bottom, left, right (cells)
+        i = self._adjust(mm, shift, grow, origin, 0)
+        while i < n:
+            # the keyframes after a growth that moved the origin are fitted at the new origin
+            mm[i:] = self._bounds(slots[i:], pose4[i:], origin[i:])
+            i = self._adjust(mm, shift, grow, origin, i)
         self._check(self._lib.sfe_map_grow(self._h, grow[0], grow[1], grow[2], grow[3]))
         self._grow[0] += grow[0]
         self._grow[1] += grow[2]
@@ -438,6 +470,9 @@ class Mapping(object):
         self._check(self._lib.sfe_map_refit(self._h, n, _L.ptr(slots, C.c_int32), _L.ptr(pose4, C.c_double),
                                             _L.ptr(origin, C.c_double), float(self.resolution), _L.ptr(mm32, C.c_int32),
                                             _L.ptr(shift32, C.c_int32), _L.ptr(decs, C.c_uint8)))
+        self._fitted(group, mm, shift)
+
+    def _fitted(self, group, mm, shift):
         for i, kf in enumerate(group):
             r0, r1, c0, c1 = (int(v) for v in mm[i])
             sr, sc = int(shift[i, 0]), int(shift[i, 1])
@@ -483,10 +518,9 @@ class Mapping(object):
         elif self.pub_occupancy2:
             return self.get_occupancy_grid2(frames, resolution)
 
-    def get_occupancy_grid1(self, frames=None, resolution=None):
-        occ_msg = OccupancyGrid()
-        occ_msg.header.frame_id = "map"
-        which = 0
+    def _render_plan(self, frames, resolution):
+        """-> (which, slots of `frames`, (rmin, rmax, cmin, cmax), (oh, ow), inv, resize, resolution)"""
+        which, slots = 0, None
         if frames is None:
             rmin, rmax, cmin, cmax = self.rmin, self.rmax, self.cmin, self.cmax
         else:
@@ -502,7 +536,6 @@ class Mapping(object):
                 rmin, rmax = min(rmin, r0), max(rmax, r1)
                 cmin, cmax = min(cmin, c0), max(cmax, c1)
             slots = np.array(slots, np.int32)
-            self._check(self._lib.sfe_map_frames(self._h, len(slots), _L.ptr(slots, C.c_int32)))
         h, w = max(0, rmax - rmin + 1), max(0, cmax - cmin + 1)
         resize = 0
         inv = 1.0
@@ -516,10 +549,12 @@ class Mapping(object):
         else:
             oh, ow = h, w
             resolution = self.resolution
-        occ = np.zeros((oh, ow), np.int8)
-        if oh * ow:
-            self._check(self._lib.sfe_map_render(self._h, which, int(rmin), int(rmax), int(cmin), int(cmax), oh, ow,
-                                                 float(inv), resize, occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return which, slots, (int(rmin), int(rmax), int(cmin), int(cmax)), (oh, ow), float(inv), resize, resolution
+
+    def _grid_msg(self, box, resolution, occ):
+        rmin, cmin = box[0], box[2]
+        occ_msg = OccupancyGrid()
+        occ_msg.header.frame_id = "map"
         occ_msg.info.origin.position.x = self.x0 + cmin * resolution
         occ_msg.info.origin.position.y = self.y0 + rmin * resolution
         occ_msg.info.origin.orientation.x = 0
@@ -532,3 +567,500 @@ class Mapping(object):
         occ_msg.data = list(occ.ravel())
         occ_msg.occ = occ
         return occ_msg
+
+    def get_occupancy_grid1(self, frames=None, resolution=None):
+        which, slots, box, (oh, ow), inv, resize, resolution = self._render_plan(frames, resolution)
+        if which:
+            self._check(self._lib.sfe_map_frames(self._h, len(slots), _L.ptr(slots, C.c_int32)))
+        occ = np.zeros((oh, ow), np.int8)
+        if oh * ow:
+            self._check(self._lib.sfe_map_render(self._h, which, box[0], box[1], box[2], box[3], oh, ow, inv, resize,
+                                                 occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return self._grid_msg(box, resolution, occ)
+
+
+# ---- S maps in lock-step ---------------------------------------------------------------------------------------------
+SETTINGS = ("x0", "y0", "width", "height", "inc", "resolution", "pub_intensity", "pub_occupancy1", "hit_prob", "miss_prob",
+            "inflation_angle", "inflation_range", "pub_occupancy2", "inflation_radius", "outlier_filter_radius",
+            "outlier_filter_min_points", "min_translation", "min_rotation")
+
+
+def plan_updates(keyframes, pose_changed, sessions, keys, poses):
+    """Mapping.update_poses' rules for flat (session, key, pose) lists -> waves of fit groups.
+
+    ``keyframes[s]`` is session s's keyframe list (None for a missed key), ``pose_changed[s](old, new)`` its gate.  Per
+    session, in list order: a missed key and an unchanged pose drop out; an accepted keyframe takes its new pose at once (so a
+    later entry for the same key is gated against it); a keyframe listed again closes the session's open group, because a slot
+    is refitted at most once per device call.  -> [wave][(session, [(keyframe, pose) in order])]: wave w holds the w-th group of
+    every session that has one, sessions in order of first appearance; a group is fitted at the poses listed in it (a keyframe
+    listed again has moved on by the time its first group is fitted)."""
+    if not (len(sessions) == len(keys) == len(poses)):
+        raise ValueError("update_poses: %d sessions, %d keys, %d poses" % (len(sessions), len(keys), len(poses)))
+    groups, order = {}, []
+    for s, key, new_pose in zip(sessions, keys, poses):
+        s = int(s)
+        kfs = keyframes[s]
+        assert key < len(kfs)
+        kf = kfs[key]
+        if not kf:
+            continue
+        if not pose_changed[s](kf.pose, new_pose):
+            continue
+        if s not in groups:
+            groups[s] = [[]]
+            order.append(s)
+        if any(kf is g for g, _ in groups[s][-1]):
+            groups[s].append([])
+        kf.pose = new_pose
+        groups[s][-1].append((kf, new_pose))
+    waves = []
+    for s in order:
+        for w, g in enumerate(groups[s]):
+            while len(waves) <= w:
+                waves.append([])
+            waves[w].append((s, g))
+    return waves
+
+
+class _SessionMap(Mapping):
+    """``MapBatch.maps[s]``: Mapping's attributes and read surface for one session of a MapBatch.  Its state on the device
+    lives in the batch's map set; its own add_keyframe / update_poses calls are batch calls for this one session."""
+
+    def __init__(self, batch, s):
+        Mapping.__init__(self, batch.ctx)
+        self._b, self._s = batch, s
+        self._n_slots = 0
+        self._hit_key = None
+        self._meas_job = -1
+
+    def configure(self):
+        raise RuntimeError("a MapBatch session is configured through MapBatch.configure")
+
+    def load_yaml(self, path):
+        raise RuntimeError("a MapBatch session is configured through MapBatch.load_yaml")
+
+    def close(self):
+        pass
+
+    def _check(self, rc):
+        return self._b.ctx._check(rc)
+
+    def _geometry_state(self):
+        return (dict(vars(self.oculus)), self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom,
+                self._hit_key, dict(self._geom_shape))
+
+    def _restore_geometry(self, state):
+        ocu, self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom, self._hit_key, shapes = state
+        vars(self.oculus).clear()
+        vars(self.oculus).update(ocu)
+        self._geom_shape = shapes
+
+    def _new_slot(self):
+        return self._n_slots        # slots are handed out densely: max_keyframes counts keyframes, not keys
+
+    def _register_geometry(self, sonar_xy, shape):
+        o = self.oculus
+        self._hit_key = (o.num_ranges, o.range_resolution, o.bearings.tobytes(), int(self.oculus_r_skip),
+                         int(self.oculus_c_skip))
+        return self._b._geometry(sonar_xy, shape)
+
+    def _read_cells(self, slot, n):
+        b = self._b
+        r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
+        got = C.c_int(0)
+        self._check(b._lib.sfe_mapset_cells(b._h, self._s, slot, r.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                            c.ctypes.data_as(C.POINTER(C.c_uint16)), _L.ptr(l, C.c_float), n, C.byref(got)))
+        k = got.value
+        return r[:k].copy(), c[:k].copy(), l[:k].copy()
+
+    def _read_logodds(self, slot, n):
+        b = self._b
+        out = np.zeros(n, np.float32)
+        self._check(b._lib.sfe_mapset_logodds(b._h, self._s, slot, _L.ptr(out, C.c_float), n))
+        return out
+
+    def _read_grid(self, which):
+        b = self._b
+        out = np.zeros((self.rows, self.cols), np.float32)
+        self._check(b._lib.sfe_mapset_read_grid(b._h, self._s, which, _L.ptr(out, C.c_float), out.size))
+        return out
+
+    @property
+    def logodds_grid(self):
+        return self._read_grid(0)
+
+    def frames_grid(self):
+        return self._read_grid(1)
+
+    def device_shape(self):
+        """(rows, cols, rows grown on top, columns grown on the left) as the device holds them"""
+        out = np.zeros(4, np.int32)
+        self._check(self._b._lib.sfe_mapset_shape(self._b._h, self._s, _L.ptr(out, C.c_int32)))
+        return tuple(int(v) for v in out)
+
+    def measure_stages(self):
+        b = self._b
+        if self._meas_job < 0:
+            raise RuntimeError("measure_stages: session %d took no part in the batch's last add_keyframes call" % self._s)
+        shape = self.oculus_image_size
+        hits, prob, fh = np.zeros(shape, np.uint8), np.zeros(shape, np.float32), np.zeros(shape[1], np.int32)
+        self._check(b._lib.sfe_mapset_measure_stages(b._h, self._meas_job, _L.ptr(hits, C.c_uint8), _L.ptr(prob, C.c_float),
+                                                     _L.ptr(fh, C.c_int32)))
+        return hits, prob, fh
+
+    def add_keyframe(self, key, pose, ping, points):
+        self._b.add_keyframes([self._s], [key], [pose], ping, [points])
+
+    def add_keyframe_logodds(self, key, pose, ping, logodds):
+        self._b.add_keyframes_logodds([self._s], [key], [pose], ping, [logodds])
+
+    def update_poses(self, keys, poses):
+        self._b.update_poses([self._s] * len(keys), keys, poses)
+
+    def get_occupancy_grid1(self, frames=None, resolution=None):
+        return self._b._render([self._s], frames, resolution)[0]
+
+
+class MapBatch(object):
+    """S occupancy maps that advance together: every stage of Mapping as one device call over the listed sessions
+    (csrc/sfe_map.hip: sfe_mapset).  ``maps[s]`` is, bit for bit, the Mapping that was given session s's calls.
+
+    The settings are Mapping's attributes (keyword arguments, or set afterwards; then ``configure()`` or ``load_yaml()``, as
+    with Mapping).  The device arena is sized here and never grows: ``max_keyframes`` keyframes per session of up to
+    ``max_pixels`` polar pixels each (the default holds a 1024 x 512 ping at the shipped skips), 20 bytes per pixel; one
+    keyframe more, or a larger image, raises."""
+
+    def __init__(self, ctx=None, n_sessions=1, max_keyframes=256, max_pixels=1 << 17, **settings):
+        if int(n_sessions) < 1 or int(max_keyframes) < 1 or int(max_pixels) < 1:
+            raise ValueError("MapBatch: n_sessions, max_keyframes and max_pixels must be positive, got %r, %r, %r"
+                             % (n_sessions, max_keyframes, max_pixels))
+        self.ctx, self.S = ctx, int(n_sessions)
+        self.max_keyframes, self.max_pixels = int(max_keyframes), int(max_pixels)
+        proto = Mapping()
+        for name in SETTINGS:
+            setattr(self, name, getattr(proto, name))
+        for name, v in settings.items():
+            if name not in SETTINGS:
+                raise TypeError("MapBatch: unknown setting %r (Mapping's settings: %s)" % (name, ", ".join(SETTINGS)))
+            setattr(self, name, v)
+        self.maps = []
+        self._h = None
+        self.last_apply_rounds = 0      # apply launches of the last add / update_poses call, as the device counted them
+
+    load_yaml = Mapping.load_yaml
+
+    def configure(self):
+        if self.pub_intensity:
+            raise NotImplementedError("MapBatch.configure: pub_intensity=True (the intensity grid) is not implemented")
+        self.close()
+        maps = []
+        for s in range(self.S):
+            v = _SessionMap(self, s)
+            for name in SETTINGS:
+                setattr(v, name, getattr(self, name))
+            v._configure_host()
+            maps.append(v)
+        if self.ctx is None:
+            self.ctx = _L.default_context()
+            for v in maps:
+                v.ctx = self.ctx
+        self._lib = self.ctx.lib
+        h = C.c_void_p()
+        self.ctx._check(self._lib.sfe_mapset_create(self.ctx.handle, self.S, maps[0].rows, maps[0].cols, self.max_keyframes,
+                                                    self.max_pixels, C.byref(h)))
+        self._h = h
+        self.maps = maps
+        self._geoms = {}
+
+    reset = configure
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._lib.sfe_mapset_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def get_intensity_grid(self):
+        raise NotImplementedError("MapBatch.get_intensity_grid: the intensity grid is not implemented")
+
+    def get_occupancy_grid2(self, *args, **kw):
+        raise NotImplementedError("MapBatch.get_occupancy_grid2: method 2 (point projection + dilation) is not implemented")
+
+    # ---- helpers -----------------------------------------------------------------------------------------------------
+    def _check(self, rc):
+        return self.ctx._check(rc)
+
+    def _geometry(self, sonar_xy, shape):
+        """equal sonar_xy tables are stored once"""
+        import hashlib
+        key = (tuple(shape), hashlib.sha256(sonar_xy.tobytes()).digest())
+        if key not in self._geoms:
+            gid = C.c_int(0)
+            self._check(self._lib.sfe_mapset_geometry(self._h, _L.ptr(sonar_xy, C.c_float), shape[0], shape[1], C.byref(gid)))
+            self._geoms[key] = gid.value
+        return self._geoms[key]
+
+    def _listed(self, what, sessions, *per_session):
+        if self._h is None:
+            raise RuntimeError("MapBatch.%s: configure() first" % what)
+        sessions = [int(s) for s in sessions]
+        for a in per_session:
+            if len(a) != len(sessions):
+                raise ValueError("MapBatch.%s: %d sessions but a list of %d" % (what, len(sessions), len(a)))
+        if len(set(sessions)) != len(sessions):
+            raise ValueError("MapBatch.%s: a session is listed twice" % what)
+        for s in sessions:
+            if not 0 <= s < self.S:
+                raise IndexError("MapBatch.%s: session %d of %d" % (what, s, self.S))
+        return sessions
+
+    def _begin(self, what, sessions, keys, poses, pings, data):
+        """the checks of an add call, before anything changes -> (sessions, pings, new keyframes)"""
+        sessions = self._listed(what, sessions, keys, poses, data)
+        if isinstance(pings, (list, tuple)):
+            if len(pings) != len(sessions):
+                raise ValueError("MapBatch.%s: %d sessions but %d pings" % (what, len(sessions), len(pings)))
+        else:
+            pings = [pings] * len(sessions)
+        for s in sessions:
+            self.maps[s]._check_supported()
+            if self.maps[s]._n_slots >= self.max_keyframes:
+                raise _L.SonarFEError("MapBatch.%s: session %d already holds max_keyframes = %d keyframes"
+                                      % (what, s, self.max_keyframes))
+        return sessions, pings
+
+    @contextlib.contextmanager
+    def _geometry_guard(self, sessions):
+        """a refused add leaves the listed sessions' geometry state (sonar settings, skips, image size, geometry id) as it
+        found it: _new_keyframe takes a ping's geometry before the device can refuse the image or the slot"""
+        keep = [(self.maps[s], self.maps[s]._geometry_state()) for s in sessions]
+        try:
+            yield
+        except BaseException:
+            for v, state in keep:
+                v._restore_geometry(state)
+            raise
+
+    def _end(self, sessions, keys, kfs):
+        before = self._apply_launches()
+        self._fit_many([(s, [(kf, kf.pose)]) for s, kf in zip(sessions, kfs)], dec=False)
+        self.last_apply_rounds = self._apply_launches() - before
+        for s, key, kf in zip(sessions, keys, kfs):
+            v = self.maps[s]
+            v._append(key, kf)
+            v._n_slots += 1
+
+    # ---- the stages --------------------------------------------------------------------------------------------------
+    def add_keyframes(self, sessions, keys, poses, pings, points):
+        """Mapping.add_keyframe for each listed session: ``pings`` one ping for all or one per session, ``points[i]`` the
+        cloud of ``sessions[i]``"""
+        sessions, pings = self._begin("add_keyframes", sessions, keys, poses, pings, points)
+        with self._geometry_guard(sessions):
+            kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            self._measure_many(sessions, kfs, points)
+        for v in self.maps:
+            v._meas_job = -1
+        for j, (s, p) in enumerate(zip(sessions, points)):
+            self.maps[s]._meas_job = j
+            if self.pub_occupancy2:
+                self.maps[s].point_cloud = p
+        self._end(sessions, keys, kfs)
+
+    def _measure_many(self, sessions, kfs, points):
+        clouds = [np.asarray(p) if len(p) else p for p in points]
+        hits = self._hits_many(sessions, clouds)
+        hit_off, hrhc, k_off, div, ktabs, ktab_at, n_k = [0], [], [], [], [], {}, 0
+        all_hits = []
+        for s, (h, hr, hc) in zip(sessions, hits):
+            v = self.maps[s]
+            h, ktab, d = v._measure_args(h, hr, hc)
+            if (hr, hc) not in ktab_at:
+                ktab_at[(hr, hc)] = n_k
+                ktabs.append(ktab)
+                n_k += len(ktab)
+            all_hits.append(h.reshape(-1, 2))
+            hit_off.append(hit_off[-1] + len(h))
+            hrhc.append((hr, hc))
+            k_off.append(ktab_at[(hr, hc)])
+            div.append(d)
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
+        hits_all = np.ascontiguousarray(np.concatenate(all_hits), np.int32) if hit_off[-1] else i32([0, 0])
+        ktab = np.ascontiguousarray(np.concatenate(ktabs), np.float32)
+        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
+        self._check(self._lib.sfe_mapset_measure(
+            self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
+            _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(i32(hit_off), C.c_int32), _L.ptr(hits_all, C.c_int32),
+            _L.ptr(i32(hrhc), C.c_int32), _L.ptr(i32(k_off), C.c_int32), _L.ptr(ktab, C.c_float), len(ktab),
+            _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
+            float(hit32), float(logit(hit32))))
+
+    def add_keyframes_logodds(self, sessions, keys, poses, pings, logodds):
+        """Mapping.add_keyframe_logodds for each listed session"""
+        sessions, pings = self._begin("add_keyframes_logodds", sessions, keys, poses, pings, logodds)
+        with self._geometry_guard(sessions):
+            kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            los = []
+            for s, lo in zip(sessions, logodds):
+                lo = np.ascontiguousarray(lo, np.float32).ravel()
+                size = self.maps[s].oculus_image_size
+                if lo.size != int(np.prod(size)):
+                    raise ValueError("add_keyframes_logodds: %d values for session %d's %r image" % (lo.size, s, size))
+                los.append(lo)
+            i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
+            self._check(self._lib.sfe_mapset_set_logodds(
+                self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
+                _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(np.ascontiguousarray(np.concatenate(los)), C.c_float)))
+        self._end(sessions, keys, kfs)
+
+    def _hits_many(self, sessions, clouds):
+        """Mapping._hits for every listed session: the outlier filter of all clouds in one device call, then the hit indices
+        (elementwise in the points) once per group of sessions that share a sonar geometry -> [(hits, hr, hc)]"""
+        out = [None] * len(sessions)
+        live = [i for i, c in enumerate(clouds) if len(c)]
+        for i in range(len(sessions)):
+            if i not in live:
+                out[i] = (None, -1, 0)
+        pts = {i: clouds[i] for i in live}
+        if live and self.outlier_filter_min_points > 1:
+            pts = {i: pcl._cloud(clouds[i][:, :2], "add_keyframes(points)") for i in live}
+            off = np.zeros(len(live) + 1, np.int32)
+            off[1:] = np.cumsum([len(pts[i]) for i in live])
+            cat = np.ascontiguousarray(np.concatenate([pts[i] for i in live]))
+            keep = np.zeros(len(cat), np.uint8)
+            with self.ctx.lock:        # the context's shared scratch, as pcl.remove_outlier
+                self._check(self._lib.sfe_remove_outlier_many(
+                    self.ctx.handle, _L.ptr(cat, C.c_float), _L.ptr(off, C.c_int32), len(live),
+                    float(self.outlier_filter_radius), int(self.outlier_filter_min_points), _L.ptr(keep, C.c_uint8)))
+            keep = keep.astype(bool)
+            pts = {i: cat[off[j]:off[j + 1]][keep[off[j]:off[j + 1]]] for j, i in enumerate(live)}
+        groups = {}
+        for i in live:
+            groups.setdefault((self.maps[sessions[i]]._hit_key, pts[i].dtype.str, pts[i].shape[1]), []).append(i)
+        for idx in groups.values():
+            v = self.maps[sessions[idx[0]]]
+            hits, hr, hc = v._hit_indices(np.concatenate([pts[i] for i in idx]) if len(idx) > 1 else pts[idx[0]])
+            at = 0
+            for i in idx:
+                out[i] = (hits[at:at + len(pts[i])], hr, hc)
+                at += len(pts[i])
+        return out
+
+    def update_poses(self, sessions, keys, poses):
+        """for s, k, p in zip(sessions, keys, poses): maps[s].update_pose(k, p) -- the same bits; the fits of all sessions in
+        one pass, their ordered applies in rounds"""
+        if self._h is None:
+            raise RuntimeError("MapBatch.update_poses: configure() first")
+        for s in sessions:
+            if not 0 <= int(s) < self.S:
+                raise IndexError("MapBatch.update_poses: session %d of %d" % (s, self.S))
+        waves = plan_updates([v.keyframes for v in self.maps], [v.pose_changed for v in self.maps], sessions, keys, poses)
+        before = self._apply_launches()
+        for wave in waves:
+            self._fit_many(wave, dec=True)
+        self.last_apply_rounds = self._apply_launches() - before
+
+    def _bounds(self, maps, slots, pose4, origin):
+        n = len(slots)
+        mm = np.zeros((n, 4), np.int32)
+        self._check(self._lib.sfe_mapset_fit_bounds(self._h, n, _L.ptr(np.ascontiguousarray(maps), C.c_int32),
+                                                    _L.ptr(np.ascontiguousarray(slots), C.c_int32),
+                                                    _L.ptr(np.ascontiguousarray(pose4), C.c_double),
+                                                    _L.ptr(np.ascontiguousarray(origin), C.c_double), float(self.resolution),
+                                                    _L.ptr(mm, C.c_int32)))
+        return mm.astype(np.int64)
+
+    def _apply_launches(self):
+        n = C.c_longlong(0)
+        self._check(self._lib.sfe_mapset_apply_launches(self._h, C.byref(n)))
+        return n.value
+
+    def _fit_many(self, wave, dec):
+        """Mapping._fit for one group per session: [(session, [(keyframe, pose) in order])], every session at most once"""
+        wave = [(s, g) for s, g in wave if g]
+        if not wave:
+            return
+        n = sum(len(g) for _, g in wave)
+        maps, slots = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        pose4, origin = np.zeros((n, 4), np.float64), np.zeros((n, 2), np.float64)
+        spans, a = [], 0
+        for s, group in wave:
+            v = self.maps[s]
+            for i, (kf, pose) in enumerate(group):
+                yaw = pose.theta()
+                maps[a + i], slots[a + i] = s, kf._slot
+                pose4[a + i] = np.cos(yaw), np.sin(yaw), pose.x(), pose.y()
+            origin[a:a + len(group)] = v.y0, v.x0
+            spans.append((a, a + len(group)))
+            a += len(group)
+        mm = self._bounds(maps, slots, pose4, origin)
+        shift = np.zeros((n, 2), np.int64)
+        grows = [[0, 0, 0, 0] for _ in wave]
+        # adjust_bounds per session; the sessions whose origin moved in the middle of their group take their remaining bounds
+        # again, all of them in one call per pass
+        at = [lo for lo, _ in spans]
+        while True:
+            again = []
+            for w, ((s, _), (lo, hi)) in enumerate(zip(wave, spans)):
+                if at[w] < hi:
+                    at[w] = lo + self.maps[s]._adjust(mm[lo:hi], shift[lo:hi], grows[w], origin[lo:hi], at[w] - lo)
+                    if at[w] < hi:
+                        again.append(np.arange(at[w], hi))
+            if not again:
+                break
+            idx = np.concatenate(again)
+            mm[idx] = self._bounds(maps[idx], slots[idx], pose4[idx], origin[idx])
+        grown = [w for w, g in enumerate(grows) if any(g)]
+        if grown:
+            self._check(self._lib.sfe_mapset_grow(
+                self._h, len(grown), _L.ptr(np.array([wave[w][0] for w in grown], np.int32), C.c_int32),
+                _L.ptr(np.ascontiguousarray(np.array([grows[w] for w in grown], np.int32)), C.c_int32)))
+            for w in grown:
+                v = self.maps[wave[w][0]]
+                v._grow[0] += grows[w][0]
+                v._grow[1] += grows[w][2]
+        mm32 = np.ascontiguousarray(mm, np.int32)
+        shift32 = np.ascontiguousarray(shift, np.int32)
+        decs = np.full(n, 1 if dec else 0, np.uint8)
+        self._check(self._lib.sfe_mapset_refit(self._h, n, _L.ptr(maps, C.c_int32), _L.ptr(slots, C.c_int32),
+                                               _L.ptr(pose4, C.c_double), _L.ptr(origin, C.c_double), float(self.resolution),
+                                               _L.ptr(mm32, C.c_int32), _L.ptr(shift32, C.c_int32), _L.ptr(decs, C.c_uint8)))
+        for (s, group), (lo, hi) in zip(wave, spans):
+            self.maps[s]._fitted([kf for kf, _ in group], mm[lo:hi], shift[lo:hi])
+
+    def get_occupancy_grids(self, sessions=None, frames=None, resolution=None):
+        """maps[s].get_occupancy_grid(frames, resolution) for the listed sessions (all by default) -> list of OccupancyGrid,
+        rendered in one device call"""
+        if self.pub_occupancy1:
+            return self._render(range(self.S) if sessions is None else sessions, frames, resolution)
+        if self.pub_occupancy2:
+            return self.get_occupancy_grid2(frames, resolution)
+        return [None] * (self.S if sessions is None else len(sessions))
+
+    def _render(self, sessions, frames, resolution):
+        sessions = self._listed("get_occupancy_grids", sessions)
+        plans = [self.maps[s]._render_plan(frames, resolution) for s in sessions]
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
+        if frames is not None:
+            off = np.zeros(len(sessions) + 1, np.int32)
+            off[1:] = np.cumsum([len(p[1]) for p in plans])
+            slots = np.ascontiguousarray(np.concatenate([p[1] for p in plans]), np.int32) if off[-1] else i32([0])
+            self._check(self._lib.sfe_mapset_frames(self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32),
+                                                    _L.ptr(off, C.c_int32), _L.ptr(slots, C.c_int32)))
+        sizes = [p[3][0] * p[3][1] for p in plans]
+        out_off = np.zeros(len(sessions) + 1, np.int64)
+        out_off[1:] = np.cumsum(sizes)
+        occ = np.zeros(int(out_off[-1]), np.int8)
+        if len(occ):
+            self._check(self._lib.sfe_mapset_render(
+                self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([p[0] for p in plans]), C.c_int32),
+                _L.ptr(i32([p[2] for p in plans]), C.c_int32), _L.ptr(i32([p[3] for p in plans]), C.c_int32),
+                _L.ptr(np.ascontiguousarray(np.array([p[4] for p in plans], np.float64)), C.c_double),
+                _L.ptr(i32([p[5] for p in plans]), C.c_int32), out_off.ctypes.data_as(C.POINTER(C.c_longlong)),
+                occ.ctypes.data_as(C.POINTER(C.c_int8)), len(occ)))
+        return [self.maps[s]._grid_msg(p[2], p[6], occ[out_off[j]:out_off[j + 1]].reshape(p[3]).copy())
+                for j, (s, p) in enumerate(zip(sessions, plans))]

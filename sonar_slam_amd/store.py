@@ -88,6 +88,23 @@ class CloudStore(object):
             raise _L.SonarFEError("cloud %d was not stored (count %d: -1 octree too deep, -3 pool full)" % (handle, m.value))
         return out
 
+    def read_many(self, handles):
+        """the points of many clouds in one call (a copy per cloud, one final synchronisation) -> list of N x 2 float32 arrays"""
+        handles = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        counts = self.counts(handles)
+        bad = np.nonzero(counts < 0)[0]
+        if len(bad):
+            raise _L.SonarFEError("cloud %d was not stored (count %d: -1 octree too deep, -3 pool full)"
+                                  % (handles[bad[0]], counts[bad[0]]))
+        out = np.zeros((int(counts.sum()), 2), np.float32)
+        got = np.zeros(len(handles), np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_read_many(self.ctx.handle, self.handle, _L.ptr(handles, _C.c_int32),
+                                                                   len(handles), _L.ptr(out, _C.c_float), len(out),
+                                                                   _L.ptr(got, _C.c_int32)))
+        ends = np.cumsum(got)
+        return [out[e - c:e].copy() for e, c in zip(ends, got)]
+
     def truncate(self, n_slots):
         with self.ctx.lock:
             self.ctx._check(self.ctx.lib.sfe_cloud_store_truncate(self.ctx.handle, self.handle, int(n_slots)))

@@ -8,7 +8,15 @@ Prints one JSON line:
 The numpy side adds only `--ref-adds` keyframes from points (the rest through add_keyframe_logodds, which skips the
 measurement) to keep the run short.
 
-    python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20]
+With `--sessions S` (default 32; 0 skips the leg) also the lock-step map, under "lockstep": a MapBatch of S sessions next
+to S looped Mapping objects on the same inputs (session s is the session above, shifted by s metres), both in this process,
+alternated call by call, the median of the repetitions:
+  add_keyframes_ms       one add_keyframes call for S sessions / S add_keyframe calls, over `--batch-keyframes` steps
+  update_poses_ms        one update_poses call that moves every keyframe of every session / S update_poses calls,
+                         `--reps` times (the poses alternate between two sets)
+  ratio                  looped / lock-step
+
+    python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
 """
 import argparse
 import json
@@ -24,7 +32,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mapping_ref  # noqa: E402
 import oracle  # noqa: E402
 from sonar_slam_amd import _lib  # noqa: E402
-from sonar_slam_amd.mapping import Mapping  # noqa: E402
+from sonar_slam_amd.mapping import MapBatch, Mapping  # noqa: E402
 from sonar_slam_amd.pose2 import Pose2  # noqa: E402
 
 
@@ -52,10 +60,78 @@ def timed(fn):
     return (time.perf_counter() - t) * 1e3
 
 
+def lockstep(ctx, ping, settings, S, K, reps):
+    """MapBatch of S sessions against S looped Mappings, alternated in one process -> the "lockstep" record"""
+    poses, clouds = session(K)
+    pose = lambda s, k, d=0.0: Pose2(poses[k][0] + s + d, poses[k][1] - d, poses[k][2] + 0.01 * d)
+    batch = MapBatch(ctx, S, K, **settings)
+    batch.configure()
+    loop = []
+    for _ in range(S):
+        m = Mapping(ctx)
+        for k, v in settings.items():
+            setattr(m, k, v)
+        m.configure()
+        loop.append(m)
+    sessions = list(range(S))
+
+    def add_batch(k):
+        batch.add_keyframes(sessions, [k] * S, [pose(s, k) for s in sessions], ping, [clouds[k]] * S)
+        ctx.sync()
+
+    def add_loop(k):
+        for s in sessions:
+            loop[s].add_keyframe(k, pose(s, k), ping, clouds[k])
+        ctx.sync()
+    t_b, t_l = [], []
+    for k in range(K):
+        first, second = (add_batch, add_loop) if k % 2 == 0 else (add_loop, add_batch)
+        a, b = timed(lambda: first(k)), timed(lambda: second(k))
+        if k:                       # step 0: geometry upload, first allocations
+            (t_b if first is add_batch else t_l).append(a)
+            (t_l if first is add_batch else t_b).append(b)
+    flat_s = [s for k in range(K) for s in sessions]
+    flat_k = [k for k in range(K) for s in sessions]
+    u_b, u_l = [], []
+    for rep in range(reps + 1):
+        d = 0.7 if rep % 2 == 0 else 0.0
+        flat_p = [pose(s, k, d) for k in range(K) for s in sessions]
+        keys_s = list(range(K))
+        poses_s = [[pose(s, k, d) for k in range(K)] for s in sessions]      # both legs get their poses ready-made
+
+        def up_batch():
+            batch.update_poses(flat_s, flat_k, flat_p)
+            ctx.sync()
+
+        def up_loop():
+            for s in sessions:
+                loop[s].update_poses(keys_s, poses_s[s])
+            ctx.sync()
+        first, second = (up_batch, up_loop) if rep % 2 == 0 else (up_loop, up_batch)
+        a, b = timed(first), timed(second)
+        if rep:                     # the first pass grows scratch buffers
+            (u_b if first is up_batch else u_l).append(a)
+            (u_l if first is up_batch else u_b).append(b)
+    equal = all(np.array_equal(batch.maps[s].logodds_grid.view(np.int32), loop[s].logodds_grid.view(np.int32))
+                for s in (0, S - 1))
+    med = lambda v: float(np.median(v))
+    out = {"sessions": S, "keyframes": K, "reps": reps, "apply_rounds": batch.last_apply_rounds,
+           "add_keyframes_ms": {"lockstep": med(t_b), "looped": med(t_l), "ratio": med(t_l) / med(t_b)},
+           "update_poses_ms": {"lockstep": med(u_b), "looped": med(u_l), "ratio": med(u_l) / med(u_b)},
+           "grids_equal": bool(equal)}
+    batch.close()
+    for m in loop:
+        m.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
     ap.add_argument("--ref-adds", type=int, default=20)
+    ap.add_argument("--sessions", type=int, default=32)
+    ap.add_argument("--batch-keyframes", type=int, default=40)
+    ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
@@ -105,6 +181,8 @@ def main():
                         "box": [int(ref.rmax - ref.rmin + 1), int(ref.cmax - ref.cmin + 1)]}
     out["grid_rows_cols"] = [int(dev.rows), int(dev.cols)]
     out["box_equal"] = [dev.rmin, dev.rmax, dev.cmin, dev.cmax] == [ref.rmin, ref.rmax, ref.cmin, ref.cmax]
+    if a.sessions > 0:
+        out["lockstep"] = lockstep(ctx, ping, settings, a.sessions, a.batch_keyframes, a.reps)
     print(json.dumps(out))
 
 
