@@ -700,6 +700,28 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
  *     geoms[b].  One synchronisation.
  *   sfe_mapset_measure: sfe_map_measure over (map, slot) jobs: all hits in one upload.  One synchronisation.
  *     sfe_mapset_measure_stages reads job b of the last call.
+ *   sfe_mapset_measure_store: the same measurement with the hits taken on the device from clouds of a cloud store of the same
+ *     context: job b = the cloud handles[b] for (maps[b], slots[b]) of geometry geoms[b], read with hit table tabs[b].
+ *     Phase one, in this call: the radius outlier filter of every cloud (sfe_remove_outlier's decision; skipped for
+ *     min_points <= 1), then per kept point its polar cell (row, column) / skips into the set's hit buffer -- the row
+ *     exactly as numpy computes it for float32 points, the column from atan2 in double and the hit table's cubic, and only
+ *     where that is safe (the guard band, below); every other point goes to its job's undecided list.  One read-back of n
+ *     counters: n_points_out[b] = the cloud's size, n_undecided_out[b] = its undecided points.  If none is undecided the
+ *     measurement runs at once and the call is complete; no point crosses to the host.  Otherwise the call is left pending:
+ *     sfe_mapset_measure_store_undecided copies the undecided points out (xy_out[2 i ..], pos_out[i] = the point's entry
+ *     in the hit buffer, ascending; cap >= their number), and phase two, sfe_mapset_measure_store_finish, takes the host's
+ *     (row, column) for exactly those entries and runs the measurement.  Any later measure call drops a pending one, which
+ *     has changed nothing.  hrhc / k_off / ktab / div are per job as in sfe_mapset_measure, given as for a cloud with points:
+ *     a cloud of zero points becomes a keyframe without a measurement (hr < 0, all miss_prob), a cloud the filter empties
+ *     keeps hr >= 0 with no hits.  Refused before anything changes: a handle the store does not hold or whose count is
+ *     negative (a failed producer) and an unknown table with SFE_ERR_ARG, a slot >= max_keyframes with SFE_ERR_CAP (a
+ *     geometry of more than max_px pixels is never registered: sfe_mapset_geometry refuses it with SFE_ERR_CAP).
+ *   sfe_mapset_hit_table: what the cells need of a sonar geometry, stored once: the float32 bearings (their ends bound the
+ *     table), oculus.b2c's cubic spline as n_intervals + 1 ascending knots and 4 double coefficients per interval (powers
+ *     of (angle - knot), highest first), margin = 2 * ulp_float32(max(1, |bearing|)) * max(1, largest column slope) + 1e-9,
+ *     num_ranges, range_resolution (range_in_double: the row in float64, for a numpy float64 scalar resolution) and the skips.
+ *     Guard band: a point is decided only if its column value is further than margin from every x.5 and its angle further
+ *     than margin from both ends of the table (outside the table the column is 0).
  *   sfe_mapset_fit_bounds: as sfe_map_fit_bounds; keyframe b carries its own pose and its own map's origin.  One synchronisation.
  *   sfe_mapset_grow: pad map maps[b] by grow4[4 b ..] = {top, bottom, left, right} (each map at most once per call); a map
  *     with four zeros costs nothing; one synchronisation for all the maps that grew.
@@ -727,6 +749,16 @@ int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
                        const float *ktab, int n_ktab, const double *div, float miss32, float logit_miss, float hit32,
                        float logit_hit);
 int sfe_mapset_measure_stages(sfe_mapset *ms, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out);
+int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings, const double *breaks, const double *coef,
+                         int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double,
+                         int r_skip, int c_skip, int *id_out);
+int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slots,
+                             const int32_t *geoms, const int32_t *handles, const int32_t *tabs, double radius, int min_points,
+                             const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab, const double *div,
+                             float miss32, float logit_miss, float hit32, float logit_hit, int32_t *n_points_out,
+                             int32_t *n_undecided_out);
+int sfe_mapset_measure_store_undecided(sfe_mapset *ms, float *xy_out, int32_t *pos_out, int cap);
+int sfe_mapset_measure_store_finish(sfe_mapset *ms, int n_cells, const int32_t *pos, const int32_t *cells);
 int sfe_mapset_fit_bounds(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4,
                           const double *origin2, double resolution, int32_t *mm_out);
 int sfe_mapset_grow(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *grow4);

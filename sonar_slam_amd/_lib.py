@@ -284,6 +284,13 @@ SIGNATURES = {
     "sfe_mapset_measure": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, C.c_int, _f64p,
                                      C.c_float, C.c_float, C.c_float, C.c_float]),
     "sfe_mapset_measure_stages": (C.c_int, [_vp, C.c_int, _u8p, _f32p, _i32p]),
+    "sfe_mapset_hit_table": (C.c_int, [_vp, _f32p, C.c_int, _f64p, _f64p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
+                                       C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_mapset_measure_store": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, C.c_double, C.c_int, _i32p,
+                                           _i32p, _f32p, C.c_int, _f64p, C.c_float, C.c_float, C.c_float, C.c_float, _i32p,
+                                           _i32p]),
+    "sfe_mapset_measure_store_undecided": (C.c_int, [_vp, _f32p, _i32p, C.c_int]),
+    "sfe_mapset_measure_store_finish": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     "sfe_mapset_fit_bounds": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f64p, _f64p, C.c_double, _i32p]),
     "sfe_mapset_grow": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     "sfe_mapset_refit": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _f64p, _f64p, C.c_double, _i32p, _i32p, _u8p]),

@@ -153,6 +153,12 @@ class SessionBatch(object):
                  oculus_horizontal_aperture=np.radians(130.0), mcd_random_state=None, mapping=None):
         from .pipeline import KeyframeBatch
         from .replay import ChainBackend
+        if mapping is not None:                                  # (checked before anything is allocated)
+            mapping = dict(mapping)
+            if "ping" not in mapping:
+                raise ValueError("SessionBatch: mapping needs a `ping` (num_ranges, range_resolution, bearings)")
+            if mapping.get("feed", "host") not in ("host", "store"):
+                raise ValueError("SessionBatch: mapping feed must be \"host\" or \"store\", got %r" % (mapping["feed"],))
         self.ctx, self.S, self.K = ctx, int(n_sessions), int(n_steps)
         # loop-closure search (replay.FrontEnd's arguments of the same names, its defaults but for nssm_enable: off here, so that a
         # batch built without it runs, sizes and records exactly what it did before the search existed)
@@ -196,14 +202,14 @@ class SessionBatch(object):
         self.shgo_replay, self._plan = bool(shgo_replay), None
         # mapping: None (no map: the batch allocates, runs and records what it did before maps existed), or a dict: `ping` (what
         # Mapping.add_keyframe reads of a ping: num_ranges, range_resolution, bearings), optionally `max_pixels`, and Mapping's
-        # settings -> self.maps, a mapping.MapBatch that step(k) feeds keyframe k of every session
-        self.maps, self._map_ping = None, None
+        # settings -> self.maps, a mapping.MapBatch that step(k) feeds keyframe k of every session; `feed`: "host" (the
+        # default: the clouds are read back and handed to add_keyframes) or "store" (add_keyframes_store: the same maps, bit
+        # for bit, from the clouds where they lie on the device)
+        self.maps, self._map_ping, self._map_feed = None, None, "host"
         if mapping is not None:
             from .mapping import MapBatch
-            mapping = dict(mapping)
-            if "ping" not in mapping:
-                raise ValueError("SessionBatch: mapping needs a `ping` (num_ranges, range_resolution, bearings)")
             self._map_ping = mapping.pop("ping")
+            self._map_feed = mapping.pop("feed", "host")
             self.maps = MapBatch(ctx, self.S, self.K, **mapping)
             self.maps.configure()
         self.init_stats = {"shgo_s": 0.0, "cost_calls": 0, "table_hits": 0, "speculated": 0, "speculation_failed": 0,
@@ -310,8 +316,12 @@ class SessionBatch(object):
         corrections are the caller's: ``self.maps.update_poses``)"""
         if self.maps is None:
             return
+        poses = [self._pose(k, s) for s in range(self.S)]
+        if self._map_feed == "store":
+            self.maps.add_keyframes_store(range(self.S), [k] * self.S, poses, self._map_ping, self.store, self.handles[:, k])
+            return
         clouds = self.store.read_many(self.handles[:, k])
-        self.maps.add_keyframes(range(self.S), [k] * self.S, [self._pose(k, s) for s in range(self.S)], self._map_ping, clouds)
+        self.maps.add_keyframes(range(self.S), [k] * self.S, poses, self._map_ping, clouds)
 
     def _scan_match_step(self, k, rec, src_h, th, T6, prev, pose):
         S, store = self.S, self.store

@@ -6,6 +6,7 @@
 // polar log-odds image and its cell list (r, c uint16 + l float32, ascending r * cols + c).  Cell lists are double-buffered:
 // a refit writes the new list next to the old one, subtracts the old, adds the new, and flips.  Growth pads the grid and
 // bumps two counters; a list keeps the counters it was written at, and its cells are shifted by the difference when read.
+#include <algorithm>
 #include <climits>
 #include <cstring>
 
@@ -926,19 +927,17 @@ __global__ __launch_bounds__(MAP_THREADS) void mapset_render_kernel(const Render
     }
 }
 
-// pcl.remove_outlier's decision (radius_count_kernel of sfe_icp.hip, the same float32 arithmetic) for many clouds: cloud
-// blockIdx.y = pts[off[y] .. off[y + 1]); keep iff more than min_points points (itself included) lie within the radius
-__global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__restrict__ pts, const int32_t *__restrict__ off,
-                                                                float r2, int min_points, uint8_t *__restrict__ keep)
+// pcl.remove_outlier's decision (radius_count_kernel of sfe_icp.hip, the same float32 arithmetic) for one cloud of a launch
+// over many: block blockIdx.x of the cloud's row; keep iff more than min_points points (itself included) lie within the radius
+__device__ __forceinline__ void radius_count_cloud(const float2 *__restrict__ cloud, int n, float r2, int min_points,
+                                                   uint8_t *__restrict__ keep, float2 *s_p /* [2048], shared */)
 {
-    __shared__ float2 s_p[2048];
-    const int base = off[blockIdx.y], n = off[blockIdx.y + 1] - base;
     if ((int)(blockIdx.x * 256) >= n)
         return; // the whole block at once
     const int i = blockIdx.x * 256 + threadIdx.x;
     float px = 0, py = 0;
     if (i < n) {
-        const float2 p = pts[base + i];
+        const float2 p = cloud[i];
         px = p.x;
         py = p.y;
     }
@@ -947,7 +946,7 @@ __global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__
         const int tn = min(2048, n - tb);
         __syncthreads();
         for (int j = threadIdx.x; j < tn; j += 256)
-            s_p[j] = pts[base + tb + j];
+            s_p[j] = cloud[tb + j];
         __syncthreads();
         for (int j = 0; j < tn; ++j) {
             const float2 t = s_p[j];
@@ -956,7 +955,134 @@ __global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__
         }
     }
     if (i < n)
-        keep[base + i] = cnt > min_points;
+        keep[i] = cnt > min_points;
+}
+
+// ... cloud blockIdx.y = pts[off[y] .. off[y + 1])
+__global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__restrict__ pts, const int32_t *__restrict__ off,
+                                                                float r2, int min_points, uint8_t *__restrict__ keep)
+{
+    __shared__ float2 s_p[2048];
+    const int base = off[blockIdx.y];
+    radius_count_cloud(pts + base, off[blockIdx.y + 1] - base, r2, min_points, keep + base, s_p);
+}
+
+// --- the store feed: a keyframe's hits straight from its cloud in a cloud store (mapping.py: MapBatch.add_keyframes_store) ----
+// One job = one cloud (pool offset, size) for one (map, slot); its points own the entries [hit_off, hit_off + n) of the call's
+// hit buffer, one (row, column) pair per point, (-1, -1) for a point that leaves no hit (map_hits_kernel skips those).
+struct FeedJob {
+    long long off;
+    int32_t n, hit_off, tab;
+};
+// what Mapping._hit_indices reads of a sonar geometry and its skips
+struct HitTab {
+    const double *breaks; // [n_iv + 1] ascending: the knots of oculus.b2c's cubic spline
+    const double *coef;   // [n_iv][4]: its cubic on [breaks[k], breaks[k + 1]) in powers of (a - breaks[k]), highest first
+    int32_t n_iv, num_ranges, num_bearings, r_skip, c_skip;
+    int32_t wide;         // ra / range_resolution - 1 in float64 (a numpy float64 scalar resolution), else in float32
+    float res32;
+    double res64, b_first, b_last, margin;
+};
+struct UndPoint {
+    float x, y;
+    int32_t pos, job; // its entry in the hit buffer
+};
+
+// the outlier filter of every job's cloud: keep[hit_off + i]
+__global__ __launch_bounds__(256) void feed_radius_count_kernel(const float2 *__restrict__ pool, const FeedJob *__restrict__ jobs,
+                                                                float r2, int min_points, uint8_t *__restrict__ keep)
+{
+    __shared__ float2 s_p[2048];
+    const FeedJob j = jobs[blockIdx.y];
+    radius_count_cloud(pool + j.off, j.n, r2, min_points, keep + j.hit_off, s_p);
+}
+
+// Mapping._hit_indices for the kept float32 points of every job (numpy 2 promotion):
+//   r = clip(int32(round(norm(p) / range_resolution - 1)), 0, num_ranges - 1) // r_skip
+//   c = clip(int32(round(b2c(arctan2(y, x)))), 0, num_bearings - 1) // c_skip
+// The row is exact: float32 multiply, add, the correctly rounded sqrtf (see store_fov_kernel), divide, subtract, rint.
+// The column is not reproduced to the last bit: numpy takes atan2f in float32 and scipy evaluates the B-spline in double;
+// here atan2 is taken in double and the spline as one cubic per knot interval (PPoly coefficients from the host).  With
+// a = the true angle, numpy's a32 = atan2f(y, x) lies within one float32 ulp u of it (u taken at max(1, largest |bearing|),
+// no smaller than the ulp of any angle inside the table), the double atan2 within 1e-15.  So the column numpy rounds lies
+// within u * slope + (the two evaluations' own difference, some 1e-12 columns) of the one computed here, where slope is
+// the largest |d column / d angle| of the table (no less than 1, so that the same number also bounds u itself).  The host
+// passes margin = 2 * u * slope + 1e-9.  A point is decided only if its column value is further than margin from every
+// rounding boundary x.5, and its angle either further than margin inside both table ends or further than margin outside
+// one (outside: fill_value -1, which clips to column 0).  Every other point goes to its job's undecided list; the host
+// runs _hit_indices on just those.
+__global__ __launch_bounds__(256) void feed_hit_cells_kernel(const float2 *__restrict__ pool, const FeedJob *__restrict__ jobs,
+                                                             const HitTab *__restrict__ tabs, const uint8_t *__restrict__ keep,
+                                                             int32_t *__restrict__ hits, UndPoint *__restrict__ und,
+                                                             int32_t *__restrict__ n_und)
+{
+    const int jb = blockIdx.y;
+    const FeedJob j = jobs[jb];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= j.n)
+        return;
+    const int pos = j.hit_off + i;
+    int hr = -1, hc = -1;
+    if (!keep || keep[pos]) {
+        const float2 p = pool[j.off + i];
+        const HitTab t = tabs[j.tab];
+        const float ra = sqrtf(__fadd_rn(__fmul_rn(p.x, p.x), __fmul_rn(p.y, p.y)));
+        int ri = INT_MIN; // what np.int32 makes of a value no int32 holds (and of nan)
+        if (t.wide) {
+            const double ro = rint(__dsub_rn(__ddiv_rn((double)ra, t.res64), 1.0));
+            if (ro >= -2147483648.0 && ro < 2147483648.0)
+                ri = (int)ro;
+        } else {
+            const float ro = rintf(__fsub_rn(__fdiv_rn(ra, t.res32), 1.0f));
+            if (ro >= -2147483648.0f && ro < 2147483648.0f)
+                ri = (int)ro;
+        }
+        ri = min(max(ri, 0), t.num_ranges - 1);
+        const double a = atan2((double)p.y, (double)p.x);
+        bool decided = false;
+        int col = 0;
+        if (a < t.b_first - t.margin || a > t.b_last + t.margin) {
+            decided = true;
+        } else if (a > t.b_first + t.margin && a < t.b_last - t.margin) {
+            int lo = 0, hi = t.n_iv; // breaks[lo] <= a < breaks[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (t.breaks[mid] <= a)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            const double d = a - t.breaks[lo];
+            const double *c = t.coef + 4 * lo;
+            const double v = ((c[0] * d + c[1]) * d + c[2]) * d + c[3];
+            if (fabs(v) < 1e9) {
+                decided = fabs(v - floor(v) - 0.5) > t.margin;
+                col = min(max((int)rint(v), 0), t.num_bearings - 1);
+            }
+        }
+        if (decided) {
+            hr = ri / t.r_skip;
+            hc = col / t.c_skip;
+        } else {
+            const int k = atomicAdd(&n_und[jb], 1);
+            UndPoint u;
+            u.x = p.x, u.y = p.y, u.pos = pos, u.job = jb;
+            und[j.hit_off + k] = u; // at most n entries per job
+        }
+    }
+    hits[2 * pos] = hr;
+    hits[2 * pos + 1] = hc;
+}
+
+// the host's cells of the undecided points
+__global__ void feed_fill_kernel(const int32_t *__restrict__ pos, const int32_t *__restrict__ cells, int n,
+                                 int32_t *__restrict__ hits)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        hits[2 * pos[i]] = cells[2 * i];
+        hits[2 * pos[i] + 1] = cells[2 * i + 1];
+    }
 }
 
 } // namespace
@@ -970,10 +1096,20 @@ struct sfe_mapset {
     float *d_logodds = nullptr, *d_l = nullptr;
     uint16_t *d_r = nullptr, *d_c = nullptr;
     int32_t *d_counts = nullptr; // [map * max_kf + slot][2]
-    MapBuf buf[6];
+    MapBuf buf[11]; // 6 .. 10: the store feed's job tables, hit buffer, keep flags, undecided lists and counters
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
     long long apply_launches = 0; // launches of mapset_apply_kernel so far
+    // the store feed: hit tables (device copies owned here), and the call that waits for the host's cells
+    std::vector<HitTab> hit_tabs;
+    struct Feed {
+        bool pending = false;
+        std::vector<int32_t> maps, slots, geoms, n_und;
+        std::vector<MeasJob> jobs;
+        std::vector<float> ktab;
+        float miss32 = 0, logit_miss = 0, hit32 = 0, logit_hit = 0;
+        int tot = 0, tot_und = 0;
+    } feed;
 };
 
 namespace {
@@ -1091,6 +1227,55 @@ int set_run_rounds(sfe_mapset *ms, int buf, const std::vector<std::vector<ApplyJ
     return 0;
 }
 
+// the measurement of a call's jobs from its hits on the device (one pair per entry; a pair outside the image leaves no
+// hit): mask, filter, columns; one synchronisation; then the slots take their geometries
+int set_measure_run(sfe_mapset *ms, const std::vector<MeasJob> &jobs, const int32_t *maps, const int32_t *slots,
+                    const int32_t *geoms, const int32_t *d_hits, const float *ktab, int n_ktab, float miss32, float logit_miss,
+                    float hit32, float logit_hit)
+{
+    sfe_ctx *ctx = ms->ctx;
+    const int n = (int)jobs.size();
+    int64_t px = 0;
+    int max_px = 0, max_cols = 0;
+    for (const MeasJob &j : jobs) {
+        px += j.slot_px;
+        max_px = max(max_px, j.slot_px);
+        max_cols = max(max_cols, j.img_cols);
+    }
+    MeasJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
+    float *d_k = set_upload(ms, 2, ktab, (size_t)n_ktab);
+    uint8_t *d_mask = (uint8_t *)buf_get(ctx, ms->buf[3], (size_t)px);
+    float *d_prob = (float *)buf_get(ctx, ms->buf[4], sizeof(float) * (size_t)px);
+    int32_t *d_fh = (int32_t *)buf_get(ctx, ms->buf[5], sizeof(int32_t) * (size_t)n * max_cols);
+    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set measurement scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
+    const unsigned ny = (unsigned)n;
+    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
+                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
+                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
+    for (int b = 0; b < n; ++b)
+        ms->slots[set_idx(ms, maps[b], slots[b])].geom = geoms[b];
+    ms->last_meas = jobs;
+    ms->last_meas_n = max_cols;
+    return 0;
+}
+
+// the second half of a store-fed measurement: every entry of the hit buffer is final
+int feed_finish(sfe_mapset *ms)
+{
+    sfe_mapset::Feed &f = ms->feed;
+    f.pending = false;
+    return set_measure_run(ms, f.jobs, f.maps.data(), f.slots.data(), f.geoms.data(), (const int32_t *)ms->buf[7].p,
+                           f.ktab.data(), (int)f.ktab.size(), f.miss32, f.logit_miss, f.hit32, f.logit_hit);
+}
+
 } // namespace
 
 extern "C" {
@@ -1148,6 +1333,8 @@ void sfe_mapset_destroy(sfe_mapset *ms)
     (void)hipFree(ms->d_counts);
     for (auto &b : ms->buf)
         (void)hipFree(b.p);
+    for (auto &t : ms->hit_tabs)
+        (void)hipFree((void *)t.breaks); // (breaks and coef are one block)
     delete ms;
 }
 
@@ -1210,9 +1397,9 @@ int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
     SFE_ARG(ctx, n >= 0 && (n == 0 || (maps && slots && geoms && hit_off && hrhc && k_off && div)) && n_ktab >= 0);
     if (n == 0)
         return 0;
+    ms->feed.pending = false;
     std::vector<MeasJob> jobs(n);
     int64_t px = 0;
-    int max_px = 0, max_cols = 0;
     for (int b = 0; b < n; ++b) {
         if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
             return rc;
@@ -1232,35 +1419,11 @@ int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
         j.px_off = px;
         j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
         px += j.slot_px;
-        max_px = max(max_px, j.slot_px);
-        max_cols = max(max_cols, j.img_cols);
     }
     const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
     SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
-    MeasJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
     int32_t *d_hits = set_upload(ms, 1, hits, 2 * (size_t)(n_hit_tot - 1));
-    float *d_k = set_upload(ms, 2, ktab, (size_t)n_ktab);
-    uint8_t *d_mask = (uint8_t *)buf_get(ctx, ms->buf[3], (size_t)px);
-    float *d_prob = (float *)buf_get(ctx, ms->buf[4], sizeof(float) * (size_t)px);
-    int32_t *d_fh = (int32_t *)buf_get(ctx, ms->buf[5], sizeof(int32_t) * (size_t)n * max_cols);
-    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set measurement scratch allocation / upload failed");
-    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
-    const unsigned ny = (unsigned)n;
-    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
-                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
-                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
-    for (int b = 0; b < n; ++b)
-        ms->slots[set_idx(ms, maps[b], slots[b])].geom = geoms[b];
-    ms->last_meas = jobs;
-    ms->last_meas_n = max_cols;
-    return 0;
+    return set_measure_run(ms, jobs, maps, slots, geoms, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit);
 }
 
 int sfe_mapset_measure_stages(sfe_mapset *ms, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
@@ -1618,6 +1781,186 @@ int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t 
     SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return 0;
+}
+
+int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings, const double *breaks, const double *coef,
+                         int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double,
+                         int r_skip, int c_skip, int *id_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, bearings && breaks && coef && id_out && num_bearings >= 2 && n_intervals >= 1 && n_intervals < (1 << 20));
+    SFE_ARG(ctx, margin > 0 && num_ranges >= 1 && range_resolution > 0 && r_skip >= 1 && c_skip >= 1);
+    for (int k = 0; k < n_intervals; ++k)
+        SFE_ARG(ctx, breaks[k] < breaks[k + 1]);
+    SFE_ARG(ctx, breaks[0] <= (double)bearings[0] && (double)bearings[num_bearings - 1] <= breaks[n_intervals]);
+    SFE_ARG(ctx, bearings[0] < bearings[num_bearings - 1]);
+    HitTab t;
+    double *d = nullptr;
+    const size_t nb = (size_t)n_intervals + 1, nc = 4 * (size_t)n_intervals;
+    SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(double) * (nb + nc)));
+    if (hipMemcpy(d, breaks, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nb, coef, sizeof(double) * nc, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: hit table upload failed");
+    }
+    t.breaks = d, t.coef = d + nb;
+    t.n_iv = n_intervals, t.num_ranges = num_ranges, t.num_bearings = num_bearings, t.r_skip = r_skip, t.c_skip = c_skip;
+    t.wide = range_in_double ? 1 : 0;
+    t.res32 = (float)range_resolution, t.res64 = range_resolution;
+    t.b_first = (double)bearings[0], t.b_last = (double)bearings[num_bearings - 1], t.margin = margin;
+    ms->hit_tabs.push_back(t);
+    *id_out = (int)ms->hit_tabs.size() - 1;
+    return 0;
+}
+
+int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slots,
+                             const int32_t *geoms, const int32_t *handles, const int32_t *tabs, double radius, int min_points,
+                             const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab, const double *div,
+                             float miss32, float logit_miss, float hit32, float logit_hit, int32_t *n_points_out,
+                             int32_t *n_undecided_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, store && sfe_store_ctx(store) == ctx && n >= 0 && n <= 65535 && n_ktab >= 0 && (n_ktab == 0 || ktab));
+    SFE_ARG(ctx, n == 0 || (maps && slots && geoms && handles && tabs && hrhc && k_off && div && n_points_out && n_undecided_out));
+    SFE_ARG(ctx, min_points <= 1 || radius >= 0);
+    sfe_mapset::Feed &f = ms->feed;
+    f.pending = false;
+    if (n == 0)
+        return 0;
+    SfeStoreView v;
+    if (int rc = sfe_store_view(store, &v))
+        return rc;
+    std::vector<MeasJob> jobs(n);
+    std::vector<FeedJob> fjobs(n);
+    int64_t px = 0, tot = 0;
+    int max_n = 0;
+    for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+        const int hd = handles[b];
+        if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "map set: cloud %d named (job %d), the store holds %d%s", hd, b, v.n_slots,
+                               (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
+        SFE_ARG(ctx, tabs[b] >= 0 && tabs[b] < (int)ms->hit_tabs.size());
+        const MapGeom &g = ms->geoms[geoms[b]];
+        const int cnt = v.cnt[hd];
+        MeasJob &j = jobs[b];
+        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
+        j.hit_off = (int32_t)tot;
+        j.n_hits = cnt;
+        // a cloud without points is a keyframe without a measurement (hr < 0); one the filter empties keeps its kernel
+        j.hr = cnt ? hrhc[2 * b] : -1, j.hc = cnt ? hrhc[2 * b + 1] : 0;
+        j.k_off = cnt ? k_off[b] : 0;
+        j.div = cnt ? div[b] : 1.0;
+        SFE_ARG(ctx, j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
+        SFE_ARG(ctx, cnt == 0 || (j.hr >= 0 && j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab));
+        j.px_off = px;
+        j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
+        px += j.slot_px;
+        fjobs[b].off = v.off[hd], fjobs[b].n = cnt, fjobs[b].hit_off = (int32_t)tot, fjobs[b].tab = tabs[b];
+        tot += cnt;
+        max_n = max(max_n, cnt);
+        SFE_ARG(ctx, tot < (1 << 30));
+    }
+    FeedJob *d_jobs = set_stage(ms, 6, fjobs);
+    HitTab *d_tabs = set_stage(ms, 10, ms->hit_tabs);
+    int32_t *d_hits = (int32_t *)buf_get(ctx, ms->buf[7], sizeof(int32_t) * 2 * (size_t)(tot + 1));
+    uint8_t *d_keep = (uint8_t *)buf_get(ctx, ms->buf[8], (size_t)(tot + 1));
+    char *d_und = (char *)buf_get(ctx, ms->buf[9], sizeof(UndPoint) * (size_t)tot + sizeof(int32_t) * (size_t)n);
+    int32_t *h_cnt = (int32_t *)sfe_pinned_io(ctx, 3, sizeof(int32_t) * (size_t)n);
+    if (!d_jobs || !d_tabs || !d_hits || !d_keep || !d_und || !h_cnt)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set store feed scratch allocation / upload failed");
+    int32_t *d_cnt = (int32_t *)(d_und + sizeof(UndPoint) * (size_t)tot);
+    SFE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)n, ctx->stream));
+    if (max_n > 0) {
+        const dim3 grid((unsigned)((max_n + 255) / 256), (unsigned)n);
+        const bool filter = min_points > 1; // Mapping._hits
+        if (filter) {
+            hipLaunchKernelGGL(feed_radius_count_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs,
+                               (float)(radius * radius), min_points, d_keep);
+            SFE_LAUNCH_CHECK(ctx);
+        }
+        hipLaunchKernelGGL(feed_hit_cells_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs, d_tabs,
+                           filter ? (const uint8_t *)d_keep : nullptr, d_hits, (UndPoint *)d_und, d_cnt);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    f.maps.assign(maps, maps + n), f.slots.assign(slots, slots + n), f.geoms.assign(geoms, geoms + n);
+    f.n_und.assign(h_cnt, h_cnt + n);
+    f.jobs = jobs;
+    f.ktab.assign(ktab, ktab + n_ktab);
+    f.miss32 = miss32, f.logit_miss = logit_miss, f.hit32 = hit32, f.logit_hit = logit_hit;
+    f.tot = (int)tot, f.tot_und = 0;
+    for (int b = 0; b < n; ++b) {
+        n_points_out[b] = jobs[b].n_hits;
+        n_undecided_out[b] = h_cnt[b];
+        f.tot_und += h_cnt[b];
+    }
+    if (f.tot_und == 0)
+        return feed_finish(ms);
+    f.pending = true;
+    return 0;
+}
+
+int sfe_mapset_measure_store_undecided(sfe_mapset *ms, float *xy_out, int32_t *pos_out, int cap)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    sfe_mapset::Feed &f = ms->feed;
+    SFE_ARG(ctx, f.pending && xy_out && pos_out && cap >= f.tot_und);
+    std::vector<UndPoint> und((size_t)f.tot_und);
+    size_t at = 0;
+    for (size_t b = 0; b < f.jobs.size(); ++b) {
+        if (!f.n_und[b])
+            continue;
+        SFE_HIP(ctx, hipMemcpyAsync(und.data() + at, (const UndPoint *)ms->buf[9].p + f.jobs[b].hit_off,
+                                    sizeof(UndPoint) * (size_t)f.n_und[b], hipMemcpyDeviceToHost, ctx->stream));
+        at += (size_t)f.n_und[b];
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // (the device appended them in no fixed order)
+    std::sort(und.begin(), und.end(), [](const UndPoint &a, const UndPoint &b) { return a.pos < b.pos; });
+    for (size_t i = 0; i < und.size(); ++i) {
+        xy_out[2 * i] = und[i].x, xy_out[2 * i + 1] = und[i].y;
+        pos_out[i] = und[i].pos;
+    }
+    return 0;
+}
+
+int sfe_mapset_measure_store_finish(sfe_mapset *ms, int n_cells, const int32_t *pos, const int32_t *cells)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    sfe_mapset::Feed &f = ms->feed;
+    SFE_ARG(ctx, f.pending && n_cells == f.tot_und && pos && cells);
+    for (int i = 0; i < n_cells; ++i)
+        SFE_ARG(ctx, pos[i] >= 0 && pos[i] < f.tot);
+    // (the keep flags have been read: their buffer takes the upload)
+    std::vector<int32_t> up(3 * (size_t)n_cells);
+    memcpy(up.data(), pos, sizeof(int32_t) * (size_t)n_cells);
+    memcpy(up.data() + n_cells, cells, sizeof(int32_t) * 2 * (size_t)n_cells);
+    int32_t *d_up = set_stage(ms, 8, up);
+    if (!d_up)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set store feed: upload of the host's cells failed");
+    hipLaunchKernelGGL(feed_fill_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, d_up,
+                       d_up + n_cells, n_cells, (int32_t *)ms->buf[7].p);
+    SFE_LAUNCH_CHECK(ctx);
+    return feed_finish(ms);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

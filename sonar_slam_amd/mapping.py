@@ -311,10 +311,16 @@ class Mapping(object):
         c = np.clip(np.int32(np.round(c)), 0, o.num_bearings - 1)
         r = o.ra2ro(np.linalg.norm(points[:, :2], axis=1))
         r = np.clip(np.int32(np.round(r)), 0, o.num_ranges - 1)
-        hc = int(round(self.inflation_angle / o.angular_resolution / self.oculus_c_skip))
-        hr = int(round(self.inflation_range / o.range_resolution / self.oculus_r_skip))
+        hr, hc = self._hit_halves()
         hits = np.c_[r // self.oculus_r_skip, c // self.oculus_c_skip].astype(np.int32)
         return hits, hr, hc
+
+    def _hit_halves(self):
+        """(hr, hc): the half sizes of the inflation kernel in pixels of the downsampled image"""
+        o = self.oculus
+        hc = int(round(self.inflation_angle / o.angular_resolution / self.oculus_c_skip))
+        hr = int(round(self.inflation_range / o.range_resolution / self.oculus_r_skip))
+        return hr, hc
 
     def _measure_args(self, hits, hr, hc):
         """-> (hits int32 [n x 2], the float32 kernel table, div) of one keyframe's measurement"""
@@ -579,6 +585,53 @@ class Mapping(object):
         return self._grid_msg(box, resolution, occ)
 
 
+# ---- the hit cells on the device (MapBatch.add_keyframes_store) ----------------------------------------------------------
+def spline_table(oculus):
+    """``oculus.b2c`` as one cubic per knot interval, in double -> (breaks [n + 1], coef [n x 4]): on
+    [breaks[k], breaks[k + 1]) the column is polyval(coef[k], angle - breaks[k]).  (The not-a-knot spline has no knot at
+    the second and the second to last bearing, so there are two intervals fewer than bearing gaps.)"""
+    from scipy.interpolate import PPoly
+    sp = oculus.b2c._spline
+    pp = PPoly.from_spline((np.asarray(sp.t, np.float64), np.asarray(sp.c, np.float64).reshape(-1), sp.k))
+    live = np.nonzero(np.diff(pp.x) > 0)[0]
+    breaks = np.ascontiguousarray(np.r_[pp.x[live], pp.x[live[-1] + 1]], np.float64)
+    return breaks, np.ascontiguousarray(pp.c[:, live].T, np.float64)
+
+
+def guard_margin(oculus, breaks, coef):
+    """How far, in columns, a column value computed from a double atan2 must stay from a rounding boundary x.5 (and, in
+    radians, its angle from the ends of the bearing table) for numpy's float32 route to round it the same way:
+    2 * ulp_float32(max(1, largest |bearing|)) * max(1, largest |column slope| of the table) + 1e-9.  numpy's atan2f is
+    within one such ulp of the angle; the factor 2 and the 1e-9 cover the last bits of the two spline evaluations."""
+    h = np.diff(breaks)
+    a, b, c = 3 * coef[:, 0], 2 * coef[:, 1], coef[:, 2]            # the slope on interval k: a d^2 + b d + c, 0 <= d <= h
+    slope = max(np.abs(c).max(), np.abs((a * h + b) * h + c).max())
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.where(a != 0, -b / (2 * a), -1.0)
+    inside = (d > 0) & (d < h)
+    if inside.any():
+        slope = max(slope, np.abs((a * d + b) * d + c)[inside].max())
+    ulp = float(np.spacing(np.float32(max(1.0, float(np.abs(oculus.bearings).max())))))
+    return 2.0 * ulp * max(1.0, float(slope)) + 1e-9
+
+
+def decide_columns(oculus, points, breaks, coef, margin):
+    """The device rule of the store feed (csrc/sfe_map.hip: feed_hit_cells_kernel), restated for tests: float32 points
+    -> (columns before the skip, decided).  Undecided points carry column -1."""
+    a = np.arctan2(points[:, 1].astype(np.float64), points[:, 0].astype(np.float64))
+    first, last = float(oculus.bearings[0]), float(oculus.bearings[-1])
+    outside = (a < first - margin) | (a > last + margin)
+    inside = (a > first + margin) & (a < last - margin)
+    k = np.clip(np.searchsorted(breaks, a, side="right") - 1, 0, len(coef) - 1)
+    d = a - breaks[k]
+    v = ((coef[k, 0] * d + coef[k, 1]) * d + coef[k, 2]) * d + coef[k, 3]
+    safe = inside & (np.abs(v - np.floor(v) - 0.5) > margin)
+    col = np.full(len(points), -1, np.int64)
+    col[safe] = np.clip(np.rint(v[safe]), 0, oculus.num_bearings - 1).astype(np.int64)
+    col[outside] = 0
+    return col, safe | outside
+
+
 # ---- S maps in lock-step ---------------------------------------------------------------------------------------------
 SETTINGS = ("x0", "y0", "width", "height", "inc", "resolution", "pub_intensity", "pub_occupancy1", "hit_prob", "miss_prob",
             "inflation_angle", "inflation_range", "pub_occupancy2", "inflation_radius", "outlier_filter_radius",
@@ -632,6 +685,19 @@ class _SessionMap(Mapping):
         self._n_slots = 0
         self._hit_key = None
         self._meas_job = -1
+
+    @property
+    def point_cloud(self):
+        """the cloud of the last keyframe (the ``pub_occupancy2`` bookkeeping).  After ``add_keyframes_store`` it is read
+        from the store when asked for: the handle must still be live then (not dropped by ``store.truncate``)."""
+        if self._cloud_ref is not None:
+            store, handle = self._cloud_ref
+            return store.read(handle)
+        return self._point_cloud
+
+    @point_cloud.setter
+    def point_cloud(self, points):
+        self._point_cloud, self._cloud_ref = points, None
 
     def configure(self):
         raise RuntimeError("a MapBatch session is configured through MapBatch.configure")
@@ -771,6 +837,9 @@ class MapBatch(object):
         self._h = h
         self.maps = maps
         self._geoms = {}
+        self._hit_tabs = {}
+        # the store feed since configure() / reset(): points fed, points the device left to the host, calls
+        self.feed_stats = {"points": 0, "undecided": 0, "calls": 0}
 
     reset = configure
 
@@ -898,6 +967,92 @@ class MapBatch(object):
             _L.ptr(i32(hrhc), C.c_int32), _L.ptr(i32(k_off), C.c_int32), _L.ptr(ktab, C.c_float), len(ktab),
             _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
             float(hit32), float(logit(hit32))))
+
+    def add_keyframes_store(self, sessions, keys, poses, pings, store, handles):
+        """``add_keyframes(sessions, keys, poses, pings, store.read_many(handles))``, bit for bit, without the clouds
+        leaving the device: the outlier filter, the hit cells and the measurement of every listed session run from the
+        store's pool (``store``: a CloudStore of this batch's context, ``handles[i]`` the cloud of ``sessions[i]``).
+
+        The device decides a point's bearing column only inside a guard band (``guard_margin``); the few points it leaves
+        undecided come back and go through ``_hit_indices`` here (``feed_stats`` counts them).  With ``pub_occupancy2``,
+        ``maps[s].point_cloud`` is read from the store on access: the handle must still be live then."""
+        handles = [int(h) for h in np.asarray(handles).reshape(-1)]
+        sessions, pings = self._begin("add_keyframes_store", sessions, keys, poses, pings, handles)
+        if getattr(store, "ctx", None) is not self.ctx:
+            raise ValueError("MapBatch.add_keyframes_store: the store belongs to another context")
+        with self._geometry_guard(sessions):
+            kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            self._measure_store(sessions, kfs, store, handles)
+        for v in self.maps:
+            v._meas_job = -1
+        for j, (s, h) in enumerate(zip(sessions, handles)):
+            self.maps[s]._meas_job = j
+            if self.pub_occupancy2:
+                self.maps[s]._cloud_ref = (store, h)
+        self._end(sessions, keys, kfs)
+
+    def _hit_table(self, v):
+        """the device's copy of what _hit_indices reads of session map v's sonar geometry, stored once per geometry"""
+        key = v._hit_key
+        if key not in self._hit_tabs:
+            o = v.oculus
+            breaks, coef = spline_table(o)
+            bearings = np.ascontiguousarray(o.bearings, np.float32)
+            wide = np.result_type(np.float32, o.range_resolution) == np.float64     # ra / res of float32 ranges
+            tid = C.c_int(0)
+            self._check(self._lib.sfe_mapset_hit_table(
+                self._h, _L.ptr(bearings, C.c_float), len(bearings), _L.ptr(breaks, C.c_double), _L.ptr(coef, C.c_double),
+                len(coef), guard_margin(o, breaks, coef), int(o.num_ranges), float(o.range_resolution), int(wide),
+                int(v.oculus_r_skip), int(v.oculus_c_skip), C.byref(tid)))
+            self._hit_tabs[key] = tid.value
+        return self._hit_tabs[key]
+
+    def _measure_store(self, sessions, kfs, store, handles):
+        n = len(sessions)
+        tabs, hrhc, k_off, div, ktabs, ktab_at, n_k = [], [], [], [], [], {}, 0
+        for s in sessions:
+            v = self.maps[s]
+            tabs.append(self._hit_table(v))
+            hr, hc = v._hit_halves()
+            _, ktab, d = v._measure_args(np.zeros((0, 2), np.int32), hr, hc)
+            if (hr, hc) not in ktab_at:
+                ktab_at[(hr, hc)] = n_k
+                ktabs.append(ktab)
+                n_k += len(ktab)
+            hrhc.append((hr, hc))
+            k_off.append(ktab_at[(hr, hc)])
+            div.append(d)
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
+        ktab = np.ascontiguousarray(np.concatenate(ktabs), np.float32)
+        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
+        n_pts, n_und = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        with self.ctx.lock:        # the store's slot table and the context's pinned staging
+            self._check(self._lib.sfe_mapset_measure_store(
+                self._h, store.handle, n, _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
+                _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(i32(handles), C.c_int32), _L.ptr(i32(tabs), C.c_int32),
+                float(self.outlier_filter_radius), int(self.outlier_filter_min_points), _L.ptr(i32(hrhc), C.c_int32),
+                _L.ptr(i32(k_off), C.c_int32), _L.ptr(ktab, C.c_float), len(ktab),
+                _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
+                float(hit32), float(logit(hit32)), _L.ptr(n_pts, C.c_int32), _L.ptr(n_und, C.c_int32)))
+            total = int(n_und.sum())
+            if total:
+                # phase two: the undecided points through _hit_indices, per sonar geometry, then the measurement
+                xy, pos = np.zeros((total, 2), np.float32), np.zeros(total, np.int32)
+                self._check(self._lib.sfe_mapset_measure_store_undecided(self._h, _L.ptr(xy, C.c_float),
+                                                                         _L.ptr(pos, C.c_int32), total))
+                job = np.searchsorted(np.cumsum(n_pts), pos, side="right")
+                cells = np.zeros((total, 2), np.int32)
+                groups = {}
+                for i, j in enumerate(job):
+                    groups.setdefault(self.maps[sessions[j]]._hit_key, []).append(i)
+                for idx in groups.values():
+                    v = self.maps[sessions[job[idx[0]]]]
+                    cells[idx] = v._hit_indices(xy[idx])[0]
+                self._check(self._lib.sfe_mapset_measure_store_finish(self._h, total, _L.ptr(pos, C.c_int32),
+                                                                      _L.ptr(np.ascontiguousarray(cells), C.c_int32)))
+        self.feed_stats["points"] += int(n_pts.sum())
+        self.feed_stats["undecided"] += total
+        self.feed_stats["calls"] += 1
 
     def add_keyframes_logodds(self, sessions, keys, poses, pings, logodds):
         """Mapping.add_keyframe_logodds for each listed session"""

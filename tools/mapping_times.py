@@ -16,7 +16,17 @@ alternated call by call, the median of the repetitions:
                          `--reps` times (the poses alternate between two sets)
   ratio                  looped / lock-step
 
+With `--feed host|store` only the map feed of a lock-step session is timed, under "feed": what chained.SessionBatch does at
+the end of every step for S sessions whose keyframe clouds lie in a CloudStore -- `host`: store.read_many + add_keyframes
+(the clouds cross to the host and back), `store`: add_keyframes_store (they stay on the device) -- over `--batch-keyframes`
+steps, the first left out:
+  step_ms                the median per step, host synchronised
+  points, undecided      points fed, and those the device left to the host (store feed)
+  readbacks_per_step     host read-backs of the measurement per step (the fit's bounds come on top on both routes)
+  grid_sha               sha256 of every session's final grid: equal between the two feeds
+
     python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
+    python tools/mapping_times.py --sessions 32 --feed store
 """
 import argparse
 import json
@@ -125,6 +135,52 @@ def lockstep(ctx, ping, settings, S, K, reps):
     return out
 
 
+def feed(ctx, ping, settings, S, K, route):
+    """the per-step map feed of S sessions from a CloudStore by one route -> the "feed" record"""
+    import hashlib
+    from sonar_slam_amd.store import CloudStore
+    poses, clouds = session(K)
+    pose = lambda s, k: Pose2(poses[k][0] + s, poses[k][1], poses[k][2])
+    store = CloudStore(ctx, capacity_points=S * K * 512, max_clouds=S * K)
+    # session s sees the session's cloud turned a little, so that no two clouds are equal
+    handles = np.array([[store.put(clouds[k].dot(np.array([[np.cos(0.002 * s), np.sin(0.002 * s)],
+                                                            [-np.sin(0.002 * s), np.cos(0.002 * s)]])))
+                         for k in range(K)] for s in range(S)], np.int32)
+    batch = MapBatch(ctx, S, K, **settings)
+    batch.configure()
+    sessions = list(range(S))
+    times, und = [], 0
+    for k in range(K):
+        args = (sessions, [k] * S, [pose(s, k) for s in sessions], ping)
+
+        def step():
+            if route == "store":
+                batch.add_keyframes_store(*args, store, handles[:, k])
+            else:
+                batch.add_keyframes(*args, store.read_many(handles[:, k]))
+            ctx.sync()
+        before = batch.feed_stats["undecided"]
+        t = timed(step)
+        und += batch.feed_stats["undecided"] > before
+        if k:                       # step 0: geometry upload, first allocations
+            times.append(t)
+    h = hashlib.sha256()
+    for v in batch.maps:
+        h.update(v.logodds_grid.tobytes())
+    stats = batch.feed_stats
+    if route == "store":
+        # the undecided counters every step, the undecided points on the steps that have some
+        readbacks = 1.0 + und / float(K)
+    else:
+        readbacks = 2.0             # the clouds (read_many), the keep flags of the outlier filter
+    out = {"route": route, "sessions": S, "steps": K, "step_ms": float(np.median(times)), "step_ms_min": float(np.min(times)),
+           "points": int(store.counts(handles.ravel()).sum()), "undecided": stats["undecided"], "fed_points": stats["points"],
+           "readbacks_per_step": readbacks, "grid_sha": h.hexdigest()}
+    batch.close()
+    store.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
@@ -132,10 +188,16 @@ def main():
     ap.add_argument("--sessions", type=int, default=32)
     ap.add_argument("--batch-keyframes", type=int, default=40)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--feed", choices=("host", "store"), default=None)
     a = ap.parse_args()
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
     settings = dict(x0=-100.0, y0=-100.0, width=200.0, height=200.0)
+    if a.feed is not None:
+        ctx = _lib.default_context()
+        print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
+                          "feed": feed(ctx, ping, settings, max(a.sessions, 1), a.batch_keyframes, a.feed)}))
+        return
     poses, clouds = session(n)
     ctx = _lib.default_context()
 
