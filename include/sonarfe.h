@@ -656,7 +656,12 @@ int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_
  *     sfe_map_shape -> {rows, cols, rows grown on top, columns grown on the left}.
  *   sfe_map_frames: a fresh grid, the listed slots added in list order.  sfe_map_render: rows r0..r1 x cols c0..c1 of a grid
  *     -> int8(clip(100 expit(v), 0, 100)), resized INTER_NEAREST to out_h x out_w with source index floor(i * inv) when
- *     resize != 0. */
+ *     resize != 0.
+ *   sfe_map_hit_table / sfe_map_measure_store / sfe_map_measure_store_undecided / sfe_map_measure_store_finish: the store
+ *     feed of one map.  Their contract is that of the sfe_mapset_* calls of the same names, below, with the `maps` argument
+ *     dropped: the same device routines decide the same points.  n keyframes of the map per call, each slot at most once.
+ *     A slot that holds an image of another geometry, an unknown geometry or a negative slot is refused with SFE_ERR_ARG, as
+ *     by sfe_map_measure; a slot is created only when its measurement runs, so a refused or dropped call leaves none behind. */
 typedef struct sfe_map sfe_map;
 int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out);
 void sfe_map_destroy(sfe_map *m);
@@ -666,6 +671,15 @@ int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geom
                     const int32_t *hits, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
                     const double *div, float miss32, float logit_miss, float hit32, float logit_hit);
 int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out);
+int sfe_map_hit_table(sfe_map *m, const float *bearings, int num_bearings, const double *breaks, const double *coef,
+                      int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double, int r_skip,
+                      int c_skip, int *id_out);
+int sfe_map_measure_store(sfe_map *m, sfe_cloud_store *store, int n, const int32_t *slots, const int32_t *geoms,
+                          const int32_t *handles, const int32_t *tabs, double radius, int min_points, const int32_t *hrhc,
+                          const int32_t *k_off, const float *ktab, int n_ktab, const double *div, float miss32,
+                          float logit_miss, float hit32, float logit_hit, int32_t *n_points_out, int32_t *n_undecided_out);
+int sfe_map_measure_store_undecided(sfe_map *m, float *xy_out, int32_t *pos_out, int cap);
+int sfe_map_measure_store_finish(sfe_map *m, int n_cells, const int32_t *pos, const int32_t *cells);
 int sfe_map_fit_bounds(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
                        double resolution, int32_t *mm_out);
 int sfe_map_grow(sfe_map *m, int top, int bottom, int left, int right);

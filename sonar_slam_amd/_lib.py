@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SONARFE_LIB: load another build of the same library (kernel A/B runs inside one process pool / one GPU call)
 LIB_PATH = os.environ.get("SONARFE_LIB") or os.path.join(_HERE, "libsonarfe.so")
 
+SFE_ERR_ARG = -1
 SFE_ERR_CAP = -4
 
 # the kernel the ICP launcher gave a job (SFE_ICP_ROUTE_* in include/sonarfe.h; Context.icp_routes)
@@ -266,6 +267,12 @@ SIGNATURES = {
     "sfe_map_measure": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, C.c_int, _f64p,
                                   C.c_float, C.c_float, C.c_float, C.c_float]),
     "sfe_map_measure_stages": (C.c_int, [_vp, C.c_int, _u8p, _f32p, _i32p]),
+    "sfe_map_hit_table": (C.c_int, [_vp, _f32p, C.c_int, _f64p, _f64p, C.c_int, C.c_double, C.c_int, C.c_double, C.c_int,
+                                    C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_map_measure_store": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_double, C.c_int, _i32p, _i32p,
+                                        _f32p, C.c_int, _f64p, C.c_float, C.c_float, C.c_float, C.c_float, _i32p, _i32p]),
+    "sfe_map_measure_store_undecided": (C.c_int, [_vp, _f32p, _i32p, C.c_int]),
+    "sfe_map_measure_store_finish": (C.c_int, [_vp, C.c_int, _i32p, _i32p]),
     "sfe_map_fit_bounds": (C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, C.c_double, _i32p]),
     "sfe_map_grow": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
     "sfe_map_refit": (C.c_int, [_vp, C.c_int, _i32p, _f64p, _f64p, C.c_double, _i32p, _i32p, _u8p]),

@@ -65,6 +65,44 @@ struct FitJob {
     int32_t *out_n;
 };
 
+struct FeedJob {
+    long long off;
+    int32_t n, hit_off, tab;
+};
+// what Mapping._hit_indices reads of a sonar geometry and its skips
+struct HitTab {
+    const double *breaks; // [n_iv + 1] ascending: the knots of oculus.b2c's cubic spline
+    const double *coef;   // [n_iv][4]: its cubic on [breaks[k], breaks[k + 1]) in powers of (a - breaks[k]), highest first
+    int32_t n_iv, num_ranges, num_bearings, r_skip, c_skip;
+    int32_t wide;         // ra / range_resolution - 1 in float64 (a numpy float64 scalar resolution), else in float32
+    float res32;
+    double res64, b_first, b_last, margin;
+};
+struct UndPoint {
+    float x, y;
+    int32_t pos, job; // its entry in the hit buffer
+};
+
+// the store feed of one owner (an sfe_map or an sfe_mapset): the call that waits for the host's cells
+struct FeedState {
+    bool pending = false;
+    std::vector<int32_t> maps, slots, geoms, n_und; // (maps: empty for an sfe_map)
+    std::vector<MeasJob> jobs;
+    std::vector<float> ktab;
+    float miss32 = 0, logit_miss = 0, hit32 = 0, logit_hit = 0;
+    int tot = 0, tot_und = 0;
+};
+
+// ---- what the measurement and the store feed need of their owner: an sfe_map and an sfe_mapset number their scratch alike
+struct FeedView {
+    sfe_ctx *ctx;
+    MapBuf *buf; // [11]
+    std::vector<HitTab> *hit_tabs;
+    FeedState *feed;
+    std::vector<MeasJob> *last_meas;
+    int *last_meas_n;
+};
+
 } // namespace
 
 struct sfe_map {
@@ -78,12 +116,18 @@ struct sfe_map {
     std::vector<MapSlot> slots;
     int32_t *d_counts = nullptr; // [slot][2]: cell count of each list buffer
     int counts_cap = 0;
-    MapBuf buf[6];
+    MapBuf buf[11]; // 0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's (as sfe_mapset's)
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
+    std::vector<HitTab> hit_tabs; // device copies owned here
+    FeedState feed;
 };
 
 namespace {
+
+FeedView map_view(sfe_map *m);
+int measure_run(const FeedView &v, const std::vector<MeasJob> &jobs, const int32_t *d_hits, const float *ktab, int n_ktab,
+                float miss32, float logit_miss, float hit32, float logit_hit);
 
 // grow-only device scratch
 void *buf_get(sfe_ctx *ctx, MapBuf &b, size_t bytes)
@@ -108,6 +152,37 @@ void *buf_get(sfe_ctx *ctx, MapBuf &b, size_t bytes)
 void *map_buf(sfe_map *m, int i, size_t bytes)
 {
     return buf_get(m->ctx, m->buf[i], bytes);
+}
+
+// n values from pageable host memory (the caller synchronises before the host array goes away)
+template <class T>
+T *buf_upload(sfe_ctx *ctx, MapBuf &b, const T *h, size_t n)
+{
+    T *d = (T *)buf_get(ctx, b, sizeof(T) * (n ? n : 1));
+    if (!d)
+        return nullptr;
+    if (n && hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        return nullptr;
+    return d;
+}
+
+// a job table through pinned staging: enqueue only
+template <class T>
+T *buf_stage(sfe_ctx *ctx, MapBuf &b, const std::vector<T> &jobs)
+{
+    const size_t bytes = sizeof(T) * jobs.size();
+    T *d = (T *)buf_get(ctx, b, bytes ? bytes : 1);
+    if (!d || !bytes)
+        return d;
+    void *pin = sfe_pinned_begin(ctx, bytes);
+    if (!pin)
+        return nullptr;
+    memcpy(pin, jobs.data(), bytes);
+    if (hipMemcpyAsync(d, pin, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        return nullptr;
+    if (sfe_pinned_end(ctx, ctx->stream))
+        return nullptr;
+    return d;
 }
 
 // --- measurement (mapping.py:170-228) ---------------------------------------------------------------------------------
@@ -391,12 +466,7 @@ int map_slot(sfe_map *m, int slot, int g)
 template <class T>
 T *map_upload(sfe_map *m, int i, const T *h, size_t n)
 {
-    T *d = (T *)map_buf(m, i, sizeof(T) * (n ? n : 1));
-    if (!d)
-        return nullptr;
-    if (n && hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, m->ctx->stream) != hipSuccess)
-        return nullptr;
-    return d;
+    return buf_upload(m->ctx, m->buf[i], h, n);
 }
 
 } // namespace
@@ -440,6 +510,8 @@ void sfe_map_destroy(sfe_map *m)
     }
     for (auto &b : m->buf)
         (void)hipFree(b.p);
+    for (auto &t : m->hit_tabs)
+        (void)hipFree((void *)t.breaks); // (breaks and coef are one block)
     delete m;
 }
 
@@ -488,9 +560,9 @@ int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geom
     SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && geoms && hit_off && hrhc && k_off && div)) && n_ktab >= 0);
     if (n == 0)
         return 0;
+    m->feed.pending = false;
     std::vector<MeasJob> jobs(n);
     int64_t px = 0;
-    int max_px = 0, max_cols = 0;
     for (int b = 0; b < n; ++b) {
         if (int rc = map_slot(m, slots[b], geoms[b]))
             return rc;
@@ -511,33 +583,11 @@ int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geom
         j.px_off = px;
         j.logodds = m->slots[slots[b]].d_logodds;
         px += j.slot_px;
-        max_px = max(max_px, j.slot_px);
-        max_cols = max(max_cols, j.img_cols);
     }
     const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
     SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
-    MeasJob *d_jobs = map_upload(m, 0, jobs.data(), jobs.size());
     int32_t *d_hits = map_upload(m, 1, hits, 2 * (size_t)(n_hit_tot - 1));
-    float *d_k = map_upload(m, 2, ktab, (size_t)n_ktab);
-    uint8_t *d_mask = (uint8_t *)map_buf(m, 3, (size_t)px);
-    float *d_prob = (float *)map_buf(m, 4, sizeof(float) * (size_t)px);
-    int32_t *d_fh = (int32_t *)map_buf(m, 5, sizeof(int32_t) * (size_t)n * max_cols);
-    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map measurement scratch allocation / upload failed");
-    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
-    const unsigned ny = (unsigned)n;
-    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
-                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
-                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
-    m->last_meas = jobs;
-    m->last_meas_n = max_cols;
-    return 0;
+    return measure_run(map_view(m), jobs, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit);
 }
 
 int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
@@ -970,24 +1020,6 @@ __global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__
 // --- the store feed: a keyframe's hits straight from its cloud in a cloud store (mapping.py: MapBatch.add_keyframes_store) ----
 // One job = one cloud (pool offset, size) for one (map, slot); its points own the entries [hit_off, hit_off + n) of the call's
 // hit buffer, one (row, column) pair per point, (-1, -1) for a point that leaves no hit (map_hits_kernel skips those).
-struct FeedJob {
-    long long off;
-    int32_t n, hit_off, tab;
-};
-// what Mapping._hit_indices reads of a sonar geometry and its skips
-struct HitTab {
-    const double *breaks; // [n_iv + 1] ascending: the knots of oculus.b2c's cubic spline
-    const double *coef;   // [n_iv][4]: its cubic on [breaks[k], breaks[k + 1]) in powers of (a - breaks[k]), highest first
-    int32_t n_iv, num_ranges, num_bearings, r_skip, c_skip;
-    int32_t wide;         // ra / range_resolution - 1 in float64 (a numpy float64 scalar resolution), else in float32
-    float res32;
-    double res64, b_first, b_last, margin;
-};
-struct UndPoint {
-    float x, y;
-    int32_t pos, job; // its entry in the hit buffer
-};
-
 // the outlier filter of every job's cloud: keep[hit_off + i]
 __global__ __launch_bounds__(256) void feed_radius_count_kernel(const float2 *__restrict__ pool, const FeedJob *__restrict__ jobs,
                                                                 float r2, int min_points, uint8_t *__restrict__ keep)
@@ -1085,6 +1117,250 @@ __global__ void feed_fill_kernel(const int32_t *__restrict__ pos, const int32_t 
     }
 }
 
+// the measurement of a call's jobs from its hits on the device (one pair per entry; a pair outside the image leaves no
+// hit): mask, filter, columns; one synchronisation
+int measure_run(const FeedView &v, const std::vector<MeasJob> &jobs, const int32_t *d_hits, const float *ktab, int n_ktab,
+                float miss32, float logit_miss, float hit32, float logit_hit)
+{
+    sfe_ctx *ctx = v.ctx;
+    const int n = (int)jobs.size();
+    int64_t px = 0;
+    int max_px = 0, max_cols = 0;
+    for (const MeasJob &j : jobs) {
+        px += j.slot_px;
+        max_px = max(max_px, j.slot_px);
+        max_cols = max(max_cols, j.img_cols);
+    }
+    MeasJob *d_jobs = buf_upload(ctx, v.buf[0], jobs.data(), jobs.size());
+    float *d_k = buf_upload(ctx, v.buf[2], ktab, (size_t)n_ktab);
+    uint8_t *d_mask = (uint8_t *)buf_get(ctx, v.buf[3], (size_t)px);
+    float *d_prob = (float *)buf_get(ctx, v.buf[4], sizeof(float) * (size_t)px);
+    int32_t *d_fh = (int32_t *)buf_get(ctx, v.buf[5], sizeof(int32_t) * (size_t)n * max_cols);
+    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map measurement scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
+    const unsigned ny = (unsigned)n;
+    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
+                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
+                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
+    *v.last_meas = jobs;
+    *v.last_meas_n = max_cols;
+    return 0;
+}
+
+// sfe_map_hit_table / sfe_mapset_hit_table
+int feed_hit_table(const FeedView &v, const float *bearings, int num_bearings, const double *breaks, const double *coef,
+                   int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double, int r_skip,
+                   int c_skip, int *id_out)
+{
+    sfe_ctx *ctx = v.ctx;
+    SFE_ARG(ctx, bearings && breaks && coef && id_out && num_bearings >= 2 && n_intervals >= 1 && n_intervals < (1 << 20));
+    SFE_ARG(ctx, margin > 0 && num_ranges >= 1 && range_resolution > 0 && r_skip >= 1 && c_skip >= 1);
+    for (int k = 0; k < n_intervals; ++k)
+        SFE_ARG(ctx, breaks[k] < breaks[k + 1]);
+    SFE_ARG(ctx, breaks[0] <= (double)bearings[0] && (double)bearings[num_bearings - 1] <= breaks[n_intervals]);
+    SFE_ARG(ctx, bearings[0] < bearings[num_bearings - 1]);
+    HitTab t;
+    double *d = nullptr;
+    const size_t nb = (size_t)n_intervals + 1, nc = 4 * (size_t)n_intervals;
+    SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(double) * (nb + nc)));
+    if (hipMemcpy(d, breaks, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nb, coef, sizeof(double) * nc, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map hit table upload failed");
+    }
+    t.breaks = d, t.coef = d + nb;
+    t.n_iv = n_intervals, t.num_ranges = num_ranges, t.num_bearings = num_bearings, t.r_skip = r_skip, t.c_skip = c_skip;
+    t.wide = range_in_double ? 1 : 0;
+    t.res32 = (float)range_resolution, t.res64 = range_resolution;
+    t.b_first = (double)bearings[0], t.b_last = (double)bearings[num_bearings - 1], t.margin = margin;
+    v.hit_tabs->push_back(t);
+    *id_out = (int)v.hit_tabs->size() - 1;
+    return 0;
+}
+
+// Phase one of a store-fed measurement (sonarfe.h: sfe_mapset_measure_store).  `slot_job(b, job)` is the owner's part: it
+// checks that keyframe b's slot may take an image of its geometry and fills the job's image size (and its log-odds image,
+// if the slot has one yet).  Nothing of the owner has changed when this returns, pending or not.
+template <class SlotJob>
+int feed_measure_store(const FeedView &fv, const char *who, sfe_cloud_store *store, int n, const int32_t *maps,
+                       const int32_t *slots, const int32_t *geoms, const int32_t *handles, const int32_t *tabs, double radius,
+                       int min_points, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
+                       const double *div, float miss32, float logit_miss, float hit32, float logit_hit, int32_t *n_points_out,
+                       int32_t *n_undecided_out, SlotJob slot_job)
+{
+    sfe_ctx *ctx = fv.ctx;
+    SFE_ARG(ctx, store && sfe_store_ctx(store) == ctx && n >= 0 && n <= 65535 && n_ktab >= 0 && (n_ktab == 0 || ktab));
+    SFE_ARG(ctx, n == 0 || (slots && geoms && handles && tabs && hrhc && k_off && div && n_points_out && n_undecided_out));
+    SFE_ARG(ctx, min_points <= 1 || radius >= 0);
+    FeedState &f = *fv.feed;
+    f.pending = false;
+    if (n == 0)
+        return 0;
+    SfeStoreView v;
+    if (int rc = sfe_store_view(store, &v))
+        return rc;
+    std::vector<MeasJob> jobs(n);
+    std::vector<FeedJob> fjobs(n);
+    int64_t px = 0, tot = 0;
+    int max_n = 0;
+    for (int b = 0; b < n; ++b) {
+        MeasJob &j = jobs[b];
+        j.logodds = nullptr;
+        if (int rc = slot_job(b, j))
+            return rc;
+        const int hd = handles[b];
+        if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "%s: cloud %d named (job %d), the store holds %d%s", who, hd, b, v.n_slots,
+                               (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
+        SFE_ARG(ctx, tabs[b] >= 0 && tabs[b] < (int)fv.hit_tabs->size());
+        const int cnt = v.cnt[hd];
+        j.hit_off = (int32_t)tot;
+        j.n_hits = cnt;
+        // a cloud without points is a keyframe without a measurement (hr < 0); one the filter empties keeps its kernel
+        j.hr = cnt ? hrhc[2 * b] : -1, j.hc = cnt ? hrhc[2 * b + 1] : 0;
+        j.k_off = cnt ? k_off[b] : 0;
+        j.div = cnt ? div[b] : 1.0;
+        SFE_ARG(ctx, j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
+        SFE_ARG(ctx, cnt == 0 || (j.hr >= 0 && j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab));
+        j.px_off = px;
+        px += j.slot_px;
+        fjobs[b].off = v.off[hd], fjobs[b].n = cnt, fjobs[b].hit_off = (int32_t)tot, fjobs[b].tab = tabs[b];
+        tot += cnt;
+        max_n = max(max_n, cnt);
+        SFE_ARG(ctx, tot < (1 << 30));
+    }
+    FeedJob *d_jobs = buf_stage(ctx, fv.buf[6], fjobs);
+    HitTab *d_tabs = buf_stage(ctx, fv.buf[10], *fv.hit_tabs);
+    int32_t *d_hits = (int32_t *)buf_get(ctx, fv.buf[7], sizeof(int32_t) * 2 * (size_t)(tot + 1));
+    uint8_t *d_keep = (uint8_t *)buf_get(ctx, fv.buf[8], (size_t)(tot + 1));
+    char *d_und = (char *)buf_get(ctx, fv.buf[9], sizeof(UndPoint) * (size_t)tot + sizeof(int32_t) * (size_t)n);
+    int32_t *h_cnt = (int32_t *)sfe_pinned_io(ctx, 3, sizeof(int32_t) * (size_t)n);
+    if (!d_jobs || !d_tabs || !d_hits || !d_keep || !d_und || !h_cnt)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "%s store feed scratch allocation / upload failed", who);
+    int32_t *d_cnt = (int32_t *)(d_und + sizeof(UndPoint) * (size_t)tot);
+    SFE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)n, ctx->stream));
+    if (max_n > 0) {
+        const dim3 grid((unsigned)((max_n + 255) / 256), (unsigned)n);
+        const bool filter = min_points > 1; // Mapping._hits
+        if (filter) {
+            hipLaunchKernelGGL(feed_radius_count_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs,
+                               (float)(radius * radius), min_points, d_keep);
+            SFE_LAUNCH_CHECK(ctx);
+        }
+        hipLaunchKernelGGL(feed_hit_cells_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs, d_tabs,
+                           filter ? (const uint8_t *)d_keep : nullptr, d_hits, (UndPoint *)d_und, d_cnt);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (maps)
+        f.maps.assign(maps, maps + n);
+    else
+        f.maps.clear();
+    f.slots.assign(slots, slots + n), f.geoms.assign(geoms, geoms + n);
+    f.n_und.assign(h_cnt, h_cnt + n);
+    f.jobs = jobs;
+    f.ktab.assign(ktab, ktab + n_ktab);
+    f.miss32 = miss32, f.logit_miss = logit_miss, f.hit32 = hit32, f.logit_hit = logit_hit;
+    f.tot = (int)tot, f.tot_und = 0;
+    for (int b = 0; b < n; ++b) {
+        n_points_out[b] = jobs[b].n_hits;
+        n_undecided_out[b] = h_cnt[b];
+        f.tot_und += h_cnt[b];
+    }
+    f.pending = true; // until the owner runs the measurement: at once if no point is undecided
+    return 0;
+}
+
+// the undecided points of the pending call, by ascending entry in the hit buffer
+int feed_undecided(const FeedView &fv, float *xy_out, int32_t *pos_out, int cap)
+{
+    sfe_ctx *ctx = fv.ctx;
+    FeedState &f = *fv.feed;
+    SFE_ARG(ctx, f.pending && xy_out && pos_out && cap >= f.tot_und);
+    std::vector<UndPoint> und((size_t)f.tot_und);
+    size_t at = 0;
+    for (size_t b = 0; b < f.jobs.size(); ++b) {
+        if (!f.n_und[b])
+            continue;
+        SFE_HIP(ctx, hipMemcpyAsync(und.data() + at, (const UndPoint *)fv.buf[9].p + f.jobs[b].hit_off,
+                                    sizeof(UndPoint) * (size_t)f.n_und[b], hipMemcpyDeviceToHost, ctx->stream));
+        at += (size_t)f.n_und[b];
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // (the device appended them in no fixed order)
+    std::sort(und.begin(), und.end(), [](const UndPoint &a, const UndPoint &b) { return a.pos < b.pos; });
+    for (size_t i = 0; i < und.size(); ++i) {
+        xy_out[2 * i] = und[i].x, xy_out[2 * i + 1] = und[i].y;
+        pos_out[i] = und[i].pos;
+    }
+    return 0;
+}
+
+// the host's cells of the pending call's undecided points into the hit buffer
+int feed_fill(const FeedView &fv, int n_cells, const int32_t *pos, const int32_t *cells)
+{
+    sfe_ctx *ctx = fv.ctx;
+    FeedState &f = *fv.feed;
+    SFE_ARG(ctx, f.pending && n_cells == f.tot_und && pos && cells);
+    for (int i = 0; i < n_cells; ++i)
+        SFE_ARG(ctx, pos[i] >= 0 && pos[i] < f.tot);
+    // (the keep flags have been read: their buffer takes the upload)
+    std::vector<int32_t> up(3 * (size_t)n_cells);
+    memcpy(up.data(), pos, sizeof(int32_t) * (size_t)n_cells);
+    memcpy(up.data() + n_cells, cells, sizeof(int32_t) * 2 * (size_t)n_cells);
+    int32_t *d_up = buf_stage(ctx, fv.buf[8], up);
+    if (!d_up)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map store feed: upload of the host's cells failed");
+    hipLaunchKernelGGL(feed_fill_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, d_up,
+                       d_up + n_cells, n_cells, (int32_t *)fv.buf[7].p);
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+// the second half of a store-fed measurement: every entry of the hit buffer is final
+int feed_finish(const FeedView &fv)
+{
+    FeedState &f = *fv.feed;
+    f.pending = false;
+    return measure_run(fv, f.jobs, (const int32_t *)fv.buf[7].p, f.ktab.data(), (int)f.ktab.size(), f.miss32, f.logit_miss,
+                       f.hit32, f.logit_hit);
+}
+
+FeedView map_view(sfe_map *m)
+{
+    return FeedView{m->ctx, m->buf, &m->hit_tabs, &m->feed, &m->last_meas, &m->last_meas_n};
+}
+
+// may `slot` take an image of geometry g?  Checks only (map_slot creates).
+int map_slot_check(sfe_map *m, int slot, int g)
+{
+    SFE_ARG(m->ctx, slot >= 0 && g >= 0 && g < (int)m->geoms.size());
+    SFE_ARG(m->ctx, slot >= (int)m->slots.size() || !m->slots[slot].d_logodds || m->slots[slot].geom == g);
+    return 0;
+}
+
+// the pending call's slots come into being, then its measurement runs
+int map_feed_finish(sfe_map *m)
+{
+    FeedState &f = m->feed;
+    for (size_t b = 0; b < f.jobs.size(); ++b) {
+        if (int rc = map_slot(m, f.slots[b], f.geoms[b])) {
+            f.pending = false;
+            return rc;
+        }
+        f.jobs[b].logodds = m->slots[f.slots[b]].d_logodds;
+    }
+    return feed_finish(map_view(m));
+}
+
 } // namespace
 
 struct sfe_mapset {
@@ -1102,14 +1378,7 @@ struct sfe_mapset {
     long long apply_launches = 0; // launches of mapset_apply_kernel so far
     // the store feed: hit tables (device copies owned here), and the call that waits for the host's cells
     std::vector<HitTab> hit_tabs;
-    struct Feed {
-        bool pending = false;
-        std::vector<int32_t> maps, slots, geoms, n_und;
-        std::vector<MeasJob> jobs;
-        std::vector<float> ktab;
-        float miss32 = 0, logit_miss = 0, hit32 = 0, logit_hit = 0;
-        int tot = 0, tot_und = 0;
-    } feed;
+    FeedState feed;
 };
 
 namespace {
@@ -1149,35 +1418,16 @@ int set_slot_used(sfe_mapset *ms, int map, int slot)
     return 0;
 }
 
-// a job table through pinned staging: enqueue only
 template <class T>
 T *set_stage(sfe_mapset *ms, int i, const std::vector<T> &jobs)
 {
-    sfe_ctx *ctx = ms->ctx;
-    const size_t bytes = sizeof(T) * jobs.size();
-    T *d = (T *)buf_get(ctx, ms->buf[i], bytes ? bytes : 1);
-    if (!d || !bytes)
-        return d;
-    void *pin = sfe_pinned_begin(ctx, bytes);
-    if (!pin)
-        return nullptr;
-    memcpy(pin, jobs.data(), bytes);
-    if (hipMemcpyAsync(d, pin, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-        return nullptr;
-    if (sfe_pinned_end(ctx, ctx->stream))
-        return nullptr;
-    return d;
+    return buf_stage(ms->ctx, ms->buf[i], jobs);
 }
 
 template <class T>
 T *set_upload(sfe_mapset *ms, int i, const T *h, size_t n)
 {
-    T *d = (T *)buf_get(ms->ctx, ms->buf[i], sizeof(T) * (n ? n : 1));
-    if (!d)
-        return nullptr;
-    if (n && hipMemcpyAsync(d, h, sizeof(T) * n, hipMemcpyHostToDevice, ms->ctx->stream) != hipSuccess)
-        return nullptr;
-    return d;
+    return buf_upload(ms->ctx, ms->buf[i], h, n);
 }
 
 int set_fit_jobs(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4, const double *origin2,
@@ -1227,50 +1477,27 @@ int set_run_rounds(sfe_mapset *ms, int buf, const std::vector<std::vector<ApplyJ
     return 0;
 }
 
-// the measurement of a call's jobs from its hits on the device (one pair per entry; a pair outside the image leaves no
-// hit): mask, filter, columns; one synchronisation; then the slots take their geometries
+FeedView set_view(sfe_mapset *ms)
+{
+    return FeedView{ms->ctx, ms->buf, &ms->hit_tabs, &ms->feed, &ms->last_meas, &ms->last_meas_n};
+}
+
+// the measurement of a call's jobs from its hits on the device; then the slots take their geometries
 int set_measure_run(sfe_mapset *ms, const std::vector<MeasJob> &jobs, const int32_t *maps, const int32_t *slots,
                     const int32_t *geoms, const int32_t *d_hits, const float *ktab, int n_ktab, float miss32, float logit_miss,
                     float hit32, float logit_hit)
 {
-    sfe_ctx *ctx = ms->ctx;
-    const int n = (int)jobs.size();
-    int64_t px = 0;
-    int max_px = 0, max_cols = 0;
-    for (const MeasJob &j : jobs) {
-        px += j.slot_px;
-        max_px = max(max_px, j.slot_px);
-        max_cols = max(max_cols, j.img_cols);
-    }
-    MeasJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
-    float *d_k = set_upload(ms, 2, ktab, (size_t)n_ktab);
-    uint8_t *d_mask = (uint8_t *)buf_get(ctx, ms->buf[3], (size_t)px);
-    float *d_prob = (float *)buf_get(ctx, ms->buf[4], sizeof(float) * (size_t)px);
-    int32_t *d_fh = (int32_t *)buf_get(ctx, ms->buf[5], sizeof(int32_t) * (size_t)n * max_cols);
-    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set measurement scratch allocation / upload failed");
-    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
-    const unsigned ny = (unsigned)n;
-    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
-                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
-                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
-    for (int b = 0; b < n; ++b)
+    if (int rc = measure_run(set_view(ms), jobs, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit))
+        return rc;
+    for (size_t b = 0; b < jobs.size(); ++b)
         ms->slots[set_idx(ms, maps[b], slots[b])].geom = geoms[b];
-    ms->last_meas = jobs;
-    ms->last_meas_n = max_cols;
     return 0;
 }
 
 // the second half of a store-fed measurement: every entry of the hit buffer is final
-int feed_finish(sfe_mapset *ms)
+int set_feed_finish(sfe_mapset *ms)
 {
-    sfe_mapset::Feed &f = ms->feed;
+    FeedState &f = ms->feed;
     f.pending = false;
     return set_measure_run(ms, f.jobs, f.maps.data(), f.slots.data(), f.geoms.data(), (const int32_t *)ms->buf[7].p,
                            f.ktab.data(), (int)f.ktab.size(), f.miss32, f.logit_miss, f.hit32, f.logit_hit);
@@ -1789,32 +2016,10 @@ int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings
 {
     if (!ms)
         return SFE_ERR_ARG;
-    sfe_ctx *ctx = ms->ctx;
-    if (int rc = sfe_use(ctx))
+    if (int rc = sfe_use(ms->ctx))
         return rc;
-    SFE_ARG(ctx, bearings && breaks && coef && id_out && num_bearings >= 2 && n_intervals >= 1 && n_intervals < (1 << 20));
-    SFE_ARG(ctx, margin > 0 && num_ranges >= 1 && range_resolution > 0 && r_skip >= 1 && c_skip >= 1);
-    for (int k = 0; k < n_intervals; ++k)
-        SFE_ARG(ctx, breaks[k] < breaks[k + 1]);
-    SFE_ARG(ctx, breaks[0] <= (double)bearings[0] && (double)bearings[num_bearings - 1] <= breaks[n_intervals]);
-    SFE_ARG(ctx, bearings[0] < bearings[num_bearings - 1]);
-    HitTab t;
-    double *d = nullptr;
-    const size_t nb = (size_t)n_intervals + 1, nc = 4 * (size_t)n_intervals;
-    SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(double) * (nb + nc)));
-    if (hipMemcpy(d, breaks, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + nb, coef, sizeof(double) * nc, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: hit table upload failed");
-    }
-    t.breaks = d, t.coef = d + nb;
-    t.n_iv = n_intervals, t.num_ranges = num_ranges, t.num_bearings = num_bearings, t.r_skip = r_skip, t.c_skip = c_skip;
-    t.wide = range_in_double ? 1 : 0;
-    t.res32 = (float)range_resolution, t.res64 = range_resolution;
-    t.b_first = (double)bearings[0], t.b_last = (double)bearings[num_bearings - 1], t.margin = margin;
-    ms->hit_tabs.push_back(t);
-    *id_out = (int)ms->hit_tabs.size() - 1;
-    return 0;
+    return feed_hit_table(set_view(ms), bearings, num_bearings, breaks, coef, n_intervals, margin, num_ranges,
+                          range_resolution, range_in_double, r_skip, c_skip, id_out);
 }
 
 int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slots,
@@ -1828,86 +2033,21 @@ int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, cons
     sfe_ctx *ctx = ms->ctx;
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, store && sfe_store_ctx(store) == ctx && n >= 0 && n <= 65535 && n_ktab >= 0 && (n_ktab == 0 || ktab));
-    SFE_ARG(ctx, n == 0 || (maps && slots && geoms && handles && tabs && hrhc && k_off && div && n_points_out && n_undecided_out));
-    SFE_ARG(ctx, min_points <= 1 || radius >= 0);
-    sfe_mapset::Feed &f = ms->feed;
-    f.pending = false;
-    if (n == 0)
-        return 0;
-    SfeStoreView v;
-    if (int rc = sfe_store_view(store, &v))
-        return rc;
-    std::vector<MeasJob> jobs(n);
-    std::vector<FeedJob> fjobs(n);
-    int64_t px = 0, tot = 0;
-    int max_n = 0;
-    for (int b = 0; b < n; ++b) {
+    SFE_ARG(ctx, n <= 0 || maps);
+    auto slot_job = [&](int b, MeasJob &j) {
         if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
             return rc;
-        const int hd = handles[b];
-        if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "map set: cloud %d named (job %d), the store holds %d%s", hd, b, v.n_slots,
-                               (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
-        SFE_ARG(ctx, tabs[b] >= 0 && tabs[b] < (int)ms->hit_tabs.size());
         const MapGeom &g = ms->geoms[geoms[b]];
-        const int cnt = v.cnt[hd];
-        MeasJob &j = jobs[b];
         j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
-        j.hit_off = (int32_t)tot;
-        j.n_hits = cnt;
-        // a cloud without points is a keyframe without a measurement (hr < 0); one the filter empties keeps its kernel
-        j.hr = cnt ? hrhc[2 * b] : -1, j.hc = cnt ? hrhc[2 * b + 1] : 0;
-        j.k_off = cnt ? k_off[b] : 0;
-        j.div = cnt ? div[b] : 1.0;
-        SFE_ARG(ctx, j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
-        SFE_ARG(ctx, cnt == 0 || (j.hr >= 0 && j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab));
-        j.px_off = px;
         j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
-        px += j.slot_px;
-        fjobs[b].off = v.off[hd], fjobs[b].n = cnt, fjobs[b].hit_off = (int32_t)tot, fjobs[b].tab = tabs[b];
-        tot += cnt;
-        max_n = max(max_n, cnt);
-        SFE_ARG(ctx, tot < (1 << 30));
-    }
-    FeedJob *d_jobs = set_stage(ms, 6, fjobs);
-    HitTab *d_tabs = set_stage(ms, 10, ms->hit_tabs);
-    int32_t *d_hits = (int32_t *)buf_get(ctx, ms->buf[7], sizeof(int32_t) * 2 * (size_t)(tot + 1));
-    uint8_t *d_keep = (uint8_t *)buf_get(ctx, ms->buf[8], (size_t)(tot + 1));
-    char *d_und = (char *)buf_get(ctx, ms->buf[9], sizeof(UndPoint) * (size_t)tot + sizeof(int32_t) * (size_t)n);
-    int32_t *h_cnt = (int32_t *)sfe_pinned_io(ctx, 3, sizeof(int32_t) * (size_t)n);
-    if (!d_jobs || !d_tabs || !d_hits || !d_keep || !d_und || !h_cnt)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set store feed scratch allocation / upload failed");
-    int32_t *d_cnt = (int32_t *)(d_und + sizeof(UndPoint) * (size_t)tot);
-    SFE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)n, ctx->stream));
-    if (max_n > 0) {
-        const dim3 grid((unsigned)((max_n + 255) / 256), (unsigned)n);
-        const bool filter = min_points > 1; // Mapping._hits
-        if (filter) {
-            hipLaunchKernelGGL(feed_radius_count_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs,
-                               (float)(radius * radius), min_points, d_keep);
-            SFE_LAUNCH_CHECK(ctx);
-        }
-        hipLaunchKernelGGL(feed_hit_cells_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs, d_tabs,
-                           filter ? (const uint8_t *)d_keep : nullptr, d_hits, (UndPoint *)d_und, d_cnt);
-        SFE_LAUNCH_CHECK(ctx);
-    }
-    SFE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    f.maps.assign(maps, maps + n), f.slots.assign(slots, slots + n), f.geoms.assign(geoms, geoms + n);
-    f.n_und.assign(h_cnt, h_cnt + n);
-    f.jobs = jobs;
-    f.ktab.assign(ktab, ktab + n_ktab);
-    f.miss32 = miss32, f.logit_miss = logit_miss, f.hit32 = hit32, f.logit_hit = logit_hit;
-    f.tot = (int)tot, f.tot_und = 0;
-    for (int b = 0; b < n; ++b) {
-        n_points_out[b] = jobs[b].n_hits;
-        n_undecided_out[b] = h_cnt[b];
-        f.tot_und += h_cnt[b];
-    }
-    if (f.tot_und == 0)
-        return feed_finish(ms);
-    f.pending = true;
+        return 0;
+    };
+    if (int rc = feed_measure_store(set_view(ms), "map set", store, n, maps, slots, geoms, handles, tabs, radius, min_points,
+                                    hrhc, k_off, ktab, n_ktab, div, miss32, logit_miss, hit32, logit_hit, n_points_out,
+                                    n_undecided_out, slot_job))
+        return rc;
+    if (ms->feed.pending && ms->feed.tot_und == 0)
+        return set_feed_finish(ms);
     return 0;
 }
 
@@ -1915,52 +2055,81 @@ int sfe_mapset_measure_store_undecided(sfe_mapset *ms, float *xy_out, int32_t *p
 {
     if (!ms)
         return SFE_ERR_ARG;
-    sfe_ctx *ctx = ms->ctx;
-    if (int rc = sfe_use(ctx))
+    if (int rc = sfe_use(ms->ctx))
         return rc;
-    sfe_mapset::Feed &f = ms->feed;
-    SFE_ARG(ctx, f.pending && xy_out && pos_out && cap >= f.tot_und);
-    std::vector<UndPoint> und((size_t)f.tot_und);
-    size_t at = 0;
-    for (size_t b = 0; b < f.jobs.size(); ++b) {
-        if (!f.n_und[b])
-            continue;
-        SFE_HIP(ctx, hipMemcpyAsync(und.data() + at, (const UndPoint *)ms->buf[9].p + f.jobs[b].hit_off,
-                                    sizeof(UndPoint) * (size_t)f.n_und[b], hipMemcpyDeviceToHost, ctx->stream));
-        at += (size_t)f.n_und[b];
-    }
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // (the device appended them in no fixed order)
-    std::sort(und.begin(), und.end(), [](const UndPoint &a, const UndPoint &b) { return a.pos < b.pos; });
-    for (size_t i = 0; i < und.size(); ++i) {
-        xy_out[2 * i] = und[i].x, xy_out[2 * i + 1] = und[i].y;
-        pos_out[i] = und[i].pos;
-    }
-    return 0;
+    return feed_undecided(set_view(ms), xy_out, pos_out, cap);
 }
 
 int sfe_mapset_measure_store_finish(sfe_mapset *ms, int n_cells, const int32_t *pos, const int32_t *cells)
 {
     if (!ms)
         return SFE_ERR_ARG;
-    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ms->ctx))
+        return rc;
+    if (int rc = feed_fill(set_view(ms), n_cells, pos, cells))
+        return rc;
+    return set_feed_finish(ms);
+}
+
+// ---- the store feed of one map: the set's routines over this map's slots (sonarfe.h) ----------------------------------
+int sfe_map_hit_table(sfe_map *m, const float *bearings, int num_bearings, const double *breaks, const double *coef,
+                      int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double, int r_skip,
+                      int c_skip, int *id_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    if (int rc = sfe_use(m->ctx))
+        return rc;
+    return feed_hit_table(map_view(m), bearings, num_bearings, breaks, coef, n_intervals, margin, num_ranges, range_resolution,
+                          range_in_double, r_skip, c_skip, id_out);
+}
+
+int sfe_map_measure_store(sfe_map *m, sfe_cloud_store *store, int n, const int32_t *slots, const int32_t *geoms,
+                          const int32_t *handles, const int32_t *tabs, double radius, int min_points, const int32_t *hrhc,
+                          const int32_t *k_off, const float *ktab, int n_ktab, const double *div, float miss32,
+                          float logit_miss, float hit32, float logit_hit, int32_t *n_points_out, int32_t *n_undecided_out)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = m->ctx;
     if (int rc = sfe_use(ctx))
         return rc;
-    sfe_mapset::Feed &f = ms->feed;
-    SFE_ARG(ctx, f.pending && n_cells == f.tot_und && pos && cells);
-    for (int i = 0; i < n_cells; ++i)
-        SFE_ARG(ctx, pos[i] >= 0 && pos[i] < f.tot);
-    // (the keep flags have been read: their buffer takes the upload)
-    std::vector<int32_t> up(3 * (size_t)n_cells);
-    memcpy(up.data(), pos, sizeof(int32_t) * (size_t)n_cells);
-    memcpy(up.data() + n_cells, cells, sizeof(int32_t) * 2 * (size_t)n_cells);
-    int32_t *d_up = set_stage(ms, 8, up);
-    if (!d_up)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set store feed: upload of the host's cells failed");
-    hipLaunchKernelGGL(feed_fill_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, d_up,
-                       d_up + n_cells, n_cells, (int32_t *)ms->buf[7].p);
-    SFE_LAUNCH_CHECK(ctx);
-    return feed_finish(ms);
+    auto slot_job = [&](int b, MeasJob &j) {
+        if (int rc = map_slot_check(m, slots[b], geoms[b]))
+            return rc;
+        for (int a = 0; a < b; ++a)
+            SFE_ARG(ctx, slots[a] != slots[b]); // a slot holds one image
+        const MapGeom &g = m->geoms[geoms[b]];
+        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
+        return 0;
+    };
+    if (int rc = feed_measure_store(map_view(m), "map", store, n, nullptr, slots, geoms, handles, tabs, radius, min_points, hrhc,
+                                    k_off, ktab, n_ktab, div, miss32, logit_miss, hit32, logit_hit, n_points_out,
+                                    n_undecided_out, slot_job))
+        return rc;
+    if (m->feed.pending && m->feed.tot_und == 0)
+        return map_feed_finish(m);
+    return 0;
+}
+
+int sfe_map_measure_store_undecided(sfe_map *m, float *xy_out, int32_t *pos_out, int cap)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    if (int rc = sfe_use(m->ctx))
+        return rc;
+    return feed_undecided(map_view(m), xy_out, pos_out, cap);
+}
+
+int sfe_map_measure_store_finish(sfe_map *m, int n_cells, const int32_t *pos, const int32_t *cells)
+{
+    if (!m)
+        return SFE_ERR_ARG;
+    if (int rc = sfe_use(m->ctx))
+        return rc;
+    if (int rc = feed_fill(map_view(m), n_cells, pos, cells))
+        return rc;
+    return map_feed_finish(m);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

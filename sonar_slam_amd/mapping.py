@@ -8,7 +8,9 @@ skips, sonar_xy (once per geometry), the outlier filter (pcl.remove_outlier), th
 per-keyframe cos / sin of the pose, pose_changed and the growth decisions of adjust_bounds.
 
 Extensions: ``update_poses(keys, poses)`` (the loop of update_pose calls, batched: the same bits) and
-``add_keyframe_logodds(key, pose, ping, logodds)`` (a ready polar log-odds image instead of points).  Refused:
+``add_keyframe_logodds(key, pose, ping, logodds)`` (a ready polar log-odds image instead of points) and
+``add_keyframe_store(key, pose, ping, store, handle)`` (the cloud taken from a ``store.CloudStore`` where it lies on the
+device: the same map, bit for bit, without the cloud crossing to the host).  Refused:
 method 2 (``get_occupancy_grid2``) and the intensity grid.  INTEGRATION.md lists the deviations.
 """
 import contextlib
@@ -174,6 +176,23 @@ class Mapping(object):
         self._geom = -1               # geometry of the next keyframe
         self._geom_shape = {}         # geometry id -> image shape
         self._grow = [0, 0]           # rows grown on top, columns grown on the left (sfe_map_shape)
+        self._hit_key = None          # what _hit_indices reads of the current geometry (the key of its device hit table)
+        self._hit_tabs = {}
+        # the store feed since configure(): points fed, points the device left to the host, calls
+        self.feed_stats = {"points": 0, "undecided": 0, "calls": 0}
+
+    @property
+    def point_cloud(self):
+        """the cloud of the last keyframe (the ``pub_occupancy2`` bookkeeping).  After a store-fed add it is read from the
+        store when asked for: the handle must still be live then (not dropped by ``store.truncate``)."""
+        if self._cloud_ref is not None:
+            store, handle = self._cloud_ref
+            return store.read(handle)
+        return self._point_cloud
+
+    @point_cloud.setter
+    def point_cloud(self, points):
+        self._point_cloud, self._cloud_ref = points, None
 
     # ---- configuration ---------------------------------------------------------------------------------------------
     def load_yaml(self, path):
@@ -209,6 +228,8 @@ class Mapping(object):
         h = C.c_void_p()
         self._check(self._lib.sfe_map_create(self.ctx.handle, self.rows, self.cols, C.byref(h)))
         self._h = h
+        self._hit_tabs = {}
+        self.feed_stats = {"points": 0, "undecided": 0, "calls": 0}
 
     def _configure_host(self):
         if self.pub_intensity:
@@ -230,6 +251,7 @@ class Mapping(object):
         self._grow = [0, 0]
         self._geom = -1
         self._geom_shape = {}
+        self._hit_key = None
         self.keyframes = []
         self.oculus = _Oculus()
 
@@ -253,9 +275,35 @@ class Mapping(object):
         return len(self.keyframes)
 
     def _register_geometry(self, sonar_xy, shape):
+        self._hit_key = self._new_hit_key()
         gid = C.c_int(0)
         self._check(self._lib.sfe_map_geometry(self._h, _L.ptr(sonar_xy, C.c_float), shape[0], shape[1], C.byref(gid)))
         return gid.value
+
+    def _new_hit_key(self):
+        o = self.oculus
+        return (o.num_ranges, o.range_resolution, o.bearings.tobytes(), int(self.oculus_r_skip), int(self.oculus_c_skip))
+
+    def _geometry_state(self):
+        return (dict(vars(self.oculus)), self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom,
+                self._hit_key, dict(self._geom_shape))
+
+    def _restore_geometry(self, state):
+        ocu, self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom, self._hit_key, shapes = state
+        vars(self.oculus).clear()
+        vars(self.oculus).update(ocu)
+        self._geom_shape = shapes
+
+    @contextlib.contextmanager
+    def _geometry_guard(self):
+        """a refused add leaves the geometry state (sonar settings, skips, image size, geometry id) as it found it:
+        _new_keyframe takes a ping's geometry before the device can refuse the image, the slot or the cloud"""
+        state = self._geometry_state()
+        try:
+            yield
+        except BaseException:
+            self._restore_geometry(state)
+            raise
 
     def _read_cells(self, slot, n):
         r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
@@ -362,6 +410,59 @@ class Mapping(object):
             self.point_cloud = points
         self._fit([kf], dec=False)
         self._append(key, kf)
+
+    def add_keyframe_store(self, key, pose, ping, store, handle):
+        """``add_keyframe(key, pose, ping, store.read(handle))``, bit for bit, without the cloud leaving the device: the
+        outlier filter, the hit cells and the measurement run from the store's pool (``store``: a CloudStore of this map's
+        context).  In mapping_node.py's flow: ``handle, n, _ = fe.callback_store(ping, store)`` in place of the feature
+        cloud, then this call in place of ``add_keyframe``.
+
+        The device decides a point's bearing column only outside a guard band (``guard_margin``); the few points it leaves
+        undecided come back and go through ``_hit_indices`` here (``feed_stats`` counts them).  With ``pub_occupancy2``,
+        ``point_cloud`` is read from the store on access: the handle must still be live then.  A dead handle, or an image
+        or a slot the map cannot hold, raises and leaves the map as it was."""
+        self._check_supported()
+        if self._h is None:
+            raise RuntimeError("Mapping.add_keyframe_store: configure() first")
+        if getattr(store, "ctx", None) is not self.ctx:
+            raise ValueError("Mapping.add_keyframe_store: the store belongs to another context")
+        handle = int(handle)
+        with self._geometry_guard():
+            kf = self._new_keyframe(pose, ping)
+            self._measure_store(kf, store, handle)
+        if self.pub_occupancy2:
+            self._cloud_ref = (store, handle)
+        self._fit([kf], dec=False)
+        self._append(key, kf)
+
+    def _hit_table(self):
+        return device_hit_table(self, self._hit_tabs, lambda *a: self._lib.sfe_map_hit_table(self._h, *a))
+
+    def _measure_store(self, kf, store, handle):
+        hr, hc = self._hit_halves()
+        _, ktab, div = self._measure_args(np.zeros((0, 2), np.int32), hr, hc)
+        tab = self._hit_table()
+        i32 = lambda *a: _L.ptr(np.array(a, np.int32), C.c_int32)
+        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
+        n_pts, n_und = np.zeros(1, np.int32), np.zeros(1, np.int32)
+        with self.ctx.lock:        # the store's slot table and the context's pinned staging
+            self._check(self._lib.sfe_map_measure_store(
+                self._h, store.handle, 1, i32(kf._slot), i32(kf.geom), i32(handle), i32(tab),
+                float(self.outlier_filter_radius), int(self.outlier_filter_min_points), i32(hr, hc), i32(0),
+                _L.ptr(ktab, C.c_float), len(ktab), _L.ptr(np.array([div], np.float64), C.c_double), float(miss32),
+                float(logit(miss32)), float(hit32), float(logit(hit32)), _L.ptr(n_pts, C.c_int32), _L.ptr(n_und, C.c_int32)))
+            total = int(n_und[0])
+            if total:
+                # phase two: the undecided points through _hit_indices, then the measurement
+                xy, pos = np.zeros((total, 2), np.float32), np.zeros(total, np.int32)
+                self._check(self._lib.sfe_map_measure_store_undecided(self._h, _L.ptr(xy, C.c_float), _L.ptr(pos, C.c_int32),
+                                                                      total))
+                cells = np.ascontiguousarray(self._hit_indices(xy)[0], np.int32)
+                self._check(self._lib.sfe_map_measure_store_finish(self._h, total, _L.ptr(pos, C.c_int32),
+                                                                   _L.ptr(cells, C.c_int32)))
+        self.feed_stats["points"] += int(n_pts[0])
+        self.feed_stats["undecided"] += total
+        self.feed_stats["calls"] += 1
 
     def add_keyframe_logodds(self, key, pose, ping, logodds):
         """add_keyframe with a ready polar log-odds image (float32, the downsampled image's shape) instead of points"""
@@ -632,6 +733,31 @@ def decide_columns(oculus, points, breaks, coef, margin):
     return col, safe | outside
 
 
+def hit_table_args(v):
+    """what the device's hit table holds of map ``v``'s sonar geometry and skips: the arguments of sfe_map_hit_table /
+    sfe_mapset_hit_table after the handle, without id_out -> (bearings, num_bearings, breaks, coef, n_intervals, margin,
+    num_ranges, range_resolution, range_in_double, r_skip, c_skip)"""
+    o = v.oculus
+    breaks, coef = spline_table(o)
+    bearings = np.ascontiguousarray(o.bearings, np.float32)
+    wide = np.result_type(np.float32, o.range_resolution) == np.float64     # ra / res of float32 ranges
+    return (bearings, len(bearings), breaks, coef, len(coef), guard_margin(o, breaks, coef), int(o.num_ranges),
+            float(o.range_resolution), int(wide), int(v.oculus_r_skip), int(v.oculus_c_skip))
+
+
+def device_hit_table(v, tabs, register):
+    """the id of the device's copy of what _hit_indices reads of map ``v``'s sonar geometry, stored once per geometry in
+    ``tabs`` (keyed by ``v._hit_key``); ``register(*ctypes arguments)`` is the owner's sfe_map(set)_hit_table call"""
+    key = v._hit_key
+    if key not in tabs:
+        bearings, nb, breaks, coef, n_iv, margin, num_ranges, res, wide, r_skip, c_skip = hit_table_args(v)
+        tid = C.c_int(0)
+        v._check(register(_L.ptr(bearings, C.c_float), nb, _L.ptr(breaks, C.c_double), _L.ptr(coef, C.c_double), n_iv, margin,
+                          num_ranges, res, wide, r_skip, c_skip, C.byref(tid)))
+        tabs[key] = tid.value
+    return tabs[key]
+
+
 # ---- S maps in lock-step ---------------------------------------------------------------------------------------------
 SETTINGS = ("x0", "y0", "width", "height", "inc", "resolution", "pub_intensity", "pub_occupancy1", "hit_prob", "miss_prob",
             "inflation_angle", "inflation_range", "pub_occupancy2", "inflation_radius", "outlier_filter_radius",
@@ -683,21 +809,7 @@ class _SessionMap(Mapping):
         Mapping.__init__(self, batch.ctx)
         self._b, self._s = batch, s
         self._n_slots = 0
-        self._hit_key = None
         self._meas_job = -1
-
-    @property
-    def point_cloud(self):
-        """the cloud of the last keyframe (the ``pub_occupancy2`` bookkeeping).  After ``add_keyframes_store`` it is read
-        from the store when asked for: the handle must still be live then (not dropped by ``store.truncate``)."""
-        if self._cloud_ref is not None:
-            store, handle = self._cloud_ref
-            return store.read(handle)
-        return self._point_cloud
-
-    @point_cloud.setter
-    def point_cloud(self, points):
-        self._point_cloud, self._cloud_ref = points, None
 
     def configure(self):
         raise RuntimeError("a MapBatch session is configured through MapBatch.configure")
@@ -711,23 +823,11 @@ class _SessionMap(Mapping):
     def _check(self, rc):
         return self._b.ctx._check(rc)
 
-    def _geometry_state(self):
-        return (dict(vars(self.oculus)), self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom,
-                self._hit_key, dict(self._geom_shape))
-
-    def _restore_geometry(self, state):
-        ocu, self.oculus_image_size, self.oculus_r_skip, self.oculus_c_skip, self._geom, self._hit_key, shapes = state
-        vars(self.oculus).clear()
-        vars(self.oculus).update(ocu)
-        self._geom_shape = shapes
-
     def _new_slot(self):
         return self._n_slots        # slots are handed out densely: max_keyframes counts keyframes, not keys
 
     def _register_geometry(self, sonar_xy, shape):
-        o = self.oculus
-        self._hit_key = (o.num_ranges, o.range_resolution, o.bearings.tobytes(), int(self.oculus_r_skip),
-                         int(self.oculus_c_skip))
+        self._hit_key = self._new_hit_key()
         return self._b._geometry(sonar_xy, shape)
 
     def _read_cells(self, slot, n):
@@ -993,19 +1093,7 @@ class MapBatch(object):
 
     def _hit_table(self, v):
         """the device's copy of what _hit_indices reads of session map v's sonar geometry, stored once per geometry"""
-        key = v._hit_key
-        if key not in self._hit_tabs:
-            o = v.oculus
-            breaks, coef = spline_table(o)
-            bearings = np.ascontiguousarray(o.bearings, np.float32)
-            wide = np.result_type(np.float32, o.range_resolution) == np.float64     # ra / res of float32 ranges
-            tid = C.c_int(0)
-            self._check(self._lib.sfe_mapset_hit_table(
-                self._h, _L.ptr(bearings, C.c_float), len(bearings), _L.ptr(breaks, C.c_double), _L.ptr(coef, C.c_double),
-                len(coef), guard_margin(o, breaks, coef), int(o.num_ranges), float(o.range_resolution), int(wide),
-                int(v.oculus_r_skip), int(v.oculus_c_skip), C.byref(tid)))
-            self._hit_tabs[key] = tid.value
-        return self._hit_tabs[key]
+        return device_hit_table(v, self._hit_tabs, lambda *a: self._lib.sfe_mapset_hit_table(self._h, *a))
 
     def _measure_store(self, sessions, kfs, store, handles):
         n = len(sessions)

@@ -185,7 +185,15 @@ class FrontEnd(object):
                  nssm_enable=True, nssm_initialization=True, nssm_initialization_params=(100, 5, 0.01), nssm_min_st_sep=8,
                  nssm_min_points=50, nssm_max_translation=10.0, nssm_max_rotation=np.deg2rad(60), nssm_source_frames=5,
                  nssm_cov_samples=30, oculus_max_range=30.0, oculus_horizontal_aperture=np.radians(130.0),
-                 mcd_random_state=None, shgo_replay=True):
+                 mcd_random_state=None, shgo_replay=True, mapping=None):
+        if mapping is not None:                                  # (checked before anything is allocated)
+            mapping = dict(mapping)
+            if "ping" not in mapping:
+                raise ValueError("FrontEnd: mapping needs a `ping` (num_ranges, range_resolution, bearings)")
+            if mapping.get("feed", "host") not in ("host", "store"):
+                raise ValueError("FrontEnd: mapping feed must be \"host\" or \"store\", got %r" % (mapping["feed"],))
+            if mapping.get("feed", "host") == "store" and store is None:
+                raise ValueError("FrontEnd: mapping feed \"store\" needs a `store` (the keyframe clouds on the device)")
         self.ctx = ctx
         self.shgo_replay = shgo_replay      # FrontEnd.shgo: replay of shgo's decisions from one table of costs (shgo_fast.py)
         self.store = store          # CloudStore: keyframe clouds stay on the device (feed_handle)
@@ -229,6 +237,36 @@ class FrontEnd(object):
         self.keyframes = []
         self.current_frame = None
         self.log = []
+        # mapping: None (no map: nothing is allocated, the records are what they were before maps existed), or a dict as
+        # chained.SessionBatch takes it: `ping` (what Mapping.add_keyframe reads of a ping: num_ranges, range_resolution,
+        # bearings), Mapping's settings, and `feed`: "host" (the default: the keyframe's cloud is read back, or is the host
+        # array, and goes to add_keyframe) or "store" (add_keyframe_store: the same map, bit for bit, from the cloud where it
+        # lies on the device) -> self.map, a mapping.Mapping that every new keyframe is added to
+        self.map, self._map_ping, self._map_feed = None, None, "host"
+        if mapping is not None:
+            from .mapping import SETTINGS, Mapping
+            self._map_ping = mapping.pop("ping")
+            self._map_feed = mapping.pop("feed", "host")
+            for name in mapping:
+                if name not in SETTINGS:
+                    raise TypeError("FrontEnd: unknown mapping setting %r (Mapping's settings: %s)" % (name, ", ".join(SETTINGS)))
+            self.map = Mapping(ctx)
+            for name, v in mapping.items():
+                setattr(self.map, name, v)
+            self.map.configure()
+
+    def _map_keyframe(self, frame):
+        """the keyframe just appended into the occupancy map: the cloud stored for it, the pose just recorded (pose
+        corrections are the caller's: ``self.map.update_poses``)"""
+        if self.map is None:
+            return
+        key, points = len(self.keyframes) - 1, frame.points
+        if self._map_feed == "store":
+            self.map.add_keyframe_store(key, frame.pose, self._map_ping, self.store, points.handle)
+        elif self.store is not None:
+            self.map.add_keyframe(key, frame.pose, self._map_ping, self.store.read(points.handle))
+        else:
+            self.map.add_keyframe(key, frame.pose, self._map_ping, points)
 
     # -- slam.py:205-227 --
     @property
@@ -700,6 +738,7 @@ class FrontEnd(object):
             self.log.append(rec)
             if self.nssm_enable and self.current_frame is not None:     # slam_ros.py:207
                 rec["nssm"] = self.add_nonsequential_scan_matching()
+            self._map_keyframe(frame)
         else:
             self._release(points)
         self.current_frame = frame

@@ -25,8 +25,18 @@ steps, the first left out:
   readbacks_per_step     host read-backs of the measurement per step (the fit's bounds come on top on both routes)
   grid_sha               sha256 of every session's final grid: equal between the two feeds
 
+With `--feed store` and no `--sessions` (or `--sessions 0`) the feed of a single Mapping, under "feed_single": three
+Mappings on the same session in this process, alternated keyframe by keyframe over `--batch-keyframes` keyframes, the first
+left out -- `add_keyframe` on clouds that are already on the host, `store.read` + `add_keyframe` (what a node whose
+clouds lie in a CloudStore has to do without the store feed), and `add_keyframe_store`:
+  add_keyframe_ms        the median per add of each route, host synchronised
+  undecided_share        points the device left to the host / points fed
+  readbacks_per_add      host read-backs of the measurement per add (the fit's bounds come on top on every route)
+  grids_equal            the three final grids are bit for bit equal
+
     python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
     python tools/mapping_times.py --sessions 32 --feed store
+    python tools/mapping_times.py --feed store --batch-keyframes 200
 """
 import argparse
 import json
@@ -181,11 +191,55 @@ def feed(ctx, ping, settings, S, K, route):
     return out
 
 
+def feed_single(ctx, ping, settings, K):
+    """one Mapping fed by add_keyframe (host clouds), store.read + add_keyframe, and add_keyframe_store -> the "feed_single" record"""
+    from sonar_slam_amd.store import CloudStore
+    poses, clouds = session(K)
+    store = CloudStore(ctx, capacity_points=K * 512, max_clouds=K)
+    handles = [store.put(c) for c in clouds]
+    host32 = [store.read(h) for h in handles]          # what add_keyframe is handed on the host route
+    maps = {}
+    for name in ("host", "read_back", "store"):
+        m = Mapping(ctx)
+        for k, v in settings.items():
+            setattr(m, k, v)
+        m.configure()
+        maps[name] = m
+    add = {"host": lambda k, p: maps["host"].add_keyframe(k, p, ping, host32[k]),
+           "read_back": lambda k, p: maps["read_back"].add_keyframe(k, p, ping, store.read(handles[k])),
+           "store": lambda k, p: maps["store"].add_keyframe_store(k, p, ping, store, handles[k])}
+    times = {name: [] for name in add}
+    names, und = list(add), 0
+    for k in range(K):
+        p = Pose2(*poses[k])
+        before = maps["store"].feed_stats["undecided"]
+        for name in names[k % 3:] + names[:k % 3]:
+            t = timed(lambda: (add[name](k, p), ctx.sync()))
+            if k:                   # keyframe 0: geometry upload, first allocations
+                times[name].append(t)
+        und += maps["store"].feed_stats["undecided"] > before
+    grids = [m.logodds_grid for m in maps.values()]
+    stats = maps["store"].feed_stats
+    out = {"keyframes": K, "image": list(maps["store"].oculus_image_size),
+           "add_keyframe_ms": {name: float(np.median(t)) for name, t in times.items()},
+           "add_keyframe_ms_min": {name: float(np.min(t)) for name, t in times.items()},
+           "points": stats["points"], "undecided": stats["undecided"],
+           "undecided_share": stats["undecided"] / float(max(stats["points"], 1)),
+           # host: the keep flags of the outlier filter; read_back: the cloud on top; store: the undecided counter every
+           # add, the undecided points on the adds that have some
+           "readbacks_per_add": {"host": 1.0, "read_back": 2.0, "store": 1.0 + und / float(K)},
+           "grids_equal": bool(all(np.array_equal(grids[0].view(np.int32), g.view(np.int32)) for g in grids[1:]))}
+    for m in maps.values():
+        m.close()
+    store.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
     ap.add_argument("--ref-adds", type=int, default=20)
-    ap.add_argument("--sessions", type=int, default=32)
+    ap.add_argument("--sessions", type=int, default=None, help="default 32; with --feed store, 0 or absent: a single Mapping")
     ap.add_argument("--batch-keyframes", type=int, default=40)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--feed", choices=("host", "store"), default=None)
@@ -193,6 +247,13 @@ def main():
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
     settings = dict(x0=-100.0, y0=-100.0, width=200.0, height=200.0)
+    if a.feed == "store" and not a.sessions:
+        ctx = _lib.default_context()
+        print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
+                          "feed_single": feed_single(ctx, ping, settings, a.batch_keyframes)}))
+        return
+    if a.sessions is None:
+        a.sessions = 32
     if a.feed is not None:
         ctx = _lib.default_context()
         print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
