@@ -640,6 +640,9 @@ int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_
  * inc_grid / dec_grid, adjust_bounds, get_occupancy_grid1); sonar_slam_amd/mapping.py is the host side.  One sfe_map per
  * Mapping owns the device state: the float32 grid [rows x cols], the sonar_xy table of every geometry, and per keyframe slot
  * its polar log-odds image and its current cell list (r, c, l in ascending r * cols + c).  Entry points take host pointers.
+ * An sfe_map is a one-map sfe_mapset, described below, and every call here is the sfe_mapset call of the same name over map 0.
+ * What differs is where the slots live: an sfe_map has no arena and so no cap on slots or pixels (beyond the 2^30 pixels of
+ * an image): a slot's buffers are allocated at its geometry's pixel count when its measurement (or sfe_map_set_logodds) runs.
  *   sfe_map_geometry: sonar_xy [img_rows * img_cols][2] float32 (mapping.py:158-163) -> geometry id.
  *   sfe_map_set_logodds: a ready log-odds image [img_rows * img_cols] for `slot` (created for `geom` on first use).
  *   sfe_map_measure: n keyframes at once: slot / geometry, hits [2 * hit_off[n]] (row, col of the downsampled image; keyframe b
@@ -658,10 +661,12 @@ int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_
  *     -> int8(clip(100 expit(v), 0, 100)), resized INTER_NEAREST to out_h x out_w with source index floor(i * inv) when
  *     resize != 0.
  *   sfe_map_hit_table / sfe_map_measure_store / sfe_map_measure_store_undecided / sfe_map_measure_store_finish: the store
- *     feed of one map.  Their contract is that of the sfe_mapset_* calls of the same names, below, with the `maps` argument
- *     dropped: the same device routines decide the same points.  n keyframes of the map per call, each slot at most once.
- *     A slot that holds an image of another geometry, an unknown geometry or a negative slot is refused with SFE_ERR_ARG, as
- *     by sfe_map_measure; a slot is created only when its measurement runs, so a refused or dropped call leaves none behind. */
+ *     feed of one map: the sfe_mapset_* calls of the same names, below, over one map.  n keyframes of the map per call, each
+ *     slot at most once.  A slot that holds an image of another geometry, an unknown geometry or a negative slot is refused
+ *     with SFE_ERR_ARG, as by sfe_map_measure; a slot gets its storage only when its measurement runs, so a refused or
+ *     dropped call leaves none behind (a measurement that fails with SFE_ERR_HIP leaves the slot unused, its buffers kept
+ *     for the next call that names it).
+ *   As the set's calls, sfe_map_fit_bounds, sfe_map_refit and sfe_map_measure_store take at most 65535 keyframes per call. */
 typedef struct sfe_map sfe_map;
 int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out);
 void sfe_map_destroy(sfe_map *m);
@@ -694,7 +699,7 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
                    int8_t *occ_out);
 
 /* ---- S occupancy maps that advance together (sonar_slam_amd/mapping.py: MapBatch; chained.SessionBatch's maps).  One
- * sfe_mapset owns the state of n_maps maps, each exactly what an sfe_map of its own would hold after the same calls: the
+ * sfe_mapset owns the state of n_maps maps, each exactly what an sfe_map of its own holds after the same calls: the
  * float32 grids (each with its own rows, columns and growth counters), one table of sonar_xy geometries shared by all maps,
  * and for every (map, slot) its polar log-odds image and its double-buffered cell list.  Every stage is one call over any
  * subset of the maps; a keyframe is named by (map, slot).  Entry points take host pointers.
@@ -728,7 +733,8 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
  *     has changed nothing.  hrhc / k_off / ktab / div are per job as in sfe_mapset_measure, given as for a cloud with points:
  *     a cloud of zero points becomes a keyframe without a measurement (hr < 0, all miss_prob), a cloud the filter empties
  *     keeps hr >= 0 with no hits.  Refused before anything changes: a handle the store does not hold or whose count is
- *     negative (a failed producer) and an unknown table with SFE_ERR_ARG, a slot >= max_keyframes with SFE_ERR_CAP (a
+ *     negative (a failed producer), an unknown table and a (map, slot) named twice in the call (a slot holds one image; checked
+ *     after the per-job checks) with SFE_ERR_ARG, a slot >= max_keyframes with SFE_ERR_CAP (a
  *     geometry of more than max_px pixels is never registered: sfe_mapset_geometry refuses it with SFE_ERR_CAP).
  *   sfe_mapset_hit_table: what the cells need of a sonar geometry, stored once: the float32 bearings (their ends bound the
  *     table), oculus.b2c's cubic spline as n_intervals + 1 ascending knots and 4 double coefficients per interval (powers

@@ -2,13 +2,28 @@
 // the fit of its pixels to grid cells, and the ordered add / subtract of its cells on a float32 grid (sonar_slam_amd/mapping.py
 // is the host side: control flow, growth decisions, everything O(keyframes)).
 //
-// State of one map (sfe_map): the grid [rows x cols] float32, the sonar_xy table of every geometry, and per keyframe slot its
-// polar log-odds image and its cell list (r, c uint16 + l float32, ascending r * cols + c).  Cell lists are double-buffered:
-// a refit writes the new list next to the old one, subtracts the old, adds the new, and flips.  Growth pads the grid and
-// bumps two counters; a list keeps the counters it was written at, and its cells are shifted by the difference when read.
+// One implementation, sfe_mapset: S maps that advance together.  Every kernel runs over (map, slot) jobs whose tables carry
+// pointers, so a job does not know which map it belongs to.  State of a map: the grid [rows x cols] float32; of the set: the
+// sonar_xy table of every geometry, and per keyframe slot its polar log-odds image and its cell list (r, c uint16 +
+// l float32, ascending r * cols + c).  Cell lists are double-buffered: a refit writes the new list next to the old one,
+// subtracts the old, adds the new, and flips.  Growth pads a grid and bumps two counters; a list keeps the counters it was
+// written at, and its cells are shifted by the difference when read.  An sfe_map is a set of one map (the end of this file).
+//
+// Slot storage, the one thing chosen at creation.  A slot record (SetSlot) carries its own device pointers:
+//   logodds  float32 [px]
+//   r, c     uint16  [2][px] each   (the double-buffered cell list)
+//   l        float32 [2][px]
+// = 20 bytes per pixel (2.1 MB at the 105 k pixels of a 1024 x 512 ping at the shipped skips), plus 8 bytes of counts.
+//   arena (sfe_mapset_create): fixed at creation for n_maps * max_keyframes slots of max_px pixels each, the pointers computed
+//     into it then.  Nothing is reallocated afterwards: a slot >= max_keyframes or an image of more than max_px pixels is
+//     refused (SFE_ERR_CAP) before any state changes.
+//   on demand (sfe_map_create): no cap.  A slot's buffers are allocated at its geometry's pixel count when its measurement
+//     (or set_logodds) runs, and the slot vector and the counts table grow to hold it, live counts kept.
+// Everything else reads the pointers of the record.  Grids are per map and grow on their own.
 #include <algorithm>
 #include <climits>
 #include <cstring>
+#include <utility>
 
 #include "sfe_internal.h"
 
@@ -28,14 +43,23 @@ struct MapBuf {
     size_t cap = 0;
 };
 
-struct MapSlot {
-    int geom = -1;
+struct SetSlot {
+    int geom = -1;              // -1: unused
+    int cur = 0;                // which buffer holds the current list
+    int has_cells = 0;
+    int base_r = 0, base_c = 0; // growth counters when the current list was written
+    int px = 0;                 // pixels its buffers hold
     float *d_logodds = nullptr;
     uint16_t *d_r[2] = {nullptr, nullptr}, *d_c[2] = {nullptr, nullptr};
     float *d_l[2] = {nullptr, nullptr};
-    int cur = 0;             // which buffer holds the current list
-    int has_cells = 0;
-    int base_r = 0, base_c = 0; // growth counters when the current list was written
+    int32_t *d_n = nullptr;     // [2]: cell count of each list buffer
+};
+
+struct SetMap {
+    int rows = 0, cols = 0;
+    float *d_grid = nullptr, *d_frames = nullptr; // (d_frames: the grid of the last frames= render)
+    int frames_rows = 0, frames_cols = 0;
+    int grow_r = 0, grow_c = 0;
 };
 
 // per keyframe of a measurement batch
@@ -83,51 +107,43 @@ struct UndPoint {
     int32_t pos, job; // its entry in the hit buffer
 };
 
-// the store feed of one owner (an sfe_map or an sfe_mapset): the call that waits for the host's cells
+
+// the store feed: the call that waits for the host's cells
 struct FeedState {
     bool pending = false;
-    std::vector<int32_t> maps, slots, geoms, n_und; // (maps: empty for an sfe_map)
+    std::vector<int32_t> maps, slots, geoms, n_und;
     std::vector<MeasJob> jobs;
     std::vector<float> ktab;
     float miss32 = 0, logit_miss = 0, hit32 = 0, logit_hit = 0;
     int tot = 0, tot_und = 0;
 };
 
-// ---- what the measurement and the store feed need of their owner: an sfe_map and an sfe_mapset number their scratch alike
-struct FeedView {
-    sfe_ctx *ctx;
-    MapBuf *buf; // [11]
-    std::vector<HitTab> *hit_tabs;
-    FeedState *feed;
-    std::vector<MeasJob> *last_meas;
-    int *last_meas_n;
-};
-
 } // namespace
 
-struct sfe_map {
+struct sfe_mapset {
     sfe_ctx *ctx = nullptr;
-    int rows = 0, cols = 0;
-    float *d_grid = nullptr;
-    float *d_frames = nullptr; // the grid of the last frames= render
-    int frames_rows = 0, frames_cols = 0;
-    int grow_r = 0, grow_c = 0;
+    bool arena = true;  // slot storage: the fixed arena, or on demand
+    int n_maps = 0;
+    int max_kf = 0;     // slots per map: fixed (arena), or as many as have been asked for (on demand)
+    int max_px = 0;     // (arena)
+    std::vector<SetMap> maps;
     std::vector<MapGeom> geoms;
-    std::vector<MapSlot> slots;
-    int32_t *d_counts = nullptr; // [slot][2]: cell count of each list buffer
+    std::vector<SetSlot> slots; // [map * max_kf + slot]
+    float *d_logodds = nullptr, *d_l = nullptr; // the arena
+    uint16_t *d_r = nullptr, *d_c = nullptr;
+    int32_t *d_counts = nullptr; // [map * max_kf + slot][2], room for counts_cap slots
     int counts_cap = 0;
-    MapBuf buf[11]; // 0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's (as sfe_mapset's)
+    // scratch.  0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's job tables, hit buffer,
+    // keep flags, undecided lists and counters, hit tables
+    MapBuf buf[11];
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
+    long long apply_launches = 0; // launches of mapset_apply_kernel so far
     std::vector<HitTab> hit_tabs; // device copies owned here
     FeedState feed;
 };
 
 namespace {
-
-FeedView map_view(sfe_map *m);
-int measure_run(const FeedView &v, const std::vector<MeasJob> &jobs, const int32_t *d_hits, const float *ktab, int n_ktab,
-                float miss32, float logit_miss, float hit32, float logit_hit);
 
 // grow-only device scratch
 void *buf_get(sfe_ctx *ctx, MapBuf &b, size_t bytes)
@@ -147,11 +163,6 @@ void *buf_get(sfe_ctx *ctx, MapBuf &b, size_t bytes)
     }
     b.cap = cap;
     return b.p;
-}
-
-void *map_buf(sfe_map *m, int i, size_t bytes)
-{
-    return buf_get(m->ctx, m->buf[i], bytes);
 }
 
 // n values from pageable host memory (the caller synchronises before the host array goes away)
@@ -369,20 +380,6 @@ __global__ __launch_bounds__(COMPACT_THREADS) void map_compact_kernel(const FitJ
     }
 }
 
-// --- apply (inc_grid / dec_grid): one keyframe's cells are unique, so its scatter has no conflicts; keyframes go in order
-__global__ void map_apply_kernel(float *grid, int rows, int cols, const uint16_t *r, const uint16_t *c, const float *l,
-                                 const int32_t *n, int dr, int dc, int sub)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= *n)
-        return;
-    const int rr = (int)r[i] + dr, cc = (int)c[i] + dc;
-    if (rr < 0 || rr >= rows || cc < 0 || cc >= cols)
-        return;   // cannot happen: every cell lies inside the grown grid
-    float *g = grid + (int64_t)rr * cols + cc;
-    *g = sub ? __fsub_rn(*g, l[i]) : __fadd_rn(*g, l[i]);
-}
-
 __global__ void map_pad_kernel(const float *src, int rows, int cols, float *dst, int dcols, int top, int left)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -392,537 +389,7 @@ __global__ void map_pad_kernel(const float *src, int rows, int cols, float *dst,
     dst[(int64_t)(r + top) * dcols + c + left] = src[i];
 }
 
-// --- render (get_occupancy_grid1, mapping.py:306-355): crop, expit, INTER_NEAREST, int8(clip(100 p, 0, 100))
-__global__ void map_render_kernel(const float *grid, int cols, int r0, int c0, int h, int w, int oh, int ow, double inv,
-                                  int resize, int8_t *out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)oh * ow)
-        return;
-    const int y = (int)(i / ow), x = (int)(i - (int64_t)y * ow);
-    int sy = y, sx = x;
-    if (resize) {
-        sy = min((int)floor(__dmul_rn((double)y, inv)), h - 1);
-        sx = min((int)floor(__dmul_rn((double)x, inv)), w - 1);
-    }
-    const double v = (double)grid[(int64_t)(r0 + sy) * cols + c0 + sx];
-    const float p = (float)__ddiv_rn(1.0, __dadd_rn(1.0, exp(-v)));
-    float q = __fmul_rn(100.0f, p);
-    q = q < 0.0f ? 0.0f : (q > 100.0f ? 100.0f : q);
-    out[i] = (int8_t)(int)q;
-}
-
-int map_grid_alloc(sfe_map *m, float **d, size_t n)
-{
-    if (hipMalloc((void **)d, n * sizeof(float)) != hipSuccess)
-        return sfe_set_err(m->ctx, SFE_ERR_HIP, "map grid allocation of %zu cells failed", n);
-    SFE_HIP(m->ctx, hipMemsetAsync(*d, 0, n * sizeof(float), m->ctx->stream));
-    return 0;
-}
-
-int map_counts(sfe_map *m)
-{
-    if (m->counts_cap >= (int)m->slots.size())
-        return 0;
-    int cap = (int)m->slots.size() * 2 + 64;
-    int32_t *d = nullptr;
-    SFE_HIP(m->ctx, hipMalloc((void **)&d, sizeof(int32_t) * 2 * cap));
-    SFE_HIP(m->ctx, hipMemsetAsync(d, 0, sizeof(int32_t) * 2 * cap, m->ctx->stream));
-    if (m->d_counts) {
-        SFE_HIP(m->ctx, hipMemcpyAsync(d, m->d_counts, sizeof(int32_t) * 2 * m->counts_cap, hipMemcpyDeviceToDevice,
-                                       m->ctx->stream));
-        SFE_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
-        (void)hipFree(m->d_counts);
-    }
-    m->d_counts = d;
-    m->counts_cap = cap;
-    return 0;
-}
-
-// the slot, created for geometry g (or checked against it)
-int map_slot(sfe_map *m, int slot, int g)
-{
-    SFE_ARG(m->ctx, slot >= 0 && g >= 0 && g < (int)m->geoms.size());
-    if (slot >= (int)m->slots.size())
-        m->slots.resize(slot + 1);
-    if (int rc = map_counts(m))
-        return rc;
-    MapSlot &s = m->slots[slot];
-    if (s.d_logodds) {
-        SFE_ARG(m->ctx, s.geom == g);
-        return 0;
-    }
-    const size_t n = (size_t)m->geoms[g].img_rows * m->geoms[g].img_cols;
-    s.geom = g;
-    SFE_HIP(m->ctx, hipMalloc((void **)&s.d_logodds, n * sizeof(float)));
-    for (int b = 0; b < 2; ++b) {
-        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_r[b], n * sizeof(uint16_t)));
-        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_c[b], n * sizeof(uint16_t)));
-        SFE_HIP(m->ctx, hipMalloc((void **)&s.d_l[b], n * sizeof(float)));
-    }
-    return 0;
-}
-
-template <class T>
-T *map_upload(sfe_map *m, int i, const T *h, size_t n)
-{
-    return buf_upload(m->ctx, m->buf[i], h, n);
-}
-
-} // namespace
-
-extern "C" {
-
-int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out)
-{
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, out != nullptr && rows > 0 && cols > 0 && (long long)rows * cols < (1LL << 31));
-    sfe_map *m = new sfe_map();
-    m->ctx = ctx;
-    m->rows = rows, m->cols = cols;
-    if (int rc = map_grid_alloc(m, &m->d_grid, (size_t)rows * cols)) {
-        delete m;
-        return rc;
-    }
-    *out = m;
-    return 0;
-}
-
-void sfe_map_destroy(sfe_map *m)
-{
-    if (!m)
-        return;
-    if (sfe_use(m->ctx) == 0)
-        (void)hipStreamSynchronize(m->ctx->stream);
-    (void)hipFree(m->d_grid);
-    (void)hipFree(m->d_frames);
-    (void)hipFree(m->d_counts);
-    for (auto &g : m->geoms)
-        (void)hipFree(g.d_xy);
-    for (auto &s : m->slots) {
-        (void)hipFree(s.d_logodds);
-        for (int b = 0; b < 2; ++b) {
-            (void)hipFree(s.d_r[b]);
-            (void)hipFree(s.d_c[b]);
-            (void)hipFree(s.d_l[b]);
-        }
-    }
-    for (auto &b : m->buf)
-        (void)hipFree(b.p);
-    for (auto &t : m->hit_tabs)
-        (void)hipFree((void *)t.breaks); // (breaks and coef are one block)
-    delete m;
-}
-
-int sfe_map_geometry(sfe_map *m, const float *sonar_xy, int img_rows, int img_cols, int *id_out)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    if (int rc = sfe_use(m->ctx))
-        return rc;
-    SFE_ARG(m->ctx, sonar_xy && id_out && img_rows > 0 && img_cols > 0 && (long long)img_rows * img_cols < (1 << 30));
-    MapGeom g;
-    g.img_rows = img_rows, g.img_cols = img_cols;
-    const size_t n = (size_t)img_rows * img_cols;
-    SFE_HIP(m->ctx, hipMalloc((void **)&g.d_xy, n * sizeof(float2)));
-    SFE_HIP(m->ctx, hipMemcpy(g.d_xy, sonar_xy, n * sizeof(float2), hipMemcpyHostToDevice));
-    m->geoms.push_back(g);
-    *id_out = (int)m->geoms.size() - 1;
-    return 0;
-}
-
-int sfe_map_set_logodds(sfe_map *m, int slot, int geom, const float *logodds)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    if (int rc = sfe_use(m->ctx))
-        return rc;
-    SFE_ARG(m->ctx, logodds != nullptr);
-    if (int rc = map_slot(m, slot, geom))
-        return rc;
-    const MapGeom &g = m->geoms[geom];
-    SFE_HIP(m->ctx, hipMemcpyAsync(m->slots[slot].d_logodds, logodds, sizeof(float) * (size_t)g.img_rows * g.img_cols,
-                                   hipMemcpyHostToDevice, m->ctx->stream));
-    SFE_HIP(m->ctx, hipStreamSynchronize(m->ctx->stream));
-    return 0;
-}
-
-int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geoms, const int32_t *hit_off,
-                    const int32_t *hits, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
-                    const double *div, float miss32, float logit_miss, float hit32, float logit_hit)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && geoms && hit_off && hrhc && k_off && div)) && n_ktab >= 0);
-    if (n == 0)
-        return 0;
-    m->feed.pending = false;
-    std::vector<MeasJob> jobs(n);
-    int64_t px = 0;
-    for (int b = 0; b < n; ++b) {
-        if (int rc = map_slot(m, slots[b], geoms[b]))
-            return rc;
-        const MapGeom &g = m->geoms[geoms[b]];
-        MeasJob &j = jobs[b];
-        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
-        j.hit_off = hit_off[b];
-        j.n_hits = hit_off[b + 1] - hit_off[b];
-        j.hr = hrhc[2 * b], j.hc = hrhc[2 * b + 1];
-        j.k_off = k_off[b];
-        // hr < 0: no points at all, the image is all miss_prob (mapping.py:224-225)
-        SFE_ARG(ctx, j.n_hits >= 0 && j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
-        if (j.hr < 0)
-            SFE_ARG(ctx, j.n_hits == 0);
-        else
-            SFE_ARG(ctx, j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab);
-        j.div = div[b];
-        j.px_off = px;
-        j.logodds = m->slots[slots[b]].d_logodds;
-        px += j.slot_px;
-    }
-    const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
-    SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
-    int32_t *d_hits = map_upload(m, 1, hits, 2 * (size_t)(n_hit_tot - 1));
-    return measure_run(map_view(m), jobs, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit);
-}
-
-int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, b >= 0 && b < (int)m->last_meas.size());
-    const MeasJob &j = m->last_meas[b];
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (hits_out)
-        SFE_HIP(ctx, hipMemcpy(hits_out, (uint8_t *)m->buf[3].p + j.px_off, (size_t)j.slot_px, hipMemcpyDeviceToHost));
-    if (prob_out)
-        SFE_HIP(ctx, hipMemcpy(prob_out, (float *)m->buf[4].p + j.px_off, sizeof(float) * j.slot_px, hipMemcpyDeviceToHost));
-    if (first_hits_out)
-        SFE_HIP(ctx, hipMemcpy(first_hits_out, (int32_t *)m->buf[5].p + (int64_t)b * m->last_meas_n,
-                               sizeof(int32_t) * j.img_cols, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// pose4 per keyframe: {cos, sin, x, y}; origin2: {y0, x0}
-static int map_fit_jobs(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
-                        std::vector<FitJob> &jobs, int &max_px)
-{
-    jobs.assign(n, FitJob());
-    max_px = 0;
-    for (int b = 0; b < n; ++b) {
-        SFE_ARG(m->ctx, slots[b] >= 0 && slots[b] < (int)m->slots.size() && m->slots[slots[b]].d_logodds);
-        const MapSlot &s = m->slots[slots[b]];
-        const MapGeom &g = m->geoms[s.geom];
-        FitJob &j = jobs[b];
-        j.xy = g.d_xy;
-        j.n_px = g.img_rows * g.img_cols;
-        j.c = pose4[4 * b], j.s = pose4[4 * b + 1], j.tx = pose4[4 * b + 2], j.ty = pose4[4 * b + 3];
-        j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1];
-        j.logodds = s.d_logodds;
-        max_px = max(max_px, j.n_px);
-    }
-    return 0;
-}
-
-int sfe_map_fit_bounds(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
-                       double resolution, int32_t *mm_out)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && pose4 && origin2 && mm_out)) && resolution > 0);
-    if (n == 0)
-        return 0;
-    std::vector<FitJob> jobs;
-    int max_px;
-    if (int rc = map_fit_jobs(m, n, slots, pose4, origin2, jobs, max_px))
-        return rc;
-    std::vector<int32_t> mm(4 * (size_t)n);
-    for (int b = 0; b < n; ++b)
-        mm[4 * b] = INT_MAX, mm[4 * b + 1] = INT_MIN, mm[4 * b + 2] = INT_MAX, mm[4 * b + 3] = INT_MIN;
-    FitJob *d_jobs = map_upload(m, 0, jobs.data(), jobs.size());
-    int32_t *d_mm = map_upload(m, 1, mm.data(), mm.size());
-    if (!d_jobs || !d_mm)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit scratch allocation / upload failed");
-    const unsigned gx = (unsigned)min((max_px + MAP_THREADS - 1) / MAP_THREADS, 64);
-    hipLaunchKernelGGL(map_bounds_kernel, dim3(gx, (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution,
-                       d_mm);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipMemcpyAsync(mm_out, d_mm, sizeof(int32_t) * 4 * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-int sfe_map_grow(sfe_map *m, int top, int bottom, int left, int right)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, top >= 0 && bottom >= 0 && left >= 0 && right >= 0);
-    if (top + bottom + left + right == 0)
-        return 0;
-    const int nr = m->rows + top + bottom, nc = m->cols + left + right;
-    SFE_ARG(ctx, (long long)nr * nc < (1LL << 31) && nr <= 65536 && nc <= 65536);
-    float *d = nullptr;
-    if (int rc = map_grid_alloc(m, &d, (size_t)nr * nc))
-        return rc;
-    const int64_t n = (int64_t)m->rows * m->cols;
-    hipLaunchKernelGGL(map_pad_kernel, dim3((unsigned)((n + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
-                       ctx->stream, m->d_grid, m->rows, m->cols, d, nc, top, left);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(m->d_grid);
-    m->d_grid = d;
-    m->rows = nr, m->cols = nc;
-    m->grow_r += top, m->grow_c += left;
-    return 0;
-}
-
-int sfe_map_refit(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2, double resolution,
-                  const int32_t *mm, const int32_t *shift2, const uint8_t *dec)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n >= 0 && (n == 0 || (slots && pose4 && origin2 && mm && shift2 && dec)) && resolution > 0);
-    if (n == 0)
-        return 0;
-    std::vector<FitJob> jobs;
-    int max_px;
-    if (int rc = map_fit_jobs(m, n, slots, pose4, origin2, jobs, max_px))
-        return rc;
-    int64_t win = 0;
-    for (int b = 0; b < n; ++b) {
-        FitJob &j = jobs[b];
-        MapSlot &s = m->slots[slots[b]];
-        for (int a = 0; a < b; ++a)
-            SFE_ARG(ctx, slots[a] != slots[b]); // one refit per slot and call: its other buffer takes the new list
-        SFE_ARG(ctx, mm[4 * b] <= mm[4 * b + 1] && mm[4 * b + 2] <= mm[4 * b + 3]);
-        j.wr0 = mm[4 * b], j.wh = mm[4 * b + 1] - mm[4 * b] + 1;
-        j.wc0 = mm[4 * b + 2], j.ww = mm[4 * b + 3] - mm[4 * b + 2] + 1;
-        j.sr = shift2[2 * b], j.sc = shift2[2 * b + 1];
-        // every cell inside the grid as it stands now (the caller grew it first)
-        SFE_ARG(ctx, j.wr0 + j.sr >= 0 && j.wr0 + j.sr + j.wh <= m->rows && j.wc0 + j.sc >= 0 &&
-                         j.wc0 + j.sc + j.ww <= m->cols);
-        SFE_ARG(ctx, (int64_t)j.wh * j.ww < (1LL << 30));
-        SFE_ARG(ctx, !dec[b] || s.has_cells);
-        j.win_off = win;
-        win += (int64_t)j.wh * j.ww;
-        const int nb = 1 - s.cur;
-        j.out_r = s.d_r[nb], j.out_c = s.d_c[nb], j.out_l = s.d_l[nb];
-        j.out_n = m->d_counts + 2 * slots[b] + nb;
-    }
-    // the job table through pinned staging: the call only enqueues (no synchronisation per batch)
-    FitJob *d_jobs = (FitJob *)map_buf(m, 0, sizeof(FitJob) * jobs.size());
-    int32_t *d_win = (int32_t *)map_buf(m, 1, sizeof(int32_t) * (size_t)win);
-    if (!d_jobs || !d_win)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit scratch allocation failed");
-    void *pin = sfe_pinned_begin(ctx, sizeof(FitJob) * jobs.size());
-    if (!pin)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map fit: pinned staging failed");
-    memcpy(pin, jobs.data(), sizeof(FitJob) * jobs.size());
-    SFE_HIP(ctx, hipMemcpyAsync(d_jobs, pin, sizeof(FitJob) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = sfe_pinned_end(ctx, ctx->stream))
-        return rc;
-    SFE_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d_win, EMPTY_SLOT, (size_t)win, ctx->stream));
-    hipLaunchKernelGGL(map_scatter_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
-                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution, d_win);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)n), dim3(COMPACT_THREADS), 0, ctx->stream, d_jobs, d_win);
-    SFE_LAUNCH_CHECK(ctx);
-    // the float32 history of every cell as the reference writes it: for each keyframe in call order, dec then inc
-    for (int b = 0; b < n; ++b) {
-        MapSlot &s = m->slots[slots[b]];
-        const unsigned nblk = (unsigned)((jobs[b].n_px + MAP_THREADS - 1) / MAP_THREADS);
-        if (dec[b]) {
-            const int o = s.cur;
-            hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_grid, m->rows, m->cols,
-                               s.d_r[o], s.d_c[o], s.d_l[o], m->d_counts + 2 * slots[b] + o, m->grow_r - s.base_r,
-                               m->grow_c - s.base_c, 1);
-            SFE_LAUNCH_CHECK(ctx);
-        }
-        const int nb = 1 - s.cur;
-        hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_grid, m->rows, m->cols,
-                           s.d_r[nb], s.d_c[nb], s.d_l[nb], m->d_counts + 2 * slots[b] + nb, 0, 0, 0);
-        SFE_LAUNCH_CHECK(ctx);
-        s.cur = nb;
-        s.has_cells = 1;
-        s.base_r = m->grow_r, s.base_c = m->grow_c;
-    }
-    return 0;
-}
-
-int sfe_map_cells(sfe_map *m, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, slot >= 0 && slot < (int)m->slots.size() && m->slots[slot].has_cells && n_out);
-    const MapSlot &s = m->slots[slot];
-    int32_t n = 0;
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SFE_HIP(ctx, hipMemcpy(&n, m->d_counts + 2 * slot + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
-    *n_out = n;
-    if (n > cap)
-        return sfe_set_err(ctx, SFE_ERR_CAP, "map cells: %d cells, room for %d", n, cap);
-    if (r_out)
-        SFE_HIP(ctx, hipMemcpy(r_out, s.d_r[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
-    if (c_out)
-        SFE_HIP(ctx, hipMemcpy(c_out, s.d_c[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
-    if (l_out)
-        SFE_HIP(ctx, hipMemcpy(l_out, s.d_l[s.cur], sizeof(float) * n, hipMemcpyDeviceToHost));
-    // the growth since the list was written (uint16 arithmetic, as the reference's keyframe.r += inc_r)
-    for (int i = 0; r_out && i < n; ++i)
-        r_out[i] = (uint16_t)(r_out[i] + (m->grow_r - s.base_r));
-    for (int i = 0; c_out && i < n; ++i)
-        c_out[i] = (uint16_t)(c_out[i] + (m->grow_c - s.base_c));
-    return 0;
-}
-
-int sfe_map_logodds(sfe_map *m, int slot, float *out, int cap)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, slot >= 0 && slot < (int)m->slots.size() && m->slots[slot].d_logodds && out);
-    const MapGeom &g = m->geoms[m->slots[slot].geom];
-    SFE_ARG(ctx, cap >= g.img_rows * g.img_cols);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SFE_HIP(ctx, hipMemcpy(out, m->slots[slot].d_logodds, sizeof(float) * g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int sfe_map_shape(sfe_map *m, int32_t *rows_cols_grow4)
-{
-    if (!m || !rows_cols_grow4)
-        return SFE_ERR_ARG;
-    rows_cols_grow4[0] = m->rows, rows_cols_grow4[1] = m->cols;
-    rows_cols_grow4[2] = m->grow_r, rows_cols_grow4[3] = m->grow_c;
-    return 0;
-}
-
-// which = 0: the map's grid; 1: the grid of the last sfe_map_frames call
-int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    const float *src = which ? m->d_frames : m->d_grid;
-    const long long n = which ? (long long)m->frames_rows * m->frames_cols : (long long)m->rows * m->cols;
-    SFE_ARG(ctx, out && src && cap >= n);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SFE_HIP(ctx, hipMemcpy(out, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-// get_occupancy_grid1(frames=...): a fresh zero grid, the listed slots' cells added in list order
-int sfe_map_frames(sfe_map *m, int n, const int32_t *slots)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    SFE_ARG(ctx, n >= 0 && (n == 0 || slots));
-    if (m->frames_rows != m->rows || m->frames_cols != m->cols) {
-        (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(m->d_frames);
-        m->d_frames = nullptr;
-        if (int rc = map_grid_alloc(m, &m->d_frames, (size_t)m->rows * m->cols))
-            return rc;
-        m->frames_rows = m->rows, m->frames_cols = m->cols;
-    } else
-        SFE_HIP(ctx, hipMemsetAsync(m->d_frames, 0, sizeof(float) * (size_t)m->rows * m->cols, ctx->stream));
-    for (int b = 0; b < n; ++b) {
-        SFE_ARG(ctx, slots[b] >= 0 && slots[b] < (int)m->slots.size() && m->slots[slots[b]].has_cells);
-        const MapSlot &s = m->slots[slots[b]];
-        const MapGeom &g = m->geoms[s.geom];
-        const unsigned nblk = (unsigned)((g.img_rows * g.img_cols + MAP_THREADS - 1) / MAP_THREADS);
-        hipLaunchKernelGGL(map_apply_kernel, dim3(nblk), dim3(MAP_THREADS), 0, ctx->stream, m->d_frames, m->rows, m->cols,
-                           s.d_r[s.cur], s.d_c[s.cur], s.d_l[s.cur], m->d_counts + 2 * slots[b] + s.cur,
-                           m->grow_r - s.base_r, m->grow_c - s.base_c, 0);
-        SFE_LAUNCH_CHECK(ctx);
-    }
-    return 0;
-}
-
-int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
-                   int8_t *occ_out)
-{
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    const float *src = which ? m->d_frames : m->d_grid;
-    SFE_ARG(ctx, src && (!which || (m->frames_rows == m->rows && m->frames_cols == m->cols)));
-    const int h = r1 - r0 + 1, w = c1 - c0 + 1;
-    SFE_ARG(ctx, out_h >= 0 && out_w >= 0 && (out_h * (long long)out_w == 0 || occ_out));
-    if ((long long)out_h * out_w == 0)
-        return 0;
-    SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && h > 0 && w > 0 && r1 < m->rows && c1 < m->cols);
-    SFE_ARG(ctx, resize || (out_h == h && out_w == w));
-    SFE_ARG(ctx, !resize || inv > 0);
-    const int64_t n = (int64_t)out_h * out_w;
-    int8_t *d = (int8_t *)map_buf(m, 2, (size_t)n);
-    if (!d)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map render scratch allocation failed");
-    hipLaunchKernelGGL(map_render_kernel, dim3((unsigned)((n + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
-                       ctx->stream, src, m->cols, r0, c0, h, w, out_h, out_w, inv, resize, d);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
-}
-
-} // extern "C"
-
-// ======================================================================================================================
-// sfe_mapset: S maps that advance together.  The kernels above run unchanged over (map, slot) jobs -- their job tables
-// carry pointers, so a job does not know which map it belongs to; what is new is the arena, the apply rounds and the
-// many-map render.
-//
-// Arena: fixed at creation for n_maps * max_keyframes slots of max_px pixels each.  Slot (map, k) owns
-//   logodds  float32 [max_px]
-//   r, c     uint16  [2][max_px] each   (the double-buffered cell list)
-//   l        float32 [2][max_px]
-// = 20 bytes per pixel, 20 * max_px bytes per keyframe (2.1 MB at the 105 k pixels of a 1024 x 512 ping at the shipped
-// skips), plus 8 bytes of counts.  Nothing is reallocated afterwards: a slot >= max_keyframes or an image of more than max_px
-// pixels is refused (SFE_ERR_CAP) before any state changes.  Grids are per map and grow on their own.
-namespace {
-
-struct SetSlot {
-    int geom = -1; // -1: unused
-    int cur = 0, has_cells = 0;
-    int base_r = 0, base_c = 0;
-};
-
-struct SetMap {
-    int rows = 0, cols = 0;
-    float *d_grid = nullptr, *d_frames = nullptr;
-    int frames_rows = 0, frames_cols = 0;
-    int grow_r = 0, grow_c = 0;
-};
-
+// --- apply (inc_grid / dec_grid) and render (get_occupancy_grid1) over job tables: one job serves one map as well as S ---
 // one ordered add / subtract of a cell list on its map's grid
 struct ApplyJob {
     float *grid;
@@ -957,7 +424,8 @@ __global__ __launch_bounds__(MAP_THREADS) void mapset_apply_kernel(const ApplyJo
     }
 }
 
-// map_render_kernel for many maps: job blockIdx.y writes its out_h x out_w image at out + out_off
+// get_occupancy_grid1 (mapping.py:306-355): crop, expit, INTER_NEAREST, int8(clip(100 p, 0, 100)); job blockIdx.y writes its
+// out_h x out_w image at out + out_off
 __global__ __launch_bounds__(MAP_THREADS) void mapset_render_kernel(const RenderJob *jobs, int8_t *out)
 {
     const RenderJob j = jobs[blockIdx.y];
@@ -1117,277 +585,8 @@ __global__ void feed_fill_kernel(const int32_t *__restrict__ pos, const int32_t 
     }
 }
 
-// the measurement of a call's jobs from its hits on the device (one pair per entry; a pair outside the image leaves no
-// hit): mask, filter, columns; one synchronisation
-int measure_run(const FeedView &v, const std::vector<MeasJob> &jobs, const int32_t *d_hits, const float *ktab, int n_ktab,
-                float miss32, float logit_miss, float hit32, float logit_hit)
-{
-    sfe_ctx *ctx = v.ctx;
-    const int n = (int)jobs.size();
-    int64_t px = 0;
-    int max_px = 0, max_cols = 0;
-    for (const MeasJob &j : jobs) {
-        px += j.slot_px;
-        max_px = max(max_px, j.slot_px);
-        max_cols = max(max_cols, j.img_cols);
-    }
-    MeasJob *d_jobs = buf_upload(ctx, v.buf[0], jobs.data(), jobs.size());
-    float *d_k = buf_upload(ctx, v.buf[2], ktab, (size_t)n_ktab);
-    uint8_t *d_mask = (uint8_t *)buf_get(ctx, v.buf[3], (size_t)px);
-    float *d_prob = (float *)buf_get(ctx, v.buf[4], sizeof(float) * (size_t)px);
-    int32_t *d_fh = (int32_t *)buf_get(ctx, v.buf[5], sizeof(int32_t) * (size_t)n * max_cols);
-    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map measurement scratch allocation / upload failed");
-    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
-    const unsigned ny = (unsigned)n;
-    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
-                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
-                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
-    *v.last_meas = jobs;
-    *v.last_meas_n = max_cols;
-    return 0;
-}
-
-// sfe_map_hit_table / sfe_mapset_hit_table
-int feed_hit_table(const FeedView &v, const float *bearings, int num_bearings, const double *breaks, const double *coef,
-                   int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double, int r_skip,
-                   int c_skip, int *id_out)
-{
-    sfe_ctx *ctx = v.ctx;
-    SFE_ARG(ctx, bearings && breaks && coef && id_out && num_bearings >= 2 && n_intervals >= 1 && n_intervals < (1 << 20));
-    SFE_ARG(ctx, margin > 0 && num_ranges >= 1 && range_resolution > 0 && r_skip >= 1 && c_skip >= 1);
-    for (int k = 0; k < n_intervals; ++k)
-        SFE_ARG(ctx, breaks[k] < breaks[k + 1]);
-    SFE_ARG(ctx, breaks[0] <= (double)bearings[0] && (double)bearings[num_bearings - 1] <= breaks[n_intervals]);
-    SFE_ARG(ctx, bearings[0] < bearings[num_bearings - 1]);
-    HitTab t;
-    double *d = nullptr;
-    const size_t nb = (size_t)n_intervals + 1, nc = 4 * (size_t)n_intervals;
-    SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(double) * (nb + nc)));
-    if (hipMemcpy(d, breaks, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d + nb, coef, sizeof(double) * nc, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map hit table upload failed");
-    }
-    t.breaks = d, t.coef = d + nb;
-    t.n_iv = n_intervals, t.num_ranges = num_ranges, t.num_bearings = num_bearings, t.r_skip = r_skip, t.c_skip = c_skip;
-    t.wide = range_in_double ? 1 : 0;
-    t.res32 = (float)range_resolution, t.res64 = range_resolution;
-    t.b_first = (double)bearings[0], t.b_last = (double)bearings[num_bearings - 1], t.margin = margin;
-    v.hit_tabs->push_back(t);
-    *id_out = (int)v.hit_tabs->size() - 1;
-    return 0;
-}
-
-// Phase one of a store-fed measurement (sonarfe.h: sfe_mapset_measure_store).  `slot_job(b, job)` is the owner's part: it
-// checks that keyframe b's slot may take an image of its geometry and fills the job's image size (and its log-odds image,
-// if the slot has one yet).  Nothing of the owner has changed when this returns, pending or not.
-template <class SlotJob>
-int feed_measure_store(const FeedView &fv, const char *who, sfe_cloud_store *store, int n, const int32_t *maps,
-                       const int32_t *slots, const int32_t *geoms, const int32_t *handles, const int32_t *tabs, double radius,
-                       int min_points, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
-                       const double *div, float miss32, float logit_miss, float hit32, float logit_hit, int32_t *n_points_out,
-                       int32_t *n_undecided_out, SlotJob slot_job)
-{
-    sfe_ctx *ctx = fv.ctx;
-    SFE_ARG(ctx, store && sfe_store_ctx(store) == ctx && n >= 0 && n <= 65535 && n_ktab >= 0 && (n_ktab == 0 || ktab));
-    SFE_ARG(ctx, n == 0 || (slots && geoms && handles && tabs && hrhc && k_off && div && n_points_out && n_undecided_out));
-    SFE_ARG(ctx, min_points <= 1 || radius >= 0);
-    FeedState &f = *fv.feed;
-    f.pending = false;
-    if (n == 0)
-        return 0;
-    SfeStoreView v;
-    if (int rc = sfe_store_view(store, &v))
-        return rc;
-    std::vector<MeasJob> jobs(n);
-    std::vector<FeedJob> fjobs(n);
-    int64_t px = 0, tot = 0;
-    int max_n = 0;
-    for (int b = 0; b < n; ++b) {
-        MeasJob &j = jobs[b];
-        j.logodds = nullptr;
-        if (int rc = slot_job(b, j))
-            return rc;
-        const int hd = handles[b];
-        if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "%s: cloud %d named (job %d), the store holds %d%s", who, hd, b, v.n_slots,
-                               (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
-        SFE_ARG(ctx, tabs[b] >= 0 && tabs[b] < (int)fv.hit_tabs->size());
-        const int cnt = v.cnt[hd];
-        j.hit_off = (int32_t)tot;
-        j.n_hits = cnt;
-        // a cloud without points is a keyframe without a measurement (hr < 0); one the filter empties keeps its kernel
-        j.hr = cnt ? hrhc[2 * b] : -1, j.hc = cnt ? hrhc[2 * b + 1] : 0;
-        j.k_off = cnt ? k_off[b] : 0;
-        j.div = cnt ? div[b] : 1.0;
-        SFE_ARG(ctx, j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
-        SFE_ARG(ctx, cnt == 0 || (j.hr >= 0 && j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab));
-        j.px_off = px;
-        px += j.slot_px;
-        fjobs[b].off = v.off[hd], fjobs[b].n = cnt, fjobs[b].hit_off = (int32_t)tot, fjobs[b].tab = tabs[b];
-        tot += cnt;
-        max_n = max(max_n, cnt);
-        SFE_ARG(ctx, tot < (1 << 30));
-    }
-    FeedJob *d_jobs = buf_stage(ctx, fv.buf[6], fjobs);
-    HitTab *d_tabs = buf_stage(ctx, fv.buf[10], *fv.hit_tabs);
-    int32_t *d_hits = (int32_t *)buf_get(ctx, fv.buf[7], sizeof(int32_t) * 2 * (size_t)(tot + 1));
-    uint8_t *d_keep = (uint8_t *)buf_get(ctx, fv.buf[8], (size_t)(tot + 1));
-    char *d_und = (char *)buf_get(ctx, fv.buf[9], sizeof(UndPoint) * (size_t)tot + sizeof(int32_t) * (size_t)n);
-    int32_t *h_cnt = (int32_t *)sfe_pinned_io(ctx, 3, sizeof(int32_t) * (size_t)n);
-    if (!d_jobs || !d_tabs || !d_hits || !d_keep || !d_und || !h_cnt)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "%s store feed scratch allocation / upload failed", who);
-    int32_t *d_cnt = (int32_t *)(d_und + sizeof(UndPoint) * (size_t)tot);
-    SFE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)n, ctx->stream));
-    if (max_n > 0) {
-        const dim3 grid((unsigned)((max_n + 255) / 256), (unsigned)n);
-        const bool filter = min_points > 1; // Mapping._hits
-        if (filter) {
-            hipLaunchKernelGGL(feed_radius_count_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs,
-                               (float)(radius * radius), min_points, d_keep);
-            SFE_LAUNCH_CHECK(ctx);
-        }
-        hipLaunchKernelGGL(feed_hit_cells_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs, d_tabs,
-                           filter ? (const uint8_t *)d_keep : nullptr, d_hits, (UndPoint *)d_und, d_cnt);
-        SFE_LAUNCH_CHECK(ctx);
-    }
-    SFE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (maps)
-        f.maps.assign(maps, maps + n);
-    else
-        f.maps.clear();
-    f.slots.assign(slots, slots + n), f.geoms.assign(geoms, geoms + n);
-    f.n_und.assign(h_cnt, h_cnt + n);
-    f.jobs = jobs;
-    f.ktab.assign(ktab, ktab + n_ktab);
-    f.miss32 = miss32, f.logit_miss = logit_miss, f.hit32 = hit32, f.logit_hit = logit_hit;
-    f.tot = (int)tot, f.tot_und = 0;
-    for (int b = 0; b < n; ++b) {
-        n_points_out[b] = jobs[b].n_hits;
-        n_undecided_out[b] = h_cnt[b];
-        f.tot_und += h_cnt[b];
-    }
-    f.pending = true; // until the owner runs the measurement: at once if no point is undecided
-    return 0;
-}
-
-// the undecided points of the pending call, by ascending entry in the hit buffer
-int feed_undecided(const FeedView &fv, float *xy_out, int32_t *pos_out, int cap)
-{
-    sfe_ctx *ctx = fv.ctx;
-    FeedState &f = *fv.feed;
-    SFE_ARG(ctx, f.pending && xy_out && pos_out && cap >= f.tot_und);
-    std::vector<UndPoint> und((size_t)f.tot_und);
-    size_t at = 0;
-    for (size_t b = 0; b < f.jobs.size(); ++b) {
-        if (!f.n_und[b])
-            continue;
-        SFE_HIP(ctx, hipMemcpyAsync(und.data() + at, (const UndPoint *)fv.buf[9].p + f.jobs[b].hit_off,
-                                    sizeof(UndPoint) * (size_t)f.n_und[b], hipMemcpyDeviceToHost, ctx->stream));
-        at += (size_t)f.n_und[b];
-    }
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    // (the device appended them in no fixed order)
-    std::sort(und.begin(), und.end(), [](const UndPoint &a, const UndPoint &b) { return a.pos < b.pos; });
-    for (size_t i = 0; i < und.size(); ++i) {
-        xy_out[2 * i] = und[i].x, xy_out[2 * i + 1] = und[i].y;
-        pos_out[i] = und[i].pos;
-    }
-    return 0;
-}
-
-// the host's cells of the pending call's undecided points into the hit buffer
-int feed_fill(const FeedView &fv, int n_cells, const int32_t *pos, const int32_t *cells)
-{
-    sfe_ctx *ctx = fv.ctx;
-    FeedState &f = *fv.feed;
-    SFE_ARG(ctx, f.pending && n_cells == f.tot_und && pos && cells);
-    for (int i = 0; i < n_cells; ++i)
-        SFE_ARG(ctx, pos[i] >= 0 && pos[i] < f.tot);
-    // (the keep flags have been read: their buffer takes the upload)
-    std::vector<int32_t> up(3 * (size_t)n_cells);
-    memcpy(up.data(), pos, sizeof(int32_t) * (size_t)n_cells);
-    memcpy(up.data() + n_cells, cells, sizeof(int32_t) * 2 * (size_t)n_cells);
-    int32_t *d_up = buf_stage(ctx, fv.buf[8], up);
-    if (!d_up)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map store feed: upload of the host's cells failed");
-    hipLaunchKernelGGL(feed_fill_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, d_up,
-                       d_up + n_cells, n_cells, (int32_t *)fv.buf[7].p);
-    SFE_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-// the second half of a store-fed measurement: every entry of the hit buffer is final
-int feed_finish(const FeedView &fv)
-{
-    FeedState &f = *fv.feed;
-    f.pending = false;
-    return measure_run(fv, f.jobs, (const int32_t *)fv.buf[7].p, f.ktab.data(), (int)f.ktab.size(), f.miss32, f.logit_miss,
-                       f.hit32, f.logit_hit);
-}
-
-FeedView map_view(sfe_map *m)
-{
-    return FeedView{m->ctx, m->buf, &m->hit_tabs, &m->feed, &m->last_meas, &m->last_meas_n};
-}
-
-// may `slot` take an image of geometry g?  Checks only (map_slot creates).
-int map_slot_check(sfe_map *m, int slot, int g)
-{
-    SFE_ARG(m->ctx, slot >= 0 && g >= 0 && g < (int)m->geoms.size());
-    SFE_ARG(m->ctx, slot >= (int)m->slots.size() || !m->slots[slot].d_logodds || m->slots[slot].geom == g);
-    return 0;
-}
-
-// the pending call's slots come into being, then its measurement runs
-int map_feed_finish(sfe_map *m)
-{
-    FeedState &f = m->feed;
-    for (size_t b = 0; b < f.jobs.size(); ++b) {
-        if (int rc = map_slot(m, f.slots[b], f.geoms[b])) {
-            f.pending = false;
-            return rc;
-        }
-        f.jobs[b].logodds = m->slots[f.slots[b]].d_logodds;
-    }
-    return feed_finish(map_view(m));
-}
-
-} // namespace
-
-struct sfe_mapset {
-    sfe_ctx *ctx = nullptr;
-    int n_maps = 0, max_kf = 0, max_px = 0;
-    std::vector<SetMap> maps;
-    std::vector<MapGeom> geoms;
-    std::vector<SetSlot> slots; // [map * max_kf + slot]
-    float *d_logodds = nullptr, *d_l = nullptr;
-    uint16_t *d_r = nullptr, *d_c = nullptr;
-    int32_t *d_counts = nullptr; // [map * max_kf + slot][2]
-    MapBuf buf[11]; // 6 .. 10: the store feed's job tables, hit buffer, keep flags, undecided lists and counters
-    int last_meas_n = 0;
-    std::vector<MeasJob> last_meas;
-    long long apply_launches = 0; // launches of mapset_apply_kernel so far
-    // the store feed: hit tables (device copies owned here), and the call that waits for the host's cells
-    std::vector<HitTab> hit_tabs;
-    FeedState feed;
-};
-
-namespace {
 
 inline size_t set_idx(const sfe_mapset *ms, int map, int slot) { return (size_t)map * ms->max_kf + slot; }
-inline float *set_logodds(sfe_mapset *ms, size_t idx) { return ms->d_logodds + idx * ms->max_px; }
-inline uint16_t *set_r(sfe_mapset *ms, size_t idx, int b) { return ms->d_r + (2 * idx + b) * ms->max_px; }
-inline uint16_t *set_c(sfe_mapset *ms, size_t idx, int b) { return ms->d_c + (2 * idx + b) * ms->max_px; }
-inline float *set_l(sfe_mapset *ms, size_t idx, int b) { return ms->d_l + (2 * idx + b) * ms->max_px; }
 
 int set_grid_alloc(sfe_mapset *ms, float **d, size_t n)
 {
@@ -1402,9 +601,12 @@ int set_slot_check(sfe_mapset *ms, int map, int slot, int g)
 {
     sfe_ctx *ctx = ms->ctx;
     SFE_ARG(ctx, map >= 0 && map < ms->n_maps && slot >= 0 && g >= 0 && g < (int)ms->geoms.size());
-    if (slot >= ms->max_kf)
+    if (slot >= ms->max_kf) {
+        if (!ms->arena)
+            return 0; // set_slot_bind makes room
         return sfe_set_err(ctx, SFE_ERR_CAP, "map set: keyframe slot %d of map %d, room for %d keyframes per map", slot, map,
                            ms->max_kf);
+    }
     const SetSlot &s = ms->slots[set_idx(ms, map, slot)];
     SFE_ARG(ctx, s.geom < 0 || s.geom == g);
     return 0;
@@ -1418,18 +620,69 @@ int set_slot_used(sfe_mapset *ms, int map, int slot)
     return 0;
 }
 
-template <class T>
-T *set_stage(sfe_mapset *ms, int i, const std::vector<T> &jobs)
+void set_slot_free(SetSlot &s)
 {
-    return buf_stage(ms->ctx, ms->buf[i], jobs);
+    (void)hipFree(s.d_logodds);
+    s.d_logodds = nullptr;
+    for (int b = 0; b < 2; ++b) {
+        (void)hipFree(s.d_r[b]);
+        (void)hipFree(s.d_c[b]);
+        (void)hipFree(s.d_l[b]);
+        s.d_r[b] = s.d_c[b] = nullptr;
+        s.d_l[b] = nullptr;
+    }
+    s.px = 0;
 }
 
-template <class T>
-T *set_upload(sfe_mapset *ms, int i, const T *h, size_t n)
+// The storage of (map, slot) for an image of geometry g, when its measurement is about to run.  The arena's pointers were
+// computed at creation.  On demand (one map): the slot vector and the counts table grow to hold the slot, live counts
+// moving to the new table, and the slot's buffers are allocated at exactly the geometry's pixel count.
+int set_slot_bind(sfe_mapset *ms, int map, int slot, int g)
 {
-    return buf_upload(ms->ctx, ms->buf[i], h, n);
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = set_slot_check(ms, map, slot, g))
+        return rc;
+    if (ms->arena)
+        return 0;
+    if (slot >= ms->max_kf) {
+        if (slot >= ms->counts_cap) {
+            const int cap = 2 * (slot + 1) + 64;
+            int32_t *d = nullptr;
+            SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(int32_t) * 2 * cap));
+            SFE_HIP(ctx, hipMemsetAsync(d, 0, sizeof(int32_t) * 2 * cap, ctx->stream));
+            if (ms->d_counts) {
+                SFE_HIP(ctx, hipMemcpyAsync(d, ms->d_counts, sizeof(int32_t) * 2 * ms->counts_cap, hipMemcpyDeviceToDevice,
+                                            ctx->stream));
+                SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                (void)hipFree(ms->d_counts);
+            }
+            ms->d_counts = d;
+            ms->counts_cap = cap;
+        }
+        ms->slots.resize(slot + 1);
+        ms->max_kf = slot + 1;
+        for (size_t i = 0; i < ms->slots.size(); ++i)
+            ms->slots[i].d_n = ms->d_counts + 2 * i;
+    }
+    SetSlot &s = ms->slots[set_idx(ms, map, slot)]; // (one map: set_create)
+    const int px = ms->geoms[g].img_rows * ms->geoms[g].img_cols;
+    if (s.px == px)
+        return 0;
+    if (s.d_logodds) { // (what a measurement that failed left behind)
+        (void)hipStreamSynchronize(ctx->stream);
+        set_slot_free(s);
+    }
+    SFE_HIP(ctx, hipMalloc((void **)&s.d_logodds, px * sizeof(float)));
+    for (int b = 0; b < 2; ++b) {
+        SFE_HIP(ctx, hipMalloc((void **)&s.d_r[b], px * sizeof(uint16_t)));
+        SFE_HIP(ctx, hipMalloc((void **)&s.d_c[b], px * sizeof(uint16_t)));
+        SFE_HIP(ctx, hipMalloc((void **)&s.d_l[b], px * sizeof(float)));
+    }
+    s.px = px;
+    return 0;
 }
 
+// pose4 per keyframe: {cos, sin, x, y}; origin2: {y0, x0}
 int set_fit_jobs(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const double *pose4, const double *origin2,
                  std::vector<FitJob> &jobs, int &max_px)
 {
@@ -1438,31 +691,32 @@ int set_fit_jobs(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot
     for (int b = 0; b < n; ++b) {
         if (int rc = set_slot_used(ms, maps[b], slots[b]))
             return rc;
-        const size_t idx = set_idx(ms, maps[b], slots[b]);
-        const MapGeom &g = ms->geoms[ms->slots[idx].geom];
+        const SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[b])];
+        const MapGeom &g = ms->geoms[s.geom];
         FitJob &j = jobs[b];
         j.xy = g.d_xy;
         j.n_px = g.img_rows * g.img_cols;
         j.c = pose4[4 * b], j.s = pose4[4 * b + 1], j.tx = pose4[4 * b + 2], j.ty = pose4[4 * b + 3];
         j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1];
-        j.logodds = set_logodds(ms, idx);
+        j.logodds = s.d_logodds;
         max_px = max(max_px, j.n_px);
     }
     return 0;
 }
 
-// rounds of applies: round i holds the i-th apply of every map that has one; a launch per round
-int set_run_rounds(sfe_mapset *ms, int buf, const std::vector<std::vector<ApplyJob>> &rounds)
+// rounds of applies: round i holds the i-th apply of every map that has one
+std::vector<ApplyJob> set_flat_rounds(const std::vector<std::vector<ApplyJob>> &rounds)
 {
-    sfe_ctx *ctx = ms->ctx;
     std::vector<ApplyJob> flat;
     for (const auto &r : rounds)
         flat.insert(flat.end(), r.begin(), r.end());
-    if (flat.empty())
-        return 0;
-    ApplyJob *d = set_stage(ms, buf, flat);
-    if (!d)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: apply job table upload failed");
+    return flat;
+}
+
+// ... a launch per round; d: the rounds' jobs back to back on the device
+int set_launch_rounds(sfe_mapset *ms, const ApplyJob *d, const std::vector<std::vector<ApplyJob>> &rounds)
+{
+    sfe_ctx *ctx = ms->ctx;
     size_t off = 0;
     for (const auto &r : rounds) {
         int px = 1;
@@ -1477,58 +731,152 @@ int set_run_rounds(sfe_mapset *ms, int buf, const std::vector<std::vector<ApplyJ
     return 0;
 }
 
-FeedView set_view(sfe_mapset *ms)
+// the jobs' slots get their storage (before any upload from pageable memory is in flight)
+int set_bind_jobs(sfe_mapset *ms, std::vector<MeasJob> &jobs, const int32_t *maps, const int32_t *slots, const int32_t *geoms)
 {
-    return FeedView{ms->ctx, ms->buf, &ms->hit_tabs, &ms->feed, &ms->last_meas, &ms->last_meas_n};
+    for (size_t b = 0; b < jobs.size(); ++b) {
+        if (int rc = set_slot_bind(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+        jobs[b].logodds = ms->slots[set_idx(ms, maps[b], slots[b])].d_logodds;
+    }
+    return 0;
 }
 
-// the measurement of a call's jobs from its hits on the device; then the slots take their geometries
+// the measurement of a call's jobs from its hits on the device (one pair per entry; a pair outside the image leaves no
+// hit): mask, filter, columns; one synchronisation; then the slots take their geometries
 int set_measure_run(sfe_mapset *ms, const std::vector<MeasJob> &jobs, const int32_t *maps, const int32_t *slots,
                     const int32_t *geoms, const int32_t *d_hits, const float *ktab, int n_ktab, float miss32, float logit_miss,
                     float hit32, float logit_hit)
 {
-    if (int rc = measure_run(set_view(ms), jobs, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit))
-        return rc;
-    for (size_t b = 0; b < jobs.size(); ++b)
+    sfe_ctx *ctx = ms->ctx;
+    const int n = (int)jobs.size();
+    int64_t px = 0;
+    int max_px = 0, max_cols = 0;
+    for (const MeasJob &j : jobs) {
+        px += j.slot_px;
+        max_px = max(max_px, j.slot_px);
+        max_cols = max(max_cols, j.img_cols);
+    }
+    MeasJob *d_jobs = buf_upload(ctx, ms->buf[0], jobs.data(), jobs.size());
+    float *d_k = buf_upload(ctx, ms->buf[2], ktab, (size_t)n_ktab);
+    uint8_t *d_mask = (uint8_t *)buf_get(ctx, ms->buf[3], (size_t)px);
+    float *d_prob = (float *)buf_get(ctx, ms->buf[4], sizeof(float) * (size_t)px);
+    int32_t *d_fh = (int32_t *)buf_get(ctx, ms->buf[5], sizeof(int32_t) * (size_t)n * max_cols);
+    if (!d_jobs || !d_hits || !d_k || !d_mask || !d_prob || !d_fh)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map measurement scratch allocation / upload failed");
+    SFE_HIP(ctx, hipMemsetAsync(d_mask, 0, (size_t)px, ctx->stream));
+    const unsigned ny = (unsigned)n;
+    hipLaunchKernelGGL(map_hits_kernel, dim3(4, ny), dim3(MAP_THREADS), 0, ctx->stream, d_jobs, d_hits, d_mask);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_filter_kernel, dim3((max_px + MAP_THREADS - 1) / MAP_THREADS, ny), dim3(MAP_THREADS), 0,
+                       ctx->stream, d_jobs, d_k, d_mask, d_prob, hit32);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_columns_kernel, dim3((max_cols + 63) / 64, ny), dim3(64), 0, ctx->stream, d_jobs, d_prob, d_fh,
+                       miss32, logit_miss, hit32, logit_hit, (int64_t)max_cols);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the uploads above read pageable memory
+    ms->last_meas = jobs;
+    ms->last_meas_n = max_cols;
+    for (int b = 0; b < n; ++b)
         ms->slots[set_idx(ms, maps[b], slots[b])].geom = geoms[b];
     return 0;
 }
 
-// the second half of a store-fed measurement: every entry of the hit buffer is final
-int set_feed_finish(sfe_mapset *ms)
+// the undecided points of the pending call, by ascending entry in the hit buffer
+int feed_undecided(sfe_mapset *ms, float *xy_out, int32_t *pos_out, int cap)
+{
+    sfe_ctx *ctx = ms->ctx;
+    FeedState &f = ms->feed;
+    SFE_ARG(ctx, f.pending && xy_out && pos_out && cap >= f.tot_und);
+    std::vector<UndPoint> und((size_t)f.tot_und);
+    size_t at = 0;
+    for (size_t b = 0; b < f.jobs.size(); ++b) {
+        if (!f.n_und[b])
+            continue;
+        SFE_HIP(ctx, hipMemcpyAsync(und.data() + at, (const UndPoint *)ms->buf[9].p + f.jobs[b].hit_off,
+                                    sizeof(UndPoint) * (size_t)f.n_und[b], hipMemcpyDeviceToHost, ctx->stream));
+        at += (size_t)f.n_und[b];
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // (the device appended them in no fixed order)
+    std::sort(und.begin(), und.end(), [](const UndPoint &a, const UndPoint &b) { return a.pos < b.pos; });
+    for (size_t i = 0; i < und.size(); ++i) {
+        xy_out[2 * i] = und[i].x, xy_out[2 * i + 1] = und[i].y;
+        pos_out[i] = und[i].pos;
+    }
+    return 0;
+}
+
+// the host's cells of the pending call's undecided points into the hit buffer
+int feed_fill(sfe_mapset *ms, int n_cells, const int32_t *pos, const int32_t *cells)
+{
+    sfe_ctx *ctx = ms->ctx;
+    FeedState &f = ms->feed;
+    SFE_ARG(ctx, f.pending && n_cells == f.tot_und && pos && cells);
+    for (int i = 0; i < n_cells; ++i)
+        SFE_ARG(ctx, pos[i] >= 0 && pos[i] < f.tot);
+    // (the keep flags have been read: their buffer takes the upload)
+    std::vector<int32_t> up(3 * (size_t)n_cells);
+    memcpy(up.data(), pos, sizeof(int32_t) * (size_t)n_cells);
+    memcpy(up.data() + n_cells, cells, sizeof(int32_t) * 2 * (size_t)n_cells);
+    int32_t *d_up = buf_stage(ctx, ms->buf[8], up);
+    if (!d_up)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map store feed: upload of the host's cells failed");
+    hipLaunchKernelGGL(feed_fill_kernel, dim3((unsigned)((n_cells + 255) / 256)), dim3(256), 0, ctx->stream, d_up,
+                       d_up + n_cells, n_cells, (int32_t *)ms->buf[7].p);
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+// the second half of a store-fed measurement: every entry of the hit buffer is final.  Only now do the call's slots get their
+// storage, so a refused or dropped call leaves none behind.
+int feed_finish(sfe_mapset *ms)
 {
     FeedState &f = ms->feed;
     f.pending = false;
+    if (int rc = set_bind_jobs(ms, f.jobs, f.maps.data(), f.slots.data(), f.geoms.data()))
+        return rc;
     return set_measure_run(ms, f.jobs, f.maps.data(), f.slots.data(), f.geoms.data(), (const int32_t *)ms->buf[7].p,
                            f.ktab.data(), (int)f.ktab.size(), f.miss32, f.logit_miss, f.hit32, f.logit_hit);
 }
 
-} // namespace
-
-extern "C" {
-
-int sfe_mapset_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyframes, int max_px, sfe_mapset **out)
+// a set of n_maps zero grids; max_keyframes > 0: slots in an arena of that many per map, max_px pixels each; 0: on demand
+int set_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyframes, int max_px, sfe_mapset **out)
 {
-    if (int rc = sfe_use(ctx))
-        return rc;
     SFE_ARG(ctx, out != nullptr && n_maps > 0 && n_maps <= 4096 && rows > 0 && cols > 0 && (long long)rows * cols < (1LL << 31));
-    SFE_ARG(ctx, max_keyframes > 0 && max_px > 0 && max_px < (1 << 30));
     SFE_ARG(ctx, (long long)n_maps * max_keyframes < (1LL << 28));
+    SFE_ARG(ctx, max_keyframes > 0 || n_maps == 1); // on demand the slot vector grows, so it is one map's
     sfe_mapset *ms = new sfe_mapset();
     ms->ctx = ctx;
+    ms->arena = max_keyframes > 0;
     ms->n_maps = n_maps, ms->max_kf = max_keyframes, ms->max_px = max_px;
     ms->maps.resize(n_maps);
     const size_t n_slots = (size_t)n_maps * max_keyframes, px = n_slots * (size_t)max_px;
     ms->slots.resize(n_slots);
-    bool ok = hipMalloc((void **)&ms->d_logodds, px * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&ms->d_l, 2 * px * sizeof(float)) == hipSuccess &&
-              hipMalloc((void **)&ms->d_r, 2 * px * sizeof(uint16_t)) == hipSuccess &&
-              hipMalloc((void **)&ms->d_c, 2 * px * sizeof(uint16_t)) == hipSuccess &&
-              hipMalloc((void **)&ms->d_counts, 2 * n_slots * sizeof(int32_t)) == hipSuccess &&
-              hipMemsetAsync(ms->d_counts, 0, 2 * n_slots * sizeof(int32_t), ctx->stream) == hipSuccess;
-    int rc = ok ? 0
-                : sfe_set_err(ctx, SFE_ERR_HIP, "map set: arena of %d maps x %d keyframes x %d pixels (%zu bytes) failed",
-                              n_maps, max_keyframes, max_px, px * 20);
+    int rc = 0;
+    if (ms->arena) {
+        bool ok = hipMalloc((void **)&ms->d_logodds, px * sizeof(float)) == hipSuccess &&
+                  hipMalloc((void **)&ms->d_l, 2 * px * sizeof(float)) == hipSuccess &&
+                  hipMalloc((void **)&ms->d_r, 2 * px * sizeof(uint16_t)) == hipSuccess &&
+                  hipMalloc((void **)&ms->d_c, 2 * px * sizeof(uint16_t)) == hipSuccess &&
+                  hipMalloc((void **)&ms->d_counts, 2 * n_slots * sizeof(int32_t)) == hipSuccess &&
+                  hipMemsetAsync(ms->d_counts, 0, 2 * n_slots * sizeof(int32_t), ctx->stream) == hipSuccess;
+        if (!ok)
+            rc = sfe_set_err(ctx, SFE_ERR_HIP, "map set: arena of %d maps x %d keyframes x %d pixels (%zu bytes) failed", n_maps,
+                             max_keyframes, max_px, px * 20);
+        ms->counts_cap = (int)n_slots;
+        for (size_t i = 0; i < n_slots && !rc; ++i) {
+            SetSlot &s = ms->slots[i];
+            s.px = max_px;
+            s.d_logodds = ms->d_logodds + i * max_px;
+            for (int b = 0; b < 2; ++b) {
+                s.d_r[b] = ms->d_r + (2 * i + b) * max_px;
+                s.d_c[b] = ms->d_c + (2 * i + b) * max_px;
+                s.d_l[b] = ms->d_l + (2 * i + b) * max_px;
+            }
+            s.d_n = ms->d_counts + 2 * i;
+        }
+    }
     for (int m = 0; m < n_maps && !rc; ++m) {
         ms->maps[m].rows = rows, ms->maps[m].cols = cols;
         rc = set_grid_alloc(ms, &ms->maps[m].d_grid, (size_t)rows * cols);
@@ -1539,6 +887,22 @@ int sfe_mapset_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyf
     }
     *out = ms;
     return 0;
+}
+
+// an sfe_map is a set of one map: its handle, and the `maps` argument of a call over n of its slots
+sfe_mapset *one(sfe_map *m) { return reinterpret_cast<sfe_mapset *>(m); }
+std::vector<int32_t> map0(int n) { return std::vector<int32_t>(n > 0 ? n : 0, 0); }
+
+} // namespace
+
+extern "C" {
+
+int sfe_mapset_create(sfe_ctx *ctx, int n_maps, int rows, int cols, int max_keyframes, int max_px, sfe_mapset **out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, max_keyframes > 0 && max_px > 0 && max_px < (1 << 30));
+    return set_create(ctx, n_maps, rows, cols, max_keyframes, max_px, out);
 }
 
 void sfe_mapset_destroy(sfe_mapset *ms)
@@ -1553,6 +917,9 @@ void sfe_mapset_destroy(sfe_mapset *ms)
     }
     for (auto &g : ms->geoms)
         (void)hipFree(g.d_xy);
+    for (auto &s : ms->slots)
+        if (!ms->arena)
+            set_slot_free(s);
     (void)hipFree(ms->d_logodds);
     (void)hipFree(ms->d_l);
     (void)hipFree(ms->d_r);
@@ -1573,7 +940,7 @@ int sfe_mapset_geometry(sfe_mapset *ms, const float *sonar_xy, int img_rows, int
     if (int rc = sfe_use(ctx))
         return rc;
     SFE_ARG(ctx, sonar_xy && id_out && img_rows > 0 && img_cols > 0 && (long long)img_rows * img_cols < (1 << 30));
-    if ((long long)img_rows * img_cols > ms->max_px)
+    if (ms->arena && (long long)img_rows * img_cols > ms->max_px)
         return sfe_set_err(ctx, SFE_ERR_CAP, "map set: a %d x %d image, room for %d pixels per keyframe", img_rows, img_cols,
                            ms->max_px);
     MapGeom g;
@@ -1600,11 +967,13 @@ int sfe_mapset_set_logodds(sfe_mapset *ms, int n, const int32_t *maps, const int
             return rc;
     size_t off = 0;
     for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_bind(ms, maps[b], slots[b], geoms[b]))
+            return rc;
         const MapGeom &g = ms->geoms[geoms[b]];
-        const size_t px = (size_t)g.img_rows * g.img_cols, idx = set_idx(ms, maps[b], slots[b]);
-        SFE_HIP(ctx, hipMemcpyAsync(set_logodds(ms, idx), logodds + off, sizeof(float) * px, hipMemcpyHostToDevice,
-                                    ctx->stream));
-        ms->slots[idx].geom = geoms[b];
+        const size_t px = (size_t)g.img_rows * g.img_cols;
+        SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[b])];
+        SFE_HIP(ctx, hipMemcpyAsync(s.d_logodds, logodds + off, sizeof(float) * px, hipMemcpyHostToDevice, ctx->stream));
+        s.geom = geoms[b];
         off += px;
     }
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1637,6 +1006,7 @@ int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
         j.n_hits = hit_off[b + 1] - hit_off[b];
         j.hr = hrhc[2 * b], j.hc = hrhc[2 * b + 1];
         j.k_off = k_off[b];
+        // hr < 0: no points at all, the image is all miss_prob (mapping.py:224-225)
         SFE_ARG(ctx, j.n_hits >= 0 && j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
         if (j.hr < 0)
             SFE_ARG(ctx, j.n_hits == 0);
@@ -1644,12 +1014,13 @@ int sfe_mapset_measure(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
             SFE_ARG(ctx, j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab);
         j.div = div[b];
         j.px_off = px;
-        j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
         px += j.slot_px;
     }
     const int n_hit_tot = hit_off[n] - hit_off[0] + 1;
     SFE_ARG(ctx, hit_off[0] == 0 && n_hit_tot >= 1 && (n_hit_tot <= 1 || hits) && (n_ktab == 0 || ktab));
-    int32_t *d_hits = set_upload(ms, 1, hits, 2 * (size_t)(n_hit_tot - 1));
+    if (int rc = set_bind_jobs(ms, jobs, maps, slots, geoms))
+        return rc;
+    int32_t *d_hits = buf_upload(ctx, ms->buf[1], hits, 2 * (size_t)(n_hit_tot - 1));
     return set_measure_run(ms, jobs, maps, slots, geoms, d_hits, ktab, n_ktab, miss32, logit_miss, hit32, logit_hit);
 }
 
@@ -1692,8 +1063,8 @@ int sfe_mapset_fit_bounds(sfe_mapset *ms, int n, const int32_t *maps, const int3
     std::vector<int32_t> mm(4 * (size_t)n);
     for (int b = 0; b < n; ++b)
         mm[4 * b] = INT_MAX, mm[4 * b + 1] = INT_MIN, mm[4 * b + 2] = INT_MAX, mm[4 * b + 3] = INT_MIN;
-    FitJob *d_jobs = set_upload(ms, 0, jobs.data(), jobs.size());
-    int32_t *d_mm = set_upload(ms, 1, mm.data(), mm.size());
+    FitJob *d_jobs = buf_upload(ctx, ms->buf[0], jobs.data(), jobs.size());
+    int32_t *d_mm = buf_upload(ctx, ms->buf[1], mm.data(), mm.size());
     if (!d_jobs || !d_mm)
         return sfe_set_err(ctx, SFE_ERR_HIP, "map set fit scratch allocation / upload failed");
     const unsigned gx = (unsigned)min((max_px + MAP_THREADS - 1) / MAP_THREADS, 64);
@@ -1785,34 +1156,29 @@ int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *
         j.win_off = win; // each keyframe's own window, back to back: the largest map sizes nothing
         win += (int64_t)j.wh * j.ww;
         const int nb = 1 - s.cur;
-        j.out_r = set_r(ms, idx, nb), j.out_c = set_c(ms, idx, nb), j.out_l = set_l(ms, idx, nb);
-        j.out_n = ms->d_counts + 2 * idx + nb;
+        j.out_r = s.d_r[nb], j.out_c = s.d_c[nb], j.out_l = s.d_l[nb];
+        j.out_n = s.d_n + nb;
     }
     SFE_ARG(ctx, win < (1LL << 40));
-    FitJob *d_jobs = set_stage(ms, 0, jobs);
+    // room for both job tables (the fits, then up to two applies per fit) and the windows, before any state changes
+    static_assert(sizeof(FitJob) % alignof(ApplyJob) == 0, "the apply jobs follow the fit jobs in one table");
+    const size_t fit_bytes = sizeof(FitJob) * (size_t)n;
     int32_t *d_win = (int32_t *)buf_get(ctx, ms->buf[1], sizeof(int32_t) * (size_t)win);
-    if (!d_jobs || !d_win)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set fit scratch allocation / upload failed");
-    SFE_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d_win, EMPTY_SLOT, (size_t)win, ctx->stream));
-    hipLaunchKernelGGL(map_scatter_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
-                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution, d_win);
-    SFE_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)n), dim3(COMPACT_THREADS), 0, ctx->stream, d_jobs, d_win);
-    SFE_LAUNCH_CHECK(ctx);
+    if (!buf_get(ctx, ms->buf[0], fit_bytes + 2 * sizeof(ApplyJob) * (size_t)n) || !d_win)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set fit scratch allocation failed");
     // the float32 history of every cell as the reference writes it, per map: for each of its keyframes in call order, dec
     // then inc.  Maps do not share cells, so the i-th apply of every map goes into round i.
     std::vector<std::vector<ApplyJob>> rounds;
     std::vector<int> seq(ms->n_maps, 0);
     for (int b = 0; b < n; ++b) {
-        const size_t idx = set_idx(ms, maps[b], slots[b]);
-        SetSlot &s = ms->slots[idx];
+        SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[b])];
         SetMap &m = ms->maps[maps[b]];
         ApplyJob a;
         a.grid = m.d_grid, a.rows = m.rows, a.cols = m.cols, a.n_px = jobs[b].n_px;
         for (int pass = dec[b] ? 0 : 1; pass < 2; ++pass) {
             const int o = pass ? 1 - s.cur : s.cur;
-            a.r = set_r(ms, idx, o), a.c = set_c(ms, idx, o), a.l = set_l(ms, idx, o);
-            a.n = ms->d_counts + 2 * idx + o;
+            a.r = s.d_r[o], a.c = s.d_c[o], a.l = s.d_l[o];
+            a.n = s.d_n + o;
             a.dr = pass ? 0 : m.grow_r - s.base_r, a.dc = pass ? 0 : m.grow_c - s.base_c;
             a.sub = pass ? 0 : 1;
             const int round = seq[maps[b]]++;
@@ -1824,7 +1190,22 @@ int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *
         s.has_cells = 1;
         s.base_r = m.grow_r, s.base_c = m.grow_c;
     }
-    return set_run_rounds(ms, 2, rounds);
+    // both job tables in one upload through pinned staging: the call only enqueues (no synchronisation per batch)
+    const std::vector<ApplyJob> flat = set_flat_rounds(rounds);
+    std::vector<char> tab(fit_bytes + sizeof(ApplyJob) * flat.size());
+    memcpy(tab.data(), jobs.data(), fit_bytes);
+    memcpy(tab.data() + fit_bytes, flat.data(), sizeof(ApplyJob) * flat.size());
+    char *d_tab = buf_stage(ctx, ms->buf[0], tab);
+    if (!d_tab)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: fit / apply job table upload failed");
+    const FitJob *d_jobs = (const FitJob *)d_tab;
+    SFE_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)d_win, EMPTY_SLOT, (size_t)win, ctx->stream));
+    hipLaunchKernelGGL(map_scatter_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
+                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs, resolution, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(map_compact_kernel, dim3((unsigned)n), dim3(COMPACT_THREADS), 0, ctx->stream, d_jobs, d_win);
+    SFE_LAUNCH_CHECK(ctx);
+    return set_launch_rounds(ms, (const ApplyJob *)(d_tab + fit_bytes), rounds);
 }
 
 int sfe_mapset_cells(sfe_mapset *ms, int map, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out)
@@ -1836,22 +1217,22 @@ int sfe_mapset_cells(sfe_mapset *ms, int map, int slot, uint16_t *r_out, uint16_
         return rc;
     if (int rc = set_slot_used(ms, map, slot))
         return rc;
-    const size_t idx = set_idx(ms, map, slot);
-    const SetSlot &s = ms->slots[idx];
+    const SetSlot &s = ms->slots[set_idx(ms, map, slot)];
     const SetMap &m = ms->maps[map];
     SFE_ARG(ctx, s.has_cells && n_out);
     int32_t n = 0;
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SFE_HIP(ctx, hipMemcpy(&n, ms->d_counts + 2 * idx + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
+    SFE_HIP(ctx, hipMemcpy(&n, s.d_n + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
     *n_out = n;
     if (n > cap)
         return sfe_set_err(ctx, SFE_ERR_CAP, "map set cells: %d cells, room for %d", n, cap);
     if (r_out)
-        SFE_HIP(ctx, hipMemcpy(r_out, set_r(ms, idx, s.cur), sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+        SFE_HIP(ctx, hipMemcpy(r_out, s.d_r[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     if (c_out)
-        SFE_HIP(ctx, hipMemcpy(c_out, set_c(ms, idx, s.cur), sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+        SFE_HIP(ctx, hipMemcpy(c_out, s.d_c[s.cur], sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     if (l_out)
-        SFE_HIP(ctx, hipMemcpy(l_out, set_l(ms, idx, s.cur), sizeof(float) * n, hipMemcpyDeviceToHost));
+        SFE_HIP(ctx, hipMemcpy(l_out, s.d_l[s.cur], sizeof(float) * n, hipMemcpyDeviceToHost));
+    // the growth since the list was written (uint16 arithmetic, as the reference's keyframe.r += inc_r)
     for (int i = 0; r_out && i < n; ++i)
         r_out[i] = (uint16_t)(r_out[i] + (m.grow_r - s.base_r));
     for (int i = 0; c_out && i < n; ++i)
@@ -1868,11 +1249,11 @@ int sfe_mapset_logodds(sfe_mapset *ms, int map, int slot, float *out, int cap)
         return rc;
     if (int rc = set_slot_used(ms, map, slot))
         return rc;
-    const size_t idx = set_idx(ms, map, slot);
-    const MapGeom &g = ms->geoms[ms->slots[idx].geom];
+    const SetSlot &s = ms->slots[set_idx(ms, map, slot)];
+    const MapGeom &g = ms->geoms[s.geom];
     SFE_ARG(ctx, out && cap >= g.img_rows * g.img_cols);
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SFE_HIP(ctx, hipMemcpy(out, set_logodds(ms, idx), sizeof(float) * g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
+    SFE_HIP(ctx, hipMemcpy(out, s.d_logodds, sizeof(float) * g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -1894,6 +1275,7 @@ int sfe_mapset_apply_launches(sfe_mapset *ms, long long *n_out)
     return 0;
 }
 
+// which = 0: the map's grid; 1: the grid of its last sfe_mapset_frames call
 int sfe_mapset_read_grid(sfe_mapset *ms, int map, int which, float *out, long long cap)
 {
     if (!ms)
@@ -1911,6 +1293,7 @@ int sfe_mapset_read_grid(sfe_mapset *ms, int map, int which, float *out, long lo
     return 0;
 }
 
+// get_occupancy_grid1(frames=...): per map a fresh zero grid, the listed slots' cells added in list order
 int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int32_t *slot_off, const int32_t *slots)
 {
     if (!ms)
@@ -1944,13 +1327,12 @@ int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int
         } else
             SFE_HIP(ctx, hipMemsetAsync(m.d_frames, 0, sizeof(float) * (size_t)m.rows * m.cols, ctx->stream));
         for (int i = slot_off[b]; i < slot_off[b + 1]; ++i) {
-            const size_t idx = set_idx(ms, maps[b], slots[i]);
-            const SetSlot &s = ms->slots[idx];
+            const SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[i])];
             const MapGeom &g = ms->geoms[s.geom];
             ApplyJob a;
             a.grid = m.d_frames, a.rows = m.rows, a.cols = m.cols, a.n_px = g.img_rows * g.img_cols;
-            a.r = set_r(ms, idx, s.cur), a.c = set_c(ms, idx, s.cur), a.l = set_l(ms, idx, s.cur);
-            a.n = ms->d_counts + 2 * idx + s.cur;
+            a.r = s.d_r[s.cur], a.c = s.d_c[s.cur], a.l = s.d_l[s.cur];
+            a.n = s.d_n + s.cur;
             a.dr = m.grow_r - s.base_r, a.dc = m.grow_c - s.base_c, a.sub = 0;
             const int round = i - slot_off[b];
             if (round >= (int)rounds.size())
@@ -1958,7 +1340,13 @@ int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int
             rounds[round].push_back(a);
         }
     }
-    return set_run_rounds(ms, 2, rounds);
+    const std::vector<ApplyJob> flat = set_flat_rounds(rounds);
+    if (flat.empty())
+        return 0;
+    const ApplyJob *d = buf_stage(ctx, ms->buf[2], flat);
+    if (!d)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set: apply job table upload failed");
+    return set_launch_rounds(ms, d, rounds);
 }
 
 int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *which, const int32_t *box4,
@@ -1997,7 +1385,7 @@ int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t 
     }
     if (jobs.empty())
         return 0;
-    RenderJob *d_jobs = set_stage(ms, 0, jobs);
+    RenderJob *d_jobs = buf_stage(ctx, ms->buf[0], jobs);
     int8_t *d = (int8_t *)buf_get(ctx, ms->buf[1], (size_t)total);
     if (!d_jobs || !d)
         return sfe_set_err(ctx, SFE_ERR_HIP, "map set render scratch allocation / upload failed");
@@ -2016,12 +1404,35 @@ int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings
 {
     if (!ms)
         return SFE_ERR_ARG;
-    if (int rc = sfe_use(ms->ctx))
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
         return rc;
-    return feed_hit_table(set_view(ms), bearings, num_bearings, breaks, coef, n_intervals, margin, num_ranges,
-                          range_resolution, range_in_double, r_skip, c_skip, id_out);
+    SFE_ARG(ctx, bearings && breaks && coef && id_out && num_bearings >= 2 && n_intervals >= 1 && n_intervals < (1 << 20));
+    SFE_ARG(ctx, margin > 0 && num_ranges >= 1 && range_resolution > 0 && r_skip >= 1 && c_skip >= 1);
+    for (int k = 0; k < n_intervals; ++k)
+        SFE_ARG(ctx, breaks[k] < breaks[k + 1]);
+    SFE_ARG(ctx, breaks[0] <= (double)bearings[0] && (double)bearings[num_bearings - 1] <= breaks[n_intervals]);
+    SFE_ARG(ctx, bearings[0] < bearings[num_bearings - 1]);
+    HitTab t;
+    double *d = nullptr;
+    const size_t nb = (size_t)n_intervals + 1, nc = 4 * (size_t)n_intervals;
+    SFE_HIP(ctx, hipMalloc((void **)&d, sizeof(double) * (nb + nc)));
+    if (hipMemcpy(d, breaks, sizeof(double) * nb, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d + nb, coef, sizeof(double) * nc, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map hit table upload failed");
+    }
+    t.breaks = d, t.coef = d + nb;
+    t.n_iv = n_intervals, t.num_ranges = num_ranges, t.num_bearings = num_bearings, t.r_skip = r_skip, t.c_skip = c_skip;
+    t.wide = range_in_double ? 1 : 0;
+    t.res32 = (float)range_resolution, t.res64 = range_resolution;
+    t.b_first = (double)bearings[0], t.b_last = (double)bearings[num_bearings - 1], t.margin = margin;
+    ms->hit_tabs.push_back(t);
+    *id_out = (int)ms->hit_tabs.size() - 1;
+    return 0;
 }
 
+// Phase one of a store-fed measurement (sonarfe.h).  Nothing of the set has changed when this returns, pending or not.
 int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slots,
                              const int32_t *geoms, const int32_t *handles, const int32_t *tabs, double radius, int min_points,
                              const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab, const double *div,
@@ -2034,21 +1445,89 @@ int sfe_mapset_measure_store(sfe_mapset *ms, sfe_cloud_store *store, int n, cons
     if (int rc = sfe_use(ctx))
         return rc;
     SFE_ARG(ctx, n <= 0 || maps);
-    auto slot_job = [&](int b, MeasJob &j) {
+    SFE_ARG(ctx, store && sfe_store_ctx(store) == ctx && n >= 0 && n <= 65535 && n_ktab >= 0 && (n_ktab == 0 || ktab));
+    SFE_ARG(ctx, n == 0 || (slots && geoms && handles && tabs && hrhc && k_off && div && n_points_out && n_undecided_out));
+    SFE_ARG(ctx, min_points <= 1 || radius >= 0);
+    FeedState &f = ms->feed;
+    f.pending = false;
+    if (n == 0)
+        return 0;
+    SfeStoreView v;
+    if (int rc = sfe_store_view(store, &v))
+        return rc;
+    std::vector<MeasJob> jobs(n);
+    std::vector<FeedJob> fjobs(n);
+    std::vector<std::pair<int32_t, int32_t>> named(n);
+    int64_t px = 0, tot = 0;
+    int max_n = 0;
+    for (int b = 0; b < n; ++b) {
+        MeasJob &j = jobs[b];
         if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
             return rc;
+        named[b] = {maps[b], slots[b]};
         const MapGeom &g = ms->geoms[geoms[b]];
         j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
-        j.logodds = set_logodds(ms, set_idx(ms, maps[b], slots[b]));
-        return 0;
-    };
-    if (int rc = feed_measure_store(set_view(ms), "map set", store, n, maps, slots, geoms, handles, tabs, radius, min_points,
-                                    hrhc, k_off, ktab, n_ktab, div, miss32, logit_miss, hit32, logit_hit, n_points_out,
-                                    n_undecided_out, slot_job))
-        return rc;
-    if (ms->feed.pending && ms->feed.tot_und == 0)
-        return set_feed_finish(ms);
-    return 0;
+        j.logodds = nullptr; // feed_finish binds the slot
+        const int hd = handles[b];
+        if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "map set: cloud %d named (job %d), the store holds %d%s", hd, b, v.n_slots,
+                               (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
+        SFE_ARG(ctx, tabs[b] >= 0 && tabs[b] < (int)ms->hit_tabs.size());
+        const int cnt = v.cnt[hd];
+        j.hit_off = (int32_t)tot;
+        j.n_hits = cnt;
+        // a cloud without points is a keyframe without a measurement (hr < 0); one the filter empties keeps its kernel
+        j.hr = cnt ? hrhc[2 * b] : -1, j.hc = cnt ? hrhc[2 * b + 1] : 0;
+        j.k_off = cnt ? k_off[b] : 0;
+        j.div = cnt ? div[b] : 1.0;
+        SFE_ARG(ctx, j.hr < 1024 && j.hc < 1024 && (j.hr < 0 || j.hc >= 0));
+        SFE_ARG(ctx, cnt == 0 || (j.hr >= 0 && j.k_off >= 0 && (int64_t)j.k_off + (2 * j.hr + 1) * (2 * j.hc + 1) <= n_ktab));
+        j.px_off = px;
+        px += j.slot_px;
+        fjobs[b].off = v.off[hd], fjobs[b].n = cnt, fjobs[b].hit_off = (int32_t)tot, fjobs[b].tab = tabs[b];
+        tot += cnt;
+        max_n = max(max_n, cnt);
+        SFE_ARG(ctx, tot < (1 << 30));
+    }
+    std::sort(named.begin(), named.end());
+    SFE_ARG(ctx, std::adjacent_find(named.begin(), named.end()) == named.end()); // a slot holds one image
+    FeedJob *d_jobs = buf_stage(ctx, ms->buf[6], fjobs);
+    HitTab *d_tabs = buf_stage(ctx, ms->buf[10], ms->hit_tabs);
+    int32_t *d_hits = (int32_t *)buf_get(ctx, ms->buf[7], sizeof(int32_t) * 2 * (size_t)(tot + 1));
+    uint8_t *d_keep = (uint8_t *)buf_get(ctx, ms->buf[8], (size_t)(tot + 1));
+    char *d_und = (char *)buf_get(ctx, ms->buf[9], sizeof(UndPoint) * (size_t)tot + sizeof(int32_t) * (size_t)n);
+    int32_t *h_cnt = (int32_t *)sfe_pinned_io(ctx, 3, sizeof(int32_t) * (size_t)n);
+    if (!d_jobs || !d_tabs || !d_hits || !d_keep || !d_und || !h_cnt)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set store feed scratch allocation / upload failed");
+    int32_t *d_cnt = (int32_t *)(d_und + sizeof(UndPoint) * (size_t)tot);
+    SFE_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(int32_t) * (size_t)n, ctx->stream));
+    if (max_n > 0) {
+        const dim3 grid((unsigned)((max_n + 255) / 256), (unsigned)n);
+        const bool filter = min_points > 1; // Mapping._hits
+        if (filter) {
+            hipLaunchKernelGGL(feed_radius_count_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs,
+                               (float)(radius * radius), min_points, d_keep);
+            SFE_LAUNCH_CHECK(ctx);
+        }
+        hipLaunchKernelGGL(feed_hit_cells_kernel, grid, dim3(256), 0, ctx->stream, (const float2 *)v.d_pool, d_jobs, d_tabs,
+                           filter ? (const uint8_t *)d_keep : nullptr, d_hits, (UndPoint *)d_und, d_cnt);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(h_cnt, d_cnt, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    f.maps.assign(maps, maps + n), f.slots.assign(slots, slots + n), f.geoms.assign(geoms, geoms + n);
+    f.n_und.assign(h_cnt, h_cnt + n);
+    f.jobs = jobs;
+    f.ktab.assign(ktab, ktab + n_ktab);
+    f.miss32 = miss32, f.logit_miss = logit_miss, f.hit32 = hit32, f.logit_hit = logit_hit;
+    f.tot = (int)tot, f.tot_und = 0;
+    for (int b = 0; b < n; ++b) {
+        n_points_out[b] = jobs[b].n_hits;
+        n_undecided_out[b] = h_cnt[b];
+        f.tot_und += h_cnt[b];
+    }
+    f.pending = true; // until the measurement runs: at once if no point is undecided
+    return f.tot_und == 0 ? feed_finish(ms) : 0;
 }
 
 int sfe_mapset_measure_store_undecided(sfe_mapset *ms, float *xy_out, int32_t *pos_out, int cap)
@@ -2057,7 +1536,7 @@ int sfe_mapset_measure_store_undecided(sfe_mapset *ms, float *xy_out, int32_t *p
         return SFE_ERR_ARG;
     if (int rc = sfe_use(ms->ctx))
         return rc;
-    return feed_undecided(set_view(ms), xy_out, pos_out, cap);
+    return feed_undecided(ms, xy_out, pos_out, cap);
 }
 
 int sfe_mapset_measure_store_finish(sfe_mapset *ms, int n_cells, const int32_t *pos, const int32_t *cells)
@@ -2066,22 +1545,52 @@ int sfe_mapset_measure_store_finish(sfe_mapset *ms, int n_cells, const int32_t *
         return SFE_ERR_ARG;
     if (int rc = sfe_use(ms->ctx))
         return rc;
-    if (int rc = feed_fill(set_view(ms), n_cells, pos, cells))
+    if (int rc = feed_fill(ms, n_cells, pos, cells))
         return rc;
-    return set_feed_finish(ms);
+    return feed_finish(ms);
 }
 
-// ---- the store feed of one map: the set's routines over this map's slots (sonarfe.h) ----------------------------------
+// ---- sfe_map: a set of one map with its slots on demand.  Every call is the set's over map 0 (sonarfe.h) ----------------
+
+int sfe_map_create(sfe_ctx *ctx, int rows, int cols, sfe_map **out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    return set_create(ctx, 1, rows, cols, 0, 0, reinterpret_cast<sfe_mapset **>(out));
+}
+
+void sfe_map_destroy(sfe_map *m) { sfe_mapset_destroy(one(m)); }
+
+int sfe_map_geometry(sfe_map *m, const float *sonar_xy, int img_rows, int img_cols, int *id_out)
+{
+    return sfe_mapset_geometry(one(m), sonar_xy, img_rows, img_cols, id_out);
+}
+
+int sfe_map_set_logodds(sfe_map *m, int slot, int geom, const float *logodds)
+{
+    const int32_t map = 0, s = slot, g = geom;
+    return sfe_mapset_set_logodds(one(m), 1, &map, &s, &g, logodds);
+}
+
+int sfe_map_measure(sfe_map *m, int n, const int32_t *slots, const int32_t *geoms, const int32_t *hit_off,
+                    const int32_t *hits, const int32_t *hrhc, const int32_t *k_off, const float *ktab, int n_ktab,
+                    const double *div, float miss32, float logit_miss, float hit32, float logit_hit)
+{
+    return sfe_mapset_measure(one(m), n, map0(n).data(), slots, geoms, hit_off, hits, hrhc, k_off, ktab, n_ktab, div, miss32,
+                              logit_miss, hit32, logit_hit);
+}
+
+int sfe_map_measure_stages(sfe_map *m, int b, uint8_t *hits_out, float *prob_out, int32_t *first_hits_out)
+{
+    return sfe_mapset_measure_stages(one(m), b, hits_out, prob_out, first_hits_out);
+}
+
 int sfe_map_hit_table(sfe_map *m, const float *bearings, int num_bearings, const double *breaks, const double *coef,
                       int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double, int r_skip,
                       int c_skip, int *id_out)
 {
-    if (!m)
-        return SFE_ERR_ARG;
-    if (int rc = sfe_use(m->ctx))
-        return rc;
-    return feed_hit_table(map_view(m), bearings, num_bearings, breaks, coef, n_intervals, margin, num_ranges, range_resolution,
-                          range_in_double, r_skip, c_skip, id_out);
+    return sfe_mapset_hit_table(one(m), bearings, num_bearings, breaks, coef, n_intervals, margin, num_ranges, range_resolution,
+                                range_in_double, r_skip, c_skip, id_out);
 }
 
 int sfe_map_measure_store(sfe_map *m, sfe_cloud_store *store, int n, const int32_t *slots, const int32_t *geoms,
@@ -2089,47 +1598,65 @@ int sfe_map_measure_store(sfe_map *m, sfe_cloud_store *store, int n, const int32
                           const int32_t *k_off, const float *ktab, int n_ktab, const double *div, float miss32,
                           float logit_miss, float hit32, float logit_hit, int32_t *n_points_out, int32_t *n_undecided_out)
 {
-    if (!m)
-        return SFE_ERR_ARG;
-    sfe_ctx *ctx = m->ctx;
-    if (int rc = sfe_use(ctx))
-        return rc;
-    auto slot_job = [&](int b, MeasJob &j) {
-        if (int rc = map_slot_check(m, slots[b], geoms[b]))
-            return rc;
-        for (int a = 0; a < b; ++a)
-            SFE_ARG(ctx, slots[a] != slots[b]); // a slot holds one image
-        const MapGeom &g = m->geoms[geoms[b]];
-        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.slot_px = g.img_rows * g.img_cols;
-        return 0;
-    };
-    if (int rc = feed_measure_store(map_view(m), "map", store, n, nullptr, slots, geoms, handles, tabs, radius, min_points, hrhc,
+    return sfe_mapset_measure_store(one(m), store, n, map0(n).data(), slots, geoms, handles, tabs, radius, min_points, hrhc,
                                     k_off, ktab, n_ktab, div, miss32, logit_miss, hit32, logit_hit, n_points_out,
-                                    n_undecided_out, slot_job))
-        return rc;
-    if (m->feed.pending && m->feed.tot_und == 0)
-        return map_feed_finish(m);
-    return 0;
+                                    n_undecided_out);
 }
 
 int sfe_map_measure_store_undecided(sfe_map *m, float *xy_out, int32_t *pos_out, int cap)
 {
-    if (!m)
-        return SFE_ERR_ARG;
-    if (int rc = sfe_use(m->ctx))
-        return rc;
-    return feed_undecided(map_view(m), xy_out, pos_out, cap);
+    return sfe_mapset_measure_store_undecided(one(m), xy_out, pos_out, cap);
 }
 
 int sfe_map_measure_store_finish(sfe_map *m, int n_cells, const int32_t *pos, const int32_t *cells)
 {
-    if (!m)
-        return SFE_ERR_ARG;
-    if (int rc = sfe_use(m->ctx))
-        return rc;
-    if (int rc = feed_fill(map_view(m), n_cells, pos, cells))
-        return rc;
-    return map_feed_finish(m);
+    return sfe_mapset_measure_store_finish(one(m), n_cells, pos, cells);
+}
+
+int sfe_map_fit_bounds(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2,
+                       double resolution, int32_t *mm_out)
+{
+    return sfe_mapset_fit_bounds(one(m), n, map0(n).data(), slots, pose4, origin2, resolution, mm_out);
+}
+
+int sfe_map_grow(sfe_map *m, int top, int bottom, int left, int right)
+{
+    const int32_t map = 0, grow4[4] = {top, bottom, left, right};
+    return sfe_mapset_grow(one(m), 1, &map, grow4);
+}
+
+int sfe_map_refit(sfe_map *m, int n, const int32_t *slots, const double *pose4, const double *origin2, double resolution,
+                  const int32_t *mm, const int32_t *shift2, const uint8_t *dec)
+{
+    return sfe_mapset_refit(one(m), n, map0(n).data(), slots, pose4, origin2, resolution, mm, shift2, dec);
+}
+
+int sfe_map_cells(sfe_map *m, int slot, uint16_t *r_out, uint16_t *c_out, float *l_out, int cap, int *n_out)
+{
+    return sfe_mapset_cells(one(m), 0, slot, r_out, c_out, l_out, cap, n_out);
+}
+
+int sfe_map_logodds(sfe_map *m, int slot, float *out, int cap) { return sfe_mapset_logodds(one(m), 0, slot, out, cap); }
+
+int sfe_map_shape(sfe_map *m, int32_t *rows_cols_grow4) { return sfe_mapset_shape(one(m), 0, rows_cols_grow4); }
+
+int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap)
+{
+    return sfe_mapset_read_grid(one(m), 0, which, out, cap);
+}
+
+int sfe_map_frames(sfe_map *m, int n, const int32_t *slots)
+{
+    const int32_t map = 0, slot_off[2] = {0, n};
+    return sfe_mapset_frames(one(m), 1, &map, slot_off, slots);
+}
+
+int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
+                   int8_t *occ_out)
+{
+    const int32_t map = 0, w = which, box4[4] = {r0, r1, c0, c1}, out_hw[2] = {out_h, out_w}, rs = resize;
+    const long long out_off = 0;
+    return sfe_mapset_render(one(m), 1, &map, &w, box4, out_hw, &inv, &rs, &out_off, occ_out, (long long)out_h * out_w);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

@@ -15,6 +15,7 @@ method 2 (``get_occupancy_grid2``) and the intensity grid.  INTEGRATION.md lists
 """
 import contextlib
 import ctypes as C
+import functools
 import math
 import types
 
@@ -305,17 +306,27 @@ class Mapping(object):
             self._restore_geometry(state)
             raise
 
+    def _bound(self, name):
+        """the device call sfe_map_`name` with this map's handle bound (a MapBatch session binds the set's call of that name,
+        its handle and the session): what the reads below go through"""
+        return functools.partial(getattr(self._lib, "sfe_map_" + name), self._h)
+
     def _read_cells(self, slot, n):
         r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
         got = C.c_int(0)
-        self._check(self._lib.sfe_map_cells(self._h, slot, r.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                            c.ctypes.data_as(C.POINTER(C.c_uint16)), _L.ptr(l, C.c_float), n, C.byref(got)))
+        self._check(self._bound("cells")(slot, r.ctypes.data_as(C.POINTER(C.c_uint16)), c.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                         _L.ptr(l, C.c_float), n, C.byref(got)))
         k = got.value
         return r[:k].copy(), c[:k].copy(), l[:k].copy()
 
     def _read_logodds(self, slot, n):
         out = np.zeros(n, np.float32)
-        self._check(self._lib.sfe_map_logodds(self._h, slot, _L.ptr(out, C.c_float), n))
+        self._check(self._bound("logodds")(slot, _L.ptr(out, C.c_float), n))
+        return out
+
+    def _read_grid(self, which):
+        out = np.zeros((self.rows, self.cols), np.float32)
+        self._check(self._bound("read_grid")(which, _L.ptr(out, C.c_float), out.size))
         return out
 
     # ---- the reference's methods -----------------------------------------------------------------------------------
@@ -381,15 +392,10 @@ class Mapping(object):
         return np.ascontiguousarray(hits, np.int32), ktab, div
 
     def _measure(self, slot, geom, hits, hr, hc):
-        hits, ktab, div = self._measure_args(hits, hr, hc)
-        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
-        arr = lambda v, t: np.ascontiguousarray(np.array(v, t))
-        self._check(self._lib.sfe_map_measure(
-            self._h, 1, _L.ptr(arr([slot], np.int32), C.c_int32), _L.ptr(arr([geom], np.int32), C.c_int32),
-            _L.ptr(arr([0, len(hits)], np.int32), C.c_int32), _L.ptr(hits if len(hits) else arr([0, 0], np.int32), C.c_int32),
-            _L.ptr(arr([hr, hc], np.int32), C.c_int32), _L.ptr(arr([0], np.int32), C.c_int32), _L.ptr(ktab, C.c_float),
-            len(ktab), _L.ptr(arr([div], np.float64), C.c_double), float(miss32), float(logit(miss32)), float(hit32),
-            float(logit(hit32))))
+        hits = _hits32(hits, hr)
+        self._check(self._lib.sfe_map_measure(self._h, 1, _i32p(slot), _i32p(geom), _i32p(0, len(hits)),
+                                              _L.ptr(hits, C.c_int32) if len(hits) else _i32p(0, 0),
+                                              *kernel_tables(self, [self], [(hr, hc)])))
 
     def measure_stages(self):
         """(hit mask, image before logit, first hits) of the last add_keyframe's measurement (for tests)"""
@@ -439,30 +445,11 @@ class Mapping(object):
         return device_hit_table(self, self._hit_tabs, lambda *a: self._lib.sfe_map_hit_table(self._h, *a))
 
     def _measure_store(self, kf, store, handle):
-        hr, hc = self._hit_halves()
-        _, ktab, div = self._measure_args(np.zeros((0, 2), np.int32), hr, hc)
-        tab = self._hit_table()
-        i32 = lambda *a: _L.ptr(np.array(a, np.int32), C.c_int32)
-        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
-        n_pts, n_und = np.zeros(1, np.int32), np.zeros(1, np.int32)
-        with self.ctx.lock:        # the store's slot table and the context's pinned staging
-            self._check(self._lib.sfe_map_measure_store(
-                self._h, store.handle, 1, i32(kf._slot), i32(kf.geom), i32(handle), i32(tab),
-                float(self.outlier_filter_radius), int(self.outlier_filter_min_points), i32(hr, hc), i32(0),
-                _L.ptr(ktab, C.c_float), len(ktab), _L.ptr(np.array([div], np.float64), C.c_double), float(miss32),
-                float(logit(miss32)), float(hit32), float(logit(hit32)), _L.ptr(n_pts, C.c_int32), _L.ptr(n_und, C.c_int32)))
-            total = int(n_und[0])
-            if total:
-                # phase two: the undecided points through _hit_indices, then the measurement
-                xy, pos = np.zeros((total, 2), np.float32), np.zeros(total, np.int32)
-                self._check(self._lib.sfe_map_measure_store_undecided(self._h, _L.ptr(xy, C.c_float), _L.ptr(pos, C.c_int32),
-                                                                      total))
-                cells = np.ascontiguousarray(self._hit_indices(xy)[0], np.int32)
-                self._check(self._lib.sfe_map_measure_store_finish(self._h, total, _L.ptr(pos, C.c_int32),
-                                                                   _L.ptr(cells, C.c_int32)))
-        self.feed_stats["points"] += int(n_pts[0])
-        self.feed_stats["undecided"] += total
-        self.feed_stats["calls"] += 1
+        head = (store.handle, 1, _i32p(kf._slot), _i32p(kf.geom), _i32p(handle), _i32p(self._hit_table()),
+                float(self.outlier_filter_radius), int(self.outlier_filter_min_points))
+        measure_store(self, [self], functools.partial(self._lib.sfe_map_measure_store, self._h, *head),
+                      functools.partial(self._lib.sfe_map_measure_store_undecided, self._h),
+                      functools.partial(self._lib.sfe_map_measure_store_finish, self._h))
 
     def add_keyframe_logodds(self, key, pose, ping, logodds):
         """add_keyframe with a ready polar log-odds image (float32, the downsampled image's shape) instead of points"""
@@ -597,17 +584,11 @@ class Mapping(object):
 
     @property
     def logodds_grid(self):
-        if self._h is None:
-            return None
-        out = np.zeros((self.rows, self.cols), np.float32)
-        self._check(self._lib.sfe_map_read_grid(self._h, 0, _L.ptr(out, C.c_float), out.size))
-        return out
+        return None if self._h is None else self._read_grid(0)
 
     def frames_grid(self):
         """the grid of the last get_occupancy_grid1(frames=...) call"""
-        out = np.zeros((self.rows, self.cols), np.float32)
-        self._check(self._lib.sfe_map_read_grid(self._h, 1, _L.ptr(out, C.c_float), out.size))
-        return out
+        return self._read_grid(1)
 
     def _check_supported(self):
         if self.pub_intensity:
@@ -686,7 +667,64 @@ class Mapping(object):
         return self._grid_msg(box, resolution, occ)
 
 
-# ---- the hit cells on the device (MapBatch.add_keyframes_store) ----------------------------------------------------------
+# ---- what Mapping and MapBatch hand the measurement ------------------------------------------------------------------------
+def _i32p(*values):
+    return _L.ptr(np.ascontiguousarray(np.array(values, np.int32).reshape(-1)), C.c_int32)
+
+
+def _hits32(hits, hr):
+    """a keyframe's hits as the device takes them: int32 [n x 2]; none for a keyframe without points (hr < 0)"""
+    return np.ascontiguousarray(hits, np.int32).reshape(-1, 2) if hr >= 0 else np.zeros((0, 2), np.int32)
+
+
+def kernel_tables(owner, views, halves=None):
+    """The inflation kernels of a measurement call with one keyframe per map view in ``views``; ``halves[i]`` = its (hr, hc),
+    by default what its sonar geometry gives.  -> the arguments every measure call ends its inputs with: hrhc, k_off, ktab (the
+    distinct float32 kernels back to back), n_ktab, div, and ``owner``'s miss / hit probabilities in float32 with their
+    logits"""
+    halves = [v._hit_halves() for v in views] if halves is None else halves
+    k_off, div, ktabs, at, n_k = [], [], [], {}, 0
+    for v, (hr, hc) in zip(views, halves):
+        _, ktab, d = v._measure_args(np.zeros((0, 2), np.int32), hr, hc)
+        if (hr, hc) not in at:
+            at[(hr, hc)] = n_k
+            ktabs.append(ktab)
+            n_k += len(ktab)
+        k_off.append(at[(hr, hc)])
+        div.append(d)
+    ktab = np.ascontiguousarray(np.concatenate(ktabs), np.float32)
+    hit32, miss32 = np.float32(owner.hit_prob), np.float32(owner.miss_prob)
+    return (_i32p(halves), _i32p(k_off), _L.ptr(ktab, C.c_float), len(ktab),
+            _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
+            float(hit32), float(logit(hit32)))
+
+
+def measure_store(owner, views, phase_one, undecided, finish):
+    """A store-fed measurement of one keyframe per map view in ``views``, the whole protocol.  The three calls are the
+    owner's sfe_map(set)_measure_store (with everything before the kernel tables bound), _undecided and _finish (with the
+    handle bound).  Phase two, for the few points the device left undecided: they come back, go through ``_hit_indices``
+    once per sonar geometry, and their cells go back before the measurement runs.  Counts into ``owner.feed_stats``."""
+    n_pts, n_und = np.zeros(len(views), np.int32), np.zeros(len(views), np.int32)
+    with owner.ctx.lock:        # the store's slot table and the context's pinned staging
+        owner._check(phase_one(*kernel_tables(owner, views), _L.ptr(n_pts, C.c_int32), _L.ptr(n_und, C.c_int32)))
+        total = int(n_und.sum())
+        if total:
+            xy, pos = np.zeros((total, 2), np.float32), np.zeros(total, np.int32)
+            owner._check(undecided(_L.ptr(xy, C.c_float), _L.ptr(pos, C.c_int32), total))
+            job = np.searchsorted(np.cumsum(n_pts), pos, side="right")
+            cells = np.zeros((total, 2), np.int32)
+            groups = {}
+            for i, j in enumerate(job):
+                groups.setdefault(views[j]._hit_key, []).append(i)
+            for idx in groups.values():
+                cells[idx] = views[job[idx[0]]]._hit_indices(xy[idx])[0]
+            owner._check(finish(total, _L.ptr(pos, C.c_int32), _L.ptr(np.ascontiguousarray(cells), C.c_int32)))
+    owner.feed_stats["points"] += int(n_pts.sum())
+    owner.feed_stats["undecided"] += total
+    owner.feed_stats["calls"] += 1
+
+
+# ---- the hit cells on the device (the store feed) ------------------------------------------------------------------------
 def spline_table(oculus):
     """``oculus.b2c`` as one cubic per knot interval, in double -> (breaks [n + 1], coef [n x 4]): on
     [breaks[k], breaks[k + 1]) the column is polyval(coef[k], angle - breaks[k]).  (The not-a-knot spline has no knot at
@@ -830,38 +868,18 @@ class _SessionMap(Mapping):
         self._hit_key = self._new_hit_key()
         return self._b._geometry(sonar_xy, shape)
 
-    def _read_cells(self, slot, n):
+    def _bound(self, name):
         b = self._b
-        r, c, l = np.zeros(n, np.uint16), np.zeros(n, np.uint16), np.zeros(n, np.float32)
-        got = C.c_int(0)
-        self._check(b._lib.sfe_mapset_cells(b._h, self._s, slot, r.ctypes.data_as(C.POINTER(C.c_uint16)),
-                                            c.ctypes.data_as(C.POINTER(C.c_uint16)), _L.ptr(l, C.c_float), n, C.byref(got)))
-        k = got.value
-        return r[:k].copy(), c[:k].copy(), l[:k].copy()
-
-    def _read_logodds(self, slot, n):
-        b = self._b
-        out = np.zeros(n, np.float32)
-        self._check(b._lib.sfe_mapset_logodds(b._h, self._s, slot, _L.ptr(out, C.c_float), n))
-        return out
-
-    def _read_grid(self, which):
-        b = self._b
-        out = np.zeros((self.rows, self.cols), np.float32)
-        self._check(b._lib.sfe_mapset_read_grid(b._h, self._s, which, _L.ptr(out, C.c_float), out.size))
-        return out
+        return functools.partial(getattr(b._lib, "sfe_mapset_" + name), b._h, self._s)
 
     @property
     def logodds_grid(self):
-        return self._read_grid(0)
-
-    def frames_grid(self):
-        return self._read_grid(1)
+        return self._read_grid(0)       # (its own _h stays None: the handle is the batch's)
 
     def device_shape(self):
         """(rows, cols, rows grown on top, columns grown on the left) as the device holds them"""
         out = np.zeros(4, np.int32)
-        self._check(self._b._lib.sfe_mapset_shape(self._b._h, self._s, _L.ptr(out, C.c_int32)))
+        self._check(self._bound("shape")(_L.ptr(out, C.c_int32)))
         return tuple(int(v) for v in out)
 
     def measure_stages(self):
@@ -1043,30 +1061,13 @@ class MapBatch(object):
     def _measure_many(self, sessions, kfs, points):
         clouds = [np.asarray(p) if len(p) else p for p in points]
         hits = self._hits_many(sessions, clouds)
-        hit_off, hrhc, k_off, div, ktabs, ktab_at, n_k = [0], [], [], [], [], {}, 0
-        all_hits = []
-        for s, (h, hr, hc) in zip(sessions, hits):
-            v = self.maps[s]
-            h, ktab, d = v._measure_args(h, hr, hc)
-            if (hr, hc) not in ktab_at:
-                ktab_at[(hr, hc)] = n_k
-                ktabs.append(ktab)
-                n_k += len(ktab)
-            all_hits.append(h.reshape(-1, 2))
-            hit_off.append(hit_off[-1] + len(h))
-            hrhc.append((hr, hc))
-            k_off.append(ktab_at[(hr, hc)])
-            div.append(d)
-        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
-        hits_all = np.ascontiguousarray(np.concatenate(all_hits), np.int32) if hit_off[-1] else i32([0, 0])
-        ktab = np.ascontiguousarray(np.concatenate(ktabs), np.float32)
-        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
+        all_hits = [_hits32(h, hr) for h, hr, _ in hits]
+        hit_off = np.cumsum([0] + [len(h) for h in all_hits])
+        hits_all = np.ascontiguousarray(np.concatenate(all_hits)) if hit_off[-1] else np.zeros(2, np.int32)
         self._check(self._lib.sfe_mapset_measure(
-            self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
-            _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(i32(hit_off), C.c_int32), _L.ptr(hits_all, C.c_int32),
-            _L.ptr(i32(hrhc), C.c_int32), _L.ptr(i32(k_off), C.c_int32), _L.ptr(ktab, C.c_float), len(ktab),
-            _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
-            float(hit32), float(logit(hit32))))
+            self._h, len(sessions), _i32p(sessions), _i32p([kf._slot for kf in kfs]), _i32p([kf.geom for kf in kfs]),
+            _i32p(hit_off), _L.ptr(hits_all, C.c_int32),
+            *kernel_tables(self, [self.maps[s] for s in sessions], [(hr, hc) for _, hr, hc in hits])))
 
     def add_keyframes_store(self, sessions, keys, poses, pings, store, handles):
         """``add_keyframes(sessions, keys, poses, pings, store.read_many(handles))``, bit for bit, without the clouds
@@ -1096,51 +1097,13 @@ class MapBatch(object):
         return device_hit_table(v, self._hit_tabs, lambda *a: self._lib.sfe_mapset_hit_table(self._h, *a))
 
     def _measure_store(self, sessions, kfs, store, handles):
-        n = len(sessions)
-        tabs, hrhc, k_off, div, ktabs, ktab_at, n_k = [], [], [], [], [], {}, 0
-        for s in sessions:
-            v = self.maps[s]
-            tabs.append(self._hit_table(v))
-            hr, hc = v._hit_halves()
-            _, ktab, d = v._measure_args(np.zeros((0, 2), np.int32), hr, hc)
-            if (hr, hc) not in ktab_at:
-                ktab_at[(hr, hc)] = n_k
-                ktabs.append(ktab)
-                n_k += len(ktab)
-            hrhc.append((hr, hc))
-            k_off.append(ktab_at[(hr, hc)])
-            div.append(d)
-        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32))
-        ktab = np.ascontiguousarray(np.concatenate(ktabs), np.float32)
-        hit32, miss32 = np.float32(self.hit_prob), np.float32(self.miss_prob)
-        n_pts, n_und = np.zeros(n, np.int32), np.zeros(n, np.int32)
-        with self.ctx.lock:        # the store's slot table and the context's pinned staging
-            self._check(self._lib.sfe_mapset_measure_store(
-                self._h, store.handle, n, _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
-                _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(i32(handles), C.c_int32), _L.ptr(i32(tabs), C.c_int32),
-                float(self.outlier_filter_radius), int(self.outlier_filter_min_points), _L.ptr(i32(hrhc), C.c_int32),
-                _L.ptr(i32(k_off), C.c_int32), _L.ptr(ktab, C.c_float), len(ktab),
-                _L.ptr(np.ascontiguousarray(np.array(div, np.float64)), C.c_double), float(miss32), float(logit(miss32)),
-                float(hit32), float(logit(hit32)), _L.ptr(n_pts, C.c_int32), _L.ptr(n_und, C.c_int32)))
-            total = int(n_und.sum())
-            if total:
-                # phase two: the undecided points through _hit_indices, per sonar geometry, then the measurement
-                xy, pos = np.zeros((total, 2), np.float32), np.zeros(total, np.int32)
-                self._check(self._lib.sfe_mapset_measure_store_undecided(self._h, _L.ptr(xy, C.c_float),
-                                                                         _L.ptr(pos, C.c_int32), total))
-                job = np.searchsorted(np.cumsum(n_pts), pos, side="right")
-                cells = np.zeros((total, 2), np.int32)
-                groups = {}
-                for i, j in enumerate(job):
-                    groups.setdefault(self.maps[sessions[j]]._hit_key, []).append(i)
-                for idx in groups.values():
-                    v = self.maps[sessions[job[idx[0]]]]
-                    cells[idx] = v._hit_indices(xy[idx])[0]
-                self._check(self._lib.sfe_mapset_measure_store_finish(self._h, total, _L.ptr(pos, C.c_int32),
-                                                                      _L.ptr(np.ascontiguousarray(cells), C.c_int32)))
-        self.feed_stats["points"] += int(n_pts.sum())
-        self.feed_stats["undecided"] += total
-        self.feed_stats["calls"] += 1
+        views = [self.maps[s] for s in sessions]
+        head = (store.handle, len(sessions), _i32p(sessions), _i32p([kf._slot for kf in kfs]), _i32p([kf.geom for kf in kfs]),
+                _i32p(handles), _i32p([self._hit_table(v) for v in views]), float(self.outlier_filter_radius),
+                int(self.outlier_filter_min_points))
+        measure_store(self, views, functools.partial(self._lib.sfe_mapset_measure_store, self._h, *head),
+                      functools.partial(self._lib.sfe_mapset_measure_store_undecided, self._h),
+                      functools.partial(self._lib.sfe_mapset_measure_store_finish, self._h))
 
     def add_keyframes_logodds(self, sessions, keys, poses, pings, logodds):
         """Mapping.add_keyframe_logodds for each listed session"""

@@ -16,7 +16,7 @@ sys.path[:0] = [ROOT, HERE]
 import mapping_ref  # noqa: E402
 from test_gpu_map_batch import _same_records, device_shape, same  # noqa: E402
 from test_gpu_map_store_feed import _near, cloud  # noqa: E402
-from test_gpu_mapping import configured, state  # noqa: E402
+from test_gpu_mapping import configured, ref_map, state  # noqa: E402
 from sonar_slam_amd import _lib  # noqa: E402
 from sonar_slam_amd.mapping import MapBatch, Mapping  # noqa: E402
 from sonar_slam_amd.pose2 import Pose2  # noqa: E402
@@ -191,6 +191,77 @@ def test_undecided_points_take_the_host_route(ctx, fix, pings, min_points):
     same_map(host, dev, "undecided points")
     for m in (host, dev):
         m.close()
+    store.close()
+
+
+@pytest.mark.parametrize("inflated", [False, True])
+@pytest.mark.parametrize("feed", ["host", "store"])
+def test_slots_on_demand_regrow_under_live_data(ctx, fix, pings, clouds, feed, inflated):
+    """A Mapping keeps its slots on demand: the slot vector and the counts table of its one-map set grow when a slot past
+    their end is asked for, while earlier slots hold cell lists.  Keys 0, 2 and 70, with key 70 in slot 70: the counts table
+    starts with room for 66 slots, so it is reallocated (and every slot's counts pointer moved) while slots 0 and 1 are live;
+    the third keyframe also grows the grid.  Then update_poses on the first and the last key in one call, and a frames=
+    render of the two.  The grid, every keyframe's r / c / l, frames_grid() and the rendered occ equal, bit for bit, those of
+    session 0 of a one-session MapBatch (whose slots lie in the arena) and of tests/mapping_ref.py given the same calls.
+
+    The comparison with mapping_ref runs with inflation off (a 1 x 1 kernel): the polar image then holds only miss_prob, 0.5
+    and hit_prob, the three values whose logit the device (double) and mapping_ref (scipy, float32) take to the same bits,
+    so it can be bit for bit from points.  `inflated`: the fixture's inflation, many values per image; the device's log-odds
+    are then within 2 ulp of mapping_ref's (test_gpu_mapping.py), so only the MapBatch is compared."""
+    over = {} if inflated else dict(inflation_angle=0.0, inflation_range=0.0)
+    m = new_map(ctx, fix, **over)
+    b = MapBatch(ctx, 1, 8, max_pixels=8192, **dict(json.loads(str(fix["settings"])), **over))
+    b.configure()
+    others = [b.maps[0]] + ([] if inflated else [ref_map(fix, **over)])
+    store = CloudStore(ctx, capacity_points=1 << 14, max_clouds=16)
+    ping, keys = pings["A"], [0, 2, 70]
+
+    def same_as(got, want, tag):
+        want = np.asarray(want)
+        cast = np.ascontiguousarray(want, got.dtype)
+        assert np.array_equal(cast, want) and bits(got, cast), tag      # (the cast kept every value)
+
+    def check(tag):
+        for x in others:
+            same_as(m.logodds_grid, x.logodds_grid, tag)
+            for k in keys:
+                for name in "rcl":
+                    same_as(getattr(m.keyframes[k], name), getattr(x.keyframes[k], name), (tag, k, name))
+
+    for key, p, pts in zip(keys, POSES, (clouds[0], clouds[1], clouds[4])):
+        h = store.put(pts)
+        if key == 70:
+            # a keyframe's slot is len(keyframes) when it is added: with the missed keys filled in first, key 70 takes slot 70
+            m.keyframes += [None] * (70 - len(m.keyframes))
+        if feed == "store":
+            m.add_keyframe_store(key, Pose2(*p), ping, store, h)
+            b.add_keyframes_store([0], [key], [Pose2(*p)], ping, store, [h])
+        else:
+            m.add_keyframe(key, Pose2(*p), ping, store.read(h))
+            b.add_keyframes([0], [key], [Pose2(*p)], ping, [store.read(h)])
+        for ref in others[1:]:
+            ref.add_keyframe(key, Pose2(*p), ping, store.read(h))
+    assert [m.keyframes[k]._slot for k in keys] == [0, 1, 70] and len(m.keyframes) == 71
+    assert m._grow[0] > 0 and m._grow[1] > 0                         # the third keyframe grew the grid
+    if inflated:
+        assert len(np.unique(m.keyframes[0].l)) > 3
+    check("adds")
+    new = [Pose2(POSES[i][0] + 0.7, POSES[i][1] - 1.1, POSES[i][2] + 0.2) for i in (0, 2)]
+    m.update_poses([0, 70], new)
+    b.update_poses([0, 0], [0, 70], new)
+    for ref in others[1:]:
+        for k, p in zip((0, 70), new):
+            ref.update_pose(k, p)
+    check("update_poses")
+    got = m.get_occupancy_grid1(frames=[0, 70])
+    frames = m.frames_grid()
+    assert got.occ.size > 1000 and np.count_nonzero(frames) > 500
+    for x in others:
+        want = x.get_occupancy_grid1(frames=[0, 70])
+        same_as(frames, x.frames_grid() if x is b.maps[0] else x.last_frames_grid, "frames grid")
+        same_as(got.occ, want.occ, "occ")
+    m.close()
+    b.close()
     store.close()
 
 
