@@ -100,7 +100,7 @@ __host__ __device__ __forceinline__ float cfar_thr_arith(const CfarThrArith &ta,
 // identical values, so the body has no branches, no exec masking and no tail code.
 //
 // BITS: the detections leave the kernel bit-packed (bit iy*cols+ix of the frame's bit stream, LSB first: the
-// layout extract_scatter_kernel reads, sfe_remap.hip) instead of as 0/1 bytes: a lane folds its 4 decisions
+// layout extract_scatter_kernel reads, sfe_extract.hip) instead of as 0/1 bytes: a lane folds its 4 decisions
 // into a nibble (one v_dot4), 8 lanes OR their nibbles into a 32-bit word over three DPP steps and one lane
 // of the 8 stores it -- the other 56 lanes aim past the end of the buffer, where the hardware drops the
 // store.  Needs cols % 32 == 0 (a row is a whole number of words and every 64-lane chunk starts on one).
@@ -1180,7 +1180,7 @@ static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int row
         const int tiles = (rows + groups * R - 1) / (groups * R);
         const long long fb = (long long)rows * cols;
         if (d_bits) {
-            const long long bb = (fb / 32 + 1) * 4; // bytes per frame of the bit stream: one pad word (sfe_remap.hip)
+            const long long bb = (fb / 32 + 1) * 4; // bytes per frame of the bit stream: one pad word (sfe_extract.hip)
             if (T == 20)
                 launch_ring<20, 5, 4, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, bb, lut);
             else if (T == 16)

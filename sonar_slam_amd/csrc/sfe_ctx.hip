@@ -100,7 +100,7 @@ const TuneKnob g_knobs[] = {
     SFE_KNOB_I(cfar_os_gated_min, 0, 256),
     SFE_KNOB_I(cfar_os_pref, 0, 1),
     SFE_KNOB_I(cfar_os_pref_x, 0, 255),
-    SFE_KNOB_I(extract_rec_cap, 0, 8192), // (ME_THREADS x ME_RPT, sfe_remap.hip)
+    SFE_KNOB_I(extract_rec_cap, 0, 8192), // (ME_THREADS x ME_RPT, sfe_extract.hip)
     SFE_KNOB_I(extract_capw, 0, 1 << 20),
     SFE_KNOB_I(extract_compact, 0, 1),
     SFE_KNOB_I(cost_many, 0, 1),

@@ -20,7 +20,7 @@ struct sfe_tuning {
     int cfar_os_gated_min = 40; //   (gate 65: 0.65 ms per 512 frames against the histogram's 1.65; gate 20: 1.84 against 1.65)
     int cfar_os_pref = 1;       // below it: the pre-filtered candidate kernel where it applies (0: sliding histogram)
     int cfar_os_pref_x = 80;    //   its level: L[x] for a pixel of about a third of full scale
-    // extraction (sfe_remap.hip)
+    // extraction (sfe_extract.hip)
     int extract_rec_cap = 0;    // record slots per workgroup region of the record path (0: ME_THREADS x ME_RPT)
     int extract_capw = 0;       // canvas words a frame of the record path may fill (0: 4096)
     int extract_compact = 1;    // inverse map in its 4-byte entries (0: the 8-byte entries of round 3)
@@ -77,7 +77,7 @@ struct sfe_ctx {
         bool pending = false;
     } pin[2];
     int pin_next = 0;
-    void *bm_clean_ptr = nullptr; // extract_dev: the canvas bitmap scratch is known to be zero up to bm_clean_bytes
+    void *bm_clean_ptr = nullptr; // sfe_extract.hip (CleanBitmap): the canvas bitmap scratch is known to be zero up to bm_clean_bytes
     size_t bm_clean_bytes = 0;
     Pin pin_io[4]; // grow-only pinned buffers of the synchronous single-item entry points (no events: the call syncs)
     // float threshold table of the sliding-sum CFAR kernel currently on the device (scratch slot 37)
@@ -124,7 +124,7 @@ struct sfe_geom {
 
 int sfe_set_err(sfe_ctx *ctx, int code, const char *fmt, ...);
 int sfe_mask_pack(sfe_ctx *ctx, const uint8_t *d_mask, int n_frames, long long px, uint32_t *d_bits,
-                  int32_t *d_nonbin); // sfe_remap.hip: byte mask -> bit stream
+                  int32_t *d_nonbin); // sfe_extract.hip: byte mask -> bit stream
 void *sfe_scratch(sfe_ctx *ctx, int slot, size_t bytes);  // grow-only device scratch; nullptr on failure
 // Pinned staging: sfe_pinned_begin hands out a host block of >= bytes (waiting, if need be, for the copy that last
 // read it -- two launches ago); the caller fills it, enqueues its hipMemcpyAsync calls on `s` and then calls

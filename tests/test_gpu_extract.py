@@ -353,8 +353,8 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
     sizes = sorted(len(w) for w in want)
     small = (sizes[2] + sizes[3]) // 2                    # half of the frames are above it
 
-    def batch(idx, cap, variant=0, env=None):
-        kb = KeyframeBatch(ctx, fe.geometry, (th, gh, tau), "SOCA", 65, None, len(idx), max_points=cap, bit_masks=True)
+    def batch(idx, cap, variant=0, env=None, bit_masks=True):
+        kb = KeyframeBatch(ctx, fe.geometry, (th, gh, tau), "SOCA", 65, None, len(idx), max_points=cap, bit_masks=bit_masks)
         restore = [(k, ctx.tune(k, v)) for k, v in (env or {}).items()]
         try:
             ctx._check(ctx.lib.sfe_extract_set_tuning(ctx.handle, variant))
@@ -367,6 +367,7 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
                 assert counts[k] == len(want[j]), (idx, cap, j)
                 if counts[k] <= cap:
                     assert np.array_equal(kb.points(k), oracle.px_to_m(want[j], fe.rows, fe.cols, fe.width, fe.height)), j
+            return counts, [kb.points(k) for k in range(len(idx)) if counts[k] <= cap]
         finally:
             for k, v in restore:
                 ctx.tune(k, v)
@@ -390,6 +391,74 @@ def test_bit_stream_batches_leave_the_canvas_bitmap_clean(ctx, shipped_cfar):
     batch(list(range(6)), small, env={"extract_capw": words[4] + 1})                      # both kinds of overflow
     batch([0, 5, 2], big, variant=2)    # the canvas path for every frame
     batch([5, 0], big)
+    # A call that ends in an error leaves what the context knows about the bitmap as it was (refused at the entry point) or
+    # unknown (an error after the first launch, which takes a failing runtime: not forced here); either way the next batch
+    # is right.  A good batch, a refused call, a byte-mask batch (its bits stay in the bitmap), the first batch again: the
+    # canvas path for every frame (variant 2), where a stale bit is a point, and the default.
+    ragged, _, _, _, _ = _geom(ctx, 100, 77, 0.1)
+    d = ctx.alloc(4096)
+    try:
+        for variant in (2, 0):
+            first = batch([0, 1, 2, 3], big, variant=variant)
+            with pytest.raises(Exception, match="polar_cols"):
+                ctx._check(ctx.lib.sfe_extract_points_bits_batch_dev(ctx.handle, ragged.handle, d.ptr, 1, 16, d.ptr, d.ptr))
+            again = batch([0, 1, 2, 3], big, variant=variant)           # the state survived the refusal
+            bytes_ = batch([0, 1, 2, 3], big, variant=variant, bit_masks=False)
+            last = batch([0, 1, 2, 3], big, variant=variant)
+            for got in (again, bytes_, last):
+                assert np.array_equal(got[0], first[0])
+                assert len(got[1]) == len(first[1]) == 4 and all(np.array_equal(a, b) for a, b in zip(got[1], first[1]))
+    finally:
+        d.free()
+
+
+def test_geometry_without_a_compact_inverse_map_takes_the_8_byte_entries(ctx):
+    """The 4-byte inverse-map entries hold a candidate's canvas row and column relative to its polar pixel's first candidate
+    in 7 bits each; a geometry where a pixel's candidates span more gets no compact table and extract_gather_kernel<false>
+    reads the 8-byte entries whatever extract_compact says.  No sonar fan does that, so the maps are made by hand: a 2 x 32
+    polar image stretched over a 300 x 64 canvas (map_y = row / 299, map_x = col * 31 / 63).  Worked out on the CPU with the
+    library's own table code (sfe_geom_tables.h): the reporting candidates of polar pixel (0, 0) lie in canvas rows 0 .. 294,
+    a span of 294 rows (columns: 3), so compact_map() gives up at the first pixel.  The inverse map (byte masks, one frame;
+    bit streams, 3 frames: records, canvas) must return the points of the dense pass, bit for bit and in its order."""
+    rows, cols, prows, pcols = 300, 64, 2, 32
+    my = np.repeat((np.arange(rows, dtype=np.float64) / (rows - 1)).reshape(-1, 1), cols, axis=1).astype(np.float32)
+    mx = np.repeat((np.arange(cols, dtype=np.float64) * (pcols - 1) / (cols - 1)).reshape(1, -1), rows, axis=0).astype(np.float32)
+    g = Geometry(ctx, mx, my, (prows, pcols), 8.0, 30.0)
+    rng = np.random.default_rng(2)
+    masks = np.stack([(rng.random((prows, pcols)) < d).astype(np.uint8) for d in (0.1, 0.5, 1.0)])
+    n, cap, wpf = len(masks), rows * cols, prows * pcols // 32 + 1
+    streams = np.zeros((n, wpf), np.uint32)
+    streams[:, :wpf - 1] = np.packbits(masks.reshape(n, -1), axis=1, bitorder="little").view(np.uint32)
+    d_bits, d_pts, d_cnt = ctx.alloc(streams.nbytes), ctx.alloc(n * cap * 16), ctx.alloc(n * 4)
+
+    def run(variant, **knobs):
+        with ctx.tuning(**knobs):
+            ctx._check(ctx.lib.sfe_extract_set_tuning(ctx.handle, variant))
+            try:
+                single = [g.extract(m) for m in masks]
+                d_pts.upload(np.full(n * cap * 2, -7.0))
+                ctx._check(ctx.lib.sfe_extract_points_bits_batch_dev(ctx.handle, g.handle, d_bits.ptr, n, cap, d_pts.ptr, d_cnt.ptr))
+                ctx.sync()
+                return single, d_cnt.download(np.int32, n), d_pts.download(np.float64, n * cap * 2).reshape(n, cap, 2)
+            finally:
+                ctx._check(ctx.lib.sfe_extract_set_tuning(ctx.handle, 0))
+
+    try:
+        d_bits.upload(streams)
+        dense = run(1)
+        assert [len(locs) for locs, _ in dense[0]] == list(dense[1]) and 0 < dense[1][0] < dense[1][1] < dense[1][2]
+        for f in range(n):                                 # (the dense pass itself against the oracle)
+            assert np.array_equal(dense[0][f][0], oracle.nonzero(oracle.remap_u8(masks[f], mx, my)))
+            assert np.array_equal(dense[2][f, :dense[1][f]], dense[0][f][1])
+        for variant, knobs in ((0, {}), (0, {"extract_compact": 0}), (2, {}), (2, {"extract_compact": 0})):
+            got = run(variant, **knobs)
+            for f in range(n):
+                assert np.array_equal(got[0][f][0], dense[0][f][0]) and np.array_equal(got[0][f][1], dense[0][f][1]), (variant, knobs, f)
+            assert np.array_equal(got[1], dense[1]) and np.array_equal(got[2], dense[2]), (variant, knobs)
+    finally:
+        for b in (d_bits, d_pts, d_cnt):
+            b.free()
+        g.close()
 
 
 @pytest.mark.parametrize("variant", [0, 1, 2])
