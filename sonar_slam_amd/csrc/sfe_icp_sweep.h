@@ -30,8 +30,8 @@
 // wave, 256 candidates per trip.
 //
 // Mapping: prep kernel = one workgroup per distinct target (many guesses on one pair share it):
-// mean, centre, strip table, bitonic sort of (strip, x-key, index) in LDS (HBM scratch beyond 8192
-// points), sorted cloud + permutation to HBM scratch, PCA normals (k-NN by the same strip sweep) for
+// mean, centre, strip table, sort of (strip, x-key, index) in LDS, strip by strip (strip_sort_lds; a bitonic sort in HBM
+// scratch beyond 8192 points), sorted cloud + permutation to HBM scratch, PCA normals (k-NN by the same strip sweep) for
 // point-to-plane.  Loop kernel = one workgroup per job, all ICP iterations in one launch: sorted target
 // resident in LDS (or walked through L2 beyond 8192 points), per iteration: transform + capped walks
 // (tiers) -> census -> trimmed quantile by exact radix select -> fp64 reduction of the 9(+1) sums ->
@@ -178,7 +178,15 @@ __device__ __forceinline__ int next_strip(const StripTab &tab, int ns, int so, i
     return -1;
 }
 
-// in-LDS bitonic sort of n2 (power of two) 64-bit keys, ascending (NT = threads of the workgroup)
+// sort key: strip (8 bits) | order key of x (32 bits) | original index (24 bits)
+#define SW_KEY(s, xk, i) (((unsigned long long)(unsigned)(s) << 56) | ((unsigned long long)(xk) << 24) | (unsigned long long)(i))
+#define SW_KEY_STRIP(k) ((int)((k) >> 56))
+#define SW_KEY_X(k) ((unsigned)(((k) >> 24) & 0xFFFFFFFFull))
+#define SW_KEY_ID(k) ((int)((k) & 0xFFFFFFull))
+
+// in-LDS bitonic sort of n2 (power of two) 64-bit keys, ascending (NT = threads of the workgroup): one workgroup barrier
+// per compare-exchange stage (91 of them for 8192 keys).  Only strip_sort_lds below calls it, for key sets with a strip
+// of more than SW_SEG_MAX keys; everything else is sorted strip by strip without workgroup barriers.
 template <int NT>
 __device__ __forceinline__ void bitonic_sort_lds(unsigned long long *keys, unsigned n2)
 {
@@ -197,6 +205,98 @@ __device__ __forceinline__ void bitonic_sort_lds(unsigned long long *keys, unsig
             __syncthreads();
         }
     }
+}
+
+// Strips of more than this many keys send the whole key set through bitonic_sort_lds (a cloud with every point at one y,
+// a degenerate inv_g); a 5000-point sonar cloud has 80-100 keys per strip.
+#define SW_SEG_MAX 1024
+
+// one wave sorts seg[0 .. len) (LDS, 2 <= len <= SW_SEG_MAX) ascending.  The bitonic network over the next power of two
+// in its all-ascending form (a merge of size k starts with i <-> i ^ (k - 1), then i <-> i | j for j = k/4 .. 1): every
+// exchange leaves the smaller key at the lower index, so the padding beyond len -- +inf in effect -- never moves and is
+// neither stored nor read.  The lanes of a wave execute their LDS accesses in program order: between two stages the
+// compiler is held back (fence + wave barrier), the hardware needs nothing.
+__device__ __forceinline__ void wave_sort_lds(unsigned long long *seg, unsigned len)
+{
+    const unsigned lane = threadIdx.x & 63;
+    unsigned p2 = 2;
+    while (p2 < len)
+        p2 <<= 1;
+    auto stage = [&](unsigned j, unsigned flip) { // flip = k - 1: first stage of a merge, 0: the others
+        for (unsigned t = lane; t < p2 / 2; t += 64) {
+            const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+            const unsigned l = flip ? (i ^ flip) : (i | j);
+            if (l < len) {
+                const unsigned long long a = seg[i], b = seg[l];
+                if (a > b) {
+                    seg[i] = b;
+                    seg[l] = a;
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    for (unsigned k = 2; k <= p2; k <<= 1) {
+        stage(k >> 1, k - 1);
+        for (unsigned j = k >> 2; j > 0; j >>= 1)
+            stage(j, 0);
+    }
+}
+
+// Sorts the n keys key_of(0 .. n) into keys[0 .. n) (LDS), ascending -- what bitonic_sort_lds makes of them (the keys
+// are distinct: their low bits are an index) -- strip by strip: the strip is the top byte of a key, so the sorted array
+// is the strips' segments one after the other.  cnt[s] = keys of strip s (LDS, SW_NS_MAX entries, final and visible to
+// the workgroup: a barrier lies behind them); wk = 2 SW_NS_MAX ints of LDS.
+//   wave 0: segment starts (running sum of cnt) and the strips in descending order of their counts
+//   all   : every key is formed and dropped into its strip's segment through a cursor (order inside: whatever comes)
+//   waves : the segments are dealt to the waves, largest first, back and forth (a wall fills some strips with several
+//           times the mean), and each is sorted by its wave alone (wave_sort_lds)
+// Three workgroup barriers in all, one of them between the scatter and the sorts and one behind them.  A strip beyond
+// SW_SEG_MAX keys (decided from cnt, the same in every wave): keys[0 .. n2) is filled as before -- padded with ~0 to the
+// power of two n2 >= n -- and goes through bitonic_sort_lds; keys holds n2 entries for that case.
+template <int NT, class KeyFn>
+__device__ __forceinline__ void strip_sort_lds(unsigned long long *keys, unsigned n, unsigned n2, const int *cnt, int *wk,
+                                               KeyFn key_of)
+{
+    static_assert(SW_NS_MAX == 64, "one lane of a wave per strip");
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int NW = NT / 64;
+    const int c = cnt[lane];
+    if (__ballot(c > SW_SEG_MAX) != 0ull) {
+        for (unsigned i = tid; i < n2; i += NT)
+            keys[i] = i < n ? key_of(i) : ~0ull;
+        __syncthreads();
+        bitonic_sort_lds<NT>(keys, n2);
+        return;
+    }
+    int *cur = wk, *deal = wk + SW_NS_MAX;
+    if (wave == 0) {
+        int beg = 0, rank = 0;
+#pragma nounroll // (unrolled, its 64 lane reads sit in SGPRs at once and the loop kernel spills more for good)
+        for (int s = 0; s < SW_NS_MAX; ++s) {
+            const int cs = __builtin_amdgcn_readlane(c, s);
+            beg += s < lane ? cs : 0;
+            rank += (cs > c || (cs == c && s < lane)) ? 1 : 0;
+        }
+        cur[lane] = beg;
+        deal[rank] = lane;
+    }
+    __syncthreads();
+    for (unsigned i = tid; i < n; i += NT) {
+        const unsigned long long k = key_of(i);
+        keys[atomicAdd(&cur[SW_KEY_STRIP(k)], 1)] = k;
+    }
+    __syncthreads();
+    for (int q = 0; q * NW < SW_NS_MAX; ++q) {
+        const int r = q * NW + ((q & 1) ? NW - 1 - wave : wave);
+        const int s = __builtin_amdgcn_readfirstlane(deal[r]);
+        const int len = __builtin_amdgcn_readfirstlane(cnt[s]);
+        if (len >= 2)
+            wave_sort_lds(keys + (__builtin_amdgcn_readfirstlane(cur[s]) - len), (unsigned)len); // (the cursor ended behind its segment)
+    }
+    __syncthreads();
 }
 
 
@@ -336,12 +436,6 @@ struct SweepQ { // per-job views of the per-query scratch (the transformed query
     const int *perm;
 };
 
-
-// sort key: strip (8 bits) | order key of x (32 bits) | original index (24 bits)
-#define SW_KEY(s, xk, i) (((unsigned long long)(unsigned)(s) << 56) | ((unsigned long long)(xk) << 24) | (unsigned long long)(i))
-#define SW_KEY_STRIP(k) ((int)((k) >> 56))
-#define SW_KEY_X(k) ((unsigned)(((k) >> 24) & 0xFFFFFFFFull))
-#define SW_KEY_ID(k) ((int)((k) & 0xFFFFFFull))
 
 // ---------------------------------------------------------------------------------------------
 // The three translation units of the strip-sweep ICP (round 5: one 3 200-line file before):

@@ -260,30 +260,38 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     // lines -- the lockstep rounds below lose little to their slowest lane.  (A cloud in arbitrary order puts
     // a wall point next to an outlier in the same wave.)  The order only steers which lane searches for which
     // query: results are stored under the query's own index, and the sums of the error minimiser run in the
-    // original order.  Sorted once per job, in the LDS that will hold the target (chunks of 8192). ----
+    // original order.  Sorted once per job, in the LDS that will hold the target (chunks of 8192): the queries of a
+    // chunk are counted per strip, then strip_sort_lds scatters their keys into the strips' segments and sorts every
+    // segment inside one wave (the full bitonic network only if a strip holds more than SW_SEG_MAX queries).  The
+    // position under the guess is formed twice -- two affine maps -- rather than kept in registers in between. ----
     {
         unsigned long long *skeys = reinterpret_cast<unsigned long long *>(lds_tgt);
         float rloc = 0.0f; // largest |T0 * src| among this thread's queries (for the movement bounds of the clearance records)
+        int *scnt = reinterpret_cast<int *>(S.hist); // queries per strip (the histograms of the radix select are idle here,
+                                                     // S.hist0 lends the sort its work area)
+        auto qpos = [&](int q) { // query q under the guess
+            const float2 sp = src[q];
+            return make_float2(affine1(T0[0], T0[1], T0[2], sp.x, sp.y), affine1(T0[3], T0[4], T0[5], sp.x, sp.y));
+        };
         for (int c0 = 0; c0 < ns; c0 += sort_chunk) { // sort_chunk = the power of two of keys this LDS region holds
             const int n = min(sort_chunk, ns - c0);
             unsigned n2 = 2;
             while (n2 < (unsigned)n)
                 n2 <<= 1;
-            for (unsigned i = tid; i < n2; i += NT) {
-                unsigned long long k = ~0ull;
-                if (i < (unsigned)n) {
-                    const float2 sp = src[c0 + i];
-                    const float rx = affine1(T0[0], T0[1], T0[2], sp.x, sp.y);
-                    const float ry = affine1(T0[3], T0[4], T0[5], sp.x, sp.y);
-                    const int st_ = strip_of(ry, S.tab.ylo, S.tab.inv_g, S.tab.ns);
-                    k = SW_KEY(st_, mono_key(rx), c0 + i);
-                    const float rr = sqrtf(f_add(f_mul(rx, rx), f_mul(ry, ry)));
-                    rloc = (rr > rloc || rr != rr) ? rr : rloc; // (a NaN sticks: no bound, no record is ever used)
-                }
-                skeys[i] = k;
+            if (tid < SW_NS_MAX)
+                scnt[tid] = 0;
+            __syncthreads();
+            for (unsigned i = tid; i < (unsigned)n; i += NT) {
+                const float2 r = qpos(c0 + i);
+                atomicAdd(&scnt[strip_of(r.y, S.tab.ylo, S.tab.inv_g, S.tab.ns)], 1);
+                const float rr = sqrtf(f_add(f_mul(r.x, r.x), f_mul(r.y, r.y)));
+                rloc = (rr > rloc || rr != rr) ? rr : rloc; // (a NaN sticks: no bound, no record is ever used)
             }
             __syncthreads();
-            bitonic_sort_lds<NT>(skeys, n2);
+            strip_sort_lds<NT>(skeys, (unsigned)n, n2, scnt, reinterpret_cast<int *>(S.hist0), [&](unsigned i) {
+                const float2 r = qpos(c0 + i);
+                return SW_KEY(strip_of(r.y, S.tab.ylo, S.tab.inv_g, S.tab.ns), mono_key(r.x), c0 + i);
+            });
             for (int i = tid; i < n; i += NT) {
                 const int q = SW_KEY_ID(skeys[i]);
                 Q.order[c0 + i] = q;

@@ -480,26 +480,31 @@ __global__ __launch_bounds__(NT, GTAIL ? 8 : 4) void icp_sweep_prep_kernel(sfe_i
     }
     const float ylo = S.tab.ylo, inv_g = S.tab.inv_g;
 
-    // sort (strip, key(x - mean_x), index); strip population and y range on the way
+    // sort (strip, key(x - mean_x), index): strip population and y range first
     unsigned n2 = 2;
     while (n2 < (unsigned)nt)
         n2 <<= 1;
     const bool in_lds = nt <= TCAP;
     unsigned long long *keys = in_lds ? S.buf : gkeys_all + J.key_off;
-    for (unsigned i = tid; i < n2; i += NT) {
+    auto key_of = [&](unsigned i) {
+        const float2 t = tgt[i];
+        return SW_KEY(strip_of(f_add(t.y, -my), ylo, inv_g, ns), mono_key(f_add(t.x, -mx)), i);
+    };
+    // (a target in LDS only counts here: strip_sort_lds forms the keys again when it knows where each of them goes)
+    for (unsigned i = tid; i < (in_lds ? (unsigned)nt : n2); i += NT) {
         unsigned long long k = ~0ull;
         if (i < (unsigned)nt) {
-            const float2 t = tgt[i];
-            const float x = f_add(t.x, -mx), y = f_add(t.y, -my);
-            const int s = strip_of(y, ylo, inv_g, ns);
-            k = SW_KEY(s, mono_key(x), i);
+            const float y = f_add(tgt[i].y, -my);
+            k = key_of(i);
+            const int s = SW_KEY_STRIP(k);
             atomicAdd(&S.cnt[s], 1);
             if (y == y) {
                 atomicMin(&S.smin_k[s], mono_key(y));
                 atomicMax(&S.smax_k[s], mono_key(y));
             }
         }
-        keys[i] = k;
+        if (!in_lds)
+            keys[i] = k;
     }
     __syncthreads();
     if (tid == 0) {
@@ -549,7 +554,10 @@ __global__ __launch_bounds__(NT, GTAIL ? 8 : 4) void icp_sweep_prep_kernel(sfe_i
     };
     float2 *nrm = snrm_all ? snrm_all + J.off : nullptr;
     if (in_lds) {
-        bitonic_sort_lds<NT>(S.buf, n2);
+        // (the keys take nt <= TCAP entries of S.buf, TCAP at most on the detour through the full network: the cursors
+        // and the deal of the strips stand in the SW_NS_MAX entries behind them)
+        static_assert(SW_PAD + 4 >= SW_NS_MAX, "the work area of the strip sort fits behind the keys");
+        strip_sort_lds<NT>(S.buf, (unsigned)nt, n2, S.cnt, reinterpret_cast<int *>(S.buf + TCAP), key_of);
         // keys -> sorted centred cloud (registers -> same LDS bytes, in the strip layout)
         constexpr int PER = TCAP / NT;
         float2 v[PER];
