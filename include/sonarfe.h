@@ -344,8 +344,12 @@ int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const 
  * Brute-force only: bit 0: 0 = packed fp32 NN loop, 1 = scalar fp32; bit 1: 0 = 64-VGPR build,
  * 2 workgroups/CU, 1 = 128-VGPR build.  bit 3 (strip sweep only): the clouds and guesses handed to the ICP
  * entry points are final, i.e. no work enqueued earlier on this context still writes them; the preparation of
- * the targets (sort, strip table, normals) then runs on a side stream next to that earlier work and only the
- * iteration kernel waits for both.  Leave it clear when a preceding call on the context produces the clouds.
+ * the targets (sort, strip table, normals) is then enqueued on a side stream of the lowest priority, not behind
+ * that earlier work, and only the iteration kernel waits for both.  What the preparation writes exists twice and
+ * consecutive batches use the copies in turn, so the preparation of a batch waits for the iteration kernel of the
+ * batch two back, not for the one right before it, and runs beside that one (batches with jobs shared
+ * by several workgroups, bit 4, keep the wait for the batch before).  The bit may change between two calls without
+ * a synchronisation.  Leave it clear when a preceding call on the context produces the clouds.
  * bit 4: never share one large job between several workgroups.  Sharing (jobs of >= 8192 queries on a target beyond
  * 8192 points, when the call holds nothing else and shares x jobs <= CUs) needs every share resident at the same
  * time, which only a device this context has to itself can promise; a share that waits 0.5 s for the others gives up

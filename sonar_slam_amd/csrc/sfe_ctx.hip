@@ -27,7 +27,8 @@ void *sfe_scratch(sfe_ctx *ctx, int slot, size_t bytes)
     if (b.p) {
         (void)hipStreamSynchronize(ctx->stream);
         if (ctx->stream2)
-            (void)hipStreamSynchronize(ctx->stream2); // the ICP target preparation may run there
+            (void)hipStreamSynchronize(ctx->stream2); // the ICP target preparation may run there (its loop kernels, of
+                                                      // either generation, run on `stream`)
         if (ctx->stream_copy)
             (void)hipStreamSynchronize(ctx->stream_copy); // an upload into the old block may still be in flight
         // a "known to be zero" note about this buffer dies with it: hipMalloc commonly hands the same address out
@@ -194,13 +195,19 @@ int sfe_ctx_create(int device, sfe_ctx **out)
     sfe_ctx *c = new sfe_ctx();
     c->device = device;
     c->n_cu = prop.multiProcessorCount;
+    // (numerically the lowest priority is the LARGEST value of the range; a device without priorities reports 0, 0)
+    int prio_least = 0, prio_greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess)
+        prio_least = 0;
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_least) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream_copy, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_compute, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_prep, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_loop, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_loop[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_loop[1], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_loop_begin, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->pin[0].ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->pin[1].ev, hipEventDisableTiming) != hipSuccess ||
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) {
@@ -234,7 +241,9 @@ void sfe_ctx_destroy(sfe_ctx *ctx)
     (void)hipEventDestroy(ctx->ev0);
     (void)hipEventDestroy(ctx->ev1);
     (void)hipEventDestroy(ctx->ev_prep);
-    (void)hipEventDestroy(ctx->ev_loop);
+    (void)hipEventDestroy(ctx->ev_loop[0]);
+    (void)hipEventDestroy(ctx->ev_loop[1]);
+    (void)hipEventDestroy(ctx->ev_loop_begin);
     (void)hipEventDestroy(ctx->ev_copy);
     (void)hipEventDestroy(ctx->ev_compute);
     (void)hipStreamDestroy(ctx->stream_copy);

@@ -196,23 +196,41 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
     const size_t o_pids = o_split + sizeof(int) * (size_t)n_split;
     const size_t o_pnrm = o_pids + sizeof(int) * (size_t)n_prep;
     const size_t tab_bytes = o_pnrm + sizeof(int) * pids_nrm.size();
-    char *d_tables = (char *)sfe_scratch(ctx, 12, tab_bytes);
-    float2 *d_stgt = (float2 *)sfe_scratch(ctx, 14, sizeof(float2) * (size_t)toff);
-    int *d_perm = (int *)sfe_scratch(ctx, 15, sizeof(int) * (size_t)toff);
-    float2 *d_snrm = p->minimizer == 1 ? (float2 *)sfe_scratch(ctx, 16, sizeof(float2) * (size_t)toff) : nullptr;
-    float *d_mean = (float *)sfe_scratch(ctx, 17, sizeof(float) * 2 * (size_t)n_prep);
-    unsigned long long *d_gkeys = (unsigned long long *)sfe_scratch(ctx, 24, sizeof(unsigned long long) * (size_t)std::max(koff, 1LL));
+    // Tuning bit 3: the caller vouches that the clouds and guesses of this batch are final (nothing enqueued on
+    // ctx->stream still writes them).  The job tables and the preparation kernels then go to the side stream and write
+    // generation g of their scratch, while the loop kernel of the batch before may still read the other one
+    // (sfe_icp_gen.h).  Without the bit: generation 0, everything on ctx->stream.
+    const bool side = (ctx->icp_variant & 8) != 0;
+    const SfeIcpGenPlan gen = sfe_icp_gen_begin(ctx->icp_gens, side, n_split > 0);
+    if (gen.sync_first) { // the launch before returned an error half-way: what it left on the streams is in no event
+        SFE_HIP(ctx, hipStreamSynchronize(ctx->stream2));
+        SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // scratch slots of what the preparation writes and the loop reads, by generation.  (A slot that grows waits for
+    // every stream of the context before it frees its block: sfe_scratch.)
+    enum { G_TABLES, G_STGT, G_PERM, G_SNRM, G_MEAN, G_GKEYS, G_TAB, G_GRID, G_N };
+    static const int gen_slot[2][G_N] = {{12, 14, 15, 16, 17, 24, 23, 38}, {72, 73, 74, 75, 76, 77, 78, 79}};
+    static_assert(SFE_NSCRATCH == 80, "generation 1 takes the last eight slots");
+    const int *gs = gen_slot[gen.g];
+    char *d_tables = (char *)sfe_scratch(ctx, gs[G_TABLES], tab_bytes);
+    float2 *d_stgt = (float2 *)sfe_scratch(ctx, gs[G_STGT], sizeof(float2) * (size_t)toff);
+    int *d_perm = (int *)sfe_scratch(ctx, gs[G_PERM], sizeof(int) * (size_t)toff);
+    float2 *d_snrm = p->minimizer == 1 ? (float2 *)sfe_scratch(ctx, gs[G_SNRM], sizeof(float2) * (size_t)toff) : nullptr;
+    float *d_mean = (float *)sfe_scratch(ctx, gs[G_MEAN], sizeof(float) * 2 * (size_t)n_prep);
+    unsigned long long *d_gkeys =
+        (unsigned long long *)sfe_scratch(ctx, gs[G_GKEYS], sizeof(unsigned long long) * (size_t)std::max(koff, 1LL));
     int4 *d_qst = (int4 *)sfe_scratch(ctx, 19, sizeof(int4) * (size_t)qoff);
     int *d_qwl = (int *)sfe_scratch(ctx, 21, sizeof(int) * 7 * (size_t)qoff);
     float2 *d_qssrc = (float2 *)sfe_scratch(ctx, 30, sizeof(float2) * (size_t)qoff);
-    StripTab *d_tab = (StripTab *)sfe_scratch(ctx, 23, sizeof(StripTab) * (size_t)n_prep);
-    int *d_grid = (int *)sfe_scratch(ctx, 38, sizeof(int) * (size_t)goff);
+    StripTab *d_tab = (StripTab *)sfe_scratch(ctx, gs[G_TAB], sizeof(StripTab) * (size_t)n_prep);
+    int *d_grid = (int *)sfe_scratch(ctx, gs[G_GRID], sizeof(int) * (size_t)goff);
     float *d_nn_d2 = (float *)sfe_scratch(ctx, 5, sizeof(float) * (size_t)qoff);
     int *d_nn_pos = (int *)sfe_scratch(ctx, 6, sizeof(int) * (size_t)qoff);
     if (!d_tables || !d_stgt || !d_perm || (p->minimizer == 1 && !d_snrm) || !d_mean || !d_gkeys || !d_qst || !d_qwl || !d_qssrc || !d_tab || !d_grid ||
         !d_nn_d2 || !d_nn_pos)
         return SFE_ERR_HIP;
-    // split jobs: the gathered source clouds of the shares and the sync areas
+    // split jobs: the gathered source clouds of the shares and the sync areas (one generation: a preparation that
+    // writes them waits for every earlier loop kernel)
     float2 *d_gsrc = nullptr;
     unsigned long long *d_sync = nullptr;
     const size_t sync_bytes = sizeof(unsigned long long) * 2 * SW_MG_MAX * SW_MG_WORDS * (size_t)n_sync;
@@ -227,14 +245,15 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
     int *d_ids = (int *)(d_tables + o_ids);
     int *d_split = (int *)(d_tables + o_split);
     int *d_pids = (int *)(d_tables + o_pids);
-    // Tuning bit 3: the caller vouches that the clouds and guesses of this batch are final (nothing enqueued on
-    // ctx->stream still writes them).  The job tables and the prep kernel then go to the side stream and run next to
-    // whatever precedes this call on ctx->stream (a batch pipeline enqueues the front end of the same step there:
-    // latency-bound kernels that leave most of a CU idle, like the prep kernel); the loop kernel waits for them.
-    const bool side = (ctx->icp_variant & 8) != 0;
+    // The side stream has the lowest priority: the preparation takes the workgroup slots that whatever runs on
+    // ctx->stream leaves free -- the loop kernel of the batch before, for its whole length, then the front end that a batch
+    // pipeline enqueues there for the same step; the loop kernel of this batch waits for it (ev_prep).
     hipStream_t ps = side ? ctx->stream2 : ctx->stream;
-    if (side && ctx->icp_loop_pending) // the previous batch's loop kernel still reads the scratch the prep rewrites
-        SFE_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_loop, 0));
+    for (int g = 0; g < 2; ++g) // the loop kernels that still read what this preparation rewrites
+        if (gen.wait[g])
+            SFE_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_loop[g], 0));
+    if (gen.wait_begin) // ... and it starts with the newest loop kernel, not with what is enqueued in front of that
+        SFE_HIP(ctx, hipStreamWaitEvent(ps, ctx->ev_loop_begin, 0));
     { // pinned staging (no stream synchronisation: this entry point only enqueues)
         char *h = (char *)sfe_pinned_begin(ctx, tab_bytes);
         if (!h)
@@ -331,6 +350,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
         return SFE_ERR_HIP;
     if (d_prof)
         SFE_HIP(ctx, hipMemsetAsync(d_prof, 0, sizeof(long long) * SFE_ICP_PROF_N, ctx->stream));
+    SFE_HIP(ctx, hipEventRecord(ctx->ev_loop_begin, ctx->stream)); // (where the next batch's preparation may start)
     SweepLaunchArgs a;
     a.ctx = ctx;
     a.p = p;
@@ -463,10 +483,9 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
             return rc;
         ids += n_multi;
     }
-    if (side) {
-        SFE_HIP(ctx, hipEventRecord(ctx->ev_loop, ctx->stream));
-        ctx->icp_loop_pending = true;
-    }
+    // (recorded without bit 3 too: the next batch may come with the bit set, its preparation on the side stream)
+    SFE_HIP(ctx, hipEventRecord(ctx->ev_loop[gen.g], ctx->stream));
+    sfe_icp_gen_end(ctx->icp_gens, gen, side, n_split > 0);
     if (debug) {
         int h[8];
         SFE_HIP(ctx, hipMemcpyAsync(h, d_dbg, sizeof h, hipMemcpyDeviceToHost, ctx->stream));

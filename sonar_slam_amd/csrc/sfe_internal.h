@@ -8,8 +8,9 @@
 #include <vector>
 
 #include "../../include/sonarfe.h"
+#include "sfe_icp_gen.h"
 
-#define SFE_NSCRATCH 72
+#define SFE_NSCRATCH 80 // (0..71: the numbers and the CF_SLOT_* / DPF_SLOT_* names in the .hip files; 72..79: sfe_icp_sweep.hip)
 #define SFE_ICP_PROF_N 96 // values sfe_icp_get_profile hands back
 
 // Launcher knobs of one context, set by name with sfe_tune (the name -> field / range table is in sfe_ctx.hip).  The
@@ -51,12 +52,16 @@ struct sfe_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // side stream of the ICP launcher (icp_variant bit 3): the prep kernel of a batch whose inputs are final runs
-    // here, next to whatever precedes the ICP call on `stream`; ev_prep orders the loop kernel behind it, ev_loop
-    // keeps the next batch's prep off the scratch the loop kernel still reads
+    // side stream of the ICP launcher (icp_variant bit 3), created with the lowest priority the device offers: the
+    // preparation of a batch whose inputs are final is enqueued here and takes the CUs that the kernels on `stream` --
+    // the loop kernel of the batch before, mostly, and the front end of the same step -- leave free.  ev_prep
+    // orders the loop kernel behind it.  What the preparation writes and the loop reads exists in two generations
+    // (sfe_icp_gen.h); ev_loop[g] is recorded behind the loop kernels that read generation g and keeps the
+    // preparation of the batch after next off that scratch; ev_loop_begin is recorded in front of a batch's loop
+    // kernels, and the next preparation starts behind it: next to a loop kernel, not next to the caller's other work.
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_prep = nullptr, ev_loop = nullptr;
-    bool icp_loop_pending = false;
+    hipEvent_t ev_prep = nullptr, ev_loop[2] = {nullptr, nullptr}, ev_loop_begin = nullptr;
+    SfeIcpGenState icp_gens;
     // copy stream of the streamed-input path (sfe_memcpy_h2d_async): uploads from pinned host memory run next to the
     // kernels on `stream`; ev_copy = behind the last upload, ev_compute = where the kernels stood when the caller last
     // said "everything enqueued so far has consumed its input" (sfe_stream_fence)
@@ -125,7 +130,9 @@ struct sfe_geom {
 int sfe_set_err(sfe_ctx *ctx, int code, const char *fmt, ...);
 int sfe_mask_pack(sfe_ctx *ctx, const uint8_t *d_mask, int n_frames, long long px, uint32_t *d_bits,
                   int32_t *d_nonbin); // sfe_extract.hip: byte mask -> bit stream
-void *sfe_scratch(sfe_ctx *ctx, int slot, size_t bytes);  // grow-only device scratch; nullptr on failure
+// grow-only device scratch; nullptr on failure.  Growing a slot frees its old block, so it first waits (host side) for
+// all three streams of the context: no kernel of an earlier ICP batch, of either generation, still reads the block.
+void *sfe_scratch(sfe_ctx *ctx, int slot, size_t bytes);
 // Pinned staging: sfe_pinned_begin hands out a host block of >= bytes (waiting, if need be, for the copy that last
 // read it -- two launches ago); the caller fills it, enqueues its hipMemcpyAsync calls on `s` and then calls
 // sfe_pinned_end(ctx, s) so the block is not reused before those copies have run.  nullptr on failure.
