@@ -5,6 +5,7 @@
 #include "sfe_internal.h"
 #include "sfe_cloudfilter.h"
 #include "sfe_remap_value.h"
+#include "sfe_extract_shape.h"
 
 #include <algorithm>
 #include <climits>
@@ -584,7 +585,7 @@ __global__ __launch_bounds__(256, 8) void extract_gather_kernel(const uint32_t *
     const int slices = gridDim.x;
     // rotate the pieces from frame to frame: workgroups are dealt to the 8 XCDs in launch order, and every XCD should
     // see every range band (cf. mode 2 of the kernel above)
-    const int sl = (int)((blockIdx.x + 5u * blockIdx.y) % (unsigned)slices);
+    const int sl = gather_slice_of(blockIdx.x, blockIdx.y, slices);
     const uint32_t *__restrict__ src = bits + (long long)f * words_per_frame;
     unsigned long long *__restrict__ bm = bitmap + (long long)f * crows * wpr;
     // records: this workgroup's region of the frame's list (SG_TAB slots: the table holds no more) and, for the few words that
@@ -602,10 +603,8 @@ __global__ __launch_bounds__(256, 8) void extract_gather_kernel(const uint32_t *
     };
     // pieces of 64 << piece_shift words (64 words = 4 polar rows of 512 beams); piece p belongs to slice p % slices.  The
     // workgroup's words, piece after piece, are looked at `blk` at a time: thread t takes words t, t + 256, ...
-    const int pwords = 64 << piece_shift;
-    const int npieces = (nwords + pwords - 1) >> (6 + piece_shift);
-    const int my_pieces = (npieces - sl + slices - 1) / slices; // pieces sl, sl + slices, ...
-    const int my_words = my_pieces * pwords;
+    // (sfe_extract_shape.h: the arithmetic, and tests/host/extract_shape_check.cpp for what it promises)
+    const int my_words = gather_my_words(gather_my_pieces(gather_pieces(nwords, piece_shift), sl, slices), piece_shift);
     int v0 = 0, blk = SG_BLOCK, par = 0;
     while (true) {
         // ---- collect: steps of `blk` words while their set pixels fit the list
@@ -615,7 +614,7 @@ __global__ __launch_bounds__(256, 8) void extract_gather_kernel(const uint32_t *
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int v = v0 + u * 256 + tid;
-                gw[u] = (sl + (v >> (6 + piece_shift)) * slices) * pwords + (v & (pwords - 1));
+                gw[u] = gather_word(sl, v, slices, piece_shift);
                 w[u] = (u * 256 + tid < blk && v < my_words && gw[u] < nwords) ? src[gw[u]] : 0u;
                 pc += __popc(w[u]);
             }
@@ -1193,34 +1192,6 @@ static ExtractRoute extract_route(const sfe_ctx *ctx, const sfe_geom *g, long lo
     return r;
 }
 
-// Workgroups of the gather kernel per frame (`slices`, never more than 64: s_rp of the merge kernel holds 64 regions + the
-// spill region) and the size of the pieces they take turns at, for a chunk of nf frames.
-struct GatherShape {
-    int slices, piece_shift;
-};
-static GatherShape gather_shape(const ExtractRoute &r, int nf)
-{
-    // workgroups per frame: enough of them to fill the device with a few frames, few enough that a
-    // workgroup's list holds several rounds of 256 set pixels when there are many
-    // 8192 workgroups per 512 frames measured best (16: 0.259 ms per 512 frames, 8: 0.274, 4: 0.36 -- a workgroup's
-    // rounds of 256 set pixels wait for their loads one after the other), in pieces of 1024 words when the frame
-    // has that many per workgroup (64 rows of 512 beams: a canvas word collects its bits from neighbouring rows,
-    // so whole bands keep the table's words to one workgroup; 0.280 -> 0.259)
-    // (record path: twice the workgroups per frame -- a workgroup's table of 1024 canvas words is its record region, and
-    // at 8 workgroups per frame the densest bands of the bench's frames filled it: 77 spilled words per frame, each a
-    // returning atomic, 2 % of the frames handed back; profiles/r05_extract_records_stats.txt.
-    // Measured: 256 frames per launch 59.1 us with 32 workgroups per frame, 72.7 with 64; 512 frames 0.147 ms with 16, 0.165
-    // with 32; 1024 frames 0.256 ms with 16.  So: 8192 workgroups per launch, but between 16 and 32 per frame for batches.)
-    int slices = std::max(2, std::min(64, 8192 / std::max(nf, 1)));
-    if (r.records && nf >= 64)
-        slices = std::max(16, std::min(32, slices));
-    slices = (int)std::max<long long>(1, std::min<long long>(slices, (r.nwords + 63) / 64));
-    int piece = 4;
-    while (piece > 0 && (r.nwords >> (6 + piece)) < slices)
-        --piece;
-    return {slices, piece};
-}
-
 // The context's "the canvas bitmap scratch is zero up to `bytes`" for the duration of one call: taken from the context at
 // construction -- which then knows nothing -- and given back by commit() once every launch of the call went through.  An
 // error return in between never commits: the state stays unknown and the next call clears the bitmap.
@@ -1328,7 +1299,7 @@ struct ExtractCall {
         p32 = d_p32 ? d_p32 + (size_t)f0 * cap : nullptr;
         bbox = d_bbox ? d_bbox + f0 : nullptr;
         counts = d_counts + f0;
-        gs = gather_shape(r, nf);
+        gs = gather_shape(r.nwords, r.records, nf); // (sfe_extract_shape.h)
         d_rec = nullptr;
         d_rec_n = d_ovf_flag = nullptr;
         if (r.records) {
