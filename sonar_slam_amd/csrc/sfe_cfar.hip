@@ -1,10 +1,15 @@
 // CFAR detectors on gfx950.  Replaces bruce_slam/src/bruce_slam/cpp/cfar.cpp:10-192.
 //
-// Three kernels:
-//   cfar_u8_ring<T,G,ALG>  the hot path (uint8 sonar image, CA/SOCA/GOCA, shipped window):
-//                          HBM-bound streaming kernel, 1 B read + 1 B written per pixel.
-//   cfar_u8_generic        any window / any variant incl. OS and the *2 threshold maps.
-//   cfar_f32_naive         float images: the reference's float sums in the reference's order.
+// Kernels:
+//   cfar_u8_ring<T,G,ALG,D,BITS,THR>  the hot path (uint8 sonar image, CA/SOCA/GOCA, the compiled windows): HBM-bound
+//                                     streaming kernel, 1 B read + 1 B (or 1 bit, BITS) written per pixel; THR adds the map.
+//   cfar_u8_slide<ALG,THR>            CA/SOCA/GOCA over a run-time window: sliding sums, window rows re-read through the caches.
+//   cfar_u8_slide_lds<ALG,THR>        the same with the window rows staged in LDS (windows of up to 80 rows).
+//   cfar_u8_os                        OS: sliding 256-bin histogram and rank walk per pixel.
+//   cfar_u8_os_gated<V16,PREF>        OS, candidates only: behind an intensity gate (PREF 0) or a pre-filter (PREF 1, 2).
+//   cfar_u8_generic                   any window / any variant incl. OS and the *2 threshold maps.
+//   cfar_f32_naive                    float images: the reference's float sums in the reference's order.
+// Which of the uint8 kernels a call takes: sfe_cfar_route.h.
 //
 // Exactness of the uint8 paths: inputs are integers 0..255, so the reference's
 // float window sums (<= 2*train_hs*255 < 2^24) are exact integers whatever the order; we sum
@@ -13,16 +18,13 @@
 // the number of window sums that pass: lut[x] = #{s : x > f(s)}; pixel fires iff s < lut[x].
 // The table is built on the host with exactly the reference's double expression.
 #include "sfe_internal.h"
+#include "sfe_cfar_route.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-
-struct CfarLut {
-    uint16_t v[256];
-};
 
 __device__ __forceinline__ uint32_t pk_add(uint32_t a, uint32_t b)
 {
@@ -71,27 +73,6 @@ __device__ __forceinline__ uint32_t pk_sub_opaque(uint32_t a, uint32_t b)
 }
 
 typedef __amdgpu_buffer_rsrc_t sfe_rsrc_t; // 128-bit buffer resource (SGPRs)
-
-// The threshold map's value for a window sum s, thr = (float)(tau * (double)(float)s / D) with D = T or 2T (cfar.cpp:27,46,67
-// as the host table below restates it), computed instead of fetched: one table gather per pixel is one L1 tag look-up
-// per pixel, and that rate -- not HBM -- bounded the map kernels (0.47-0.60 ms per 512 frames whatever the window).
-// The quotient is formed with the reciprocal of D and two residual corrections (fma), which is the correctly rounded
-// quotient for every operand the host has tried: cfar_u8_dev evaluates this very sequence for every possible sum of the
-// launch and compares it with the table bit by bit -- a single difference and the kernel keeps the table (ta.on = 0).
-struct CfarThrArith {
-    double tau, rinv, d;
-    int on;
-};
-__host__ __device__ __forceinline__ float cfar_thr_arith(const CfarThrArith &ta, uint32_t sv)
-{
-    const double p = ta.tau * (double)(float)sv;
-    double q = p * ta.rinv;
-    double e = fma(-ta.d, q, p);
-    q = fma(e, ta.rinv, q);
-    e = fma(-ta.d, q, p);
-    q = fma(e, ta.rinv, q);
-    return (float)q;
-}
 
 
 // Tiles and column chunks OVERLAP instead of being predicated: a tile is always a whole number
@@ -514,11 +495,6 @@ __global__ __launch_bounds__(256) void cfar_u8_slide_lds(const uint8_t *__restri
 // nth_element for every pixel; the generic kernel counted ranks in O((2T)^2).  Decision and threshold are table
 // look-ups over the 256 possible values of v, built on the host with the reference's double expression.
 // ---------------------------------------------------------------------------------------------
-struct CfarOsTab {
-    uint16_t min_x[256]; // pixel fires iff x >= min_x[v]  (256 = never); the intensity gate is folded in
-    float thr[256];      // (float)(tau * v)
-};
-
 __global__ __launch_bounds__(64) void cfar_u8_os(const uint8_t *__restrict__ img, uint8_t *__restrict__ mask,
                                                  float *__restrict__ thr, int rows, int cols, int n_frames, int T, int G,
                                                  int k, int tile_rows, int tiles_per_frame, int chunks_per_row,
@@ -605,19 +581,6 @@ __global__ __launch_bounds__(64) void cfar_u8_os(const uint8_t *__restrict__ img
 // copy (1 B in + 1 B out per pixel + the halo).  Same masks as cfar_u8_os / the reference (tests: every OS case with a
 // gate runs through this kernel).  Replaces cfar.cpp:76-96 + feature_extraction.py:224.
 // ---------------------------------------------------------------------------------------------
-#define OSG_TR 128 // tile rows
-#define OSG_TC 128 // tile columns (bytes per staged row)
-#define OSG_LIST 192 // candidates a wave collects before it takes 64 of them
-
-struct CfarOsGateTab {
-    int16_t L[256]; // pixel value x -> largest v with x > tau * v and x above the gate; -1: never fires
-    int xc;         // smallest x with L[x] >= 0 (L grows with x: "can fire at all" is one threshold); 257: none
-    // PREF (no gate, or a low one: round 6): the level l0 of the pre-filter and what the kernel needs of it
-    int x_hi;       // smallest x with L[x] > l0 (257: none)
-    int c0;         // l0 + 1: a training cell counts as "above" when it is >= c0
-    int m_le;       // 2T - (k + 1): at most that many cells above l0 <=> at least k + 1 cells <= l0
-};
-
 // cfar.os() WITHOUT the gate (the drop-in's plain `cfar.os`, `feature.yaml alg: OS` with a low threshold): rounds 2-5 ran the
 // sliding 256-bin histogram for every pixel (cfar_u8_os: 4 % of HBM).  PREF turns the image's own statistics into the gate:
 //     x fires  <=>  at least k + 1 training cells are <= L[x]  =>  (L[x] > l0)  or  (at least k + 1 cells are <= l0)
@@ -970,347 +933,150 @@ __global__ __launch_bounds__(256) void cfar_f32_naive(const float *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
-// host side
+// host side: describe the call (CfarCall), ask sfe_cfar_route.h for its route, launch what the route names.
+// One table of template instances per kernel template, indexed as the route says.
 // ---------------------------------------------------------------------------------------------
-static bool build_lut(int alg, int T, double tau, int intensity_thr, CfarLut *lut)
+typedef void (*RingKernel)(const uint8_t *, uint8_t *, int, int, int, int, int, int, long long, CfarLut, float *, CfarThrArith, int);
+typedef void (*SlideKernel)(const uint8_t *, uint8_t *, float *, const float *, int, int, int, int, int, int, int, int, CfarLut,
+                            CfarThrArith);
+typedef void (*OsGatedKernel)(const uint8_t *, uint8_t *, int, int, int, int, int, int, int, int, CfarOsGateTab);
+
+#define RING_ALGS(T, G, D, BITS, THR)                                                                                  \
+    {cfar_u8_ring<T, G, SFE_CFAR_CA, D, BITS, THR>, cfar_u8_ring<T, G, SFE_CFAR_SOCA, D, BITS, THR>,                   \
+     cfar_u8_ring<T, G, SFE_CFAR_GOCA, D, BITS, THR>}
+#define RING_ALL(T, G, D) {RING_ALGS(T, G, D, false, false), RING_ALGS(T, G, D, true, false), RING_ALGS(T, G, D, false, true)},
+#define RING_MASK(T, G, D) {RING_ALGS(T, G, D, false, false), {}, {}},
+// [CfarRoute::instance][CfarOut][alg]
+static const RingKernel ring_kernels[CFAR_RING_INSTANCES][3][3] = {CFAR_RING_WINDOW_LIST(RING_ALL) CFAR_RING_V3(RING_MASK)};
+#define SLIDE_ALGS(K, THR) {K<SFE_CFAR_CA, THR>, K<SFE_CFAR_SOCA, THR>, K<SFE_CFAR_GOCA, THR>}
+// [LDS ring][threshold map][alg]
+static const SlideKernel slide_kernels[2][2][3] = {{SLIDE_ALGS(cfar_u8_slide, false), SLIDE_ALGS(cfar_u8_slide, true)},
+                                                   {SLIDE_ALGS(cfar_u8_slide_lds, false), SLIDE_ALGS(cfar_u8_slide_lds, true)}};
+// [v16][PREF]
+static const OsGatedKernel os_gated_kernels[2][3] = {
+    {cfar_u8_os_gated<false, 0>, cfar_u8_os_gated<false, 1>, cfar_u8_os_gated<false, 2>},
+    {cfar_u8_os_gated<true, 0>, cfar_u8_os_gated<true, 1>, cfar_u8_os_gated<true, 2>}};
+
+// cfar_thr_arith checked against the reference expression for every window sum of (alg, T, tau), cached per context
+static int thr_arith_checked(sfe_ctx *ctx, int alg, int T, double tau)
 {
-    if (!(tau >= 0.0) || !std::isfinite(tau))
-        return false;
-    const int smax = (alg == SFE_CFAR_CA) ? 255 * 2 * T : 255 * T;
-    if (smax + 1 > 65535)
-        return false;
-    auto passes = [&](int x, int s) -> bool {
-        const float sf = (float)s; // the reference holds the sum in a float (exact here)
-        const double t = (alg == SFE_CFAR_CA) ? tau * sf / (2.0 * T) : tau * sf / T;
-        return (double)(float)x > t;
-    };
-    for (int x = 0; x < 256; ++x) {
-        int cnt = 0;
-        if (!(intensity_thr >= 0 && x <= intensity_thr) && passes(x, 0)) {
-            int lo = 0, hi = smax; // passes(lo) true; find the largest passing s (monotone in s)
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (passes(x, mid))
-                    lo = mid;
-                else
-                    hi = mid - 1;
-            }
-            cnt = lo + 1;
-        }
-        lut->v[x] = (uint16_t)cnt;
+    SfeCfarCache &c = ctx->cfar_cache;
+    if (!c.arith.is(alg, T, tau)) {
+        c.arith_on = cfar_thr_arith_check(alg, T, tau);
+        c.arith = {alg, T, tau};
     }
-    return true;
+    return c.arith_on;
 }
 
-template <int T, int G, int D, bool BITS, bool THR = false>
-static void launch_ring(sfe_ctx *ctx, int alg, const uint8_t *d_img, uint8_t *d_mask, int rows, int cols,
-                        int n_frames, int groups, int tiles, long long out_frame_bytes, const CfarLut &lut,
-                        float *d_thr = nullptr, CfarThrArith ta = CfarThrArith{0.0, 0.0, 1.0, 0})
+// thr = (float)(tau * s / T) per integer window sum s, with the reference's double expression: the sliding-sum kernel's
+// table on the device (scratch slot 37), uploaded when (alg, T, tau) or the slot's block changed
+static int slide_thr_table(sfe_ctx *ctx, int alg, int T, double tau, const float **d_tab)
 {
-    const int chunks = ((cols >> 2) + 63) / 64;
-    const long long bpf = ((long long)tiles * chunks + 3) / 4;             // workgroups per frame
-    const unsigned blocks = (unsigned)((((long long)n_frames + 7) / 8) * 8 * bpf); // frames padded to the 8 XCDs
-    const int full_last = 0; // (1: the last tile as long as the others, rounds 1-4)
-    if (alg == SFE_CFAR_SOCA)
-        hipLaunchKernelGGL((cfar_u8_ring<T, G, SFE_CFAR_SOCA, D, BITS, THR>), dim3(blocks), dim3(256), 0, ctx->stream,
-                           d_img, d_mask, rows, cols, n_frames, groups, tiles, chunks, out_frame_bytes, lut, d_thr, ta, full_last);
-    else if (alg == SFE_CFAR_GOCA)
-        hipLaunchKernelGGL((cfar_u8_ring<T, G, SFE_CFAR_GOCA, D, BITS, THR>), dim3(blocks), dim3(256), 0, ctx->stream,
-                           d_img, d_mask, rows, cols, n_frames, groups, tiles, chunks, out_frame_bytes, lut, d_thr, ta, full_last);
-    else
-        hipLaunchKernelGGL((cfar_u8_ring<T, G, SFE_CFAR_CA, D, BITS, THR>), dim3(blocks), dim3(256), 0, ctx->stream,
-                           d_img, d_mask, rows, cols, n_frames, groups, tiles, chunks, out_frame_bytes, lut, d_thr, ta, full_last);
-}
-
-// cfar_thr_arith checked against the reference expression for every window sum of (alg, T, tau): on = 1 when each of them
-// agrees bit by bit (cached per context)
-static CfarThrArith thr_arith_checked(sfe_ctx *ctx, int alg, int T, double tau)
-{
-    const double d = (alg == SFE_CFAR_CA) ? 2.0 * T : (double)T;
-    CfarThrArith ta{tau, 1.0 / d, d, 1};
-    if (ctx->tha_alg == alg && ctx->tha_T == T && ctx->tha_tau == tau) {
-        ta.on = ctx->tha_on;
-        return ta;
+    SfeCfarCache &c = ctx->cfar_cache;
+    const size_t n = (size_t)cfar_smax(alg, T) + 1;
+    float *tab = (float *)sfe_scratch(ctx, 37, sizeof(float) * n);
+    if (!tab)
+        return SFE_ERR_HIP;
+    if (!(c.tab.is(alg, T, tau) && c.tab_ptr == tab)) {
+        float *h = (float *)sfe_pinned_begin(ctx, sizeof(float) * n);
+        if (!h)
+            return SFE_ERR_HIP;
+        for (size_t sv = 0; sv < n; ++sv)
+            h[sv] = (float)cfar_ref_thr(alg, T, tau, (long long)sv);
+        SFE_HIP(ctx, hipMemcpyAsync(tab, h, sizeof(float) * n, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = sfe_pinned_end(ctx, ctx->stream))
+            return rc;
+        c.tab = {alg, T, tau};
+        c.tab_ptr = tab;
     }
-    const int smax = (alg == SFE_CFAR_CA) ? 255 * 2 * T : 255 * T;
-    for (int sv = 0; sv <= smax && ta.on; ++sv) {
-        const float sf = (float)sv;
-        const float want = (float)((alg == SFE_CFAR_CA) ? tau * (double)sf / (2.0 * T) : tau * (double)sf / T);
-        const float got = cfar_thr_arith(ta, (uint32_t)sv);
-        if (__builtin_memcmp(&want, &got, sizeof want) != 0)
-            ta.on = 0; // (never seen: the kernels then read the table)
-    }
-    ctx->tha_alg = alg;
-    ctx->tha_T = T;
-    ctx->tha_tau = tau;
-    ctx->tha_on = ta.on;
-    return ta;
-}
-
-// R-row groups per tile.  Measured on MI355X (tools/cfar_sweep.py, 1024 frames of 1024x512, XCD-aware
-// map + alternating march direction):  1 group/tile 5.1 TB/s with FETCH = 1.30x the image bytes,
-// 2 groups 5.1 TB/s with 1.13x, 4 groups 4.9 TB/s with 1.07x, whole column 3.1 TB/s.  Short tiles win
-// on time (the kernel is bound by each wave's serial row march, more independent waves hide it);
-// 2 groups keep that speed and most of the 2*(T+G) halo rows a tile re-reads are L2 hits.
-static int default_groups(const sfe_ctx *, int rows, int, int, int R) { return rows >= 2 * R ? 2 : 1; }
-
-static int launch_os_hist(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int rows, int cols, int T, int G, int k,
-                          double tau, int intensity_thr, uint8_t *d_mask, float *d_thr)
-{
-    CfarOsTab tab;
-    for (int v = 0; v < 256; ++v) {
-        const double t = tau * (double)(float)v; // cfar.cpp:92 / :186
-        tab.thr[v] = (float)t;
-        int mx = 256;
-        for (int x = 255; x >= 0; --x) // (double)x > t is monotone in x
-            if ((double)(float)x > t && !(intensity_thr >= 0 && x <= intensity_thr))
-                mx = x;
-            else
-                break;
-        tab.min_x[v] = (uint16_t)mx;
-    }
-    const int tile_rows = std::min(rows, std::max(256, 8 * T));
-    const int tiles = (rows + tile_rows - 1) / tile_rows;
-    const int chunks = (cols + 63) / 64;
-    const long long blocks = (long long)n_frames * tiles * chunks;
-    hipLaunchKernelGGL(cfar_u8_os, dim3((unsigned)blocks), dim3(64), 0, ctx->stream, d_img, d_mask, d_thr, rows, cols,
-                       n_frames, T, G, k, tile_rows, tiles, chunks, tab);
+    *d_tab = tab;
     return 0;
 }
 
-// pref: the pre-filtered form for a missing or low gate (see the kernel); *applied (nullable) = false when it does not apply
-// (no level to filter on, a window the packed counters do not hold) and nothing was launched
-static int launch_os_gated(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int rows, int cols, int T, int G, int k, double tau,
-                           int intensity_thr, uint8_t *d_mask, bool pref = false, bool *applied = nullptr)
+// out: the byte mask, or the bit stream with bits set (CFAR_OUT_BITS; the caller packs the byte kernels' masks itself
+// when *pack comes back true, and nothing was launched)
+static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int rows, int cols, int alg, int T, int G, int k,
+                       double tau, int intensity_thr, uint8_t *d_out, float *d_thr, bool *pack = nullptr)
 {
-    CfarOsGateTab tab;
-    for (int x = 0; x < 256; ++x) {
-        int L = -1;
-        if (!(intensity_thr >= 0 && x <= intensity_thr))
-            for (int v = 0; v < 256; ++v) { // (double)x > tau * v is monotone in v: the largest v that still holds
-                const double t = tau * (double)(float)v; // cfar.cpp:92
-                if ((double)(float)x > t)
-                    L = v;
-                else
-                    break;
-            }
-        tab.L[x] = (int16_t)L;
-    }
-    tab.xc = 257;
-    for (int x = 255; x >= 0; --x)
-        if (tab.L[x] >= 0)
-            tab.xc = x;
-    tab.x_hi = 257;
-    tab.c0 = 1;
-    tab.m_le = 0;
-    if (pref) {
-        // the level: what a pixel of a third of full scale is compared with (L[80]; tuning cfar_os_pref_x moves it).  Any level is
-        // exact; this one keeps both kinds of candidates rare on sonar images
-        const int xs = std::min(255, std::max(tab.xc, ctx->tune.cfar_os_pref_x));
-        const int l0 = xs <= 255 ? tab.L[xs] : -1;
-        const bool ok = l0 >= 0 && l0 < 255 && 2 * T <= 127 && k + 1 <= 2 * T;
-        if (applied)
-            *applied = ok;
-        if (!ok)
-            return 0;
-        tab.c0 = l0 + 1;
-        tab.m_le = 2 * T - (k + 1);
-        for (int x = 255; x >= 0; --x)
-            if (tab.L[x] > l0)
-                tab.x_hi = x;
-    }
-    const int tiles_y = (rows + OSG_TR - 1) / OSG_TR, tiles_x = (cols + OSG_TC - 1) / OSG_TC;
-    const size_t smem = (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC + (size_t)OSG_TR * (OSG_TC / 8) + sizeof(unsigned short) * 4 * (OSG_LIST + 256) +
-                        (pref ? (size_t)8 * 32 * 2 * 4 : 0);
-    const bool v16 = cols % 16 == 0 && (((uintptr_t)d_img | (uintptr_t)d_mask) & 15) == 0;
-    const int pv = !pref ? 0 : T == 20 ? 2 : 1;
-    auto kernel = pv == 2 ? (v16 ? cfar_u8_os_gated<true, 2> : cfar_u8_os_gated<false, 2>)
-                  : pv == 1 ? (v16 ? cfar_u8_os_gated<true, 1> : cfar_u8_os_gated<false, 1>)
-                            : (v16 ? cfar_u8_os_gated<true, 0> : cfar_u8_os_gated<false, 0>);
-    SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((long long)n_frames * tiles_y * tiles_x)), dim3(256), smem, ctx->stream,
-                       d_img, d_mask, rows, cols, n_frames, T, G, k, tiles_y, tiles_x, tab);
-    return 0;
-}
+    CfarCall c;
+    c.rows = rows, c.cols = cols, c.n_frames = n_frames, c.alg = alg, c.T = T, c.G = G, c.k = k;
+    c.tau = tau, c.intensity_thr = intensity_thr;
+    c.img_align = cfar_align_of(d_img), c.out_align = cfar_align_of(d_out), c.thr_align = cfar_align_of(d_thr);
+    c.out = pack ? CFAR_OUT_BITS : d_thr ? CFAR_OUT_MASK_THR : CFAR_OUT_MASK;
+    c.variant = ctx->cfar_variant, c.tile_rows = ctx->cfar_tile_rows;
+    c.os_gated = ctx->tune.cfar_os_gated, c.os_gated_min = ctx->tune.cfar_os_gated_min;
+    c.os_pref = ctx->tune.cfar_os_pref, c.os_pref_x = ctx->tune.cfar_os_pref_x;
+    c.thr_arith_on = (d_thr && alg >= SFE_CFAR_CA && alg < SFE_CFAR_OS && T >= 1) ? thr_arith_checked(ctx, alg, T, tau) : 0;
 
-// d_bits != nullptr: the ring kernel writes the bit-packed detections there (BITS variant) and d_mask is not used;
-// the caller has checked that the ring kernel applies (ring_bits_applicable).
-static int cfar_u8_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames, int rows, int cols, int alg,
-                       int T, int G, int k, double tau, int intensity_thr, uint8_t *d_mask, float *d_thr,
-                       uint32_t *d_bits = nullptr)
-{
-    if (d_bits)
-        d_mask = reinterpret_cast<uint8_t *>(d_bits);
-    SFE_ARG(ctx, d_img && d_mask);
-    SFE_ARG(ctx, n_frames >= 0 && rows >= 0 && cols >= 0);
-    SFE_ARG(ctx, alg >= SFE_CFAR_CA && alg <= SFE_CFAR_OS);
-    SFE_ARG(ctx, T >= 1 && G >= 0);
-    if (alg == SFE_CFAR_OS)
-        SFE_ARG(ctx, k >= 0 && k < 2 * T);
-    if (n_frames == 0 || rows == 0 || cols == 0)
-        return 0;
-    CfarLut lut;
-    // register-ring kernel: instantiated for the shipped window (Ntc 40, Ngc 10 -> 20, 5) and for the other windows
-    // the reference's feature.yaml comments and tests go through: (32, 8), (20, 4), (16, 2)
-    const bool ring_window = (T == 20 && G == 5) || (T == 16 && G == 4) || (T == 10 && G == 2) || (T == 8 && G == 1);
-    const int ringR = 2 * (T + G) + 2;
-    // (with a threshold map: when it can be computed, cfar_thr_arith, and not next to the bit-stream output)
-    const CfarThrArith thr_ta = (d_thr && alg != SFE_CFAR_OS) ? thr_arith_checked(ctx, alg, T, tau) : CfarThrArith{0.0, 0.0, 1.0, 0};
-    bool ring = (alg != SFE_CFAR_OS) && (!d_thr || (thr_ta.on && !d_bits && reinterpret_cast<uintptr_t>(d_thr) % 16 == 0)) && (cols % 4 == 0) && cols >= 256 && rows >= ringR && (size_t)rows * cols < (1u << 30) &&
-                ctx->cfar_variant != 1 &&
-                ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_mask)) % 4 == 0) &&
-                ring_window && build_lut(alg, T, tau, intensity_thr, &lut);
-    if (ctx->cfar_variant >= 2 && !ring)
+    const CfarRoute r = cfar_route(c);
+    if (r.refusal)
+        return sfe_set_err(ctx, SFE_ERR_ARG, "bad argument: %s (%s:%d)", r.refusal, __FILE__, __LINE__);
+    if (r.ring_forced)
         return sfe_set_err(ctx, SFE_ERR_ARG, "ring CFAR kernel forced but not applicable to this call");
-    // every other window / the threshold maps: sliding-sum kernel (run-time window), then the OS histogram kernel;
-    // what is left (odd widths, unaligned buffers, windows beyond the 16-bit sums) takes the generic kernel
-    const bool aligned = (cols % 4 == 0) && (size_t)rows * cols < (1u << 30) &&
-                         ((reinterpret_cast<uintptr_t>(d_img) | reinterpret_cast<uintptr_t>(d_mask)) % 4 == 0) &&
-                         (!d_thr || reinterpret_cast<uintptr_t>(d_thr) % 16 == 0);
-    const bool slide = !ring && alg != SFE_CFAR_OS && aligned && ctx->cfar_variant != 1 &&
-                       build_lut(alg, T, tau, intensity_thr, &lut);
-    const bool os_hist = !ring && alg == SFE_CFAR_OS && ctx->cfar_variant != 1 && 2 * T <= 255 &&
-                         (size_t)rows * cols < (1u << 30);
-    if (ring) {
-        const int R = ringR;
-        int groups = ctx->cfar_tile_rows > 0 ? std::max(1, std::min(ctx->cfar_tile_rows / R, rows / R))
-                                             : std::max(1, std::min(104 / R, rows / R)); // ~104-row tiles (see default_groups)
-        if (T == 20)
-            groups = ctx->cfar_tile_rows > 0 ? groups : default_groups(ctx, rows, cols, n_frames, R);
-        const int tiles = (rows + groups * R - 1) / (groups * R);
-        const long long fb = (long long)rows * cols;
-        if (d_bits) {
-            const long long bb = (fb / 32 + 1) * 4; // bytes per frame of the bit stream: one pad word (sfe_extract.hip)
-            if (T == 20)
-                launch_ring<20, 5, 4, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, bb, lut);
-            else if (T == 16)
-                launch_ring<16, 4, 6, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, bb, lut);
-            else if (T == 10)
-                launch_ring<10, 2, 13, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, bb, lut);
-            else
-                launch_ring<8, 1, 5, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, bb, lut);
-        } else if (d_thr) {
-            if (T == 20)
-                launch_ring<20, 5, 4, false, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut, d_thr, thr_ta);
-            else if (T == 16)
-                launch_ring<16, 4, 6, false, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut, d_thr, thr_ta);
-            else if (T == 10)
-                launch_ring<10, 2, 13, false, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut, d_thr, thr_ta);
-            else
-                launch_ring<8, 1, 5, false, true>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut, d_thr, thr_ta);
-        } else if (T == 20 && ctx->cfar_variant == 3)
-            launch_ring<20, 5, 13, false>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut);
-        else if (T == 20)
-            launch_ring<20, 5, 4, false>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut);
-        else if (T == 16)
-            launch_ring<16, 4, 6, false>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut);
-        else if (T == 10)
-            launch_ring<10, 2, 13, false>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut);
-        else
-            launch_ring<8, 1, 5, false>(ctx, alg, d_img, d_mask, rows, cols, n_frames, groups, tiles, fb, lut);
-    } else if (d_bits) {
-        return sfe_set_err(ctx, SFE_ERR_ARG, "internal: bit-packed CFAR output asked of a non-ring window");
-    } else if (slide) {
+    if (pack)
+        *pack = r.kernel == CFAR_PACK;
+    const dim3 grid((unsigned)r.workgroups);
+    switch (r.kernel) {
+    case CFAR_NONE:
+    case CFAR_PACK:
+        return 0;
+    case CFAR_RING: {
+        const int full_last = 0; // (1: the last tile as long as the others, rounds 1-4)
+        hipLaunchKernelGGL(ring_kernels[r.instance][c.out][alg], grid, dim3(256), 0, ctx->stream, d_img, d_out, rows, cols,
+                           n_frames, r.groups, r.tiles, r.chunks, r.out_frame_bytes, r.lut, d_thr, r.ta, full_last);
+        break;
+    }
+    case CFAR_SLIDE_LDS:
+    case CFAR_SLIDE: {
         const float *d_tab = nullptr;
-        if (d_thr) { // thr = (float)(tau * s / T) per integer window sum s, with the reference's double expression
-            const int smax = (alg == SFE_CFAR_CA) ? 255 * 2 * T : 255 * T;
-            float *tab = (float *)sfe_scratch(ctx, 37, sizeof(float) * (size_t)(smax + 1));
-            if (!tab)
-                return SFE_ERR_HIP;
-            if (!(ctx->thr_tab_alg == alg && ctx->thr_tab_T == T && ctx->thr_tab_tau == tau && ctx->thr_tab_ptr == tab)) {
-                float *h = (float *)sfe_pinned_begin(ctx, sizeof(float) * (size_t)(smax + 1));
-                if (!h)
-                    return SFE_ERR_HIP;
-                for (int sv = 0; sv <= smax; ++sv) {
-                    const float sf = (float)sv;
-                    h[sv] = (float)((alg == SFE_CFAR_CA) ? tau * (double)sf / (2.0 * T) : tau * (double)sf / T);
-                }
-                SFE_HIP(ctx, hipMemcpyAsync(tab, h, sizeof(float) * (size_t)(smax + 1), hipMemcpyHostToDevice, ctx->stream));
-                if (int rc = sfe_pinned_end(ctx, ctx->stream))
-                    return rc;
-                ctx->thr_tab_alg = alg;
-                ctx->thr_tab_T = T;
-                ctx->thr_tab_tau = tau;
-                ctx->thr_tab_ptr = tab;
-            }
-            d_tab = tab;
-        }
-        // long tiles: a tile starts with 2T loads per lane to build its first windows
-        const int tile_rows = std::min(rows, std::max(128, 8 * T));
-        const int tiles = (rows + tile_rows - 1) / tile_rows;
-        const int chunks = std::max(1, ((cols >> 2) + 63) / 64);
-        const long long bpf = ((long long)tiles * chunks + 3) / 4;
-        const unsigned blocks = (unsigned)((((long long)n_frames + 7) / 8) * 8 * bpf);
-        // window rows staged in LDS (R KiB per workgroup) unless the window is too tall for it
-        const int R = 2 * (T + G) + 2;
-        const size_t ring_bytes = (size_t)R * 1024;
-        // beyond two workgroups per CU (R > 80 rows = 80 KiB) the ring starves the CU of waves and re-reading the four
-        // rows through the caches is faster (measured (80, 20): 15 % of HBM with the LDS ring, 25 % without)
-        const bool lds_ring = ring_bytes <= 80 * 1024;
-#define SLIDE_LAUNCH(A, THRB)                                                                                          \
-    do {                                                                                                               \
-        if (lds_ring) {                                                                                                \
-            SFE_HIP(ctx, hipFuncSetAttribute((const void *)cfar_u8_slide_lds<A, THRB>,                                 \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ring_bytes));            \
-            hipLaunchKernelGGL((cfar_u8_slide_lds<A, THRB>), dim3(blocks), dim3(256), ring_bytes, ctx->stream, d_img,  \
-                               d_mask, d_thr, d_tab, rows, cols, n_frames, T, G, tile_rows, tiles, chunks, lut, thr_ta); \
-        } else {                                                                                                       \
-            hipLaunchKernelGGL((cfar_u8_slide<A, THRB>), dim3(blocks), dim3(256), 0, ctx->stream, d_img, d_mask,       \
-                               d_thr, d_tab, rows, cols, n_frames, T, G, tile_rows, tiles, chunks, lut, thr_ta);       \
-        }                                                                                                              \
-    } while (0)
-        if (alg == SFE_CFAR_SOCA) {
-            if (d_thr)
-                SLIDE_LAUNCH(SFE_CFAR_SOCA, true);
-            else
-                SLIDE_LAUNCH(SFE_CFAR_SOCA, false);
-        } else if (alg == SFE_CFAR_GOCA) {
-            if (d_thr)
-                SLIDE_LAUNCH(SFE_CFAR_GOCA, true);
-            else
-                SLIDE_LAUNCH(SFE_CFAR_GOCA, false);
-        } else {
-            if (d_thr)
-                SLIDE_LAUNCH(SFE_CFAR_CA, true);
-            else
-                SLIDE_LAUNCH(SFE_CFAR_CA, false);
-        }
-#undef SLIDE_LAUNCH
-    } else if (os_hist && !d_thr && aligned && (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC <= 96 * 1024 &&
-               ctx->tune.cfar_os_gated && intensity_thr >= ctx->tune.cfar_os_gated_min) {
-        // OS behind a gate: only the pixels above it are looked at (cfar_u8_os_gated).  It pays when the gate removes most
-        // pixels -- measured on 512 sonar frames, (Ntc 40, Ngc 10, k 10): gate 65 0.65 ms against the histogram kernel's
-        // 1.65 ms; gate 20 (four pixels in ten pass) 1.84 against 1.65 -- so a low gate keeps the histogram kernel
-        // (feature.yaml ships 65; tuning cfar_os_gated_min moves the limit).
-        if (int rc = launch_os_gated(ctx, d_img, n_frames, rows, cols, T, G, k, tau, intensity_thr, d_mask))
-            return rc;
-    } else if (os_hist) {
-        // no gate, or a low one: the pre-filtered candidate kernel (round 6) where it applies, else the sliding histogram
-        bool done = false;
-        if (!d_thr && aligned && (size_t)(OSG_TR + 2 * (T + G)) * OSG_TC <= 96 * 1024 && ctx->tune.cfar_os_pref)
-            if (int rc = launch_os_gated(ctx, d_img, n_frames, rows, cols, T, G, k, tau, intensity_thr, d_mask, true, &done))
+        if (d_thr)
+            if (int rc = slide_thr_table(ctx, alg, T, tau, &d_tab))
                 return rc;
-        if (!done)
-        if (int rc = launch_os_hist(ctx, d_img, n_frames, rows, cols, T, G, k, tau, intensity_thr, d_mask, d_thr))
-            return rc;
-    } else {
-        const int tr = std::min(rows, 64);
-        const int tiles = (rows + tr - 1) / tr;
-        const long long threads = (long long)n_frames * tiles * cols;
-        const unsigned blocks = (unsigned)((threads + 255) / 256);
-        hipLaunchKernelGGL(cfar_u8_generic, dim3(blocks), dim3(256), 0, ctx->stream, d_img, d_mask, d_thr, rows,
-                           cols, n_frames, tr, tiles, alg, T, G, k, tau, intensity_thr);
+        const SlideKernel kernel = slide_kernels[r.kernel == CFAR_SLIDE_LDS][d_thr != nullptr][alg];
+        if (r.lds_bytes)
+            SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_bytes));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), (size_t)r.lds_bytes, ctx->stream, d_img, d_out, d_thr, d_tab, rows, cols,
+                           n_frames, T, G, r.tile_rows, r.tiles, r.chunks, r.lut, r.ta);
+        break;
+    }
+    case CFAR_OS_GATED:
+    case CFAR_OS_PREF: {
+        const OsGatedKernel kernel = os_gated_kernels[r.v16][r.instance];
+        SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds_bytes));
+        hipLaunchKernelGGL(kernel, grid, dim3(256), (size_t)r.lds_bytes, ctx->stream, d_img, d_out, rows, cols, n_frames, T, G, k,
+                           r.tiles, r.chunks, r.gate_tab);
+        break;
+    }
+    case CFAR_OS_HIST:
+        hipLaunchKernelGGL(cfar_u8_os, grid, dim3(64), 0, ctx->stream, d_img, d_out, d_thr, rows, cols, n_frames, T, G, k,
+                           r.tile_rows, r.tiles, r.chunks, r.os_tab);
+        break;
+    case CFAR_GENERIC:
+        hipLaunchKernelGGL(cfar_u8_generic, grid, dim3(256), 0, ctx->stream, d_img, d_out, d_thr, rows, cols, n_frames,
+                           r.tile_rows, r.tiles, alg, T, G, k, tau, intensity_thr);
+        break;
     }
     SFE_LAUNCH_CHECK(ctx);
     return 0;
 }
 
-// the call the BITS ring kernel takes: a ring window, whole 32-bit words per row, no threshold map
-static bool ring_bits_applicable(const sfe_ctx *ctx, const uint8_t *d_img, int rows, int cols, int alg, int T, int G)
+// upload one image, run `launch` on it, download the mask and (if asked) the threshold map, wait
+template <typename Pixel, typename Launch>
+static int cfar_host_call(sfe_ctx *ctx, const Pixel *img, size_t n, uint8_t *mask_out, float *thr_out, Launch launch)
 {
-    const bool ring_window = (T == 20 && G == 5) || (T == 16 && G == 4) || (T == 10 && G == 2) || (T == 8 && G == 1);
-    return ring_window && alg != SFE_CFAR_OS && cols % 32 == 0 && cols >= 256 && rows >= 2 * (T + G) + 2 &&
-           (size_t)rows * cols < (1u << 30) && ctx->cfar_variant == 0 && reinterpret_cast<uintptr_t>(d_img) % 4 == 0;
+    Pixel *d_img = (Pixel *)sfe_scratch(ctx, 0, n * sizeof(Pixel));
+    uint8_t *d_mask = (uint8_t *)sfe_scratch(ctx, 1, n);
+    float *d_thr = thr_out ? (float *)sfe_scratch(ctx, 2, n * sizeof(float)) : nullptr;
+    if (!d_img || !d_mask || (thr_out && !d_thr))
+        return SFE_ERR_HIP;
+    SFE_HIP(ctx, hipMemcpyAsync(d_img, img, n * sizeof(Pixel), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = launch(d_img, d_mask, d_thr))
+        return rc;
+    SFE_HIP(ctx, hipMemcpyAsync(mask_out, d_mask, n, hipMemcpyDeviceToHost, ctx->stream));
+    if (thr_out)
+        SFE_HIP(ctx, hipMemcpyAsync(thr_out, d_thr, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 extern "C" {
@@ -1325,12 +1091,14 @@ int sfe_cfar_u8_bits_batch_dev(sfe_ctx *ctx, const uint8_t *d_img, int n_frames,
     const long long px = (long long)rows * cols, wpf = (px + 31) / 32 + 1;
     if (n_frames == 0 || px == 0)
         return 0;
-    CfarLut probe;
-    if (ring_bits_applicable(ctx, d_img, rows, cols, alg, train_hs, guard_hs) && train_hs >= 1 &&
-        build_lut(alg, train_hs, tau, intensity_thr, &probe))
-        return cfar_u8_dev(ctx, d_img, n_frames, rows, cols, alg, train_hs, guard_hs, k, tau, intensity_thr, nullptr,
-                           nullptr, d_bits);
-    // every other window: the byte kernels into a scratch mask, a bounded number of frames at a time, then packed
+    // the BITS ring kernel where it applies
+    bool pack = false;
+    if (int rc = cfar_u8_dev(ctx, d_img, n_frames, rows, cols, alg, train_hs, guard_hs, k, tau, intensity_thr,
+                             reinterpret_cast<uint8_t *>(d_bits), nullptr, &pack))
+        return rc;
+    if (!pack)
+        return 0;
+    // every other call: the byte kernels into a scratch mask, a bounded number of frames at a time, then packed
     const int chunk = (int)std::max<long long>(1, std::min<long long>(n_frames, (256ll << 20) / px));
     uint8_t *d_tmp = (uint8_t *)sfe_scratch(ctx, 41, (size_t)chunk * px);
     if (!d_tmp)
@@ -1375,20 +1143,9 @@ int sfe_cfar_u8(sfe_ctx *ctx, const uint8_t *img, int rows, int cols, int alg, i
     const size_t n = (size_t)rows * cols;
     if (n == 0)
         return 0;
-    uint8_t *d_img = (uint8_t *)sfe_scratch(ctx, 0, n);
-    uint8_t *d_mask = (uint8_t *)sfe_scratch(ctx, 1, n);
-    float *d_thr = thr_out ? (float *)sfe_scratch(ctx, 2, n * sizeof(float)) : nullptr;
-    if (!d_img || !d_mask || (thr_out && !d_thr))
-        return SFE_ERR_HIP;
-    SFE_HIP(ctx, hipMemcpyAsync(d_img, img, n, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = cfar_u8_dev(ctx, d_img, 1, rows, cols, alg, train_hs, guard_hs, k, tau, intensity_thr, d_mask,
-                             d_thr))
-        return rc;
-    SFE_HIP(ctx, hipMemcpyAsync(mask_out, d_mask, n, hipMemcpyDeviceToHost, ctx->stream));
-    if (thr_out)
-        SFE_HIP(ctx, hipMemcpyAsync(thr_out, d_thr, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return cfar_host_call(ctx, img, n, mask_out, thr_out, [&](const uint8_t *d_img, uint8_t *d_mask, float *d_thr) {
+        return cfar_u8_dev(ctx, d_img, 1, rows, cols, alg, train_hs, guard_hs, k, tau, intensity_thr, d_mask, d_thr);
+    });
 }
 
 int sfe_cfar_f32(sfe_ctx *ctx, const float *img, int rows, int cols, int alg, int train_hs, int guard_hs, int k,
@@ -1404,21 +1161,12 @@ int sfe_cfar_f32(sfe_ctx *ctx, const float *img, int rows, int cols, int alg, in
     const size_t n = (size_t)rows * cols;
     if (n == 0)
         return 0;
-    float *d_img = (float *)sfe_scratch(ctx, 0, n * sizeof(float));
-    uint8_t *d_mask = (uint8_t *)sfe_scratch(ctx, 1, n);
-    float *d_thr = thr_out ? (float *)sfe_scratch(ctx, 2, n * sizeof(float)) : nullptr;
-    if (!d_img || !d_mask || (thr_out && !d_thr))
-        return SFE_ERR_HIP;
-    SFE_HIP(ctx, hipMemcpyAsync(d_img, img, n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(cfar_f32_naive, dim3(blocks), dim3(256), 0, ctx->stream, d_img, d_mask, d_thr, rows, cols,
-                       alg, train_hs, guard_hs, k, tau);
-    SFE_LAUNCH_CHECK(ctx);
-    SFE_HIP(ctx, hipMemcpyAsync(mask_out, d_mask, n, hipMemcpyDeviceToHost, ctx->stream));
-    if (thr_out)
-        SFE_HIP(ctx, hipMemcpyAsync(thr_out, d_thr, n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return 0;
+    return cfar_host_call(ctx, img, n, mask_out, thr_out, [&](const float *d_img, uint8_t *d_mask, float *d_thr) {
+        hipLaunchKernelGGL(cfar_f32_naive, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_img, d_mask, d_thr,
+                           rows, cols, alg, train_hs, guard_hs, k, tau);
+        SFE_LAUNCH_CHECK(ctx);
+        return 0;
+    });
 }
 
 } // extern "C"

@@ -48,6 +48,20 @@ struct sfe_tuning {
     int icp_debug = 0;          // watchdogs of the sweep kernel reported on stderr (synchronises every call)
 };
 
+// CFAR (sfe_cfar.hip): what the last call with a threshold map checked and uploaded, so that a stream of equal calls does
+// neither again
+struct SfeCfarCache {
+    struct Key {
+        int alg = -1, T = -1;
+        double tau = 0.0;
+        bool is(int a, int t, double u) const { return alg == a && T == t && tau == u; }
+    };
+    Key arith;                     // cfar_thr_arith checked against the reference expression for these: arith_on
+    int arith_on = 0;
+    Key tab;                       // float threshold table of the sliding-sum kernel on the device at tab_ptr (scratch slot 37)
+    const void *tab_ptr = nullptr;
+};
+
 struct sfe_ctx {
     int device = -1;
     hipStream_t stream = nullptr;
@@ -85,12 +99,7 @@ struct sfe_ctx {
     void *bm_clean_ptr = nullptr; // sfe_extract.hip (CleanBitmap): the canvas bitmap scratch is known to be zero up to bm_clean_bytes
     size_t bm_clean_bytes = 0;
     Pin pin_io[4]; // grow-only pinned buffers of the synchronous single-item entry points (no events: the call syncs)
-    // float threshold table of the sliding-sum CFAR kernel currently on the device (scratch slot 37)
-    int thr_tab_alg = -1, thr_tab_T = -1;
-    double thr_tab_tau = 0.0;
-    const void *thr_tab_ptr = nullptr;
-    int tha_alg = -1, tha_T = -1, tha_on = 0; // cfar_thr_arith checked against the reference expression for these
-    double tha_tau = 0.0;
+    SfeCfarCache cfar_cache;
     int cfar_tile_rows = 0;
     int cfar_variant = 0;
     int icp_variant = 0;
