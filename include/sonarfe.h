@@ -663,7 +663,7 @@ int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_
  *     sfe_map_shape -> {rows, cols, rows grown on top, columns grown on the left}.
  *   sfe_map_frames: a fresh grid, the listed slots added in list order.  sfe_map_render: rows r0..r1 x cols c0..c1 of a grid
  *     -> int8(clip(100 expit(v), 0, 100)), resized INTER_NEAREST to out_h x out_w with source index floor(i * inv) when
- *     resize != 0.
+ *     resize != 0.  sfe_map_render2: sfe_mapset_render2, below, for one image of this map.
  *   sfe_map_hit_table / sfe_map_measure_store / sfe_map_measure_store_undecided / sfe_map_measure_store_finish: the store
  *     feed of one map: the sfe_mapset_* calls of the same names, below, over one map.  n keyframes of the map per call, each
  *     slot at most once.  A slot that holds an image of another geometry, an unknown geometry or a negative slot is refused
@@ -701,6 +701,9 @@ int sfe_map_read_grid(sfe_map *m, int which, float *out, long long cap);
 int sfe_map_frames(sfe_map *m, int n, const int32_t *slots);
 int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int out_h, int out_w, double inv, int resize,
                    int8_t *occ_out);
+int sfe_map_render2(sfe_map *m, int n_slots, const int32_t *slots, int r0, int r1, int c0, int c1, const double *xy, int n_pts,
+                    int filter, double radius, int min_points, int dilate_hs, double y0, double x0, double resolution,
+                    int out_h, int out_w, double inv, int resize, int8_t *occ_out);
 
 /* ---- S occupancy maps that advance together (sonar_slam_amd/mapping.py: MapBatch; chained.SessionBatch's maps).  One
  * sfe_mapset owns the state of n_maps maps, each exactly what an sfe_map of its own holds after the same calls: the
@@ -760,6 +763,17 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
  *   sfe_mapset_render: n images in one launch and one read-back: job b renders box4[4 b ..] = {r0, r1, c0, c1} of map maps[b]'s
  *     grid (which[b] = 1: its frames grid) to out_hw[2 b ..] = {out_h, out_w} at occ_out + out_off[b]; `total` bytes in all.
  *     inv / resize as sfe_map_render.
+ *   sfe_mapset_render2: the point-projection map (method 2: get_occupancy_grid2, mapping.py:357-439), n images in one call
+ *     and one read-back; int8 cells of -1 (unknown), 0 (free) and 100 (occupied).  Job b works on the known region box4[4 b ..]
+ *     = {r0, r1, c0, c1} of map maps[b] -- the caller's: the union of the boxes of the listed keyframes -- whose corner lies at
+ *     origin2[2 b ..] = {y0, x0} metres: every cell of the current lists of slots[slot_off[b] .. slot_off[b + 1]) is free;
+ *     its points are xy[2 pt_off[b] .. 2 pt_off[b + 1]) (float64 x, y; all jobs in one upload).  With filter[b] != 0 the
+ *     points are rounded to float32 and go through sfe_remove_outlier's decision with radius[b] / min_points[b], and the kept
+ *     float32 points are projected; otherwise the doubles are.  Projection: r = rint((y - y0) / resolution[b]), c likewise,
+ *     in double; a point outside the region is dropped.  Every region cell under the element
+ *     getStructuringElement(MORPH_ELLIPSE, (2 dilate_hs[b] + 1,) * 2) of a projected point becomes 100, above 0.  The region
+ *     is then resized as in sfe_mapset_render (out_hw / inv / resize / out_off / total).  A region that is empty, leaves the
+ *     map or lists a slot without cells is refused with SFE_ERR_ARG; at most 65535 jobs and 65535 listed slots per call.
  * sfe_remove_outlier_many: sfe_remove_outlier's decision for n_clouds clouds in one launch: cloud c = pts[off[c] .. off[c + 1])
  *   (points), keep_out[i] = 1 for the points that stay.  One synchronisation. */
 typedef struct sfe_mapset sfe_mapset;
@@ -797,6 +811,11 @@ int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int
 int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *which, const int32_t *box4,
                       const int32_t *out_hw, const double *inv, const int32_t *resize, const long long *out_off,
                       int8_t *occ_out, long long total);
+int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot_off, const int32_t *slots,
+                       const int32_t *box4, const int32_t *pt_off, const double *xy, const int32_t *filter,
+                       const double *radius, const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
+                       const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
+                       const long long *out_off, int8_t *occ_out, long long total);
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,
                             uint8_t *keep_out);
 

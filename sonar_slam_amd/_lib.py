@@ -284,6 +284,9 @@ SIGNATURES = {
     "sfe_map_frames": (C.c_int, [_vp, C.c_int, _i32p]),
     "sfe_map_render": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
                                  C.POINTER(C.c_int8)]),
+    "sfe_map_render2": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, C.c_double,
+                                  C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
+                                  C.POINTER(C.c_int8)]),
     "sfe_mapset_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "sfe_mapset_destroy": (None, [_vp]),
     "sfe_mapset_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
@@ -310,6 +313,8 @@ SIGNATURES = {
     "sfe_mapset_frames": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p]),
     "sfe_mapset_render": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong),
                                     C.POINTER(C.c_int8), C.c_longlong]),
+    "sfe_mapset_render2": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, _f64p,
+                                     _f64p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_int8), C.c_longlong]),
     "sfe_remove_outlier_many": (C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_double, C.c_int, _u8p]),
 }
 

@@ -310,8 +310,8 @@ __global__ __launch_bounds__(COST_MANY_THREADS) void matching_cost_many_kernel(c
     }
 }
 
-// cv2.getStructuringElement(MORPH_ELLIPSE, (2h+1, 2h+1), (h, h)) row spans
-static std::vector<int32_t> cost_ellipse_spans(int dilate_hs)
+// cv2.getStructuringElement(MORPH_ELLIPSE, (2h+1, 2h+1), (h, h)) row spans (sfe_internal.h: sfe_map.hip stamps them too)
+std::vector<int32_t> cost_ellipse_spans(int dilate_hs)
 {
     const int size = 2 * dilate_hs + 1;
     std::vector<int32_t> span(2 * (size_t)size);

@@ -215,6 +215,10 @@ struct SfeStoreView {
 };
 int sfe_store_view(sfe_cloud_store *s, SfeStoreView *v);
 
+// sfe_cost.hip: cv2.getStructuringElement(MORPH_ELLIPSE, (2h+1, 2h+1)) as row spans: row i of the element covers columns
+// [span[2 i], span[2 i + 1])
+std::vector<int32_t> cost_ellipse_spans(int dilate_hs);
+
 // sfe_downsample.hip: pcl.downsample with indices on a device-resident cloud of any size (rank sort in global memory)
 struct SfeDsHeader {
     float cx, cy, radius;

@@ -8,6 +8,7 @@
 // l float32, ascending r * cols + c).  Cell lists are double-buffered: a refit writes the new list next to the old one,
 // subtracts the old, adds the new, and flips.  Growth pads a grid and bumps two counters; a list keeps the counters it was
 // written at, and its cells are shifted by the difference when read.  An sfe_map is a set of one map (the end of this file).
+// Method 2 (get_occupancy_grid2: point projection + dilation) reads those cell lists and writes no state: sfe_mapset_render2.
 //
 // Slot storage, the one thing chosen at creation.  A slot record (SetSlot) carries its own device pointers:
 //   logodds  float32 [px]
@@ -134,8 +135,9 @@ struct sfe_mapset {
     int32_t *d_counts = nullptr; // [map * max_kf + slot][2], room for counts_cap slots
     int counts_cap = 0;
     // scratch.  0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's job tables, hit buffer,
-    // keep flags, undecided lists and counters, hit tables
-    MapBuf buf[11];
+    // keep flags, undecided lists and counters, hit tables; 11 .. 16: method 2's job tables, list table, spans, points,
+    // float32 points + keep flags, work images
+    MapBuf buf[17];
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
     long long apply_launches = 0; // launches of mapset_apply_kernel so far
@@ -483,6 +485,133 @@ __global__ __launch_bounds__(256) void radius_count_many_kernel(const float2 *__
     __shared__ float2 s_p[2048];
     const int base = off[blockIdx.y];
     radius_count_cloud(pts + base, off[blockIdx.y + 1] - base, r2, min_points, keep + base, s_p);
+}
+
+// --- method 2 (get_occupancy_grid2, mapping.py:357-439) over job tables: one job = one published image --------------------
+// Its work image is the known region, h x w int8, at work + work_off: -1 everywhere, 0 where a listed keyframe has a cell,
+// 100 under the ellipse element of every kept point that projects into the region; then INTER_NEAREST into the packed output.
+// The launches follow each other on the context's stream, which keeps 100 above 0; (b) and (d) store a constant, so equal
+// stores from several threads need no ordering.
+struct Render2Job {
+    int32_t h, w, oh, ow, resize;
+    int32_t pt_off, n_pts; // its points in the call's point table
+    int32_t filter;        // the radius filter runs: the projection then reads the float32-rounded point
+    int32_t min_points;
+    float r2;
+    int32_t hs, span_off;  // half size of the element; its row spans in the call's span table
+    double y0, x0, res;    // the region's corner in metres, the map's resolution
+    double inv;
+    int64_t work_off, out_off;
+};
+
+// the current cell list of one listed keyframe of a job
+struct MarkJob {
+    int8_t *img;
+    int32_t h, w;
+    const uint16_t *r, *c;
+    const int32_t *n;
+    int32_t dr, dc; // growth since the list was written, less the region's corner
+    int32_t n_px;   // upper bound of *n
+};
+
+// (a) every work image of the call starts unknown: they lie back to back, n16 16-byte words in all
+__global__ __launch_bounds__(MAP_THREADS) void map2_fill_kernel(uint4 *work, int64_t n16)
+{
+    const uint4 unknown = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (int64_t)gridDim.x * blockDim.x)
+        work[i] = unknown;
+}
+
+// (b) occ[keyframe.r - rmin, keyframe.c - cmin] = 0: list blockIdx.y, shifted as mapset_apply_kernel shifts it
+__global__ __launch_bounds__(MAP_THREADS) void map2_mark_kernel(const MarkJob *jobs)
+{
+    const MarkJob j = jobs[blockIdx.y];
+    const int n = min(*j.n, j.n_px);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int rr = (int)j.r[i] + j.dr, cc = (int)j.c[i] + j.dc;
+        if (rr < 0 || rr >= j.h || cc < 0 || cc >= j.w)
+            continue; // cannot happen: the region is the union of the listed keyframes' boxes
+        j.img[(int64_t)rr * j.w + cc] = 0;
+    }
+}
+
+// (c) the points as pybind hands them to pcl.remove_outlier (float32), every point kept until the filter says otherwise
+__global__ __launch_bounds__(MAP_THREADS) void map2_cast_kernel(const double2 *__restrict__ xy, int n, float2 *__restrict__ xy32,
+                                                                uint8_t *__restrict__ keep)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const double2 p = xy[i];
+    xy32[i] = make_float2((float)p.x, (float)p.y);
+    keep[i] = 1;
+}
+
+// ... and the filter's decision for the jobs that run it: job blockIdx.y, block blockIdx.x of its cloud's row
+__global__ __launch_bounds__(256) void map2_radius_count_kernel(const Render2Job *__restrict__ jobs, const float2 *__restrict__ xy32,
+                                                                uint8_t *__restrict__ keep)
+{
+    __shared__ float2 s_p[2048];
+    const int32_t filter = jobs[blockIdx.y].filter, off = jobs[blockIdx.y].pt_off, n = jobs[blockIdx.y].n_pts;
+    if (!filter)
+        return; // the whole block at once
+    radius_count_cloud(xy32 + off, n, jobs[blockIdx.y].r2, jobs[blockIdx.y].min_points, keep + off, s_p);
+}
+
+// (d) r = int32(round((y - y0) / resolution)), c likewise, in double (y0 is a numpy float64 scalar, so numpy widens a
+// float32 cloud): one IEEE subtract, one divide, round half to even.  A point outside the region is dropped; one inside is
+// dilated by the element, clipped at the region's border (cv2.dilate's constant border).  One thread per (point, element
+// row): it stores the row's span.
+__global__ __launch_bounds__(MAP_THREADS) void map2_stamp_kernel(const Render2Job *__restrict__ jobs,
+                                                                 const double2 *__restrict__ xy, const float2 *__restrict__ xy32,
+                                                                 const uint8_t *__restrict__ keep,
+                                                                 const int32_t *__restrict__ spans, int8_t *work)
+{
+    const Render2Job j = jobs[blockIdx.y];
+    const int size = 2 * j.hs + 1;
+    const int64_t n = (int64_t)j.n_pts * size;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
+        const int p = (int)(t / size), i = (int)(t - (int64_t)p * size);
+        const int q = j.pt_off + p;
+        if (!keep[q])
+            continue;
+        double x, y;
+        if (j.filter) {
+            const float2 f = xy32[q];
+            x = (double)f.x, y = (double)f.y;
+        } else {
+            const double2 d = xy[q];
+            x = d.x, y = d.y;
+        }
+        const double fr = rint(__ddiv_rn(__dsub_rn(y, j.y0), j.res)), fc = rint(__ddiv_rn(__dsub_rn(x, j.x0), j.res));
+        if (!(fr >= 0.0 && fr < (double)j.h && fc >= 0.0 && fc < (double)j.w))
+            continue; // (a NaN too)
+        const int rr = (int)fr + i - j.hs;
+        if (rr < 0 || rr >= j.h)
+            continue;
+        const int left = (int)fc - j.hs;
+        const int c0 = max(left + spans[j.span_off + 2 * i], 0), c1 = min(left + spans[j.span_off + 2 * i + 1], j.w);
+        int8_t *row = work + j.work_off + (int64_t)rr * j.w;
+        for (int cc = c0; cc < c1; ++cc)
+            row[cc] = 100;
+    }
+}
+
+// (e) cv2.resize(occ, None, None, ratio, ratio, INTER_NEAREST), or the copy: mapset_render_kernel's index rule
+__global__ __launch_bounds__(MAP_THREADS) void map2_resize_kernel(const Render2Job *__restrict__ jobs,
+                                                                  const int8_t *__restrict__ work, int8_t *__restrict__ out)
+{
+    const Render2Job j = jobs[blockIdx.y];
+    const int64_t n = (int64_t)j.oh * j.ow;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int y = (int)(i / j.ow), x = (int)(i - (int64_t)y * j.ow);
+        int sy = y, sx = x;
+        if (j.resize) {
+            sy = min((int)floor(__dmul_rn((double)y, j.inv)), j.h - 1);
+            sx = min((int)floor(__dmul_rn((double)x, j.inv)), j.w - 1);
+        }
+        out[j.out_off + i] = work[j.work_off + (int64_t)sy * j.w + sx];
+    }
 }
 
 // --- the store feed: a keyframe's hits straight from its cloud in a cloud store (mapping.py: MapBatch.add_keyframes_store) ----
@@ -1398,6 +1527,132 @@ int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t 
     return 0;
 }
 
+// get_occupancy_grid2 for n images in one call and one read-back.  Job b: map maps[b]; the free cells are the current lists of
+// slots[slot_off[b] .. slot_off[b + 1]); the known region is box4[4 b ..] = {r0, r1, c0, c1} (the union of those lists' boxes:
+// the caller's), its corner origin2[2 b ..] = {y0, x0} metres; its points xy[2 pt_off[b] .. 2 pt_off[b + 1]) (float64 x, y).
+int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot_off, const int32_t *slots,
+                       const int32_t *box4, const int32_t *pt_off, const double *xy, const int32_t *filter,
+                       const double *radius, const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
+                       const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
+                       const long long *out_off, int8_t *occ_out, long long total)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && n <= 65535 && total >= 0 && (total == 0 || occ_out));
+    SFE_ARG(ctx, n == 0 || (maps && slot_off && box4 && pt_off && filter && radius && min_points && dilate_hs && origin2 &&
+                            resolution && out_hw && inv && resize && out_off));
+    if (n == 0)
+        return 0;
+    SFE_ARG(ctx, slot_off[0] == 0 && pt_off[0] == 0);
+    std::vector<Render2Job> jobs;
+    std::vector<MarkJob> marks;
+    std::vector<int64_t> mark_work; // the work image of each list, as an offset until the scratch is there
+    std::vector<int32_t> spans;
+    std::vector<std::pair<int, int>> span_at; // (half size, offset) of the elements already in `spans`
+    int64_t work = 0, max_out = 0, max_stamp = 0;
+    int max_px = 1, max_pts = 0;
+    bool any_filter = false;
+    for (int b = 0; b < n; ++b) {
+        SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps);
+        SFE_ARG(ctx, slot_off[b + 1] >= slot_off[b] && (slot_off[b + 1] == slot_off[b] || slots));
+        SFE_ARG(ctx, pt_off[b + 1] >= pt_off[b] && (pt_off[b + 1] == pt_off[b] || xy));
+        const SetMap &m = ms->maps[maps[b]];
+        const int r0 = box4[4 * b], r1 = box4[4 * b + 1], c0 = box4[4 * b + 2], c1 = box4[4 * b + 3];
+        Render2Job j;
+        j.h = r1 - r0 + 1, j.w = c1 - c0 + 1, j.oh = out_hw[2 * b], j.ow = out_hw[2 * b + 1];
+        j.resize = resize[b], j.inv = inv[b], j.out_off = out_off[b];
+        SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && j.h > 0 && j.w > 0 && r1 < m.rows && c1 < m.cols);
+        SFE_ARG(ctx, j.oh >= 0 && j.ow >= 0 && (j.resize ? j.inv > 0 : (j.oh == j.h && j.ow == j.w)));
+        SFE_ARG(ctx, j.out_off >= 0 && j.out_off + (int64_t)j.oh * j.ow <= total);
+        j.pt_off = pt_off[b], j.n_pts = pt_off[b + 1] - pt_off[b];
+        j.filter = filter[b] != 0, j.min_points = min_points[b], j.r2 = (float)(radius[b] * radius[b]);
+        j.hs = dilate_hs[b];
+        SFE_ARG(ctx, j.hs >= 0 && j.hs <= 4096 && resolution[b] > 0);
+        j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1], j.res = resolution[b];
+        j.span_off = -1;
+        for (const auto &e : span_at)
+            if (e.first == j.hs)
+                j.span_off = e.second;
+        if (j.span_off < 0) {
+            j.span_off = (int)spans.size();
+            span_at.push_back({j.hs, j.span_off});
+            const std::vector<int32_t> sp = cost_ellipse_spans(j.hs);
+            spans.insert(spans.end(), sp.begin(), sp.end());
+        }
+        j.work_off = work;
+        work += (int64_t)j.h * j.w;
+        for (int i = slot_off[b]; i < slot_off[b + 1]; ++i) {
+            if (int rc = set_slot_used(ms, maps[b], slots[i]))
+                return rc;
+            const SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[i])];
+            SFE_ARG(ctx, s.has_cells);
+            MarkJob k;
+            k.img = nullptr, k.h = j.h, k.w = j.w;
+            k.r = s.d_r[s.cur], k.c = s.d_c[s.cur], k.n = s.d_n + s.cur;
+            k.dr = m.grow_r - s.base_r - r0, k.dc = m.grow_c - s.base_c - c0;
+            k.n_px = ms->geoms[s.geom].img_rows * ms->geoms[s.geom].img_cols;
+            max_px = max(max_px, k.n_px);
+            marks.push_back(k);
+            mark_work.push_back(j.work_off);
+        }
+        max_out = max(max_out, (int64_t)j.oh * j.ow);
+        max_pts = max(max_pts, j.n_pts);
+        max_stamp = max(max_stamp, (int64_t)j.n_pts * (2 * j.hs + 1));
+        any_filter = any_filter || (j.filter && j.n_pts > 0);
+        jobs.push_back(j);
+    }
+    SFE_ARG(ctx, marks.size() <= 65535 && work < (1LL << 40));
+    const int n_pts = pt_off[n];
+    const int64_t n16 = (work + 15) / 16;
+    int8_t *d_work = (int8_t *)buf_get(ctx, ms->buf[16], (size_t)n16 * 16);
+    int8_t *d_out = (int8_t *)buf_get(ctx, ms->buf[1], (size_t)(total ? total : 1));
+    if (!d_work || !d_out)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set render2: scratch of %lld + %lld bytes failed", (long long)n16 * 16, total);
+    for (size_t i = 0; i < marks.size(); ++i)
+        marks[i].img = d_work + mark_work[i];
+    const Render2Job *d_jobs = buf_stage(ctx, ms->buf[11], jobs);
+    const MarkJob *d_marks = buf_stage(ctx, ms->buf[12], marks);
+    const int32_t *d_spans = buf_stage(ctx, ms->buf[13], spans);
+    const double2 *d_xy = (const double2 *)buf_upload(ctx, ms->buf[14], xy, 2 * (size_t)n_pts);
+    float2 *d_xy32 = (float2 *)buf_get(ctx, ms->buf[15], (sizeof(float2) + 1) * (size_t)(n_pts ? n_pts : 1));
+    if (!d_jobs || !d_marks || !d_spans || !d_xy || !d_xy32)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set render2: table / point upload failed");
+    uint8_t *d_keep = (uint8_t *)(d_xy32 + (n_pts ? n_pts : 1));
+    const auto blocks = [](int64_t items) { return (unsigned)std::min<int64_t>((items + MAP_THREADS - 1) / MAP_THREADS, 1 << 20); };
+    hipLaunchKernelGGL(map2_fill_kernel, dim3(blocks(n16)), dim3(MAP_THREADS), 0, ctx->stream, (uint4 *)d_work, n16);
+    SFE_LAUNCH_CHECK(ctx);
+    if (!marks.empty()) {
+        hipLaunchKernelGGL(map2_mark_kernel, dim3(blocks(max_px), (unsigned)marks.size()), dim3(MAP_THREADS), 0, ctx->stream,
+                           d_marks);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    if (n_pts) {
+        hipLaunchKernelGGL(map2_cast_kernel, dim3(blocks(n_pts)), dim3(MAP_THREADS), 0, ctx->stream, d_xy, n_pts, d_xy32,
+                           d_keep);
+        SFE_LAUNCH_CHECK(ctx);
+        if (any_filter) {
+            hipLaunchKernelGGL(map2_radius_count_kernel, dim3((unsigned)((max_pts + 255) / 256), (unsigned)n), dim3(256), 0,
+                               ctx->stream, d_jobs, (const float2 *)d_xy32, d_keep);
+            SFE_LAUNCH_CHECK(ctx);
+        }
+        hipLaunchKernelGGL(map2_stamp_kernel, dim3(blocks(max_stamp), (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs,
+                           d_xy, (const float2 *)d_xy32, (const uint8_t *)d_keep, d_spans, d_work);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    if (max_out) {
+        hipLaunchKernelGGL(map2_resize_kernel, dim3(blocks(max_out), (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs,
+                           (const int8_t *)d_work, d_out);
+        SFE_LAUNCH_CHECK(ctx);
+        // (bytes of `total` no job covers are whatever the scratch held: the offsets are the caller's)
+        SFE_HIP(ctx, hipMemcpyAsync(occ_out, d_out, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (and xy may go away)
+    return 0;
+}
+
 int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings, const double *breaks, const double *coef,
                          int n_intervals, double margin, int num_ranges, double range_resolution, int range_in_double,
                          int r_skip, int c_skip, int *id_out)
@@ -1657,6 +1912,18 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
     const int32_t map = 0, w = which, box4[4] = {r0, r1, c0, c1}, out_hw[2] = {out_h, out_w}, rs = resize;
     const long long out_off = 0;
     return sfe_mapset_render(one(m), 1, &map, &w, box4, out_hw, &inv, &rs, &out_off, occ_out, (long long)out_h * out_w);
+}
+
+int sfe_map_render2(sfe_map *m, int n_slots, const int32_t *slots, int r0, int r1, int c0, int c1, const double *xy, int n_pts,
+                    int filter, double radius, int min_points, int dilate_hs, double y0, double x0, double resolution,
+                    int out_h, int out_w, double inv, int resize, int8_t *occ_out)
+{
+    const int32_t map = 0, slot_off[2] = {0, n_slots}, box4[4] = {r0, r1, c0, c1}, pt_off[2] = {0, n_pts}, f = filter;
+    const int32_t mp = min_points, hs = dilate_hs, out_hw[2] = {out_h, out_w}, rs = resize;
+    const double origin2[2] = {y0, x0};
+    const long long out_off = 0;
+    return sfe_mapset_render2(one(m), 1, &map, slot_off, slots, box4, pt_off, xy, &f, &radius, &mp, &hs, origin2, &resolution,
+                              out_hw, &inv, &rs, &out_off, occ_out, (long long)out_h * out_w);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

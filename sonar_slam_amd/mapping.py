@@ -1,4 +1,5 @@
-"""bruce_slam's log-odds occupancy map (bruce_slam/mapping.py, method 1) with the per-pixel work on the device.
+"""bruce_slam's occupancy map (bruce_slam/mapping.py: the log-odds grid, method 1, and the point-projection map, method 2)
+with the per-pixel work on the device.
 
 ``Mapping`` keeps the reference's attributes, defaults and control flow; the polar measurement image, the fit of every
 pixel of a keyframe to grid cells with its deduplication, the ordered add / subtract of the cells on the float32 grid, growth
@@ -10,8 +11,13 @@ per-keyframe cos / sin of the pose, pose_changed and the growth decisions of adj
 Extensions: ``update_poses(keys, poses)`` (the loop of update_pose calls, batched: the same bits) and
 ``add_keyframe_logodds(key, pose, ping, logodds)`` (a ready polar log-odds image instead of points) and
 ``add_keyframe_store(key, pose, ping, store, handle)`` (the cloud taken from a ``store.CloudStore`` where it lies on the
-device: the same map, bit for bit, without the cloud crossing to the host).  Refused:
-method 2 (``get_occupancy_grid2``) and the intensity grid.  INTEGRATION.md lists the deviations.
+device: the same map, bit for bit, without the cloud crossing to the host).
+
+Method 2 (``get_occupancy_grid2``): the selection of the cloud by ``frames`` and the known region (the union of the listed
+keyframes' cell boxes) are taken here; marking the free cells from the keyframes' cell lists, the outlier filter, the
+projection, the inflation by the ellipse element and the resize run in one device call (sfe_map_render2), bit for bit the
+reference's int8 image.  With ``pub_occupancy1`` off a keyframe takes no measurement, as in the reference, and
+``get_occupancy_grid`` serves method 2.  Refused: the intensity grid.  INTEGRATION.md lists the deviations.
 """
 import contextlib
 import ctypes as C
@@ -156,7 +162,7 @@ class Mapping(object):
         self.miss_prob = 0.3
         self.inflation_angle = 0.05
         self.inflation_range = 0.5
-        # method 2: point projection (refused; its bookkeeping is kept)
+        # method 2: point projection
         self.pub_occupancy2 = True
         self.point_cloud = None
         self.inflation_radius = 0.5
@@ -355,8 +361,10 @@ class Mapping(object):
         return kf
 
     def _hits(self, points):
-        """-> (hits [n x 2] int32 of the downsampled image, hr, hc); None for no points (mapping.py:172-205)"""
-        if not len(points):
+        """-> (hits [n x 2] int32 of the downsampled image, hr, hc); None for no points (mapping.py:172-205).  With
+        pub_occupancy1 off the reference takes no measurement (mapping.py:170; `points` is then the SLAM cloud, kept for
+        method 2): the slot gets the all-miss image, which nothing reads, and its cell list is what the fit makes of it"""
+        if not self.pub_occupancy1 or not len(points):
             return None, -1, 0
         if self.outlier_filter_min_points > 1:
             points = pcl.remove_outlier(points[:, :2], self.outlier_filter_radius, self.outlier_filter_min_points,
@@ -597,8 +605,36 @@ class Mapping(object):
     def get_intensity_grid(self):
         raise NotImplementedError("Mapping.get_intensity_grid: the intensity grid is not implemented")
 
+    def _check_method2(self, what, cloud):
+        """what method 2 needs, named when it is missing.  (Before configure() the answer stays NotImplementedError, a
+        RuntimeError like the other entry points' "configure() first".)"""
+        if self.rows is None:
+            raise NotImplementedError("%s: get_occupancy_grid2 is not implemented for a map that was never configured: "
+                                      "configure() first" % what)
+        if not self.pub_occupancy2:
+            raise RuntimeError("%s: the map was configured with pub_occupancy2=False, so it has no dilate_size" % what)
+        if cloud is None:
+            raise RuntimeError("%s: no point_cloud yet: add a keyframe, or set point_cloud to the SLAM cloud "
+                               "(x, y, z, key)" % what)
+        if self.dilate_size < 1 or self.dilate_size % 2 == 0:
+            raise ValueError("%s: dilate_size = %r; the ellipse element is built for odd sizes (2 * dilate_hs + 1, as "
+                             "configure() sets it)" % (what, self.dilate_size))
+
     def get_occupancy_grid2(self, frames=None, resolution=None):
-        raise NotImplementedError("Mapping.get_occupancy_grid2: method 2 (point projection + dilation) is not implemented")
+        """mapping.py:357-439: unknown -1, the listed keyframes' cells 0 (all keyframes by default), the cells under the
+        inflated projection of ``point_cloud`` 100 (with ``frames``: of its rows whose column 3 is a listed key)"""
+        cloud = self.point_cloud if self.rows is not None and self.pub_occupancy2 else None
+        self._check_method2("Mapping.get_occupancy_grid2", cloud)
+        points = select_points(np.asarray(cloud), frames)
+        slots, box, origin, (oh, ow), inv, resize, resolution = self._render2_plan(frames, resolution)
+        xy = np.ascontiguousarray(points, np.float64)
+        occ = np.zeros((oh, ow), np.int8)
+        self._check(self._lib.sfe_map_render2(
+            self._h, len(slots), _L.ptr(slots, C.c_int32), box[0], box[1], box[2], box[3],
+            _L.ptr(xy if len(xy) else np.zeros(2), C.c_double), len(xy), int(self.outlier_filter_min_points > 1),
+            float(self.outlier_filter_radius), int(self.outlier_filter_min_points), self.dilate_size // 2, origin[0], origin[1],
+            float(self.resolution), oh, ow, inv, resize, occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return self._grid_msg(box, resolution, occ, origin)
 
     def get_occupancy_grid(self, frames=None, resolution=None):
         if self.pub_occupancy1:
@@ -625,6 +661,11 @@ class Mapping(object):
                 cmin, cmax = min(cmin, c0), max(cmax, c1)
             slots = np.array(slots, np.int32)
         h, w = max(0, rmax - rmin + 1), max(0, cmax - cmin + 1)
+        (oh, ow), inv, resize, resolution = self._resize_plan(h, w, resolution)
+        return which, slots, (int(rmin), int(rmax), int(cmin), int(cmax)), (oh, ow), inv, resize, resolution
+
+    def _resize_plan(self, h, w, resolution):
+        """the resize both methods end with -> ((oh, ow), inv, resize, the resolution published)"""
         resize = 0
         inv = 1.0
         if resolution is not None and resolution > 0 and abs(resolution - self.resolution) > self.resolution * 1e-1:
@@ -637,14 +678,38 @@ class Mapping(object):
         else:
             oh, ow = h, w
             resolution = self.resolution
-        return which, slots, (int(rmin), int(rmax), int(cmin), int(cmax)), (oh, ow), float(inv), resize, resolution
+        return (oh, ow), float(inv), resize, resolution
 
-    def _grid_msg(self, box, resolution, occ):
+    def _render2_plan(self, frames, resolution):
+        """method 2's known region and sizes -> (slots of `frames`, (rmin, rmax, cmin, cmax), (y0, x0) of its corner,
+        (oh, ow), inv, resize, resolution).  The region is the tight box of the cells marked free, which is the union of the
+        listed keyframes' cell boxes; its corner is taken with the map's resolution, also when the image is resized
+        (mapping.py:401-402).  Nothing marked: the reference's IndexError (mapping.py:384)."""
+        slots, boxes = [], []
+        for k in (range(len(self.keyframes)) if frames is None else frames):
+            if k >= len(self.keyframes) or self.keyframes[k] is None:
+                continue
+            slots.append(self.keyframes[k]._slot)
+            boxes.append(self.keyframes[k].cell_box())
+        if not slots:
+            raise IndexError("get_occupancy_grid2: no keyframe of frames=%r has cells, so there is no known region"
+                             % (None if frames is None else list(frames),))
+        rmin, cmin = min(b[0] for b in boxes), min(b[2] for b in boxes)
+        rmax, cmax = max(b[1] for b in boxes), max(b[3] for b in boxes)
+        x0 = self.x0 + cmin * self.resolution
+        y0 = self.y0 + rmin * self.resolution
+        size, inv, resize, resolution = self._resize_plan(rmax - rmin + 1, cmax - cmin + 1, resolution)
+        return (np.array(slots, np.int32), (int(rmin), int(rmax), int(cmin), int(cmax)), (float(y0), float(x0)), size, inv,
+                resize, resolution)
+
+    def _grid_msg(self, box, resolution, occ, origin=None):
+        """the message of an image of `box`; its origin as method 1 takes it (with the published resolution), or `origin` =
+        (y, x) as given (method 2)"""
         rmin, cmin = box[0], box[2]
         occ_msg = OccupancyGrid()
         occ_msg.header.frame_id = "map"
-        occ_msg.info.origin.position.x = self.x0 + cmin * resolution
-        occ_msg.info.origin.position.y = self.y0 + rmin * resolution
+        occ_msg.info.origin.position.x = self.x0 + cmin * resolution if origin is None else origin[1]
+        occ_msg.info.origin.position.y = self.y0 + rmin * resolution if origin is None else origin[0]
         occ_msg.info.origin.orientation.x = 0
         occ_msg.info.origin.orientation.y = 0
         occ_msg.info.origin.orientation.z = 0
@@ -665,6 +730,21 @@ class Mapping(object):
             self._check(self._lib.sfe_map_render(self._h, which, box[0], box[1], box[2], box[3], oh, ow, inv, resize,
                                                  occ.ctypes.data_as(C.POINTER(C.c_int8))))
         return self._grid_msg(box, resolution, occ)
+
+
+# ---- method 2's cloud -----------------------------------------------------------------------------------------------------
+def select_points(point_cloud, frames):
+    """the points get_occupancy_grid2 projects (mapping.py:365-372), as written there: columns x, y of the whole cloud, or
+    with `frames` the rows whose column 3 is k, for every k in list order (a key listed twice gives its rows twice; a key
+    without a keyframe still gives its rows), behind np.zeros((0, 2)): float64"""
+    points = point_cloud[:, :2]
+    if frames is not None:
+        points = [np.zeros((0, 2))]
+        keys = np.uint32(point_cloud[:, 3])
+        for k in frames:
+            points.append(point_cloud[keys == k, :2])
+        points = np.concatenate(points)
+    return points
 
 
 # ---- what Mapping and MapBatch hand the measurement ------------------------------------------------------------------------
@@ -904,6 +984,9 @@ class _SessionMap(Mapping):
     def get_occupancy_grid1(self, frames=None, resolution=None):
         return self._b._render([self._s], frames, resolution)[0]
 
+    def get_occupancy_grid2(self, frames=None, resolution=None):
+        return self._b.get_occupancy_grid2([self._s], frames, resolution)[0]
+
 
 class MapBatch(object):
     """S occupancy maps that advance together: every stage of Mapping as one device call over the listed sessions
@@ -975,8 +1058,42 @@ class MapBatch(object):
     def get_intensity_grid(self):
         raise NotImplementedError("MapBatch.get_intensity_grid: the intensity grid is not implemented")
 
-    def get_occupancy_grid2(self, *args, **kw):
-        raise NotImplementedError("MapBatch.get_occupancy_grid2: method 2 (point projection + dilation) is not implemented")
+    def get_occupancy_grid2(self, sessions=None, frames=None, resolution=None, point_clouds=None):
+        """maps[s].get_occupancy_grid2(frames, resolution) for the listed sessions (all by default) -> list of OccupancyGrid,
+        rendered in one device call.  ``point_clouds[i]`` replaces the stored cloud of ``sessions[i]`` for this call."""
+        if self._h is None:
+            raise NotImplementedError("MapBatch.get_occupancy_grid2: get_occupancy_grid2 is not implemented for a batch that "
+                                      "was never configured: configure() first")
+        sessions = self._listed("get_occupancy_grid2", range(self.S) if sessions is None else sessions,
+                                *(() if point_clouds is None else (point_clouds,)))
+        views = [self.maps[s] for s in sessions]
+        clouds = [v.point_cloud if self.pub_occupancy2 else None for v in views] if point_clouds is None else point_clouds
+        for s, v, cloud in zip(sessions, views, clouds):
+            v._check_method2("MapBatch.get_occupancy_grid2 (session %d)" % s, cloud)
+        points = [np.ascontiguousarray(select_points(np.asarray(c), frames), np.float64) for c in clouds]
+        plans = [v._render2_plan(frames, resolution) for v in views]
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32).reshape(-1))
+        f64 = lambda a: np.ascontiguousarray(np.array(a, np.float64).reshape(-1))
+        off = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        slots = np.concatenate([p[0] for p in plans]).astype(np.int32)
+        xy = np.concatenate(points) if sum(len(p) for p in points) else np.zeros((1, 2))
+        out_off = np.zeros(len(sessions) + 1, np.int64)
+        out_off[1:] = np.cumsum([p[3][0] * p[3][1] for p in plans])
+        occ = np.zeros(max(1, int(out_off[-1])), np.int8)
+        n = len(sessions)
+        self._check(self._lib.sfe_mapset_render2(
+            self._h, n, _L.ptr(i32(sessions), C.c_int32), _L.ptr(off([len(p[0]) for p in plans]), C.c_int32),
+            _L.ptr(slots, C.c_int32), _L.ptr(i32([p[1] for p in plans]), C.c_int32),
+            _L.ptr(off([len(p) for p in points]), C.c_int32), _L.ptr(np.ascontiguousarray(xy), C.c_double),
+            _L.ptr(i32([v.outlier_filter_min_points > 1 for v in views]), C.c_int32),
+            _L.ptr(f64([v.outlier_filter_radius for v in views]), C.c_double),
+            _L.ptr(i32([v.outlier_filter_min_points for v in views]), C.c_int32),
+            _L.ptr(i32([v.dilate_size // 2 for v in views]), C.c_int32), _L.ptr(f64([p[2] for p in plans]), C.c_double),
+            _L.ptr(f64([v.resolution for v in views]), C.c_double), _L.ptr(i32([p[3] for p in plans]), C.c_int32),
+            _L.ptr(f64([p[4] for p in plans]), C.c_double), _L.ptr(i32([p[5] for p in plans]), C.c_int32),
+            out_off.ctypes.data_as(C.POINTER(C.c_longlong)), occ.ctypes.data_as(C.POINTER(C.c_int8)), int(out_off[-1])))
+        return [v._grid_msg(p[1], p[6], occ[out_off[j]:out_off[j + 1]].reshape(p[3]).copy(), p[2])
+                for j, (v, p) in enumerate(zip(views, plans))]
 
     # ---- helpers -----------------------------------------------------------------------------------------------------
     def _check(self, rc):
@@ -1127,7 +1244,7 @@ class MapBatch(object):
         """Mapping._hits for every listed session: the outlier filter of all clouds in one device call, then the hit indices
         (elementwise in the points) once per group of sessions that share a sonar geometry -> [(hits, hr, hc)]"""
         out = [None] * len(sessions)
-        live = [i for i, c in enumerate(clouds) if len(c)]
+        live = [i for i, c in enumerate(clouds) if len(c)] if self.pub_occupancy1 else []     # (Mapping._hits)
         for i in range(len(sessions)):
             if i not in live:
                 out[i] = (None, -1, 0)
@@ -1244,7 +1361,7 @@ class MapBatch(object):
         if self.pub_occupancy1:
             return self._render(range(self.S) if sessions is None else sessions, frames, resolution)
         if self.pub_occupancy2:
-            return self.get_occupancy_grid2(frames, resolution)
+            return self.get_occupancy_grid2(sessions, frames, resolution)
         return [None] * (self.S if sessions is None else len(sessions))
 
     def _render(self, sessions, frames, resolution):

@@ -34,9 +34,21 @@ clouds lie in a CloudStore has to do without the store feed), and `add_keyframe_
   readbacks_per_add      host read-backs of the measurement per add (the fit's bounds come on top on every route)
   grids_equal            the three final grids are bit for bit equal
 
+With `--method 2` only the point-projection map is timed, under "method2": a Mapping of `--batch-keyframes` keyframes with
+its keyed SLAM cloud (every keyframe's 300 points registered with its pose: float32 x, y, 0, key), fed with pub_occupancy1
+off, and -- with `--sessions S` > 0 -- a MapBatch of S such sessions (session s shifted by s metres):
+  get_occupancy_grid2_ms one call, the whole map and `frames` = the last 10 keyframes at 0.5 m: the device route (host
+                         selection and plan, one sfe_map_render2 call, read-back) next to the numpy restatement
+                         tests/mapping2_ref.py on the cell lists read back beforehand (its filter is the C oracle's), the
+                         median of `--reps` alternated repetitions
+  lockstep               one MapBatch.get_occupancy_grid2 call for all S sessions; `numpy_one_session_ms` is the restatement
+                         for one of them
+  images_equal           the device images equal the restatement's
+
     python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
     python tools/mapping_times.py --sessions 32 --feed store
     python tools/mapping_times.py --feed store --batch-keyframes 200
+    python tools/mapping_times.py --method 2 --sessions 32
 """
 import argparse
 import json
@@ -49,6 +61,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mapping2_ref  # noqa: E402
 import mapping_ref  # noqa: E402
 import oracle  # noqa: E402
 from sonar_slam_amd import _lib  # noqa: E402
@@ -235,6 +248,69 @@ def feed_single(ctx, ping, settings, K):
     return out
 
 
+def method2(ctx, ping, settings, S, K, reps):
+    """get_occupancy_grid2 of one Mapping, and of a MapBatch of S sessions, next to the numpy restatement -> the "method2" record"""
+    poses, clouds = session(K)
+
+    def keyed(shift):
+        parts = []
+        for k, ((x, y, th), pts) in enumerate(zip(poses, clouds)):
+            c, s = np.cos(th), np.sin(th)
+            g = np.c_[c * pts[:, 0] - s * pts[:, 1] + x + shift, s * pts[:, 0] + c * pts[:, 1] + y]
+            parts.append(np.c_[g, np.zeros(len(g)), np.full(len(g), float(k))])
+        return np.concatenate(parts).astype(np.float32)
+    settings = dict(settings, pub_occupancy1=False)
+    m = Mapping(ctx)
+    for k, v in settings.items():
+        setattr(m, k, v)
+    m.configure()
+    cloud = keyed(0.0)
+    for k in range(K):
+        m.add_keyframe(k, Pose2(*poses[k]), ping, cloud)
+    cells = [(kf.r, kf.c) for kf in m.keyframes]
+    queries = {"all": dict(), "last10_coarse": dict(frames=list(range(max(0, K - 10), K)), resolution=0.5)}
+    med = lambda v: float(np.median(v))
+    out = {"keyframes": K, "points": len(cloud), "dilate_size": int(m.dilate_size), "reps": reps, "get_occupancy_grid2_ms": {}}
+    equal = True
+    for name, kw in queries.items():
+        t_d, t_n = [], []
+        for rep in range(reps + 1):
+            got, want = [None], [None]
+            dev = lambda: got.__setitem__(0, m.get_occupancy_grid2(**kw))
+            ref = lambda: want.__setitem__(0, mapping2_ref.occupancy_grid2(m, cells, cloud, oracle.remove_outlier, **kw))
+            first, second = (dev, ref) if rep % 2 == 0 else (ref, dev)
+            a, b = timed(first), timed(second)
+            if rep:                 # the first call grows the scratch
+                (t_d if first is dev else t_n).append(a)
+                (t_n if first is dev else t_d).append(b)
+            equal = equal and np.array_equal(got[0].occ, want[0]["data"])
+        out["get_occupancy_grid2_ms"][name] = {"device": med(t_d), "numpy": med(t_n), "image": list(got[0].occ.shape),
+                                               "selected_points": len(want[0]["points"]), "kept": want[0]["kept"]}
+    if S > 0:
+        batch = MapBatch(ctx, S, K, **settings)
+        batch.configure()
+        sessions = list(range(S))
+        shifted = [keyed(float(s)) for s in sessions]
+        for k in range(K):
+            batch.add_keyframes(sessions, [k] * S, [Pose2(poses[k][0] + s, poses[k][1], poses[k][2]) for s in sessions], ping,
+                                shifted)
+        out["lockstep"] = {"sessions": S}
+        for name, kw in queries.items():
+            t_b = [timed(lambda: batch.get_occupancy_grid2(**kw)) for _ in range(reps + 1)][1:]
+            v = batch.maps[S - 1]
+            last = [(kf.r, kf.c) for kf in v.keyframes]
+            t_n = [timed(lambda: mapping2_ref.occupancy_grid2(v, last, shifted[S - 1], oracle.remove_outlier, **kw))
+                   for _ in range(max(1, reps // 2))]
+            want = mapping2_ref.occupancy_grid2(v, last, shifted[S - 1], oracle.remove_outlier, **kw)
+            equal = equal and np.array_equal(batch.get_occupancy_grid2(**kw)[S - 1].occ, want["data"])
+            out["lockstep"][name] = {"lockstep_ms": med(t_b), "numpy_one_session_ms": med(t_n),
+                                     "numpy_all_sessions_ms": med(t_n) * S}
+        batch.close()
+    out["images_equal"] = bool(equal)
+    m.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
@@ -243,10 +319,16 @@ def main():
     ap.add_argument("--batch-keyframes", type=int, default=40)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--feed", choices=("host", "store"), default=None)
+    ap.add_argument("--method", type=int, choices=(1, 2), default=1, help="2: time get_occupancy_grid2 only")
     a = ap.parse_args()
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
     settings = dict(x0=-100.0, y0=-100.0, width=200.0, height=200.0)
+    if a.method == 2:
+        ctx = _lib.default_context()
+        print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
+                          "method2": method2(ctx, ping, settings, a.sessions or 0, a.batch_keyframes, a.reps)}))
+        return
     if a.feed == "store" and not a.sessions:
         ctx = _lib.default_context()
         print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
