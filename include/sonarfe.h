@@ -454,6 +454,11 @@ void sfe_cloud_store_destroy(sfe_cloud_store *s);
 int sfe_cloud_store_count(sfe_cloud_store *s); /* slots in use = the next handle */
 /* one cloud from the host (a feature message that arrived over the wire), enqueue only */
 int sfe_cloud_store_put(sfe_ctx *ctx, sfe_cloud_store *s, int64_t stamp, const float *pts, int n, int32_t *handle_out);
+/* ... with a key per point (keys[i] >= 0, else SFE_ERR_ARG and no slot): a keyed slot like the one
+ * sfe_cloud_store_get_points_keys leaves, read back by sfe_cloud_store_read_keys.  For a cloud that arrives already keyed: the
+ * SLAM cloud (x, y, 0, key) of slam_ros.py:317-359 as the mapping node receives it.  Enqueue only. */
+int sfe_cloud_store_put_keys(sfe_ctx *ctx, sfe_cloud_store *s, int64_t stamp, const float *pts, const int32_t *keys, int n,
+                             int32_t *handle_out);
 /* n_frames clouds straight from sfe_cloud_filter_batch_dev's outputs (d_clouds [n_frames][cap][2] float32, d_counts),
  * device to device, enqueue only; stamps (host, nullable) are kept with the slots; handles_out (host, nullable) */
 int sfe_cloud_store_put_batch_dev(sfe_ctx *ctx, sfe_cloud_store *s, const int64_t *stamps, const float *d_clouds,
@@ -663,7 +668,8 @@ int sfe_pose2_sample_transforms(const double *target_xycs, const double *source_
  *     sfe_map_shape -> {rows, cols, rows grown on top, columns grown on the left}.
  *   sfe_map_frames: a fresh grid, the listed slots added in list order.  sfe_map_render: rows r0..r1 x cols c0..c1 of a grid
  *     -> int8(clip(100 expit(v), 0, 100)), resized INTER_NEAREST to out_h x out_w with source index floor(i * inv) when
- *     resize != 0.  sfe_map_render2: sfe_mapset_render2, below, for one image of this map.
+ *     resize != 0.  sfe_map_render2: sfe_mapset_render2, below, for one image of this map; sfe_map_render2_store:
+ *     sfe_mapset_render2_store for one image, its frame list frames[0 .. n_frames).
  *   sfe_map_hit_table / sfe_map_measure_store / sfe_map_measure_store_undecided / sfe_map_measure_store_finish: the store
  *     feed of one map: the sfe_mapset_* calls of the same names, below, over one map.  n keyframes of the map per call, each
  *     slot at most once.  A slot that holds an image of another geometry, an unknown geometry or a negative slot is refused
@@ -704,6 +710,10 @@ int sfe_map_render(sfe_map *m, int which, int r0, int r1, int c0, int c1, int ou
 int sfe_map_render2(sfe_map *m, int n_slots, const int32_t *slots, int r0, int r1, int c0, int c1, const double *xy, int n_pts,
                     int filter, double radius, int min_points, int dilate_hs, double y0, double x0, double resolution,
                     int out_h, int out_w, double inv, int resize, int8_t *occ_out);
+int sfe_map_render2_store(sfe_map *m, sfe_cloud_store *store, int n_slots, const int32_t *slots, int r0, int r1, int c0, int c1,
+                          int handle, int all_frames, const int32_t *frames, int n_frames, int filter, double radius,
+                          int min_points, int dilate_hs, double y0, double x0, double resolution, int out_h, int out_w,
+                          double inv, int resize, int8_t *occ_out);
 
 /* ---- S occupancy maps that advance together (sonar_slam_amd/mapping.py: MapBatch; chained.SessionBatch's maps).  One
  * sfe_mapset owns the state of n_maps maps, each exactly what an sfe_map of its own holds after the same calls: the
@@ -774,6 +784,16 @@ int sfe_map_render2(sfe_map *m, int n_slots, const int32_t *slots, int r0, int r
  *     getStructuringElement(MORPH_ELLIPSE, (2 dilate_hs[b] + 1,) * 2) of a projected point becomes 100, above 0.  The region
  *     is then resized as in sfe_mapset_render (out_hw / inv / resize / out_off / total).  A region that is empty, leaves the
  *     map or lists a slot without cells is refused with SFE_ERR_ARG; at most 65535 jobs and 65535 listed slots per call.
+ *   sfe_mapset_render2_store: sfe_mapset_render2 with job b's points taken in place from cloud handles[b] of `store` (a store
+ *     of the set's context): no point and no key is copied, the image is the only read-back.  all_frames[b] != 0 takes every
+ *     point of the cloud; otherwise the selection of mapping.py:365-372 over frames[frame_off[b] .. frame_off[b + 1]): for
+ *     every listed k, the points whose key is k -- a key listed twice gives its points twice (they count twice in the filter),
+ *     a k no point carries (a negative one, a key beyond the session) gives none, an empty list no point at all.  The stored
+ *     float32 points go to the filter's decision as they are when filter[b] != 0, and the kept ones (all selected ones
+ *     without the filter) are widened to double and projected: the image is sfe_mapset_render2's for xy = the selected
+ *     float32 points as doubles.  Refused with SFE_ERR_ARG before anything changes, besides sfe_mapset_render2's refusals: a
+ *     store of another context, a handle the store does not hold or whose count is < 0, a frame list for a cloud without
+ *     keys (one not built by sfe_cloud_store_get_points_keys[_many] or sfe_cloud_store_put_keys).
  * sfe_remove_outlier_many: sfe_remove_outlier's decision for n_clouds clouds in one launch: cloud c = pts[off[c] .. off[c + 1])
  *   (points), keep_out[i] = 1 for the points that stay.  One synchronisation. */
 typedef struct sfe_mapset sfe_mapset;
@@ -816,6 +836,12 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
                        const double *radius, const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
                        const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
                        const long long *out_off, int8_t *occ_out, long long total);
+int sfe_mapset_render2_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slot_off,
+                             const int32_t *slots, const int32_t *box4, const int32_t *handles, const int32_t *all_frames,
+                             const int32_t *frame_off, const int32_t *frames, const int32_t *filter, const double *radius,
+                             const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
+                             const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
+                             const long long *out_off, int8_t *occ_out, long long total);
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,
                             uint8_t *keep_out);
 

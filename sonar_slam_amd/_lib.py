@@ -219,6 +219,7 @@ SIGNATURES = {
     "sfe_cloud_store_destroy": (None, [_vp]),
     "sfe_cloud_store_count": (C.c_int, [_vp]),
     "sfe_cloud_store_put": (C.c_int, [_vp, _vp, C.c_int64, _f32p, C.c_int, _i32p]),
+    "sfe_cloud_store_put_keys": (C.c_int, [_vp, _vp, C.c_int64, _f32p, _i32p, C.c_int, _i32p]),
     "sfe_cloud_store_put_batch_dev": (C.c_int, [_vp, _vp, _i64p, _vp, _vp, C.c_int, C.c_int64, C.c_int, _i32p]),
     "sfe_cloud_store_meta": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _i64p, _i64p, _i32p]),
     "sfe_cloud_store_read": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_int, C.POINTER(C.c_int)]),
@@ -287,6 +288,9 @@ SIGNATURES = {
     "sfe_map_render2": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _f64p, C.c_int, C.c_int, C.c_double,
                                   C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_int,
                                   C.POINTER(C.c_int8)]),
+    "sfe_map_render2_store": (C.c_int, [_vp, _vp, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p,
+                                        C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
+                                        C.c_int, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_int8)]),
     "sfe_mapset_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "sfe_mapset_destroy": (None, [_vp]),
     "sfe_mapset_geometry": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, C.POINTER(C.c_int)]),
@@ -315,6 +319,9 @@ SIGNATURES = {
                                     C.POINTER(C.c_int8), C.c_longlong]),
     "sfe_mapset_render2": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _f64p, _i32p, _f64p, _i32p, _i32p, _f64p,
                                      _f64p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong), C.POINTER(C.c_int8), C.c_longlong]),
+    "sfe_mapset_render2_store": (C.c_int, [_vp, _vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
+                                           _f64p, _i32p, _i32p, _f64p, _f64p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong),
+                                           C.POINTER(C.c_int8), C.c_longlong]),
     "sfe_remove_outlier_many": (C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_double, C.c_int, _u8p]),
 }
 

@@ -323,6 +323,41 @@ class SessionBatch(object):
         clouds = self.store.read_many(self.handles[:, k])
         self.maps.add_keyframes(range(self.S), [k] * self.S, poses, self._map_ping, clouds)
 
+    def slam_clouds(self, sessions=None):
+        """``FrontEnd.slam_cloud()`` for the listed sessions (all by default): the keyframes recorded so far under the batch's
+        current poses, tagged with their keys and downsampled at ``point_resolution``, in one ``get_points_keys_many`` call ->
+        handles of new keyed slots, one per listed session, which the caller drops with ``store.truncate``"""
+        sessions = [int(s) for s in (range(self.S) if sessions is None else sessions)]
+        for s in sessions:
+            if not 0 <= s < self.S:
+                raise IndexError("SessionBatch.slam_clouds: session %d of %d" % (s, self.S))
+        n = 0
+        while n < self.K and self.poses[n] is not None and np.all(self.handles[:, n] >= 0):
+            n += 1
+        frames = list(range(n))
+        h = self.store.get_points_keys_many([self.handles[s, frames] for s in sessions],
+                                            [[_store.pose_T6(self._pose(f, s)) for f in frames] for s in sessions],
+                                            [frames] * len(sessions), self.point_resolution)
+        self._made(h, n - 1, "SLAM")
+        return h
+
+    def occupancy_grids2(self, sessions=None, frames=None, resolution=None):
+        """``FrontEnd.occupancy_grid2(frames, resolution)`` for the listed sessions (all by default) -> list of OccupancyGrid:
+        their SLAM clouds are built in the store (``slam_clouds``), rendered from there in one device call
+        (``MapBatch.get_occupancy_grid2_store``) and dropped again.  Needs ``mapping=dict(...)`` with ``pub_occupancy2``
+        on."""
+        if self.maps is None:
+            raise RuntimeError("SessionBatch.occupancy_grids2: the batch owns no maps: construct it with mapping=dict(ping=...)")
+        if not self.maps.pub_occupancy2:
+            raise RuntimeError("SessionBatch.occupancy_grids2: the maps were configured with pub_occupancy2=False")
+        sessions = list(range(self.S) if sessions is None else sessions)
+        n_slots = len(self.store)
+        try:
+            clouds = self.slam_clouds(sessions)
+            return self.maps.get_occupancy_grid2_store(self.store, clouds, sessions, frames, resolution)
+        finally:
+            self.store.truncate(n_slots)
+
     def _scan_match_step(self, k, rec, src_h, th, T6, prev, pose):
         S, store = self.S, self.store
         tgt_h = store.get_points(th, T6, self.point_resolution)

@@ -212,6 +212,9 @@ struct SfeStoreView {
     const int64_t *off;     // host mirror (valid for slots < n_slots)
     const int32_t *cnt;
     int n_slots;
+    const int32_t *d_key;   // a key per pool point, for the keyed slots (nullptr: no slot is keyed yet)
+    const uint8_t *keyed;   // host, n_keyed entries: the slot was built by a keyed entry point
+    int n_keyed;
 };
 int sfe_store_view(sfe_cloud_store *s, SfeStoreView *v);
 

@@ -136,8 +136,8 @@ struct sfe_mapset {
     int counts_cap = 0;
     // scratch.  0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's job tables, hit buffer,
     // keep flags, undecided lists and counters, hit tables; 11 .. 16: method 2's job tables, list table, spans, points,
-    // float32 points + keep flags, work images
-    MapBuf buf[17];
+    // float32 points + keep flags, work images; 17, 18: its store route's frame lists, multiplicities + keep flags
+    MapBuf buf[19];
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
     long long apply_launches = 0; // launches of mapset_apply_kernel so far
@@ -502,6 +502,9 @@ struct Render2Job {
     double y0, x0, res;    // the region's corner in metres, the map's resolution
     double inv;
     int64_t work_off, out_off;
+    // the store route (sfe_mapset_render2_store): its cloud in the store's pool, its frame list in the call's list table
+    int64_t pool_off;
+    int32_t frame_off, n_frames; // n_frames < 0: all frames
 };
 
 // the current cell list of one listed keyframe of a job
@@ -558,13 +561,88 @@ __global__ __launch_bounds__(256) void map2_radius_count_kernel(const Render2Job
     radius_count_cloud(xy32 + off, n, jobs[blockIdx.y].r2, jobs[blockIdx.y].min_points, keep + off, s_p);
 }
 
+// (c') the store route's points stay where they are, float32 in the store's pool; what mapping.py:365-372 makes of them is a
+// multiset: point i is taken once for every entry of the job's frame list that equals its key (a key listed twice gives its
+// rows twice, an entry no point carries gives nothing; keys are >= 0, so a negative entry is such an entry).  mult[i] is
+// that multiplicity, 1 for every point of a job that takes all frames; keep[i] = mult[i] > 0 until the filter says otherwise.
+// Job blockIdx.y, block blockIdx.x of its cloud's row; the list goes through LDS in tiles of 1024 entries.
+__global__ __launch_bounds__(256) void map2_select_kernel(const Render2Job *__restrict__ jobs, const int32_t *__restrict__ key_pool,
+                                                          const int32_t *__restrict__ frames, int32_t *__restrict__ mult,
+                                                          uint8_t *__restrict__ keep)
+{
+    __shared__ int32_t s_f[1024];
+    const int32_t n = jobs[blockIdx.y].n_pts, off = jobs[blockIdx.y].pt_off, nf = jobs[blockIdx.y].n_frames;
+    if ((int)(blockIdx.x * 256) >= n)
+        return; // the whole block at once
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int m = 1;
+    if (nf >= 0) {
+        const int32_t *list = frames + jobs[blockIdx.y].frame_off;
+        const int32_t key = i < n ? key_pool[jobs[blockIdx.y].pool_off + i] : -1;
+        m = 0;
+        for (int tb = 0; tb < nf; tb += 1024) {
+            const int tn = min(1024, nf - tb);
+            __syncthreads();
+            for (int j = threadIdx.x; j < tn; j += 256)
+                s_f[j] = list[tb + j];
+            __syncthreads();
+            for (int j = 0; j < tn; ++j)
+                m += s_f[j] == key;
+        }
+    }
+    if (i < n) {
+        mult[off + i] = m;
+        keep[off + i] = m > 0;
+    }
+}
+
+// ... and radius_count_cloud's decision over that multiset: every neighbour counts mult times (a point's own copies too), so
+// a selected point stays iff the host's count over the repeated rows would keep its copies
+__global__ __launch_bounds__(256) void map2_radius_count_store_kernel(const Render2Job *__restrict__ jobs,
+                                                                      const float2 *__restrict__ pool,
+                                                                      const int32_t *__restrict__ mult, uint8_t *__restrict__ keep)
+{
+    __shared__ float2 s_p[2048];
+    __shared__ int32_t s_m[2048];
+    const Render2Job &jb = jobs[blockIdx.y];
+    const int32_t n = jb.n_pts, off = jb.pt_off, min_points = jb.min_points;
+    const float r2 = jb.r2;
+    if (!jb.filter || (int)(blockIdx.x * 256) >= n)
+        return; // the whole block at once
+    const float2 *cloud = pool + jb.pool_off;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    float px = 0, py = 0;
+    if (i < n) {
+        const float2 p = cloud[i];
+        px = p.x;
+        py = p.y;
+    }
+    long long cnt = 0;
+    for (int tb = 0; tb < n; tb += 2048) {
+        const int tn = min(2048, n - tb);
+        __syncthreads();
+        for (int j = threadIdx.x; j < tn; j += 256) {
+            s_p[j] = cloud[tb + j];
+            s_m[j] = mult[off + tb + j];
+        }
+        __syncthreads();
+        for (int j = 0; j < tn; ++j) {
+            const float2 t = s_p[j];
+            const float dx = __fadd_rn(px, -t.x), dy = __fadd_rn(py, -t.y);
+            cnt += __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) <= r2 ? s_m[j] : 0;
+        }
+    }
+    if (i < n)
+        keep[off + i] = mult[off + i] > 0 && cnt > (long long)min_points;
+}
+
 // (d) r = int32(round((y - y0) / resolution)), c likewise, in double (y0 is a numpy float64 scalar, so numpy widens a
 // float32 cloud): one IEEE subtract, one divide, round half to even.  A point outside the region is dropped; one inside is
 // dilated by the element, clipped at the region's border (cv2.dilate's constant border).  One thread per (point, element
-// row): it stores the row's span.
+// row): it stores the row's span.  With `pool` (the store route) the point is the float32 one of the job's cloud there.
 __global__ __launch_bounds__(MAP_THREADS) void map2_stamp_kernel(const Render2Job *__restrict__ jobs,
                                                                  const double2 *__restrict__ xy, const float2 *__restrict__ xy32,
-                                                                 const uint8_t *__restrict__ keep,
+                                                                 const float2 *__restrict__ pool, const uint8_t *__restrict__ keep,
                                                                  const int32_t *__restrict__ spans, int8_t *work)
 {
     const Render2Job j = jobs[blockIdx.y];
@@ -576,7 +654,10 @@ __global__ __launch_bounds__(MAP_THREADS) void map2_stamp_kernel(const Render2Jo
         if (!keep[q])
             continue;
         double x, y;
-        if (j.filter) {
+        if (pool) {
+            const float2 f = pool[j.pool_off + p];
+            x = (double)f.x, y = (double)f.y;
+        } else if (j.filter) {
             const float2 f = xy32[q];
             x = (double)f.x, y = (double)f.y;
         } else {
@@ -1530,23 +1611,43 @@ int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t 
 // get_occupancy_grid2 for n images in one call and one read-back.  Job b: map maps[b]; the free cells are the current lists of
 // slots[slot_off[b] .. slot_off[b + 1]); the known region is box4[4 b ..] = {r0, r1, c0, c1} (the union of those lists' boxes:
 // the caller's), its corner origin2[2 b ..] = {y0, x0} metres; its points xy[2 pt_off[b] .. 2 pt_off[b + 1]) (float64 x, y).
-int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot_off, const int32_t *slots,
-                       const int32_t *box4, const int32_t *pt_off, const double *xy, const int32_t *filter,
-                       const double *radius, const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
-                       const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
-                       const long long *out_off, int8_t *occ_out, long long total)
+// Where a render2 call's points come from: the host (pt_off / xy), or clouds of a store (`store` set), taken in place.
+struct Render2Src {
+    const int32_t *pt_off = nullptr;
+    const double *xy = nullptr;
+    sfe_cloud_store *store = nullptr;
+    const int32_t *handles = nullptr, *all_frames = nullptr, *frame_off = nullptr, *frames = nullptr;
+};
+
+static int set_render2(sfe_mapset *ms, const Render2Src &src, int n, const int32_t *maps, const int32_t *slot_off,
+                       const int32_t *slots, const int32_t *box4, const int32_t *filter, const double *radius,
+                       const int32_t *min_points, const int32_t *dilate_hs, const double *origin2, const double *resolution,
+                       const int32_t *out_hw, const double *inv, const int32_t *resize, const long long *out_off,
+                       int8_t *occ_out, long long total)
 {
     if (!ms)
         return SFE_ERR_ARG;
     sfe_ctx *ctx = ms->ctx;
     if (int rc = sfe_use(ctx))
         return rc;
+    const int32_t *pt_off = src.pt_off;
+    const double *xy = src.xy;
     SFE_ARG(ctx, n >= 0 && n <= 65535 && total >= 0 && (total == 0 || occ_out));
-    SFE_ARG(ctx, n == 0 || (maps && slot_off && box4 && pt_off && filter && radius && min_points && dilate_hs && origin2 &&
-                            resolution && out_hw && inv && resize && out_off));
+    SFE_ARG(ctx, n == 0 || (maps && slot_off && box4 && filter && radius && min_points && dilate_hs && origin2 && resolution &&
+                            out_hw && inv && resize && out_off));
+    SfeStoreView v = {};
+    if (src.store) {
+        SFE_ARG(ctx, sfe_store_ctx(src.store) == ctx && (n == 0 || (src.handles && src.all_frames && src.frame_off)));
+    } else {
+        SFE_ARG(ctx, n == 0 || pt_off);
+    }
     if (n == 0)
         return 0;
-    SFE_ARG(ctx, slot_off[0] == 0 && pt_off[0] == 0);
+    SFE_ARG(ctx, slot_off[0] == 0 && (src.store ? src.frame_off[0] == 0 : pt_off[0] == 0));
+    if (src.store)
+        if (int rc = sfe_store_view(src.store, &v))
+            return rc;
+    int64_t tot_pts = 0; // the store route's point table: mult / keep entries
     std::vector<Render2Job> jobs;
     std::vector<MarkJob> marks;
     std::vector<int64_t> mark_work; // the work image of each list, as an offset until the scratch is there
@@ -1558,7 +1659,7 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
     for (int b = 0; b < n; ++b) {
         SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps);
         SFE_ARG(ctx, slot_off[b + 1] >= slot_off[b] && (slot_off[b + 1] == slot_off[b] || slots));
-        SFE_ARG(ctx, pt_off[b + 1] >= pt_off[b] && (pt_off[b + 1] == pt_off[b] || xy));
+        SFE_ARG(ctx, src.store || (pt_off[b + 1] >= pt_off[b] && (pt_off[b + 1] == pt_off[b] || xy)));
         const SetMap &m = ms->maps[maps[b]];
         const int r0 = box4[4 * b], r1 = box4[4 * b + 1], c0 = box4[4 * b + 2], c1 = box4[4 * b + 3];
         Render2Job j;
@@ -1567,7 +1668,26 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
         SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && j.h > 0 && j.w > 0 && r1 < m.rows && c1 < m.cols);
         SFE_ARG(ctx, j.oh >= 0 && j.ow >= 0 && (j.resize ? j.inv > 0 : (j.oh == j.h && j.ow == j.w)));
         SFE_ARG(ctx, j.out_off >= 0 && j.out_off + (int64_t)j.oh * j.ow <= total);
-        j.pt_off = pt_off[b], j.n_pts = pt_off[b + 1] - pt_off[b];
+        j.pool_off = 0, j.frame_off = 0, j.n_frames = -1;
+        if (src.store) {
+            const int hd = src.handles[b];
+            if (hd < 0 || hd >= v.n_slots || v.cnt[hd] < 0)
+                return sfe_set_err(ctx, SFE_ERR_ARG, "map set render2: cloud %d named (job %d), the store holds %d%s", hd, b,
+                                   v.n_slots, (hd >= 0 && hd < v.n_slots) ? " and that one was not stored" : "");
+            SFE_ARG(ctx, src.frame_off[b + 1] >= src.frame_off[b] && (src.frame_off[b + 1] == src.frame_off[b] || src.frames));
+            if (!src.all_frames[b]) {
+                if (!v.d_key || hd >= v.n_keyed || !v.keyed[hd])
+                    return sfe_set_err(ctx, SFE_ERR_ARG, "map set render2: a frame list for cloud %d (job %d), which has no keys "
+                                       "(it was not built by a keyed entry point)", hd, b);
+                j.frame_off = src.frame_off[b], j.n_frames = src.frame_off[b + 1] - src.frame_off[b];
+            }
+            j.pool_off = v.off[hd];
+            j.pt_off = (int32_t)tot_pts, j.n_pts = v.cnt[hd];
+            tot_pts += j.n_pts;
+            SFE_ARG(ctx, tot_pts < (1 << 30));
+        } else {
+            j.pt_off = pt_off[b], j.n_pts = pt_off[b + 1] - pt_off[b];
+        }
         j.filter = filter[b] != 0, j.min_points = min_points[b], j.r2 = (float)(radius[b] * radius[b]);
         j.hs = dilate_hs[b];
         SFE_ARG(ctx, j.hs >= 0 && j.hs <= 4096 && resolution[b] > 0);
@@ -1605,7 +1725,7 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
         jobs.push_back(j);
     }
     SFE_ARG(ctx, marks.size() <= 65535 && work < (1LL << 40));
-    const int n_pts = pt_off[n];
+    const int n_pts = src.store ? (int)tot_pts : pt_off[n];
     const int64_t n16 = (work + 15) / 16;
     int8_t *d_work = (int8_t *)buf_get(ctx, ms->buf[16], (size_t)n16 * 16);
     int8_t *d_out = (int8_t *)buf_get(ctx, ms->buf[1], (size_t)(total ? total : 1));
@@ -1616,11 +1736,26 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
     const Render2Job *d_jobs = buf_stage(ctx, ms->buf[11], jobs);
     const MarkJob *d_marks = buf_stage(ctx, ms->buf[12], marks);
     const int32_t *d_spans = buf_stage(ctx, ms->buf[13], spans);
-    const double2 *d_xy = (const double2 *)buf_upload(ctx, ms->buf[14], xy, 2 * (size_t)n_pts);
-    float2 *d_xy32 = (float2 *)buf_get(ctx, ms->buf[15], (sizeof(float2) + 1) * (size_t)(n_pts ? n_pts : 1));
-    if (!d_jobs || !d_marks || !d_spans || !d_xy || !d_xy32)
-        return sfe_set_err(ctx, SFE_ERR_HIP, "map set render2: table / point upload failed");
-    uint8_t *d_keep = (uint8_t *)(d_xy32 + (n_pts ? n_pts : 1));
+    // the host route's points: float64, float32 + keep flags; the store route's: frame lists, multiplicities + keep flags
+    const double2 *d_xy = nullptr;
+    float2 *d_xy32 = nullptr;
+    const int32_t *d_frames = nullptr;
+    int32_t *d_mult = nullptr;
+    uint8_t *d_keep = nullptr;
+    if (src.store) {
+        const std::vector<int32_t> lists(src.frames, src.frames + (src.frames ? src.frame_off[n] : 0));
+        d_frames = buf_stage(ctx, ms->buf[17], lists);
+        d_mult = (int32_t *)buf_get(ctx, ms->buf[18], (sizeof(int32_t) + 1) * (size_t)(n_pts ? n_pts : 1));
+        if (!d_jobs || !d_marks || !d_spans || !d_frames || !d_mult)
+            return sfe_set_err(ctx, SFE_ERR_HIP, "map set render2: table upload failed");
+        d_keep = (uint8_t *)(d_mult + (n_pts ? n_pts : 1));
+    } else {
+        d_xy = (const double2 *)buf_upload(ctx, ms->buf[14], xy, 2 * (size_t)n_pts);
+        d_xy32 = (float2 *)buf_get(ctx, ms->buf[15], (sizeof(float2) + 1) * (size_t)(n_pts ? n_pts : 1));
+        if (!d_jobs || !d_marks || !d_spans || !d_xy || !d_xy32)
+            return sfe_set_err(ctx, SFE_ERR_HIP, "map set render2: table / point upload failed");
+        d_keep = (uint8_t *)(d_xy32 + (n_pts ? n_pts : 1));
+    }
     const auto blocks = [](int64_t items) { return (unsigned)std::min<int64_t>((items + MAP_THREADS - 1) / MAP_THREADS, 1 << 20); };
     hipLaunchKernelGGL(map2_fill_kernel, dim3(blocks(n16)), dim3(MAP_THREADS), 0, ctx->stream, (uint4 *)d_work, n16);
     SFE_LAUNCH_CHECK(ctx);
@@ -1630,16 +1765,28 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
         SFE_LAUNCH_CHECK(ctx);
     }
     if (n_pts) {
-        hipLaunchKernelGGL(map2_cast_kernel, dim3(blocks(n_pts)), dim3(MAP_THREADS), 0, ctx->stream, d_xy, n_pts, d_xy32,
-                           d_keep);
-        SFE_LAUNCH_CHECK(ctx);
-        if (any_filter) {
-            hipLaunchKernelGGL(map2_radius_count_kernel, dim3((unsigned)((max_pts + 255) / 256), (unsigned)n), dim3(256), 0,
-                               ctx->stream, d_jobs, (const float2 *)d_xy32, d_keep);
+        const dim3 rows((unsigned)((max_pts + 255) / 256), (unsigned)n); // a block per 256 points of every job's cloud
+        const float2 *d_pool = src.store ? (const float2 *)v.d_pool : nullptr;
+        if (src.store) {
+            hipLaunchKernelGGL(map2_select_kernel, rows, dim3(256), 0, ctx->stream, d_jobs, v.d_key, d_frames, d_mult, d_keep);
             SFE_LAUNCH_CHECK(ctx);
+            if (any_filter) {
+                hipLaunchKernelGGL(map2_radius_count_store_kernel, rows, dim3(256), 0, ctx->stream, d_jobs, d_pool,
+                                   (const int32_t *)d_mult, d_keep);
+                SFE_LAUNCH_CHECK(ctx);
+            }
+        } else {
+            hipLaunchKernelGGL(map2_cast_kernel, dim3(blocks(n_pts)), dim3(MAP_THREADS), 0, ctx->stream, d_xy, n_pts, d_xy32,
+                               d_keep);
+            SFE_LAUNCH_CHECK(ctx);
+            if (any_filter) {
+                hipLaunchKernelGGL(map2_radius_count_kernel, rows, dim3(256), 0, ctx->stream, d_jobs, (const float2 *)d_xy32,
+                                   d_keep);
+                SFE_LAUNCH_CHECK(ctx);
+            }
         }
         hipLaunchKernelGGL(map2_stamp_kernel, dim3(blocks(max_stamp), (unsigned)n), dim3(MAP_THREADS), 0, ctx->stream, d_jobs,
-                           d_xy, (const float2 *)d_xy32, (const uint8_t *)d_keep, d_spans, d_work);
+                           d_xy, (const float2 *)d_xy32, d_pool, (const uint8_t *)d_keep, d_spans, d_work);
         SFE_LAUNCH_CHECK(ctx);
     }
     if (max_out) {
@@ -1651,6 +1798,35 @@ int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t
     }
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (and xy may go away)
     return 0;
+}
+
+int sfe_mapset_render2(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot_off, const int32_t *slots,
+                       const int32_t *box4, const int32_t *pt_off, const double *xy, const int32_t *filter,
+                       const double *radius, const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
+                       const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
+                       const long long *out_off, int8_t *occ_out, long long total)
+{
+    Render2Src src;
+    src.pt_off = pt_off, src.xy = xy;
+    return set_render2(ms, src, n, maps, slot_off, slots, box4, filter, radius, min_points, dilate_hs, origin2, resolution,
+                       out_hw, inv, resize, out_off, occ_out, total);
+}
+
+// sfe_mapset_render2 with job b's points taken from cloud handles[b] of `store`, in place (sonarfe.h)
+int sfe_mapset_render2_store(sfe_mapset *ms, sfe_cloud_store *store, int n, const int32_t *maps, const int32_t *slot_off,
+                             const int32_t *slots, const int32_t *box4, const int32_t *handles, const int32_t *all_frames,
+                             const int32_t *frame_off, const int32_t *frames, const int32_t *filter, const double *radius,
+                             const int32_t *min_points, const int32_t *dilate_hs, const double *origin2,
+                             const double *resolution, const int32_t *out_hw, const double *inv, const int32_t *resize,
+                             const long long *out_off, int8_t *occ_out, long long total)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    SFE_ARG(ms->ctx, store);
+    Render2Src src;
+    src.store = store, src.handles = handles, src.all_frames = all_frames, src.frame_off = frame_off, src.frames = frames;
+    return set_render2(ms, src, n, maps, slot_off, slots, box4, filter, radius, min_points, dilate_hs, origin2, resolution,
+                       out_hw, inv, resize, out_off, occ_out, total);
 }
 
 int sfe_mapset_hit_table(sfe_mapset *ms, const float *bearings, int num_bearings, const double *breaks, const double *coef,
@@ -1924,6 +2100,20 @@ int sfe_map_render2(sfe_map *m, int n_slots, const int32_t *slots, int r0, int r
     const long long out_off = 0;
     return sfe_mapset_render2(one(m), 1, &map, slot_off, slots, box4, pt_off, xy, &f, &radius, &mp, &hs, origin2, &resolution,
                               out_hw, &inv, &rs, &out_off, occ_out, (long long)out_h * out_w);
+}
+
+int sfe_map_render2_store(sfe_map *m, sfe_cloud_store *store, int n_slots, const int32_t *slots, int r0, int r1, int c0, int c1,
+                          int handle, int all_frames, const int32_t *frames, int n_frames, int filter, double radius,
+                          int min_points, int dilate_hs, double y0, double x0, double resolution, int out_h, int out_w,
+                          double inv, int resize, int8_t *occ_out)
+{
+    const int32_t map = 0, slot_off[2] = {0, n_slots}, box4[4] = {r0, r1, c0, c1}, frame_off[2] = {0, n_frames};
+    const int32_t hd = handle, all = all_frames, f = filter, mp = min_points, hs = dilate_hs, out_hw[2] = {out_h, out_w};
+    const double origin2[2] = {y0, x0};
+    const long long out_off = 0;
+    return sfe_mapset_render2_store(one(m), store, 1, &map, slot_off, slots, box4, &hd, &all, frame_off, frames, &f, &radius,
+                                    &mp, &hs, origin2, &resolution, out_hw, &inv, &resize, &out_off, occ_out,
+                                    (long long)out_h * out_w);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

@@ -598,6 +598,9 @@ int sfe_store_view(sfe_cloud_store *s, SfeStoreView *v)
     v->off = s->off.data();
     v->cnt = s->cnt.data();
     v->n_slots = s->n_slots;
+    v->d_key = s->d_key;
+    v->keyed = s->keyed.data();
+    v->n_keyed = (int)std::min<size_t>(s->keyed.size(), (size_t)s->n_slots);
     return 0;
 }
 
@@ -818,6 +821,46 @@ int sfe_cloud_store_put(sfe_ctx *ctx, sfe_cloud_store *s, int64_t stamp, const f
     if (int rc = sfe_pinned_end(ctx, ctx->stream))
         return rc;
     return sfe_store_append_dev(s, &stamp, (const float *)(d + 16), (const int32_t *)d, 1, n, 0, handle_out);
+}
+
+// sfe_cloud_store_put with a key per point: a keyed slot, as get_points_keys leaves one
+int sfe_cloud_store_put_keys(sfe_ctx *ctx, sfe_cloud_store *s, int64_t stamp, const float *pts, const int32_t *keys, int n,
+                             int32_t *handle_out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, s && s->ctx == ctx && n >= 0 && (n == 0 || (pts && keys)) && handle_out);
+    for (int i = 0; i < n; ++i)
+        if (keys[i] < 0)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "cloud store: put_keys: key %d of point %d is negative", keys[i], i);
+    if (int rc = store_key_pool(s))
+        return rc;
+    // [count | points | keys] through the event-guarded pinned staging: enqueue only
+    const size_t b_pts = sizeof(float) * 2 * (size_t)n, bytes = 16 + b_pts + sizeof(int32_t) * (size_t)n;
+    char *h = (char *)sfe_pinned_begin(ctx, bytes);
+    char *d = (char *)sfe_scratch(ctx, 47, bytes);
+    if (!h || !d)
+        return SFE_ERR_HIP;
+    *(int32_t *)h = n;
+    if (n) {
+        memcpy(h + 16, pts, b_pts);
+        memcpy(h + 16 + b_pts, keys, sizeof(int32_t) * (size_t)n);
+    }
+    SFE_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = sfe_pinned_end(ctx, ctx->stream))
+        return rc;
+    const int first = s->n_slots;
+    if (int rc = sfe_store_append_dev(s, &stamp, (const float *)(d + 16), (const int32_t *)d, 1, n, 0, handle_out))
+        return rc;
+    if (n) {
+        hipLaunchKernelGGL(store_commit_keys_kernel, dim3(64, 1), dim3(256), 0, ctx->stream, (const int32_t *)(d + 16 + b_pts), n,
+                           (const int64_t *)s->d_off, (const int32_t *)s->d_cnt, first, s->d_key);
+        SFE_LAUNCH_CHECK(ctx);
+    }
+    if ((int32_t)s->keyed.size() < s->n_slots)
+        s->keyed.resize((size_t)s->n_slots, 0);
+    s->keyed[(size_t)first] = 1;
+    return 0;
 }
 
 int sfe_cloud_store_count(sfe_cloud_store *s) { return s ? s->n_slots : 0; }

@@ -636,6 +636,29 @@ class Mapping(object):
             float(self.resolution), oh, ow, inv, resize, occ.ctypes.data_as(C.POINTER(C.c_int8))))
         return self._grid_msg(box, resolution, occ, origin)
 
+    def get_occupancy_grid2_store(self, store, handle, frames=None, resolution=None):
+        """``get_occupancy_grid2(frames, resolution)`` with ``point_cloud = np.c_[store.read(handle), 0,
+        store.read_keys(handle)].astype(np.float32)``, without the cloud leaving the device: the selection by ``frames``
+        (``select_points``' multiset), the outlier filter and the projection read cloud ``handle`` of ``store`` (a CloudStore
+        of this map's context) where it lies.  The cloud is a keyed one -- ``FrontEnd.slam_cloud()``,
+        ``store.get_points_keys(...)`` or ``store.put_keys(...)`` -- or, with ``frames=None``, any cloud.  ``point_cloud`` is
+        neither read nor set.  A dead handle, or a frame list for a cloud without keys, raises SonarFEError; nothing
+        changes then."""
+        what = "Mapping.get_occupancy_grid2_store"
+        self._check_method2(what, ())
+        if getattr(store, "ctx", None) is not self.ctx:
+            raise ValueError("%s: the store belongs to another context" % what)
+        slots, box, origin, (oh, ow), inv, resize, resolution = self._render2_plan(frames, resolution)
+        listed = frame_list(frames)
+        occ = np.zeros((oh, ow), np.int8)
+        self._check(self._lib.sfe_map_render2_store(
+            self._h, store.handle, len(slots), _L.ptr(slots, C.c_int32), box[0], box[1], box[2], box[3], int(handle), int(frames is None),
+            _L.ptr(listed if len(listed) else np.zeros(1, np.int32), C.c_int32), len(listed),
+            int(self.outlier_filter_min_points > 1), float(self.outlier_filter_radius), int(self.outlier_filter_min_points),
+            self.dilate_size // 2, origin[0], origin[1], float(self.resolution), oh, ow, inv, resize,
+            occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return self._grid_msg(box, resolution, occ, origin)
+
     def get_occupancy_grid(self, frames=None, resolution=None):
         if self.pub_occupancy1:
             return self.get_occupancy_grid1(frames, resolution)
@@ -745,6 +768,17 @@ def select_points(point_cloud, frames):
             points.append(point_cloud[keys == k, :2])
         points = np.concatenate(points)
     return points
+
+
+def frame_list(frames):
+    """`frames` as the device's selection reads it: int32, in list order, repeats kept.  The stored keys are integers in
+    [0, 2^31), so an entry that is none (negative, too large, not a whole number) selects nothing, as in select_points'
+    comparison; it becomes -1, which no key equals."""
+    out = []
+    for k in (() if frames is None else frames):
+        whole = isinstance(k, (int, np.integer)) or (isinstance(k, (float, np.floating)) and np.isfinite(k) and k == int(k))
+        out.append(int(k) if whole and 0 <= int(k) < 2 ** 31 else -1)
+    return np.array(out, np.int32)
 
 
 # ---- what Mapping and MapBatch hand the measurement ------------------------------------------------------------------------
@@ -987,6 +1021,9 @@ class _SessionMap(Mapping):
     def get_occupancy_grid2(self, frames=None, resolution=None):
         return self._b.get_occupancy_grid2([self._s], frames, resolution)[0]
 
+    def get_occupancy_grid2_store(self, store, handle, frames=None, resolution=None):
+        return self._b.get_occupancy_grid2_store(store, [handle], [self._s], frames, resolution)[0]
+
 
 class MapBatch(object):
     """S occupancy maps that advance together: every stage of Mapping as one device call over the listed sessions
@@ -1085,6 +1122,46 @@ class MapBatch(object):
             self._h, n, _L.ptr(i32(sessions), C.c_int32), _L.ptr(off([len(p[0]) for p in plans]), C.c_int32),
             _L.ptr(slots, C.c_int32), _L.ptr(i32([p[1] for p in plans]), C.c_int32),
             _L.ptr(off([len(p) for p in points]), C.c_int32), _L.ptr(np.ascontiguousarray(xy), C.c_double),
+            _L.ptr(i32([v.outlier_filter_min_points > 1 for v in views]), C.c_int32),
+            _L.ptr(f64([v.outlier_filter_radius for v in views]), C.c_double),
+            _L.ptr(i32([v.outlier_filter_min_points for v in views]), C.c_int32),
+            _L.ptr(i32([v.dilate_size // 2 for v in views]), C.c_int32), _L.ptr(f64([p[2] for p in plans]), C.c_double),
+            _L.ptr(f64([v.resolution for v in views]), C.c_double), _L.ptr(i32([p[3] for p in plans]), C.c_int32),
+            _L.ptr(f64([p[4] for p in plans]), C.c_double), _L.ptr(i32([p[5] for p in plans]), C.c_int32),
+            out_off.ctypes.data_as(C.POINTER(C.c_longlong)), occ.ctypes.data_as(C.POINTER(C.c_int8)), int(out_off[-1])))
+        return [v._grid_msg(p[1], p[6], occ[out_off[j]:out_off[j + 1]].reshape(p[3]).copy(), p[2])
+                for j, (v, p) in enumerate(zip(views, plans))]
+
+    def get_occupancy_grid2_store(self, store, handles, sessions=None, frames=None, resolution=None):
+        """maps[s].get_occupancy_grid2_store(store, handles[i], frames, resolution) for s = sessions[i] (all sessions by
+        default) -> list of OccupancyGrid, rendered in one device call from the clouds where they lie in ``store`` (a
+        CloudStore of this batch's context): ``SessionBatch.slam_clouds()``' handles, or any keyed clouds."""
+        what = "get_occupancy_grid2_store"
+        if self._h is None:
+            raise NotImplementedError("MapBatch.%s: get_occupancy_grid2 is not implemented for a batch that was never "
+                                      "configured: configure() first" % what)
+        handles = [int(h) for h in np.asarray(handles).reshape(-1)]
+        sessions = self._listed(what, range(self.S) if sessions is None else sessions, handles)
+        views = [self.maps[s] for s in sessions]
+        for s, v in zip(sessions, views):
+            v._check_method2("MapBatch.%s (session %d)" % (what, s), ())
+        if getattr(store, "ctx", None) is not self.ctx:
+            raise ValueError("MapBatch.%s: the store belongs to another context" % what)
+        plans = [v._render2_plan(frames, resolution) for v in views]
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32).reshape(-1))
+        f64 = lambda a: np.ascontiguousarray(np.array(a, np.float64).reshape(-1))
+        off = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+        slots = np.concatenate([p[0] for p in plans]).astype(np.int32)
+        listed = frame_list(frames)
+        n = len(sessions)
+        lists = np.ascontiguousarray(np.tile(listed, n)) if len(listed) else np.zeros(1, np.int32)
+        out_off = np.zeros(n + 1, np.int64)
+        out_off[1:] = np.cumsum([p[3][0] * p[3][1] for p in plans])
+        occ = np.zeros(max(1, int(out_off[-1])), np.int8)
+        self._check(self._lib.sfe_mapset_render2_store(
+            self._h, store.handle, n, _L.ptr(i32(sessions), C.c_int32), _L.ptr(off([len(p[0]) for p in plans]), C.c_int32),
+            _L.ptr(slots, C.c_int32), _L.ptr(i32([p[1] for p in plans]), C.c_int32), _L.ptr(i32(handles), C.c_int32),
+            _L.ptr(i32([frames is None] * n), C.c_int32), _L.ptr(off([len(listed)] * n), C.c_int32), _L.ptr(lists, C.c_int32),
             _L.ptr(i32([v.outlier_filter_min_points > 1 for v in views]), C.c_int32),
             _L.ptr(f64([v.outlier_filter_radius for v in views]), C.c_double),
             _L.ptr(i32([v.outlier_filter_min_points for v in views]), C.c_int32),

@@ -527,6 +527,35 @@ class FrontEnd(object):
         all_points = np.concatenate(all_points)
         return pcl.downsample(all_points[:, :2], all_points[:, (2,)], self.point_resolution)
 
+    def slam_cloud(self):
+        """the cloud ``publish_point_cloud`` publishes (slam_ros.py:317-359): every keyframe's points under its current pose,
+        tagged with its key, through ``pcl.downsample(points, keys, point_resolution)``.  With a store: a keyed CloudRef, a
+        new slot that the caller drops with ``store.truncate(ref.handle)`` (its keys: ``store.read_keys``).  Without one: the
+        (N, 4) float32 array x, y, 0, key."""
+        points, keys = self.get_points_keys(range(len(self.keyframes)))
+        if self.store is not None:
+            return points
+        keys = np.asarray(keys).reshape(-1, 1)
+        return np.c_[points, np.zeros_like(keys), keys].astype(np.float32).reshape(-1, 4)
+
+    def occupancy_grid2(self, frames=None, resolution=None):
+        """``self.map.get_occupancy_grid2(frames, resolution)`` of the SLAM cloud, which never leaves the device: the cloud
+        is built in the store (``slam_cloud``), rendered from there (``Mapping.get_occupancy_grid2_store``) and dropped
+        again.  Needs ``mapping=dict(...)`` with ``pub_occupancy2`` on, and a store."""
+        if self.map is None:
+            raise RuntimeError("FrontEnd.occupancy_grid2: the front end owns no map: construct it with mapping=dict(ping=...)")
+        if not self.map.pub_occupancy2:
+            raise RuntimeError("FrontEnd.occupancy_grid2: the map was configured with pub_occupancy2=False")
+        if self.store is None:
+            raise RuntimeError("FrontEnd.occupancy_grid2: the front end has no store: the SLAM cloud is built in one "
+                               "(construct it with store=CloudStore(...))")
+        n_slots = len(self.store)
+        try:
+            cloud = self.slam_cloud()
+            return self.map.get_occupancy_grid2_store(self.store, cloud.handle, frames, resolution)
+        finally:
+            self.store.truncate(n_slots)
+
     def _fov_bounds(self, source_frames):
         return fov_bounds([self.keyframes[f].pose for f in source_frames], [self.keyframes[f].cov for f in source_frames],
                           self.oculus_max_range, self.oculus_horizontal_aperture)

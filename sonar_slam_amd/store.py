@@ -45,6 +45,24 @@ class CloudStore(object):
                                                              _L.ptr(pts, _C.c_float), len(pts), _C.byref(h)))
         return h.value
 
+    def put_keys(self, points, keys, stamp=0):
+        """``put`` with a key per point (integers in [0, 2^31)): a keyed cloud, as ``get_points_keys`` leaves one -> handle.
+        For a cloud that arrives already keyed, such as the SLAM cloud a mapping node receives: ``put_keys(cloud[:, :2],
+        cloud[:, 3])``; ``read_keys`` reads the keys back."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+        wide = np.asarray(keys).reshape(-1)
+        if len(wide) != len(pts):
+            raise ValueError("CloudStore.put_keys: %d points but %d keys" % (len(pts), len(wide)))
+        if len(wide) and not (np.all(wide >= 0) and np.all(wide < 2 ** 31) and np.all(wide == np.floor(wide))):
+            raise ValueError("CloudStore.put_keys: keys must be integers in [0, 2^31)")
+        ks = np.ascontiguousarray(wide, np.int32)
+        h = _C.c_int32(-1)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store_put_keys(self.ctx.handle, self.handle, int(stamp),
+                                                                  _L.ptr(pts, _C.c_float), _L.ptr(ks, _C.c_int32), len(pts),
+                                                                  _C.byref(h)))
+        return h.value
+
     def put_batch_dev(self, d_clouds, d_counts, n_frames, cap, stamps=None, flags=0):
         """n_frames clouds straight from the resident cloud filter's outputs (device buffers) -> handles"""
         handles = np.zeros(n_frames, np.int32)

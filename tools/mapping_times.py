@@ -45,10 +45,20 @@ off, and -- with `--sessions S` > 0 -- a MapBatch of S such sessions (session s 
                          for one of them
   images_equal           the device images equal the restatement's
 
+With `--method 2 --feed store` the store route of method 2 is timed next to the host route, under "method2_store": the
+same map, its keyed SLAM cloud in a CloudStore (put_keys), both routes in this process, alternated call by call, the median
+of `--reps` repetitions (`--feed host`: the host leg alone):
+  host                   what a caller has to do today: store.read + store.read_keys, the (N, 4) cloud, select_points on the
+                         host, get_occupancy_grid2 (upload of float64 pairs, render, read-back)
+  store                  get_occupancy_grid2_store: the cloud stays where it is
+  lockstep               with `--sessions S` > 0: one MapBatch call for all S sessions by each route
+  images_equal           both routes give the same images
+
     python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
     python tools/mapping_times.py --sessions 32 --feed store
     python tools/mapping_times.py --feed store --batch-keyframes 200
     python tools/mapping_times.py --method 2 --sessions 32
+    python tools/mapping_times.py --method 2 --feed store --sessions 32
 """
 import argparse
 import json
@@ -311,6 +321,93 @@ def method2(ctx, ping, settings, S, K, reps):
     return out
 
 
+def method2_store(ctx, ping, settings, S, K, reps, routes):
+    """get_occupancy_grid2 of a cloud that lies in a CloudStore, by the host route and the store route -> the "method2_store"
+    record"""
+    from sonar_slam_amd.store import CloudStore
+    poses, clouds = session(K)
+
+    def keyed(shift):
+        parts = []
+        for k, ((x, y, th), pts) in enumerate(zip(poses, clouds)):
+            c, s = np.cos(th), np.sin(th)
+            g = np.c_[c * pts[:, 0] - s * pts[:, 1] + x + shift, s * pts[:, 0] + c * pts[:, 1] + y]
+            parts.append(np.c_[g, np.zeros(len(g)), np.full(len(g), float(k))])
+        return np.concatenate(parts).astype(np.float32)
+
+    def read_back(h):
+        pts = store.read(h)
+        return np.c_[pts, np.zeros(len(pts)), store.read_keys(h)].astype(np.float32)
+    settings = dict(settings, pub_occupancy1=False)
+    store = CloudStore(ctx, capacity_points=(max(S, 0) + 1) * K * 320, max_clouds=max(S, 0) + 2)
+    m = Mapping(ctx)
+    for k, v in settings.items():
+        setattr(m, k, v)
+    m.configure()
+    cloud = keyed(0.0)
+    for k in range(K):
+        m.add_keyframe(k, Pose2(*poses[k]), ping, cloud)
+    handle = store.put_keys(cloud[:, :2], cloud[:, 3])
+    queries = {"all": dict(), "last10_coarse": dict(frames=list(range(max(0, K - 10), K)), resolution=0.5)}
+    med = lambda v: float(np.median(v))
+    out = {"keyframes": K, "points": len(cloud), "reps": reps, "routes": list(routes), "get_occupancy_grid2_ms": {}}
+    equal = True
+
+    def alternate(legs):
+        """-> ({route: times without the first round}, {route: last result})"""
+        times, last = {r: [] for r in legs}, {}
+        names = list(legs)
+        for rep in range(reps + 1):
+            for r in names[rep % len(names):] + names[:rep % len(names)]:
+                t = time.perf_counter()
+                last[r] = legs[r]()
+                if rep:             # the first call grows the scratch
+                    times[r].append((time.perf_counter() - t) * 1e3)
+        return times, last
+
+    def one_host(kw):
+        m.point_cloud = read_back(handle)
+        return m.get_occupancy_grid2(**kw)
+    for name, kw in queries.items():
+        legs = {"host": lambda: one_host(kw), "store": lambda: m.get_occupancy_grid2_store(store, handle, **kw)}
+        times, last = alternate({r: legs[r] for r in routes})
+        if len(routes) == 2:
+            equal = equal and np.array_equal(last["host"].occ, last["store"].occ)
+        rec = {r: med(times[r]) for r in routes}
+        rec.update({r + "_min": float(np.min(times[r])) for r in routes})
+        rec["image"] = list(last[routes[0]].occ.shape)
+        if len(routes) == 2:
+            rec["host_over_store"] = rec["host"] / rec["store"]
+        out["get_occupancy_grid2_ms"][name] = rec
+    if S > 0:
+        batch = MapBatch(ctx, S, K, **settings)
+        batch.configure()
+        sessions = list(range(S))
+        shifted = [keyed(float(s)) for s in sessions]
+        for k in range(K):
+            batch.add_keyframes(sessions, [k] * S, [Pose2(poses[k][0] + s, poses[k][1], poses[k][2]) for s in sessions], ping,
+                                shifted)
+        handles = [store.put_keys(c[:, :2], c[:, 3]) for c in shifted]
+        out["lockstep"] = {"sessions": S}
+        for name, kw in queries.items():
+            legs = {"host": lambda: batch.get_occupancy_grid2(point_clouds=[read_back(h) for h in handles], **kw),
+                    "store": lambda: batch.get_occupancy_grid2_store(store, handles, **kw)}
+            times, last = alternate({r: legs[r] for r in routes})
+            if len(routes) == 2:
+                equal = equal and all(np.array_equal(a.occ, b.occ) for a, b in zip(last["host"], last["store"]))
+            rec = {r: med(times[r]) for r in routes}
+            rec.update({r + "_min": float(np.min(times[r])) for r in routes})
+            if len(routes) == 2:
+                rec["host_over_store"] = rec["host"] / rec["store"]
+            out["lockstep"][name] = rec
+        batch.close()
+    if len(routes) == 2:
+        out["images_equal"] = bool(equal)
+    m.close()
+    store.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
@@ -324,6 +421,12 @@ def main():
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
     settings = dict(x0=-100.0, y0=-100.0, width=200.0, height=200.0)
+    if a.method == 2 and a.feed is not None:
+        ctx = _lib.default_context()
+        routes = ("host", "store") if a.feed == "store" else ("host",)
+        print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
+                          "method2_store": method2_store(ctx, ping, settings, a.sessions or 0, a.batch_keyframes, a.reps, routes)}))
+        return
     if a.method == 2:
         ctx = _lib.default_context()
         print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
