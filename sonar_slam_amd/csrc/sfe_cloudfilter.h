@@ -60,3 +60,4 @@ struct CfBBox {
     int n;                    // stored points (the frame's count clamped to the capacity)
 };
 #define CF_SLOT_BBOX 63
+#define CF_SLOT_PROF 24 // sfe_cf_get_profile: phase stamps of the downsample kernel's profile build

@@ -273,6 +273,86 @@ __device__ __forceinline__ int cf_block_excl_scan(int v, int *s_tmp, int *total)
     return incl - v + s_tmp[wave];
 }
 
+// pcl.remove_outlier: keep a point iff more than min_points points (itself included) lie within the
+// radius; order preserved.  One workgroup per frame: counts (cloud tiled through LDS), scan, gather.
+//
+// Fast path for clouds that come out of the downsample (one medoid per octree leaf, in path = Morton order, leaf
+// keys kept): the leaves are grouped into the cells of the coarsest tree level whose cells are still at least
+// one radius wide (at most level CF_CELL_LEVELS), a cell is a contiguous run of the sorted cloud, and a point
+// only counts the points of the 3 x 3 cells around its own -- every point within the radius lies in one of them.
+// The same float distance test on a superset of the points that can pass it: identical counts, ~75 tests per
+// point instead of ~2500.
+#define CF_CELL_LEVELS 6
+#define CF_CELL_PTS 8192 // points the fast path holds in LDS
+__device__ __forceinline__ unsigned cf_spread(unsigned v) // bit i -> bit 2i (6 bits)
+{
+    v = (v | (v << 4)) & 0x30Fu;
+    v = (v | (v << 2)) & 0x333u;
+    v = (v | (v << 1)) & 0x555u;
+    return v;
+}
+__device__ __forceinline__ unsigned cf_squeeze(unsigned v) // bit 2i -> bit i
+{
+    v &= 0x555u;
+    v = (v | (v >> 1)) & 0x333u;
+    v = (v | (v >> 2)) & 0x30Fu;
+    v = (v | (v >> 4)) & 0x03Fu;
+    return v;
+}
+
+// cell level of the fast path: the deepest level (<= CF_CELL_LEVELS, <= the tree's depth) whose cells are >= radius * 1.001
+// wide; -1 = none (a radius wider than the root cell, a zero radius, NaN): brute force
+__device__ __forceinline__ int cf_cell_level(float root_radius, int zlev, float r2)
+{
+    int lc = -1;
+    const float need = sqrtf(r2) * 1.001f; // the margin dwarfs the rounding of the tree's cell boundaries
+    float width = root_radius * 2.0f;      // level 0 = the root cell
+    if (need > 0.0f && width >= need) {    // (NaN -> brute force)
+        lc = 0;
+        while (lc < CF_CELL_LEVELS && lc < zlev && width * 0.5f >= need) {
+            width *= 0.5f;
+            ++lc;
+        }
+    }
+    return lc;
+}
+// cell starts of a cloud in path order (c_start[0 .. ncell], preset to n by the caller, barrier behind the preset): leaf
+// i, in cell c, whose predecessor lies in cell cp.  The first leaf of a cell writes its index as the cell's start AND
+// as the start of the empty cells between the previous occupied cell and its own ("the next occupied cell's start":
+// starts grow with the cell index).  Round 6: one barrier instead of the 2 log2(ncell) of a suffix-minimum sweep over
+// the cells (24 at the deepest level).
+__device__ __forceinline__ void cf_cell_starts(unsigned short *c_start, int i, unsigned c, unsigned cp)
+{
+    if (cp != c)
+        for (unsigned cc = cp + 1u; cc <= c; ++cc) // (cp + 1 wraps to 0 for the first leaf: the cells in front of it)
+            c_start[cc] = (unsigned short)i;
+}
+// points of the 3 x 3 cells around cell ck (level lc) that lie within the radius of p
+__device__ __forceinline__ int cf_cell_count(float2 p, unsigned ck, int lc, const float2 *c_p, const unsigned short *c_start,
+                                             float r2)
+{
+    int cnt = 0;
+    const int ix = (int)cf_squeeze(ck), iy = (int)cf_squeeze(ck >> 1), side = 1 << lc;
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int cy = iy + dy;
+        if (cy < 0 || cy >= side)
+            continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int cx = ix + dx;
+            if (cx < 0 || cx >= side)
+                continue;
+            const unsigned m = cf_spread((unsigned)cx) | (cf_spread((unsigned)cy) << 1);
+            const int j1 = c_start[m + 1];
+            for (int j = c_start[m]; j < j1; ++j) {
+                const float2 t = c_p[j];
+                const float ddx = __fadd_rn(p.x, -t.x), ddy = __fadd_rn(p.y, -t.y);
+                cnt += __fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)) <= r2;
+            }
+        }
+    }
+    return cnt;
+}
+
 // The same downsample for trees of <= 8 levels (16 path-key bits: every sonar fan at the shipped 0.5 m), with the stable
 // sort done as an LSD radix sort of the point INDICES in LDS instead of a bitonic sort of (key << 16 | index): the
 // bitonic network is 105 stages with a workgroup barrier each for 16384 slots; this is two passes of 8 key bits with
@@ -300,31 +380,72 @@ __device__ __forceinline__ int cf_block_excl_scan(int v, int *s_tmp, int *total)
 #define CF_RDX_CHUNK 17
 #define CF_RDX_CHUNK_BIG 19
 #define CF_LDS_PTS_BIG (CF_RDX_CHUNK_BIG * 1024)
-template <int CHUNK>
+//
+// The tail: pcl.remove_outlier of the frame's own downsampled cloud, in the same workgroup.  At its end the kernel holds
+// everything cf_radius_filter_kernel would reload from HBM a moment later -- the medoids in leaf = Morton order and, through
+// them, the leaf keys (a medoid is a point of its leaf: its path key IS the leaf's) -- and LDS the sorted points no longer
+// need.  The medoids of a round of 1024 leaves go to LDS slots [round * 1024, ...), in place: every leaf of a later round
+// starts at or behind its own index, so the slots are dead once the round's reads are behind a barrier.  Cell level,
+// cell starts, 3 x 3 counts, scan and compaction are cf_radius_filter_kernel's cell path (the same device functions).
+// tail.mode: CF_TAIL_NONE = the downsampled cloud goes to ds_out for a later kernel (what rounds 2-6 did);
+// CF_TAIL_COPY = min_points <= 1, the medoids ARE the output; CF_TAIL_FILTER = the outlier filter.  A frame the tail cannot
+// take -- handed to another downsample launch, no cell level for this radius (brute force), more than CF_CELL_PTS leaves,
+// cloud + cell starts beyond the launch's LDS -- is written as under CF_TAIL_NONE and appended to tail.list, over which
+// cf_radius_filter_kernel strides afterwards.
+// PROF: workgroup 0 stamps clock64() at its phase ends into tail.prof (tools/filter_phases.py); off in the shipped build.
+#define CF_TAIL_NONE 0
+#define CF_TAIL_COPY 1
+#define CF_TAIL_FILTER 2
+#define CF_PROF_N 16 // stamps: 0 start, 1 keys, 2..5 sort passes, 6 leaf scan + starts, 7 point gather, 8 medoids, 9 radius filter
+struct CfTail {
+    int mode;
+    float r2;
+    int min_points;
+    float2 *out;         // [frame][cap]: the filtered clouds
+    int32_t *out_counts; // [frame]
+    int *list, *n_list;  // frames left to cf_radius_filter_kernel
+    long long *prof;     // PROF builds: CF_PROF_N stamps of workgroup 0
+};
+template <int CHUNK, bool PROF>
 __global__ __launch_bounds__(1024) void cf_downsample_radix_kernel(const float2 *__restrict__ p32, long long cap,
                                                                    CfHeader *__restrict__ hdrs, float2 *__restrict__ ds_out,
                                                                    int *__restrict__ seg_all, int n2cap,
                                                                    unsigned *__restrict__ leaf_keys_all,
                                                                    float2 *__restrict__ spts_all, int lds_bytes, int sort_cols,
-                                                                   int *marked, int *n_marked)
+                                                                   int *marked, int *n_marked, const CfTail tail)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[]; // ids[2][n2cap], key[n2cap], cnt[16][sort_cols]: u16
     __shared__ int s_scan[1024];
     const int f = blockIdx.x, tid = threadIdx.x;
+#define CF_STAMP(k)                                                                                                    \
+    do {                                                                                                               \
+        if (PROF && blockIdx.x == 0 && threadIdx.x == 0)                                                               \
+            tail.prof[k] = clock64();                                                                                  \
+    } while (0)
+    CF_STAMP(0);
     const CfHeader h = hdrs[f];
     const int n = h.n;
     const float2 *pts = p32 + (size_t)f * cap;
     float2 *out = ds_out + (size_t)f * cap;
-    if (n == 0)
+    if (n == 0) {
+        if (tail.mode != CF_TAIL_NONE && tid == 0)
+            tail.out_counts[f] = 0; // (n_out is 0 from the header's birth)
         return;
+    }
     if (n > n2cap) { // more points than the LDS of this launch holds: the HBM-scratch sort launched last takes the frame
-        if (tid == 0)
+        if (tid == 0) {
             cf_mark_global(hdrs, f, marked, n_marked);
+            if (tail.mode != CF_TAIL_NONE)
+                tail.list[atomicAdd(tail.n_list, 1)] = f;
+        }
         return;
     }
     if (2 * h.levels > 16) { // deeper tree: the 64-bit bitonic instantiation launched behind takes the frame
-        if (tid == 0)
+        if (tid == 0) {
             hdrs[f].n_seg = CF_NEEDS_WIDE;
+            if (tail.mode != CF_TAIL_NONE)
+                tail.list[atomicAdd(tail.n_list, 1)] = f;
+        }
         return;
     }
     unsigned short *idA = reinterpret_cast<unsigned short *>(lds_raw);
@@ -335,6 +456,7 @@ __global__ __launch_bounds__(1024) void cf_downsample_radix_kernel(const float2 
         idA[i] = (unsigned short)i;
         skey[i] = (unsigned short)cf_path_key(pts[i], h);
     }
+    CF_STAMP(1);
     // a column's chunk of the current order: m consecutive positions, m odd so that the columns' 16-bit reads spread
     // over the LDS banks (sort_cols = 1024, or 512 for capacities of <= 8192 points, whose LDS share is 64 KB)
     const int m = ((n + sort_cols - 1) / sort_cols) | 1;
@@ -406,19 +528,31 @@ __global__ __launch_bounds__(1024) void cf_downsample_radix_kernel(const float2 
         unsigned short *t_ = idA;
         idA = idB;
         idB = t_;
+        CF_STAMP(2 + pass);
     }
     __syncthreads();
     // leaf starts: positions whose key differs from the previous one (block scan over per-thread chunks)
     const int per = (n + 1023) / 1024;
     const int b0 = tid * per, e0 = min(b0 + per, n);
     int c = 0;
+    unsigned starts = 0; // bit k: position b0 + k starts a leaf (per <= CHUNK: n <= CHUNK * 1024)
     {
-        unsigned prev = (b0 > 0 && b0 < n) ? skey[idA[b0 - 1]] : 0u;
-        for (int r = b0; r < e0; ++r) {
-            const unsigned k = skey[idA[r]];
-            c += (r == 0) || (k != prev);
-            prev = k;
-        }
+        unsigned idv[CHUNK], kv[CHUNK];
+        const unsigned idp = (b0 > 0 && b0 < n) ? idA[b0 - 1] : 0u;
+#pragma unroll
+        for (int k = 0; k < CHUNK; ++k)
+            idv[k] = b0 + k < e0 ? idA[b0 + k] : 0u;
+        unsigned prev = (b0 > 0 && b0 < n) ? skey[idp] : 0u;
+#pragma unroll
+        for (int k = 0; k < CHUNK; ++k)
+            kv[k] = b0 + k < e0 ? skey[idv[k]] : 0u;
+#pragma unroll
+        for (int k = 0; k < CHUNK; ++k)
+            if (b0 + k < e0) {
+                starts |= (unsigned)((b0 + k == 0) || (kv[k] != prev)) << k;
+                prev = kv[k];
+            }
+        c = __popc(starts);
     }
     int n_seg;
     const int seg_base = cf_block_excl_scan(c, s_scan, &n_seg);
@@ -432,21 +566,27 @@ __global__ __launch_bounds__(1024) void cf_downsample_radix_kernel(const float2 
     const bool in_lds = (size_t)n * sizeof(float2) <= (size_t)lds_bytes;
     {
         int sidx = seg_base;
-        unsigned prev = (b0 > 0 && b0 < n) ? skey[idA[b0 - 1]] : 0u;
-        for (int r = b0; r < e0; ++r) {
-            const unsigned k = skey[idA[r]];
-            if ((r == 0) || (k != prev))
-                s_seg[sidx++] = r;
-            prev = k;
-        }
+#pragma unroll
+        for (int k = 0; k < CHUNK; ++k)
+            if ((starts >> k) & 1u)
+                s_seg[sidx++] = b0 + k;
     }
     if (tid == 0)
         s_seg[n_seg] = n;
+    // the tail's route for this frame (uniform over the workgroup)
+    const int lc = tail.mode == CF_TAIL_FILTER ? cf_cell_level(h.radius, h.levels, tail.r2) : -1;
+    const int ncell = 1 << (2 * max(lc, 0));
+    const bool tail_filter = tail.mode == CF_TAIL_FILTER && lc >= 0 && n_seg <= CF_CELL_PTS && // (cloud + cell starts + cells)
+                             (sizeof(float2) + sizeof(unsigned short)) * (size_t)n_seg +
+                                     sizeof(unsigned short) * (size_t)(ncell + 2) <= (size_t)lds_bytes;
+    const bool tail_copy = tail.mode == CF_TAIL_COPY;
+    const bool keep_ds = !tail_filter && !tail_copy; // the downsampled cloud and its leaf keys go to HBM for a later kernel
     __syncthreads(); // same workgroup: its own stores are visible to it after the barrier
-    if (leaf_keys_all) { // the leaves' paths (= Morton codes) while the keys are still there
+    if (leaf_keys_all && keep_ds) { // the leaves' paths (= Morton codes) while the keys are still there
         for (int sg = tid; sg < n_seg; sg += 1024)
             leaf_keys_all[(size_t)f * cap + sg] = (unsigned)skey[idA[s_seg[sg]]];
     }
+    CF_STAMP(6);
     {
         constexpr int NV = CHUNK == CF_RDX_CHUNK ? 16 : CHUNK; // n <= 16384, or <= CHUNK * 1024 in the build for larger capacities
         float2 v[NV];
@@ -465,84 +605,218 @@ __global__ __launch_bounds__(1024) void cf_downsample_radix_kernel(const float2 
         }
     }
     __syncthreads(); // same workgroup: its own stores (LDS or HBM) are visible to it after the barrier
-    // one thread per leaf: float centroid in original order, first point at minimum distance
-    auto medoids = [&](const auto *spts) {
+    CF_STAMP(7);
+    float2 *c_p = reinterpret_cast<float2 *>(lds_raw); // tail_filter: the downsampled cloud
+    float2 *fout = tail.out + (size_t)f * cap;
+    // Medoids: float centroid in original order, first point at minimum distance.  A lane per leaf keeps one lane in eight
+    // busy (median leaf 2 points, longest of a wave's 64 leaves 40-90), and the distances -- a correctly rounded sqrtf each --
+    // are nine tenths of the instructions.  Where the LDS has room for a centroid and a winner per leaf behind the sorted
+    // points (par), only the centroid's chain stays a lane per leaf; the distances are dealt to the lanes by POINTS: every
+    // thread takes the chunk of consecutive positions it scanned for leaf starts above (it knows their leaves from
+    // `starts` and seg_base), keeps the first minimum of each leaf's run in its chunk and hands it in by an atomic minimum
+    // over (distance bits, position) -- distances are >= +0, so their bits order like the floats; the minimum of the pairs
+    // is the first point at the minimum distance, in whatever order the threads arrive.  A leaf without a distance below
+    // FLT_MAX keeps its first point, as the serial loop's `d < best` does.
+    const bool par = in_lds && sizeof(float2) * (size_t)n + 16 * (size_t)n_seg <= (size_t)lds_bytes;
+    float2 *l_cen = reinterpret_cast<float2 *>(lds_raw + sizeof(float2) * (size_t)n);
+    unsigned long long *l_best = reinterpret_cast<unsigned long long *>(l_cen + n_seg);
+    if (par) {
+        const float2 *spts = reinterpret_cast<const float2 *>(lds_raw);
+        constexpr int U = 8;
         for (int sg = tid; sg < n_seg; sg += 1024) {
             const int r0 = s_seg[sg], r1 = s_seg[sg + 1];
             float sx = 0.0f, sy = 0.0f;
-            for (int r = r0; r < r1; ++r) {
-                const float2 p = spts[r];
-                sx = __fadd_rn(sx, p.x);
-                sy = __fadd_rn(sy, p.y);
+            for (int r = r0; r < r1; r += U) { // (reads issued ahead; ONE chain of additions in sorted order)
+                float2 p[U];
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    p[k] = spts[min(r + k, r1 - 1)];
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    if (r + k < r1) {
+                        sx = __fadd_rn(sx, p[k].x);
+                        sy = __fadd_rn(sy, p[k].y);
+                    }
+            }
+            const float cntf = (float)(r1 - r0);
+            l_cen[sg] = make_float2(__fdiv_rn(sx, cntf), __fdiv_rn(sy, cntf));
+            l_best[sg] = ((unsigned long long)0x7F7FFFFFu << 32) | (unsigned)r0; // (FLT_MAX, first point)
+        }
+        __syncthreads();
+        {
+            float2 p[CHUNK];
+#pragma unroll
+            for (int k = 0; k < CHUNK; ++k)
+                p[k] = b0 + k < e0 ? spts[b0 + k] : make_float2(0.0f, 0.0f);
+            int leaf = seg_base - 1; // (a chunk that begins inside a leaf: the leaf started in an earlier chunk)
+            float best = 3.402823466e+38f;
+            unsigned bpos = 0;
+            float2 c = make_float2(0.0f, 0.0f);
+#pragma unroll
+            for (int k = 0; k < CHUNK; ++k)
+                if (b0 + k < e0) {
+                    if ((starts >> k) & 1u) {
+                        if (best < 3.402823466e+38f)
+                            atomicMin(&l_best[leaf], ((unsigned long long)__float_as_uint(best) << 32) | bpos);
+                        ++leaf;
+                        best = 3.402823466e+38f;
+                        c = l_cen[leaf];
+                    } else if (k == 0) {
+                        c = l_cen[leaf];
+                    }
+                    const float dx = __fadd_rn(p[k].x, -c.x), dy = __fadd_rn(p[k].y, -c.y);
+                    // sqrtf, not __fsqrt_rn (see cf_downsample_kernel)
+                    const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
+                    if (d < best) {
+                        best = d;
+                        bpos = (unsigned)(b0 + k);
+                    }
+                }
+            if (best < 3.402823466e+38f)
+                atomicMin(&l_best[leaf], ((unsigned long long)__float_as_uint(best) << 32) | bpos);
+        }
+        __syncthreads();
+    }
+    auto medoids = [&](const auto *spts) {
+        for (int base = 0; base < n_seg; base += 1024) {
+            const int sg = base + tid;
+            float2 med = make_float2(0.0f, 0.0f);
+            if (sg < n_seg && par) {
+                med = spts[(unsigned)l_best[sg]];
+            } else if (sg < n_seg) { // one thread per leaf
+            const int r0 = s_seg[sg], r1 = s_seg[sg + 1];
+            float sx = 0.0f, sy = 0.0f;
+            // reads issued ahead, U points at a time; the centroid stays ONE chain of additions in sorted order
+            // (= ascending original index: the sort is stable), the distances are the same expression, and the first
+            // point at the minimum distance wins
+            constexpr int U = 8;
+            for (int r = r0; r < r1; r += U) {
+                float2 p[U];
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    p[k] = spts[min(r + k, r1 - 1)];
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    if (r + k < r1) {
+                        sx = __fadd_rn(sx, p[k].x);
+                        sy = __fadd_rn(sy, p[k].y);
+                    }
             }
             const float cntf = (float)(r1 - r0);
             sx = __fdiv_rn(sx, cntf);
             sy = __fdiv_rn(sy, cntf);
             float best = 3.402823466e+38f;
-            int bi = r0;
-            for (int r = r0; r < r1; ++r) {
-                const float2 p = spts[r];
-                const float dx = __fadd_rn(p.x, -sx), dy = __fadd_rn(p.y, -sy);
-                // sqrtf, not __fsqrt_rn (see cf_downsample_kernel)
-                const float d = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
-                if (d < best) {
-                    best = d;
-                    bi = r;
+            med = spts[r0];
+            for (int r = r0; r < r1; r += U) {
+                float2 p[U];
+                float d[U];
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    p[k] = spts[min(r + k, r1 - 1)];
+#pragma unroll
+                for (int k = 0; k < U; ++k) {
+                    const float dx = __fadd_rn(p[k].x, -sx), dy = __fadd_rn(p[k].y, -sy);
+                    // sqrtf, not __fsqrt_rn (see cf_downsample_kernel)
+                    d[k] = sqrtf(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)));
                 }
+#pragma unroll
+                for (int k = 0; k < U; ++k)
+                    if (r + k < r1 && d[k] < best) {
+                        best = d[k];
+                        med = p[k];
+                    }
             }
-            out[sg] = spts[bi];
+            }
+            if (tail_filter) {
+                if (in_lds)
+                    __syncthreads(); // this round's leaves are read: slots [base, base + 1024) lie in front of every later leaf
+                if (sg < n_seg)
+                    c_p[sg] = med;
+            } else if (sg < n_seg) {
+                (tail_copy ? fout : out)[sg] = med;
+            }
         }
     };
     if (in_lds)
         medoids(reinterpret_cast<const float2 *>(lds_raw)); // (LDS address space: ds_read, not flat)
     else
         medoids(static_cast<const float2 *>(spts_g));
+    CF_STAMP(8);
+    if (!tail_filter) {
+        if (tid == 0) {
+            hdrs[f].n_seg = n_seg;
+            hdrs[f].n_out = n_seg;
+            hdrs[f].zlev = leaf_keys_all ? h.levels : -1;
+            if (tail_copy)
+                tail.out_counts[f] = n_seg;
+            else if (tail.mode != CF_TAIL_NONE)
+                tail.list[atomicAdd(tail.n_list, 1)] = f;
+        }
+        CF_STAMP(9);
+        return;
+    }
+    // the outlier filter on the cloud in LDS: cf_radius_filter_kernel's cell path
+    unsigned short *c_start = reinterpret_cast<unsigned short *>(lds_raw + sizeof(float2) * (size_t)n_seg);
+    const int sh = 2 * (h.levels - lc);
+    unsigned short *c_cell = c_start + (ncell + 2); // cell of every point of the cloud
+    __syncthreads(); // the cloud is complete, the sorted points behind it are dead
+    for (int i = tid; i < n_seg; i += 1024)
+        c_cell[i] = (unsigned short)((unsigned)cf_path_key(c_p[i], h) >> sh);
+    __syncthreads();
+    // cell starts: start of cell c = the first point whose cell is >= c (the cells grow along the cloud) -- the same table as
+    // cf_cell_starts builds, by one binary search per cell instead of a serial fill of every run of empty cells (a sonar fan
+    // covers a part of its bounding box).  Measured on a bench frame: the tail takes 46-48 k cycles either way; its time is
+    // the ~75 distance tests per point of the counts below.
+    for (int c = tid; c <= ncell; c += 1024) {
+        int lo = 0, hi = n_seg;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((int)c_cell[mid] < c)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        c_start[c] = (unsigned short)lo;
+    }
+    __syncthreads();
+    int carry = 0; // kept points of the previous chunks of 1024
+    for (int base = 0; base < n_seg; base += 1024) {
+        const int i = base + tid;
+        float2 p = make_float2(0, 0);
+        int cnt = 0;
+        if (i < n_seg) {
+            p = c_p[i];
+            cnt = cf_cell_count(p, c_cell[i], lc, c_p, c_start, tail.r2);
+        }
+        const int keep = (i < n_seg) && cnt > tail.min_points;
+        int kept_here;
+        const int at = cf_block_excl_scan(keep, s_scan, &kept_here);
+        if (keep)
+            fout[carry + at] = p;
+        carry += kept_here;
+    }
     if (tid == 0) {
         hdrs[f].n_seg = n_seg;
-        hdrs[f].n_out = n_seg;
-        hdrs[f].zlev = leaf_keys_all ? h.levels : -1;
+        hdrs[f].n_out = carry;
+        hdrs[f].zlev = h.levels;
+        tail.out_counts[f] = carry;
     }
+    CF_STAMP(9);
+#undef CF_STAMP
 }
 
-// pcl.remove_outlier: keep a point iff more than min_points points (itself included) lie within the
-// radius; order preserved.  One workgroup per frame: counts (cloud tiled through LDS), scan, gather.
-//
-// Fast path for clouds that come out of the downsample (one medoid per octree leaf, in path = Morton order, leaf
-// keys kept): the leaves are grouped into the cells of the coarsest tree level whose cells are still at least
-// one radius wide (at most level CF_CELL_LEVELS), a cell is a contiguous run of the sorted cloud, and a point
-// only counts the points of the 3 x 3 cells around its own -- every point within the radius lies in one of them.
-// The same float distance test on a superset of the points that can pass it: identical counts, ~75 tests per
-// point instead of ~2500.
-#define CF_CELL_LEVELS 6
-#define CF_CELL_PTS 8192 // points the fast path holds in LDS
-__device__ __forceinline__ unsigned cf_spread(unsigned v) // bit i -> bit 2i (6 bits)
-{
-    v = (v | (v << 4)) & 0x30Fu;
-    v = (v | (v << 2)) & 0x333u;
-    v = (v | (v << 1)) & 0x555u;
-    return v;
-}
-__device__ __forceinline__ unsigned cf_squeeze(unsigned v) // bit 2i -> bit i
-{
-    v &= 0x555u;
-    v = (v | (v >> 1)) & 0x333u;
-    v = (v | (v >> 2)) & 0x30Fu;
-    v = (v | (v >> 4)) & 0x03Fu;
-    return v;
-}
-
-__global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__restrict__ in_all, long long cap,
-                                                                CfHeader *__restrict__ hdrs, float r2, int min_points,
-                                                                float *__restrict__ out_all,
-                                                                int32_t *__restrict__ out_counts, int do_filter,
-                                                                const unsigned *__restrict__ leaf_keys_all)
+// one frame (the whole workgroup)
+__device__ __forceinline__ void cf_radius_filter_frame(const int f, const float2 *__restrict__ in_all, long long cap,
+                                                       CfHeader *__restrict__ hdrs, float r2, int min_points,
+                                                       float *__restrict__ out_all, int32_t *__restrict__ out_counts,
+                                                       int do_filter, const unsigned *__restrict__ leaf_keys_all)
 {
     // dynamic LDS: cell path = the cloud, then the cell starts; brute-force path = a tile of 2048 points (the
     // launcher sizes it for whichever is larger, so two workgroups share a CU either way)
     extern __shared__ __attribute__((aligned(16))) unsigned char cf_dyn[];
     float2 *s_p = reinterpret_cast<float2 *>(cf_dyn);
     __shared__ int s_scan[1024];
-    const int f = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const CfHeader h = hdrs[f];
     const int n = h.n_seg;
     const float2 *pts = in_all + (size_t)f * cap;
@@ -552,19 +826,9 @@ __global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__
             out_counts[f] = -1;
         return;
     }
-    // cell level: deepest level (<= CF_CELL_LEVELS, <= the tree's depth) whose cells are >= radius * 1.001 wide
     int lc = -1;
-    if (do_filter && leaf_keys_all && h.zlev >= 0 && n <= CF_CELL_PTS && n > 0) {
-        const float need = sqrtf(r2) * 1.001f; // the margin dwarfs the rounding of the tree's cell boundaries
-        float width = h.radius * 2.0f;          // level 0 = the root cell
-        if (need > 0.0f && width >= need) {     // (NaN -> brute force)
-            lc = 0;
-            while (lc < CF_CELL_LEVELS && lc < h.zlev && width * 0.5f >= need) {
-                width *= 0.5f;
-                ++lc;
-            }
-        }
-    }
+    if (do_filter && leaf_keys_all && h.zlev >= 0 && n <= CF_CELL_PTS && n > 0)
+        lc = cf_cell_level(h.radius, h.zlev, r2);
     float2 *c_p = reinterpret_cast<float2 *>(cf_dyn);
     unsigned short *c_start = reinterpret_cast<unsigned short *>(cf_dyn + sizeof(float2) * CF_CELL_PTS);
     const int ncell = 1 << (2 * max(lc, 0));
@@ -574,16 +838,9 @@ __global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__
         for (int c = tid; c <= ncell; c += 1024)
             c_start[c] = (unsigned short)n; // "no leaf at or after this cell" until proven otherwise
         __syncthreads();
-        // the first leaf of a cell writes its index as the cell's start AND as the start of the empty cells between the
-        // previous occupied cell and its own ("the next occupied cell's start": starts grow with the cell index).  Round 6:
-        // one barrier instead of the 2 log2(ncell) of a suffix-minimum sweep over the cells (24 at the deepest level).
         for (int i = tid; i < n; i += 1024) {
             c_p[i] = pts[i];
-            const unsigned c = keys[i] >> sh;
-            const unsigned cp = i == 0 ? 0xFFFFFFFFu : keys[i - 1] >> sh;
-            if (cp != c)
-                for (unsigned cc = cp + 1u; cc <= c; ++cc) // (cp + 1 wraps to 0 for the first leaf: the cells in front of it)
-                    c_start[cc] = (unsigned short)i;
+            cf_cell_starts(c_start, i, keys[i] >> sh, i == 0 ? 0xFFFFFFFFu : keys[i - 1] >> sh);
         }
         __syncthreads();
     }
@@ -595,27 +852,8 @@ __global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__
             p = pts[i];
         int cnt = 0;
         if (do_filter && lc >= 0) {
-            if (i < n) {
-                const unsigned ck = (leaf_keys_all + (size_t)f * cap)[i] >> sh;
-                const int ix = (int)cf_squeeze(ck), iy = (int)cf_squeeze(ck >> 1), side = 1 << lc;
-                for (int dy = -1; dy <= 1; ++dy) {
-                    const int cy = iy + dy;
-                    if (cy < 0 || cy >= side)
-                        continue;
-                    for (int dx = -1; dx <= 1; ++dx) {
-                        const int cx = ix + dx;
-                        if (cx < 0 || cx >= side)
-                            continue;
-                        const unsigned m = cf_spread((unsigned)cx) | (cf_spread((unsigned)cy) << 1);
-                        const int j1 = c_start[m + 1];
-                        for (int j = c_start[m]; j < j1; ++j) {
-                            const float2 t = c_p[j];
-                            const float ddx = __fadd_rn(p.x, -t.x), ddy = __fadd_rn(p.y, -t.y);
-                            cnt += __fadd_rn(__fmul_rn(ddx, ddx), __fmul_rn(ddy, ddy)) <= r2;
-                        }
-                    }
-                }
-            }
+            if (i < n)
+                cnt = cf_cell_count(p, (leaf_keys_all + (size_t)f * cap)[i] >> sh, lc, c_p, c_start, r2);
         } else if (do_filter) {
             for (int tb = 0; tb < n; tb += 2048) {
                 const int tn = min(2048, n - tb);
@@ -645,6 +883,28 @@ __global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__
     }
 }
 
+// frame_list == nullptr: one workgroup per frame (blockIdx.x) -- calls without a downsample.  Else the workgroups stride
+// over the listed frames, the ones cf_downsample_radix_kernel's tail left over (see there): none on a sonar fan at the
+// shipped settings, where a launch of one workgroup per frame for ~1300 points each took 0.36 ms per 4096 frames.
+__global__ __launch_bounds__(1024) void cf_radius_filter_kernel(const float2 *__restrict__ in_all, long long cap,
+                                                                CfHeader *__restrict__ hdrs, float r2, int min_points,
+                                                                float *__restrict__ out_all,
+                                                                int32_t *__restrict__ out_counts, int do_filter,
+                                                                const unsigned *__restrict__ leaf_keys_all,
+                                                                const int *__restrict__ frame_list,
+                                                                const int *__restrict__ n_list)
+{
+    if (frame_list) {
+        const int nl = *n_list;
+        for (int i = blockIdx.x; i < nl; i += gridDim.x) {
+            cf_radius_filter_frame(frame_list[i], in_all, cap, hdrs, r2, min_points, out_all, out_counts, do_filter, leaf_keys_all);
+            __syncthreads(); // (the next frame reuses the LDS)
+        }
+    } else {
+        cf_radius_filter_frame(blockIdx.x, in_all, cap, hdrs, r2, min_points, out_all, out_counts, do_filter, leaf_keys_all);
+    }
+}
+
 // staged hand-over from the extraction: bounding box + count -> octree root and depth (what cf_cast_bbox_kernel's last thread does)
 __global__ __launch_bounds__(256) void cf_header_from_bbox_kernel(const CfBBox *__restrict__ bbox, int n_frames, float max_size,
                                                                   CfHeader *__restrict__ hdrs)
@@ -654,6 +914,25 @@ __global__ __launch_bounds__(256) void cf_header_from_bbox_kernel(const CfBBox *
         const CfBBox b = bbox[f];
         hdrs[f] = cf_make_header(b.mnx, b.mny, b.mxx, b.mxy, max_size, b.n);
     }
+}
+
+// debug: phase stamps of workgroup 0 of cf_downsample_radix_kernel (process-wide switch: a timing tool's, not a context's).
+// enable: 0 = the shipped build, 1 = the stamped build, 2 = the stamped build without its tail (the route of rounds 2-6:
+// downsampled clouds to HBM, cf_radius_filter_kernel on every frame), for a breakdown of that route.
+static int g_cf_prof = 0;
+extern "C" int sfe_cf_get_profile(sfe_ctx *ctx, int enable, long long *stamps)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (stamps) { // the stamps of the last profiled launch on this context
+        long long *d_prof = (long long *)sfe_scratch(ctx, CF_SLOT_PROF, sizeof(long long) * CF_PROF_N);
+        if (!d_prof)
+            return SFE_ERR_HIP;
+        SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SFE_HIP(ctx, hipMemcpy(stamps, d_prof, sizeof(long long) * CF_PROF_N, hipMemcpyDeviceToHost));
+    }
+    g_cf_prof = enable;
+    return 0;
 }
 
 float sfe_cf_max_size(float resolution)
@@ -723,6 +1002,7 @@ int sfe_cf_run_staged(sfe_ctx *ctx, int n_frames, int64_t cap, float resolution,
         return SFE_ERR_HIP;
     const float2 *stage = d_p32;
     unsigned *d_lkeys = nullptr; // leaf keys of the downsampled clouds (radius filter fast path)
+    int *d_tail_list = nullptr, *d_list_n = nullptr; // frames the radix kernel's tail left to cf_radius_filter_kernel
     if (do_ds) {
         // 48 key bits + 16 index bits: a frame whose tree is deeper than 24 levels reports count -1
         size_t n2 = 2;
@@ -740,13 +1020,16 @@ int sfe_cf_run_staged(sfe_ctx *ctx, int n_frames, int64_t cap, float resolution,
             // scratch by the last launch.  (Rounds 2-5 chose by the batch's capacity: one dense ping sent all frames to HBM.)
             const size_t n2l = std::min<size_t>(n2, CF_SORT_CAP); // LDS slots of the bitonic launch (a power of two)
             const size_t n2r = cap <= CF_SORT_CAP ? n2 : (size_t)CF_LDS_PTS_BIG; // ... and of the radix launch
-            int *d_marked = nullptr; // capacities beyond the LDS sort: [n_frames] frames that want the HBM sort + [1] how many
-            if (cap > CF_SORT_CAP) {
-                d_marked = (int *)sfe_scratch(ctx, 52, sizeof(int) * ((size_t)n_frames + 1));
-                if (!d_marked)
-                    return SFE_ERR_HIP;
-                SFE_HIP(ctx, hipMemsetAsync(d_marked + n_frames, 0, sizeof(int), ctx->stream));
-            }
+            // two frame lists and their lengths, [n_marked, n_tail | marked[n_frames] | tail[n_frames]]: the frames that want
+            // the HBM sort (capacities beyond the LDS sort only) and the frames the radix kernel's tail leaves to
+            // cf_radius_filter_kernel
+            d_list_n = (int *)sfe_scratch(ctx, 52, sizeof(int) * (2 * (size_t)n_frames + 2));
+            if (!d_list_n)
+                return SFE_ERR_HIP;
+            SFE_HIP(ctx, hipMemsetAsync(d_list_n, 0, 2 * sizeof(int), ctx->stream));
+            int *d_marked = cap > CF_SORT_CAP ? d_list_n + 2 : nullptr;
+            if (g_cf_prof != 2) // (debug: 2 = stamps of the two-kernel route, every frame through cf_radius_filter_kernel)
+                d_tail_list = d_list_n + 2 + n_frames;
             {
                 // indices + keys + counters for the sort, then (same bytes) every point of the frame in sorted order.
                 // (The LDS is sized by the CAPACITY: 128 KB = one frame per CU at 16 384 points, 64 KB = two per CU at 8 192.
@@ -762,17 +1045,32 @@ int sfe_cf_run_staged(sfe_ctx *ctx, int n_frames, int64_t cap, float resolution,
                 // (the sorted points take the same bytes when they fit, else their HBM scratch: the kernel looks at lds_bytes)
                 const size_t rdx_smem = big ? 3 * 2 * n2r + 2 * (n_cnt + n_cnt / 16)
                                             : std::max<size_t>(3 * 2 * n2r + 2 * (n_cnt + n_cnt / 16), sizeof(float2) * n2r);
-                auto rk = big ? cf_downsample_radix_kernel<CF_RDX_CHUNK_BIG> : cf_downsample_radix_kernel<CF_RDX_CHUNK>;
+                CfTail tail{};
+                tail.mode = !d_tail_list ? CF_TAIL_NONE : do_filter ? CF_TAIL_FILTER : CF_TAIL_COPY;
+                tail.r2 = (float)(radius * radius);
+                tail.min_points = min_points;
+                tail.out = reinterpret_cast<float2 *>(d_out);
+                tail.out_counts = d_out_counts;
+                tail.list = d_tail_list;
+                tail.n_list = d_list_n + 1;
+                auto rk = big ? cf_downsample_radix_kernel<CF_RDX_CHUNK_BIG, false> : cf_downsample_radix_kernel<CF_RDX_CHUNK, false>;
+                if (g_cf_prof) { // debug: the stamped instantiation (sfe_cf_get_profile)
+                    tail.prof = (long long *)sfe_scratch(ctx, CF_SLOT_PROF, sizeof(long long) * CF_PROF_N);
+                    if (!tail.prof)
+                        return SFE_ERR_HIP;
+                    SFE_HIP(ctx, hipMemsetAsync(tail.prof, 0, sizeof(long long) * CF_PROF_N, ctx->stream));
+                    rk = big ? cf_downsample_radix_kernel<CF_RDX_CHUNK_BIG, true> : cf_downsample_radix_kernel<CF_RDX_CHUNK, true>;
+                }
                 SFE_HIP(ctx, hipFuncSetAttribute((const void *)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rdx_smem));
                 hipLaunchKernelGGL(rk, dim3(n_frames), dim3(1024), rdx_smem, ctx->stream, d_p32,
                                    (long long)cap, d_hdr, d_ds, d_seg, (int)n2r, d_lkeys, d_spts, (int)rdx_smem, sort_cols, d_marked,
-                                   d_marked ? d_marked + n_frames : nullptr);
+                                   d_marked ? d_list_n : nullptr, tail);
             }
             SFE_HIP(ctx, hipFuncSetAttribute((const void *)cf_downsample_kernel<true, unsigned long long>,
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(8 * n2l)));
             hipLaunchKernelGGL((cf_downsample_kernel<true, unsigned long long>), dim3(n_frames), dim3(1024), 8 * n2l,
                                ctx->stream, d_p32, (long long)cap, d_hdr, d_ds, d_seg, (unsigned long long *)nullptr, (long long)n2l, 1,
-                               (unsigned *)nullptr, d_marked, d_marked ? d_marked + n_frames : nullptr, (const int *)nullptr);
+                               (unsigned *)nullptr, d_marked, d_marked ? d_list_n : nullptr, (const int *)nullptr);
             if (cap > CF_SORT_CAP) { // the listed frames (> CF_SORT_CAP points): a few workgroups stride over the list
                 const int gw = std::min(n_frames, 256); // (one per CU: a batch whose frames ALL want this sort -- 2048 x 1024 pings -- keeps its parallelism)
                 unsigned long long *d_gk = (unsigned long long *)sfe_scratch(ctx, 29, 8 * n2 * (size_t)gw);
@@ -780,7 +1078,7 @@ int sfe_cf_run_staged(sfe_ctx *ctx, int n_frames, int64_t cap, float resolution,
                     return SFE_ERR_HIP;
                 hipLaunchKernelGGL((cf_downsample_kernel<false, unsigned long long>), dim3(gw), dim3(1024), 0,
                                    ctx->stream, d_p32, (long long)cap, d_hdr, d_ds, d_seg, d_gk, (long long)n2, 1,
-                                   (unsigned *)nullptr, (int *)nullptr, d_marked + n_frames, (const int *)d_marked);
+                                   (unsigned *)nullptr, (int *)nullptr, d_list_n, (const int *)d_marked);
             }
         }
         stage = d_ds;
@@ -788,10 +1086,13 @@ int sfe_cf_run_staged(sfe_ctx *ctx, int n_frames, int64_t cap, float resolution,
     const size_t cell_smem = sizeof(float2) * CF_CELL_PTS + sizeof(unsigned short) * ((1 << (2 * CF_CELL_LEVELS)) + 2);
     SFE_HIP(ctx, hipFuncSetAttribute((const void *)cf_radius_filter_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)cell_smem));
-    hipLaunchKernelGGL(cf_radius_filter_kernel, dim3(n_frames), dim3(1024),
+    // after a downsample: the frames its tail left over, a few workgroups striding over their list (it is empty on a sonar
+    // fan at the shipped settings; a batch whose frames ALL come here -- a radius wider than the fan -- keeps half the CUs)
+    const int gw = d_tail_list ? std::min(n_frames, 128) : n_frames;
+    hipLaunchKernelGGL(cf_radius_filter_kernel, dim3(gw), dim3(1024),
                        d_lkeys ? cell_smem : sizeof(float2) * 2048, ctx->stream, stage,
                        (long long)cap, d_hdr, (float)(radius * radius), min_points, d_out, d_out_counts, do_filter ? 1 : 0,
-                       (const unsigned *)d_lkeys);
+                       (const unsigned *)d_lkeys, (const int *)d_tail_list, (const int *)(d_tail_list ? d_list_n + 1 : nullptr));
     SFE_LAUNCH_CHECK(ctx);
     return 0;
 }
