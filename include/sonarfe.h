@@ -845,6 +845,46 @@ int sfe_mapset_render2_store(sfe_mapset *ms, sfe_cloud_store *store, int n, cons
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,
                             uint8_t *keep_out);
 
+/* ---- the intensity mosaic of bruce_slam/mapping.py (pub_intensity: :128-130, :241-243, :272-298, :442-444, :457-459,
+ * :498-499).  Off until sfe_mapset_enable_intensity: a set that never enables it allocates, launches and records exactly
+ * what it did before these calls existed.  The sfe_map calls are the set's over map 0.
+ *   sfe_mapset_enable_intensity: refused with SFE_ERR_ARG once a geometry is registered or a slot is in use.  Per slot the
+ *     subsampled ping uint8 [px] and a double-buffered payload uint8 [2][px] next to l (+3 bytes per pixel: the arena
+ *     becomes 23 bytes per pixel); per map a uint32 sum grid and a uint16 counter grid of the float grid's shape, zeroed.
+ *     From then on sfe_mapset_refit writes i = image[first pixel of the cell] next to l, its applies add / subtract i on
+ *     the sum grid and 1 on the counter grid (both wrapping) in the same launches, and sfe_mapset_grow pads both grids with
+ *     zeros on all four sides.  A fit of a slot without an image is refused before anything changes.
+ *   sfe_mapset_set_intensity: n full-size pings, back to back in `images`, image b for (maps[b], slots[b]) of geometry
+ *     geoms[b]; shape4[4 b ..] = {full_rows, full_cols, r_skip, c_skip}.  The slot keeps image[::r_skip, ::c_skip], which
+ *     must have the geometry's image shape (SFE_ERR_ARG otherwise; a slot beyond the arena SFE_ERR_CAP; both before anything
+ *     changes).  One upload through the pinned staging, one launch; enqueue only.
+ *   sfe_mapset_set_intensity_dev: the same from n device pointers, row b of image i at d_images[i] + b * row_stride[i]
+ *     (row_stride >= full_cols; full_rows rows must be readable); nothing is uploaded but the job table.
+ *   sfe_mapset_render_intensity: get_intensity_grid for n maps in one launch and one read-back: job b writes box4[4 b ..] =
+ *     {r0, r1, c0, c1} of map maps[b] at out + out_off[b], `total` bytes in all: -1 where the counter is 0, else
+ *     (int8) rint(((double) sum / 255.0) * 100.0 / (double) counter), rint half to even (csrc/sfe_map_intensity.h).
+ *   sfe_mapset_read_intensity: the two grids of one map (either pointer may be null), cap cells each.
+ *   sfe_mapset_slot_intensity: a slot's subsampled image and the payload i of its current cell list (in the order of
+ *     sfe_mapset_cells; any of the three outputs may be null). */
+int sfe_mapset_enable_intensity(sfe_mapset *ms);
+int sfe_mapset_set_intensity(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                             const int32_t *shape4, const uint8_t *images);
+int sfe_mapset_set_intensity_dev(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                                 const int32_t *shape4, const void *const *d_images, const long long *row_stride);
+int sfe_mapset_render_intensity(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *box4, const long long *out_off,
+                                long long total, int8_t *out);
+int sfe_mapset_read_intensity(sfe_mapset *ms, int map, uint32_t *intensity_out, uint16_t *counter_out, long long cap);
+int sfe_mapset_slot_intensity(sfe_mapset *ms, int map, int slot, uint8_t *image_out, int image_cap, uint8_t *i_out,
+                              int cells_cap, int *n_out);
+int sfe_map_enable_intensity(sfe_map *m);
+int sfe_map_set_intensity(sfe_map *m, int slot, int geom, int full_rows, int full_cols, int r_skip, int c_skip,
+                          const uint8_t *image);
+int sfe_map_set_intensity_dev(sfe_map *m, int slot, int geom, int full_rows, int full_cols, int r_skip, int c_skip,
+                              const void *d_image, long long row_stride);
+int sfe_map_render_intensity(sfe_map *m, int r0, int r1, int c0, int c1, int8_t *out);
+int sfe_map_read_intensity(sfe_map *m, uint32_t *intensity_out, uint16_t *counter_out, long long cap);
+int sfe_map_slot_intensity(sfe_map *m, int slot, uint8_t *image_out, int image_cap, uint8_t *i_out, int cells_cap, int *n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -323,6 +323,20 @@ SIGNATURES = {
                                            _f64p, _i32p, _i32p, _f64p, _f64p, _i32p, _f64p, _i32p, C.POINTER(C.c_longlong),
                                            C.POINTER(C.c_int8), C.c_longlong]),
     "sfe_remove_outlier_many": (C.c_int, [_vp, _f32p, _i32p, C.c_int, C.c_double, C.c_int, _u8p]),
+    "sfe_mapset_enable_intensity": (C.c_int, [_vp]),
+    "sfe_mapset_set_intensity": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p]),
+    "sfe_mapset_set_intensity_dev": (C.c_int, [_vp, C.c_int, _i32p, _i32p, _i32p, _i32p, C.POINTER(_vp),
+                                               C.POINTER(C.c_longlong)]),
+    "sfe_mapset_render_intensity": (C.c_int, [_vp, C.c_int, _i32p, _i32p, C.POINTER(C.c_longlong), C.c_longlong,
+                                              C.POINTER(C.c_int8)]),
+    "sfe_mapset_read_intensity": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.c_longlong]),
+    "sfe_mapset_slot_intensity": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_map_enable_intensity": (C.c_int, [_vp]),
+    "sfe_map_set_intensity": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _u8p]),
+    "sfe_map_set_intensity_dev": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong]),
+    "sfe_map_render_intensity": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int8)]),
+    "sfe_map_read_intensity": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.c_longlong]),
+    "sfe_map_slot_intensity": (C.c_int, [_vp, C.c_int, _u8p, C.c_int, _u8p, C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib = None

@@ -159,6 +159,13 @@ class SessionBatch(object):
                 raise ValueError("SessionBatch: mapping needs a `ping` (num_ranges, range_resolution, bearings)")
             if mapping.get("feed", "host") not in ("host", "store"):
                 raise ValueError("SessionBatch: mapping feed must be \"host\" or \"store\", got %r" % (mapping["feed"],))
+            if mapping.get("pub_intensity"):
+                # the mosaic samples the batch's own resident frames: they must be the map ping's num_ranges x num_bearings
+                want = (int(mapping["ping"].num_ranges), len(mapping["ping"].bearings))
+                if (int(geometry.polar_rows), int(geometry.polar_cols)) != want:
+                    raise ValueError("SessionBatch: mapping with pub_intensity: the batch's frames are %d x %d, the map ping's "
+                                     "num_ranges x num_bearings is %d x %d"
+                                     % (geometry.polar_rows, geometry.polar_cols, want[0], want[1]))
         self.ctx, self.S, self.K = ctx, int(n_sessions), int(n_steps)
         # loop-closure search (replay.FrontEnd's arguments of the same names, its defaults but for nssm_enable: off here, so that a
         # batch built without it runs, sizes and records exactly what it did before the search existed)
@@ -317,11 +324,27 @@ class SessionBatch(object):
         if self.maps is None:
             return
         poses = [self._pose(k, s) for s in range(self.S)]
+        images = {"images": self._frame_images(k)} if self.maps.pub_intensity else {}
         if self._map_feed == "store":
-            self.maps.add_keyframes_store(range(self.S), [k] * self.S, poses, self._map_ping, self.store, self.handles[:, k])
+            self.maps.add_keyframes_store(range(self.S), [k] * self.S, poses, self._map_ping, self.store, self.handles[:, k],
+                                          **images)
             return
         clouds = self.store.read_many(self.handles[:, k])
-        self.maps.add_keyframes(range(self.S), [k] * self.S, poses, self._map_ping, clouds)
+        self.maps.add_keyframes(range(self.S), [k] * self.S, poses, self._map_ping, clouds, **images)
+
+    def _frame_images(self, k):
+        """the pings of step k where they lie in ``d_frames``, one view per session: the intensity mosaic samples them in
+        place, no ping crosses to the host and back"""
+        from .mapping import DeviceImage
+        base = self.d_frames.ptr.value + k * self.S * self.frame_bytes
+        return [DeviceImage(base + s * self.frame_bytes, self.kb.rows, self.kb.cols) for s in range(self.S)]
+
+    def intensity_grids(self, sessions=None):
+        """``maps.get_intensity_grid(sessions)``: the published intensity mosaics of the listed sessions (all by default).
+        Needs ``mapping=dict(..., pub_intensity=True, intensity_skips="oculus")``."""
+        if self.maps is None:
+            raise RuntimeError("SessionBatch.intensity_grids: the batch owns no maps: construct it with mapping=dict(ping=...)")
+        return self.maps.get_intensity_grid(sessions)
 
     def slam_clouds(self, sessions=None):
         """``FrontEnd.slam_cloud()`` for the listed sessions (all by default): the keyframes recorded so far under the batch's

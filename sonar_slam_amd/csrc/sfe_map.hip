@@ -9,12 +9,19 @@
 // subtracts the old, adds the new, and flips.  Growth pads a grid and bumps two counters; a list keeps the counters it was
 // written at, and its cells are shifted by the difference when read.  An sfe_map is a set of one map (the end of this file).
 // Method 2 (get_occupancy_grid2: point projection + dilation) reads those cell lists and writes no state: sfe_mapset_render2.
+// The intensity mosaic (pub_intensity, mapping.py:241-243, 272-298, 442-444), only after sfe_mapset_enable_intensity: per
+// slot the subsampled ping (uint8) and a fourth list payload i next to l; per map a uint32 sum grid and a uint16 counter grid
+// of the float grid's shape, updated by the same applies and padded by the same growth; sfe_mapset_render_intensity.
 //
 // Slot storage, the one thing chosen at creation.  A slot record (SetSlot) carries its own device pointers:
 //   logodds  float32 [px]
 //   r, c     uint16  [2][px] each   (the double-buffered cell list)
 //   l        float32 [2][px]
 // = 20 bytes per pixel (2.1 MB at the 105 k pixels of a 1024 x 512 ping at the shipped skips), plus 8 bytes of counts.
+// With the intensity mosaic enabled also
+//   image    uint8   [px]           (the ping at the geometry's skips)
+//   i        uint8   [2][px]
+// = 23 bytes per pixel.
 //   arena (sfe_mapset_create): fixed at creation for n_maps * max_keyframes slots of max_px pixels each, the pointers computed
 //     into it then.  Nothing is reallocated afterwards: a slot >= max_keyframes or an image of more than max_px pixels is
 //     refused (SFE_ERR_CAP) before any state changes.
@@ -27,6 +34,7 @@
 #include <utility>
 
 #include "sfe_internal.h"
+#include "sfe_map_intensity.h"
 
 namespace {
 
@@ -54,6 +62,9 @@ struct SetSlot {
     uint16_t *d_r[2] = {nullptr, nullptr}, *d_c[2] = {nullptr, nullptr};
     float *d_l[2] = {nullptr, nullptr};
     int32_t *d_n = nullptr;     // [2]: cell count of each list buffer
+    // the intensity mosaic (null unless enabled)
+    int has_image = 0;
+    uint8_t *d_image = nullptr, *d_i[2] = {nullptr, nullptr};
 };
 
 struct SetMap {
@@ -61,6 +72,8 @@ struct SetMap {
     float *d_grid = nullptr, *d_frames = nullptr; // (d_frames: the grid of the last frames= render)
     int frames_rows = 0, frames_cols = 0;
     int grow_r = 0, grow_c = 0;
+    uint32_t *d_inten = nullptr; // the intensity mosaic's sum and counter grids (null unless enabled)
+    uint16_t *d_count = nullptr;
 };
 
 // per keyframe of a measurement batch
@@ -88,6 +101,16 @@ struct FitJob {
     uint16_t *out_r, *out_c;
     float *out_l;
     int32_t *out_n;
+    const uint8_t *image; // the intensity mosaic's payload (null: none)
+    uint8_t *out_i;
+};
+
+// per keyframe of an intensity upload: out[i * img_cols + j] = src[i * r_skip * stride + j * c_skip]
+struct SampleJob {
+    const uint8_t *src;
+    uint8_t *out;
+    int32_t img_rows, img_cols, r_skip, c_skip;
+    int64_t stride;
 };
 
 struct FeedJob {
@@ -132,12 +155,15 @@ struct sfe_mapset {
     std::vector<SetSlot> slots; // [map * max_kf + slot]
     float *d_logodds = nullptr, *d_l = nullptr; // the arena
     uint16_t *d_r = nullptr, *d_c = nullptr;
+    bool intensity = false;               // sfe_mapset_enable_intensity
+    uint8_t *d_image = nullptr, *d_i = nullptr; // its part of the arena
     int32_t *d_counts = nullptr; // [map * max_kf + slot][2], room for counts_cap slots
     int counts_cap = 0;
     // scratch.  0 .. 5: job tables, hits, kernels, mask, image, first hits; 6 .. 10: the store feed's job tables, hit buffer,
     // keep flags, undecided lists and counters, hit tables; 11 .. 16: method 2's job tables, list table, spans, points,
-    // float32 points + keep flags, work images; 17, 18: its store route's frame lists, multiplicities + keep flags
-    MapBuf buf[19];
+    // float32 points + keep flags, work images; 17, 18: its store route's frame lists, multiplicities + keep flags;
+    // 19, 20: the intensity upload's job table and full-size images
+    MapBuf buf[21];
     int last_meas_n = 0;
     std::vector<MeasJob> last_meas;
     long long apply_launches = 0; // launches of mapset_apply_kernel so far
@@ -372,6 +398,8 @@ __global__ __launch_bounds__(COMPACT_THREADS) void map_compact_kernel(const FitJ
             j.out_r[k] = (uint16_t)(j.wr0 + rr + j.sr);
             j.out_c[k] = (uint16_t)(j.wc0 + cc + j.sc);
             j.out_l[k] = j.logodds[v];
+            if (j.out_i)
+                j.out_i[k] = j.image[v];
         }
         carry += tot;
         __syncthreads();
@@ -382,13 +410,27 @@ __global__ __launch_bounds__(COMPACT_THREADS) void map_compact_kernel(const FitJ
     }
 }
 
-__global__ void map_pad_kernel(const float *src, int rows, int cols, float *dst, int dcols, int top, int left)
+template <class T>
+__global__ void map_pad_kernel(const T *src, int rows, int cols, T *dst, int dcols, int top, int left)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)rows * cols)
         return;
     const int r = (int)(i / cols), c = (int)(i - (int64_t)r * cols);
     dst[(int64_t)(r + top) * dcols + c + left] = src[i];
+}
+
+// r2n(ping.ping)[::r_skip, ::c_skip] (mapping.py:242) of job blockIdx.y: consecutive threads take consecutive columns of a
+// row, so with c_skip == 1 a wave reads and writes whole runs of bytes; with c_skip > 1 it reads every c_skip-th byte of
+// the same lines
+__global__ __launch_bounds__(MAP_THREADS) void map_sample_kernel(const SampleJob *jobs)
+{
+    const SampleJob j = jobs[blockIdx.y];
+    const int n = j.img_rows * j.img_cols;
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < n; p += gridDim.x * blockDim.x) {
+        const int y = p / j.img_cols, x = p - y * j.img_cols;
+        j.out[p] = j.src[(int64_t)y * j.r_skip * j.stride + (int64_t)x * j.c_skip];
+    }
 }
 
 // --- apply (inc_grid / dec_grid) and render (get_occupancy_grid1) over job tables: one job serves one map as well as S ---
@@ -402,6 +444,17 @@ struct ApplyJob {
     int32_t dr, dc; // growth since the list was written
     int32_t sub;
     int32_t n_px; // upper bound of *n (the pixels of its image)
+    // the intensity mosaic rides along (null: none): grid_i[cell] += / -= i, grid_n[cell] += / -= 1, wrapping
+    uint32_t *grid_i;
+    uint16_t *grid_n;
+    const uint8_t *i;
+};
+
+struct RenderIJob {
+    const uint32_t *grid_i;
+    const uint16_t *grid_n;
+    int32_t cols, r0, c0, h, w;
+    int64_t out_off;
 };
 
 struct RenderJob {
@@ -421,8 +474,29 @@ __global__ __launch_bounds__(MAP_THREADS) void mapset_apply_kernel(const ApplyJo
         const int rr = (int)j.r[i] + j.dr, cc = (int)j.c[i] + j.dc;
         if (rr < 0 || rr >= j.rows || cc < 0 || cc >= j.cols)
             continue; // cannot happen: every cell lies inside the grown grid
-        float *g = j.grid + (int64_t)rr * j.cols + cc;
+        const int64_t cell = (int64_t)rr * j.cols + cc;
+        float *g = j.grid + cell;
         *g = j.sub ? __fsub_rn(*g, j.l[i]) : __fadd_rn(*g, j.l[i]);
+        if (j.grid_i) {
+            // the counter's neighbours in its dword belong to other lanes: a 16-bit load and a 16-bit store, nothing wider
+            uint32_t *gi = j.grid_i + cell;
+            uint16_t *gn = j.grid_n + cell;
+            const uint32_t v = j.i[i];
+            *gi = j.sub ? *gi - v : *gi + v;
+            *gn = (uint16_t)(j.sub ? *gn - 1u : *gn + 1u);
+        }
+    }
+}
+
+// get_intensity_grid (mapping.py:272-298): job blockIdx.y writes its h x w box at out + out_off
+__global__ __launch_bounds__(MAP_THREADS) void mapset_render_intensity_kernel(const RenderIJob *jobs, int8_t *out)
+{
+    const RenderIJob j = jobs[blockIdx.y];
+    const int64_t n = (int64_t)j.h * j.w;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int y = (int)(i / j.w), x = (int)(i - (int64_t)y * j.w);
+        const int64_t cell = (int64_t)(j.r0 + y) * j.cols + j.c0 + x;
+        out[j.out_off + i] = sfe_map_intensity_value(j.grid_i[cell], j.grid_n[cell]);
     }
 }
 
@@ -806,6 +880,20 @@ int set_grid_alloc(sfe_mapset *ms, float **d, size_t n)
     return 0;
 }
 
+// the intensity mosaic's two grids of one map, zeroed
+int set_mosaic_alloc(sfe_mapset *ms, uint32_t **gi, uint16_t **gn, size_t n)
+{
+    *gi = nullptr, *gn = nullptr;
+    if (hipMalloc((void **)gi, n * sizeof(uint32_t)) != hipSuccess || hipMalloc((void **)gn, n * sizeof(uint16_t)) != hipSuccess) {
+        (void)hipFree(*gi);
+        *gi = nullptr, *gn = nullptr;
+        return sfe_set_err(ms->ctx, SFE_ERR_HIP, "map set intensity grid allocation of %zu cells failed", n);
+    }
+    SFE_HIP(ms->ctx, hipMemsetAsync(*gi, 0, n * sizeof(uint32_t), ms->ctx->stream));
+    SFE_HIP(ms->ctx, hipMemsetAsync(*gn, 0, n * sizeof(uint16_t), ms->ctx->stream));
+    return 0;
+}
+
 // may (map, slot) take an image of geometry g?  Checks only.
 int set_slot_check(sfe_mapset *ms, int map, int slot, int g)
 {
@@ -838,9 +926,13 @@ void set_slot_free(SetSlot &s)
         (void)hipFree(s.d_r[b]);
         (void)hipFree(s.d_c[b]);
         (void)hipFree(s.d_l[b]);
+        (void)hipFree(s.d_i[b]);
         s.d_r[b] = s.d_c[b] = nullptr;
         s.d_l[b] = nullptr;
+        s.d_i[b] = nullptr;
     }
+    (void)hipFree(s.d_image);
+    s.d_image = nullptr;
     s.px = 0;
 }
 
@@ -887,7 +979,11 @@ int set_slot_bind(sfe_mapset *ms, int map, int slot, int g)
         SFE_HIP(ctx, hipMalloc((void **)&s.d_r[b], px * sizeof(uint16_t)));
         SFE_HIP(ctx, hipMalloc((void **)&s.d_c[b], px * sizeof(uint16_t)));
         SFE_HIP(ctx, hipMalloc((void **)&s.d_l[b], px * sizeof(float)));
+        if (ms->intensity)
+            SFE_HIP(ctx, hipMalloc((void **)&s.d_i[b], (size_t)px));
     }
+    if (ms->intensity)
+        SFE_HIP(ctx, hipMalloc((void **)&s.d_image, (size_t)px));
     s.px = px;
     return 0;
 }
@@ -909,6 +1005,11 @@ int set_fit_jobs(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slot
         j.c = pose4[4 * b], j.s = pose4[4 * b + 1], j.tx = pose4[4 * b + 2], j.ty = pose4[4 * b + 3];
         j.y0 = origin2[2 * b], j.x0 = origin2[2 * b + 1];
         j.logodds = s.d_logodds;
+        j.image = nullptr, j.out_i = nullptr;
+        if (ms->intensity) {
+            SFE_ARG(ms->ctx, s.has_image); // (sfe_mapset_set_intensity first)
+            j.image = s.d_image;
+        }
         max_px = max(max_px, j.n_px);
     }
     return 0;
@@ -1124,6 +1225,8 @@ void sfe_mapset_destroy(sfe_mapset *ms)
     for (auto &m : ms->maps) {
         (void)hipFree(m.d_grid);
         (void)hipFree(m.d_frames);
+        (void)hipFree(m.d_inten);
+        (void)hipFree(m.d_count);
     }
     for (auto &g : ms->geoms)
         (void)hipFree(g.d_xy);
@@ -1134,6 +1237,8 @@ void sfe_mapset_destroy(sfe_mapset *ms)
     (void)hipFree(ms->d_l);
     (void)hipFree(ms->d_r);
     (void)hipFree(ms->d_c);
+    (void)hipFree(ms->d_image);
+    (void)hipFree(ms->d_i);
     (void)hipFree(ms->d_counts);
     for (auto &b : ms->buf)
         (void)hipFree(b.p);
@@ -1303,7 +1408,7 @@ int sfe_mapset_grow(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *g
         const long long nr = (long long)m.rows + g[0] + g[1], nc = (long long)m.cols + g[2] + g[3];
         SFE_ARG(ctx, nr * nc < (1LL << 31) && nr <= 65536 && nc <= 65536);
     }
-    std::vector<float *> old;
+    std::vector<void *> old;
     for (int b = 0; b < n; ++b) {
         const int32_t *g = grow4 + 4 * b;
         if (g[0] + g[1] + g[2] + g[3] == 0)
@@ -1311,20 +1416,40 @@ int sfe_mapset_grow(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *g
         SetMap &m = ms->maps[maps[b]];
         const int nr = m.rows + g[0] + g[1], nc = m.cols + g[2] + g[3];
         float *d = nullptr;
+        uint32_t *di = nullptr;
+        uint16_t *dn = nullptr;
         if (int rc = set_grid_alloc(ms, &d, (size_t)nr * nc))
             return rc;
+        if (ms->intensity)
+            if (int rc = set_mosaic_alloc(ms, &di, &dn, (size_t)nr * nc)) {
+                (void)hipFree(d);
+                return rc;
+            }
         const int64_t cells = (int64_t)m.rows * m.cols;
-        hipLaunchKernelGGL(map_pad_kernel, dim3((unsigned)((cells + MAP_THREADS - 1) / MAP_THREADS)), dim3(MAP_THREADS), 0,
-                           ctx->stream, m.d_grid, m.rows, m.cols, d, nc, g[0], g[2]);
+        const dim3 pad_grid((unsigned)((cells + MAP_THREADS - 1) / MAP_THREADS));
+        hipLaunchKernelGGL(map_pad_kernel<float>, pad_grid, dim3(MAP_THREADS), 0, ctx->stream, (const float *)m.d_grid, m.rows,
+                           m.cols, d, nc, g[0], g[2]);
         SFE_LAUNCH_CHECK(ctx);
         old.push_back(m.d_grid);
         m.d_grid = d;
+        if (ms->intensity) {
+            // (on the left and right the reference raises: mapping.py:555-562, 574-581 pad columns with np.r_)
+            hipLaunchKernelGGL(map_pad_kernel<uint32_t>, pad_grid, dim3(MAP_THREADS), 0, ctx->stream,
+                               (const uint32_t *)m.d_inten, m.rows, m.cols, di, nc, g[0], g[2]);
+            SFE_LAUNCH_CHECK(ctx);
+            hipLaunchKernelGGL(map_pad_kernel<uint16_t>, pad_grid, dim3(MAP_THREADS), 0, ctx->stream,
+                               (const uint16_t *)m.d_count, m.rows, m.cols, dn, nc, g[0], g[2]);
+            SFE_LAUNCH_CHECK(ctx);
+            old.push_back(m.d_inten);
+            old.push_back(m.d_count);
+            m.d_inten = di, m.d_count = dn;
+        }
         m.rows = nr, m.cols = nc;
         m.grow_r += g[0], m.grow_c += g[2];
     }
     if (!old.empty()) {
         SFE_HIP(ctx, hipStreamSynchronize(ctx->stream)); // one for all the maps that grew
-        for (float *p : old)
+        for (void *p : old)
             (void)hipFree(p);
     }
     return 0;
@@ -1368,6 +1493,7 @@ int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *
         const int nb = 1 - s.cur;
         j.out_r = s.d_r[nb], j.out_c = s.d_c[nb], j.out_l = s.d_l[nb];
         j.out_n = s.d_n + nb;
+        j.out_i = ms->intensity ? s.d_i[nb] : nullptr;
     }
     SFE_ARG(ctx, win < (1LL << 40));
     // room for both job tables (the fits, then up to two applies per fit) and the windows, before any state changes
@@ -1385,9 +1511,11 @@ int sfe_mapset_refit(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *
         SetMap &m = ms->maps[maps[b]];
         ApplyJob a;
         a.grid = m.d_grid, a.rows = m.rows, a.cols = m.cols, a.n_px = jobs[b].n_px;
+        a.grid_i = m.d_inten, a.grid_n = m.d_count; // (null unless the mosaic is enabled)
         for (int pass = dec[b] ? 0 : 1; pass < 2; ++pass) {
             const int o = pass ? 1 - s.cur : s.cur;
             a.r = s.d_r[o], a.c = s.d_c[o], a.l = s.d_l[o];
+            a.i = s.d_i[o];
             a.n = s.d_n + o;
             a.dr = pass ? 0 : m.grow_r - s.base_r, a.dc = pass ? 0 : m.grow_c - s.base_c;
             a.sub = pass ? 0 : 1;
@@ -1541,6 +1669,7 @@ int sfe_mapset_frames(sfe_mapset *ms, int n_maps, const int32_t *maps, const int
             const MapGeom &g = ms->geoms[s.geom];
             ApplyJob a;
             a.grid = m.d_frames, a.rows = m.rows, a.cols = m.cols, a.n_px = g.img_rows * g.img_cols;
+            a.grid_i = nullptr, a.grid_n = nullptr, a.i = nullptr; // (the mosaic has no frames= form)
             a.r = s.d_r[s.cur], a.c = s.d_c[s.cur], a.l = s.d_l[s.cur];
             a.n = s.d_n + s.cur;
             a.dr = m.grow_r - s.base_r, a.dc = m.grow_c - s.base_c, a.sub = 0;
@@ -1605,6 +1734,243 @@ int sfe_mapset_render(sfe_mapset *ms, int n, const int32_t *maps, const int32_t 
     // (bytes of `total` no job covers are whatever the scratch held: the offsets are the caller's)
     SFE_HIP(ctx, hipMemcpyAsync(occ_out, d, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// ---- the intensity mosaic (sonarfe.h) ----------------------------------------------------------------------------------------
+int sfe_mapset_enable_intensity(sfe_mapset *ms)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (ms->intensity)
+        return 0;
+    SFE_ARG(ctx, ms->geoms.empty()); // before the first geometry ...
+    for (const SetSlot &s : ms->slots)
+        SFE_ARG(ctx, s.geom < 0 && s.px == (ms->arena ? ms->max_px : 0)); // ... and the first slot
+    if (ms->arena) {
+        const size_t px = ms->slots.size() * (size_t)ms->max_px;
+        if (hipMalloc((void **)&ms->d_image, px) != hipSuccess || hipMalloc((void **)&ms->d_i, 2 * px) != hipSuccess) {
+            (void)hipFree(ms->d_image);
+            ms->d_image = ms->d_i = nullptr;
+            return sfe_set_err(ctx, SFE_ERR_HIP, "map set: intensity arena of %zu bytes failed", 3 * px);
+        }
+    }
+    for (SetMap &m : ms->maps)
+        if (int rc = set_mosaic_alloc(ms, &m.d_inten, &m.d_count, (size_t)m.rows * m.cols)) {
+            for (SetMap &k : ms->maps) {
+                (void)hipFree(k.d_inten);
+                (void)hipFree(k.d_count);
+                k.d_inten = nullptr, k.d_count = nullptr;
+            }
+            (void)hipFree(ms->d_image);
+            (void)hipFree(ms->d_i);
+            ms->d_image = ms->d_i = nullptr;
+            return rc;
+        }
+    if (ms->arena)
+        for (size_t i = 0; i < ms->slots.size(); ++i) {
+            SetSlot &s = ms->slots[i];
+            s.d_image = ms->d_image + i * ms->max_px;
+            for (int b = 0; b < 2; ++b)
+                s.d_i[b] = ms->d_i + (2 * i + b) * ms->max_px;
+        }
+    ms->intensity = true;
+    return 0;
+}
+
+// The checks of an intensity upload, then (with `images`) one upload of all n full-size images through the pinned staging,
+// one launch of the sampler over the jobs.  shape4[4 b ..] = {full_rows, full_cols, r_skip, c_skip}.
+static int set_intensity(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                         const int32_t *shape4, const uint8_t *images, const void *const *d_images, const long long *stride)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, ms->intensity && n >= 0 && n <= 65535);
+    SFE_ARG(ctx, n == 0 || (maps && slots && geoms && shape4 && (images || (d_images && stride))));
+    if (n == 0)
+        return 0;
+    size_t total = 0;
+    int max_px = 1;
+    std::vector<std::pair<int32_t, int32_t>> named(n);
+    for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_check(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+        named[b] = {maps[b], slots[b]};
+        const MapGeom &g = ms->geoms[geoms[b]];
+        const int32_t fr = shape4[4 * b], fc = shape4[4 * b + 1], rs = shape4[4 * b + 2], cs = shape4[4 * b + 3];
+        SFE_ARG(ctx, fr > 0 && fc > 0 && rs >= 1 && cs >= 1 && (long long)fr * fc < (1LL << 31));
+        // the full image is num_ranges x num_bearings of the slot's geometry
+        if ((fr + rs - 1) / rs != g.img_rows || (fc + cs - 1) / cs != g.img_cols)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "map set intensity: a %d x %d image at skips %d, %d is %d x %d, the geometry's "
+                               "image is %d x %d (job %d)", fr, fc, rs, cs, (fr + rs - 1) / rs, (fc + cs - 1) / cs, g.img_rows,
+                               g.img_cols, b);
+        if (!images) {
+            // every sampled byte inside the rows the caller describes
+            SFE_ARG(ctx, d_images[b] && stride[b] >= fc);
+        }
+        total += (size_t)fr * fc;
+        max_px = max(max_px, g.img_rows * g.img_cols);
+    }
+    std::sort(named.begin(), named.end());
+    SFE_ARG(ctx, std::adjacent_find(named.begin(), named.end()) == named.end()); // a slot holds one image
+    uint8_t *d_full = nullptr;
+    void *pin = nullptr;
+    if (images) {
+        d_full = (uint8_t *)buf_get(ctx, ms->buf[20], total);
+        pin = d_full ? sfe_pinned_begin(ctx, total) : nullptr;
+        if (!d_full || !pin)
+            return sfe_set_err(ctx, SFE_ERR_HIP, "map set intensity: staging of %zu bytes failed", total);
+    }
+    std::vector<SampleJob> jobs(n);
+    size_t off = 0;
+    for (int b = 0; b < n; ++b) {
+        if (int rc = set_slot_bind(ms, maps[b], slots[b], geoms[b]))
+            return rc;
+        const MapGeom &g = ms->geoms[geoms[b]];
+        SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[b])];
+        SampleJob &j = jobs[b];
+        j.img_rows = g.img_rows, j.img_cols = g.img_cols, j.r_skip = shape4[4 * b + 2], j.c_skip = shape4[4 * b + 3];
+        j.out = s.d_image;
+        if (images) {
+            j.src = d_full + off, j.stride = shape4[4 * b + 1];
+            off += (size_t)shape4[4 * b] * shape4[4 * b + 1];
+        } else {
+            j.src = (const uint8_t *)d_images[b], j.stride = stride[b];
+        }
+    }
+    if (images) {
+        memcpy(pin, images, total);
+        SFE_HIP(ctx, hipMemcpyAsync(d_full, pin, total, hipMemcpyHostToDevice, ctx->stream));
+        if (sfe_pinned_end(ctx, ctx->stream))
+            return sfe_set_err(ctx, SFE_ERR_HIP, "map set intensity: staging failed");
+    }
+    const SampleJob *d_jobs = buf_stage(ctx, ms->buf[19], jobs);
+    if (!d_jobs)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set intensity: job table upload failed");
+    hipLaunchKernelGGL(map_sample_kernel, dim3((unsigned)((max_px + MAP_THREADS - 1) / MAP_THREADS), (unsigned)n),
+                       dim3(MAP_THREADS), 0, ctx->stream, d_jobs);
+    SFE_LAUNCH_CHECK(ctx);
+    for (int b = 0; b < n; ++b) {
+        SetSlot &s = ms->slots[set_idx(ms, maps[b], slots[b])];
+        s.geom = geoms[b];
+        s.has_image = 1;
+    }
+    return 0;
+}
+
+int sfe_mapset_set_intensity(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                             const int32_t *shape4, const uint8_t *images)
+{
+    if (ms && n > 0)
+        SFE_ARG(ms->ctx, images);
+    return set_intensity(ms, n, maps, slots, geoms, shape4, images, nullptr, nullptr);
+}
+
+int sfe_mapset_set_intensity_dev(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *slots, const int32_t *geoms,
+                                 const int32_t *shape4, const void *const *d_images, const long long *row_stride)
+{
+    if (ms && n > 0)
+        SFE_ARG(ms->ctx, d_images && row_stride);
+    return set_intensity(ms, n, maps, slots, geoms, shape4, nullptr, d_images, row_stride);
+}
+
+int sfe_mapset_render_intensity(sfe_mapset *ms, int n, const int32_t *maps, const int32_t *box4, const long long *out_off,
+                                long long total, int8_t *out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, ms->intensity && n >= 0 && n <= 65535 && total >= 0 && (total == 0 || out));
+    SFE_ARG(ctx, n == 0 || (maps && box4 && out_off));
+    std::vector<RenderIJob> jobs;
+    int64_t max_out = 0;
+    for (int b = 0; b < n; ++b) {
+        SFE_ARG(ctx, maps[b] >= 0 && maps[b] < ms->n_maps);
+        const SetMap &m = ms->maps[maps[b]];
+        const int r0 = box4[4 * b], r1 = box4[4 * b + 1], c0 = box4[4 * b + 2], c1 = box4[4 * b + 3];
+        RenderIJob j;
+        j.grid_i = m.d_inten, j.grid_n = m.d_count, j.cols = m.cols;
+        j.r0 = r0, j.c0 = c0, j.h = r1 - r0 + 1, j.w = c1 - c0 + 1, j.out_off = out_off[b];
+        SFE_ARG(ctx, r0 >= 0 && c0 >= 0 && j.h > 0 && j.w > 0 && r1 < m.rows && c1 < m.cols);
+        SFE_ARG(ctx, j.out_off >= 0 && j.out_off + (int64_t)j.h * j.w <= total);
+        max_out = max(max_out, (int64_t)j.h * j.w);
+        jobs.push_back(j);
+    }
+    if (jobs.empty())
+        return 0;
+    const RenderIJob *d_jobs = buf_stage(ctx, ms->buf[0], jobs);
+    int8_t *d = (int8_t *)buf_get(ctx, ms->buf[1], (size_t)total);
+    if (!d_jobs || !d)
+        return sfe_set_err(ctx, SFE_ERR_HIP, "map set intensity render scratch allocation / upload failed");
+    const unsigned gx = (unsigned)std::min<int64_t>((max_out + MAP_THREADS - 1) / MAP_THREADS, 1 << 20);
+    hipLaunchKernelGGL(mapset_render_intensity_kernel, dim3(gx, (unsigned)jobs.size()), dim3(MAP_THREADS), 0, ctx->stream,
+                       d_jobs, d);
+    SFE_LAUNCH_CHECK(ctx);
+    // (bytes of `total` no job covers are whatever the scratch held: the offsets are the caller's)
+    SFE_HIP(ctx, hipMemcpyAsync(out, d, (size_t)total, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int sfe_mapset_read_intensity(sfe_mapset *ms, int map, uint32_t *intensity_out, uint16_t *counter_out, long long cap)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, ms->intensity && map >= 0 && map < ms->n_maps);
+    const SetMap &m = ms->maps[map];
+    const long long n = (long long)m.rows * m.cols;
+    SFE_ARG(ctx, cap >= n && (intensity_out || counter_out));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (intensity_out)
+        SFE_HIP(ctx, hipMemcpy(intensity_out, m.d_inten, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    if (counter_out)
+        SFE_HIP(ctx, hipMemcpy(counter_out, m.d_count, sizeof(uint16_t) * (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sfe_mapset_slot_intensity(sfe_mapset *ms, int map, int slot, uint8_t *image_out, int image_cap, uint8_t *i_out,
+                              int cells_cap, int *n_out)
+{
+    if (!ms)
+        return SFE_ERR_ARG;
+    sfe_ctx *ctx = ms->ctx;
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, ms->intensity);
+    if (int rc = set_slot_used(ms, map, slot))
+        return rc;
+    const SetSlot &s = ms->slots[set_idx(ms, map, slot)];
+    const MapGeom &g = ms->geoms[s.geom];
+    SFE_ARG(ctx, s.has_image);
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (image_out) {
+        SFE_ARG(ctx, image_cap >= g.img_rows * g.img_cols);
+        SFE_HIP(ctx, hipMemcpy(image_out, s.d_image, (size_t)g.img_rows * g.img_cols, hipMemcpyDeviceToHost));
+    }
+    if (i_out || n_out) {
+        // (the payload of a cell does not move with the growth that shifts its r and c: sfe_mapset_cells)
+        SFE_ARG(ctx, s.has_cells);
+        int32_t n = 0;
+        SFE_HIP(ctx, hipMemcpy(&n, s.d_n + s.cur, sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (n_out)
+            *n_out = n;
+        if (i_out) {
+            if (n > cells_cap)
+                return sfe_set_err(ctx, SFE_ERR_CAP, "map set slot intensity: %d cells, room for %d", n, cells_cap);
+            SFE_HIP(ctx, hipMemcpy(i_out, s.d_i[s.cur], (size_t)n, hipMemcpyDeviceToHost));
+        }
+    }
     return 0;
 }
 
@@ -2114,6 +2480,39 @@ int sfe_map_render2_store(sfe_map *m, sfe_cloud_store *store, int n_slots, const
     return sfe_mapset_render2_store(one(m), store, 1, &map, slot_off, slots, box4, &hd, &all, frame_off, frames, &f, &radius,
                                     &mp, &hs, origin2, &resolution, out_hw, &inv, &resize, &out_off, occ_out,
                                     (long long)out_h * out_w);
+}
+
+int sfe_map_enable_intensity(sfe_map *m) { return sfe_mapset_enable_intensity(one(m)); }
+
+int sfe_map_set_intensity(sfe_map *m, int slot, int geom, int full_rows, int full_cols, int r_skip, int c_skip,
+                          const uint8_t *image)
+{
+    const int32_t map = 0, s = slot, g = geom, shape4[4] = {full_rows, full_cols, r_skip, c_skip};
+    return sfe_mapset_set_intensity(one(m), 1, &map, &s, &g, shape4, image);
+}
+
+int sfe_map_set_intensity_dev(sfe_map *m, int slot, int geom, int full_rows, int full_cols, int r_skip, int c_skip,
+                              const void *d_image, long long row_stride)
+{
+    const int32_t map = 0, s = slot, g = geom, shape4[4] = {full_rows, full_cols, r_skip, c_skip};
+    return sfe_mapset_set_intensity_dev(one(m), 1, &map, &s, &g, shape4, &d_image, &row_stride);
+}
+
+int sfe_map_render_intensity(sfe_map *m, int r0, int r1, int c0, int c1, int8_t *out)
+{
+    const int32_t map = 0, box4[4] = {r0, r1, c0, c1};
+    const long long out_off = 0;
+    return sfe_mapset_render_intensity(one(m), 1, &map, box4, &out_off, (long long)(r1 - r0 + 1) * (c1 - c0 + 1), out);
+}
+
+int sfe_map_read_intensity(sfe_map *m, uint32_t *intensity_out, uint16_t *counter_out, long long cap)
+{
+    return sfe_mapset_read_intensity(one(m), 0, intensity_out, counter_out, cap);
+}
+
+int sfe_map_slot_intensity(sfe_map *m, int slot, uint8_t *image_out, int image_cap, uint8_t *i_out, int cells_cap, int *n_out)
+{
+    return sfe_mapset_slot_intensity(one(m), 0, slot, image_out, image_cap, i_out, cells_cap, n_out);
 }
 
 int sfe_remove_outlier_many(sfe_ctx *ctx, const float *pts, const int32_t *off, int n_clouds, double radius, int min_points,

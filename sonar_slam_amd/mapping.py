@@ -17,7 +17,13 @@ Method 2 (``get_occupancy_grid2``): the selection of the cloud by ``frames`` and
 keyframes' cell boxes) are taken here; marking the free cells from the keyframes' cell lists, the outlier filter, the
 projection, the inflation by the ellipse element and the resize run in one device call (sfe_map_render2), bit for bit the
 reference's int8 image.  With ``pub_occupancy1`` off a keyframe takes no measurement, as in the reference, and
-``get_occupancy_grid`` serves method 2.  Refused: the intensity grid.  INTEGRATION.md lists the deviations.
+``get_occupancy_grid`` serves method 2.
+
+The intensity mosaic (``pub_intensity``, ``get_intensity_grid``) is opt-in: the reference's line for it names two variables
+that exist nowhere (mapping.py:242), so ``pub_intensity=True`` alone is refused as before; with ``intensity_skips="oculus"``
+the ping is subsampled by the map's own skips and the mosaic is built on the device next to the log-odds grid: the same cell
+lists carry the ping's byte, the same applies update a uint32 sum grid and a uint16 counter grid.  The ping's image is
+``ping.ping`` or the keyword ``image=``.  INTEGRATION.md lists the deviations.
 """
 import contextlib
 import ctypes as C
@@ -93,8 +99,49 @@ class _Oculus(object):
         return changed
 
 
+class DeviceImage(object):
+    """a uint8 [rows x cols] ping that lies on the device: ``ptr`` (a ctypes.c_void_p, or an address) of its first byte,
+    ``stride`` bytes from one row to the next (``cols`` by default).  What ``MapBatch``'s ``images=`` takes in a list."""
+
+    def __init__(self, ptr, rows, cols, stride=None):
+        self.ptr = ptr if isinstance(ptr, C.c_void_p) else C.c_void_p(int(ptr))
+        self.shape = (int(rows), int(cols))
+        self.stride = int(cols if stride is None else stride)
+        if self.stride < self.shape[1]:
+            raise ValueError("DeviceImage: a row stride of %d bytes for %d columns" % (self.stride, self.shape[1]))
+
+
+def intensity_setting(what, pub_intensity, intensity_skips):
+    """-> whether the intensity mosaic is on.  ``intensity_skips``: None (the reference as it stands: ``pub_intensity`` cannot
+    run) or "oculus" (its ``r_skip`` / ``c_skip`` are the map's ``oculus_r_skip`` / ``oculus_c_skip``)."""
+    if intensity_skips is not None and intensity_skips != "oculus":
+        raise ValueError("%s: intensity_skips must be None or \"oculus\", got %r" % (what, intensity_skips))
+    if pub_intensity and intensity_skips is None:
+        raise NotImplementedError(
+            "%s: pub_intensity=True (the intensity grid) is not implemented as the reference writes it: its mapping.py:242 "
+            "subsamples the ping by r_skip and c_skip, names that are defined nowhere, so its first add_keyframe ends in "
+            "NameError.  Set intensity_skips=\"oculus\" to subsample by the map's own oculus_r_skip / oculus_c_skip, the only "
+            "values under which the pixels match sonar_xy" % what)
+    return bool(pub_intensity)
+
+
+def ping_image(what, ping, image, oculus):
+    """the full-size image of an add with the mosaic on: ``image`` or ``ping.ping`` -> uint8 [num_ranges x num_bearings],
+    contiguous (the stand-in for the reference's r2n(ping.ping))"""
+    src = image if image is not None else getattr(ping, "ping", None)
+    if src is None:
+        raise ValueError("%s: pub_intensity is on, so the add needs the ping's image: ping.ping or image=" % what)
+    img = np.asarray(src)
+    want = (int(oculus.num_ranges), int(oculus.num_bearings))
+    if img.dtype != np.uint8 or img.shape != want:
+        raise ValueError("%s: the ping's image is %s %r, the ping's geometry says uint8 %r (num_ranges x num_bearings)"
+                         % (what, img.dtype, img.shape, want))
+    return np.ascontiguousarray(img)
+
+
 class Submap(object):
-    """one keyframe: ``k`` and ``pose`` live on the host; ``r``, ``c``, ``l`` and ``logodds`` are read back from the device"""
+    """one keyframe: ``k`` and ``pose`` live on the host; ``r``, ``c``, ``l``, ``logodds`` and, with the intensity mosaic,
+    ``i`` and ``intensity`` are read back from the device"""
 
     def __init__(self, owner, slot):
         self._m = owner
@@ -127,6 +174,18 @@ class Submap(object):
         m = self._m
         return m._read_logodds(self._slot, int(np.prod(m._geom_shape[self.geom])))
 
+    @property
+    def intensity(self):
+        """the subsampled ping, raveled (mapping.py:243); None without the mosaic"""
+        m = self._m
+        return m._read_slot_intensity(self._slot, int(np.prod(m._geom_shape[self.geom])), True) if m._intensity else None
+
+    @property
+    def i(self):
+        """intensity[sel] of the current cell list (mapping.py:499); None without the mosaic"""
+        m = self._m
+        return m._read_slot_intensity(self._slot, int(np.prod(m._geom_shape[self.geom])), False) if m._intensity else None
+
     def cell_box(self):
         """(rmin, rmax, cmin, cmax) of its cells in the grid's current coordinates"""
         dr, dc = self._m._grow[0] - self.base[0], self._m._grow[1] - self.base[1]
@@ -152,11 +211,10 @@ class Mapping(object):
         self.oculus_r_skip = None
         self.oculus_c_skip = None
 
-        self.intensity_grid = None
-        self.counter_grid = None
-
         # method 1: log-odds update rule
         self.pub_intensity = False
+        self.intensity_skips = None   # None: pub_intensity is refused (mapping.py:242 cannot run); "oculus": the map's skips
+        self._intensity = False       # the mosaic is on (configure)
         self.pub_occupancy1 = True
         self.hit_prob = 0.8
         self.miss_prob = 0.3
@@ -187,6 +245,19 @@ class Mapping(object):
         self._hit_tabs = {}
         # the store feed since configure(): points fed, points the device left to the host, calls
         self.feed_stats = {"points": 0, "undecided": 0, "calls": 0}
+
+    @property
+    def intensity_grid(self):
+        """uint32 [rows x cols], read back; None without the mosaic, as in the reference"""
+        return self._read_intensity()[0] if self._intensity and self._live() else None
+
+    @property
+    def counter_grid(self):
+        """uint16 [rows x cols], read back; None without the mosaic"""
+        return self._read_intensity()[1] if self._intensity and self._live() else None
+
+    def _live(self):
+        return getattr(self, "_h", None) is not None
 
     @property
     def point_cloud(self):
@@ -235,12 +306,13 @@ class Mapping(object):
         h = C.c_void_p()
         self._check(self._lib.sfe_map_create(self.ctx.handle, self.rows, self.cols, C.byref(h)))
         self._h = h
+        if self._intensity:
+            self._check(self._lib.sfe_map_enable_intensity(self._h))
         self._hit_tabs = {}
         self.feed_stats = {"points": 0, "undecided": 0, "calls": 0}
 
     def _configure_host(self):
-        if self.pub_intensity:
-            raise NotImplementedError("Mapping.configure: pub_intensity=True (the intensity grid) is not implemented")
+        self._intensity = intensity_setting("Mapping.configure", self.pub_intensity, self.intensity_skips)
         self.hit_logodds = logit(self.hit_prob)
         self.miss_logodds = logit(self.miss_prob)
         xs = np.arange(0, self.width, self.resolution)
@@ -330,6 +402,21 @@ class Mapping(object):
         self._check(self._bound("logodds")(slot, _L.ptr(out, C.c_float), n))
         return out
 
+    def _read_intensity(self):
+        inten, count = np.zeros((self.rows, self.cols), np.uint32), np.zeros((self.rows, self.cols), np.uint16)
+        self._check(self._bound("read_intensity")(inten.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  count.ctypes.data_as(C.POINTER(C.c_uint16)), inten.size))
+        return inten, count
+
+    def _read_slot_intensity(self, slot, n, image):
+        out = np.zeros(n, np.uint8)
+        if image:
+            self._check(self._bound("slot_intensity")(slot, _L.ptr(out, C.c_uint8), n, None, 0, None))
+            return out
+        got = C.c_int(0)
+        self._check(self._bound("slot_intensity")(slot, None, 0, _L.ptr(out, C.c_uint8), n, C.byref(got)))
+        return out[:got.value].copy()
+
     def _read_grid(self, which):
         out = np.zeros((self.rows, self.cols), np.float32)
         self._check(self._bound("read_grid")(which, _L.ptr(out, C.c_float), out.size))
@@ -415,17 +502,34 @@ class Mapping(object):
                                                      _L.ptr(fh, C.c_int32)))
         return hits, prob, fh
 
-    def add_keyframe(self, key, pose, ping, points):
+    def _image_guard(self, what, image):
+        """what an add runs its geometry and measurement steps under: with the mosaic, ``_geometry_guard`` (a missing or
+        misshapen image leaves the map as it was); without it nothing, and ``image=`` is refused"""
+        if self._intensity:
+            return self._geometry_guard()
+        if image is not None:
+            raise ValueError("%s: image= without the intensity mosaic (pub_intensity with intensity_skips)" % what)
+        return contextlib.nullcontext()
+
+    def _set_image(self, kf, img):
+        self._check(self._lib.sfe_map_set_intensity(self._h, kf._slot, kf.geom, img.shape[0], img.shape[1],
+                                                    int(self.oculus_r_skip), int(self.oculus_c_skip), _L.ptr(img, C.c_uint8)))
+
+    def add_keyframe(self, key, pose, ping, points, image=None):
         self._check_supported()
-        kf = self._new_keyframe(pose, ping)
-        hits, hr, hc = self._hits(np.asarray(points) if len(points) else points)
-        self._measure(kf._slot, kf.geom, hits, hr, hc)
+        with self._image_guard("Mapping.add_keyframe", image):
+            kf = self._new_keyframe(pose, ping)
+            img = ping_image("Mapping.add_keyframe", ping, image, self.oculus) if self._intensity else None
+            hits, hr, hc = self._hits(np.asarray(points) if len(points) else points)
+            self._measure(kf._slot, kf.geom, hits, hr, hc)
+            if img is not None:
+                self._set_image(kf, img)
         if self.pub_occupancy2:
             self.point_cloud = points
         self._fit([kf], dec=False)
         self._append(key, kf)
 
-    def add_keyframe_store(self, key, pose, ping, store, handle):
+    def add_keyframe_store(self, key, pose, ping, store, handle, image=None):
         """``add_keyframe(key, pose, ping, store.read(handle))``, bit for bit, without the cloud leaving the device: the
         outlier filter, the hit cells and the measurement run from the store's pool (``store``: a CloudStore of this map's
         context).  In mapping_node.py's flow: ``handle, n, _ = fe.callback_store(ping, store)`` in place of the feature
@@ -441,9 +545,14 @@ class Mapping(object):
         if getattr(store, "ctx", None) is not self.ctx:
             raise ValueError("Mapping.add_keyframe_store: the store belongs to another context")
         handle = int(handle)
+        if image is not None and not self._intensity:
+            self._image_guard("Mapping.add_keyframe_store", image)
         with self._geometry_guard():
             kf = self._new_keyframe(pose, ping)
+            img = ping_image("Mapping.add_keyframe_store", ping, image, self.oculus) if self._intensity else None
             self._measure_store(kf, store, handle)
+            if img is not None:
+                self._set_image(kf, img)
         if self.pub_occupancy2:
             self._cloud_ref = (store, handle)
         self._fit([kf], dec=False)
@@ -459,14 +568,18 @@ class Mapping(object):
                       functools.partial(self._lib.sfe_map_measure_store_undecided, self._h),
                       functools.partial(self._lib.sfe_map_measure_store_finish, self._h))
 
-    def add_keyframe_logodds(self, key, pose, ping, logodds):
+    def add_keyframe_logodds(self, key, pose, ping, logodds, image=None):
         """add_keyframe with a ready polar log-odds image (float32, the downsampled image's shape) instead of points"""
         self._check_supported()
-        kf = self._new_keyframe(pose, ping)
-        lo = np.ascontiguousarray(logodds, np.float32).ravel()
-        if lo.size != int(np.prod(self.oculus_image_size)):
-            raise ValueError("add_keyframe_logodds: %d values for a %r image" % (lo.size, self.oculus_image_size))
-        self._check(self._lib.sfe_map_set_logodds(self._h, kf._slot, kf.geom, _L.ptr(lo, C.c_float)))
+        with self._image_guard("Mapping.add_keyframe_logodds", image):
+            kf = self._new_keyframe(pose, ping)
+            img = ping_image("Mapping.add_keyframe_logodds", ping, image, self.oculus) if self._intensity else None
+            lo = np.ascontiguousarray(logodds, np.float32).ravel()
+            if lo.size != int(np.prod(self.oculus_image_size)):
+                raise ValueError("add_keyframe_logodds: %d values for a %r image" % (lo.size, self.oculus_image_size))
+            self._check(self._lib.sfe_map_set_logodds(self._h, kf._slot, kf.geom, _L.ptr(lo, C.c_float)))
+            if img is not None:
+                self._set_image(kf, img)
         self._fit([kf], dec=False)
         self._append(key, kf)
 
@@ -599,11 +712,26 @@ class Mapping(object):
         return self._read_grid(1)
 
     def _check_supported(self):
-        if self.pub_intensity:
-            raise NotImplementedError("Mapping.add_keyframe: pub_intensity=True (the intensity grid) is not implemented")
+        if self.pub_intensity and not self._intensity:
+            raise NotImplementedError("Mapping.add_keyframe: pub_intensity=True (the intensity grid) was set after configure(): "
+                                      "the map was configured without it")
+
+    def _intensity_box(self, what):
+        """what get_intensity_grid needs, named when it is missing -> the box it renders"""
+        if not (self._intensity and self._live()):
+            raise NotImplementedError("%s: get_intensity_grid is not implemented for a map without the intensity grid: "
+                                      "configure() with pub_intensity=True and intensity_skips=\"oculus\"" % what)
+        if not any(kf is not None for kf in self.keyframes):
+            raise RuntimeError("%s: no keyframe yet, so there is no box to publish" % what)
+        return int(self.rmin), int(self.rmax), int(self.cmin), int(self.cmax)
 
     def get_intensity_grid(self):
-        raise NotImplementedError("Mapping.get_intensity_grid: the intensity grid is not implemented")
+        """mapping.py:272-298: the box of the mosaic, -1 where nothing was counted, else the mean intensity in percent"""
+        box = self._intensity_box("Mapping.get_intensity_grid")
+        occ = np.zeros((box[1] - box[0] + 1, box[3] - box[2] + 1), np.int8)
+        self._check(self._lib.sfe_map_render_intensity(self._h, box[0], box[1], box[2], box[3],
+                                                       occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return self._grid_msg(box, self.resolution, occ)
 
     def _check_method2(self, what, cloud):
         """what method 2 needs, named when it is missing.  (Before configure() the answer stays NotImplementedError, a
@@ -911,7 +1039,7 @@ def device_hit_table(v, tabs, register):
 
 
 # ---- S maps in lock-step ---------------------------------------------------------------------------------------------
-SETTINGS = ("x0", "y0", "width", "height", "inc", "resolution", "pub_intensity", "pub_occupancy1", "hit_prob", "miss_prob",
+SETTINGS = ("x0", "y0", "width", "height", "inc", "resolution", "pub_intensity", "intensity_skips", "pub_occupancy1", "hit_prob", "miss_prob",
             "inflation_angle", "inflation_range", "pub_occupancy2", "inflation_radius", "outlier_filter_radius",
             "outlier_filter_min_points", "min_translation", "min_rotation")
 
@@ -986,6 +1114,9 @@ class _SessionMap(Mapping):
         b = self._b
         return functools.partial(getattr(b._lib, "sfe_mapset_" + name), b._h, self._s)
 
+    def _live(self):
+        return getattr(self._b, "_h", None) is not None
+
     @property
     def logodds_grid(self):
         return self._read_grid(0)       # (its own _h stays None: the handle is the batch's)
@@ -1006,11 +1137,20 @@ class _SessionMap(Mapping):
                                                      _L.ptr(fh, C.c_int32)))
         return hits, prob, fh
 
-    def add_keyframe(self, key, pose, ping, points):
-        self._b.add_keyframes([self._s], [key], [pose], ping, [points])
+    def _images1(self, ping, image):
+        """the batch's images= for this one session"""
+        if image is None and self._intensity:
+            image = getattr(ping, "ping", None)
+        return None if image is None else [image]
 
-    def add_keyframe_logodds(self, key, pose, ping, logodds):
-        self._b.add_keyframes_logodds([self._s], [key], [pose], ping, [logodds])
+    def add_keyframe(self, key, pose, ping, points, image=None):
+        self._b.add_keyframes([self._s], [key], [pose], ping, [points], images=self._images1(ping, image))
+
+    def add_keyframe_logodds(self, key, pose, ping, logodds, image=None):
+        self._b.add_keyframes_logodds([self._s], [key], [pose], ping, [logodds], images=self._images1(ping, image))
+
+    def get_intensity_grid(self):
+        return self._b.get_intensity_grid([self._s])[0]
 
     def update_poses(self, keys, poses):
         self._b.update_poses([self._s] * len(keys), keys, poses)
@@ -1031,8 +1171,12 @@ class MapBatch(object):
 
     The settings are Mapping's attributes (keyword arguments, or set afterwards; then ``configure()`` or ``load_yaml()``, as
     with Mapping).  The device arena is sized here and never grows: ``max_keyframes`` keyframes per session of up to
-    ``max_pixels`` polar pixels each (the default holds a 1024 x 512 ping at the shipped skips), 20 bytes per pixel; one
-    keyframe more, or a larger image, raises."""
+    ``max_pixels`` polar pixels each (the default holds a 1024 x 512 ping at the shipped skips), 20 bytes per pixel (23 with
+    the intensity mosaic); one keyframe more, or a larger image, raises.
+
+    With the mosaic on (``pub_intensity=True, intensity_skips="oculus"``) every add takes ``images=``: the listed sessions'
+    full-size pings as one host ``uint8 [n x num_ranges x num_bearings]`` array (or a list of such images), or a list of
+    ``DeviceImage`` views of pings that already lie on the device, which are sampled in place."""
 
     def __init__(self, ctx=None, n_sessions=1, max_keyframes=256, max_pixels=1 << 17, **settings):
         if int(n_sessions) < 1 or int(max_keyframes) < 1 or int(max_pixels) < 1:
@@ -1049,13 +1193,13 @@ class MapBatch(object):
             setattr(self, name, v)
         self.maps = []
         self._h = None
-        self.last_apply_rounds = 0      # apply launches of the last add / update_poses call, as the device counted them
+        self._intensity = False         # the intensity mosaic is on (configure)
+        self.last_apply_rounds = 0     # apply launches of the last add / update_poses call, as the device counted them
 
     load_yaml = Mapping.load_yaml
 
     def configure(self):
-        if self.pub_intensity:
-            raise NotImplementedError("MapBatch.configure: pub_intensity=True (the intensity grid) is not implemented")
+        self._intensity = intensity_setting("MapBatch.configure", self.pub_intensity, self.intensity_skips)
         self.close()
         maps = []
         for s in range(self.S):
@@ -1073,6 +1217,8 @@ class MapBatch(object):
         self.ctx._check(self._lib.sfe_mapset_create(self.ctx.handle, self.S, maps[0].rows, maps[0].cols, self.max_keyframes,
                                                     self.max_pixels, C.byref(h)))
         self._h = h
+        if self._intensity:
+            self.ctx._check(self._lib.sfe_mapset_enable_intensity(self._h))
         self.maps = maps
         self._geoms = {}
         self._hit_tabs = {}
@@ -1092,8 +1238,25 @@ class MapBatch(object):
         except Exception:
             pass
 
-    def get_intensity_grid(self):
-        raise NotImplementedError("MapBatch.get_intensity_grid: the intensity grid is not implemented")
+    def get_intensity_grid(self, sessions=None):
+        """maps[s].get_intensity_grid() for the listed sessions (all by default) -> list of OccupancyGrid, rendered in one
+        device call"""
+        what = "MapBatch.get_intensity_grid"
+        if getattr(self, "_h", None) is None or not getattr(self, "_intensity", False):
+            raise NotImplementedError("%s: get_intensity_grid is not implemented for a batch without the intensity grid: "
+                                      "configure() with pub_intensity=True and intensity_skips=\"oculus\"" % what)
+        sessions = self._listed("get_intensity_grid", range(self.S) if sessions is None else sessions)
+        boxes = [self.maps[s]._intensity_box("%s (session %d)" % (what, s)) for s in sessions]
+        shapes = [(b[1] - b[0] + 1, b[3] - b[2] + 1) for b in boxes]
+        out_off = np.zeros(len(sessions) + 1, np.int64)
+        out_off[1:] = np.cumsum([h * w for h, w in shapes])
+        occ = np.zeros(max(1, int(out_off[-1])), np.int8)
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32).reshape(-1))
+        self._check(self._lib.sfe_mapset_render_intensity(
+            self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32(boxes), C.c_int32),
+            out_off.ctypes.data_as(C.POINTER(C.c_longlong)), int(out_off[-1]), occ.ctypes.data_as(C.POINTER(C.c_int8))))
+        return [self.maps[s]._grid_msg(b, self.maps[s].resolution, occ[out_off[j]:out_off[j + 1]].reshape(shp).copy())
+                for j, (s, b, shp) in enumerate(zip(sessions, boxes, shapes))]
 
     def get_occupancy_grid2(self, sessions=None, frames=None, resolution=None, point_clouds=None):
         """maps[s].get_occupancy_grid2(frames, resolution) for the listed sessions (all by default) -> list of OccupancyGrid,
@@ -1200,9 +1363,15 @@ class MapBatch(object):
                 raise IndexError("MapBatch.%s: session %d of %d" % (what, s, self.S))
         return sessions
 
-    def _begin(self, what, sessions, keys, poses, pings, data):
+    def _begin(self, what, sessions, keys, poses, pings, data, images=None):
         """the checks of an add call, before anything changes -> (sessions, pings, new keyframes)"""
         sessions = self._listed(what, sessions, keys, poses, data)
+        if self._intensity and images is None:
+            raise ValueError("MapBatch.%s: pub_intensity is on, so the add needs images= (the listed sessions' pings)" % what)
+        if not self._intensity and images is not None:
+            raise ValueError("MapBatch.%s: images= without the intensity mosaic (pub_intensity with intensity_skips)" % what)
+        if images is not None and len(images) != len(sessions):
+            raise ValueError("MapBatch.%s: %d sessions but %d images" % (what, len(sessions), len(images)))
         if isinstance(pings, (list, tuple)):
             if len(pings) != len(sessions):
                 raise ValueError("MapBatch.%s: %d sessions but %d pings" % (what, len(sessions), len(pings)))
@@ -1227,6 +1396,41 @@ class MapBatch(object):
                 v._restore_geometry(state)
             raise
 
+    def _images(self, what, sessions, pings, images):
+        """the checks of an add's images=, after the listed sessions took their pings' geometry -> what _set_images takes:
+        None (mosaic off), ("dev", views) or ("host", contiguous uint8 images)"""
+        if not self._intensity:
+            return None
+        if all(isinstance(im, DeviceImage) for im in images):
+            for s, im in zip(sessions, images):
+                o = self.maps[s].oculus
+                if im.shape != (int(o.num_ranges), int(o.num_bearings)):
+                    raise ValueError("MapBatch.%s: session %d's device image is %r, its ping's geometry says %r (num_ranges x "
+                                     "num_bearings)" % (what, s, im.shape, (int(o.num_ranges), int(o.num_bearings))))
+            return "dev", list(images)
+        if any(isinstance(im, DeviceImage) for im in images):
+            raise ValueError("MapBatch.%s: images= mixes device views and host images" % what)
+        return "host", [ping_image("MapBatch.%s (session %d)" % (what, s), ping, im, self.maps[s].oculus)
+                        for s, ping, im in zip(sessions, pings, images)]
+
+    def _set_images(self, sessions, kfs, images):
+        if images is None:
+            return
+        kind, imgs = images
+        i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32).reshape(-1))
+        views = [self.maps[s] for s in sessions]
+        shape4 = i32([[im.shape[0], im.shape[1], int(v.oculus_r_skip), int(v.oculus_c_skip)] for v, im in zip(views, imgs)])
+        head = (self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
+                _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(shape4, C.c_int32))
+        if kind == "dev":
+            ptrs = (C.c_void_p * len(imgs))(*[im.ptr.value for im in imgs])
+            strides = np.array([im.stride for im in imgs], np.int64)
+            self._check(self._lib.sfe_mapset_set_intensity_dev(*head, ptrs, strides.ctypes.data_as(C.POINTER(C.c_longlong))))
+        else:
+            flat = np.ascontiguousarray(np.concatenate([im.ravel() for im in imgs]))
+            with self.ctx.lock:        # the context's pinned staging
+                self._check(self._lib.sfe_mapset_set_intensity(*head, _L.ptr(flat, C.c_uint8)))
+
     def _end(self, sessions, keys, kfs):
         before = self._apply_launches()
         self._fit_many([(s, [(kf, kf.pose)]) for s, kf in zip(sessions, kfs)], dec=False)
@@ -1237,13 +1441,15 @@ class MapBatch(object):
             v._n_slots += 1
 
     # ---- the stages --------------------------------------------------------------------------------------------------
-    def add_keyframes(self, sessions, keys, poses, pings, points):
+    def add_keyframes(self, sessions, keys, poses, pings, points, images=None):
         """Mapping.add_keyframe for each listed session: ``pings`` one ping for all or one per session, ``points[i]`` the
-        cloud of ``sessions[i]``"""
-        sessions, pings = self._begin("add_keyframes", sessions, keys, poses, pings, points)
+        cloud of ``sessions[i]``, ``images[i]`` its ping's image (with the intensity mosaic, and only then)"""
+        sessions, pings = self._begin("add_keyframes", sessions, keys, poses, pings, points, images)
         with self._geometry_guard(sessions):
             kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            images = self._images("add_keyframes", sessions, pings, images)
             self._measure_many(sessions, kfs, points)
+            self._set_images(sessions, kfs, images)
         for v in self.maps:
             v._meas_job = -1
         for j, (s, p) in enumerate(zip(sessions, points)):
@@ -1263,7 +1469,7 @@ class MapBatch(object):
             _i32p(hit_off), _L.ptr(hits_all, C.c_int32),
             *kernel_tables(self, [self.maps[s] for s in sessions], [(hr, hc) for _, hr, hc in hits])))
 
-    def add_keyframes_store(self, sessions, keys, poses, pings, store, handles):
+    def add_keyframes_store(self, sessions, keys, poses, pings, store, handles, images=None):
         """``add_keyframes(sessions, keys, poses, pings, store.read_many(handles))``, bit for bit, without the clouds
         leaving the device: the outlier filter, the hit cells and the measurement of every listed session run from the
         store's pool (``store``: a CloudStore of this batch's context, ``handles[i]`` the cloud of ``sessions[i]``).
@@ -1272,12 +1478,14 @@ class MapBatch(object):
         undecided come back and go through ``_hit_indices`` here (``feed_stats`` counts them).  With ``pub_occupancy2``,
         ``maps[s].point_cloud`` is read from the store on access: the handle must still be live then."""
         handles = [int(h) for h in np.asarray(handles).reshape(-1)]
-        sessions, pings = self._begin("add_keyframes_store", sessions, keys, poses, pings, handles)
+        sessions, pings = self._begin("add_keyframes_store", sessions, keys, poses, pings, handles, images)
         if getattr(store, "ctx", None) is not self.ctx:
             raise ValueError("MapBatch.add_keyframes_store: the store belongs to another context")
         with self._geometry_guard(sessions):
             kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            images = self._images("add_keyframes_store", sessions, pings, images)
             self._measure_store(sessions, kfs, store, handles)
+            self._set_images(sessions, kfs, images)
         for v in self.maps:
             v._meas_job = -1
         for j, (s, h) in enumerate(zip(sessions, handles)):
@@ -1299,11 +1507,12 @@ class MapBatch(object):
                       functools.partial(self._lib.sfe_mapset_measure_store_undecided, self._h),
                       functools.partial(self._lib.sfe_mapset_measure_store_finish, self._h))
 
-    def add_keyframes_logodds(self, sessions, keys, poses, pings, logodds):
+    def add_keyframes_logodds(self, sessions, keys, poses, pings, logodds, images=None):
         """Mapping.add_keyframe_logodds for each listed session"""
-        sessions, pings = self._begin("add_keyframes_logodds", sessions, keys, poses, pings, logodds)
+        sessions, pings = self._begin("add_keyframes_logodds", sessions, keys, poses, pings, logodds, images)
         with self._geometry_guard(sessions):
             kfs = [self.maps[s]._new_keyframe(pose, ping) for s, pose, ping in zip(sessions, poses, pings)]
+            images = self._images("add_keyframes_logodds", sessions, pings, images)
             los = []
             for s, lo in zip(sessions, logodds):
                 lo = np.ascontiguousarray(lo, np.float32).ravel()
@@ -1315,6 +1524,7 @@ class MapBatch(object):
             self._check(self._lib.sfe_mapset_set_logodds(
                 self._h, len(sessions), _L.ptr(i32(sessions), C.c_int32), _L.ptr(i32([kf._slot for kf in kfs]), C.c_int32),
                 _L.ptr(i32([kf.geom for kf in kfs]), C.c_int32), _L.ptr(np.ascontiguousarray(np.concatenate(los)), C.c_float)))
+            self._set_images(sessions, kfs, images)
         self._end(sessions, keys, kfs)
 
     def _hits_many(self, sessions, clouds):

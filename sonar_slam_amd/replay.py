@@ -194,6 +194,10 @@ class FrontEnd(object):
                 raise ValueError("FrontEnd: mapping feed must be \"host\" or \"store\", got %r" % (mapping["feed"],))
             if mapping.get("feed", "host") == "store" and store is None:
                 raise ValueError("FrontEnd: mapping feed \"store\" needs a `store` (the keyframe clouds on the device)")
+            if mapping.get("pub_intensity"):
+                # (the front end receives feature messages, not pings: it has no image to hand the mosaic)
+                raise ValueError("FrontEnd: mapping with pub_intensity needs every keyframe's ping, which the front end never "
+                                 "sees; build the intensity mosaic with Mapping.add_keyframe(..., image=ping) instead")
         self.ctx = ctx
         self.shgo_replay = shgo_replay      # FrontEnd.shgo: replay of shgo's decisions from one table of costs (shgo_fast.py)
         self.store = store          # CloudStore: keyframe clouds stay on the device (feed_handle)

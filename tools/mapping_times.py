@@ -54,11 +54,24 @@ of `--reps` repetitions (`--feed host`: the host leg alone):
   lockstep               with `--sessions S` > 0: one MapBatch call for all S sessions by each route
   images_equal           both routes give the same images
 
+With `--intensity` only the intensity mosaic (pub_intensity with intensity_skips="oculus") is timed, under "intensity": two
+Mappings on the same session and pings in this process, the mosaic on and off, alternated call by call:
+  add_keyframe_ms        the median per add_keyframe from points over `--keyframes` keyframes: on, off, and the numpy
+                         restatement tests/intensity_ref.py (its first `--ref-adds` adds)
+  update_poses_ms        one update_poses call that moves all `--keyframes` keyframes, `--reps` alternated repetitions: on,
+                         off, and the restatement's update_pose loop (once)
+  render_ms              get_intensity_grid() over the whole box, device and numpy; images_equal
+  lockstep_feed          with `--sessions S` > 0: one add_keyframes call for S sessions over `--batch-keyframes` steps, two
+                         MapBatches alternated: `device` takes the S pings where they lie on the device (what
+                         chained.SessionBatch feeds from its resident frames), `host` the same pings as a host array (one
+                         upload of S pings per step); `off` is the same call without the mosaic
+
     python tools/mapping_times.py [--keyframes 1000] [--ref-adds 20] [--sessions 32] [--batch-keyframes 40] [--reps 5]
     python tools/mapping_times.py --sessions 32 --feed store
     python tools/mapping_times.py --feed store --batch-keyframes 200
     python tools/mapping_times.py --method 2 --sessions 32
     python tools/mapping_times.py --method 2 --feed store --sessions 32
+    python tools/mapping_times.py --intensity --sessions 32
 """
 import argparse
 import json
@@ -71,11 +84,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import intensity_ref  # noqa: E402
 import mapping2_ref  # noqa: E402
 import mapping_ref  # noqa: E402
 import oracle  # noqa: E402
 from sonar_slam_amd import _lib  # noqa: E402
-from sonar_slam_amd.mapping import MapBatch, Mapping  # noqa: E402
+from sonar_slam_amd.mapping import DeviceImage, MapBatch, Mapping  # noqa: E402
 from sonar_slam_amd.pose2 import Pose2  # noqa: E402
 
 
@@ -408,6 +422,108 @@ def method2_store(ctx, ping, settings, S, K, reps, routes):
     return out
 
 
+def intensity(ctx, ping, settings, n, ref_adds, S, K, reps):
+    """the intensity mosaic on against off, the numpy restatement, and the lock-step feed from device pings against host
+    pings -> the "intensity" record"""
+    poses, clouds = session(n)
+    rng = np.random.default_rng(11)
+    images = [rng.integers(0, 256, (ping.num_ranges, len(ping.bearings)), dtype=np.uint8) for _ in range(8)]
+    on_settings = dict(settings, pub_intensity=True, intensity_skips="oculus")
+    maps = {}
+    for name, st in (("on", on_settings), ("off", settings)):
+        m = Mapping(ctx)
+        for k, v in st.items():
+            setattr(m, k, v)
+        m.configure()
+        maps[name] = m
+    ref = intensity_ref.Mapping()
+    ref.remove_outlier = oracle.remove_outlier
+    for k, v in settings.items():
+        setattr(ref, k, v)
+    ref.configure()
+    add = {"on": lambda k: maps["on"].add_keyframe(k, Pose2(*poses[k]), ping, clouds[k], image=images[k % 8]),
+           "off": lambda k: maps["off"].add_keyframe(k, Pose2(*poses[k]), ping, clouds[k])}
+    t_add = {"on": [], "off": []}
+    for k in range(n):
+        for name in (("on", "off") if k % 2 == 0 else ("off", "on")):
+            t = timed(lambda: (add[name](k), ctx.sync()))
+            if k:                   # keyframe 0: geometry upload, first allocations
+                t_add[name].append(t)
+    t_ref = []
+    for k in range(n):
+        if k < ref_adds:
+            t_ref.append(timed(lambda: ref.add_keyframe(k, Pose2(*poses[k]), ping, clouds[k], image=images[k % 8])))
+        else:
+            ref.add_keyframe_logodds(k, Pose2(*poses[k]), ping, maps["on"].keyframes[k].logodds, image=images[k % 8])
+    med = lambda v: float(np.median(v))
+    out = {"keyframes": n, "image": list(maps["on"].oculus_image_size), "reps": reps,
+           "add_keyframe_ms": {"on": med(t_add["on"]), "off": med(t_add["off"]), "numpy": med(t_ref),
+                               "on_min": float(np.min(t_add["on"])), "off_min": float(np.min(t_add["off"]))}}
+    t_up = {"on": [], "off": []}
+    keys = list(range(n))
+    for r in range(reps + 1):
+        d = 0.7 if r % 2 == 0 else 0.0
+        new = [Pose2(poses[k][0] + d, poses[k][1] - d, poses[k][2] + 0.01 * d) for k in keys]
+        for name in (("on", "off") if r % 2 == 0 else ("off", "on")):
+            t = timed(lambda: (maps[name].update_poses(keys, new), ctx.sync()))
+            if r:                   # the first pass grows scratch buffers
+                t_up[name].append(t)
+        if r == 0:
+            def ref_loop():
+                for k in keys:
+                    ref.update_pose(k, new[k])
+            t_up["numpy"] = [timed(ref_loop)]
+    out["update_poses_ms"] = {name: med(v) for name, v in t_up.items()}
+    out["update_poses_ms"].update({name + "_min": float(np.min(t_up[name])) for name in ("on", "off")})
+    # (the restatement made the first move only: bring it to the maps' last poses before comparing)
+    if reps % 2 == 1:
+        for k in keys:
+            ref.update_pose(k, Pose2(*poses[k]))
+    maps["on"].get_intensity_grid()
+    rd = [timed(maps["on"].get_intensity_grid) for _ in range(3)]
+    rr = [timed(ref.get_intensity_grid) for _ in range(3)]
+    got, want = maps["on"].get_intensity_grid(), ref.get_intensity_grid()
+    out["render_ms"] = {"device": med(rd), "numpy": med(rr), "box": list(got.occ.shape)}
+    out["images_equal"] = bool(got.occ.shape == want.occ.shape and np.array_equal(got.occ, want.occ))
+    out["grids_equal"] = bool(np.array_equal(maps["on"].intensity_grid, ref.intensity_grid) and
+                              np.array_equal(maps["on"].counter_grid, ref.counter_grid) and
+                              np.array_equal(maps["on"].logodds_grid.view(np.int32), maps["off"].logodds_grid.view(np.int32)))
+    for m in maps.values():
+        m.close()
+    if S > 0:
+        rows, cols = images[0].shape
+        frames = np.stack([images[s % 8] for s in range(S)])
+        d_frames = ctx.alloc(frames.nbytes)
+        d_frames.upload(frames)
+        views = [DeviceImage(d_frames.ptr.value + s * rows * cols, rows, cols) for s in range(S)]
+        batches = {}
+        for name, st in (("device", on_settings), ("host", on_settings), ("off", settings)):
+            b = MapBatch(ctx, S, K, **st)
+            b.configure()
+            batches[name] = b
+        sessions = list(range(S))
+        kw = {"device": dict(images=views), "host": dict(images=frames), "off": {}}
+        t_feed = {name: [] for name in batches}
+        names = list(batches)
+        for k in range(K):
+            args = (sessions, [k] * S, [Pose2(poses[k][0] + s, poses[k][1], poses[k][2]) for s in sessions], ping, [clouds[k]] * S)
+            for name in names[k % 3:] + names[:k % 3]:
+                t = timed(lambda: (batches[name].add_keyframes(*args, **kw[name]), ctx.sync()))
+                if k:               # step 0: geometry upload, first allocations
+                    t_feed[name].append(t)
+        same = all(np.array_equal(batches["device"].maps[s].intensity_grid, batches["host"].maps[s].intensity_grid)
+                   for s in (0, S - 1))
+        out["lockstep_feed"] = {"sessions": S, "steps": K, "ping_bytes_per_step": int(frames.nbytes),
+                                "add_keyframes_ms": {name: med(v) for name, v in t_feed.items()},
+                                "add_keyframes_ms_min": {name: float(np.min(v)) for name, v in t_feed.items()},
+                                "apply_rounds": {name: b.last_apply_rounds for name, b in batches.items()},
+                                "grids_equal": bool(same)}
+        for b in batches.values():
+            b.close()
+        d_frames.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--keyframes", type=int, default=1000)
@@ -417,10 +533,17 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--feed", choices=("host", "store"), default=None)
     ap.add_argument("--method", type=int, choices=(1, 2), default=1, help="2: time get_occupancy_grid2 only")
+    ap.add_argument("--intensity", action="store_true", help="time the intensity mosaic only")
     a = ap.parse_args()
     n = a.keyframes
     ping = mapping_ref.SessionPing(512, 1024, 30.0 / 1024)
     settings = dict(x0=-100.0, y0=-100.0, width=200.0, height=200.0)
+    if a.intensity:
+        ctx = _lib.default_context()
+        print(json.dumps({"tool": "mapping_times", "device": ctx.name(),
+                          "intensity": intensity(ctx, ping, settings, a.keyframes, a.ref_adds, a.sessions or 0,
+                                                 a.batch_keyframes, a.reps)}))
+        return
     if a.method == 2 and a.feed is not None:
         ctx = _lib.default_context()
         routes = ("host", "store") if a.feed == "store" else ("host",)
