@@ -11,13 +11,15 @@
  *       match                                       -> sfe_match
  *       remove_outlier                              -> sfe_remove_outlier
  *       downsample (both overloads)                 -> sfe_downsample
+ *       ... the three on N x 3 clouds                -> sfe_match3, sfe_remove_outlier3, sfe_downsample3
  *       ICP.loadFromYaml / compute / getCovariance  -> sfe_icp_* (params parsed host-side)
  *   feature_extraction.py:223-238 (CFAR gate, cv2.remap, nonzero, px->m)
  *                                                   -> sfe_geom_*, sfe_remap_u8, sfe_extract_points
  *
  * Conventions
  *   - plain pointers and sizes only; images are row-major (C order, numpy default):
- *     rows = range bins, cols = beams.  Point clouds are N x 2 float32 row-major.
+ *     rows = range bins, cols = beams.  Point clouds are N x 2 float32 row-major
+ *     (N x 3 for the entry points whose name ends in 3).
  *     Transforms are 3 x 3 float32 row-major (Pose2 matrix).
  *   - entry points without a _dev suffix take HOST pointers (they copy in, run the
  *     HIP kernels, copy out) and are what the Python shims call.  *_dev entry points
@@ -242,6 +244,22 @@ int sfe_remove_outlier(sfe_ctx *ctx, const float *pts, int n, double radius, int
  * out_idx (nullable): their indices in the input (the descriptor overload gathers with them). */
 int sfe_downsample(sfe_ctx *ctx, const float *pts, int n, float resolution, float *out,
                    int32_t *out_idx, int *n_out);
+/* The five calls above on N x 3 clouds (pcl.cpp's functions are dimension-generic; the reference carries such clouds as
+ * Keyframe.points3D): the same arguments, points as packed float[n][3] (12-byte stride, no padding).  The rules are the
+ * 2-D rules with one more coordinate: d2 = ((dx dx + dy dy) + dz dz), every product and sum rounded to float; the
+ * octree is 8-way (child bit2 = z > centre z) with 3 key bits per level, so a tree deeper than 21 levels is cut there
+ * (the 2-D rank chain: 31).  A cloud with z = 0 gives the 2-D call's result.  Brute-force kernels, quadratic in the
+ * cloud size.  The 3-D downsample always writes out_idx (required) and has no resident route.  3-D ICP is not
+ * provided. */
+int sfe_match3(sfe_ctx *ctx, const float *ref, int n_ref, const float *in, int n_in, float max_dist,
+               int32_t *ids, float *d2);
+int sfe_match_knn3(sfe_ctx *ctx, const float *ref, int n_ref, const float *in, int n_in, int knn, float max_dist,
+                   int32_t *ids, float *d2);
+int sfe_knn_density3(sfe_ctx *ctx, const float *pts, int n, int knn, float *dens_out);
+int sfe_remove_outlier3(sfe_ctx *ctx, const float *pts, int n, double radius, int min_points,
+                        float *out, int *n_out);
+int sfe_downsample3(sfe_ctx *ctx, const float *pts, int n, float resolution, float *out,
+                    int32_t *out_idx, int *n_out);
 /* pcl.ICP.compute(source, target, guess) (pcl.cpp:198-212).  Returns SFE_ICP_* (>= 0) or a
  * hard error (< 0).  On a nonzero status T_out = guess (pcl.cpp:203,207-210). */
 int sfe_icp_compute(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src,

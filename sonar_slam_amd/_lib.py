@@ -181,6 +181,13 @@ SIGNATURES = {
     "sfe_remove_outlier": (C.c_int, [_vp, _f32p, C.c_int, C.c_double, C.c_int, _f32p,
                                      C.POINTER(C.c_int)]),
     "sfe_downsample": (C.c_int, [_vp, _f32p, C.c_int, C.c_float, _f32p, _i32p, C.POINTER(C.c_int)]),
+    # the same five on N x 3 clouds (sfe_pcl3.hip): points as packed float triples
+    "sfe_match3": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_float, _i32p, _f32p]),
+    "sfe_match_knn3": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, _i32p, _f32p]),
+    "sfe_knn_density3": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "sfe_remove_outlier3": (C.c_int, [_vp, _f32p, C.c_int, C.c_double, C.c_int, _f32p,
+                                      C.POINTER(C.c_int)]),
+    "sfe_downsample3": (C.c_int, [_vp, _f32p, C.c_int, C.c_float, _f32p, _i32p, C.POINTER(C.c_int)]),
     "sfe_icp_compute": (C.c_int, [_vp, C.POINTER(IcpParams), _f32p, C.c_int, _f32p, C.c_int, _f32p,
                                   _f32p, C.POINTER(C.c_int)]),
     "sfe_icp_compute_guesses": (C.c_int, [_vp, C.POINTER(IcpParams), _f32p, C.c_int, _f32p, C.c_int,

@@ -11,6 +11,13 @@ Same names and call signatures as ``PYBIND11_MODULE(pcl, m)``
     density_filter(points[, descriptors], knn, min_density, max_density)           pcl.cpp:76-126 (raises like
                    the reference does; knn_density / max_density_filter are the working pieces)
 
+Clouds are N x 2, or -- for ``match``, ``remove_outlier``, ``downsample``, ``knn_density`` and ``max_density_filter`` --
+N x 3, as pcl.cpp takes them (fromEigen labels a z row when mat.cols() == 3, pcl.cpp:23,39; every function returns
+topRows(mat_in.cols())): an N x 3 cloud goes to HIP kernels of its own (sfe_pcl3.hip; the 2-D rules with one more
+coordinate, an 8-way tree for ``downsample``; brute force, quadratic in the cloud size) and comes back N' x 3; ``match``
+wants both clouds of one width (RuntimeError otherwise, like libnabo).  ``ICP.compute*`` stays 2-D: N x 3 clouds and
+4 x 4 guesses raise NotImplementedError.
+
 Extension (not in the reference): ``ICP.compute_batch(source, target, guesses)`` runs the
 many-guesses-one-pair loop of SLAM.compute_icp_with_cov (slam.py:346-358) in one launch.
 ``ICP.loadFromYaml`` also takes the data-point filters of a chain (``icp_config.parse_icp_chain``); they run on the
@@ -36,16 +43,34 @@ def _cloud(a, name):
     return a
 
 
+def _cloud23(a, name):
+    """a cloud of the filter / matcher functions: N x 2, or N x 3 as the reference's pcl.cpp takes it (fromEigen labels
+    a z row when mat.cols() == 3, pcl.cpp:23,39).  ICP keeps ``_cloud``: 3-D ICP is not provided."""
+    a = _np.ascontiguousarray(a, _np.float32)
+    if a.ndim != 2 or a.shape[1] not in (2, 3):
+        raise TypeError("%s: expected an N x 2 or N x 3 array, got shape %r" % (name, a.shape))
+    return a
+
+
+def _fn(ctx, name, cloud):
+    """the library entry point ``name`` for the cloud's width (``name`` + "3" for N x 3)"""
+    return getattr(ctx.lib, name + "3" if cloud.shape[1] == 3 else name)
+
+
 def match(ref, pts, knn, max_dist, ctx=None):
     """KDTreeMatcher replacement (pcl.cpp:161-174): the knn exact nearest reference points of every query in
-    ascending (d2, index) order, squared distances, -1 / inf beyond max_dist.
+    ascending (d2, index) order, squared distances, -1 / inf beyond max_dist.  Both clouds N x 2 or both N x 3.
     -> (ids int32 [knn x N], dists float32 [knn x N]) like the pybind IntMatrix / Matrix pair."""
     knn = int(knn)
     if knn < 1:
         raise RuntimeError("pcl.match: knn must be >= 1, got %d" % knn)
+    ref = _cloud23(ref, "match(ref)")
+    pts = _cloud23(pts, "match(in)")
+    if ref.shape[1] != pts.shape[1]:
+        # libnabo: "Query has different dimensionality than the cloud" (a std::runtime_error)
+        raise RuntimeError("pcl.match: the reference cloud is N x %d and the query cloud N x %d (libnabo refuses a query "
+                           "of another dimensionality)" % (ref.shape[1], pts.shape[1]))
     ctx = ctx or _L.default_context()
-    ref = _cloud(ref, "match(ref)")
-    pts = _cloud(pts, "match(in)")
     if knn > len(ref):
         # libnabo: "Requesting more points (k) than available in cloud" (a std::runtime_error -> RuntimeError through
         # pybind); knn_density mirrors the same throw (ADVICE r2)
@@ -56,53 +81,56 @@ def match(ref, pts, knn, max_dist, ctx=None):
     if len(pts):
         with ctx.lock:
             if knn == 1:    # the SLAM node's only use (slam.py:418): one pass over the reference
-                ctx._check(ctx.lib.sfe_match(ctx.handle, _L.ptr(ref, _C.c_float), len(ref),
-                                             _L.ptr(pts, _C.c_float), len(pts), float(max_dist),
-                                             _L.ptr(ids, _C.c_int32), _L.ptr(d2, _C.c_float)))
+                ctx._check(_fn(ctx, "sfe_match", pts)(ctx.handle, _L.ptr(ref, _C.c_float), len(ref),
+                                                      _L.ptr(pts, _C.c_float), len(pts), float(max_dist),
+                                                      _L.ptr(ids, _C.c_int32), _L.ptr(d2, _C.c_float)))
             else:
-                ctx._check(ctx.lib.sfe_match_knn(ctx.handle, _L.ptr(ref, _C.c_float), len(ref),
-                                                 _L.ptr(pts, _C.c_float), len(pts), knn, float(max_dist),
-                                                 _L.ptr(ids, _C.c_int32), _L.ptr(d2, _C.c_float)))
+                ctx._check(_fn(ctx, "sfe_match_knn", pts)(ctx.handle, _L.ptr(ref, _C.c_float), len(ref),
+                                                          _L.ptr(pts, _C.c_float), len(pts), knn, float(max_dist),
+                                                          _L.ptr(ids, _C.c_int32), _L.ptr(d2, _C.c_float)))
     return ids, d2
 
 
 def remove_outlier(points, radius, min_points, ctx=None):
-    """PCL RadiusOutlierRemoval replacement (pcl.cpp:54-74)."""
+    """PCL RadiusOutlierRemoval replacement (pcl.cpp:54-74); N x 2 or N x 3 (pcl.cpp:61-62 sets .z), same width back."""
+    pts = _cloud23(points, "remove_outlier(points)")
     ctx = ctx or _L.default_context()
-    pts = _cloud(points, "remove_outlier(points)")
     out = _np.zeros_like(pts)
     n = _C.c_int(0)
     if len(pts):
         with ctx.lock:
-            ctx._check(ctx.lib.sfe_remove_outlier(ctx.handle, _L.ptr(pts, _C.c_float), len(pts),
-                                                  float(radius), int(min_points),
-                                                  _L.ptr(out, _C.c_float), _C.byref(n)))
+            ctx._check(_fn(ctx, "sfe_remove_outlier", pts)(ctx.handle, _L.ptr(pts, _C.c_float), len(pts),
+                                                           float(radius), int(min_points),
+                                                           _L.ptr(out, _C.c_float), _C.byref(n)))
     return out[:n.value].copy()
 
 
 def downsample(points, *args, **kw):
     """libpointmatcher OctreeGridDataPointsFilter replacement (pcl.cpp:128-159), both overloads:
     ``downsample(points, resolution)`` -> points' and
-    ``downsample(points, descriptors, resolution)`` -> (points', descriptors')."""
-    ctx = kw.pop("ctx", None) or _L.default_context()
+    ``downsample(points, descriptors, resolution)`` -> (points', descriptors').  N x 3 points go through the 8-way
+    tree libpointmatcher builds for 3-D features and come back N' x 3."""
+    ctx = kw.pop("ctx", None)
     if len(args) == 1:
         desc, resolution = None, args[0]
     elif len(args) == 2:
         desc, resolution = _np.ascontiguousarray(args[0], _np.float32), args[1]
     else:
         raise TypeError("downsample(points, resolution) or downsample(points, descriptors, resolution)")
-    pts = _cloud(points, "downsample(points)")
+    pts = _cloud23(points, "downsample(points)")
     if desc is not None and len(desc) != len(pts):
         raise TypeError("downsample: %d descriptors for %d points" % (len(desc), len(pts)))
     if len(pts) == 0:  # pcl.cpp:130-131,145-146
         return pts if desc is None else (pts, desc)
+    ctx = ctx or _L.default_context()
     out = _np.zeros_like(pts)
-    idx = _np.zeros(len(pts), _np.int32) if desc is not None else None   # (only the descriptor overload needs the indices)
+    # (only the descriptor overload needs the indices; the 3-D call always hands them back)
+    idx = _np.zeros(len(pts), _np.int32) if desc is not None or pts.shape[1] == 3 else None
     n = _C.c_int(0)
     with ctx.lock:
-        ctx._check(ctx.lib.sfe_downsample(ctx.handle, _L.ptr(pts, _C.c_float), len(pts), float(resolution),
-                                          _L.ptr(out, _C.c_float), _L.ptr(idx, _C.c_int32) if idx is not None else None,
-                                          _C.byref(n)))
+        ctx._check(_fn(ctx, "sfe_downsample", pts)(ctx.handle, _L.ptr(pts, _C.c_float), len(pts), float(resolution),
+                                                   _L.ptr(out, _C.c_float),
+                                                   _L.ptr(idx, _C.c_int32) if idx is not None else None, _C.byref(n)))
     out = out[:n.value].copy()
     return out if desc is None else (out, desc[idx[:n.value]].copy())
 
@@ -152,19 +180,19 @@ def srand(seed):
 def knn_density(points, knn, ctx=None):
     """The ``densities`` descriptor pcl.density_filter computes first (pcl.cpp:81-88): libpointmatcher
     SurfaceNormalDataPointsFilter{knn, keepDensities}: knn / ((4/3) pi r^3), r = the largest distance of one of the
-    point's knn nearest points (itself included) from their mean.  -> float32 [N]"""
-    ctx = ctx or _L.default_context()
-    pts = _cloud(points, "knn_density(points)")
+    point's knn nearest points (itself included) from their mean.  N x 2 or N x 3 points.  -> float32 [N]"""
+    pts = _cloud23(points, "knn_density(points)")
     knn = int(knn)
     if knn < 1:
         raise RuntimeError("knn_density: knn must be >= 1")
     if knn > len(pts):
         raise RuntimeError("Requesting more points than available in cloud")   # libnabo
+    ctx = ctx or _L.default_context()
     dens = _np.zeros(len(pts), _np.float32)
     if len(pts):
         with ctx.lock:
-            ctx._check(ctx.lib.sfe_knn_density(ctx.handle, _L.ptr(pts, _C.c_float), len(pts), knn,
-                                               _L.ptr(dens, _C.c_float)))
+            ctx._check(_fn(ctx, "sfe_knn_density", pts)(ctx.handle, _L.ptr(pts, _C.c_float), len(pts), knn,
+                                                        _L.ptr(dens, _C.c_float)))
     return dens
 
 
@@ -183,7 +211,7 @@ def max_density_filter(points, *args, **kw):
         desc, knn, max_density = _np.ascontiguousarray(args[0], _np.float32), args[1], args[2]
     else:
         raise TypeError("max_density_filter(points, [descriptors,] knn, max_density)")
-    pts = _cloud(points, "max_density_filter(points)")
+    pts = _cloud23(points, "max_density_filter(points)")
     if len(pts) == 0:
         return pts if desc is None else (pts, desc)
     dens = knn_density(pts, knn, ctx=ctx)
