@@ -11,6 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import mapping_ref  # noqa: E402
+from mapping_edges import data_agrees, ulps  # noqa: E402
 import oracle  # noqa: E402
 from sonar_slam_amd import _lib  # noqa: E402
 from sonar_slam_amd.mapping import Mapping  # noqa: E402
@@ -56,26 +57,6 @@ def state(m):
     return dict(box=[int(m.rmin), int(m.rmax), int(m.cmin), int(m.cmax)], x0=float(m.x0), y0=float(m.y0), rows=int(m.rows),
                 cols=int(m.cols), width=float(m.width), height=float(m.height), grid=sha(m.logodds_grid),
                 keyframes=sha(*[a for kf in kfs for a in (kf.r, kf.c, kf.l)]))
-
-
-def ulps(a, b):
-    ia = np.asarray(a, np.float32).view(np.int32).astype(np.int64)
-    ib = np.asarray(b, np.float32).view(np.int32).astype(np.int64)
-    ia = np.where(ia < 0, -(ia & 0x7FFFFFFF), ia)
-    ib = np.where(ib < 0, -(ib & 0x7FFFFFFF), ib)
-    return np.abs(ia - ib)
-
-
-def data_agrees(got, want, p100):
-    """int8 data equal, except where the reference's float32 100 p lies within a few ulp of an integer: there each cell may
-    differ by one.  -> number of such cells that differ"""
-    got, want = np.asarray(got, np.int64), np.asarray(want, np.int64)
-    assert got.shape == want.shape
-    diff = got != want
-    near = ulps(p100, np.round(p100).astype(np.float32)) <= 4
-    assert not (diff & ~near).any(), np.nonzero(diff & ~near)
-    assert (np.abs(got - want)[diff] == 1).all()
-    return int(diff.sum())
 
 
 @pytest.mark.parametrize("batched", [False, True])
