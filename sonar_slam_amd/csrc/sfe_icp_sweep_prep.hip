@@ -73,6 +73,35 @@ __device__ __forceinline__ void sweep_knn_normals(const sfe_icp_params &P, const
                 // stays is the tie rule's call; ties inside the list are looked for once, at the end of the search)
                 if (!EXACT && KM >= 2)
                     tie_seen |= bd[KM - 2] == bd[KM - 1] && bd[KM - 1] < INFINITY;
+                if constexpr (!EXACT) {
+                    // d < bd[KM-1] here.  Slot by slot from the end, every slot on its own: it keeps its entry, takes the
+                    // newcomer or takes the entry above it -- the distance is the median of the three, the position follows
+                    // the two compares (a compare, a median and two selects per slot: the exchange below takes five
+                    // instructions).  A slot whose entry stays for every lane of the wave ends the insertion: the list
+                    // is sorted, so nothing above it moves either (a fifth fewer vector instructions in the whole kernel at
+                    // the bench's shape: profiles/icp_prep_knn_times.txt, where the list as packed fp64 keys is measured too).
+                    static_assert(KM >= 2, "slot 0 is written in slot 1's step");
+                    bool below = true; // d < bd[k]
+#pragma unroll
+                    for (int k = KM - 1; k >= 1; --k) {
+                        const bool above = d < bd[k - 1];
+                        bj[k] = above ? bj[k - 1] : (below ? j : bj[k]);
+                        bd[k] = __builtin_amdgcn_fmed3f(bd[k - 1], bd[k], d);
+                        below = above;
+                        // (the slot is written here, in its own registers: left to itself the compiler first runs all the
+                        // compares down to the last slot that moves and then fills the slots through copies, six
+                        // instructions per slot)
+                        asm volatile("" : "+v"(bd[k]), "+v"(bj[k]));
+                        if (__builtin_amdgcn_ballot_w64(above) == 0)
+                            break;
+                        if (k == 1) {
+                            bj[0] = above ? j : bj[0];
+                            bd[0] = above ? d : bd[0];
+                        }
+                    }
+                    kth = bd[KM - 1];
+                    return;
+                }
                 bd[KM - 1] = d;
                 bj[KM - 1] = j;
 #pragma unroll
