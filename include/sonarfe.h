@@ -13,14 +13,15 @@
  *       downsample (both overloads)                 -> sfe_downsample
  *       ... the three on N x 3 clouds                -> sfe_match3, sfe_remove_outlier3, sfe_downsample3
  *       ICP.loadFromYaml / compute / getCovariance  -> sfe_icp_* (params parsed host-side)
+ *       ICP.compute on N x 3 clouds, 4 x 4 guesses  -> sfe_icp3_compute_jobs
  *   feature_extraction.py:223-238 (CFAR gate, cv2.remap, nonzero, px->m)
  *                                                   -> sfe_geom_*, sfe_remap_u8, sfe_extract_points
  *
  * Conventions
  *   - plain pointers and sizes only; images are row-major (C order, numpy default):
  *     rows = range bins, cols = beams.  Point clouds are N x 2 float32 row-major
- *     (N x 3 for the entry points whose name ends in 3).
- *     Transforms are 3 x 3 float32 row-major (Pose2 matrix).
+ *     (N x 3 for the entry points whose name ends in 3 or begins with sfe_icp3).
+ *     Transforms are 3 x 3 float32 row-major (Pose2 matrix); 4 x 4 for sfe_icp3_compute_jobs.
  *   - entry points without a _dev suffix take HOST pointers (they copy in, run the
  *     HIP kernels, copy out) and are what the Python shims call.  *_dev entry points
  *     take DEVICE pointers obtained from sfe_malloc and only enqueue work on the
@@ -249,8 +250,8 @@ int sfe_downsample(sfe_ctx *ctx, const float *pts, int n, float resolution, floa
  * 2-D rules with one more coordinate: d2 = ((dx dx + dy dy) + dz dz), every product and sum rounded to float; the
  * octree is 8-way (child bit2 = z > centre z) with 3 key bits per level, so a tree deeper than 21 levels is cut there
  * (the 2-D rank chain: 31).  A cloud with z = 0 gives the 2-D call's result.  Brute-force kernels, quadratic in the
- * cloud size.  The 3-D downsample always writes out_idx (required) and has no resident route.  3-D ICP is not
- * provided. */
+ * cloud size.  The 3-D downsample always writes out_idx (required) and has no resident route.  3-D ICP is
+ * sfe_icp3_compute_jobs, further down. */
 int sfe_match3(sfe_ctx *ctx, const float *ref, int n_ref, const float *in, int n_in, float max_dist,
                int32_t *ids, float *d2);
 int sfe_match_knn3(sfe_ctx *ctx, const float *ref, int n_ref, const float *in, int n_in, int knn, float max_dist,
@@ -281,6 +282,37 @@ int sfe_icp_compute_pairs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
 int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
                          int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
                          int32_t *status, int32_t *iters);
+/* pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (PM::ICP::compute, pcl.cpp:198-212, is dimension-generic; the
+ * reference carries such clouds as Keyframe.points3D): the point-to-point chain of the shipped config/icp.yaml, i.e.
+ * sfe_icp_params with minimizer == 0 (anything else: SFE_ERR_ARG, like a job slice that is empty or outside the clouds).
+ * Host pointers, the job table of sfe_icp_compute_jobs; src / tgt packed float[n][3], guesses16 / T_out16 4 x 4 row-major
+ * per job.  One workgroup per job, brute-force search (sfe_icp3.hip); jobs naming the same target slice share nothing.
+ * The route record of the last 2-D call stays as it is.  Rules, restated from libpointmatcher (parity unpinned, like the
+ * 2-D chain); where one also exists in 2-D it is the 2-D rule with one more coordinate, so that a job whose clouds have
+ * z = 0 and whose guess embeds a 3 x 3 guess reports the 2-D job's status and iterations and its pose to rounding:
+ *   frame     reference mean per axis: fp64 sum rounded to float; the reference is centred by a float subtraction.
+ *             T0 = translate(-mean) * guess, every 4 x 4 product entry (((a0 b0 + a1 b1) + a2 b2) + a3 b3) with each
+ *             product and sum rounded to float; r = T0 * source (the 3-term affine, same rounding); every iteration
+ *             matches c = T_iter * r.  Result T = translate(+mean) * (T_iter * T0); on a nonzero status T = the guess
+ *             and iterations are as run.
+ *   matcher   exact 1-NN, d2 = ((dx dx + dy dy) + dz dz) rounded at every step, no fma; ties: the lowest reference
+ *             index; a query with !(d2 <= fl(maxDist * maxDist)), NaN included, has no match (-1, inf).
+ *   outliers  MaxDist: d2 <= fl(maxDist^2).  Trimmed: d2 <= the k-th smallest of the n finite d2, k = (unsigned)((float)n
+ *             * ratio), n - 1 when ratio >= 1; none finite: SFE_ICP_NO_OUTLIER.  No pair kept: SFE_ICP_NO_POINT.
+ *   minimiser over the kept pairs (p = moved source point, q = its centred reference point) the fp64 sums W, sum p, sum q,
+ *             sum q p^T; mp = sum p / W, mq = sum q / W, H = sum q p^T - (sum q) mp^T; R = the proper rotation closest to
+ *             H (U V^T of the SVD H = U S V^T, the column of U of the smallest singular value negated when det < 0;
+ *             computed as the top eigenvector of Horn's 4 x 4 matrix by fp64 Jacobi sweeps, sfe_icp3_solve.h);
+ *             t = mq - R mp.  The step is rounded to float once, T_iter = T_step * T_iter.  H of rank <= 1 (all kept
+ *             pairs collinear) leaves R undetermined: some finite rotation comes back, no particular one.
+ *   checkers  Counter as in 2-D.  Differential: the history holds T_iter's float rotation block and translation, the
+ *             identity first (a sliding window of 64 entries); per step, in fp64 from those floats, the rotation error
+ *             is 2 atan2(|vec(q_i conj(q_i-1))|, |w|) with q the quaternion of the block by Eigen's branch rule (trace
+ *             > 0, else the largest diagonal entry), the translation error the norm of the difference; both averaged
+ *             over smoothLength and compared as in 2-D; NaN: SFE_ICP_NAN_ROT / SFE_ICP_NAN_TRANS. */
+int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
+                          int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
+                          int32_t *status, int32_t *iters);
 /* Data-point filters of a libpointmatcher ICP chain (readingDataPointsFilters / referenceDataPointsFilters), 2-D.
  * A stage keeps a point (x, y) when
  *   SFE_DPF_MAX_DIST     dim -1: sqrtf(x*x + y*y) < |f[0]|, dim 0 / 1: x / y < f[0]           (maxDist = f[0])

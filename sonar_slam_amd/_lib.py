@@ -196,6 +196,9 @@ SIGNATURES = {
                                         _f32p, _i32p, _i32p]),
     "sfe_icp_compute_jobs": (C.c_int, [_vp, C.POINTER(IcpParams), _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int,
                                        _f32p, _i32p, _i32p]),
+    # ... on N x 3 clouds with 4 x 4 guesses (sfe_icp3.hip): same job table, 16 floats per guess and per result
+    "sfe_icp3_compute_jobs": (C.c_int, [_vp, C.POINTER(IcpParams), _f32p, C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int,
+                                        _f32p, _i32p, _i32p]),
     "sfe_icp_filter_clouds_dev": (C.c_int, [_vp, C.POINTER(IcpDpf), C.c_int, _vp, _i32p, C.c_int, _vp, _i32p]),
     "sfe_icp_compute_guesses_chain": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpDpf), C.c_int, C.POINTER(IcpDpf),
                                                 C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p, C.c_int, _f32p, _i32p, _i32p]),

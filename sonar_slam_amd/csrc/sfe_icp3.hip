@@ -1,0 +1,533 @@
+// 3-D point-to-point ICP on gfx950: pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (pcl.cpp:198-212; PM::ICP is
+// dimension-generic), the module set of the shipped config/icp.yaml -- KDTreeMatcher {knn 1}, MaxDist and TrimmedDist outlier
+// filters, PointToPointErrorMinimizer, Counter and Differential transformation checkers (sfe_icp_params with minimizer 0).
+//
+// The rules (include/sonarfe.h at sfe_icp3_compute_jobs) are the 2-D chain's with one more coordinate:
+//   centre the target on its mean, T0 = translate(-mean) * guess, reading = T0 * source            (once)
+//   loop: cur = T_iter * reading
+//         exact 1-NN of every cur point in the target, d2 = ((dx dx + dy dy) + dz dz), lowest index on ties, none beyond maxDist
+//         keep = [d2 <= MaxDist^2] * [d2 <= quantile_ratio(finite d2)]
+//         T_step = the rigid motion that minimises the kept pairs' squared distances (sfe_icp3_solve.h), rounded to float
+//         T_iter = T_step * T_iter ; Counter / Differential checkers
+//   result = translate(+mean) * (T_iter * T0)
+//
+// Mapping: as icp_job_kernel of sfe_icp.hip.  ONE workgroup of 1024 threads runs the whole ICP of one job; the centred target
+// sits in LDS as three arrays (x, y, z: 48 KiB for 4096 points, padded with +inf) for all iterations, larger targets are
+// streamed through the same tile; a lane owns up to two source points per pass and scans the tile in index order with a strict
+// '<' (lowest index on ties); nearest distances and indices go to HBM scratch; the trimmed quantile is the radix select on the
+// float bit patterns; the 16 sums are reduced in fp64 in a fixed order; one lane solves and runs the checkers.
+// fp32 VALU + LDS broadcast reads, no MFMA.  LDS: 48 KiB tile + 2.1 KiB sums + 1 KiB histogram + 3 KiB history = 55 KiB,
+// so two workgroups fit the 160 KiB of a CU where the register count allows it.
+#include "sfe_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "sfe_icp_common.h"
+#include "sfe_icp3_solve.h"
+
+#define ICP3_TCAP 4096 // target points resident in LDS (48 KiB as three float arrays)
+#define ICP3_UNR 4     // target points per LDS read of the scan; the tile is padded to a multiple of it
+#define ICP3_PB 2      // source points per lane and pass over the target, at most (one LDS read serves both)
+
+static_assert(ICP3_TCAP % ICP3_UNR == 0, "the tile is read ICP3_UNR points at a time");
+static_assert(ICP3_NSUM == 16, "point-to-point in 3-D: W, sum p, sum q, sum q p^T");
+
+// c = a * b, 4 x 4 row-major, every entry (((a0 b0 + a1 b1) + a2 b2) + a3 b3) with each product and sum rounded to float
+__device__ __forceinline__ void mat4_mul(const float *a, const float *b, float *c)
+{
+    float r[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float s = f_mul(a[i * 4], b[j]);
+            s = f_add(s, f_mul(a[i * 4 + 1], b[4 + j]));
+            s = f_add(s, f_mul(a[i * 4 + 2], b[8 + j]));
+            s = f_add(s, f_mul(a[i * 4 + 3], b[12 + j]));
+            r[i * 4 + j] = s;
+        }
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+        c[i] = r[i];
+}
+
+// one row of a 4 x 4 transform on a point: ((a x + b y) + c z) + d, every product and sum rounded to float
+__device__ __forceinline__ float affine3(const float *row, float x, float y, float z)
+{
+    return f_add(f_add(f_add(f_mul(row[0], x), f_mul(row[1], y)), f_mul(row[2], z)), row[3]);
+}
+
+__device__ __forceinline__ float dist3(float px, float py, float pz, float tx, float ty, float tz)
+{
+    const float dx = f_add(px, -tx), dy = f_add(py, -ty), dz = f_add(pz, -tz);
+    return f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
+}
+
+struct Icp3Job {
+    int src_start, n_src, tgt_start, n_tgt;
+    long long scratch_off; // offset (in points) of this job's slice of the NN scratch
+};
+
+struct Icp3Shared {
+    float tx[ICP3_TCAP], ty[ICP3_TCAP], tz[ICP3_TCAP];
+    double red[ICP_WAVES * ICP3_NSUM + ICP3_NSUM];
+    unsigned hist[256];
+    unsigned sel_prefix, sel_k;
+    int flag_iterate, flag_status;
+    float Ti[16];
+    float mean[3];
+    float hist_T[ICP_MAX_HIST][12]; // rotation block (9, row-major) and translation (3) of T_iter after every step
+};
+static_assert(sizeof(((Icp3Shared *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3_NSUM + ICP3_NSUM),
+              "block_sum<ICP3_NSUM> needs (waves + 1) x ICP3_NSUM doubles");
+static_assert(sizeof(Icp3Shared) <= 64 * 1024, "two workgroups per CU");
+
+// load target points [base, base + n) of the job (packed float triples), centred on the mean, into the LDS tile (+inf pad)
+__device__ __forceinline__ void load_tile3(Icp3Shared &S, const float *__restrict__ tgt, int base, int n)
+{
+    const float mx = S.mean[0], my = S.mean[1], mz = S.mean[2];
+    const int npad = (n + ICP3_UNR - 1) / ICP3_UNR * ICP3_UNR;
+    for (int i = threadIdx.x; i < npad; i += ICP_THREADS) {
+        float x = INFINITY, y = INFINITY, z = INFINITY;
+        if (i < n) {
+            const float *t = tgt + 3 * (size_t)(base + i);
+            x = f_add(t[0], -mx);
+            y = f_add(t[1], -my);
+            z = f_add(t[2], -mz);
+        }
+        S.tx[i] = x;
+        S.ty[i] = y;
+        S.tz[i] = z;
+    }
+}
+
+// Exact arg-min over the LDS tile (tn points, global indices from tb) for NP query points per lane: index order and a strict
+// '<', so the lowest index wins among equal distances; NaN distances and the +inf pad never win.
+template <int NP>
+__device__ __forceinline__ void nn3_scan_tile(const Icp3Shared &S, int tn, int tb, const float (&px)[ICP3_PB],
+                                              const float (&py)[ICP3_PB], const float (&pz)[ICP3_PB], float (&best)[ICP3_PB],
+                                              int (&bi)[ICP3_PB])
+{
+    const int npad = (tn + ICP3_UNR - 1) / ICP3_UNR * ICP3_UNR;
+    for (int j = 0; j < npad; j += ICP3_UNR) {
+        const float4 x4 = *reinterpret_cast<const float4 *>(&S.tx[j]); // LDS broadcast reads
+        const float4 y4 = *reinterpret_cast<const float4 *>(&S.ty[j]);
+        const float4 z4 = *reinterpret_cast<const float4 *>(&S.tz[j]);
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            const float d0 = dist3(px[k], py[k], pz[k], x4.x, y4.x, z4.x);
+            const float d1 = dist3(px[k], py[k], pz[k], x4.y, y4.y, z4.y);
+            const float d2 = dist3(px[k], py[k], pz[k], x4.z, y4.z, z4.z);
+            const float d3 = dist3(px[k], py[k], pz[k], x4.w, y4.w, z4.w);
+            if (d0 < best[k]) {
+                best[k] = d0;
+                bi[k] = tb + j;
+            }
+            if (d1 < best[k]) {
+                best[k] = d1;
+                bi[k] = tb + j + 1;
+            }
+            if (d2 < best[k]) {
+                best[k] = d2;
+                bi[k] = tb + j + 2;
+            }
+            if (d3 < best[k]) {
+                best[k] = d3;
+                bi[k] = tb + j + 3;
+            }
+        }
+    }
+}
+
+// k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns): the radix select of job_select_kth (sfe_icp.hip) on this
+// kernel's shared block; called by the whole workgroup
+__device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
+{
+    if (tid == 0) {
+        S.sel_k = k_sel;
+        S.sel_prefix = 0;
+    }
+    __syncthreads();
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256)
+            S.hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = S.sel_prefix;
+        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int i = tid; i < ns; i += ICP_THREADS) {
+            const float d = nn_d2[i];
+            if (d != INFINITY) {
+                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
+                if ((u & himask) == prefix)
+                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned k = S.sel_k, b = 0;
+            for (; b < 255; ++b) { // (b stops at 255: the shift below stays inside the word whatever the histogram holds)
+                const unsigned h = S.hist[b];
+                if (k < h)
+                    break;
+                k -= h;
+            }
+            S.sel_k = k;
+            S.sel_prefix = prefix | (b << shift);
+        }
+        __syncthreads();
+    }
+    return __uint_as_float(S.sel_prefix);
+}
+
+// One lane: solve from the reduced sums, T_iter = T_step * T_iter (to LDS), then the Counter and Differential checkers in
+// libpointmatcher's order.  Checker state: nhist / counter / iters in the lane's registers, the history in LDS.  Not inlined:
+// the fp64 Jacobi sweeps want more registers than the scan loop, and one lane runs them once per iteration.
+__device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const double (&acc)[ICP3_NSUM], Icp3Shared &S,
+                                                     int &nhist, int &counter, int &iters, int &status, int &iterate)
+{
+    status = SFE_ICP_OK;
+    iterate = 1;
+    if (acc[0] == 0.0) {
+        status = SFE_ICP_NO_POINT;
+        return;
+    }
+    double R[9], t[3];
+    icp3_solve(acc, R, t);
+    const float Ts[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
+                          (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.0f,        0.0f,        0.0f,        1.0f};
+    float Ti[16], Tn[16];
+    for (int i = 0; i < 16; ++i)
+        Ti[i] = S.Ti[i];
+    mat4_mul(Ts, Ti, Tn);
+    for (int i = 0; i < 16; ++i)
+        S.Ti[i] = Tn[i];
+    ++iters;
+    ++counter;
+    if (counter >= P.max_iter) {
+        iterate = 0; // CounterTransformationChecker: MaxNumIterationsReached
+    } else if (P.use_diff_checker) {
+        if (nhist == ICP_MAX_HIST) { // keep a sliding window (only the last smooth_len + 1 entries are read)
+            for (int i = 1; i < ICP_MAX_HIST; ++i)
+                for (int k = 0; k < 12; ++k)
+                    S.hist_T[i - 1][k] = S.hist_T[i][k];
+            --nhist;
+        }
+        for (int r = 0; r < 3; ++r) {
+            for (int c = 0; c < 3; ++c)
+                S.hist_T[nhist][3 * r + c] = Tn[4 * r + c];
+            S.hist_T[nhist][9 + r] = Tn[4 * r + 3];
+        }
+        ++nhist;
+        // rotations.size() > smoothLength; size counts the init entry (= iters + 1)
+        if (iters + 1 > P.smooth_len) {
+            double rsum = 0, tsum = 0;
+            for (int i = nhist - 1; i >= nhist - P.smooth_len; --i) {
+                rsum += icp3_rot_dist(S.hist_T[i], S.hist_T[i - 1]);
+                const double dx = (double)S.hist_T[i][9] - S.hist_T[i - 1][9];
+                const double dy = (double)S.hist_T[i][10] - S.hist_T[i - 1][10];
+                const double dz = (double)S.hist_T[i][11] - S.hist_T[i - 1][11];
+                tsum += sqrt((dx * dx + dy * dy) + dz * dz);
+            }
+            rsum /= P.smooth_len;
+            tsum /= P.smooth_len;
+            if (rsum < P.min_diff_rot && tsum < P.min_diff_trans)
+                iterate = 0;
+            if (isnan(rsum))
+                status = SFE_ICP_NAN_ROT;
+            else if (isnan(tsum))
+                status = SFE_ICP_NAN_TRANS;
+        }
+    }
+}
+
+__global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P, const Icp3Job *__restrict__ jobs,
+                                                               const float *__restrict__ src_all,
+                                                               const float *__restrict__ tgt_all,
+                                                               const float *__restrict__ guess_all,
+                                                               float *__restrict__ nn_d2_all, int *__restrict__ nn_idx_all,
+                                                               float *__restrict__ T_out, int *__restrict__ status_out,
+                                                               int *__restrict__ iters_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    Icp3Shared &S = *reinterpret_cast<Icp3Shared *>(smem_raw);
+
+    const Icp3Job J = jobs[blockIdx.x];
+    const int ns = J.n_src, nt = J.n_tgt;
+    const float *__restrict__ src = src_all + 3 * (size_t)J.src_start;
+    const float *__restrict__ tgt = tgt_all + 3 * (size_t)J.tgt_start;
+    float *__restrict__ nn_d2 = nn_d2_all + J.scratch_off;
+    int *__restrict__ nn_idx = nn_idx_all + J.scratch_off;
+    const float *guess = guess_all + 16 * (size_t)blockIdx.x;
+    const int tid = threadIdx.x;
+    const bool resident = nt <= ICP3_TCAP;
+
+    // ---- reference mean (fp64 accumulation, rounded to float) ----
+    {
+        double m[3] = {0, 0, 0};
+        for (int i = tid; i < nt; i += ICP_THREADS) {
+            const float *t = tgt + 3 * (size_t)i;
+            m[0] += t[0];
+            m[1] += t[1];
+            m[2] += t[2];
+        }
+        block_sum<3>(m, S.red);
+        if (tid == 0) {
+            S.mean[0] = (float)(m[0] / nt);
+            S.mean[1] = (float)(m[1] / nt);
+            S.mean[2] = (float)(m[2] / nt);
+        }
+        __syncthreads();
+    }
+    const float mx = S.mean[0], my = S.mean[1], mz = S.mean[2];
+    if (resident) {
+        load_tile3(S, tgt, 0, nt);
+        __syncthreads();
+    }
+
+    // ---- T0 = translate(-mean) * guess ; T_iter = I ----
+    float T0[16];
+    {
+        const float Tc[16] = {1, 0, 0, -mx, 0, 1, 0, -my, 0, 0, 1, -mz, 0, 0, 0, 1};
+        float g[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            g[i] = guess[i];
+        mat4_mul(Tc, g, T0);
+    }
+    if (tid == 0) {
+        for (int i = 0; i < 16; ++i)
+            S.Ti[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        for (int k = 0; k < 12; ++k) // DifferentialTransformationChecker::init pushes the identity
+            S.hist_T[0][k] = (k == 0 || k == 4 || k == 8) ? 1.0f : 0.0f;
+        S.flag_iterate = 1;
+        S.flag_status = SFE_ICP_OK;
+    }
+    __syncthreads();
+    int nhist = 1, counter = 0, iters = 0; // thread 0's
+
+    const float r2_match = f_mul(P.matcher_max_dist, P.matcher_max_dist);
+    const float r2_filter = f_mul(P.max_dist_filter, P.max_dist_filter);
+
+    while (true) {
+        float Ti[12];
+#pragma unroll
+        for (int i = 0; i < 12; ++i)
+            Ti[i] = S.Ti[i];
+
+        // ---- match: exact 1-NN of cur = Ti * (T0 * src) in the centred target ----
+        double nfin_d[1] = {0};
+        for (int base = 0; base < ns; base += ICP_THREADS * ICP3_PB) {
+            const int np = (ns - base > ICP_THREADS) ? ICP3_PB : 1; // uniform: queries per lane in this pass
+            float px[ICP3_PB], py[ICP3_PB], pz[ICP3_PB], best[ICP3_PB];
+            int bi[ICP3_PB];
+#pragma unroll
+            for (int k = 0; k < ICP3_PB; ++k) {
+                const int i = base + k * ICP_THREADS + tid;
+                float x = 0, y = 0, z = 0;
+                if (k < np && i < ns) {
+                    const float *s = src + 3 * (size_t)i;
+                    const float sx = s[0], sy = s[1], sz = s[2];
+                    const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+                    x = affine3(Ti, rx, ry, rz);
+                    y = affine3(Ti + 4, rx, ry, rz);
+                    z = affine3(Ti + 8, rx, ry, rz);
+                }
+                px[k] = x;
+                py[k] = y;
+                pz[k] = z;
+                best[k] = INFINITY;
+                bi[k] = -1;
+            }
+            for (int tb = 0; tb < nt; tb += ICP3_TCAP) {
+                const int tn = min(ICP3_TCAP, nt - tb);
+                if (!resident) {
+                    __syncthreads();
+                    load_tile3(S, tgt, tb, tn);
+                    __syncthreads();
+                }
+                if (np == 1)
+                    nn3_scan_tile<1>(S, tn, tb, px, py, pz, best, bi);
+                else
+                    nn3_scan_tile<ICP3_PB>(S, tn, tb, px, py, pz, best, bi);
+            }
+#pragma unroll
+            for (int k = 0; k < ICP3_PB; ++k) {
+                const int i = base + k * ICP_THREADS + tid;
+                if (k < np && i < ns) {
+                    float d = best[k];
+                    int id = bi[k];
+                    if (id < 0 || !(d <= r2_match)) { // (id < 0: nothing nearer than +inf, NaN included)
+                        id = -1;
+                        d = INFINITY;
+                    } else {
+                        nfin_d[0] += 1.0;
+                    }
+                    nn_d2[i] = d;
+                    nn_idx[i] = id;
+                }
+            }
+        }
+        block_sum<1>(nfin_d, S.red); // also orders the nn_d2 / nn_idx stores before the re-reads below
+        const unsigned nfin = (unsigned)nfin_d[0];
+
+        // ---- TrimmedDistOutlierFilter limit: exact order statistic by radix select ----
+        float limit = INFINITY;
+        if (P.use_trimmed_filter) {
+            if (nfin == 0) { // "no outlier to filter" (uniform: every thread leaves)
+                if (tid == 0)
+                    S.flag_status = SFE_ICP_NO_OUTLIER;
+                break;
+            }
+            const unsigned k_sel = (P.trim_ratio >= 1.0f) ? nfin - 1 : (unsigned)f_mul((float)nfin, P.trim_ratio);
+            limit = job3_select_kth(S, nn_d2, ns, tid, min(k_sel, nfin - 1));
+            __syncthreads();
+        }
+
+        // ---- error minimiser: accumulate over kept pairs ----
+        double acc[ICP3_NSUM];
+#pragma unroll
+        for (int i = 0; i < ICP3_NSUM; ++i)
+            acc[i] = 0;
+        for (int i = tid; i < ns; i += ICP_THREADS) {
+            const int id = nn_idx[i];
+            const float d = nn_d2[i];
+            if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit)))
+                continue;
+            const float *s = src + 3 * (size_t)i;
+            const float sx = s[0], sy = s[1], sz = s[2];
+            const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+            const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
+            double q[3];
+            if (resident) {
+                q[0] = S.tx[id];
+                q[1] = S.ty[id];
+                q[2] = S.tz[id];
+            } else {
+                const float *t = tgt + 3 * (size_t)id;
+                q[0] = f_add(t[0], -mx);
+                q[1] = f_add(t[1], -my);
+                q[2] = f_add(t[2], -mz);
+            }
+            acc[0] += 1.0;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                acc[1 + a] += p[a];
+                acc[4 + a] += q[a];
+#pragma unroll
+                for (int b = 0; b < 3; ++b)
+                    acc[7 + 3 * a + b] += q[a] * p[b];
+            }
+        }
+        block_sum<ICP3_NSUM>(acc, S.red);
+
+        // ---- solve, compose, check (thread 0) ----
+        if (tid == 0) {
+            int status, iterate;
+            icp3_solve_and_check(P, acc, S, nhist, counter, iters, status, iterate);
+            S.flag_status = status;
+            S.flag_iterate = (status == SFE_ICP_OK) ? iterate : 0;
+        }
+        __syncthreads();
+        if (!S.flag_iterate)
+            break;
+    }
+    __syncthreads(); // (the break on "no outlier to filter": thread 0's status store before it is read)
+
+    if (tid == 0) {
+        const int status = S.flag_status;
+        float *To = T_out + 16 * (size_t)blockIdx.x;
+        if (status == SFE_ICP_OK) {
+            const float Tfwd[16] = {1, 0, 0, mx, 0, 1, 0, my, 0, 0, 1, mz, 0, 0, 0, 1};
+            float Ti[16], tmp[16], res[16];
+            for (int i = 0; i < 16; ++i)
+                Ti[i] = S.Ti[i];
+            mat4_mul(Ti, T0, tmp);
+            mat4_mul(Tfwd, tmp, res);
+            for (int i = 0; i < 16; ++i)
+                To[i] = res[i];
+        } else {
+            for (int i = 0; i < 16; ++i) // pcl.cpp:203,207-210: T stays the guess
+                To[i] = guess[i];
+        }
+        status_out[blockIdx.x] = status;
+        iters_out[blockIdx.x] = iters;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+static int check_params3(sfe_ctx *ctx, const sfe_icp_params *p)
+{
+    SFE_ARG(ctx, p != nullptr);
+    if (p->minimizer != 0)
+        return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP runs the point-to-point error minimiser only (minimizer = %d)", p->minimizer);
+    SFE_ARG(ctx, p->max_iter >= 1);
+    SFE_ARG(ctx, !p->use_diff_checker || (p->smooth_len >= 1 && p->smooth_len < ICP_MAX_HIST));
+    SFE_ARG(ctx, !p->use_trimmed_filter || (p->trim_ratio >= 0.0f && p->trim_ratio <= 1.0f));
+    SFE_ARG(ctx, p->matcher_max_dist > 0.0f);
+    return 0;
+}
+
+extern "C" {
+
+int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
+                          int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
+                          int32_t *status, int32_t *iters)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (int rc = check_params3(ctx, p))
+        return rc;
+    SFE_ARG(ctx, n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
+                     (n_jobs == 0 || (src && tgt && jobs4 && guesses16 && T_out16 && status)));
+    if (n_jobs == 0)
+        return 0;
+    std::vector<Icp3Job> jobs((size_t)n_jobs);
+    long long soff = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t *q = jobs4 + 4 * (size_t)j;
+        if (q[0] < 0 || q[1] <= 0 || q[2] < 0 || q[3] <= 0 || (long long)q[0] + q[1] > n_src_pts ||
+            (long long)q[2] + q[3] > n_tgt_pts)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP job %d (%d+%d, %d+%d) is empty or lies outside the clouds (%d, %d points)",
+                               j, q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
+        jobs[j] = {q[0], q[1], q[2], q[3], soff};
+        soff += q[1];
+    }
+    const size_t b_src = sizeof(float) * 3 * (size_t)n_src_pts, b_tgt = sizeof(float) * 3 * (size_t)n_tgt_pts;
+    const size_t b_g = sizeof(float) * 16 * (size_t)n_jobs, b_st = sizeof(int32_t) * (size_t)n_jobs, b_out = b_g + 2 * b_st;
+    const size_t b_jobs = sizeof(Icp3Job) * (size_t)n_jobs;
+    float *d_src = (float *)sfe_scratch(ctx, 0, b_src);
+    float *d_tgt = (float *)sfe_scratch(ctx, 1, b_tgt);
+    float *d_g = (float *)sfe_scratch(ctx, 2, b_g);
+    char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
+    Icp3Job *d_jobs = (Icp3Job *)sfe_scratch(ctx, 4, b_jobs);
+    float *d_nn_d2 = (float *)sfe_scratch(ctx, 5, sizeof(float) * (size_t)soff);
+    int *d_nn_idx = (int *)sfe_scratch(ctx, 6, sizeof(int) * (size_t)soff);
+    // pinned blocks both ways: [guesses | job table] up, [T | status | iterations] down
+    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_g + b_jobs);
+    char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
+    if (!d_src || !d_tgt || !d_g || !d_out || !d_jobs || !d_nn_d2 || !d_nn_idx || !h_in || !h_out)
+        return SFE_ERR_HIP;
+    memcpy(h_in, guesses16, b_g);
+    memcpy(h_in + b_g, jobs.data(), b_jobs);
+    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, b_src, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, b_tgt, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_g, h_in, b_g, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_jobs, h_in + b_g, b_jobs, hipMemcpyHostToDevice, ctx->stream));
+    int32_t *d_st = (int32_t *)(d_out + b_g);
+    SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)sizeof(Icp3Shared)));
+    hipLaunchKernelGGL(icp3_job_kernel, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Icp3Shared), ctx->stream, *p, d_jobs, d_src,
+                       d_tgt, d_g, d_nn_d2, d_nn_idx, (float *)d_out, d_st, d_st + n_jobs);
+    SFE_LAUNCH_CHECK(ctx);
+    SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    memcpy(T_out16, h_out, b_g);
+    memcpy(status, h_out + b_g, b_st);
+    if (iters)
+        memcpy(iters, h_out + b_g + b_st, b_st);
+    return 0;
+}
+
+} // extern "C"

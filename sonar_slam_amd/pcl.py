@@ -15,8 +15,10 @@ Clouds are N x 2, or -- for ``match``, ``remove_outlier``, ``downsample``, ``knn
 N x 3, as pcl.cpp takes them (fromEigen labels a z row when mat.cols() == 3, pcl.cpp:23,39; every function returns
 topRows(mat_in.cols())): an N x 3 cloud goes to HIP kernels of its own (sfe_pcl3.hip; the 2-D rules with one more
 coordinate, an 8-way tree for ``downsample``; brute force, quadratic in the cloud size) and comes back N' x 3; ``match``
-wants both clouds of one width (RuntimeError otherwise, like libnabo).  ``ICP.compute*`` stays 2-D: N x 3 clouds and
-4 x 4 guesses raise NotImplementedError.
+wants both clouds of one width (RuntimeError otherwise, like libnabo).  ``ICP.compute*`` takes N x 3 clouds with 4 x 4
+guesses too (PM::ICP::compute is dimension-generic) and returns 4 x 4 transforms: the point-to-point chain of the shipped
+icp.yaml on a HIP kernel of its own (sfe_icp3.hip, brute force); mixed widths, data-point filters, the MinDist / MedianDist
+/ Bound modules and point-to-plane raise NotImplementedError on 3-D input.
 
 Extension (not in the reference): ``ICP.compute_batch(source, target, guesses)`` runs the
 many-guesses-one-pair loop of SLAM.compute_icp_with_cov (slam.py:346-358) in one launch.
@@ -45,7 +47,7 @@ def _cloud(a, name):
 
 def _cloud23(a, name):
     """a cloud of the filter / matcher functions: N x 2, or N x 3 as the reference's pcl.cpp takes it (fromEigen labels
-    a z row when mat.cols() == 3, pcl.cpp:23,39).  ICP keeps ``_cloud``: 3-D ICP is not provided."""
+    a z row when mat.cols() == 3, pcl.cpp:23,39).  The 2-D-only callers keep ``_cloud``."""
     a = _np.ascontiguousarray(a, _np.float32)
     if a.ndim != 2 or a.shape[1] not in (2, 3):
         raise TypeError("%s: expected an N x 2 or N x 3 array, got shape %r" % (name, a.shape))
@@ -341,15 +343,89 @@ class ICP(object):
             raise TypeError("ICP.compute: guess must be 3 x 3, got %r" % (g.shape,))
         return _np.ascontiguousarray(g)
 
+    # ---- N x 3 clouds with 4 x 4 guesses: the point-to-point chain on sfe_icp3_compute_jobs ----
+    @staticmethod
+    def _is3d(clouds, guess_shapes, what):
+        """True when the call is a 3-D one: every cloud N x 3 and every guess 4 x 4.  False: leave it to the 2-D path
+        (whose ``_cloud`` / ``_guess`` refuse what it does not take).  Mixed input raises here."""
+        widths = set(_np.shape(c)[1] for c in clouds if _np.ndim(c) == 2 and _np.shape(c)[1] in (2, 3))
+        if len(widths) == 2:
+            raise NotImplementedError("%s: source and target of different widths (N x 2 with N x 3): libpointmatcher "
+                                      "matches clouds of one dimension only" % what)
+        if widths != {3}:
+            return False
+        if any(tuple(s) == (3, 3) for s in guess_shapes):
+            raise NotImplementedError("%s: N x 3 clouds with a 3 x 3 guess: a 3-D cloud needs a 4 x 4 transform "
+                                      "(PM::ICP::compute checks the guess against the cloud's dimension)" % what)
+        for s in guess_shapes:
+            if tuple(s) != (4, 4):
+                raise TypeError("%s: guess must be 4 x 4 for N x 3 clouds, got %r" % (what, tuple(s)))
+        return True
+
+    def _chain3(self, what):
+        """the chain's params for a 3-D call; the modules that exist in 2-D only are refused"""
+        p = self._chain()
+        if self._stages() is not None:
+            raise NotImplementedError("%s: data-point filters on N x 3 clouds: the device stages of a chain are 2-D "
+                                      "(sfe_icp_dpf); filter the clouds with pcl.downsample / remove_outlier first" % what)
+        if self._outliers() is not None:
+            raise NotImplementedError("%s: MinDist / MedianDist outlier filters and the Bound checker on N x 3 clouds: "
+                                      "the 3-D kernel runs the modules of the shipped icp.yaml only" % what)
+        if p.minimizer == 1:
+            raise NotImplementedError("%s: PointToPlaneErrorMinimizer on N x 3 clouds: the normal equations here are "
+                                      "the 2-D ones; 3-D ICP is point-to-point" % what)
+        return p
+
+    def _call3(self, ctx, src, tgt, jobs4, g, T, st, it):
+        n = len(jobs4)
+        with ctx.lock:
+            ctx._check(ctx.lib.sfe_icp3_compute_jobs(ctx.handle, _C.byref(self.params), _L.ptr(src, _C.c_float), len(src),
+                                                     _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(jobs4, _C.c_int32),
+                                                     _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                                                     _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+
+    def _pairs3(self, srcs, tgts, guesses, what):
+        """3-D jobs (source cloud, target cloud, guess) -> (messages, T [n x 4 x 4], iterations)"""
+        self._chain3(what)
+        ctx = self._ctx or _L.default_context()
+        srcs = [_cloud23(s, what + "(source)") for s in srcs]
+        tgts = [_cloud23(t, what + "(target)") for t in tgts]
+        if any(len(s) == 0 for s in srcs) or any(len(t) == 0 for t in tgts):
+            raise RuntimeError("%s: empty point cloud (libpointmatcher would throw)" % what)
+        n = len(guesses)
+        g = _np.ascontiguousarray(_np.stack([_np.asarray(x, _np.float32) for x in guesses]), _np.float32)
+        # a cloud handed in several times (compute_batch: one pair, many guesses) goes up once
+        pools, jobs4 = ([], []), _np.zeros((n, 4), _np.int32)
+        for side, clouds in enumerate((srcs, tgts)):
+            seen, off = {}, 0
+            for j, c in enumerate(clouds):
+                if id(c) not in seen:
+                    seen[id(c)] = off
+                    pools[side].append(c)
+                    off += len(c)
+                jobs4[j, 2 * side], jobs4[j, 2 * side + 1] = seen[id(c)], len(c)
+        src = _np.ascontiguousarray(_np.concatenate(pools[0]), _np.float32)
+        tgt = _np.ascontiguousarray(_np.concatenate(pools[1]), _np.float32)
+        T = _np.zeros((n, 4, 4), _np.float32)
+        st = _np.zeros(n, _np.int32)
+        it = _np.zeros(n, _np.int32)
+        self._call3(ctx, src, tgt, jobs4, g, T, st, it)
+        msgs = [_L.ICP_STATUS_MESSAGES.get(int(s), "ICP failure %d" % s) for s in st]
+        return msgs, T, it
+
     def compute(self, source, target, guess):
-        """-> (message, T): ("success", T 3x3 float32) or (ConvergenceError text, guess)."""
+        """-> (message, T): ("success", T 3x3 float32) or (ConvergenceError text, guess); N x 3 clouds with a 4 x 4
+        guess: T 4x4."""
         msgs, Ts, _ = self.compute_batch(source, target, [guess])
         return msgs[0], Ts[0]
 
     def compute_batch(self, source, target, guesses):
         """Many initial guesses on one cloud pair in one launch.
-        -> (messages [n], T [n x 3 x 3] float32, iterations [n])"""
+        -> (messages [n], T [n x 3 x 3] float32, iterations [n]); N x 3 clouds with 4 x 4 guesses: T [n x 4 x 4]"""
         self._chain()
+        if self._is3d([source, target], [_np.shape(x) for x in guesses], "ICP.compute"):
+            src, tgt = _cloud23(source, "ICP.compute(source)"), _cloud23(target, "ICP.compute(target)")
+            return self._pairs3([src] * len(guesses), [tgt] * len(guesses), guesses, "ICP.compute")
         ctx = self._ctx or _L.default_context()
         src = _cloud(source, "ICP.compute(source)")
         tgt = _cloud(target, "ICP.compute(target)")
@@ -366,7 +442,8 @@ class ICP(object):
 
     def compute_pairs(self, sources, targets, guesses):
         """Many independent (source, target, guess) scan matches in ONE launch (extension; the job
-        farm's unit).  -> (messages [n], T [n x 3 x 3] float32, iterations [n])"""
+        farm's unit).  -> (messages [n], T [n x 3 x 3] float32, iterations [n]); N x 3 clouds with 4 x 4 guesses:
+        T [n x 4 x 4]"""
         self._chain()
         ctx = self._ctx or _L.default_context()
         n = len(sources)
@@ -374,6 +451,8 @@ class ICP(object):
             raise TypeError("compute_pairs: %d sources, %d targets, %d guesses" % (n, len(targets), len(guesses)))
         if n == 0:
             return [], _np.zeros((0, 3, 3), _np.float32), _np.zeros(0, _np.int32)
+        if self._is3d(list(sources) + list(targets), [_np.shape(x) for x in guesses], "ICP.compute_pairs"):
+            return self._pairs3(sources, targets, guesses, "ICP.compute_pairs")
         srcs = [_cloud(s, "ICP.compute_pairs(source)") for s in sources]
         tgts = [_cloud(t, "ICP.compute_pairs(target)") for t in targets]
         if any(len(s) == 0 for s in srcs) or any(len(t) == 0 for t in tgts):
@@ -398,9 +477,31 @@ class ICP(object):
         chunk): src_all / tgt_all = clouds back to back (N x 2 float32), jobs4 = n x (src_start, n_src,
         tgt_start, n_tgt) in points, guesses9 = n x 9.  Jobs may share clouds; jobs naming the same target slice
         share its preparation.  -> (status int32 [n], T [n x 3 x 3] float32, iterations int32 [n]); the three
-        arrays may be handed in preallocated (``out=(status, T, iters)``, e.g. views of shared memory)."""
+        arrays may be handed in preallocated (``out=(status, T, iters)``, e.g. views of shared memory).  N x 3 pools
+        take n x 16 guesses (4 x 4 row-major) and return T [n x 4 x 4]."""
         self._chain()
         ctx = self._ctx or _L.default_context()
+        n_g = _np.size(guesses9) // max(len(_np.reshape(_np.asarray(jobs4), (-1, 4))), 1)
+        if self._is3d([src_all, tgt_all], [(4, 4) if n_g == 16 else (3, 3) if n_g == 9 else (n_g,)], "ICP.compute_jobs"):
+            self._chain3("ICP.compute_jobs")
+            src = _cloud23(src_all, "ICP.compute_jobs(src_all)")
+            tgt = _cloud23(tgt_all, "ICP.compute_jobs(tgt_all)")
+            jobs4 = _np.ascontiguousarray(jobs4, _np.int32).reshape(-1, 4)
+            n = len(jobs4)
+            g = _np.ascontiguousarray(guesses9, _np.float32).reshape(n, 16)
+            st, T, it = out if out is not None else (_np.zeros(n, _np.int32), _np.zeros((n, 4, 4), _np.float32),
+                                                     _np.zeros(n, _np.int32))
+            for a, shape, dt in ((st, (n,), _np.int32), (T, (n, 4, 4), _np.float32), (it, (n,), _np.int32)):
+                if not (isinstance(a, _np.ndarray) and a.shape == shape and a.dtype == dt and a.flags.c_contiguous):
+                    raise TypeError("ICP.compute_jobs: out= wants C-contiguous (status int32 [n], T float32 [n x 4 x 4], "
+                                    "iterations int32 [n]) for N x 3 clouds")
+            if n and ((jobs4[:, 1] <= 0).any() or (jobs4[:, 3] <= 0).any()):
+                raise RuntimeError("ICP.compute_jobs: empty point cloud (libpointmatcher would throw)")
+            self._call3(ctx, src, tgt, jobs4, g, T, st, it)
+            return st, T, it
+        if n_g == 16:
+            raise NotImplementedError("ICP.compute_jobs: 4 x 4 guesses (n x 16) with N x 2 clouds: a 2-D cloud needs "
+                                      "3 x 3 transforms (n x 9)")
         src = _cloud(src_all, "ICP.compute_jobs(src_all)")
         tgt = _cloud(tgt_all, "ICP.compute_jobs(tgt_all)")
         jobs4 = _np.ascontiguousarray(jobs4, _np.int32).reshape(-1, 4)
