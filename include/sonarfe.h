@@ -618,6 +618,59 @@ int sfe_feature_extract_ping_store(sfe_ctx *ctx, sfe_geom *g, sfe_cloud_store *s
                                    double radius, int min_points, int64_t cap, int flags, int32_t *handle_out,
                                    int32_t *n_out, int32_t *n_raw_out, float *cloud_out, uint8_t *vis_out);
 
+/* ---- device-resident keyframe clouds in 3-D (sfe_store3.hip) ------------------------------------------------------
+ * The keyframe store for N x 3 float32 clouds (Keyframe.points3D, slam_objects.py:101-106; the reference re-transforms
+ * every keyframe's 3-D cloud on the host at every graph update, Keyframe.transform_points_3D, :200-223).  One pool of
+ * packed points float[n][3] (12-byte stride, as sfe_match3 takes them) in HBM and a slot table (stamp, offset, count) per
+ * cloud; a cloud is named by its handle (slot index, handed out in order) and slots are released in stack order.  Clouds
+ * are packed back to back: a slot begins where the one before it ends.  The slot table lives on the host: a cloud comes
+ * from the host (its size is known) or from sfe_cloud_store3_get_points (which synchronises once for the sizes), so no
+ * entry point has to wait for sizes and no cloud can fail to fit after the fact -- a call that may not fit returns
+ * SFE_ERR_CAP before it changes anything: no slot, no count, the next handle as it was.  Sizes and offsets are 64-bit (a
+ * pool may pass 2^31 points); one cloud or one concatenation holds at most 2^28 points.
+ *
+ * The transform rule (get_points, overlap) is Keyframe.transform_points_3D's numpy expression on float32 arrays,
+ * points.dot(H[:3, :3].T) + H[:3, 3], as numpy evaluates it: per output coordinate i
+ *     fl( fma(p2, Hi2, fma(p1, Hi1, fl(p0 * Hi0))) + Hi3 )
+ * (the 3-term form of SFE_STORE_F32_POINTS).  H12 = rows 0..2 of the 4 x 4 float32 matrix, row-major, 12 floats.
+ *
+ * Not provided in 3-D: keyed clouds, the field-of-view gate and the loop-closure search; a device-to-device producer. */
+typedef struct sfe_cloud_store3 sfe_cloud_store3;
+int sfe_cloud_store3_create(sfe_ctx *ctx, int64_t capacity_points, int32_t max_clouds, sfe_cloud_store3 **out);
+void sfe_cloud_store3_destroy(sfe_cloud_store3 *s);
+int sfe_cloud_store3_count(sfe_cloud_store3 *s); /* slots in use = the next handle */
+/* one cloud from the host (pts [n][3]; n == 0: an empty slot), enqueue only.  SFE_ERR_CAP, and nothing changes, if the pool
+ * or the slot table has no room for it. */
+int sfe_cloud_store3_put(sfe_ctx *ctx, sfe_cloud_store3 *s, int64_t stamp, const float *pts, int n, int32_t *handle_out);
+/* slot table of clouds first .. first + n - 1 (each output nullable); never synchronises */
+int sfe_cloud_store3_meta(sfe_ctx *ctx, sfe_cloud_store3 *s, int32_t first, int32_t n, int64_t *stamps, int64_t *offsets,
+                          int32_t *counts);
+/* the points of one cloud (out: room for cap points of 3 floats; SFE_ERR_CAP with *n_out set if it holds more) */
+int sfe_cloud_store3_read(sfe_ctx *ctx, sfe_cloud_store3 *s, int32_t handle, float *out, int cap, int *n_out);
+/* release every slot >= n_slots and the pool behind them */
+int sfe_cloud_store3_truncate(sfe_ctx *ctx, sfe_cloud_store3 *s, int32_t n_slots);
+/* SLAM.get_points on 3-D clouds for n_jobs targets at once: job j takes the clouds handles[j*m .. j*m+m) (-1 = unused),
+ * moves cloud k by H12[(j*m+k)*12 ..], concatenates them in list order and runs the 3-D pcl.downsample(resolution) -- the
+ * 8-way tree, key and medoid rules of sfe_downsample3, bit for bit; resolution <= 0: no downsample.  Each result becomes a
+ * new slot (handles_out, host; stamps nullable); a job without points gives an empty slot.  Every stage is one launch for
+ * all jobs of the call (at most 65 535).  One synchronisation, for the jobs' output sizes; the results are placed compactly:
+ * the next slot starts right behind the downsampled cloud.  SFE_ERR_CAP, and nothing changes, if the call's upper bound --
+ * the sum of its input counts, or its n_jobs slots -- does not fit. */
+int sfe_cloud_store3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handles, const float *H12, int n_jobs, int m,
+                                float resolution, const int64_t *stamps, int32_t *handles_out);
+/* sfe_icp3_compute_jobs over handles: pairs = n_jobs x (source handle, target handle), guesses / results 16 floats per job.
+ * The same kernel on the store's pool, no point copied: T, status and iterations are bit for bit those of the host-pointer
+ * call on the same clouds.  The same parameter check (minimizer == 0).  A pair that names an empty or unknown cloud is
+ * refused with SFE_ERR_ARG before any launch. */
+int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store3 *s, const int32_t *pairs,
+                           const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);
+/* SLAM.get_overlap in 3-D for n_jobs (source, target) pairs in one launch: the source moved by H12[j*12 ..];
+ * counts_out[j] = its points with a target point within max_dist under the rules of sfe_match3: d2 =
+ * fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), matched iff d2 <= fl(max_dist * max_dist), NaN and infinite distances never.
+ * An empty source or target counts 0; an unknown handle is SFE_ERR_ARG. */
+int sfe_cloud_store3_overlap(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *pairs, const float *H12, int n_jobs,
+                             float max_dist, int32_t *counts_out);
+
 /* ---- global-initialisation matching cost: slam.py:461-570 ---------------- */
 /*
  * get_matching_cost_subroutine1 builds a dilated occupancy grid of the target cloud and hands

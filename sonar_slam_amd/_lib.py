@@ -241,6 +241,17 @@ SIGNATURES = {
                                                   C.c_int, C.POINTER(IcpDpf), C.c_int, _vp, _i32p, _f32p, C.c_int, _f32p,
                                                   _i32p, _i32p]),
     "sfe_cloud_store_overlap": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, C.c_int, _i32p]),
+    # the keyframe store for N x 3 clouds (sfe_store3.hip): 12 floats per transform, 16 per guess and per result
+    "sfe_cloud_store3_create": (C.c_int, [_vp, C.c_int64, C.c_int32, C.POINTER(_vp)]),
+    "sfe_cloud_store3_destroy": (None, [_vp]),
+    "sfe_cloud_store3_count": (C.c_int, [_vp]),
+    "sfe_cloud_store3_put": (C.c_int, [_vp, _vp, C.c_int64, _f32p, C.c_int, _i32p]),
+    "sfe_cloud_store3_meta": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, _i64p, _i64p, _i32p]),
+    "sfe_cloud_store3_read": (C.c_int, [_vp, _vp, C.c_int32, _f32p, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_cloud_store3_truncate": (C.c_int, [_vp, _vp, C.c_int32]),
+    "sfe_cloud_store3_get_points": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_int, C.c_float, _i64p, _i32p]),
+    "sfe_icp3_store_compute": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_cloud_store3_overlap": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, _i32p]),
     "sfe_feature_extract_ping_store": (C.c_int, [_vp, _vp, _vp, C.c_int64, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_double, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int64, C.c_int,
                                                  _i32p, _i32p, _i32p, _f32p, _u8p]),

@@ -66,7 +66,8 @@ __device__ __forceinline__ float dist3(float px, float py, float pz, float tx, f
 }
 
 struct Icp3Job {
-    int src_start, n_src, tgt_start, n_tgt;
+    long long src_start, tgt_start; // first point of the job's clouds in their pools (a store's pool may pass 2^31 points)
+    int n_src, n_tgt;
     long long scratch_off; // offset (in points) of this job's slice of the NN scratch
 };
 
@@ -457,7 +458,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
 }
 
 // ---------------------------------------------------------------------------------------------
-static int check_params3(sfe_ctx *ctx, const sfe_icp_params *p)
+int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
 {
     SFE_ARG(ctx, p != nullptr);
     if (p->minimizer != 0)
@@ -469,36 +470,21 @@ static int check_params3(sfe_ctx *ctx, const sfe_icp_params *p)
     return 0;
 }
 
-extern "C" {
-
-int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
-                          int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
-                          int32_t *status, int32_t *iters)
+// The launch both entry points share (sfe_icp3_compute_jobs on clouds it has just copied up, sfe_icp3_store_compute on a
+// store's pool): a validated job table over two device pools, host guesses and host results.  Stages [guesses | job table],
+// launches icp3_job_kernel, brings [T | status | iterations] back: one copy each way, one synchronisation.
+int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt, const int64_t *jobs4,
+                     const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters)
 {
-    if (int rc = sfe_use(ctx))
-        return rc;
-    if (int rc = check_params3(ctx, p))
-        return rc;
-    SFE_ARG(ctx, n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
-                     (n_jobs == 0 || (src && tgt && jobs4 && guesses16 && T_out16 && status)));
-    if (n_jobs == 0)
-        return 0;
     std::vector<Icp3Job> jobs((size_t)n_jobs);
     long long soff = 0;
     for (int j = 0; j < n_jobs; ++j) {
-        const int32_t *q = jobs4 + 4 * (size_t)j;
-        if (q[0] < 0 || q[1] <= 0 || q[2] < 0 || q[3] <= 0 || (long long)q[0] + q[1] > n_src_pts ||
-            (long long)q[2] + q[3] > n_tgt_pts)
-            return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP job %d (%d+%d, %d+%d) is empty or lies outside the clouds (%d, %d points)",
-                               j, q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
-        jobs[j] = {q[0], q[1], q[2], q[3], soff};
+        const int64_t *q = jobs4 + 4 * (size_t)j;
+        jobs[j] = {(long long)q[0], (long long)q[2], (int)q[1], (int)q[3], soff};
         soff += q[1];
     }
-    const size_t b_src = sizeof(float) * 3 * (size_t)n_src_pts, b_tgt = sizeof(float) * 3 * (size_t)n_tgt_pts;
     const size_t b_g = sizeof(float) * 16 * (size_t)n_jobs, b_st = sizeof(int32_t) * (size_t)n_jobs, b_out = b_g + 2 * b_st;
     const size_t b_jobs = sizeof(Icp3Job) * (size_t)n_jobs;
-    float *d_src = (float *)sfe_scratch(ctx, 0, b_src);
-    float *d_tgt = (float *)sfe_scratch(ctx, 1, b_tgt);
     float *d_g = (float *)sfe_scratch(ctx, 2, b_g);
     char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
     Icp3Job *d_jobs = (Icp3Job *)sfe_scratch(ctx, 4, b_jobs);
@@ -507,19 +493,18 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
     // pinned blocks both ways: [guesses | job table] up, [T | status | iterations] down
     char *h_in = (char *)sfe_pinned_io(ctx, 2, b_g + b_jobs);
     char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
-    if (!d_src || !d_tgt || !d_g || !d_out || !d_jobs || !d_nn_d2 || !d_nn_idx || !h_in || !h_out)
+    if (!d_g || !d_out || !d_jobs || !d_nn_d2 || !d_nn_idx || !h_in || !h_out)
         return SFE_ERR_HIP;
     memcpy(h_in, guesses16, b_g);
     memcpy(h_in + b_g, jobs.data(), b_jobs);
-    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, b_src, hipMemcpyHostToDevice, ctx->stream));
-    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, b_tgt, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_g, h_in, b_g, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_jobs, h_in + b_g, b_jobs, hipMemcpyHostToDevice, ctx->stream));
     int32_t *d_st = (int32_t *)(d_out + b_g);
     SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)sizeof(Icp3Shared)));
-    hipLaunchKernelGGL(icp3_job_kernel, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Icp3Shared), ctx->stream, *p, d_jobs, d_src,
-                       d_tgt, d_g, d_nn_d2, d_nn_idx, (float *)d_out, d_st, d_st + n_jobs);
+    hipLaunchKernelGGL(icp3_job_kernel, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Icp3Shared), ctx->stream, *p,
+                       (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, d_nn_d2, d_nn_idx, (float *)d_out, d_st,
+                       d_st + n_jobs);
     SFE_LAUNCH_CHECK(ctx);
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -528,6 +513,40 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
     if (iters)
         memcpy(iters, h_out + b_g + b_st, b_st);
     return 0;
+}
+
+extern "C" {
+
+int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src_pts, const float *tgt,
+                          int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
+                          int32_t *status, int32_t *iters)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    if (int rc = sfe_icp3_check_params(ctx, p))
+        return rc;
+    SFE_ARG(ctx, n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
+                     (n_jobs == 0 || (src && tgt && jobs4 && guesses16 && T_out16 && status)));
+    if (n_jobs == 0)
+        return 0;
+    std::vector<int64_t> jobs((size_t)n_jobs * 4);
+    for (int j = 0; j < n_jobs; ++j) {
+        const int32_t *q = jobs4 + 4 * (size_t)j;
+        if (q[0] < 0 || q[1] <= 0 || q[2] < 0 || q[3] <= 0 || (long long)q[0] + q[1] > n_src_pts ||
+            (long long)q[2] + q[3] > n_tgt_pts)
+            return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP job %d (%d+%d, %d+%d) is empty or lies outside the clouds (%d, %d points)",
+                               j, q[0], q[1], q[2], q[3], n_src_pts, n_tgt_pts);
+        for (int k = 0; k < 4; ++k)
+            jobs[4 * (size_t)j + k] = q[k];
+    }
+    const size_t b_src = sizeof(float) * 3 * (size_t)n_src_pts, b_tgt = sizeof(float) * 3 * (size_t)n_tgt_pts;
+    float *d_src = (float *)sfe_scratch(ctx, 0, b_src);
+    float *d_tgt = (float *)sfe_scratch(ctx, 1, b_tgt);
+    if (!d_src || !d_tgt)
+        return SFE_ERR_HIP;
+    SFE_HIP(ctx, hipMemcpyAsync(d_src, src, b_src, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, b_tgt, hipMemcpyHostToDevice, ctx->stream));
+    return sfe_icp3_run_dev(ctx, p, d_src, d_tgt, jobs.data(), guesses16, n_jobs, T_out16, status, iters);
 }
 
 } // extern "C"

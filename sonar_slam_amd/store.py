@@ -6,6 +6,9 @@ Here the clouds stay in HBM from the feature extractor to the scan matcher: a cl
 integer handle; ``get_points`` (transform + concatenate + pcl.downsample), ``icp`` and ``overlap`` take
 handles; the host sees sizes (a few bytes per cloud) and results, and the points only when it asks
 (``read``: the PointCloud2 for rviz / the mapping node).
+
+``CloudStore3`` (``sfe_cloud_store3``) is the same for the N x 3 clouds a keyframe carries (``Keyframe.points3D``,
+slam_objects.py:101-106, 200-223): ``put``, ``get_points``, ``icp`` and ``overlap`` over handles, with 4 x 4 transforms.
 """
 import ctypes as _C
 
@@ -336,6 +339,153 @@ class CloudStore(object):
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:
             self.ctx.lib.sfe_cloud_store_destroy(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pose_H12(matrix):
+    """The twelve float32 numbers Keyframe.transform_points_3D reads from a 4 x 4 matrix H (slam_objects.py:200-223,
+    ``points.dot(H[:3, :3].T) + H[:3, 3]``): rows 0..2, row-major."""
+    H = np.asarray(matrix, np.float32)
+    if H.shape != (4, 4):
+        raise TypeError("CloudStore3: a transform must be 4 x 4, got %r" % (H.shape,))
+    return H[:3, :].reshape(12)
+
+
+class CloudStore3(object):
+    """``sfe_cloud_store3``: the keyframe store for N x 3 float32 clouds (``Keyframe.points3D``).  Clouds live in HBM under
+    integer handles; ``get_points`` (transform + concatenate + the 3-D ``pcl.downsample``), ``icp`` (the 3-D point-to-point
+    ICP of ``pcl.ICP``) and ``overlap`` take handles and return, bit for bit, what the host-pointer ``pcl`` calls return on
+    the same clouds moved by numpy's float32 ``points.dot(H[:3, :3].T) + H[:3, 3]``.  A call that does not fit the pool or the
+    slot table raises (SFE_ERR_CAP) and leaves the store as it was.  No keyed clouds, field-of-view gate or loop-closure
+    search in 3-D, and no device-to-device producer: clouds come in through ``put``."""
+
+    def __init__(self, ctx=None, capacity_points=1 << 22, max_clouds=1 << 16):
+        self.ctx = ctx or _L.default_context()
+        h = _C.c_void_p()
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_create(self.ctx.handle, int(capacity_points), int(max_clouds),
+                                                                 _C.byref(h)))
+        self.handle = h
+        self.capacity_points, self.max_clouds = int(capacity_points), int(max_clouds)
+
+    def put(self, points, stamp=0):
+        """one host cloud (N x 3, rounded to float32 like the pybind boundary; N may be 0) -> handle"""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        h = _C.c_int32(-1)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_put(self.ctx.handle, self.handle, int(stamp),
+                                                              _L.ptr(pts, _C.c_float), len(pts), _C.byref(h)))
+        return h.value
+
+    def __len__(self):
+        return int(self.ctx.lib.sfe_cloud_store3_count(self.handle))
+
+    def meta(self, first=0, n=None):
+        """-> (stamps int64, offsets int64, counts int32) of clouds first .. first + n - 1"""
+        n = len(self) - first if n is None else int(n)
+        st, off, cnt = np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_meta(self.ctx.handle, self.handle, int(first), n,
+                                                               _L.ptr(st, _C.c_int64), _L.ptr(off, _C.c_int64),
+                                                               _L.ptr(cnt, _C.c_int32)))
+        return st, off, cnt
+
+    def counts(self, handles):
+        handles = np.asarray(handles, np.int64).reshape(-1)
+        if len(handles) == 0:
+            return np.zeros(0, np.int32)
+        lo, hi = int(handles.min()), int(handles.max())
+        return self.meta(lo, hi - lo + 1)[2][handles - lo]
+
+    def read(self, handle):
+        """the points of one cloud (N x 3 float32), copied to the host"""
+        n = int(self.counts([handle])[0])
+        out = np.zeros((n, 3), np.float32)
+        m = _C.c_int(0)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_read(self.ctx.handle, self.handle, int(handle),
+                                                               _L.ptr(out, _C.c_float), len(out), _C.byref(m)))
+        return out
+
+    def truncate(self, n_slots):
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_truncate(self.ctx.handle, self.handle, int(n_slots)))
+
+    def get_points(self, handle_lists, transforms, resolution, stamps=None):
+        """SLAM.get_points on 3-D clouds for many targets at once.  ``handle_lists``: one list of handles per target (-1 =
+        unused; the lists may differ in length); ``transforms``: per target one 4 x 4 matrix per listed handle (cloud k is
+        moved by ``points.dot(H[:3, :3].T) + H[:3, 3]`` in float32).  The clouds of a target are concatenated in list order
+        and downsampled like ``pcl.downsample(points, resolution)`` (``resolution <= 0``: not at all).
+        -> new handles int32 [n_targets]"""
+        n_jobs = len(handle_lists)
+        if len(transforms) != n_jobs:
+            raise ValueError("CloudStore3.get_points: %d handle lists but %d transform lists" % (n_jobs, len(transforms)))
+        m = max([len(h) for h in handle_lists] + [1])
+        handles = np.full((n_jobs, m), -1, np.int32)
+        H12 = np.zeros((n_jobs, m, 12), np.float32)
+        for j, (hs, Hs) in enumerate(zip(handle_lists, transforms)):
+            if len(hs) != len(Hs):
+                raise ValueError("CloudStore3.get_points: target %d lists %d handles but %d transforms" % (j, len(hs), len(Hs)))
+            for k, (h, H) in enumerate(zip(hs, Hs)):
+                handles[j, k] = int(h)
+                H12[j, k] = pose_H12(H)
+        out = np.full(n_jobs, -1, np.int32)
+        st = None if stamps is None else np.ascontiguousarray(stamps, np.int64).reshape(n_jobs)
+        with self.ctx.lock:
+            # float(resolution) through c_float: the rounding pcl.downsample applies at the same boundary
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_get_points(
+                self.ctx.handle, self.handle, _L.ptr(handles, _C.c_int32), _L.ptr(H12, _C.c_float), n_jobs, m,
+                float(resolution), None if st is None else _L.ptr(st, _C.c_int64), _L.ptr(out, _C.c_int32)))
+        return out
+
+    def icp(self, pairs, guesses, params):
+        """The 3-D scan match over handles: pairs [n x 2] = (source, target), guesses [n x 4 x 4]
+        -> (status int32 [n], T [n x 4 x 4] float32, iterations int32 [n]), bit for bit ``pcl.ICP.compute_jobs`` on the same
+        clouds.  ``params``: an ``IcpParams`` or an ``icp_config.IcpChain``; what ``pcl.ICP`` refuses on N x 3 input
+        (data-point filters, the MinDist / MedianDist / Bound modules, point-to-plane) is refused here in the same words."""
+        from . import pcl as _pcl
+        icp = _pcl.ICP(self.ctx)
+        if isinstance(params, _cfg.IcpChain):
+            icp.setChain(params)
+        elif isinstance(params, _L.IcpParams):
+            icp.setParams(params)
+        else:
+            raise TypeError("CloudStore3.icp: expected an IcpParams or an icp_config.IcpChain, got %s" % type(params).__name__)
+        p = icp._chain3("CloudStore3.icp")
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = len(pairs)
+        g = np.ascontiguousarray(np.asarray(guesses, np.float32).reshape(n, 16))
+        T, st, it = np.zeros((n, 4, 4), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_icp3_store_compute(
+                self.ctx.handle, _C.byref(p), self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(g, _C.c_float), n,
+                _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))
+        return st, T, it
+
+    def overlap(self, pairs, transforms, max_dist):
+        """SLAM.get_overlap in 3-D for many (source, target) pairs: the source moved by its 4 x 4 transform, the points of
+        it with a target point within ``max_dist`` (``pcl.match(target, moved, 1, max_dist)``, ids != -1) -> int32 [n]"""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = len(pairs)
+        if len(transforms) != n:
+            raise ValueError("CloudStore3.overlap: %d pairs but %d transforms" % (n, len(transforms)))
+        H12 = np.ascontiguousarray(np.stack([pose_H12(H) for H in transforms]) if n else np.zeros((0, 12)), np.float32)
+        out = np.zeros(n, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_overlap(
+                self.ctx.handle, self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(H12, _C.c_float), n, float(max_dist),
+                _L.ptr(out, _C.c_int32)))
+        return out
+
+    def close(self):
+        if self.handle is not None and self.ctx.handle is not None:
+            self.ctx.lib.sfe_cloud_store3_destroy(self.handle)
         self.handle = None
 
     def __del__(self):
