@@ -214,7 +214,8 @@ typedef struct sfe_icp_params {
     float max_dist_filter;   /*   .maxDist (icp.yaml:13) */
     int use_trimmed_filter;  /* TrimmedDistOutlierFilter listed (icp.yaml:14) */
     float trim_ratio;        /*   .ratio (icp.yaml:15) */
-    int minimizer;           /* 0 PointToPointErrorMinimizer (icp.yaml:20), 1 2-D PointToPlane (icp.yaml:18-19) */
+    int minimizer;           /* 0 PointToPointErrorMinimizer (icp.yaml:20), 1 2-D PointToPlane (icp.yaml:18-19, force2D: 1;
+                              * N x 2 clouds only), 2 3-D PointToPlane (force2D: 0; N x 3 clouds only, sfe_icp3_*) */
     int max_iter;            /* CounterTransformationChecker.maxIterationCount (icp.yaml:24) */
     int use_diff_checker;    /* DifferentialTransformationChecker listed (icp.yaml:25) */
     float min_diff_rot;      /*   .minDiffRotErr (icp.yaml:26) */
@@ -261,6 +262,20 @@ int sfe_remove_outlier3(sfe_ctx *ctx, const float *pts, int n, double radius, in
                         float *out, int *n_out);
 int sfe_downsample3(sfe_ctx *ctx, const float *pts, int n, float resolution, float *out,
                     int32_t *out_idx, int *n_out);
+/* Surface normals of an N x 3 cloud (libpointmatcher's SurfaceNormalDataPointsFilter {knn, keepNormals}; the routine the
+ * 3-D point-to-plane ICP runs on its targets, here on the cloud as given, not centred).  Host pointers, pts and normals_out
+ * packed float[n][3], 2 <= knn <= 16.  For point i:
+ *   neighbours  its k = min(knn, n) nearest points of the cloud, i itself included: d2 = fl(fl(fl(dx dx) + fl(dy dy)) +
+ *               fl(dz dz)), no fma, in lexicographic (d2, index) order -- equal distances go to the lowest index (the order
+ *               of sfe_match_knn3).  A point whose d2 is not below +inf (NaN or infinite coordinates on either side) is
+ *               nobody's neighbour, so a neighbourhood may hold fewer than k points, or none.
+ *   normal      in fp64 from the float coordinates, in neighbour order: m = the neighbours' mean, C = sum (u - m)(u - m)^T;
+ *               the unit eigenvector of C's smallest eigenvalue by a cyclic Jacobi (pairs (0,1), (0,2), (1,2), at most 12
+ *               sweeps, none once the off-diagonal squares are below 1e-36 of the diagonal's; sfe_icp3_plane.h), the
+ *               lowest column among equal eigenvalues, rounded to float.  Its sign is the Jacobi's: nothing here
+ *               depends on it.  Always finite and of unit length: C = 0 (k < 2, coincident points, an empty
+ *               neighbourhood) gives (1, 0, 0); collinear points give some unit vector across the line. */
+int sfe_normals3(sfe_ctx *ctx, const float *pts, int n, int knn, float *normals_out);
 /* pcl.ICP.compute(source, target, guess) (pcl.cpp:198-212).  Returns SFE_ICP_* (>= 0) or a
  * hard error (< 0).  On a nonzero status T_out = guess (pcl.cpp:203,207-210). */
 int sfe_icp_compute(sfe_ctx *ctx, const sfe_icp_params *p, const float *src, int n_src,
@@ -283,8 +298,10 @@ int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src
                          int n_tgt_pts, const int32_t *jobs4, const float *guesses9, int n_jobs, float *T_out9,
                          int32_t *status, int32_t *iters);
 /* pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (PM::ICP::compute, pcl.cpp:198-212, is dimension-generic; the
- * reference carries such clouds as Keyframe.points3D): the point-to-point chain of the shipped config/icp.yaml, i.e.
- * sfe_icp_params with minimizer == 0 (anything else: SFE_ERR_ARG, like a job slice that is empty or outside the clouds).
+ * reference carries such clouds as Keyframe.points3D): the chain of the shipped config/icp.yaml with its point-to-point
+ * minimiser (sfe_icp_params with minimizer == 0) or with PointToPlaneErrorMinimizer {force2D: 0} (minimizer == 2, with
+ * 2 <= normals_knn <= 16); minimizer == 1, the 2-D form, is SFE_ERR_ARG here (3-D clouds take the point-to-point or the 3-D
+ * point-to-plane minimiser), like a job slice that is empty or outside the clouds.
  * Host pointers, the job table of sfe_icp_compute_jobs; src / tgt packed float[n][3], guesses16 / T_out16 4 x 4 row-major
  * per job.  One workgroup per job, brute-force search (sfe_icp3.hip); jobs naming the same target slice share nothing.
  * The route record of the last 2-D call stays as it is.  Rules, restated from libpointmatcher (parity unpinned, like the
@@ -305,6 +322,15 @@ int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src
  *             computed as the top eigenvector of Horn's 4 x 4 matrix by fp64 Jacobi sweeps, sfe_icp3_solve.h);
  *             t = mq - R mp.  The step is rounded to float once, T_iter = T_step * T_iter.  H of rank <= 1 (all kept
  *             pairs collinear) leaves R undetermined: some finite rotation comes back, no particular one.
+ *   minimizer 2  the normals of every distinct target (by first point and size) of the call are taken once, in front of the
+ *             job kernel, by the rule of sfe_normals3 on the CENTRED target (3 floats per point in device scratch).  Match,
+ *             outlier filters and checkers are the ones above.  Per kept pair, with n the normal of q, all widened to
+ *             fp64: c = p x n, F = (c, n), e = n . (p - q); the fp64 sums W += 1, A += F F^T (21 distinct entries),
+ *             b -= F e.  W == 0: SFE_ICP_NO_POINT.  A x = b by a 6 x 6 Cholesky with the 2-D minimiser's rule: A00 > 0
+ *             and every later pivot > 1e-10 x its diagonal entry, else SFE_ICP_SINGULAR (T = the guess).  r = x[0..2],
+ *             t = x[3..5], R = Rodrigues' rotation by |r| about r / |r| (the identity for |r| == 0); T_step = [R t]
+ *             rounded to float.  A planar target (every z = 0 cloud) has parallel normals and a rank-3 A: status 5, so
+ *             z = 0 input does NOT reduce to the 2-D point-to-plane result.
  *   checkers  Counter as in 2-D.  Differential: the history holds T_iter's float rotation block and translation, the
  *             identity first (a sliding window of 64 entries); per step, in fp64 from those floats, the rotation error
  *             is 2 atan2(|vec(q_i conj(q_i-1))|, |w|) with q the quaternion of the block by Eigen's branch rule (trace
@@ -660,7 +686,8 @@ int sfe_cloud_store3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t
                                 float resolution, const int64_t *stamps, int32_t *handles_out);
 /* sfe_icp3_compute_jobs over handles: pairs = n_jobs x (source handle, target handle), guesses / results 16 floats per job.
  * The same kernel on the store's pool, no point copied: T, status and iterations are bit for bit those of the host-pointer
- * call on the same clouds.  The same parameter check (minimizer == 0).  A pair that names an empty or unknown cloud is
+ * call on the same clouds.  The same parameter check (minimizer 0 or 2; with 2, pairs on one target handle share its
+ * normals).  A pair that names an empty or unknown cloud is
  * refused with SFE_ERR_ARG before any launch. */
 int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store3 *s, const int32_t *pairs,
                            const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);

@@ -185,6 +185,7 @@ SIGNATURES = {
     "sfe_match3": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_float, _i32p, _f32p]),
     "sfe_match_knn3": (C.c_int, [_vp, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_float, _i32p, _f32p]),
     "sfe_knn_density3": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
+    "sfe_normals3": (C.c_int, [_vp, _f32p, C.c_int, C.c_int, _f32p]),
     "sfe_remove_outlier3": (C.c_int, [_vp, _f32p, C.c_int, C.c_double, C.c_int, _f32p,
                                       C.POINTER(C.c_int)]),
     "sfe_downsample3": (C.c_int, [_vp, _f32p, C.c_int, C.c_float, _f32p, _i32p, C.POINTER(C.c_int)]),

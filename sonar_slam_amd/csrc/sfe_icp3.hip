@@ -1,6 +1,7 @@
-// 3-D point-to-point ICP on gfx950: pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (pcl.cpp:198-212; PM::ICP is
-// dimension-generic), the module set of the shipped config/icp.yaml -- KDTreeMatcher {knn 1}, MaxDist and TrimmedDist outlier
-// filters, PointToPointErrorMinimizer, Counter and Differential transformation checkers (sfe_icp_params with minimizer 0).
+// 3-D ICP on gfx950: pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (pcl.cpp:198-212; PM::ICP is dimension-generic),
+// the module set of the shipped config/icp.yaml -- KDTreeMatcher {knn 1}, MaxDist and TrimmedDist outlier filters,
+// PointToPointErrorMinimizer (sfe_icp_params with minimizer 0) or PointToPlaneErrorMinimizer {force2D: 0} (minimizer 2),
+// Counter and Differential transformation checkers.
 //
 // The rules (include/sonarfe.h at sfe_icp3_compute_jobs) are the 2-D chain's with one more coordinate:
 //   centre the target on its mean, T0 = translate(-mean) * guess, reading = T0 * source            (once)
@@ -8,6 +9,8 @@
 //         exact 1-NN of every cur point in the target, d2 = ((dx dx + dy dy) + dz dz), lowest index on ties, none beyond maxDist
 //         keep = [d2 <= MaxDist^2] * [d2 <= quantile_ratio(finite d2)]
 //         T_step = the rigid motion that minimises the kept pairs' squared distances (sfe_icp3_solve.h), rounded to float
+//                  (minimizer 2: the step of the linearised point-to-plane system, sfe_icp3_plane.h; the target's surface
+//                  normals come from normals3_kernel, which runs once per distinct target in front of the job kernel)
 //         T_iter = T_step * T_iter ; Counter / Differential checkers
 //   result = translate(+mean) * (T_iter * T0)
 //
@@ -15,16 +18,21 @@
 // sits in LDS as three arrays (x, y, z: 48 KiB for 4096 points, padded with +inf) for all iterations, larger targets are
 // streamed through the same tile; a lane owns up to two source points per pass and scans the tile in index order with a strict
 // '<' (lowest index on ties); nearest distances and indices go to HBM scratch; the trimmed quantile is the radix select on the
-// float bit patterns; the 16 sums are reduced in fp64 in a fixed order; one lane solves and runs the checkers.
-// fp32 VALU + LDS broadcast reads, no MFMA.  LDS: 48 KiB tile + 2.1 KiB sums + 1 KiB histogram + 3 KiB history = 55 KiB,
-// so two workgroups fit the 160 KiB of a CU where the register count allows it.
+// float bit patterns; the 16 sums (point-to-plane: 28, accumulated in two passes over the kept pairs) are reduced in fp64 in a
+// fixed order; one lane solves and runs the checkers.
+// fp32 VALU + LDS broadcast reads, no MFMA.  LDS: 48 KiB tile + 2.1 KiB sums (point-to-plane: 3.7 KiB) + 1 KiB histogram +
+// 3 KiB history = 55 KiB, so two workgroups fit the 160 KiB of a CU where the register count allows it.
 #include "sfe_internal.h"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <type_traits>
+#include <utility>
 
 #include "sfe_icp_common.h"
+#include "sfe_icp3_plane.h"
 #include "sfe_icp3_solve.h"
 
 #define ICP3_TCAP 4096 // target points resident in LDS (48 KiB as three float arrays)
@@ -33,6 +41,17 @@
 
 static_assert(ICP3_TCAP % ICP3_UNR == 0, "the tile is read ICP3_UNR points at a time");
 static_assert(ICP3_NSUM == 16, "point-to-point in 3-D: W, sum p, sum q, sum q p^T");
+static_assert(ICP3P_NSUM == 28, "point-to-plane in 3-D: W, the upper triangle of sum F F^T, -sum F e");
+static_assert(ICP3P_PIVOT_RTOL == ICP_PIVOT_RTOL, "one singularity rule for the 2-D and the 3-D point-to-plane systems");
+
+#define ICP3_POINT 0 // sfe_icp_params.minimizer of the two instantiations
+#define ICP3_PLANE 2
+#define N3_TILE 2048 // points per LDS tile of the normals kernel (24 KiB), as P3_TILE of sfe_pcl3.hip
+
+template <int MIN>
+struct Icp3Sums {
+    static constexpr int N = MIN == ICP3_PLANE ? ICP3P_NSUM : ICP3_NSUM;
+};
 
 // c = a * b, 4 x 4 row-major, every entry (((a0 b0 + a1 b1) + a2 b2) + a3 b3) with each product and sum rounded to float
 __device__ __forceinline__ void mat4_mul(const float *a, const float *b, float *c)
@@ -69,11 +88,13 @@ struct Icp3Job {
     long long src_start, tgt_start; // first point of the job's clouds in their pools (a store's pool may pass 2^31 points)
     int n_src, n_tgt;
     long long scratch_off; // offset (in points) of this job's slice of the NN scratch
+    long long nrm_off;     // offset (in points) of its target's normals (point-to-plane; jobs on one target share them)
 };
 
-struct Icp3Shared {
+template <int NS> // the minimiser's sums: 16 or 28
+struct Icp3SharedT {
     float tx[ICP3_TCAP], ty[ICP3_TCAP], tz[ICP3_TCAP];
-    double red[ICP_WAVES * ICP3_NSUM + ICP3_NSUM];
+    double red[ICP_WAVES * NS + NS];
     unsigned hist[256];
     unsigned sel_prefix, sel_k;
     int flag_iterate, flag_status;
@@ -81,11 +102,15 @@ struct Icp3Shared {
     float mean[3];
     float hist_T[ICP_MAX_HIST][12]; // rotation block (9, row-major) and translation (3) of T_iter after every step
 };
-static_assert(sizeof(((Icp3Shared *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3_NSUM + ICP3_NSUM),
+static_assert(sizeof(((Icp3SharedT<ICP3_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3_NSUM + ICP3_NSUM),
               "block_sum<ICP3_NSUM> needs (waves + 1) x ICP3_NSUM doubles");
-static_assert(sizeof(Icp3Shared) <= 64 * 1024, "two workgroups per CU");
+static_assert(sizeof(((Icp3SharedT<ICP3P_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3P_NSUM + ICP3P_NSUM),
+              "block_sum<ICP3P_NSUM> needs (waves + 1) x ICP3P_NSUM doubles");
+static_assert(sizeof(Icp3SharedT<ICP3_NSUM>) <= 64 * 1024 && sizeof(Icp3SharedT<ICP3P_NSUM>) <= 64 * 1024,
+              "two workgroups per CU");
 
 // load target points [base, base + n) of the job (packed float triples), centred on the mean, into the LDS tile (+inf pad)
+template <class Icp3Shared>
 __device__ __forceinline__ void load_tile3(Icp3Shared &S, const float *__restrict__ tgt, int base, int n)
 {
     const float mx = S.mean[0], my = S.mean[1], mz = S.mean[2];
@@ -106,7 +131,7 @@ __device__ __forceinline__ void load_tile3(Icp3Shared &S, const float *__restric
 
 // Exact arg-min over the LDS tile (tn points, global indices from tb) for NP query points per lane: index order and a strict
 // '<', so the lowest index wins among equal distances; NaN distances and the +inf pad never win.
-template <int NP>
+template <int NP, class Icp3Shared>
 __device__ __forceinline__ void nn3_scan_tile(const Icp3Shared &S, int tn, int tb, const float (&px)[ICP3_PB],
                                               const float (&py)[ICP3_PB], const float (&pz)[ICP3_PB], float (&best)[ICP3_PB],
                                               int (&bi)[ICP3_PB])
@@ -144,6 +169,7 @@ __device__ __forceinline__ void nn3_scan_tile(const Icp3Shared &S, int tn, int t
 
 // k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns): the radix select of job_select_kth (sfe_icp.hip) on this
 // kernel's shared block; called by the whole workgroup
+template <class Icp3Shared>
 __device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
 {
     if (tid == 0) {
@@ -184,9 +210,13 @@ __device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_
 
 // One lane: solve from the reduced sums, T_iter = T_step * T_iter (to LDS), then the Counter and Differential checkers in
 // libpointmatcher's order.  Checker state: nhist / counter / iters in the lane's registers, the history in LDS.  Not inlined:
-// the fp64 Jacobi sweeps want more registers than the scan loop, and one lane runs them once per iteration.
-__device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const double (&acc)[ICP3_NSUM], Icp3Shared &S,
-                                                     int &nhist, int &counter, int &iters, int &status, int &iterate)
+// the fp64 Jacobi sweeps want more registers than the scan loop, and one lane runs them once per iteration.  MIN picks the
+// minimiser's solve (point-to-plane: a system that counts as singular ends the job with SFE_ICP_SINGULAR before anything is
+// composed or counted); everything behind it is the same code for both.
+template <int MIN>
+__device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const double (&acc)[Icp3Sums<MIN>::N],
+                                                     Icp3SharedT<Icp3Sums<MIN>::N> &S, int &nhist, int &counter, int &iters,
+                                                     int &status, int &iterate)
 {
     status = SFE_ICP_OK;
     iterate = 1;
@@ -195,7 +225,14 @@ __device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const
         return;
     }
     double R[9], t[3];
-    icp3_solve(acc, R, t);
+    if constexpr (MIN == ICP3_PLANE) {
+        if (icp3p_solve(acc, R, t)) {
+            status = SFE_ICP_SINGULAR;
+            return;
+        }
+    } else {
+        icp3_solve(acc, R, t);
+    }
     const float Ts[16] = {(float)R[0], (float)R[1], (float)R[2], (float)t[0], (float)R[3], (float)R[4], (float)R[5], (float)t[1],
                           (float)R[6], (float)R[7], (float)R[8], (float)t[2], 0.0f,        0.0f,        0.0f,        1.0f};
     float Ti[16], Tn[16];
@@ -243,14 +280,72 @@ __device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const
     }
 }
 
+// block_sum<NV> in two steps, for sums that are accumulated in several passes: the wave sums of the values [OFF, OFF + CNT)
+// to their places in s_red (any number of calls that together cover [0, NV)), then the rest of block_sum.  Every value
+// is reduced in block_sum's order.
+template <int NV, int OFF, int CNT>
+__device__ __forceinline__ void block_sum_waves(const double (&v)[CNT], double *s_red)
+{
+    static_assert(OFF >= 0 && CNT >= 1 && OFF + CNT <= NV, "a part of the NV values");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+        const double s = wave_sum(v[i]);
+        if (lane == 0)
+            s_red[wave * NV + OFF + i] = s;
+    }
+}
+
+template <int NV>
+__device__ __forceinline__ void block_sum_finish(double (&v)[NV], double *s_red)
+{
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = 0;
+        for (int w = 0; w < ICP_WAVES; ++w) // fixed order: deterministic
+            s += s_red[w * NV + threadIdx.x];
+        s_red[ICP_WAVES * NV + threadIdx.x] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        v[i] = s_red[ICP_WAVES * NV + i];
+    __syncthreads();
+}
+
+// The reference mean of a target of nt packed points (fp64 accumulation, rounded to float) into mean[0 .. 3) (LDS), by a
+// workgroup of ICP_THREADS; red: (waves + 1) x 3 doubles of LDS.  One piece of code for the job kernel and for the kernel
+// that centres a target before its normals are taken: both see the same three floats.
+__device__ __forceinline__ void icp3_target_mean(const float *__restrict__ tgt, int nt, int tid, double *red, float *mean)
+{
+    double m[3] = {0, 0, 0};
+    for (int i = tid; i < nt; i += ICP_THREADS) {
+        const float *t = tgt + 3 * (size_t)i;
+        m[0] += t[0];
+        m[1] += t[1];
+        m[2] += t[2];
+    }
+    block_sum<3>(m, red);
+    if (tid == 0) {
+        mean[0] = (float)(m[0] / nt);
+        mean[1] = (float)(m[1] / nt);
+        mean[2] = (float)(m[2] / nt);
+    }
+    __syncthreads();
+}
+
+template <int MIN>
 __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P, const Icp3Job *__restrict__ jobs,
                                                                const float *__restrict__ src_all,
                                                                const float *__restrict__ tgt_all,
                                                                const float *__restrict__ guess_all,
+                                                               const float *__restrict__ nrm_all,
                                                                float *__restrict__ nn_d2_all, int *__restrict__ nn_idx_all,
                                                                float *__restrict__ T_out, int *__restrict__ status_out,
                                                                int *__restrict__ iters_out)
 {
+    constexpr int NS = Icp3Sums<MIN>::N;
+    using Icp3Shared = Icp3SharedT<NS>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Icp3Shared &S = *reinterpret_cast<Icp3Shared *>(smem_raw);
 
@@ -265,22 +360,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
     const bool resident = nt <= ICP3_TCAP;
 
     // ---- reference mean (fp64 accumulation, rounded to float) ----
-    {
-        double m[3] = {0, 0, 0};
-        for (int i = tid; i < nt; i += ICP_THREADS) {
-            const float *t = tgt + 3 * (size_t)i;
-            m[0] += t[0];
-            m[1] += t[1];
-            m[2] += t[2];
-        }
-        block_sum<3>(m, S.red);
-        if (tid == 0) {
-            S.mean[0] = (float)(m[0] / nt);
-            S.mean[1] = (float)(m[1] / nt);
-            S.mean[2] = (float)(m[2] / nt);
-        }
-        __syncthreads();
-    }
+    icp3_target_mean(tgt, nt, tid, S.red, S.mean);
     const float mx = S.mean[0], my = S.mean[1], mz = S.mean[2];
     if (resident) {
         load_tile3(S, tgt, 0, nt);
@@ -387,46 +467,111 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
         }
 
         // ---- error minimiser: accumulate over kept pairs ----
-        double acc[ICP3_NSUM];
+        double acc[NS];
+        if constexpr (MIN == ICP3_PLANE) {
+            // F = (p x n, n), e = n . (p - q): A += F F^T (upper triangle, row by row), b -= F e, W += 1; the normal of the
+            // matched target point is gathered from HBM (one per kept pair).  28 fp64 accumulators beside the pair's own
+            // values do not fit the 128 registers of a 1024-thread workgroup, so the kept pairs are walked twice: W and
+            // the rows of A that begin with p x n (16 sums), then the n n^T block and b (12 sums).  Each sum is reduced
+            // exactly as block_sum<28> would reduce it.
+            auto pass = [&](auto part) {
+                constexpr int PART = decltype(part)::value;
+                constexpr int OFF = PART ? 16 : 0, CNT = PART ? 12 : 16;
+                double a[CNT];
 #pragma unroll
-        for (int i = 0; i < ICP3_NSUM; ++i)
-            acc[i] = 0;
-        for (int i = tid; i < ns; i += ICP_THREADS) {
-            const int id = nn_idx[i];
-            const float d = nn_d2[i];
-            if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit)))
-                continue;
-            const float *s = src + 3 * (size_t)i;
-            const float sx = s[0], sy = s[1], sz = s[2];
-            const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
-            const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
-            double q[3];
-            if (resident) {
-                q[0] = S.tx[id];
-                q[1] = S.ty[id];
-                q[2] = S.tz[id];
-            } else {
-                const float *t = tgt + 3 * (size_t)id;
-                q[0] = f_add(t[0], -mx);
-                q[1] = f_add(t[1], -my);
-                q[2] = f_add(t[2], -mz);
+                for (int i = 0; i < CNT; ++i)
+                    a[i] = 0;
+                for (int i = tid; i < ns; i += ICP_THREADS) {
+                    const int id = nn_idx[i];
+                    const float d = nn_d2[i];
+                    if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) &&
+                          (!P.use_trimmed_filter || d <= limit)))
+                        continue;
+                    const float *s = src + 3 * (size_t)i;
+                    const float sx = s[0], sy = s[1], sz = s[2];
+                    const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+                    const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
+                    const float *nv = nrm_all + 3 * (size_t)(J.nrm_off + id);
+                    const double n0 = nv[0], n1 = nv[1], n2 = nv[2];
+                    const double F[6] = {p[1] * n2 - p[2] * n1, p[2] * n0 - p[0] * n2, p[0] * n1 - p[1] * n0, n0, n1, n2};
+                    if constexpr (PART == 0) {
+                        a[0] += 1.0;
+                        int k = 1;
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+#pragma unroll
+                            for (int c = r; c < 6; ++c)
+                                a[k++] += F[r] * F[c];
+                    } else {
+                        double q[3];
+                        if (resident) {
+                            q[0] = S.tx[id];
+                            q[1] = S.ty[id];
+                            q[2] = S.tz[id];
+                        } else {
+                            const float *t = tgt + 3 * (size_t)id;
+                            q[0] = f_add(t[0], -mx);
+                            q[1] = f_add(t[1], -my);
+                            q[2] = f_add(t[2], -mz);
+                        }
+                        const double e = (n0 * (p[0] - q[0]) + n1 * (p[1] - q[1])) + n2 * (p[2] - q[2]);
+                        int k = 0;
+#pragma unroll
+                        for (int r = 3; r < 6; ++r)
+#pragma unroll
+                            for (int c = r; c < 6; ++c)
+                                a[k++] += F[r] * F[c];
+#pragma unroll
+                        for (int r = 0; r < 6; ++r)
+                            a[6 + r] -= F[r] * e;
+                    }
+                }
+                block_sum_waves<NS, OFF, CNT>(a, S.red);
+            };
+            pass(std::integral_constant<int, 0>());
+            pass(std::integral_constant<int, 1>());
+            block_sum_finish<NS>(acc, S.red);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                acc[i] = 0;
+            for (int i = tid; i < ns; i += ICP_THREADS) {
+                const int id = nn_idx[i];
+                const float d = nn_d2[i];
+                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit)))
+                    continue;
+                const float *s = src + 3 * (size_t)i;
+                const float sx = s[0], sy = s[1], sz = s[2];
+                const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+                const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
+                double q[3];
+                if (resident) {
+                    q[0] = S.tx[id];
+                    q[1] = S.ty[id];
+                    q[2] = S.tz[id];
+                } else {
+                    const float *t = tgt + 3 * (size_t)id;
+                    q[0] = f_add(t[0], -mx);
+                    q[1] = f_add(t[1], -my);
+                    q[2] = f_add(t[2], -mz);
+                }
+                acc[0] += 1.0;
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    acc[1 + a] += p[a];
+                    acc[4 + a] += q[a];
+#pragma unroll
+                    for (int b = 0; b < 3; ++b)
+                        acc[7 + 3 * a + b] += q[a] * p[b];
+                }
             }
-            acc[0] += 1.0;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                acc[1 + a] += p[a];
-                acc[4 + a] += q[a];
-#pragma unroll
-                for (int b = 0; b < 3; ++b)
-                    acc[7 + 3 * a + b] += q[a] * p[b];
-            }
+            block_sum<NS>(acc, S.red);
         }
-        block_sum<ICP3_NSUM>(acc, S.red);
 
         // ---- solve, compose, check (thread 0) ----
         if (tid == 0) {
             int status, iterate;
-            icp3_solve_and_check(P, acc, S, nhist, counter, iters, status, iterate);
+            icp3_solve_and_check<MIN>(P, acc, S, nhist, counter, iters, status, iterate);
             S.flag_status = status;
             S.flag_iterate = (status == SFE_ICP_OK) ? iterate : 0;
         }
@@ -458,11 +603,169 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Surface normals of the targets of a point-to-plane call: one table entry per distinct target
+// ---------------------------------------------------------------------------------------------
+struct Nrm3Target {
+    long long start;   // its first point in the pool
+    long long nrm_off; // where its normals go (in points)
+    int n;             // its points (> 0)
+    int pad;
+};
+
+// the float mean of every target, exactly as icp3_job_kernel takes it (one workgroup per target)
+__global__ __launch_bounds__(ICP_THREADS) void nrm3_mean_kernel(const Nrm3Target *__restrict__ targets,
+                                                                const float *__restrict__ pts_all, float *__restrict__ means)
+{
+    __shared__ double s_red[ICP_WAVES * 3 + 3];
+    __shared__ float s_mean[3];
+    const Nrm3Target G = targets[blockIdx.x];
+    icp3_target_mean(pts_all + 3 * (size_t)G.start, G.n, threadIdx.x, s_red, s_mean);
+    if (threadIdx.x < 3)
+        means[3 * (size_t)blockIdx.x + threadIdx.x] = s_mean[threadIdx.x];
+}
+
+// One lane per point of target blockIdx.y (`first` + blockIdx.y of the table): its k = min(knn, n) nearest points of the
+// same target, itself included, in the lexicographic (d2, index) order of match_knn3_kernel (sfe_pcl3.hip) -- a k-slot
+// insertion list in registers filled in one pass over the target, which goes through LDS as packed triples, N3_TILE points
+// at a time, centred on the target's mean (means == nullptr: as given); a point whose d2 is not below +inf (NaN, infinite
+// or overflowing coordinates) is nobody's neighbour, so a list may end short.  Then, in fp64 from the float coordinates in
+// list order: the neighbours' mean, C = sum (u - m)(u - m)^T, icp3p_normal (sfe_icp3_plane.h), rounded to float.
+__global__ __launch_bounds__(256) void normals3_kernel(const Nrm3Target *__restrict__ targets, int first,
+                                                       const float *__restrict__ pts_all, const float *__restrict__ means,
+                                                       int knn, float *__restrict__ nrm_all)
+{
+    __shared__ float s_t[3 * N3_TILE];
+    const Nrm3Target G = targets[first + blockIdx.y];
+    const int n = G.n;
+    if (blockIdx.x * 256 >= n) // (uniform: the whole workgroup leaves before any barrier)
+        return;
+    const float *__restrict__ pts = pts_all + 3 * (size_t)G.start;
+    float mx = 0.0f, my = 0.0f, mz = 0.0f; // (x - 0 = x for every float)
+    if (means) {
+        mx = means[3 * (size_t)(first + blockIdx.y)];
+        my = means[3 * (size_t)(first + blockIdx.y) + 1];
+        mz = means[3 * (size_t)(first + blockIdx.y) + 2];
+    }
+    const int K = min(min(knn, ICP_KMAX), n);
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool act = i < n;
+    float qx = 0, qy = 0, qz = 0;
+    if (act) {
+        qx = f_add(pts[3 * (size_t)i], -mx);
+        qy = f_add(pts[3 * (size_t)i + 1], -my);
+        qz = f_add(pts[3 * (size_t)i + 2], -mz);
+    }
+    float bd[ICP_KMAX];
+    int bi[ICP_KMAX];
+    float kth = INFINITY;
+#pragma unroll
+    for (int q = 0; q < ICP_KMAX; ++q) {
+        bd[q] = INFINITY;
+        bi[q] = 0;
+    }
+    for (int tb = 0; tb < n; tb += N3_TILE) {
+        const int tn = min(N3_TILE, n - tb);
+        __syncthreads();
+        for (int j = threadIdx.x; j < 3 * tn; j += 256) { // consecutive floats: coalesced
+            const int a = j % 3;
+            s_t[j] = f_add(pts[3 * (size_t)tb + j], -(a == 0 ? mx : a == 1 ? my : mz));
+        }
+        __syncthreads();
+        if (act) {
+            for (int j = 0; j < tn; ++j) { // every lane reads the same LDS words: a broadcast
+                const float d = dist3(qx, qy, qz, s_t[3 * j], s_t[3 * j + 1], s_t[3 * j + 2]);
+                if (d < kth) { // kth = the list's K-th distance (inf until it is full); NaN and inf: never
+                    // position = number of kept entries <= d (ascending index: equal distances keep the earlier point)
+                    int p = 0;
+#pragma unroll
+                    for (int q = 0; q < ICP_KMAX; ++q)
+                        p += (q < K && bd[q] <= d) ? 1 : 0;
+#pragma unroll
+                    for (int q = ICP_KMAX - 1; q >= 1; --q) {
+                        if (q < K && q > p) {
+                            bd[q] = bd[q - 1];
+                            bi[q] = bi[q - 1];
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < ICP_KMAX; ++q) {
+                        if (q == p) {
+                            bd[q] = d;
+                            bi[q] = tb + j;
+                        }
+                        if (q == K - 1)
+                            kth = bd[q];
+                    }
+                }
+            }
+        }
+    }
+    if (!act)
+        return;
+    double sx = 0, sy = 0, sz = 0;
+    int cnt = 0;
+#pragma unroll
+    for (int q = 0; q < ICP_KMAX; ++q)
+        if (q < K && bd[q] < INFINITY) {
+            const float *t = pts + 3 * (size_t)bi[q];
+            sx += (double)f_add(t[0], -mx);
+            sy += (double)f_add(t[1], -my);
+            sz += (double)f_add(t[2], -mz);
+            ++cnt;
+        }
+    double C[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (cnt > 0) {
+        sx /= cnt;
+        sy /= cnt;
+        sz /= cnt;
+#pragma unroll
+        for (int q = 0; q < ICP_KMAX; ++q)
+            if (q < K && bd[q] < INFINITY) {
+                const float *t = pts + 3 * (size_t)bi[q];
+                const double ux = (double)f_add(t[0], -mx) - sx, uy = (double)f_add(t[1], -my) - sy,
+                             uz = (double)f_add(t[2], -mz) - sz;
+                C[0] += ux * ux;
+                C[1] += ux * uy;
+                C[2] += ux * uz;
+                C[4] += uy * uy;
+                C[5] += uy * uz;
+                C[8] += uz * uz;
+            }
+    }
+    double nv[3];
+    icp3p_normal(C, nv);
+    float *o = nrm_all + 3 * (size_t)(G.nrm_off + i);
+    o[0] = (float)nv[0];
+    o[1] = (float)nv[1];
+    o[2] = (float)nv[2];
+}
+
+// The normals of n_targets targets of one pool (table on the device and on the host), enqueue only: the means where the
+// ICP centres its targets (d_means != nullptr), then normals3_kernel with the target in blockIdx.y.
+static int icp3_normals_dev(sfe_ctx *ctx, const Nrm3Target *d_targets, const Nrm3Target *h_targets, int n_targets,
+                            const float *d_pts, float *d_means, int knn, float *d_nrm)
+{
+    if (d_means)
+        hipLaunchKernelGGL(nrm3_mean_kernel, dim3(n_targets), dim3(ICP_THREADS), 0, ctx->stream, d_targets, d_pts, d_means);
+    for (int first = 0; first < n_targets; first += 65535) { // (blockIdx.y)
+        const int m = std::min(65535, n_targets - first);
+        int max_n = 1;
+        for (int k = 0; k < m; ++k)
+            max_n = std::max(max_n, h_targets[first + k].n);
+        hipLaunchKernelGGL(normals3_kernel, dim3((unsigned)((max_n + 255) / 256), (unsigned)m), dim3(256), 0, ctx->stream,
+                           d_targets, first, d_pts, (const float *)d_means, knn, d_nrm);
+    }
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
 int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
 {
     SFE_ARG(ctx, p != nullptr);
-    if (p->minimizer != 0)
-        return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP runs the point-to-point error minimiser only (minimizer = %d)", p->minimizer);
+    if (p->minimizer != ICP3_POINT && p->minimizer != ICP3_PLANE)
+        return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP runs the point-to-point error minimiser (0) and the 3-D point-to-plane one "
+                                             "(2, force2D: 0), not minimizer = %d", p->minimizer);
+    SFE_ARG(ctx, p->minimizer != ICP3_PLANE || (p->normals_knn >= 2 && p->normals_knn <= ICP_KMAX));
     SFE_ARG(ctx, p->max_iter >= 1);
     SFE_ARG(ctx, !p->use_diff_checker || (p->smooth_len >= 1 && p->smooth_len < ICP_MAX_HIST));
     SFE_ARG(ctx, !p->use_trimmed_filter || (p->trim_ratio >= 0.0f && p->trim_ratio <= 1.0f));
@@ -471,27 +774,42 @@ int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
 }
 
 // The launch both entry points share (sfe_icp3_compute_jobs on clouds it has just copied up, sfe_icp3_store_compute on a
-// store's pool): a validated job table over two device pools, host guesses and host results.  Stages [guesses | job table],
-// launches icp3_job_kernel, brings [T | status | iterations] back: one copy each way, one synchronisation.
+// store's pool): a validated job table over two device pools, host guesses and host results.  Stages [guesses | job table
+// | target table], launches icp3_job_kernel -- for point-to-plane behind the normals of the call's distinct targets (by
+// first point and size: the 30 guesses of a compute_batch, or store pairs on one handle, take them once), in stream order
+// -- and brings [T | status | iterations] back: one copy each way, one synchronisation.
 int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt, const int64_t *jobs4,
                      const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters)
 {
+    const bool plane = p->minimizer == ICP3_PLANE;
     std::vector<Icp3Job> jobs((size_t)n_jobs);
-    long long soff = 0;
+    std::vector<Nrm3Target> targets;
+    std::map<std::pair<long long, int>, long long> seen; // (first point, size) of a target -> where its normals go
+    long long soff = 0, noff = 0;
     for (int j = 0; j < n_jobs; ++j) {
         const int64_t *q = jobs4 + 4 * (size_t)j;
-        jobs[j] = {(long long)q[0], (long long)q[2], (int)q[1], (int)q[3], soff};
+        long long at = 0;
+        if (plane) {
+            const auto ins = seen.emplace(std::make_pair((long long)q[2], (int)q[3]), noff);
+            if (ins.second) {
+                targets.push_back({(long long)q[2], noff, (int)q[3], 0});
+                noff += q[3];
+            }
+            at = ins.first->second;
+        }
+        jobs[j] = {(long long)q[0], (long long)q[2], (int)q[1], (int)q[3], soff, at};
         soff += q[1];
     }
+    const int n_targets = (int)targets.size();
     const size_t b_g = sizeof(float) * 16 * (size_t)n_jobs, b_st = sizeof(int32_t) * (size_t)n_jobs, b_out = b_g + 2 * b_st;
-    const size_t b_jobs = sizeof(Icp3Job) * (size_t)n_jobs;
+    const size_t b_jobs = sizeof(Icp3Job) * (size_t)n_jobs, b_tg = sizeof(Nrm3Target) * (size_t)n_targets;
     float *d_g = (float *)sfe_scratch(ctx, 2, b_g);
     char *d_out = (char *)sfe_scratch(ctx, 3, b_out);
     Icp3Job *d_jobs = (Icp3Job *)sfe_scratch(ctx, 4, b_jobs);
     float *d_nn_d2 = (float *)sfe_scratch(ctx, 5, sizeof(float) * (size_t)soff);
     int *d_nn_idx = (int *)sfe_scratch(ctx, 6, sizeof(int) * (size_t)soff);
-    // pinned blocks both ways: [guesses | job table] up, [T | status | iterations] down
-    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_g + b_jobs);
+    // pinned blocks both ways: [guesses | job table | target table] up, [T | status | iterations] down
+    char *h_in = (char *)sfe_pinned_io(ctx, 2, b_g + b_jobs + b_tg);
     char *h_out = (char *)sfe_pinned_io(ctx, 3, b_out);
     if (!d_g || !d_out || !d_jobs || !d_nn_d2 || !d_nn_idx || !h_in || !h_out)
         return SFE_ERR_HIP;
@@ -500,11 +818,31 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, 
     SFE_HIP(ctx, hipMemcpyAsync(d_g, h_in, b_g, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_jobs, h_in + b_g, b_jobs, hipMemcpyHostToDevice, ctx->stream));
     int32_t *d_st = (int32_t *)(d_out + b_g);
-    SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sizeof(Icp3Shared)));
-    hipLaunchKernelGGL(icp3_job_kernel, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Icp3Shared), ctx->stream, *p,
-                       (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, d_nn_d2, d_nn_idx, (float *)d_out, d_st,
-                       d_st + n_jobs);
+    if (plane) {
+        // normals: 3 floats per point of every distinct target (HBM); [target table | means] in one slot
+        float *d_nrm = (float *)sfe_scratch(ctx, 7, sizeof(float) * 3 * (size_t)noff);
+        char *d_tg = (char *)sfe_scratch(ctx, 8, b_tg + sizeof(float) * 3 * (size_t)n_targets);
+        if (!d_nrm || !d_tg)
+            return SFE_ERR_HIP;
+        memcpy(h_in + b_g + b_jobs, targets.data(), b_tg);
+        SFE_HIP(ctx, hipMemcpyAsync(d_tg, h_in + b_g + b_jobs, b_tg, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = icp3_normals_dev(ctx, (const Nrm3Target *)d_tg, targets.data(), n_targets, d_tgt, (float *)(d_tg + b_tg),
+                                      p->normals_knn, d_nrm))
+            return rc;
+        using Shared = Icp3SharedT<ICP3P_NSUM>;
+        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<ICP3_PLANE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)sizeof(Shared)));
+        hipLaunchKernelGGL(icp3_job_kernel<ICP3_PLANE>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, *p,
+                           (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, (const float *)d_nrm, d_nn_d2, d_nn_idx,
+                           (float *)d_out, d_st, d_st + n_jobs);
+    } else {
+        using Shared = Icp3SharedT<ICP3_NSUM>;
+        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<ICP3_POINT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)sizeof(Shared)));
+        hipLaunchKernelGGL(icp3_job_kernel<ICP3_POINT>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, *p,
+                           (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, (const float *)nullptr, d_nn_d2, d_nn_idx,
+                           (float *)d_out, d_st, d_st + n_jobs);
+    }
     SFE_LAUNCH_CHECK(ctx);
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -547,6 +885,30 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
     SFE_HIP(ctx, hipMemcpyAsync(d_src, src, b_src, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, b_tgt, hipMemcpyHostToDevice, ctx->stream));
     return sfe_icp3_run_dev(ctx, p, d_src, d_tgt, jobs.data(), guesses16, n_jobs, T_out16, status, iters);
+}
+
+int sfe_normals3(sfe_ctx *ctx, const float *pts, int n, int knn, float *normals_out)
+{
+    if (int rc = sfe_use(ctx))
+        return rc;
+    SFE_ARG(ctx, n >= 0 && n <= (1 << 28) && knn >= 2 && knn <= ICP_KMAX && (n == 0 || (pts && normals_out)));
+    if (n == 0)
+        return 0;
+    const size_t b_pts = sizeof(float) * 3 * (size_t)n;
+    float *d_pts = (float *)sfe_scratch(ctx, 0, b_pts);
+    float *d_nrm = (float *)sfe_scratch(ctx, 7, b_pts);
+    Nrm3Target *d_tg = (Nrm3Target *)sfe_scratch(ctx, 8, sizeof(Nrm3Target));
+    Nrm3Target *h_tg = (Nrm3Target *)sfe_pinned_io(ctx, 2, sizeof(Nrm3Target));
+    if (!d_pts || !d_nrm || !d_tg || !h_tg)
+        return SFE_ERR_HIP;
+    *h_tg = {0, 0, n, 0};
+    SFE_HIP(ctx, hipMemcpyAsync(d_pts, pts, b_pts, hipMemcpyHostToDevice, ctx->stream));
+    SFE_HIP(ctx, hipMemcpyAsync(d_tg, h_tg, sizeof(Nrm3Target), hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = icp3_normals_dev(ctx, d_tg, h_tg, 1, d_pts, nullptr, knn, d_nrm)) // the cloud as given: no centring
+        return rc;
+    SFE_HIP(ctx, hipMemcpyAsync(normals_out, d_nrm, b_pts, hipMemcpyDeviceToHost, ctx->stream));
+    SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 } // extern "C"

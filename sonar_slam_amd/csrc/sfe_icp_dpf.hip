@@ -343,6 +343,9 @@ int sfe_icp_dpf_run_host(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
                          const sfe_icp_dpf *rf, int n_rf, const float *d_src, const float *d_tgt, const int32_t *jobs4,
                          const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters)
 {
+    // (the filters run in front of the launch that checks the parameters: a minimiser the 2-D kernels do not have -- 2, the
+    // 3-D point-to-plane one -- is refused before they do)
+    SFE_ARG(ctx, p != nullptr && (p->minimizer == 0 || p->minimizer == 1));
     DpfSlices S, R;
     dpf_slices(jobs4, n_jobs, 0, S);
     dpf_slices(jobs4, n_jobs, 2, R);

@@ -15,7 +15,9 @@ silently ignoring a filter would change the pose):
     outlierFilters     MaxDistOutlierFilter {maxDist}, TrimmedDistOutlierFilter {ratio}; with ``parse_icp_chain``
                        also MinDistOutlierFilter {minDist}, MedianDistOutlierFilter {factor}, NullOutlierFilter
                        (each at most once, any order; the weights are the product of the filters')
-    errorMinimizer     PointToPointErrorMinimizer | PointToPlaneErrorMinimizer {force2D: 1}
+    errorMinimizer     PointToPointErrorMinimizer | PointToPlaneErrorMinimizer {force2D: 1} (the 2-D form, N x 2 clouds);
+                       with ``parse_icp_chain`` also PointToPlaneErrorMinimizer {force2D: 0} or without parameters
+                       (libpointmatcher's default): the 3-D form, ``minimizer = 2``, N x 3 clouds only
     transformationCheckers  CounterTransformationChecker {maxIterationCount},
                             DifferentialTransformationChecker {minDiffRotErr, minDiffTransErr,
                                                                smoothLength};
@@ -112,7 +114,7 @@ def _positive(name, key, v):
 
 def _params(doc, ox=None):
     """the sections other than the data-point filters -> IcpParams; ``ox`` (an IcpOutliers to fill: parse_icp_chain)
-    takes the modules of _CHAIN_ONLY, without it they are refused"""
+    takes the modules of _CHAIN_ONLY and the 3-D point-to-plane minimiser, without it they are refused"""
     p = dict(matcher_max_dist=float("inf"), use_max_dist_filter=0, max_dist_filter=0.0,
              use_trimmed_filter=0, trim_ratio=1.0, minimizer=0, max_iter=40, use_diff_checker=0,
              min_diff_rot=0.001, min_diff_trans=0.01, smooth_len=3, normals_knn=10)
@@ -163,9 +165,14 @@ def _params(doc, ox=None):
         if name == "PointToPointErrorMinimizer":
             p["minimizer"] = 0
         elif name == "PointToPlaneErrorMinimizer":
-            if int(ep.get("force2D", 0)) != 1:
+            if int(ep.get("force2D", 0)) == 1:
+                p["minimizer"] = 1
+            elif ox is not None and int(ep.get("force2D", 0)) == 0:
+                # force4DOF, sensorStdDev, ...: a parameter that is not restated would change the pose silently
+                _known_params(name, ep, ("force2D",))
+                p["minimizer"] = 2      # libpointmatcher's default: the 3-D normal equations (N x 3 clouds)
+            else:
                 raise IcpConfigError("PointToPlaneErrorMinimizer needs force2D: 1 (clouds are 2-D)")
-            p["minimizer"] = 1
         else:
             raise IcpConfigError("unsupported error minimizer %r" % name)
 
@@ -230,8 +237,8 @@ class IcpChain(object):
 
     @staticmethod
     def device_stages(stages):
-        """the stages the device runs (SurfaceNormal keeps every point and is ``normals_knn``) ->
-        (ctypes array of IcpDpf or None, count)"""
+        """the stages the device runs (SurfaceNormal keeps every point and is ``normals_knn``: a chain whose only stage
+        it is has none, which is what a 3-D point-to-plane chain looks like) -> (ctypes array of IcpDpf or None, count)"""
         dev = [s for s in stages if isinstance(s, IcpDpf)]
         if not dev:
             return None, 0
@@ -375,7 +382,7 @@ def parse_icp_chain(text):
         if isinstance(s, SurfaceNormalStage):
             if i != len(reference) - 1:
                 raise IcpConfigError("SurfaceNormalDataPointsFilter must be the last referenceDataPointsFilters stage")
-            if params.minimizer != 1:
+            if params.minimizer not in (1, 2):
                 raise IcpConfigError("SurfaceNormalDataPointsFilter is only supported in a point-to-plane chain "
                                      "(PointToPlaneErrorMinimizer), where it sets the normals")
             params.normals_knn = s.knn

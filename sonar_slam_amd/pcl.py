@@ -16,9 +16,10 @@ N x 3, as pcl.cpp takes them (fromEigen labels a z row when mat.cols() == 3, pcl
 topRows(mat_in.cols())): an N x 3 cloud goes to HIP kernels of its own (sfe_pcl3.hip; the 2-D rules with one more
 coordinate, an 8-way tree for ``downsample``; brute force, quadratic in the cloud size) and comes back N' x 3; ``match``
 wants both clouds of one width (RuntimeError otherwise, like libnabo).  ``ICP.compute*`` takes N x 3 clouds with 4 x 4
-guesses too (PM::ICP::compute is dimension-generic) and returns 4 x 4 transforms: the point-to-point chain of the shipped
-icp.yaml on a HIP kernel of its own (sfe_icp3.hip, brute force); mixed widths, data-point filters, the MinDist / MedianDist
-/ Bound modules and point-to-plane raise NotImplementedError on 3-D input.
+guesses too (PM::ICP::compute is dimension-generic) and returns 4 x 4 transforms: the chain of the shipped icp.yaml with
+its point-to-point minimiser or with ``PointToPlaneErrorMinimizer {force2D: 0}`` (``minimizer = 2``) on a HIP kernel of its
+own (sfe_icp3.hip, brute force); mixed widths, data-point filters, the MinDist / MedianDist / Bound modules and the 2-D
+point-to-plane form (``force2D: 1``) raise NotImplementedError on 3-D input, the 3-D form on N x 2 input.
 
 Extension (not in the reference): ``ICP.compute_batch(source, target, guesses)`` runs the
 many-guesses-one-pair loop of SLAM.compute_icp_with_cov (slam.py:346-358) in one launch.
@@ -198,6 +199,28 @@ def knn_density(points, knn, ctx=None):
     return dens
 
 
+def surface_normals(points, knn, ctx=None):
+    """The ``normals`` descriptor of libpointmatcher's SurfaceNormalDataPointsFilter{knn, keepNormals} on an N x 3 cloud
+    (extension; the routine the 3-D point-to-plane ICP runs on its targets): per point the unit eigenvector of the smallest
+    eigenvalue of the scatter matrix of its min(knn, N) nearest points, itself included, ties in distance to the lowest
+    index; the sign is arbitrary.  Degenerate neighbourhoods give a finite unit vector ((1, 0, 0) for coincident points).
+    ``include/sonarfe.h`` at ``sfe_normals3`` spells the rule out.  2 <= knn <= 16.  -> float32 [N x 3].  N x 2 clouds raise
+    NotImplementedError (the 2-D normals exist inside the 2-D ICP kernels only)."""
+    pts = _cloud23(points, "surface_normals(points)")
+    if pts.shape[1] != 3:
+        raise NotImplementedError("surface_normals: N x 2 clouds: the 2-D normals are computed inside the 2-D ICP kernels "
+                                  "and are not exposed; pass an N x 3 cloud")
+    knn = int(knn)
+    if not 2 <= knn <= 16:
+        raise RuntimeError("surface_normals: knn %d outside [2, 16]" % knn)
+    ctx = ctx or _L.default_context()
+    out = _np.zeros((len(pts), 3), _np.float32)
+    if len(pts):
+        with ctx.lock:
+            ctx._check(ctx.lib.sfe_normals3(ctx.handle, _L.ptr(pts, _C.c_float), len(pts), knn, _L.ptr(out, _C.c_float)))
+    return out
+
+
 def max_density_filter(points, *args, **kw):
     """What the body of the reference's ``density_filter`` does once its stray ``minDensity`` parameter is taken out
     (pcl.cpp:76-126): densities from the knn nearest neighbours (``knn_density``), then libpointmatcher's
@@ -343,7 +366,13 @@ class ICP(object):
             raise TypeError("ICP.compute: guess must be 3 x 3, got %r" % (g.shape,))
         return _np.ascontiguousarray(g)
 
-    # ---- N x 3 clouds with 4 x 4 guesses: the point-to-point chain on sfe_icp3_compute_jobs ----
+    def _chain2(self, what):
+        """a 2-D call: the 3-D point-to-plane minimiser is refused before anything reaches the library"""
+        if self._chain().minimizer == 2:
+            raise NotImplementedError("%s: PointToPlaneErrorMinimizer {force2D: 0} on N x 2 clouds: libpointmatcher would "
+                                      "run its 2-D form there; say force2D: 1 (minimizer = 1) for 2-D clouds" % what)
+
+    # ---- N x 3 clouds with 4 x 4 guesses: the point-to-point or 3-D point-to-plane chain on sfe_icp3_compute_jobs ----
     @staticmethod
     def _is3d(clouds, guess_shapes, what):
         """True when the call is a 3-D one: every cloud N x 3 and every guess 4 x 4.  False: leave it to the 2-D path
@@ -372,8 +401,9 @@ class ICP(object):
             raise NotImplementedError("%s: MinDist / MedianDist outlier filters and the Bound checker on N x 3 clouds: "
                                       "the 3-D kernel runs the modules of the shipped icp.yaml only" % what)
         if p.minimizer == 1:
-            raise NotImplementedError("%s: PointToPlaneErrorMinimizer on N x 3 clouds: the normal equations here are "
-                                      "the 2-D ones; 3-D ICP is point-to-point" % what)
+            raise NotImplementedError("%s: PointToPlaneErrorMinimizer {force2D: 1} on N x 3 clouds: its normal equations "
+                                      "are the 2-D ones; 3-D clouds take the point-to-point minimiser or force2D: 0 "
+                                      "(minimizer = 2)" % what)
         return p
 
     def _call3(self, ctx, src, tgt, jobs4, g, T, st, it):
@@ -429,6 +459,7 @@ class ICP(object):
         ctx = self._ctx or _L.default_context()
         src = _cloud(source, "ICP.compute(source)")
         tgt = _cloud(target, "ICP.compute(target)")
+        self._chain2("ICP.compute")
         g = _np.ascontiguousarray(_np.stack([self._guess(x) for x in guesses]), _np.float32)
         n = len(g)
         if len(src) == 0 or len(tgt) == 0:
@@ -455,6 +486,7 @@ class ICP(object):
             return self._pairs3(sources, targets, guesses, "ICP.compute_pairs")
         srcs = [_cloud(s, "ICP.compute_pairs(source)") for s in sources]
         tgts = [_cloud(t, "ICP.compute_pairs(target)") for t in targets]
+        self._chain2("ICP.compute_pairs")
         if any(len(s) == 0 for s in srcs) or any(len(t) == 0 for t in tgts):
             raise RuntimeError("ICP.compute_pairs: empty point cloud (libpointmatcher would throw)")
         so = _np.zeros(n + 1, _np.int32)
@@ -504,6 +536,7 @@ class ICP(object):
                                       "3 x 3 transforms (n x 9)")
         src = _cloud(src_all, "ICP.compute_jobs(src_all)")
         tgt = _cloud(tgt_all, "ICP.compute_jobs(tgt_all)")
+        self._chain2("ICP.compute_jobs")
         jobs4 = _np.ascontiguousarray(jobs4, _np.int32).reshape(-1, 4)
         n = len(jobs4)
         g = _np.ascontiguousarray(guesses9, _np.float32).reshape(n, 9)
@@ -525,7 +558,7 @@ class ICP(object):
         ``sensorStdDev``; the reference cannot run that chain (icp.yaml configures no normals) and the 2-D form
         is not defined anywhere, so a point-to-plane chain raises instead of returning a made-up matrix.  No
         caller in the reference reads either (grep)."""
-        if self._chain().minimizer == 1:
+        if self._chain().minimizer in (1, 2):
             raise NotImplementedError("ICP.getCovariance for a point-to-plane chain: libpointmatcher's Censi estimate "
                                       "is 3-D only and the reference never runs this chain; use "
                                       "SLAM.compute_icp_with_cov's sampled covariance (slam.py:325-387)")

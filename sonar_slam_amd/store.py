@@ -448,7 +448,9 @@ class CloudStore3(object):
         """The 3-D scan match over handles: pairs [n x 2] = (source, target), guesses [n x 4 x 4]
         -> (status int32 [n], T [n x 4 x 4] float32, iterations int32 [n]), bit for bit ``pcl.ICP.compute_jobs`` on the same
         clouds.  ``params``: an ``IcpParams`` or an ``icp_config.IcpChain``; what ``pcl.ICP`` refuses on N x 3 input
-        (data-point filters, the MinDist / MedianDist / Bound modules, point-to-plane) is refused here in the same words."""
+        (data-point filters, the MinDist / MedianDist / Bound modules, the 2-D point-to-plane form) is refused here in the
+        same words; ``minimizer = 2`` (PointToPlaneErrorMinimizer {force2D: 0}) runs, pairs on one target handle sharing its
+        normals."""
         from . import pcl as _pcl
         icp = _pcl.ICP(self.ctx)
         if isinstance(params, _cfg.IcpChain):

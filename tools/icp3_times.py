@@ -4,6 +4,14 @@ pair (the loop of SLAM.compute_icp_with_cov), and ``compute_pairs`` on 256 pairs
 (x, y) columns of the same clouds stand next to them.  Medians over --reps calls after two warm-up calls; one JSON line.
 
     python tools/icp3_times.py [--reps 9] [--pairs 256] [--n 5000]
+
+``--minimizer plane`` times the 3-D calls with the point-to-plane minimiser (``minimizer = 2``) instead, ``--minimizer both``
+alternates the two minimisers call by call in one process and prints every repeat (``series``), the medians, the ratio plane /
+point, and ``pcl.surface_normals`` alone on one target of either size (a host call: the copy up, the normals kernel, the copy
+down) with its share of the plane time of ``compute`` and of the 30 guesses, which have one distinct target each; the normals
+of the 256 targets of ``compute_pairs`` are one launch, whose share is read from a kernel trace
+(``rocprofv3 --kernel-trace -- python tools/icp3_times.py --minimizer plane``).  ``--minimizer point`` (the default) prints
+what the tool always printed.
 """
 import argparse
 import json
@@ -54,11 +62,55 @@ def planar(T4):
     return T3
 
 
+def minimizers(ctx, a, s, t, guess, guesses, big, out):
+    """the three 3-D shapes with the point-to-plane minimiser, alone or alternated with point-to-point"""
+    kinds = {"point": 0, "plane": 2}
+    if a.minimizer == "plane":
+        kinds.pop("point")
+    icps = {}
+    for k, m in kinds.items():
+        icps[k] = pcl.ICP(ctx)
+        icps[k].setParams(icp_config.shipped_params(minimizer=m))
+    srcs, tgts, gb = [p[0] for p in big], [p[1] for p in big], [guess] * len(big)
+    pairs_name = "compute_pairs_%d_x_%dx%d" % (a.pairs, a.n, a.n)
+    shapes = (("compute_800x800", lambda i: i.compute(s, t, guess), a.reps),
+              ("compute_batch_30_guesses_800x800", lambda i: i.compute_batch(s, t, guesses), a.reps),
+              (pairs_name, lambda i: i.compute_pairs(srcs, tgts, gb), max(a.reps // 3, 5 if len(kinds) == 2 else 1)))
+    out.update({"minimizer": a.minimizer, "series": {k: {} for k in kinds}, "ms": {k: {} for k in kinds}})
+    for name, call, reps in shapes:
+        ser = {k: [] for k in kinds}
+        for r in range(reps + 2):                      # two warm-up rounds, then alternate call by call
+            for k in kinds:
+                t0 = time.perf_counter()
+                call(icps[k])
+                if r >= 2:
+                    ser[k].append(round(1e3 * (time.perf_counter() - t0), 4))
+        for k in kinds:
+            out["series"][k][name] = ser[k]
+            out["ms"][k][name] = round(float(np.median(ser[k])), 4)
+    for k in kinds:
+        msgs, _, it = icps[k].compute_pairs(srcs, tgts, gb)
+        out["iterations"][k] = {"pairs_mean": round(float(np.mean(it)), 2), "pairs_success": int(sum(m == "success" for m in msgs)),
+                                "batch_mean": round(float(np.mean(icps[k].compute_batch(s, t, guesses)[2])), 2)}
+    knn = icp_config.shipped_params().normals_knn
+    nrm = {"surface_normals_800": med_ms(lambda: pcl.surface_normals(t, knn, ctx=ctx), a.reps),
+           "surface_normals_%d" % a.n: med_ms(lambda: pcl.surface_normals(big[0][1], knn, ctx=ctx), a.reps)}
+    out["normals_ms"] = nrm
+    ms = out["ms"]["plane"]
+    out["normals_share"] = {"compute_800x800": round(nrm["surface_normals_800"] / ms["compute_800x800"], 3),
+                            "compute_batch_30_guesses_800x800": round(nrm["surface_normals_800"] / ms["compute_batch_30_guesses_800x800"], 3),
+                            }  # (the pairs' normals run as one launch over all targets: their share is read from a kernel trace)
+    if "point" in kinds:
+        out["plane_over_point"] = {n: round(ms[n] / out["ms"]["point"][n], 3) for n in ms}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--pairs", type=int, default=256)
     ap.add_argument("--n", type=int, default=5000)
+    ap.add_argument("--minimizer", choices=("point", "plane", "both"), default="point")
     a = ap.parse_args()
     ctx = _lib.default_context()
     icp = pcl.ICP(ctx)
@@ -72,6 +124,9 @@ def main():
                for _ in range(30)]
     big = [pair(rng, a.n, truth) for _ in range(a.pairs)]
     out = {"tool": "icp3_times", "device": ctx.name(), "reps": a.reps, "ms": {}, "iterations": {}}
+    if a.minimizer != "point":
+        print(json.dumps(minimizers(ctx, a, s, t, guess, guesses, big, out)))
+        return
     for name, cut, g_of in (("3d", lambda c: c, lambda g: g), ("2d", lambda c: np.ascontiguousarray(c[:, :2]), planar)):
         s1, t1 = cut(s), cut(t)
         srcs, tgts = [cut(p[0]) for p in big], [cut(p[1]) for p in big]
