@@ -660,7 +660,19 @@ int sfe_feature_extract_ping_store(sfe_ctx *ctx, sfe_geom *g, sfe_cloud_store *s
  *     fl( fma(p2, Hi2, fma(p1, Hi1, fl(p0 * Hi0))) + Hi3 )
  * (the 3-term form of SFE_STORE_F32_POINTS).  H12 = rows 0..2 of the 4 x 4 float32 matrix, row-major, 12 floats.
  *
- * Not provided in 3-D: keyed clouds, the field-of-view gate and the loop-closure search; a device-to-device producer. */
+ *
+ * Keyed clouds.  A slot may carry an int32 key >= 0 per point (the keyframe index a point of the SLAM cloud came from) and a
+ * selection byte per point, in two pools parallel to the point pool and indexed by the same offsets.  The two pools are
+ * allocated at the first keyed call (put_keys, get_points_keys), so a store that never uses keys costs what it costs
+ * without them; if that allocation fails the call returns SFE_ERR_HIP and nothing has changed.  With them the store runs
+ * the SLAM cloud (get_points_keys) and the candidate selection of the loop-closure search (fov_select, compact_selected,
+ * match_keys: slam.py:873-902, :977-997) over handles.  Every call that takes jobs runs one launch per stage for all of
+ * them (at most 65 535); every call that creates slots tests an upper bound of its result before it launches anything,
+ * returns SFE_ERR_CAP with the store untouched otherwise, and places its results compactly after one synchronisation for
+ * the sizes.  All counts are integers: no result depends on the order of the atomics.
+ *
+ * Not provided in 3-D: a device-to-device producer (clouds come in through put / put_keys), and the FrontEnd /
+ * SessionBatch wiring of the 2-D store. */
 typedef struct sfe_cloud_store3 sfe_cloud_store3;
 int sfe_cloud_store3_create(sfe_ctx *ctx, int64_t capacity_points, int32_t max_clouds, sfe_cloud_store3 **out);
 void sfe_cloud_store3_destroy(sfe_cloud_store3 *s);
@@ -697,6 +709,60 @@ int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_stor
  * An empty source or target counts 0; an unknown handle is SFE_ERR_ARG. */
 int sfe_cloud_store3_overlap(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *pairs, const float *H12, int n_jobs,
                              float max_dist, int32_t *counts_out);
+/* sfe_cloud_store3_put with a key per point: a keyed slot from the host.  Any keys[i] < 0 is SFE_ERR_ARG and leaves no slot;
+ * n == 0 gives an empty keyed slot. */
+int sfe_cloud_store3_put_keys(sfe_ctx *ctx, sfe_cloud_store3 *s, int64_t stamp, const float *pts, const int32_t *keys, int n,
+                              int32_t *handle_out);
+/* 1: the slot carries keys; 0: it does not; SFE_ERR_ARG: no such slot (or s == NULL) */
+int sfe_cloud_store3_keyed(sfe_cloud_store3 *s, int32_t handle);
+/* SLAM.get_points(frames, ref, return_keys=True) on 3-D clouds (slam.py:229-292; the SLAM cloud of slam_ros.py:317-359) for
+ * n_jobs targets at once.  Job j takes the entries [job_off[j], job_off[j+1]) of handles / H12 (12 floats each) / keys
+ * (job_off[0] == 0; a handle of -1 is unused).  Cloud k is moved by H12[k*12 ..] under the store's transform rule, every one
+ * of its points is tagged keys[k] (>= 0, else SFE_ERR_ARG), and the clouds are concatenated in list order.  The job then
+ * runs the 3-D pcl.downsample(points, keys, resolution), the descriptor overload: the points are those of
+ * sfe_cloud_store3_get_points for the same inputs, and a leaf's medoid brings its tag along.  resolution <= 0: the tagged
+ * concatenation itself.  Inputs may be plain or keyed slots; a stored key is ignored.  Each result is one new keyed slot.
+ * Launches, synchronisation, placement and SFE_ERR_CAP as in sfe_cloud_store3_get_points. */
+int sfe_cloud_store3_get_points_keys(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handles, const float *H12,
+                                     const int32_t *keys, const int32_t *job_off, int n_jobs, float resolution,
+                                     const int64_t *stamps, int32_t *handles_out);
+/* the keys of one keyed cloud (out: room for cap keys; SFE_ERR_CAP with *n_out set if it holds more).  A plain slot is
+ * SFE_ERR_ARG. */
+int sfe_cloud_store3_read_keys(sfe_ctx *ctx, sfe_cloud_store3 *s, int32_t handle, int32_t *out, int cap, int *n_out);
+/* The field-of-view gate of the loop-closure search (slam.py:875-899) with one more coordinate in the transform and the
+ * range, for n_jobs keyed clouds in one launch: job j = cloud handles[j] against frames [frame_off[j], frame_off[j+1])
+ * (frame_off[0] == 0) of Hinv12 (12 floats per frame: rows 0..2 of pose.inverse()) / range_bound / bearing_bound.  For point
+ * p and frame f, q = p moved by Hinv12[f] (the store's transform rule),
+ *     range = sqrtf(fl(fl(fl(qx qx) + fl(qy qy)) + fl(qz qz)))       correctly rounded: np.linalg.norm(local, axis=1) on
+ *                                                                    a float32 N x 3 array
+ * and f sees p iff (double)range < range_bound[f] and |atan2(qy, qx)| < bearing_bound[f].  The bearing is the horizontal
+ * one, over the x and y columns, as mapping.py:183-185 takes it from 3-column points; there is no elevation gate because the
+ * reference has none, so a z = 0 cloud gives the 2-D gate's result.  A point is selected iff some frame sees it.
+ * key_counts_out[j*n_keys + k] = the selected points of job j with key k (keys >= n_keys are selected but not counted);
+ * n_selected_out[j], n_ambiguous_out[j] per job.  The ambiguity rule is sfe_cloud_store_fov_select's: atan2 runs in double
+ * and decides only outside 1e-6 a + 1e-30 of the bound; a point that no frame selects for certain and some frame leaves
+ * undecided counts as ambiguous and is left unselected -- the caller then evaluates the gate in numpy for that cloud and
+ * hands the result to sfe_cloud_store3_set_selection.  The selection bytes stay on the device, per cloud (a cloud named
+ * by two jobs of one call keeps the bytes of one of them).  A plain slot is SFE_ERR_ARG. */
+int sfe_cloud_store3_fov_select(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handles, int n_jobs, const float *Hinv12,
+                                const double *range_bound, const double *bearing_bound, const int32_t *frame_off, int n_keys,
+                                int32_t *key_counts_out, int32_t *n_selected_out, int32_t *n_ambiguous_out);
+/* the host's selection (a byte per point, non-zero = selected) replaces the device's; n must equal the cloud's count */
+int sfe_cloud_store3_set_selection(sfe_ctx *ctx, sfe_cloud_store3 *s, int32_t handle, const uint8_t *sel, int n);
+/* points[sel], keys[sel] (slam.py:898-899) of n_jobs keyed clouds, order kept: each result is a new keyed slot (empty if
+ * nothing was selected).  A cloud for which no selection was written (by fov_select or set_selection) is SFE_ERR_ARG.
+ * SFE_ERR_CAP, and nothing changes, if the call's upper bound -- the sum of its clouds' counts, or its n_jobs slots --
+ * does not fit. */
+int sfe_cloud_store3_compact_selected(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handles, int n_jobs,
+                                      const int64_t *stamps, int32_t *handles_out);
+/* get_overlap(..., return_indices=True) and the per-key count of slam.py:977-985 for n_jobs pairs in one launch: job j
+ * moves source pairs[2j] by H12[j*12 ..]; every moved point gets its sfe_match3 neighbour in the keyed target pairs[2j+1]
+ * (the nearest point, the lowest index among equal distances, kept iff d2 <= fl(max_dist * max_dist); NaN and infinite
+ * distances never match).  key_counts_out[j*n_keys + k] = the matches whose neighbour has key k (keys >= n_keys are not
+ * counted); overlap_out[j] = the number of matches = what sfe_cloud_store3_overlap returns for the pair.  An empty source
+ * or target gives zeros; a plain target is SFE_ERR_ARG. */
+int sfe_cloud_store3_match_keys(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *pairs, const float *H12, int n_jobs,
+                                float max_dist, int n_keys, int32_t *key_counts_out, int32_t *overlap_out);
 
 /* ---- global-initialisation matching cost: slam.py:461-570 ---------------- */
 /*

@@ -253,6 +253,16 @@ SIGNATURES = {
     "sfe_cloud_store3_get_points": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_int, C.c_float, _i64p, _i32p]),
     "sfe_icp3_store_compute": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _f32p, C.c_int, _f32p, _i32p, _i32p]),
     "sfe_cloud_store3_overlap": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, _i32p]),
+    # ... its keyed clouds: the SLAM cloud and the candidate selection of the loop-closure search over handles
+    "sfe_cloud_store3_put_keys": (C.c_int, [_vp, _vp, C.c_int64, _f32p, _i32p, C.c_int, _i32p]),
+    "sfe_cloud_store3_keyed": (C.c_int, [_vp, C.c_int32]),
+    "sfe_cloud_store3_get_points_keys": (C.c_int, [_vp, _vp, _i32p, _f32p, _i32p, _i32p, C.c_int, C.c_float, _i64p, _i32p]),
+    "sfe_cloud_store3_read_keys": (C.c_int, [_vp, _vp, C.c_int32, _i32p, C.c_int, C.POINTER(C.c_int)]),
+    "sfe_cloud_store3_fov_select": (C.c_int, [_vp, _vp, _i32p, C.c_int, _f32p, _f64p, _f64p, _i32p, C.c_int, _i32p, _i32p,
+                                              _i32p]),
+    "sfe_cloud_store3_set_selection": (C.c_int, [_vp, _vp, C.c_int32, _u8p, C.c_int]),
+    "sfe_cloud_store3_compact_selected": (C.c_int, [_vp, _vp, _i32p, C.c_int, _i64p, _i32p]),
+    "sfe_cloud_store3_match_keys": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, C.c_int, _i32p, _i32p]),
     "sfe_feature_extract_ping_store": (C.c_int, [_vp, _vp, _vp, C.c_int64, _u8p, C.c_int, C.c_int, C.c_int, C.c_int,
                                                  C.c_double, C.c_int, C.c_float, C.c_double, C.c_int, C.c_int64, C.c_int,
                                                  _i32p, _i32p, _i32p, _f32p, _u8p]),

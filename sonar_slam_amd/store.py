@@ -8,7 +8,8 @@ handles; the host sees sizes (a few bytes per cloud) and results, and the points
 (``read``: the PointCloud2 for rviz / the mapping node).
 
 ``CloudStore3`` (``sfe_cloud_store3``) is the same for the N x 3 clouds a keyframe carries (``Keyframe.points3D``,
-slam_objects.py:101-106, 200-223): ``put``, ``get_points``, ``icp`` and ``overlap`` over handles, with 4 x 4 transforms.
+slam_objects.py:101-106, 200-223): ``put``, ``get_points``, ``icp`` and ``overlap`` over handles, with 4 x 4 transforms, and
+the keyed clouds of the loop-closure search (``get_points_keys``, ``fov_select``, ``compact_selected``, ``match_keys``).
 """
 import ctypes as _C
 
@@ -357,13 +358,30 @@ def pose_H12(matrix):
     return H[:3, :].reshape(12)
 
 
+def fov3_numpy(points, Hinv, range_bound, bearing_bound):
+    """One frame of the field-of-view gate of slam.py:891-894 on an N x 3 float32 cloud, in plain numpy: the points moved
+    into the frame by ``Keyframe.transform_points_3D``'s product, the range over all three columns, the bearing over x and y
+    (no elevation gate: the reference has none) -> bool [N]"""
+    points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    H = np.asarray(Hinv, np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        local_points = points.dot(H[:3, :3].T) + H[:3, 3]
+        ranges = np.linalg.norm(local_points, axis=1)
+        bearings = np.arctan2(local_points[:, 1], local_points[:, 0])
+        return (ranges < range_bound) & (abs(bearings) < bearing_bound)
+
+
 class CloudStore3(object):
     """``sfe_cloud_store3``: the keyframe store for N x 3 float32 clouds (``Keyframe.points3D``).  Clouds live in HBM under
     integer handles; ``get_points`` (transform + concatenate + the 3-D ``pcl.downsample``), ``icp`` (the 3-D point-to-point
     ICP of ``pcl.ICP``) and ``overlap`` take handles and return, bit for bit, what the host-pointer ``pcl`` calls return on
     the same clouds moved by numpy's float32 ``points.dot(H[:3, :3].T) + H[:3, 3]``.  A call that does not fit the pool or the
-    slot table raises (SFE_ERR_CAP) and leaves the store as it was.  No keyed clouds, field-of-view gate or loop-closure
-    search in 3-D, and no device-to-device producer: clouds come in through ``put``."""
+    slot table raises (SFE_ERR_CAP) and leaves the store as it was.
+
+    Keyed clouds (a keyframe index per point): ``put_keys`` / ``get_points_keys`` make them -- the SLAM cloud of
+    slam_ros.py:317-359 -- and ``fov_select``, ``compact_selected`` and ``match_keys`` run the candidate selection of the
+    loop-closure search (slam.py:873-902, :977-997) on them, many clouds per call.  No device-to-device producer (clouds
+    come in through ``put`` / ``put_keys``) and no ``FrontEnd`` / ``SessionBatch`` wiring in 3-D."""
 
     def __init__(self, ctx=None, capacity_points=1 << 22, max_clouds=1 << 16):
         self.ctx = ctx or _L.default_context()
@@ -484,6 +502,169 @@ class CloudStore3(object):
                 self.ctx.handle, self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(H12, _C.c_float), n, float(max_dist),
                 _L.ptr(out, _C.c_int32)))
         return out
+
+    # -- keyed clouds: the SLAM cloud and the candidate selection of the loop-closure search (slam.py:873-902, :977-997) --
+    @staticmethod
+    def _keys(keys, n, what):
+        wide = np.asarray(keys).reshape(-1)
+        if len(wide) != n:
+            raise ValueError("%s: %d keys for %d %s" % (what[0], len(wide), n, what[1]))
+        if len(wide) and not (np.all(wide >= 0) and np.all(wide < 2 ** 31) and np.all(wide == np.floor(wide))):
+            raise ValueError("%s: keys must be integers in [0, 2^31)" % what[0])
+        return np.ascontiguousarray(wide, np.int32)
+
+    @staticmethod
+    def _points3(points, what):
+        pts = np.asarray(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("%s: points must be N x 3, got %r" % (what, pts.shape))
+        return np.ascontiguousarray(pts, np.float32)
+
+    def put_keys(self, points, keys, stamp=0):
+        """``put`` with a key per point (integers in [0, 2^31)): a keyed cloud, as ``get_points_keys`` leaves one -> handle"""
+        pts = self._points3(points, "CloudStore3.put_keys")
+        ks = self._keys(keys, len(pts), ("CloudStore3.put_keys", "points"))
+        h = _C.c_int32(-1)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_put_keys(self.ctx.handle, self.handle, int(stamp),
+                                                                   _L.ptr(pts, _C.c_float), _L.ptr(ks, _C.c_int32), len(pts),
+                                                                   _C.byref(h)))
+        return h.value
+
+    def is_keyed(self, handle):
+        r = int(self.ctx.lib.sfe_cloud_store3_keyed(self.handle, int(handle)))
+        if r < 0:
+            raise ValueError("CloudStore3.is_keyed: no cloud %d" % int(handle))
+        return bool(r)
+
+    def get_points_keys(self, handle_lists, transform_lists, key_lists, resolution, stamps=None):
+        """``SLAM.get_points(frames, ref, return_keys=True)`` on 3-D clouds for many targets at once: per target a list of
+        handles (-1 = unused), one 4 x 4 matrix and one key per listed handle.  Cloud k is moved by its matrix, every point of
+        it tagged with its key, the clouds concatenated in list order and downsampled like ``pcl.downsample(points, keys,
+        resolution)`` (``resolution <= 0``: not at all).  The points are those of ``get_points`` for the same inputs.
+        -> new keyed handles int32 [n_targets] (their keys: ``read_keys``)"""
+        n_jobs = len(handle_lists)
+        if len(transform_lists) != n_jobs or len(key_lists) != n_jobs:
+            raise ValueError("CloudStore3.get_points_keys: %d handle lists but %d transform lists and %d key lists"
+                             % (n_jobs, len(transform_lists), len(key_lists)))
+        hs, Hs, ks, off = [], [], [], [0]
+        for j, (h, H, k) in enumerate(zip(handle_lists, transform_lists, key_lists)):
+            if len(H) != len(h):
+                raise ValueError("CloudStore3.get_points_keys: target %d lists %d handles but %d transforms" % (j, len(h), len(H)))
+            ks.append(self._keys(k, len(h), ("CloudStore3.get_points_keys: target %d" % j, "handles")))
+            hs.extend(int(x) for x in h)
+            Hs.extend(pose_H12(x) for x in H)
+            off.append(len(hs))
+        handles = np.ascontiguousarray(hs, np.int32).reshape(-1)
+        H12 = np.ascontiguousarray(np.stack(Hs) if Hs else np.zeros((0, 12)), np.float32)
+        keys = np.ascontiguousarray(np.concatenate(ks) if ks else np.zeros(0), np.int32)
+        job_off = np.ascontiguousarray(off, np.int32)
+        out = np.full(n_jobs, -1, np.int32)
+        st = None if stamps is None else np.ascontiguousarray(stamps, np.int64).reshape(n_jobs)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_get_points_keys(
+                self.ctx.handle, self.handle, _L.ptr(handles, _C.c_int32), _L.ptr(H12, _C.c_float), _L.ptr(keys, _C.c_int32),
+                _L.ptr(job_off, _C.c_int32), n_jobs, float(resolution), None if st is None else _L.ptr(st, _C.c_int64),
+                _L.ptr(out, _C.c_int32)))
+        return out
+
+    def read_keys(self, handle):
+        """the keys of one keyed cloud (int32 [N]), copied to the host"""
+        n = int(self.counts([handle])[0])
+        out = np.zeros(n, np.int32)
+        m = _C.c_int(0)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_read_keys(self.ctx.handle, self.handle, int(handle),
+                                                                    _L.ptr(out, _C.c_int32), len(out), _C.byref(m)))
+        return out
+
+    def fov_select(self, handles, Hinv_lists, range_bounds, bearing_bounds, n_keys, resolve=True):
+        """The field-of-view gate of slam.py:875-899 on keyed 3-D clouds, many at once: cloud ``handles[j]`` against the
+        frames of ``Hinv_lists[j]`` (4 x 4 matrices, ``pose.inverse()``) with ``range_bounds[j]`` / ``bearing_bounds[j]`` (one
+        float64 per frame).  A point is selected iff some frame sees it (``fov3_numpy``); the selection stays on the device
+        for ``compact_selected``.  -> (per-key counts of the selected points int32 [n x n_keys], selected int32 [n],
+        undecided int32 [n]).  With ``resolve`` a cloud the device could not decide (a bearing within 1e-6 of its bound) is read
+        back, gated by ``fov3_numpy`` and written with ``set_selection``, so the caller always gets numpy's selection and
+        the third array is zero; without it the three arrays are the device's own."""
+        h = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        n_jobs = len(h)
+        if not (len(Hinv_lists) == len(range_bounds) == len(bearing_bounds) == n_jobs):
+            raise ValueError("CloudStore3.fov_select: %d handles but %d frame lists, %d range-bound lists and %d bearing-bound "
+                             "lists" % (n_jobs, len(Hinv_lists), len(range_bounds), len(bearing_bounds)))
+        n_keys = int(n_keys)
+        if n_keys < 0:
+            raise ValueError("CloudStore3.fov_select: n_keys must be >= 0")
+        Hs, rbs, bbs, off = [], [], [], [0]
+        for j in range(n_jobs):
+            rb = np.asarray(range_bounds[j], np.float64).reshape(-1)
+            bb = np.asarray(bearing_bounds[j], np.float64).reshape(-1)
+            if not (len(Hinv_lists[j]) == len(rb) == len(bb)):
+                raise ValueError("CloudStore3.fov_select: cloud %d has %d frames but %d range bounds and %d bearing bounds"
+                                 % (j, len(Hinv_lists[j]), len(rb), len(bb)))
+            Hs.extend(pose_H12(H) for H in Hinv_lists[j])
+            rbs.append(rb)
+            bbs.append(bb)
+            off.append(len(Hs))
+        H12 = np.ascontiguousarray(np.stack(Hs) if Hs else np.zeros((0, 12)), np.float32)
+        rb = np.ascontiguousarray(np.concatenate(rbs) if rbs else np.zeros(0), np.float64)
+        bb = np.ascontiguousarray(np.concatenate(bbs) if bbs else np.zeros(0), np.float64)
+        frame_off = np.ascontiguousarray(off, np.int32)
+        hist = np.zeros((n_jobs, n_keys), np.int32)
+        n_sel, n_amb = np.zeros(n_jobs, np.int32), np.zeros(n_jobs, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_fov_select(
+                self.ctx.handle, self.handle, _L.ptr(h, _C.c_int32), n_jobs, _L.ptr(H12, _C.c_float), _L.ptr(rb, _C.c_double),
+                _L.ptr(bb, _C.c_double), _L.ptr(frame_off, _C.c_int32), n_keys, _L.ptr(hist, _C.c_int32),
+                _L.ptr(n_sel, _C.c_int32), _L.ptr(n_amb, _C.c_int32)))
+        if resolve:
+            for j in np.nonzero(n_amb)[0]:
+                pts, keys = self.read(int(h[j])), self.read_keys(int(h[j]))
+                sel = np.zeros(len(pts), bool)
+                for H, r, b in zip(Hinv_lists[j], rbs[j], bbs[j]):
+                    sel |= fov3_numpy(pts, H, r, b)
+                self.set_selection(int(h[j]), sel)
+                picked = keys[sel]
+                hist[j] = np.bincount(picked[picked < n_keys], minlength=n_keys)[:n_keys]
+                n_sel[j], n_amb[j] = int(sel.sum()), 0
+        return hist, n_sel, n_amb
+
+    def set_selection(self, handle, sel):
+        """the host's selection (one value per point, non-zero = selected) replaces the device's"""
+        sel = np.ascontiguousarray(np.asarray(sel).reshape(-1) != 0, np.uint8)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_set_selection(self.ctx.handle, self.handle, int(handle),
+                                                                        _L.ptr(sel, _C.c_uint8), len(sel)))
+
+    def compact_selected(self, handles, stamps=None):
+        """``points[sel]``, ``keys[sel]`` (slam.py:898-899) of many keyed clouds, order kept -> new keyed handles int32 [n]"""
+        h = np.ascontiguousarray(handles, np.int32).reshape(-1)
+        st = None if stamps is None else np.ascontiguousarray(stamps, np.int64).reshape(len(h))
+        out = np.full(len(h), -1, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_compact_selected(
+                self.ctx.handle, self.handle, _L.ptr(h, _C.c_int32), len(h), None if st is None else _L.ptr(st, _C.c_int64),
+                _L.ptr(out, _C.c_int32)))
+        return out
+
+    def match_keys(self, pairs, transforms, max_dist, n_keys):
+        """slam.py:977-985 for many (source, keyed target) pairs: the source moved by its 4 x 4 transform, every moved point
+        matched like ``pcl.match(target, moved, 1, max_dist)`` -> (per-key counts of the matched targets int32 [n x n_keys],
+        overlaps int32 [n] = ``overlap`` of the same pairs)"""
+        pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        n = len(pairs)
+        if len(transforms) != n:
+            raise ValueError("CloudStore3.match_keys: %d pairs but %d transforms" % (n, len(transforms)))
+        n_keys = int(n_keys)
+        if n_keys < 0:
+            raise ValueError("CloudStore3.match_keys: n_keys must be >= 0")
+        H12 = np.ascontiguousarray(np.stack([pose_H12(H) for H in transforms]) if n else np.zeros((0, 12)), np.float32)
+        hist = np.zeros((n, n_keys), np.int32)
+        ov = np.zeros(n, np.int32)
+        with self.ctx.lock:
+            self.ctx._check(self.ctx.lib.sfe_cloud_store3_match_keys(
+                self.ctx.handle, self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(H12, _C.c_float), n, float(max_dist), n_keys,
+                _L.ptr(hist, _C.c_int32), _L.ptr(ov, _C.c_int32)))
+        return hist, ov
 
     def close(self):
         if self.handle is not None and self.ctx.handle is not None:

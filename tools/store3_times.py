@@ -12,6 +12,11 @@ around it covers the device work.  Medians and the spread (min .. max) over --re
 route.  The results of the two routes are compared bit for bit once per shape.
 
     python tools/store3_times.py [--shapes 32x800 256x5000] [--reps 5]
+
+``--keys`` times the keyed clouds instead (``keys_leg``): the candidate selection of the loop-closure search over handles
+next to the same selection through ``read``, numpy and the host-pointer ``pcl`` calls, one session at a time.
+
+    python tools/store3_times.py --keys [--keys-shapes 32x40x800 1x200x800] [--reps 5]
 """
 import argparse
 import os
@@ -22,7 +27,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sonar_slam_amd import _lib, icp_config, pcl  # noqa: E402
-from sonar_slam_amd.store import CloudStore3  # noqa: E402
+from sonar_slam_amd.store import CloudStore3, fov3_numpy  # noqa: E402
 
 f32 = np.float32
 RESOLUTION, OVERLAP_DIST = 0.1, 0.2
@@ -60,12 +65,132 @@ def session(seed, n):
     return clouds, between, guess
 
 
+def keyed_session(seed, n_kf, n):
+    """n_kf keyframes of n points along a circle of 6 m radius, each cloud a sector (range < 11 m, |bearing| < 1 rad) of one
+    world seen from its pose -> (clouds float32 in their own frames, poses float64 4 x 4)"""
+    rng = np.random.default_rng(seed)
+    world = rng.uniform(-1, 1, (40 * n, 3)) * np.array([16.0, 16.0, 2.0])
+    clouds, poses = [], []
+    for k in range(n_kf):
+        th = 2 * np.pi * k / (n_kf - 1.0)
+        P = rigid((0.01, -0.02, 1.0), th + np.pi / 2, (6.0 * np.cos(th), 6.0 * np.sin(th), 0.1 * np.sin(3 * th)))
+        Pi = np.linalg.inv(P)
+        local = world @ Pi[:3, :3].T + Pi[:3, 3]
+        seen = np.nonzero((np.linalg.norm(local, axis=1) < 11.0) & (np.abs(np.arctan2(local[:, 1], local[:, 0])) < 1.0))[0]
+        pick = rng.permutation(seen)[:n]
+        clouds.append((local[pick] + rng.normal(0, 0.004, (len(pick), 3))).astype(f32))
+        poses.append(P)
+    return clouds, poses
+
+
+KEYS_RESOLUTION, KEYS_MAX_DIST, KEYS_SEP, KEYS_SOURCES = 0.3, 0.5, 4, 2
+
+
+def keys_leg(ctx, shapes, reps):
+    """The candidate selection of the loop-closure search (slam.py:873-902, :977-985) for every session: the keyed target from
+    all keyframes but the last KEYS_SEP in the global frame, the field-of-view gate of the last KEYS_SOURCES keyframes, the
+    selected points, and the last keyframe's cloud under an estimated pose matched against them, counted per key.
+
+      store route   get_points_keys, fov_select, compact_selected, match_keys: each ONE call for all sessions
+      host route    per session: ``read`` every cloud, numpy transform and tags, pcl.downsample(points, keys, resolution),
+                    store.fov3_numpy per source frame, boolean index, pcl.match and np.unique
+    """
+    print("\nstore3_times --keys on %s: resolution %g, gate of %d frames, matching radius %g m; %d timed selections per route, "
+          "alternated" % (ctx.name(), KEYS_RESOLUTION, KEYS_SOURCES, KEYS_MAX_DIST, reps))
+    for shape in shapes:
+        S, n_kf, n = (int(v) for v in shape.split("x"))
+        data = [keyed_session(7000 * S + k, n_kf, n) for k in range(S)]
+        n_tgt = n_kf - KEYS_SEP
+        store = CloudStore3(ctx, capacity_points=S * (n_kf + 2 * n_tgt) * n + 1024, max_clouds=S * (n_kf + 4) + 8)
+        hk = [[store.put(c) for c in clouds] for clouds, _ in data]
+        ctx.sync()
+        base = len(store)
+        tf = list(range(n_tgt))
+        sf = [n_kf - 1 - k for k in range(KEYS_SOURCES)]
+        Hg = [[np.asarray(poses[k], f32) for k in tf] for _, poses in data]
+        Hinv = [[np.asarray(np.linalg.inv(poses[k]), f32) for k in sf] for _, poses in data]
+        rb = [[12.0 + 0.5 * k for k in range(KEYS_SOURCES)]] * S
+        bb = [[1.2 + 0.05 * k for k in range(KEYS_SOURCES)]] * S
+        est = [np.asarray(poses[-1] @ rigid((0, 0, 1), 0.004, (0.03, -0.02, 0.01)), f32) for _, poses in data]
+
+        def store_step():
+            t = [time.perf_counter()]
+            tgt = store.get_points_keys([[h[k] for k in tf] for h in hk], Hg, [tf] * S, KEYS_RESOLUTION)
+            t.append(time.perf_counter())
+            hist, n_sel, n_amb = store.fov_select(tgt, Hinv, rb, bb, n_kf)
+            t.append(time.perf_counter())
+            near = store.compact_selected(tgt)
+            t.append(time.perf_counter())
+            hist1, ov = store.match_keys([[h[-1], int(x)] for h, x in zip(hk, near)], est, KEYS_MAX_DIST, n_kf)
+            t.append(time.perf_counter())
+            sizes = store.counts(tgt)
+            store.truncate(base)
+            return np.diff(t), (hist, n_sel, hist1, ov, sizes)
+
+        def host_step():
+            t = [0.0] * 4
+            out = []
+            for j, h in enumerate(hk):
+                t0 = time.perf_counter()
+                clouds = [store.read(x) for x in h]
+                cat = np.concatenate([move(clouds[k], H) for k, H in zip(tf, Hg[j])])
+                tags = np.concatenate([np.full(len(clouds[k]), k, f32) for k in tf])
+                points, keys = pcl.downsample(cat, tags, KEYS_RESOLUTION, ctx=ctx)
+                t1 = time.perf_counter()
+                sel = np.zeros(len(points), bool)
+                for H, r, b in zip(Hinv[j], rb[j], bb[j]):
+                    sel |= fov3_numpy(points, H, r, b)
+                frames, counts = np.unique(np.int32(keys[sel]), return_counts=True)
+                t2 = time.perf_counter()
+                near_p, near_k = points[sel], keys[sel]
+                t3 = time.perf_counter()
+                ids = pcl.match(near_p, move(clouds[-1], est[j]), 1, KEYS_MAX_DIST, ctx=ctx)[0][0]
+                frames1, counts1 = np.unique(np.int32(near_k[ids[ids != -1]]), return_counts=True)
+                t4 = time.perf_counter()
+                for k, d in enumerate((t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+                    t[k] += d
+                out.append((np.bincount(frames, weights=counts, minlength=n_kf).astype(np.int32), int(sel.sum()),
+                            np.bincount(frames1, weights=counts1, minlength=n_kf).astype(np.int32), int((ids != -1).sum()),
+                            len(points)))
+            return np.array(t), tuple(np.array([o[k] for o in out], np.int32) for k in range(5))
+
+        _, rs = store_step()
+        _, rh = host_step()
+        same = all(np.array_equal(x, y) for x, y in zip(rs, rh))
+        if not same:
+            sys.exit("--keys %s: the two routes differ" % shape)
+        ts, th = [], []
+        for _ in range(reps):
+            ts.append(store_step()[0])
+            th.append(host_step()[0])
+        ts, th = 1e3 * np.array(ts), 1e3 * np.array(th)
+        print("\n%d sessions x %d keyframes of %d points: keyed targets of %d .. %d points, %d .. %d selected, overlaps %d .. %d, "
+              "results of the two routes equal" % (S, n_kf, n, rs[4].min(), rs[4].max(), rs[1].min(), rs[1].max(), rs[3].min(),
+                                                    rs[3].max()))
+        print("  %-18s %28s %28s %8s" % ("ms per selection", "store handles", "host pointers", "ratio"))
+        for k, name in enumerate(("get_points_keys", "fov_select", "compact_selected", "match_keys")):
+            ms, mh = np.median(ts[:, k]), np.median(th[:, k])
+            print("  %-18s %9.3f (%8.3f .. %8.3f) %9.3f (%8.3f .. %8.3f) %7.2fx"
+                  % (name, ms, ts[:, k].min(), ts[:, k].max(), mh, th[:, k].min(), th[:, k].max(), mh / ms))
+        ss, sh = ts.sum(axis=1), th.sum(axis=1)
+        print("  %-18s %9.3f (%8.3f .. %8.3f) %9.3f (%8.3f .. %8.3f) %7.2fx"
+              % ("selection", np.median(ss), ss.min(), ss.max(), np.median(sh), sh.min(), sh.max(), np.median(sh) / np.median(ss)))
+        store.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["32x800", "256x5000"], help="sessions x points per keyframe cloud")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--keys", action="store_true", help="time the keyed clouds (the candidate selection of the loop-closure "
+                                                        "search) instead of the SLAM step")
+    ap.add_argument("--keys-shapes", nargs="+", default=["32x40x800", "1x200x800"],
+                    help="--keys: sessions x keyframes x points per keyframe cloud")
     a = ap.parse_args()
     ctx = _lib.default_context()
+    if a.keys:
+        keys_leg(ctx, a.keys_shapes, a.reps)
+        return
     params = icp_config.shipped_params()
     icp = pcl.ICP(ctx=ctx)
     icp.setParams(params)
