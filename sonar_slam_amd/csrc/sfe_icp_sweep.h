@@ -74,7 +74,8 @@ struct StripTab {
     float ylo, inv_g;         // strip(y) = clamp(int((y - ylo) * inv_g), 0, ns - 1)
     float ext_x;              // x extent of the finite points (initial cap of the search)
     // witness grid (iteration 0): cell (ix, iy) = clamp(int((x - gx0) * ginv)), clamp(int((y - gy0) * ginv));
-    // grid[iy * gnx + ix] = sorted position of the target point nearest to the cell's centre (0: none)
+    // grid[iy * gnx + ix] = sorted position of a target point near the cell's centre; far from every point: the witness of
+    // the cell's coarse cell, metres away (0: the target has no finite point)
     float gx0, gy0, ginv;
     int gnx, gny;
     int grid_off64; // this target's slice of the witness-grid scratch starts at int 64 * grid_off64

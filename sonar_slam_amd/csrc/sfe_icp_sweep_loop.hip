@@ -699,7 +699,8 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                     } else if (fresh && valid && grid != nullptr) {
                         // first iteration: no previous neighbour yet -- the target point nearest to the centre of the
                         // query's grid cell (prep kernel) is the witness: a real target within half a cell diagonal
-                        // of the best one, instead of whatever the own strip's x-walk happens to meet first
+                        // of the best one, instead of whatever the own strip's x-walk happens to meet first (far from every
+                        // structure the cell holds its coarse cell's witness: any target within maxDist will do there)
                         float gxv = f_mul(f_add(px, -tab.gx0), tab.ginv), gyv = f_mul(f_add(py, -tab.gy0), tab.ginv);
                         gxv = fminf(fmaxf(gxv, 0.0f), (float)(tab.gnx - 1)); // NaN -> 0
                         gyv = fminf(fmaxf(gyv, 0.0f), (float)(tab.gny - 1));
@@ -720,7 +721,8 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                                 grid_hit = P.use_trimmed_filter && C < Cmax && dw < r2m_up && (sw_cache & 8) != 0; // (a witness just beyond maxDist settles nothing)
                             }
                         }
-                        // A query WITHOUT a usable witness (an empty cell far from every structure, a witness beyond maxDist)
+                        // A query WITHOUT a usable witness (a witness beyond maxDist: far from every structure a cell holds its
+                        // coarse cell's, metres away; an empty cell: no finite target)
                         // would now walk its whole maxDist window -- nothing bounds it until it meets a target -- while the
                         // witnessed queries of its wave, and after the pass the whole workgroup, wait for it.  It is put off
                         // to the same forced next round instead, where it searches next to everybody else.  (Suspended

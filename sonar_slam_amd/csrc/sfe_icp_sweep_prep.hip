@@ -2,6 +2,11 @@
 // distinct target; many guesses on one pair share it).  Shared definitions and the overview: sfe_icp_sweep.h.
 #include "sfe_icp_sweep.h"
 
+// second level of the witness grid (sweep_grid_witness)
+#define SW_COARSE_SHIFT 3    // a coarse cell is 8 x 8 fine cells ...
+#define SW_COARSE_MAX 256    // ... or 16 x 16, 32 x 32, ...: the first that leaves at most this many coarse cells
+#define SW_COARSE_SWEEPS SW_COARSE_MAX // most dilation sweeps of the coarse level: enough for a single row of cells
+
 template <int NT, int TCAP>
 struct PrepShared {
     // first the sort keys, then (same bytes) the sorted cloud with its sentinels
@@ -12,6 +17,7 @@ struct PrepShared {
     int cnt[SW_NS_MAX];
     unsigned smin_k[SW_NS_MAX], smax_k[SW_NS_MAX];
     StripTab tab;
+    unsigned coarse[2 * SW_COARSE_MAX]; // second level of the witness grid (sweep_grid_witness)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -235,14 +241,16 @@ __device__ __forceinline__ void sweep_knn_normals(const sfe_icp_params &P, const
 // cell (the point nearest to the centre wins: one atomicMin on (distance bits | position)), then
 // a few dilation sweeps hand witnesses to the empty cells around occupied ones (a cell takes, among its 8 neighbours'
 // witnesses, the one nearest to its own centre; in place, so a sweep carries them further than one cell).  Cells
-// that stay empty are far from every structure: queries there start the first iteration without a witness, as before.
+// that stay empty are far from every structure (the scattered outliers of a scan land there): they take their witness
+// from a second, coarse level of the grid, below.
 // (A per-cell nearest-neighbour search was tried first: the empty two thirds of a sonar fan's bounding box have their
 // nearest point metres away, and those searches cost 2 ms per 512 targets.)
 #define SW_GRID_SWEEPS 4
 template <int NT>
 __device__ __forceinline__ void sweep_grid_witness(const StripTab &tab, const float2 *__restrict__ s_tgt,
-                                                   int *__restrict__ grid_out, unsigned *grid)
+                                                   int *__restrict__ grid_out, unsigned *grid, unsigned *coarse)
 { // grid: LDS, SW_GRID_MAX words: (distance to the cell centre, top 16 bits of its float pattern) << 16 | position
+  // coarse: LDS, 2 x SW_COARSE_MAX words (2 KB): the second level and the buffer its sweeps write
     const int gnx = tab.gnx, gny = tab.gny, ncell = gnx * gny, len = tab.len;
     const float cs = tab.ginv > 0.0f ? 1.0f / tab.ginv : 0.0f;
     const float gx0 = tab.gx0, gy0 = tab.gy0, ginv = tab.ginv;
@@ -301,8 +309,82 @@ __device__ __forceinline__ void sweep_grid_witness(const StripTab &tab, const fl
         }
         __syncthreads();
     }
-    for (int c = threadIdx.x; c < ncell; c += NT)
-        grid_out[c] = (int)grid[c];
+    // Second, coarse level: one cell per F x F fine cells over the same box (F = 1 << SW_COARSE_SHIFT, doubled until at
+    // most SW_COARSE_MAX cells are left).  A coarse cell takes, among the witnesses of its fine cells, the one nearest to
+    // ITS centre (the same atomicMin), and the coarse grid is dilated -- synchronously, between two buffers: the result
+    // does not depend on the order of the threads -- until a sweep changes nothing: two sweeps on a sonar cloud's
+    // 70 cells; SW_COARSE_SWEEPS bounds the loop and never binds (a witness crosses a single row of SW_COARSE_MAX cells
+    // in one sweep fewer), so no cell stays empty unless the target has no finite point.  Every fine cell that is still
+    // empty is handed its coarse cell's witness: metres away, but a real target, and a query that meets one within
+    // maxDist need not look for one in the whole maxDist box (the loop kernel's cooperative tier, ~770 candidates).
+    int fs = SW_COARSE_SHIFT;
+    while ((((gnx - 1) >> fs) + 1) * (((gny - 1) >> fs) + 1) > SW_COARSE_MAX)
+        ++fs;
+    const int cnx = ((gnx - 1) >> fs) + 1, cny = ((gny - 1) >> fs) + 1, ncc = cnx * cny;
+    const float ccs = (float)(1 << fs) * cs;
+    auto coarse_centre = [&](int cc) {
+        const int iy = cc / cnx, ix = cc - iy * cnx;
+        return make_float2(gx0 + ((float)ix + 0.5f) * ccs, gy0 + ((float)iy + 0.5f) * ccs);
+    };
+    unsigned *ca = coarse, *cb = coarse + SW_COARSE_MAX;
+    for (int cc = threadIdx.x; cc < ncc; cc += NT)
+        ca[cc] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (int c = threadIdx.x; c < ncell; c += NT) {
+        const unsigned w = grid[c];
+        if (w == 0)
+            continue;
+        const int iy = c / gnx, ix = c - iy * gnx, cc = (iy >> fs) * cnx + (ix >> fs);
+        const float2 m = coarse_centre(cc), t = s_tgt[w];
+        atomicMin(&ca[cc], (__float_as_uint(dist2(m.x, m.y, t.x, t.y)) & 0xFFFF0000u) | w); // (w < 65536: claimed above)
+    }
+    __syncthreads();
+    for (int cc = threadIdx.x; cc < ncc; cc += NT)
+        ca[cc] = (ca[cc] == 0xFFFFFFFFu) ? 0u : (ca[cc] & 0xFFFFu);
+    __syncthreads();
+    for (int it = 0; it < SW_COARSE_SWEEPS; ++it) {
+        int changed = 0;
+        for (int cc = threadIdx.x; cc < ncc; cc += NT) {
+            unsigned v = ca[cc];
+            if (v == 0) {
+                const int iy = cc / cnx, ix = cc - iy * cnx;
+                const float2 m = coarse_centre(cc);
+                float best = INFINITY;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const int dx = (k < 3) ? k - 1 : (k == 3 ? -1 : (k == 4 ? 1 : k - 6));
+                    const int dy = (k < 3) ? -1 : (k < 5 ? 0 : 1);
+                    const int jx = ix + dx, jy = iy + dy;
+                    if (jx < 0 || jx >= cnx || jy < 0 || jy >= cny)
+                        continue;
+                    const unsigned w = ca[jy * cnx + jx];
+                    if (w != 0) {
+                        const float2 t = s_tgt[w];
+                        const float d = dist2(m.x, m.y, t.x, t.y);
+                        if (d < best) {
+                            best = d;
+                            v = w;
+                        }
+                    }
+                }
+                changed |= v != 0;
+            }
+            cb[cc] = v;
+        }
+        if (!__syncthreads_or(changed))
+            break; // (cb is a copy of ca)
+        unsigned *const t = ca;
+        ca = cb;
+        cb = t;
+    }
+    for (int c = threadIdx.x; c < ncell; c += NT) {
+        unsigned w = grid[c];
+        if (w == 0) {
+            const int iy = c / gnx, ix = c - iy * gnx;
+            w = ca[(iy >> fs) * cnx + (ix >> fs)];
+        }
+        grid_out[c] = (int)w;
+    }
 }
 
 // bitonic sort of n2 (power of two, > CH) 64-bit keys in HBM scratch by one workgroup (targets that do not fit LDS; once
@@ -576,9 +658,9 @@ __global__ __launch_bounds__(NT, GTAIL ? 8 : 4) void icp_sweep_prep_kernel(sfe_i
         if constexpr (GTAIL) {
             const int room = (TCAP + SW_PAD + 4 - used_slots) * 2, ncell = S.tab.gnx * S.tab.gny;
             unsigned *tail = reinterpret_cast<unsigned *>(S.buf + used_slots);
-            sweep_grid_witness<NT>(S.tab, cloud, out, ncell <= room ? tail : reinterpret_cast<unsigned *>(out));
+            sweep_grid_witness<NT>(S.tab, cloud, out, ncell <= room ? tail : reinterpret_cast<unsigned *>(out), S.coarse);
         } else {
-            sweep_grid_witness<NT>(S.tab, cloud, out, reinterpret_cast<unsigned *>(s_grid));
+            sweep_grid_witness<NT>(S.tab, cloud, out, reinterpret_cast<unsigned *>(s_grid), S.coarse);
         }
     };
     float2 *nrm = snrm_all ? snrm_all + J.off : nullptr;
