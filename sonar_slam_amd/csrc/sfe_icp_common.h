@@ -3,6 +3,7 @@
 // explicit IEEE roundings (no contraction) so both kernels and the oracle take the same decisions.
 #pragma once
 #include "sfe_internal.h"
+#include "sfe_wave_sum_plan.h"
 
 #ifndef ICP_THREADS
 #define ICP_THREADS 1024
@@ -55,6 +56,83 @@ __device__ __forceinline__ double wave_sum(double v)
     s += __hiloint2double(__builtin_amdgcn_readlane(hi, 31), __builtin_amdgcn_readlane(lo, 31));
     s += __hiloint2double(__builtin_amdgcn_readlane(hi, 47), __builtin_amdgcn_readlane(lo, 47));
     s += __hiloint2double(__builtin_amdgcn_readlane(hi, 63), __builtin_amdgcn_readlane(lo, 63));
+    return s;
+}
+
+// v of the lane that the DPP control names (sfe_wave_sum_plan.h); the lanes outside `BANKS` keep `old`.  (With every bank
+// written and a control under which every lane has a source, `old` is never read: bound_ctrl says so, which spares the
+// copy of `old` into the destination.)
+template <int CTRL, int BANKS = 0xf>
+__device__ __forceinline__ double dpp_mov_f64(double old, double v)
+{
+    constexpr bool ALL = BANKS == 0xf;
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(v), CTRL, 0xf, BANKS, ALL);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(v), CTRL, 0xf, BANKS, ALL);
+    return __hiloint2double(hi, lo);
+}
+
+// a constant lane mask as a per-lane condition, set up by two scalar moves where it is used (a compare of the lane number,
+// and a literal that the compiler sees, are hoisted out of the ICP iteration loop and spilled: two v_readlane per use)
+template <unsigned long long M>
+__device__ __forceinline__ bool wsp_lane_mask()
+{
+    static_assert((unsigned)(M >> 32) == (unsigned)M, "the same word for both halves of the wave");
+    unsigned m;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(m) : "n"((unsigned)M));
+    return __builtin_amdgcn_inverse_ballot_w64(((unsigned long long)m << 32) | m);
+}
+
+// one traded register of levels 0 and 1 (a lane bit that the bank masks cannot tell apart): the lanes with `up` keep
+// `hi_slot` and add their partner's, the others `lo_slot`
+template <int CTRL>
+__device__ __forceinline__ double wsp_trade(bool up, double lo_slot, double hi_slot)
+{
+    const double keep = up ? hi_slot : lo_slot, give = up ? lo_slot : hi_slot;
+    return keep + dpp_mov_f64<CTRL>(0.0, give);
+}
+
+// The nine sums of wave_sum(a[0]) .. wave_sum(a[8]) at once, bit for bit (NaN payloads aside), by the transposed tree of
+// sfe_wave_sum_plan.h: lane l holds the total of accumulator wsp_final_slot(l & 15) -- 11 adds per lane inside the rows (8
+// for the traded accumulators, 3 for the ninth) and 3 over them instead of 63, and no per-accumulator v_readlane chain.  No address register and no LDS (see
+// dpp_row_shr_add); the whole wave must be active.
+__device__ __forceinline__ double wave_sum_n(const double (&a)[WSP_N + 1])
+{
+    static_assert(wsp_partner(0, 0) == wsp_dpp_src(WSP_DPP_QUAD_1032, 0) && wsp_partner(1, 1) == wsp_dpp_src(WSP_DPP_QUAD_2301, 1) &&
+                      wsp_partner(2, 2) == wsp_dpp_src(WSP_DPP_ROW_SHL4, 2) && wsp_partner(2, 14) == wsp_dpp_src(WSP_DPP_ROW_SHR4, 14) &&
+                      wsp_partner(3, 5) == wsp_dpp_src(WSP_DPP_ROW_ROR8, 5),
+                  "the DPP controls reach the plan's partners (all lanes: tests/host/wave_sum_plan_check.cpp)");
+    const bool up0 = wsp_lane_mask<wsp_upper_mask(0)>(), up1 = wsp_lane_mask<wsp_upper_mask(1)>();
+    double b[4], c[2];
+    // level 0: 8 -> 4
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        b[j] = wsp_trade<WSP_DPP_QUAD_1032>(up0, a[j], a[j + 4]);
+    double x = a[WSP_RIDER] + dpp_mov_f64<WSP_DPP_QUAD_1032>(0.0, a[WSP_RIDER]);
+    // level 1: 4 -> 2
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+        c[j] = wsp_trade<WSP_DPP_QUAD_2301>(up1, b[j], b[j + 2]);
+    x = x + dpp_mov_f64<WSP_DPP_QUAD_2301>(0.0, x);
+    // level 2: 2 -> 1, told apart by the banks: u = the partner's c[0] where bit 2 is clear, the own c[1] elsewhere; w the other way round
+    const double u2 = dpp_mov_f64<WSP_DPP_ROW_SHL4, WSP_BANKS_BIT2_CLEAR>(c[1], c[0]);
+    const double w2 = dpp_mov_f64<WSP_DPP_ROW_SHR4, WSP_BANKS_BIT2_SET>(c[0], c[1]);
+    const double d = u2 + w2;
+    x = x + dpp_mov_f64<WSP_DPP_ROW_HALF_MIRROR>(0.0, x);
+    // level 3: the slot against the rider
+    const double u3 = dpp_mov_f64<WSP_DPP_ROW_ROR8, WSP_BANKS_BIT3_CLEAR>(x, d);
+    const double w3 = dpp_mov_f64<WSP_DPP_ROW_ROR8, WSP_BANKS_BIT3_SET>(d, x);
+    const double e = u3 + w3;
+    // the rows: ((r0 + r1) + r2) + r3
+    const unsigned lo = (unsigned)__double2loint(e), hi = (unsigned)__double2hiint(e);
+    const auto l32 = __builtin_amdgcn_permlane32_swap(lo, lo, false, false), h32 = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    const auto l01 = __builtin_amdgcn_permlane16_swap(l32[0], l32[0], false, false),
+               h01 = __builtin_amdgcn_permlane16_swap(h32[0], h32[0], false, false),
+               l23 = __builtin_amdgcn_permlane16_swap(l32[1], l32[1], false, false),
+               h23 = __builtin_amdgcn_permlane16_swap(h32[1], h32[1], false, false);
+    double s = __hiloint2double((int)h01[0], (int)l01[0]);
+    s += __hiloint2double((int)h01[1], (int)l01[1]);
+    s += __hiloint2double((int)h23[0], (int)l23[0]);
+    s += __hiloint2double((int)h23[1], (int)l23[1]);
     return s;
 }
 

@@ -1614,12 +1614,13 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                         }
                     }
                 }
-#pragma unroll
-                for (int k = 0; k < NA; ++k) {
-                    const double sk = wave_sum(a[k]);
-                    if (lane == 0)
-                        S.red[NA * w0 + k] = sk;
-                }
+                // the nine wave totals by one transposed tree (sfe_wave_sum_plan.h; the same adds as nine wave_sum calls):
+                // every lane ends up with the total of one of them, and every lane stores its own (the lanes that hold the
+                // same total write the same bits to the same word; a predicate for nine lanes would be one more
+                // loop-invariant mask for the iteration loop to spill)
+                static_assert(NA == WSP_N + 1, "the plan's accumulators");
+                const double sk = wave_sum_n(a);
+                S.red[NA * w0 + wsp_final_slot(lane & 15)] = sk;
                 if (lane == 0)
                     S.xr[w0] = cnt; // (the exchange words of the split jobs are idle between their exchanges)
             }

@@ -1,6 +1,6 @@
 #!/bin/bash
 # ISA of the bench's build of the ICP loop kernel alone (compile only, no GPU): register / spill figures and the static
-# instruction mix; with a marker name, the region between `asm volatile("; NAME_BEGIN")` and `; NAME_END`.
+# instruction mix; the mix of the region between `asm volatile("; NAME_BEGIN")` and `; NAME_END`: tools/icp_isa_region.py out.s NAME.
 # usage: tools/icp_isa.sh [out.s] [extra hipcc flags]
 out=${1:-/tmp/icp_loop_bench.s}; shift
 cd "$(dirname "$0")/../sonar_slam_amd/csrc" || exit 1
