@@ -421,8 +421,15 @@ struct SweepShared {
 // (m and the factor on the last step's movement: tuning sw_recm / sw_reck)
 #define SW_REC_MIN_ITER 12
 
+struct __attribute__((aligned(16))) SweepSlot { // one processing slot of a job: what the fresh pass of an iteration reads
+    float rx, ry; // the slot's query under the guess, r = T0 * src (formed once per job: T0 never changes)
+    int order;    // the query's own index
+    unsigned rec; // its clearance record (0: none)
+};
+static_assert(sizeof(SweepSlot) == 16, "one 16-byte load per slot");
+
 struct SweepQ { // per-job views of the per-query scratch (the transformed query itself is never stored: whoever needs
-                // it again recomputes it from the source point, two affine maps with wave-uniform coefficients)
+                // it again recomputes it from its position under the guess, one affine map with wave-uniform coefficients)
     int4 *st;     // clearance record of a `none` query: (px, py, clearance) as float bits; .z doubles as the runner-up
                   // distance a search carries from the first pass to the second (records build)
     float *d2;    // best so far / final d2
@@ -430,10 +437,11 @@ struct SweepQ { // per-job views of the per-query scratch (the transformed query
     int *wl[2];   // work lists of suspended queries (ping-pong between rounds)
     int *mid;     // queries that outlived the first pass (compacted for the second)
     int *lng;     // queries handed to the cooperative tier this round
-    int *order;   // all queries, neighbours in space next to each other (see the sort at the kernel start)
-    int *slot_of; // ... and the inverse: position of query q in that order
-    unsigned *rec; // clearance records, by position in `order` (the fresh pass streams through them)
-    float2 *ssrc; // their source points in that order
+    SweepSlot *slot; // all queries, neighbours in space next to each other (see the sort at the kernel start): guess-frame
+                     // position, index and clearance record of each (the fresh pass streams through them)
+    int *slot_of;    // ... and the inverse: position of query q in that order
+    float2 *rsrc;    // guess-frame position r = T0 * src of query q, under its own index (per job: two jobs on one source
+                     // cloud have their own guesses)
     const int *perm;
 };
 
@@ -460,7 +468,8 @@ struct SweepLaunchArgs {
     const int *d_grid;
     int4 *d_qst;
     int *d_qwl;
-    float2 *d_qssrc;
+    float2 *d_qrsrc;
+    SweepSlot *d_qslot;
     float *d_nn_d2;
     int *d_nn_pos;
     float *d_T9;

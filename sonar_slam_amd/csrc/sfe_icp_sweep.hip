@@ -210,7 +210,7 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
     // every stream of the context before it frees its block: sfe_scratch.)
     enum { G_TABLES, G_STGT, G_PERM, G_SNRM, G_MEAN, G_GKEYS, G_TAB, G_GRID, G_N };
     static const int gen_slot[2][G_N] = {{12, 14, 15, 16, 17, 24, 23, 38}, {72, 73, 74, 75, 76, 77, 78, 79}};
-    static_assert(SFE_NSCRATCH == 80, "generation 1 takes the last eight slots");
+    static_assert(SFE_NSCRATCH == 81, "generation 1 takes slots 72..79, the loop kernel's slot records the last one");
     const int *gs = gen_slot[gen.g];
     char *d_tables = (char *)sfe_scratch(ctx, gs[G_TABLES], tab_bytes);
     float2 *d_stgt = (float2 *)sfe_scratch(ctx, gs[G_STGT], sizeof(float2) * (size_t)toff);
@@ -220,13 +220,16 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
     unsigned long long *d_gkeys =
         (unsigned long long *)sfe_scratch(ctx, gs[G_GKEYS], sizeof(unsigned long long) * (size_t)std::max(koff, 1LL));
     int4 *d_qst = (int4 *)sfe_scratch(ctx, 19, sizeof(int4) * (size_t)qoff);
-    int *d_qwl = (int *)sfe_scratch(ctx, 21, sizeof(int) * 7 * (size_t)qoff);
-    float2 *d_qssrc = (float2 *)sfe_scratch(ctx, 30, sizeof(float2) * (size_t)qoff);
+    // per query: 5 ints of work lists and the slot index, the guess-frame position under the query's own index and the
+    // 16-byte slot record (20 + 8 + 16 B; the order, record and sorted-source arrays these replace were 28 + 8 B)
+    int *d_qwl = (int *)sfe_scratch(ctx, 21, sizeof(int) * 5 * (size_t)qoff);
+    float2 *d_qrsrc = (float2 *)sfe_scratch(ctx, 30, sizeof(float2) * (size_t)qoff);
+    SweepSlot *d_qslot = (SweepSlot *)sfe_scratch(ctx, 80, sizeof(SweepSlot) * (size_t)qoff);
     StripTab *d_tab = (StripTab *)sfe_scratch(ctx, gs[G_TAB], sizeof(StripTab) * (size_t)n_prep);
     int *d_grid = (int *)sfe_scratch(ctx, gs[G_GRID], sizeof(int) * (size_t)goff);
     float *d_nn_d2 = (float *)sfe_scratch(ctx, 5, sizeof(float) * (size_t)qoff);
     int *d_nn_pos = (int *)sfe_scratch(ctx, 6, sizeof(int) * (size_t)qoff);
-    if (!d_tables || !d_stgt || !d_perm || (p->minimizer == 1 && !d_snrm) || !d_mean || !d_gkeys || !d_qst || !d_qwl || !d_qssrc || !d_tab || !d_grid ||
+    if (!d_tables || !d_stgt || !d_perm || (p->minimizer == 1 && !d_snrm) || !d_mean || !d_gkeys || !d_qst || !d_qwl || !d_qrsrc || !d_qslot || !d_tab || !d_grid ||
         !d_nn_d2 || !d_nn_pos)
         return SFE_ERR_HIP;
     // split jobs: the gathered source clouds of the shares and the sync areas (one generation: a preparation that
@@ -365,7 +368,8 @@ int sfe_icp_sweep_launch(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
     a.d_grid = d_grid;
     a.d_qst = d_qst;
     a.d_qwl = d_qwl;
-    a.d_qssrc = d_qssrc;
+    a.d_qrsrc = d_qrsrc;
+    a.d_qslot = d_qslot;
     a.d_nn_d2 = d_nn_d2;
     a.d_nn_pos = d_nn_pos;
     a.d_T9 = d_T9;

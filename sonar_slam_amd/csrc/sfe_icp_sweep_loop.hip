@@ -57,8 +57,8 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     sfe_icp_params P, const SweepJob *__restrict__ jobs, const int *__restrict__ job_ids, const float2 *__restrict__ src_all,
     const float *__restrict__ guess_all, const float2 *__restrict__ stgt_all, const int *__restrict__ perm_all,
     const float2 *__restrict__ snrm_all, const float *__restrict__ mean_all, const StripTab *__restrict__ tab_all,
-    const int *__restrict__ grid_all, int4 *__restrict__ q_st_all, int *__restrict__ q_wl_all, float2 *__restrict__ q_ssrc_all,
-    float *__restrict__ nn_d2_all,
+    const int *__restrict__ grid_all, int4 *__restrict__ q_st_all, int *__restrict__ q_wl_all, float2 *__restrict__ q_rsrc_all,
+    SweepSlot *__restrict__ q_slot_all, float *__restrict__ nn_d2_all,
     int *__restrict__ nn_pos_all, float *__restrict__ T_out, int *__restrict__ status_out,
     int *__restrict__ iters_out, long long *prof, int *dbg, int sw_budget, int sw_budget_a, int sw_cache, int t_cap, int q_cap, int sort_chunk, float sw_m, float sw_kappa,
     unsigned long long *__restrict__ sync_all, int sw_cache2, sfe_icp_outliers O_arg)
@@ -123,14 +123,13 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
             Q.pos[i] = pz;
         }
     };
-    Q.wl[0] = q_wl_all + 7 * J.q_off;
+    Q.wl[0] = q_wl_all + 5 * J.q_off;
     Q.wl[1] = Q.wl[0] + ns;
     Q.mid = Q.wl[1] + ns;
     Q.lng = Q.mid + ns;
-    Q.order = Q.lng + ns;
-    Q.slot_of = Q.order + ns;
-    Q.rec = reinterpret_cast<unsigned *>(Q.slot_of + ns);
-    Q.ssrc = q_ssrc_all + J.q_off;
+    Q.slot_of = Q.lng + ns;
+    Q.slot = q_slot_all + J.q_off;
+    Q.rsrc = q_rsrc_all + J.q_off;
     Q.perm = perm_all + J.tgt_off;
     const float *guess = guess_all + 9 * (size_t)J.out;
     const int tid = threadIdx.x, lane = threadIdx.x & 63;
@@ -158,8 +157,9 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     }
 
     // ---- T0 = T_refIn_refMean^-1 * guess ; T_iter = I ----
-    float T0[9];
-    {
+    // T0 is formed twice, by the same operations: for the sort below, which leaves every query's r = T0 * src in scratch
+    // (the iterations only read r), and by thread 0 for the final composition -- not held across the iteration loop.
+    auto make_T0 = [&](float (&T0)[9]) {
         const float Tinv[9] = {1, 0, -mx, 0, 1, -my, 0, 0, 1};
         float g[9];
 #pragma unroll
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
 #pragma unroll
         for (int i = 0; i < 9; ++i)
             T0[i] = sw_uniform(T0[i]);
-    }
+    };
     __syncthreads(); // strip table in place
 
     // ---- split jobs: what the shares of a job tell each other ----
@@ -263,8 +263,11 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     // original order.  Sorted once per job, in the LDS that will hold the target (chunks of 8192): the queries of a
     // chunk are counted per strip, then strip_sort_lds scatters their keys into the strips' segments and sorts every
     // segment inside one wave (the full bitonic network only if a strip holds more than SW_SEG_MAX queries).  The
-    // position under the guess is formed twice -- two affine maps -- rather than kept in registers in between. ----
+    // position under the guess is formed three times -- count, key, slot record: two affine maps each -- rather than kept
+    // in registers in between; the third leaves it in the slot record and in Q.rsrc for all the iterations. ----
     {
+        float T0[9];
+        make_T0(T0);
         unsigned long long *skeys = reinterpret_cast<unsigned long long *>(lds_tgt);
         float rloc = 0.0f; // largest |T0 * src| among this thread's queries (for the movement bounds of the clearance records)
         int *scnt = reinterpret_cast<int *>(S.hist); // queries per strip (the histograms of the radix select are idle here,
@@ -294,10 +297,15 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
             });
             for (int i = tid; i < n; i += NT) {
                 const int q = SW_KEY_ID(skeys[i]);
-                Q.order[c0 + i] = q;
-                Q.ssrc[c0 + i] = src[q];
+                const float2 r = qpos(q);
+                SweepSlot sl;
+                sl.rx = r.x;
+                sl.ry = r.y;
+                sl.order = q;
+                sl.rec = 0u; // no clearance record yet
+                Q.slot[c0 + i] = sl;
+                Q.rsrc[q] = r;
                 Q.slot_of[q] = c0 + i;
-                Q.rec[c0 + i] = 0u; // no clearance record yet
             }
             __syncthreads();
         }
@@ -367,11 +375,10 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
     const bool sw_jump = (sw_cache & 2) != 0;
     const float sw_margin = sw_uniform(1.0f + 0.01f * (float)((sw_cache >> 16) & 255));
     int wd_outer = 0;
-    // cur = Ti * (T0 * src): the same two roundings wherever a query is (re)computed
-    auto xform = [&](const float (&Ti)[9], float2 sp) {
-        const float rx = affine1(T0[0], T0[1], T0[2], sp.x, sp.y);
-        const float ry = affine1(T0[3], T0[4], T0[5], sp.x, sp.y);
-        return make_float2(affine1(Ti[0], Ti[1], Ti[2], rx, ry), affine1(Ti[3], Ti[4], Ti[5], rx, ry));
+    // cur = Ti * r, r = T0 * src as the sort left it (a float stored and read back: the bits it had when it was
+    // recomputed at every use, NaN and -0 included): the same two roundings wherever a query is (re)computed
+    auto xform = [&](const float (&Ti)[9], float2 r) {
+        return make_float2(affine1(Ti[0], Ti[1], Ti[2], r.x, r.y), affine1(Ti[3], Ti[4], Ti[5], r.x, r.y));
     };
     bool use_cache = false; // from the second iteration on: Q.pos / Q.st hold the previous iteration's results
     const bool sw_rec = REC && (sw_cache & 16) != 0; // clearance records (0: A/B without them)
@@ -610,28 +617,24 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 // early do not sit idle through the long searches of their neighbours.  What exhausts the
                 // second budget too goes to tier 2. --
                 auto walk_pass = [&](const int *list, int n, bool fresh, int budget, bool last) {
-                float2 sp_next = make_float2(0, 0); // fresh pass: the next slice's source point is fetched a slice ahead
-                int q_next = 0;                     // ... and so is its index
-                if (fresh && tid < n) {
-                    sp_next = Q.ssrc[tid];
-                    q_next = Q.order[tid];
-                }
+                // fresh pass: the next slice's slot record (guess-frame position, index, clearance record) is fetched a
+                // slice ahead, one 16-byte load
+                SweepSlot sl_next = {0.0f, 0.0f, 0, 0u};
+                if (fresh && tid < n)
+                    sl_next = Q.slot[tid];
                 const float sC = f_mul(sqrtf(C), 1.00001f); // (the cap of this round as a radius, for the records)
                 for (int k0 = 0; k0 < n; k0 += NT) {
                     const int slot = k0 + tid;
                     const bool valid = slot < n;
-                    const float2 sp_cur = sp_next;
-                    const int q_cur = q_next;
+                    const float2 sp_cur = make_float2(sl_next.rx, sl_next.ry);
+                    const int q_cur = sl_next.order;
                     int prev = 0;
-                    // clearance record of the query (0: none); fetched here, not a slice ahead like the source point:
-                    // measured, the register that would carry it costs more than the latency of this coalesced read
-                    const unsigned rec = (fresh && rec_use && valid) ? Q.rec[slot] : 0u;
+                    // clearance record of the query (0: none): the last word of its slot record
+                    const unsigned rec = (fresh && rec_use && valid) ? sl_next.rec : 0u;
                     if (fresh && use_cache && valid)
                         prev = Pz(q_cur); // last iteration's result of this query (used after the transform)
-                    if (fresh && slot + NT < n) {
-                        sp_next = Q.ssrc[slot + NT];
-                        q_next = Q.order[slot + NT];
-                    }
+                    if (fresh && slot + NT < n)
+                        sl_next = Q.slot[slot + NT];
                     int q = 0, bpos = 0;
                     float px = 0, py = 0, best = W2;
                     float second = INFINITY; // smallest distance met so far to a target other than the (then) best one
@@ -647,7 +650,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                             q = (int)(e & SW_QMASK);
                             own_done = (e & SW_OWN_DONE) != 0;
                             tied = (e & SW_TIED) != 0;
-                            const float2 p = xform(Ti, src[q]);
+                            const float2 p = xform(Ti, Q.rsrc[q]);
                             px = p.x;
                             py = p.y;
                             bpos = -2 - Pz(q);
@@ -970,11 +973,11 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                             if (!(R > 0.0f))
                                 r = 0u;
                         }
-                        Q.rec[fresh ? slot : Q.slot_of[q]] = r;
+                        Q.slot[fresh ? slot : Q.slot_of[q]].rec = r;
                     }
                     if (rec_on && is_long) { // the next tier continues from what this one has seen; no record meanwhile
                         Q.st[q].z = __float_as_int(second);
-                        Q.rec[fresh ? slot : Q.slot_of[q]] = 0u;
+                        Q.slot[fresh ? slot : Q.slot_of[q]].rec = 0u;
                     }
                     tally_settled(is_none, is_exact, best);
                     if (__ballot(grid_hit || grid_defer) && lane == 0)
@@ -1014,30 +1017,22 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 auto triage_pass = [&]() {
                     const float sC = f_mul(sqrtf(C), 1.00001f);
                     int *wl_next = Q.wl[cur ^ 1];
-                    // (query index, source point, record) of the next slice are requested a slice ahead: three words from HBM
-                    // scratch whose latency would otherwise stand in front of every slice
-                    int q_n = 0;
-                    float2 sp_n = make_float2(0, 0);
-                    unsigned rec_n = 0u;
-                    if (tid < ns) {
-                        q_n = Q.order[tid];
-                        sp_n = Q.ssrc[tid];
-                        rec_n = Q.rec[tid];
-                    }
+                    // the slot record of the next slice (guess-frame position, query index, record) is requested a slice
+                    // ahead: one 16-byte load from HBM scratch whose latency would otherwise stand in front of every slice
+                    SweepSlot sl_n = {0.0f, 0.0f, 0, 0u};
+                    if (tid < ns)
+                        sl_n = Q.slot[tid];
                     for (int k0 = 0; k0 < ns; k0 += NT) {
                         const int slot = k0 + tid;
                         const bool valid = slot < ns;
                         int q = 0, bpos = 0;
                         float px = 0, py = 0, best = W2;
                         bool skip = false, rec_hit = false;
-                        const int q_c = q_n;
-                        const float2 sp = sp_n;
-                        const unsigned rec = rec_n;
-                        if (slot + NT < ns) {
-                            q_n = Q.order[slot + NT];
-                            sp_n = Q.ssrc[slot + NT];
-                            rec_n = Q.rec[slot + NT];
-                        }
+                        const int q_c = sl_n.order;
+                        const float2 sp = make_float2(sl_n.rx, sl_n.ry);
+                        const unsigned rec = sl_n.rec;
+                        if (slot + NT < ns)
+                            sl_n = Q.slot[slot + NT];
                         if (valid) {
                             q = q_c;
                             const int prev = Pz(q);
@@ -1091,7 +1086,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                             setQ(q, best, SW_INEXACT_OF(bpos));
                         if (is_long) { // (nothing visited yet: no runner-up, no record meanwhile)
                             Q.st[q].z = __float_as_int(INFINITY);
-                            Q.rec[slot] = 0u;
+                            Q.slot[slot].rec = 0u;
                         }
                         tally_settled(is_none, is_exact, best, !predict);
                         const unsigned long long ms = __ballot(is_susp), ml = __ballot(is_long);
@@ -1160,7 +1155,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                     float bn = 0;
                     auto fetch = [&](int sl) {
                         qn = (int)((unsigned)Q.lng[sl] & SW_QMASK);
-                        pn = src[qn];
+                        pn = Q.rsrc[qn];
                         bn = Dz(qn);
                         posn = Pz(qn);
                     };
@@ -1577,7 +1572,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                         const int i = base + lane;
                         int id;
                         if (kept(i, i < ns, id, cnt)) {
-                            const float2 p = xform(Ti, src[i]);
+                            const float2 p = xform(Ti, Q.rsrc[i]);
                             const float2 q = T[id + 1];
                             const double px = p.x, py = p.y, qx = q.x, qy = q.y;
                             a[0] += px;
@@ -1595,7 +1590,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                         const int i = base + lane;
                         int id;
                         if (kept(i, i < ns, id, cnt)) {
-                            const float2 sp = src[i]; // (both requests leave before either answer is waited for)
+                            const float2 sp = Q.rsrc[i]; // (both requests leave before either answer is waited for)
                             const float2 n = snrm[id];
                             const float2 q = T[id + 1];
                             const float2 p = xform(Ti, sp);
@@ -1674,9 +1669,10 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
         float *To = T_out + 9 * (size_t)J.out;
         if (status == SFE_ICP_OK) {
             const float Tfwd[9] = {1, 0, mx, 0, 1, my, 0, 0, 1};
-            float Ti[9], tmp[9], res[9];
+            float Ti[9], T0[9], tmp[9], res[9];
             for (int i = 0; i < 9; ++i)
                 Ti[i] = S.Ti[i];
+            make_T0(T0); // (as the sort formed it: the same operations on the same words)
             mat3_mul(Ti, T0, tmp);
             mat3_mul(Tfwd, tmp, res);
             for (int i = 0; i < 9; ++i)
@@ -1826,8 +1822,8 @@ int sweep_launch_loop(const SweepLaunchArgs &a, int n, const int *d_ids, size_t 
     const size_t smem = sweep_ctl_bytes<NT, PROF, REC>() + body;
     SFE_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     hipLaunchKernelGGL(kernel, dim3(n), dim3(NT), smem, ctx->stream, *a.p, a.d_jobs, d_ids, a.d_src, a.d_guess9, a.d_stgt,
-                       a.d_perm, a.d_snrm, a.d_mean, a.d_tab, a.d_grid, a.d_qst, a.d_qwl, a.d_qssrc, a.d_nn_d2, a.d_nn_pos,
-                       a.d_T9, a.d_status, a.d_iters, a.d_prof, a.d_dbg, a.sw_budget, a.sw_budget_a, a.sw_cache, t_cap, q_cap,
+                       a.d_perm, a.d_snrm, a.d_mean, a.d_tab, a.d_grid, a.d_qst, a.d_qwl, a.d_qrsrc, a.d_qslot, a.d_nn_d2,
+                       a.d_nn_pos, a.d_T9, a.d_status, a.d_iters, a.d_prof, a.d_dbg, a.sw_budget, a.sw_budget_a, a.sw_cache, t_cap, q_cap,
                        pow2_floor(body / 8), a.sw_m, a.sw_kappa, a.d_sync, a.sw_cache2, ox);
     SFE_LAUNCH_CHECK(ctx);
     return 0;

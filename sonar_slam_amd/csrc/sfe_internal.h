@@ -10,7 +10,7 @@
 #include "../../include/sonarfe.h"
 #include "sfe_icp_gen.h"
 
-#define SFE_NSCRATCH 80 // (0..71: the numbers and the CF_SLOT_* / DPF_SLOT_* names in the .hip files; 72..79: sfe_icp_sweep.hip)
+#define SFE_NSCRATCH 81 // (0..71: the numbers and the CF_SLOT_* / DPF_SLOT_* names in the .hip files; 72..80: sfe_icp_sweep.hip)
 #define SFE_ICP_PROF_N 96 // values sfe_icp_get_profile hands back
 
 // Launcher knobs of one context, set by name with sfe_tune (the name -> field / range table is in sfe_ctx.hip).  The
