@@ -37,6 +37,7 @@
 // (tiers) -> census -> trimmed quantile by exact radix select -> fp64 reduction of the 9(+1) sums ->
 // closed-form solve and checkers on one lane.
 #include "sfe_icp_common.h"
+#include "sfe_icp_sweep_plan.h" // the sizes, the job tiers, SweepPrep / SweepJob, the lists of builds
 
 #include <algorithm>
 #include <cstdlib>
@@ -44,24 +45,6 @@
 #include <map>
 #include <type_traits>
 #include <utility>
-
-#define SW_TCAP 8192   // target points resident in LDS
-#define SW_NS_MAX 64   // strips per target
-#define SW_PAD (SW_NS_MAX + 4) // sentinels: one in front, one behind every strip, two spare behind the last
-#define SW_GRID_MAX 8192 // most cells a target's witness grid can have (built in the prep kernel's LDS: 4 B per cell)
-// Job tiers (the scan matches bruce_slam itself produces are 10^2..10^3 points, slam.py:769,1032): the
-// same kernels instantiated for one-wave and four-wave workgroups, several jobs per CU, chosen by the launcher from
-// n_src / n_tgt.  {threads, target capacity of the prep kernel's LDS, witness-grid cells}
-#define SW_T0_NT 64
-#define SW_T0_TCAP 512
-#define SW_T0_GRID 512
-#define SW_T1_NT 256
-#define SW_T1_TCAP 2048
-#define SW_T1_GRID 2048
-// Many-to-one batches on large clouds (BASELINE configs[4]: 30 guesses x one 20 000 x 20 000 pair, slam.py:346-358): a
-// job is split over up to SW_MG_MAX workgroups (queries by strip band), which meet in a per-job sync area
-#define SW_MG_MAX 16
-#define SW_MG_WORDS 272 // 32-bit words one exchange can carry (a 256-bin histogram + scalars)
 
 // Strip table of one target (built by the prep kernel, read by every job on that target).
 // Sorted-cloud layout (float2 positions): [0] NaN, then for every strip s its points ascending in x
@@ -83,22 +66,6 @@ struct StripTab {
     int sbeg[SW_NS_MAX + 1];
     float smin[SW_NS_MAX];    // smallest y of any point in strips >= s (+inf if none)
     float smax[SW_NS_MAX];    // largest y of any point in strips <= s (-inf if none)
-};
-
-struct SweepPrep {
-    int tgt_start, n_tgt, ns, pad_;
-    long long off;     // offset (points) of this target's slice of the sorted-cloud scratch (stride n_tgt + SW_PAD)
-    long long key_off; // targets beyond the LDS capacity: offset of their sort keys in HBM scratch
-    long long grid_off; // offset (ints, a multiple of 64) of its witness grid
-};
-
-struct SweepJob {
-    int src_start, n_src, n_tgt, prep;
-    long long tgt_off; // = SweepPrep.off of its target
-    long long q_off;   // offset (points) of this job's slice of the per-query scratch
-    int out;           // index of the caller's job (guess, T_out, status, iterations) this record works for
-    int grp, ngrp;     // split jobs: this record is share `grp` of `ngrp` (1: the whole job)
-    int sync;          // ... and their sync area is number `sync`
 };
 
 // order-preserving map float -> uint32 (NaN of either sign sorts last)
@@ -418,8 +385,7 @@ struct SweepShared {
 // the clouds have converged (a few mm per iteration against neighbour distances of centimetres) almost every query
 // takes this path: the iteration costs a transform, one distance and the census.  Decisions and results are those of
 // the full search: the skip needs a strict gap (1e-5 relative, two orders above the fp32 rounding of the distances).
-// (m and the factor on the last step's movement: tuning sw_recm / sw_reck)
-#define SW_REC_MIN_ITER 12
+// (m and the factor on the last step's movement: tuning sw_recm / sw_reck; the chains that take them: SW_REC_MIN_ITER)
 
 struct __attribute__((aligned(16))) SweepSlot { // one processing slot of a job: what the fresh pass of an iteration reads
     float rx, ry; // the slot's query under the guess, r = T0 * src (formed once per job: T0 never changes)
@@ -512,7 +478,3 @@ int sweep_launch_tiny(sfe_ctx *ctx, const sfe_icp_params *p, int n, const SweepJ
                       const float2 *d_src, const float2 *d_tgt, const float *d_guess9, const int *d_perm, const float2 *d_snrm,
                       const float *d_mean, const StripTab *d_tab, float *d_T9, int32_t *d_status, int32_t *d_iters, int tiny_tmax,
                       int tiny_smax, const sfe_icp_outliers &ox);
-// limits of the one-wave kernel the host side sorts jobs by (sfe_icp_tiny.h)
-#define SW_TINY_MAX 512        // most points of either cloud
-#define SW_TINY_PAIRS_SHORT 400000
-#define SW_TINY_PAIRS_LONG 120000

@@ -1829,30 +1829,9 @@ int sweep_launch_loop(const SweepLaunchArgs &a, int n, const int *d_ids, size_t 
     return 0;
 }
 
-// the builds the host side asks for: {threads, min waves per EU (the VGPR budget), target in LDS, results in LDS, counted
-// profile, clearance records, job shared by several workgroups}
+// the builds the host side asks for: SW_LOOP_BUILDS (sfe_icp_sweep_plan.h)
 #define SW_LOOP_INST(...) template int sweep_launch_loop<__VA_ARGS__>(const SweepLaunchArgs &, int, const int *, size_t, int, int);
-#ifdef SW_INSPECT // (tools/icp_isa.sh: the bench's build alone, for a look at its ISA)
-SW_LOOP_INST(ICP_THREADS, 8, true, true, false, true, false)
-#else
-SW_LOOP_INST(SW_T0_NT, 4, true, true, false, true, false)
-SW_LOOP_INST(SW_T0_NT, 4, true, true, false, false, false)
-SW_LOOP_INST(SW_T1_NT, 4, true, true, true, false, false)
-SW_LOOP_INST(SW_T1_NT, 4, true, true, false, true, false)
-SW_LOOP_INST(SW_T1_NT, 4, true, true, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 4, true, true, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, true, true, true, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, true, true, false, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, true, false, true, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, true, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 4, true, false, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, false, true, false, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, false, false, true, false)
-SW_LOOP_INST(ICP_THREADS, 8, true, false, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 4, false, false, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 8, false, false, false, false, false)
-SW_LOOP_INST(ICP_THREADS, 4, false, false, false, false, true)
-#endif
+SW_LOOP_BUILDS(SW_LOOP_INST)
 
 int sweep_launch_split(sfe_ctx *ctx, hipStream_t ps, int n_split, SweepJob *d_jobs, const int *d_split, const float2 *d_src,
                        const float *d_guess9, const float *d_mean, const StripTab *d_tab, float2 *d_gsrc)

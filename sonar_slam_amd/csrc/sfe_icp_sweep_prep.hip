@@ -789,17 +789,12 @@ int sweep_launch_prep(sfe_ctx *ctx, hipStream_t ps, const sfe_icp_params *p, int
     return 0;
 }
 
-// the builds the host side asks for (sfe_icp_sweep.hip: job classes t0 / t1 / 1024 threads; the 1024-thread kernel with its
-// witness grid in LDS of its own, or inside the key buffer at neighbour-list capacities 8 / 10)
+// the builds the host side asks for: SW_PREP_BUILDS (sfe_icp_sweep_plan.h)
 #define SW_PREP_INST(NT, TCAP, GM, GTAIL, KMF)                                                                                   \
     template int sweep_launch_prep<NT, TCAP, GM, GTAIL, KMF>(sfe_ctx *, hipStream_t, const sfe_icp_params *, int, const SweepPrep *, \
                                                              const int *, const float2 *, float2 *, int *, float2 *, float *,     \
                                                              unsigned long long *, StripTab *, int *);
-SW_PREP_INST(SW_T0_NT, SW_T0_TCAP, SW_T0_GRID, false, 0)
-SW_PREP_INST(SW_T1_NT, SW_T1_TCAP, SW_T1_GRID, false, 0)
-SW_PREP_INST(ICP_THREADS, SW_TCAP, SW_GRID_MAX, false, 0)
-SW_PREP_INST(ICP_THREADS, SW_TCAP, SW_GRID_MAX, true, 8)
-SW_PREP_INST(ICP_THREADS, SW_TCAP, SW_GRID_MAX, true, 10)
+SW_PREP_BUILDS(SW_PREP_INST)
 
 int sweep_launch_normals(sfe_ctx *ctx, hipStream_t ps, const sfe_icp_params *p, int n, int per, const SweepPrep *d_preps,
                          const int *d_pids, const float2 *d_stgt, const int *d_perm, float2 *d_snrm, const StripTab *d_tab)
