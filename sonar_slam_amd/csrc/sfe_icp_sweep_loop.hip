@@ -606,7 +606,6 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                     predict = triage && (sw_cache & (1 << 25)) != 0 && (sw_cache & (1 << 26)) != 0 && P.use_trimmed_filter &&
                               limit_prev < INFINITY && limit_prev > 0.0f;
                 }
-                const bool rec_use = rec_on && rec_epoch < it;
                 const int *wl = Q.wl[cur];
                 int *wl_next = Q.wl[cur ^ 1];
                 // -- tier 1: one lane per query.  The first pass (fresh queries only) transforms the query,
@@ -616,7 +615,17 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                 // all strips in lockstep rounds (pick a strip -> lower bound -> walk), so lanes that finished
                 // early do not sit idle through the long searches of their neighbours.  What exhausts the
                 // second budget too goes to tier 2. --
-                auto walk_pass = [&](const int *list, int n, bool fresh, int budget, bool last) {
+                // The pass exists twice: `rec_mode` carries this iteration's rec_on as a constant, and everything in the pass
+                // that depends on it -- the margin of the stop bound, the runner-up `second`, the record written at the end,
+                // SW_PARTIAL, the union scan -- follows the constant, not the run-time flag.  Until the records switch on
+                // (the first ~10 iterations of a bench job, where the lane-per-query walks are) a walk then carries no
+                // runner-up, compares no cursor with bpos for it and computes no margin: a third of the trip loop's vector
+                // instructions.  Both instances are inlined at every call: as a function the pass would keep its whole
+                // search state in scratch.
+                auto walk_pass_as = [&](auto rec_mode, const int *list, int n, bool fresh, int budget, bool last)
+                                        __attribute__((always_inline)) {
+                constexpr bool rec_on = decltype(rec_mode)::value; // (hides the run-time flag within the pass)
+                const bool rec_use = rec_on && rec_epoch < it;
                 // fresh pass: the next slice's slot record (guess-frame position, index, clearance record) is fetched a
                 // slice ahead, one 16-byte load
                 SweepSlot sl_next = {0.0f, 0.0f, 0, 0u};
@@ -655,7 +664,7 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                             py = p.y;
                             bpos = -2 - Pz(q);
                             best = Dz(q);
-                            if (e & SW_PARTIAL) // handed on by the first pass: what it had seen
+                            if (rec_on && (e & SW_PARTIAL)) // handed on by the first pass: what it had seen
                                 second = __int_as_float(Q.st[q].z);
                         }
                     }
@@ -1008,6 +1017,17 @@ __global__ __launch_bounds__(NT, MINW) __attribute__((amdgpu_waves_per_eu(MINW, 
                         }
                     }
                 }
+                };
+                // rec_on is the same for the whole workgroup (decided from LDS words and wave-uniform values): one scalar
+                // branch per call.  A build without records holds the instance without them only.
+                auto walk_pass = [&](const int *list, int n, bool fresh, int budget, bool last) __attribute__((always_inline)) {
+                    if constexpr (REC) {
+                        if (__builtin_amdgcn_readfirstlane((int)rec_on)) {
+                            walk_pass_as(std::true_type{}, list, n, fresh, budget, last);
+                            return;
+                        }
+                    }
+                    walk_pass_as(std::false_type{}, list, n, fresh, budget, last);
                 };
                 // The fresh pass of an iteration in triage mode (most queries are settled by their clearance records): the same
                 // decisions as walk_pass(fresh) takes when it does not search -- transform, witness, record / clearance

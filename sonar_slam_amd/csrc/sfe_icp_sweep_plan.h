@@ -441,7 +441,10 @@ static inline void sweep_plan(const SweepPlanIn &in, SweepPlan &pl)
     // launch: p2plane30 8.78-8.87 -> 8.64-8.76 ms, shipped chain 4.07 -> 3.93-4.00 ms per 1024 jobs.
     pl.sw_cache2 = in.sw_union_iters | (in.sw_union_max << 8);
     // The build with clearance records carries more per-lane state (the 64-VGPR budget makes every register count:
-    // the same chain runs ~10 % slower in it until the records start to hit), so it only takes chains that are set to
+    // the same chain ran ~10 % slower in it until the records start to hit; since the walks of the iterations before
+    // that are an instance of their own without the records' bookkeeping, a 12-iteration chain on the bench's pairs,
+    // whose records hit from iteration 9 on, takes 15.55 ms per 4096 jobs in it and 16.30 ms in the build without --
+    // it was 16.48 against 16.29, profiles/icp_walk_modes_times.txt), so it only takes chains that are set to
     // run many iterations: a fixed count (no differential checker) of at least SW_REC_MIN_ITER -- and only the builds
     // with LDS-resident targets: for the one-workgroup-per-CU builds with the target in HBM (30 guesses x one
     // 20 000 x 20 000 pair) the records cost more than they save (24.6 -> 30.9 ms, tools/hires_times.py).

@@ -1,7 +1,8 @@
 #!/bin/bash
 # ISA of the bench's build of the ICP loop kernel alone (compile only, no GPU): register / spill figures and the static
 # instruction mix; the mix of the region between `asm volatile("; NAME_BEGIN")` and `; NAME_END`: tools/icp_isa_region.py out.s NAME;
-# the counts by loop depth: tools/icp_isa_depth.py out.s [depth] [which kernel of the file].
+# the counts by loop depth: tools/icp_isa_depth.py out.s [depth] [which kernel of the file]; the innermost loops that come
+# from a range of source lines, by call site (build with -gline-tables-only): tools/icp_isa_loops.py out.s LO-HI.
 # usage: tools/icp_isa.sh [out.s] [extra hipcc flags]
 out=${1:-/tmp/icp_loop_bench.s}; shift
 cd "$(dirname "$0")/../sonar_slam_amd/csrc" || exit 1
