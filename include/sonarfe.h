@@ -355,7 +355,7 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
 #define SFE_DPF_MAX_STAGES 8 /* stages per side of a chain */
 typedef struct sfe_icp_dpf {
     int kind;          /* SFE_DPF_* */
-    int dim;           /* MAX_DIST / MIN_DIST: -1 (norm), 0 (x), 1 (y) */
+    int dim;           /* MAX_DIST / MIN_DIST: -1 (norm), 0 (x), 1 (y); the 3-D entry points (sfe_icp3_*) also take 2 (z) */
     int remove_inside; /* BOUNDING_BOX */
     float f[6];        /* the stage's thresholds, see above */
 } sfe_icp_dpf;
@@ -415,6 +415,54 @@ int sfe_icp_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const 
                                    const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src,
                                    int n_src_pts, const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses9,
                                    int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
+/* ---- the same chains on N x 3 clouds (a chain written for 3-D: icp_config.IcpChain with dims = 3) ----
+ * Restated from libpointmatcher's published behaviour (parity unpinned, like the 2-D chain); each rule is the 2-D one with
+ * one more coordinate.  Data-point stages are sfe_icp_dpf with the SFE_DPF_* kinds; a stage keeps a point (x, y, z) when
+ *   SFE_DPF_MAX_DIST     dim -1: sqrtf(fl(fl(fl(x x) + fl(y y)) + fl(z z))) < |f[0]|; dim 0 / 1 / 2: x / y / z < f[0]
+ *   SFE_DPF_MIN_DIST     dim -1: the same norm > |f[0]|; dim 0 / 1 / 2: |x| / |y| / |z| > |f[0]|
+ *   SFE_DPF_BOUNDING_BOX (xMin < x < xMax && yMin < y < yMax && zMin < z < zMax) != remove_inside, f = xMin xMax yMin yMax
+ *                        zMin zMax (all six are used)
+ *   SFE_DPF_OCTREE_GRID  exactly sfe_downsample3(cloud, f[0]): the 8-way tree with its key and medoid rules and its leaf
+ *                        order, bit for bit; the tree is cut at 21 levels like sfe_downsample3's, so no cloud is refused and
+ *                        SFE_ICP_DPF_DEPTH never occurs in 3-D
+ * Every product / sum is rounded to float, sqrtf is correctly rounded, the comparisons are strict: a NaN coordinate fails
+ * them.  Kept points keep their order.  A cloud with z = 0 under a MAX_DIST / MIN_DIST stage with dim <= 1 keeps exactly
+ * the points the 2-D stage keeps of its (x, y) columns.
+ *
+ * sfe_icp3_filter_clouds_dev runs n_stages stages in order over n_clouds device-resident clouds of packed float triples,
+ * cloud c = d_pts[off[c] .. off[c+1]) (off: host, n_clouds + 1 entries, in points, each cloud <= 2^28 points).  The
+ * survivors go to d_out back to back (cloud c after the survivors of clouds 0 .. c-1; d_out holds off[n_clouds] points
+ * and does not overlap d_pts), their number to counts_out[c] (host).  Consecutive predicate stages are one pass; an
+ * octree stage is one launch per step for all clouds.  One stream synchronisation, for the counts.  SFE_ERR_ARG before any
+ * launch: a stage with dim > 2 or < -1, an octree size that is not finite and > 0, an unknown kind, more than
+ * SFE_DPF_MAX_STAGES stages. */
+int sfe_icp3_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_stages, const float *d_pts,
+                               const int64_t *off, int n_clouds, float *d_out, int32_t *counts_out);
+/* sfe_icp3_compute_jobs with a whole chain.  The reading stages run once on every distinct source slice of the call, the
+ * reference stages once on every distinct target slice, each in the cloud's own frame before any guess is applied; ICP
+ * then runs on the filtered clouds: the reference mean is the filtered target's, whether the LDS tile is resident or
+ * streamed is decided by the filtered target's size, and with minimizer == 2 the normals are taken once per distinct
+ * filtered target.  A job whose filtered reading or reference is empty reports SFE_ICP_DPF_EMPTY with T = the guess and 0
+ * iterations; the other jobs are unaffected.
+ * The modules of sfe_icp_outliers run inside the loop, on the matcher's float d2 of sfe_icp3_compute_jobs:
+ *   MinDist     d2 >= fl(minDist minDist)
+ *   MedianDist  d2 <= fl(factor x median), median = the (unsigned)(n x 0.5f)-th smallest (0-based) of the n finite d2;
+ *               none finite: SFE_ICP_NO_OUTLIER
+ * A pair is kept only if every listed filter, MaxDist and Trimmed included, keeps it; no pair kept: SFE_ICP_NO_POINT.
+ * BoundTransformationChecker runs on the accumulated T_iter (reference-mean frame, identity at the start), in fp64 from the
+ * float entries like the 3-D Differential checker: the rotation is 2 atan2(|vec q|, |w|) of the rotation block's
+ * quaternion against the identity's (Eigen's branch rule), the translation sqrt((tx tx + ty ty) + tz tz); out of bounds
+ * when the rotation > (double)max_rotation_norm or the translation > (double)max_translation_norm (a NaN never is).  The
+ * job then reports SFE_ICP_BOUND with T = the guess.  Its place among the checkers is the 2-D rule: Bound is skipped on
+ * the iteration at which a Counter listed before it reaches its limit (bound_order bit 0), and a Differential NaN status
+ * wins over Bound's only when the Differential checker is listed first (bit 1).
+ * With o == NULL (or all zero) and no stages the call is sfe_icp3_compute_jobs, bit for bit; a chain without the modules
+ * of sfe_icp_outliers runs the kernel of sfe_icp3_compute_jobs.  SFE_ERR_ARG before any launch: what
+ * sfe_icp3_filter_clouds_dev refuses in a stage list, and the outlier settings the 2-D *_chain_ext calls refuse. */
+int sfe_icp3_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd,
+                                    int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts,
+                                    const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs,
+                                    float *T_out16, int32_t *status, int32_t *iters);
 /* A-B knob for the ICP kernels.  bit 2: 0 = strip-sweep exact NN search (default; targets beyond 8192
  * points are walked through L2 instead of LDS), 1 = brute-force tile scan for everything.
  * Brute-force only: bit 0: 0 = packed fp32 NN loop, 1 = scalar fp32; bit 1: 0 = 64-VGPR build,
@@ -703,6 +751,11 @@ int sfe_cloud_store3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t
  * refused with SFE_ERR_ARG before any launch. */
 int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store3 *s, const int32_t *pairs,
                            const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);
+/* ... with a whole chain: sfe_icp3_compute_jobs_chain_ext over handles, bit for bit.  The filtered clouds go to context
+ * scratch; the store's slots, pool and count are unchanged afterwards.  o == NULL and no stages: sfe_icp3_store_compute. */
+int sfe_icp3_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd,
+                                     int n_rd, const sfe_icp_dpf *rf, int n_rf, sfe_cloud_store3 *s, const int32_t *pairs,
+                                     const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);
 /* SLAM.get_overlap in 3-D for n_jobs (source, target) pairs in one launch: the source moved by H12[j*12 ..];
  * counts_out[j] = its points with a target point within max_dist under the rules of sfe_match3: d2 =
  * fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), matched iff d2 <= fl(max_dist * max_dist), NaN and infinite distances never.

@@ -217,6 +217,11 @@ SIGNATURES = {
     "sfe_icp_compute_jobs_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
                                                  C.c_int, C.POINTER(IcpDpf), C.c_int, _f32p, C.c_int, _f32p, C.c_int, _i32p,
                                                  _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    # ... the chains on N x 3 clouds (sfe_icp3_dpf.hip, sfe_icp3.hip): 64-bit cloud offsets, 16 floats per guess and result
+    "sfe_icp3_filter_clouds_dev": (C.c_int, [_vp, C.POINTER(IcpDpf), C.c_int, _vp, _i64p, C.c_int, _vp, _i32p]),
+    "sfe_icp3_compute_jobs_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                  C.c_int, C.POINTER(IcpDpf), C.c_int, _f32p, C.c_int, _f32p, C.c_int, _i32p,
+                                                  _f32p, C.c_int, _f32p, _i32p, _i32p]),
     "sfe_icp_set_tuning": (C.c_int, [_vp, C.c_int]),
     "sfe_icp_get_profile": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_longlong)]),
     "sfe_icp_last_routes": (C.c_int, [_vp, _i32p, C.c_int, _i32p]),
@@ -252,6 +257,9 @@ SIGNATURES = {
     "sfe_cloud_store3_truncate": (C.c_int, [_vp, _vp, C.c_int32]),
     "sfe_cloud_store3_get_points": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_int, C.c_float, _i64p, _i32p]),
     "sfe_icp3_store_compute": (C.c_int, [_vp, C.POINTER(IcpParams), _vp, _i32p, _f32p, C.c_int, _f32p, _i32p, _i32p]),
+    "sfe_icp3_store_compute_chain_ext": (C.c_int, [_vp, C.POINTER(IcpParams), C.POINTER(IcpOutliers), C.POINTER(IcpDpf),
+                                                   C.c_int, C.POINTER(IcpDpf), C.c_int, _vp, _i32p, _f32p, C.c_int, _f32p,
+                                                   _i32p, _i32p]),
     "sfe_cloud_store3_overlap": (C.c_int, [_vp, _vp, _i32p, _f32p, C.c_int, C.c_float, _i32p]),
     # ... its keyed clouds: the SLAM cloud and the candidate selection of the loop-closure search over handles
     "sfe_cloud_store3_put_keys": (C.c_int, [_vp, _vp, C.c_int64, _f32p, _i32p, C.c_int, _i32p]),

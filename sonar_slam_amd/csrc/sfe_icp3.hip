@@ -1,7 +1,9 @@
 // 3-D ICP on gfx950: pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (pcl.cpp:198-212; PM::ICP is dimension-generic),
 // the module set of the shipped config/icp.yaml -- KDTreeMatcher {knn 1}, MaxDist and TrimmedDist outlier filters,
 // PointToPointErrorMinimizer (sfe_icp_params with minimizer 0) or PointToPlaneErrorMinimizer {force2D: 0} (minimizer 2),
-// Counter and Differential transformation checkers.
+// Counter and Differential transformation checkers.  A chain written for N x 3 clouds adds, in the EXT build of the job kernel,
+// the MinDist and MedianDist outlier filters and the Bound checker (sfe_icp_outliers; sfe_icp3_compute_jobs_chain_ext), and in
+// front of the launch its data-point filters (sfe_icp3_dpf.hip).
 //
 // The rules (include/sonarfe.h at sfe_icp3_compute_jobs) are the 2-D chain's with one more coordinate:
 //   centre the target on its mean, T0 = translate(-mean) * guess, reading = T0 * source            (once)
@@ -32,6 +34,7 @@
 #include <utility>
 
 #include "sfe_icp_common.h"
+#include "sfe_icp3_chain.h"
 #include "sfe_icp3_plane.h"
 #include "sfe_icp3_solve.h"
 
@@ -52,6 +55,20 @@ template <int MIN>
 struct Icp3Sums {
     static constexpr int N = MIN == ICP3_PLANE ? ICP3P_NSUM : ICP3_NSUM;
 };
+
+// What the job kernel gets by value: the chain's parameters and, in the EXT builds only, the modules sfe_icp_params has no
+// field for (MinDist / MedianDist outlier filters, Bound checker).  The EXT = 0 form is sfe_icp_params and nothing else, so
+// the kernel of a chain without those modules has the arguments, the code and the registers it had before they existed.
+template <int EXT>
+struct Icp3Args {
+    sfe_icp_params P;
+};
+template <>
+struct Icp3Args<1> {
+    sfe_icp_params P;
+    sfe_icp_outliers O;
+};
+static_assert(sizeof(Icp3Args<0>) == sizeof(sfe_icp_params), "the plain kernel takes sfe_icp_params alone");
 
 // c = a * b, 4 x 4 row-major, every entry (((a0 b0 + a1 b1) + a2 b2) + a3 b3) with each product and sum rounded to float
 __device__ __forceinline__ void mat4_mul(const float *a, const float *b, float *c)
@@ -213,11 +230,14 @@ __device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_
 // the fp64 Jacobi sweeps want more registers than the scan loop, and one lane runs them once per iteration.  MIN picks the
 // minimiser's solve (point-to-plane: a system that counts as singular ends the job with SFE_ICP_SINGULAR before anything is
 // composed or counted); everything behind it is the same code for both.
-template <int MIN>
-__device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const double (&acc)[Icp3Sums<MIN>::N],
+// EXT: the Bound checker in its place of the list (sfe_icp_outliers.bound_order: the rule of icp_solve_and_check,
+// sfe_icp_common.h, with icp3_bound_out for the test).
+template <int MIN, int EXT>
+__device__ __noinline__ void icp3_solve_and_check(const Icp3Args<EXT> &A, const double (&acc)[Icp3Sums<MIN>::N],
                                                      Icp3SharedT<Icp3Sums<MIN>::N> &S, int &nhist, int &counter, int &iters,
                                                      int &status, int &iterate)
 {
+    const sfe_icp_params &P = A.P;
     status = SFE_ICP_OK;
     iterate = 1;
     if (acc[0] == 0.0) {
@@ -243,6 +263,17 @@ __device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const
         S.Ti[i] = Tn[i];
     ++iters;
     ++counter;
+    // Bound: not evaluated when a Counter listed before it has just reached its limit; its status ends the job at once
+    // unless a Differential checker listed before it runs first (whose NaN status then wins)
+    bool out = false;
+    if constexpr (EXT) {
+        const sfe_icp_outliers &O = A.O;
+        out = O.use_bound && !((O.bound_order & 1) && counter >= P.max_iter) && icp3_bound_out(O, Tn);
+        if (out && !(O.bound_order & 2)) {
+            status = SFE_ICP_BOUND;
+            return;
+        }
+    }
     if (counter >= P.max_iter) {
         iterate = 0; // CounterTransformationChecker: MaxNumIterationsReached
     } else if (P.use_diff_checker) {
@@ -277,6 +308,10 @@ __device__ __noinline__ void icp3_solve_and_check(const sfe_icp_params &P, const
             else if (isnan(tsum))
                 status = SFE_ICP_NAN_TRANS;
         }
+    }
+    if constexpr (EXT) {
+        if (out && status == SFE_ICP_OK)
+            status = SFE_ICP_BOUND;
     }
 }
 
@@ -334,8 +369,11 @@ __device__ __forceinline__ void icp3_target_mean(const float *__restrict__ tgt, 
     __syncthreads();
 }
 
-template <int MIN>
-__global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P, const Icp3Job *__restrict__ jobs,
+// EXT = 1: the kernel of a chain that lists a MinDist or MedianDist outlier filter or a Bound checker (sfe_icp_outliers;
+// rules at sfe_icp3_compute_jobs_chain_ext in include/sonarfe.h).  The median is a second radix select over the same finite
+// d2; MinDist and the median limit join the keep test of both minimisers' sums; Bound runs in icp3_solve_and_check.
+template <int MIN, int EXT>
+__global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, const Icp3Job *__restrict__ jobs,
                                                                const float *__restrict__ src_all,
                                                                const float *__restrict__ tgt_all,
                                                                const float *__restrict__ guess_all,
@@ -346,6 +384,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
 {
     constexpr int NS = Icp3Sums<MIN>::N;
     using Icp3Shared = Icp3SharedT<NS>;
+    const sfe_icp_params &P = A.P;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Icp3Shared &S = *reinterpret_cast<Icp3Shared *>(smem_raw);
 
@@ -390,6 +429,9 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
 
     const float r2_match = f_mul(P.matcher_max_dist, P.matcher_max_dist);
     const float r2_filter = f_mul(P.max_dist_filter, P.max_dist_filter);
+    float min2 = 0.0f; // EXT: MinDist^2
+    if constexpr (EXT)
+        min2 = f_mul(A.O.min_dist, A.O.min_dist);
 
     while (true) {
         float Ti[12];
@@ -465,6 +507,27 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
             limit = job3_select_kth(S, nn_d2, ns, tid, min(k_sel, nfin - 1));
             __syncthreads();
         }
+        // ---- MedianDistOutlierFilter limit (EXT): factor x the median, the same select at rank icp3_median_rank ----
+        float med_limit = INFINITY;
+        if constexpr (EXT) {
+            if (A.O.use_median) {
+                if (nfin == 0) { // "no outlier to filter" (uniform)
+                    if (tid == 0)
+                        S.flag_status = SFE_ICP_NO_OUTLIER;
+                    break;
+                }
+                // (the barrier above: every wave has read the trimmed limit out of S.sel_prefix, which this select resets)
+                med_limit = f_mul(A.O.median_factor, job3_select_kth(S, nn_d2, ns, tid, icp3_median_rank(nfin)));
+                __syncthreads(); // (... and the median out of it before anything else writes it)
+            }
+        }
+        // a pair that MaxDist and Trimmed keep: do the EXT filters keep it too?
+        auto ext_keep = [&](float d) {
+            if constexpr (EXT)
+                return icp3_ox_keep(A.O, min2, med_limit, d);
+            else
+                return true;
+        };
 
         // ---- error minimiser: accumulate over kept pairs ----
         double acc[NS];
@@ -485,7 +548,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
                     const int id = nn_idx[i];
                     const float d = nn_d2[i];
                     if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) &&
-                          (!P.use_trimmed_filter || d <= limit)))
+                          (!P.use_trimmed_filter || d <= limit) && ext_keep(d)))
                         continue;
                     const float *s = src + 3 * (size_t)i;
                     const float sx = s[0], sy = s[1], sz = s[2];
@@ -538,7 +601,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
             for (int i = tid; i < ns; i += ICP_THREADS) {
                 const int id = nn_idx[i];
                 const float d = nn_d2[i];
-                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit)))
+                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit) &&
+                      ext_keep(d)))
                     continue;
                 const float *s = src + 3 * (size_t)i;
                 const float sx = s[0], sy = s[1], sz = s[2];
@@ -571,7 +635,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(sfe_icp_params P,
         // ---- solve, compose, check (thread 0) ----
         if (tid == 0) {
             int status, iterate;
-            icp3_solve_and_check<MIN>(P, acc, S, nhist, counter, iters, status, iterate);
+            icp3_solve_and_check<MIN, EXT>(A, acc, S, nhist, counter, iters, status, iterate);
             S.flag_status = status;
             S.flag_iterate = (status == SFE_ICP_OK) ? iterate : 0;
         }
@@ -777,11 +841,29 @@ int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
 // store's pool): a validated job table over two device pools, host guesses and host results.  Stages [guesses | job table
 // | target table], launches icp3_job_kernel -- for point-to-plane behind the normals of the call's distinct targets (by
 // first point and size: the 30 guesses of a compute_batch, or store pairs on one handle, take them once), in stream order
-// -- and brings [T | status | iterations] back: one copy each way, one synchronisation.
-int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt, const int64_t *jobs4,
-                     const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters)
+// -- and brings [T | status | iterations] back: one copy each way, one synchronisation.  `o` (nullable; all zero: none)
+// names the modules of the EXT build; without any the launch is the plain kernel's.
+template <int MIN, int EXT>
+static int icp3_launch(sfe_ctx *ctx, const Icp3Args<EXT> &A, int n_jobs, const Icp3Job *d_jobs, const float *d_src,
+                       const float *d_tgt, const float *d_g, const float *d_nrm, float *d_nn_d2, int *d_nn_idx, float *d_T,
+                       int32_t *d_st)
+{
+    using Shared = Icp3SharedT<Icp3Sums<MIN>::N>;
+    SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<MIN, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)sizeof(Shared)));
+    hipLaunchKernelGGL((icp3_job_kernel<MIN, EXT>), dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, A, d_jobs,
+                       d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx, d_T, d_st, d_st + n_jobs);
+    return 0;
+}
+
+int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const float *d_src,
+                     const float *d_tgt, const int64_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
+                     int32_t *status, int32_t *iters)
 {
     const bool plane = p->minimizer == ICP3_PLANE;
+    const bool ext = o && (o->use_min_dist || o->use_median || o->use_bound);
+    const Icp3Args<0> A0{*p};
+    const Icp3Args<1> A1{*p, ext ? *o : sfe_icp_outliers{}};
     std::vector<Icp3Job> jobs((size_t)n_jobs);
     std::vector<Nrm3Target> targets;
     std::map<std::pair<long long, int>, long long> seen; // (first point, size) of a target -> where its normals go
@@ -829,19 +911,17 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, 
         if (int rc = icp3_normals_dev(ctx, (const Nrm3Target *)d_tg, targets.data(), n_targets, d_tgt, (float *)(d_tg + b_tg),
                                       p->normals_knn, d_nrm))
             return rc;
-        using Shared = Icp3SharedT<ICP3P_NSUM>;
-        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<ICP3_PLANE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)sizeof(Shared)));
-        hipLaunchKernelGGL(icp3_job_kernel<ICP3_PLANE>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, *p,
-                           (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, (const float *)d_nrm, d_nn_d2, d_nn_idx,
-                           (float *)d_out, d_st, d_st + n_jobs);
+        if (int rc = ext ? icp3_launch<ICP3_PLANE, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
+                                                      (float *)d_out, d_st)
+                         : icp3_launch<ICP3_PLANE, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
+                                                      (float *)d_out, d_st))
+            return rc;
     } else {
-        using Shared = Icp3SharedT<ICP3_NSUM>;
-        SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<ICP3_POINT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)sizeof(Shared)));
-        hipLaunchKernelGGL(icp3_job_kernel<ICP3_POINT>, dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, *p,
-                           (const Icp3Job *)d_jobs, d_src, d_tgt, (const float *)d_g, (const float *)nullptr, d_nn_d2, d_nn_idx,
-                           (float *)d_out, d_st, d_st + n_jobs);
+        if (int rc = ext ? icp3_launch<ICP3_POINT, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, nullptr, d_nn_d2, d_nn_idx,
+                                                      (float *)d_out, d_st)
+                         : icp3_launch<ICP3_POINT, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, nullptr, d_nn_d2, d_nn_idx,
+                                                      (float *)d_out, d_st))
+            return rc;
     }
     SFE_LAUNCH_CHECK(ctx);
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
@@ -859,9 +939,20 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
                           int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
                           int32_t *status, int32_t *iters)
 {
+    return sfe_icp3_compute_jobs_chain_ext(ctx, p, nullptr, nullptr, 0, nullptr, 0, src, n_src_pts, tgt, n_tgt_pts, jobs4,
+                                           guesses16, n_jobs, T_out16, status, iters);
+}
+
+int sfe_icp3_compute_jobs_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd,
+                                    int n_rd, const sfe_icp_dpf *rf, int n_rf, const float *src, int n_src_pts,
+                                    const float *tgt, int n_tgt_pts, const int32_t *jobs4, const float *guesses16, int n_jobs,
+                                    float *T_out16, int32_t *status, int32_t *iters)
+{
     if (int rc = sfe_use(ctx))
         return rc;
     if (int rc = sfe_icp3_check_params(ctx, p))
+        return rc;
+    if (int rc = sfe_icp3_check_chain(ctx, o, rd, n_rd, rf, n_rf))
         return rc;
     SFE_ARG(ctx, n_jobs >= 0 && n_src_pts >= 0 && n_tgt_pts >= 0 &&
                      (n_jobs == 0 || (src && tgt && jobs4 && guesses16 && T_out16 && status)));
@@ -884,7 +975,8 @@ int sfe_icp3_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *sr
         return SFE_ERR_HIP;
     SFE_HIP(ctx, hipMemcpyAsync(d_src, src, b_src, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_tgt, tgt, b_tgt, hipMemcpyHostToDevice, ctx->stream));
-    return sfe_icp3_run_dev(ctx, p, d_src, d_tgt, jobs.data(), guesses16, n_jobs, T_out16, status, iters);
+    return sfe_icp3_chain_run_dev(ctx, p, o, rd, n_rd, rf, n_rf, d_src, d_tgt, jobs.data(), guesses16, n_jobs, T_out16, status,
+                                  iters);
 }
 
 int sfe_normals3(sfe_ctx *ctx, const float *pts, int n, int knn, float *normals_out)

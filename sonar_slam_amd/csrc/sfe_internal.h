@@ -10,7 +10,7 @@
 #include "../../include/sonarfe.h"
 #include "sfe_icp_gen.h"
 
-#define SFE_NSCRATCH 81 // (0..71: the numbers and the CF_SLOT_* / DPF_SLOT_* names in the .hip files; 72..80: sfe_icp_sweep.hip)
+#define SFE_NSCRATCH 81 // (0..71: the numbers and the CF_SLOT_* / DPF_SLOT_* / DPF3_SLOT_* names in the .hip files; 72..80: sfe_icp_sweep.hip)
 #define SFE_ICP_PROF_N 96 // values sfe_icp_get_profile hands back
 
 // Launcher knobs of one context, set by name with sfe_tune (the name -> field / range table is in sfe_ctx.hip).  The
@@ -198,9 +198,19 @@ int sfe_icp_dpf_run_host(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
 // sfe_icp3.hip: the parameter check of the 3-D ICP (minimizer 0, or 2 with its normals_knn), and one 3-D ICP call on device pools of packed
 // float triples with a validated job table (n_jobs x (src_start, n_src, tgt_start, n_tgt) in points, every cloud non-empty
 // and inside its pool), host guesses (16 floats per job) and host results; one synchronisation.  iters may be nullptr.
+// `o` (nullable; all zero: none): the MinDist / MedianDist / Bound modules, which pick the EXT build of the job kernel.
 int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p);
-int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const float *d_src, const float *d_tgt, const int64_t *jobs4,
-                     const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);
+int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const float *d_src,
+                     const float *d_tgt, const int64_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
+                     int32_t *status, int32_t *iters);
+// sfe_icp3_dpf.hip: the argument checks of a 3-D chain's modules and stages (no launch), and sfe_icp3_run_dev behind the
+// chain's data-point filters: every distinct slice of the job table filtered once, the job table rebuilt on the filtered
+// pools (context scratch).  Without stages it is sfe_icp3_run_dev.
+int sfe_icp3_check_chain(sfe_ctx *ctx, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd, const sfe_icp_dpf *rf,
+                         int n_rf);
+int sfe_icp3_chain_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd, int n_rd,
+                           const sfe_icp_dpf *rf, int n_rf, const float *d_src, const float *d_tgt, const int64_t *jobs4,
+                           const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters);
 
 // sfe_store.hip: append n_frames clouds ([f][cap] float2 + counts[f], device) to a store; enqueue only
 struct sfe_cloud_store;

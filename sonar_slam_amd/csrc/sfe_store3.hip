@@ -45,6 +45,7 @@
 //     fl( fma(p2, Hi2, fma(p1, Hi1, fl(p0 * Hi0))) + Hi3 )
 // -- the 3-term form of SFE_STORE_F32_POINTS in sfe_store.hip -- written with explicit intrinsics.
 #include "sfe_icp_common.h"
+#include "sfe_octree3.h"
 #include "sfe_store3_slots.h"
 
 #include <algorithm>
@@ -65,12 +66,6 @@ struct sfe_cloud_store3 {
     int32_t *d_key = nullptr;  // [capacity]: a key per pool point, at the point's offset (allocated at the first keyed call)
     uint8_t *d_sel = nullptr;  // [capacity]: a selection byte per pool point (allocated with d_key)
     Store3Slots slots;
-};
-
-struct S3Header { // Ds3Header
-    float cx, cy, cz, radius;
-    int levels;
-    int n_seg;
 };
 
 struct S3Pair { // one overlap / match_keys job
@@ -406,6 +401,56 @@ __global__ __launch_bounds__(256) void s3_place_keys_kernel(const int32_t *__res
     int32_t *__restrict__ dst = key_pool + (top + out_off[blockIdx.y]);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += 256 * gridDim.x)
         dst[i] = src[i];
+}
+
+// the downsample stages and the placement as enqueue-only steps (sfe_octree3.h): get_points below and the octree stage of a
+// 3-D ICP chain run them
+float sfe_s3_max_size(float resolution)
+{
+    char buf[64];
+    snprintf(buf, sizeof buf, "%f", (double)resolution); // pcl.cpp:134: std::to_string(float), as sfe_downsample3
+    return strtof(buf, nullptr);
+}
+
+int sfe_s3_octree_enqueue(sfe_ctx *ctx, const float *d_cat, const S3Job *d_jobs, int n_jobs, int max_tot, float max_size,
+                          const S3OctreeBufs &b)
+{
+    SFE_ARG(ctx, n_jobs >= 1 && n_jobs <= S3_MAX_JOBS && max_tot >= 0);
+    const unsigned nb = (unsigned)std::max((max_tot + 255) / 256, 1);
+    const dim3 per_point(nb, (unsigned)n_jobs), per_job((unsigned)n_jobs);
+    hipLaunchKernelGGL(s3_bbox_kernel, per_job, dim3(1024), 0, ctx->stream, d_cat, d_jobs, max_size, b.hdr);
+    hipLaunchKernelGGL(s3_key_kernel, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const S3Header *)b.hdr, b.keys);
+    hipLaunchKernelGGL(s3_rank_kernel, per_point, dim3(256), 0, ctx->stream, (const unsigned long long *)b.keys, d_jobs, b.sidx,
+                       b.skeys);
+    hipLaunchKernelGGL(s3_segment_kernel, per_job, dim3(1024), 0, ctx->stream, (const unsigned long long *)b.skeys, d_jobs, b.seg,
+                       b.hdr);
+    if (b.midx)
+        hipLaunchKernelGGL(s3_medoid_kernel<true>, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const int *)b.sidx,
+                           (const int *)b.seg, (const S3Header *)b.hdr, b.out, b.midx);
+    else
+        hipLaunchKernelGGL(s3_medoid_kernel<false>, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const int *)b.sidx,
+                           (const int *)b.seg, (const S3Header *)b.hdr, b.out, (int *)nullptr);
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int sfe_s3_offsets_enqueue(sfe_ctx *ctx, const S3Job *d_jobs, const S3Header *d_hdr, int n_jobs, int raw, int *d_cnt,
+                           long long *d_off)
+{
+    hipLaunchKernelGGL(s3_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_jobs, d_hdr, n_jobs, raw, d_cnt, d_off);
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int sfe_s3_place_enqueue(sfe_ctx *ctx, const float *d_from, const S3Job *d_jobs, int n_jobs, int max_tot, const int *d_cnt,
+                         const long long *d_off, long long top, float *pool)
+{
+    SFE_ARG(ctx, n_jobs >= 1 && n_jobs <= S3_MAX_JOBS && max_tot >= 0);
+    const unsigned nb = (unsigned)std::max((max_tot + 255) / 256, 1);
+    hipLaunchKernelGGL(s3_place_kernel, dim3(std::min(3u * nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream, d_from, d_jobs,
+                       d_cnt, d_off, top, pool);
+    SFE_LAUNCH_CHECK(ctx);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -816,9 +861,7 @@ static int s3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handl
         if (int rc = s3_key_pools(s))
             return rc;
     const int raw = !(resolution > 0.0f);
-    char buf[64];
-    snprintf(buf, sizeof buf, "%f", (double)resolution); // pcl.cpp:134: std::to_string(float), as sfe_downsample3
-    const float max_size = strtof(buf, nullptr);
+    const float max_size = sfe_s3_max_size(resolution);
 
     const size_t np = (size_t)std::max<int64_t>(total, 1);
     const size_t b_jobs = sizeof(S3Job) * (size_t)n_jobs, b_segs = sizeof(S3Seg) * segs.size();
@@ -859,7 +902,7 @@ static int s3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handl
     long long *d_off = (long long *)d_place;
     int32_t *d_cnt = (int32_t *)(d_place + sizeof(long long) * (size_t)n_jobs);
     const unsigned nb = (unsigned)std::max((max_tot + 255) / 256, 1);
-    const dim3 per_point(nb, (unsigned)n_jobs), per_job((unsigned)n_jobs);
+    const dim3 per_point(nb, (unsigned)n_jobs);
     if (keys)
         hipLaunchKernelGGL(s3_gather_kernel<true>, per_point, dim3(256), 0, ctx->stream, (const float *)s->d_pool, d_jobs, d_segs,
                            d_cat, d_segkey, d_ckey);
@@ -867,29 +910,19 @@ static int s3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *handl
         hipLaunchKernelGGL(s3_gather_kernel<false>, per_point, dim3(256), 0, ctx->stream, (const float *)s->d_pool, d_jobs, d_segs,
                            d_cat, (const int32_t *)nullptr, (int32_t *)nullptr);
     if (!raw) {
-        hipLaunchKernelGGL(s3_bbox_kernel, per_job, dim3(1024), 0, ctx->stream, (const float *)d_cat, d_jobs, max_size, d_hdr);
-        hipLaunchKernelGGL(s3_key_kernel, per_point, dim3(256), 0, ctx->stream, (const float *)d_cat, d_jobs,
-                           (const S3Header *)d_hdr, d_keys);
-        hipLaunchKernelGGL(s3_rank_kernel, per_point, dim3(256), 0, ctx->stream, (const unsigned long long *)d_keys, d_jobs, d_sidx,
-                           d_skeys);
-        hipLaunchKernelGGL(s3_segment_kernel, per_job, dim3(1024), 0, ctx->stream, (const unsigned long long *)d_skeys, d_jobs,
-                           d_seg, d_hdr);
-        if (keys) {
-            hipLaunchKernelGGL(s3_medoid_kernel<true>, per_point, dim3(256), 0, ctx->stream, (const float *)d_cat, d_jobs,
-                               (const int *)d_sidx, (const int *)d_seg, (const S3Header *)d_hdr, d_out, d_midx);
+        if (int rc = sfe_s3_octree_enqueue(ctx, d_cat, d_jobs, n_jobs, max_tot, max_size,
+                                           S3OctreeBufs{d_keys, d_skeys, d_sidx, d_seg, d_hdr, d_out, d_midx}))
+            return rc;
+        if (keys)
             hipLaunchKernelGGL(s3_pick_keys_kernel, per_point, dim3(256), 0, ctx->stream, (const int32_t *)d_ckey, d_jobs,
                                (const int *)d_midx, (const S3Header *)d_hdr, d_okey);
-        } else {
-            hipLaunchKernelGGL(s3_medoid_kernel<false>, per_point, dim3(256), 0, ctx->stream, (const float *)d_cat, d_jobs,
-                               (const int *)d_sidx, (const int *)d_seg, (const S3Header *)d_hdr, d_out, (int *)nullptr);
-        }
     }
-    hipLaunchKernelGGL(s3_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_jobs, (const S3Header *)d_hdr, n_jobs, raw, d_cnt,
-                       d_off);
+    if (int rc = sfe_s3_offsets_enqueue(ctx, d_jobs, d_hdr, n_jobs, raw, d_cnt, d_off))
+        return rc;
     // (the results lie within [top, top + total): the sum of the jobs' sizes is at most the bound tested above)
-    hipLaunchKernelGGL(s3_place_kernel, dim3(std::min(3u * nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream,
-                       (const float *)(raw ? d_cat : d_out), d_jobs, (const int *)d_cnt, (const long long *)d_off,
-                       (long long)t.top, s->d_pool);
+    if (int rc = sfe_s3_place_enqueue(ctx, raw ? d_cat : d_out, d_jobs, n_jobs, max_tot, d_cnt, d_off, (long long)t.top,
+                                      s->d_pool))
+        return rc;
     if (keys)
         hipLaunchKernelGGL(s3_place_keys_kernel, dim3(std::min(nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream,
                            (const int32_t *)(raw ? d_ckey : d_okey), d_jobs, (const int *)d_cnt, (const long long *)d_off,
@@ -1164,9 +1197,20 @@ int sfe_cloud_store3_match_keys(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t
 int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store3 *s, const int32_t *pairs,
                            const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters)
 {
+    return sfe_icp3_store_compute_chain_ext(ctx, p, nullptr, nullptr, 0, nullptr, 0, s, pairs, guesses16, n_jobs, T_out16, status,
+                                            iters);
+}
+
+// the chain's filters write context scratch only: the store's slots, pool and count stay as they are
+int sfe_icp3_store_compute_chain_ext(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const sfe_icp_dpf *rd,
+                                     int n_rd, const sfe_icp_dpf *rf, int n_rf, sfe_cloud_store3 *s, const int32_t *pairs,
+                                     const float *guesses16, int n_jobs, float *T_out16, int32_t *status, int32_t *iters)
+{
     if (int rc = s3_check(ctx, s))
         return rc;
     if (int rc = sfe_icp3_check_params(ctx, p))
+        return rc;
+    if (int rc = sfe_icp3_check_chain(ctx, o, rd, n_rd, rf, n_rf))
         return rc;
     SFE_ARG(ctx, n_jobs >= 0 && (n_jobs == 0 || (pairs && guesses16 && T_out16 && status)));
     if (n_jobs == 0)
@@ -1186,7 +1230,8 @@ int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_stor
         jobs4[4 * (size_t)j + 2] = t.off[(size_t)ht];
         jobs4[4 * (size_t)j + 3] = t.cnt[(size_t)ht];
     }
-    return sfe_icp3_run_dev(ctx, p, s->d_pool, s->d_pool, jobs4.data(), guesses16, n_jobs, T_out16, status, iters);
+    return sfe_icp3_chain_run_dev(ctx, p, o, rd, n_rd, rf, n_rf, s->d_pool, s->d_pool, jobs4.data(), guesses16, n_jobs, T_out16,
+                                  status, iters);
 }
 
 int sfe_cloud_store3_overlap(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t *pairs, const float *H12, int n_jobs,

@@ -47,6 +47,13 @@ the fixture that would pin them):
     another sampling method (libpointmatcher's default 0, FirstPoint, is not restated) or maxPointByNode != 1,
     dim >= 2 (3-D), a SurfaceNormal with epsilon != 0 or maxDist, or anywhere but the last reference stage of a
     point-to-plane chain, unknown parameter names, readingStepDataPointsFilters.
+
+Chains for N x 3 clouds: a chain says which dimension it was written for.  ``parse_icp_chain(text, dims=3)`` (and
+``IcpChain(..., dims=3)``) makes a 3-D chain: ``dim: 2`` (the z axis) is accepted, BoundingBox uses zMin / zMax, OctreeGrid
+is the 8-way tree of ``pcl.downsample`` on N x 3 clouds, and the Bound checker measures the 3-D rotation angle.  ``pcl.ICP``
+and ``store.CloudStore3.icp`` run such a chain's filters and modules on N x 3 clouds and refuse it on N x 2 clouds; a chain
+with ``dims=2`` (the default) stays what it was, refused with filters or extra modules on N x 3 clouds.  The stage rules are
+the ones above with one more coordinate (include/sonarfe.h at ``sfe_icp3_filter_clouds_dev``).
 """
 import math
 
@@ -227,13 +234,18 @@ class SurfaceNormalStage(object):
 class IcpChain(object):
     """A parsed ICP chain: ``params`` (IcpParams), ``reading`` and ``reference`` (lists of data-point filter stages:
     ``IcpDpf`` structures, and on the reference side possibly a final ``SurfaceNormalStage``), ``outliers``
-    (IcpOutliers: MinDist / MedianDist outlier filters and the Bound checker; all zero when none is listed)."""
+    (IcpOutliers: MinDist / MedianDist outlier filters and the Bound checker; all zero when none is listed), ``dims`` (2
+    or 3: the dimension of the clouds the chain was written for; it decides what ``dim: 2``, zMin / zMax, the octree and
+    the Bound checker's rotation mean)."""
 
-    def __init__(self, params, reading=(), reference=(), outliers=None):
+    def __init__(self, params, reading=(), reference=(), outliers=None, dims=2):
+        if dims not in (2, 3):
+            raise IcpConfigError("IcpChain: dims must be 2 or 3 (got %r)" % (dims,))
         self.params = params
         self.reading = list(reading)
         self.reference = list(reference)
         self.outliers = outliers if outliers is not None else IcpOutliers()
+        self.dims = int(dims)
 
     @staticmethod
     def device_stages(stages):
@@ -257,13 +269,16 @@ class IcpChain(object):
 
     def as_dict(self):
         """plain, picklable values (what a farm worker receives); ``IcpChain.from_dict`` rebuilds the chain exactly"""
-        return {"params": self.params.as_dict(), "reading": [_stage_dict(s) for s in self.reading],
-                "reference": [_stage_dict(s) for s in self.reference], "outliers": self.outliers.as_dict()}
+        d = {"params": self.params.as_dict(), "reading": [_stage_dict(s) for s in self.reading],
+             "reference": [_stage_dict(s) for s in self.reference], "outliers": self.outliers.as_dict()}
+        if self.dims == 3:      # (a 2-D chain's dictionary is what it always was)
+            d["dims"] = 3
+        return d
 
     @staticmethod
     def from_dict(d):
         return IcpChain(IcpParams(**d["params"]), [_stage_of(x) for x in d["reading"]],
-                        [_stage_of(x) for x in d["reference"]], IcpOutliers(**d["outliers"]))
+                        [_stage_of(x) for x in d["reference"]], IcpOutliers(**d["outliers"]), dims=d.get("dims", 2))
 
     def __eq__(self, other):
         return isinstance(other, IcpChain) and self.as_dict() == other.as_dict()
@@ -304,8 +319,12 @@ def _known_params(name, fp, allowed):
         raise IcpConfigError("%s: unsupported parameters %r" % (name, sorted(unknown)))
 
 
-def _dim(name, fp):
+def _dim(name, fp, dims=2):
     dim = int(fp.get("dim", -1))
+    if dims == 3:
+        if dim > 2 or dim < -1:
+            raise IcpConfigError("%s: dim %d is not -1, 0, 1 or 2" % (name, dim))
+        return dim
     if dim >= 2:
         raise IcpConfigError("%s: dim %d is a 3-D axis (the sonar clouds are 2-D)" % (name, dim))
     if dim < -1:
@@ -313,17 +332,17 @@ def _dim(name, fp):
     return dim
 
 
-def _stage(name, fp):
+def _stage(name, fp, dims=2):
     """one YAML data-point filter entry -> IcpDpf or SurfaceNormalStage (defaults: libpointmatcher's)"""
     if name in _RANDOM:
         raise IcpConfigError("%s draws random numbers: results would not be reproducible" % name)
     st = IcpDpf()
     if name == "MaxDistDataPointsFilter":
         _known_params(name, fp, ("dim", "maxDist"))
-        st.kind, st.dim, st.f[0] = DPF_MAX_DIST, _dim(name, fp), float(fp.get("maxDist", 1.0))
+        st.kind, st.dim, st.f[0] = DPF_MAX_DIST, _dim(name, fp, dims), float(fp.get("maxDist", 1.0))
     elif name == "MinDistDataPointsFilter":
         _known_params(name, fp, ("dim", "minDist"))
-        st.kind, st.dim, st.f[0] = DPF_MIN_DIST, _dim(name, fp), float(fp.get("minDist", 1.0))
+        st.kind, st.dim, st.f[0] = DPF_MIN_DIST, _dim(name, fp, dims), float(fp.get("minDist", 1.0))
     elif name == "BoundingBoxDataPointsFilter":
         keys = ("xMin", "xMax", "yMin", "yMax", "zMin", "zMax")
         _known_params(name, fp, keys + ("removeInside",))
@@ -358,9 +377,12 @@ def _stage(name, fp):
     return st
 
 
-def parse_icp_chain(text):
+def parse_icp_chain(text, dims=2):
     """YAML text -> IcpChain: the IcpParams of ``parse_icp_yaml`` plus the reading and reference data-point filters and
-    the outlier filters / checker of ``IcpChain.outliers``."""
+    the outlier filters / checker of ``IcpChain.outliers``.  ``dims=3``: a chain for N x 3 clouds (``dim: 2`` is the z
+    axis; ``IcpChain.dims`` is 3)."""
+    if dims not in (2, 3):
+        raise IcpConfigError("parse_icp_chain: dims must be 2 or 3 (got %r)" % (dims,))
     doc = _load(text)
     if doc.get("readingStepDataPointsFilters"):
         raise IcpConfigError("readingStepDataPointsFilters are not supported")
@@ -371,7 +393,7 @@ def parse_icp_chain(text):
             nodes = [nodes]
         if len(nodes) > MAX_STAGES:
             raise IcpConfigError("%s: %d stages, at most %d" % (key, len(nodes), MAX_STAGES))
-        sides[key] = [_stage(*_single(node, key)) for node in nodes]
+        sides[key] = [_stage(*_single(node, key), dims=dims) for node in nodes]
     outliers = IcpOutliers()
     params = _params(doc, outliers)
     reading, reference = sides["readingDataPointsFilters"], sides["referenceDataPointsFilters"]
@@ -386,4 +408,4 @@ def parse_icp_chain(text):
                 raise IcpConfigError("SurfaceNormalDataPointsFilter is only supported in a point-to-plane chain "
                                      "(PointToPlaneErrorMinimizer), where it sets the normals")
             params.normals_knn = s.knn
-    return IcpChain(params, reading, reference, outliers)
+    return IcpChain(params, reading, reference, outliers, dims=dims)

@@ -279,8 +279,9 @@ class ICP(object):
         self.params = None
         self.chain = None   # icp_config.IcpChain: params + the data-point filters (empty after setParams)
 
-    def loadFromYaml(self, filename, strict=None):
-        """pcl.cpp:187-197.  A file that cannot be opened makes the reference print a message and fall back to
+    def loadFromYaml(self, filename, strict=None, dims=2):
+        """pcl.cpp:187-197.  ``dims=3`` (extension): the file is a chain for N x 3 clouds (``icp_config.parse_icp_chain``
+        with ``dims=3``): its data-point filters and MinDist / MedianDist / Bound modules then run on N x 3 clouds.  A file that cannot be opened makes the reference print a message and fall back to
         PM::ICP::setDefault(): random sub-sampling of the reading, surface-normal sampling of the reference and a
         3-D point-to-plane chain -- not reproducible and not what any bruce_slam launch file intends.  Default
         (``strict`` True): an error instead of a silently different chain (deviations).
@@ -305,7 +306,7 @@ class ICP(object):
                                "surface normals), which this front end does not provide: fix the path, install a "
                                "chain with setParams(), or pass strict=False / set SONARFE_YAML_FALLBACK=shipped to "
                                "carry on with the chain of the shipped config/icp.yaml" % (filename, e))
-        self.setChain(_cfg.parse_icp_chain(text))
+        self.setChain(_cfg.parse_icp_chain(text, dims=dims))
 
     def setParams(self, params):
         """Extension: install an ``IcpParams`` directly (a chain without data-point filters)."""
@@ -318,7 +319,10 @@ class ICP(object):
         device and before any guess is applied; ICP then runs on the filtered clouds.  A job left with an empty cloud
         reports status 7, one whose octree stage would need more than 24 levels status 8 (T = the guess).  Its
         ``outliers`` (MinDist / MedianDist outlier filters, BoundTransformationChecker) run inside the ICP loop; a job
-        the Bound checker stops reports status 9, "limit out of bounds" (T = the guess)."""
+        the Bound checker stops reports status 9, "limit out of bounds" (T = the guess).  ``chain.dims`` says which clouds
+        the chain was written for: a ``dims=3`` chain runs all of this on N x 3 clouds with 4 x 4 guesses (the rules with one
+        more coordinate, no status 8) and is refused on N x 2 clouds; a ``dims=2`` chain with filters or those modules is
+        refused on N x 3 clouds."""
         self.params = chain.params
         self.chain = chain
 
@@ -367,10 +371,20 @@ class ICP(object):
         return _np.ascontiguousarray(g)
 
     def _chain2(self, what):
-        """a 2-D call: the 3-D point-to-plane minimiser is refused before anything reaches the library"""
+        """a 2-D call: the 3-D point-to-plane minimiser and a chain written for N x 3 clouds are refused before anything
+        reaches the library"""
         if self._chain().minimizer == 2:
             raise NotImplementedError("%s: PointToPlaneErrorMinimizer {force2D: 0} on N x 2 clouds: libpointmatcher would "
                                       "run its 2-D form there; say force2D: 1 (minimizer = 1) for 2-D clouds" % what)
+        ch = self.chain
+        if ch is not None and ch.dims == 3:
+            raise NotImplementedError("%s: a chain written for N x 3 clouds (dims = 3) on N x 2 clouds: its dim: 2, zMin / "
+                                      "zMax, 8-way octree and Bound rotation have no 2-D meaning; parse the chain with "
+                                      "dims = 2 for 2-D clouds" % what)
+        if ch is not None and any(isinstance(s, _L.IcpDpf) and s.kind in (_L.DPF_MAX_DIST, _L.DPF_MIN_DIST) and s.dim == 2
+                                  for s in ch.reading + ch.reference):
+            raise NotImplementedError("%s: a data-point filter stage with dim: 2 (the z axis) on N x 2 clouds: the device "
+                                      "stages of a 2-D chain take dim -1, 0 or 1" % what)
 
     # ---- N x 3 clouds with 4 x 4 guesses: the point-to-point or 3-D point-to-plane chain on sfe_icp3_compute_jobs ----
     @staticmethod
@@ -392,12 +406,14 @@ class ICP(object):
         return True
 
     def _chain3(self, what):
-        """the chain's params for a 3-D call; the modules that exist in 2-D only are refused"""
+        """the chain's params for a 3-D call; the filters and modules of a chain that was not written for N x 3 clouds
+        (``dims != 3``) are refused"""
         p = self._chain()
-        if self._stages() is not None:
+        dims3 = self.chain is not None and self.chain.dims == 3
+        if self._stages() is not None and not dims3:
             raise NotImplementedError("%s: data-point filters on N x 3 clouds: the device stages of a chain are 2-D "
                                       "(sfe_icp_dpf); filter the clouds with pcl.downsample / remove_outlier first" % what)
-        if self._outliers() is not None:
+        if self._outliers() is not None and not dims3:
             raise NotImplementedError("%s: MinDist / MedianDist outlier filters and the Bound checker on N x 3 clouds: "
                                       "the 3-D kernel runs the modules of the shipped icp.yaml only" % what)
         if p.minimizer == 1:
@@ -406,8 +422,24 @@ class ICP(object):
                                       "(minimizer = 2)" % what)
         return p
 
+    def _ext3(self):
+        """the arguments a ``*_chain_ext`` call of a dims = 3 chain puts behind the params (outliers, reading stages,
+        reference stages), or None when the chain lists neither stages nor modules: the plain entry point then"""
+        stages, ox = self._stages(), self._outliers()
+        if stages is None and ox is None:
+            return None
+        return (None if ox is None else _C.byref(ox),) + (stages or (None, 0, None, 0))
+
     def _call3(self, ctx, src, tgt, jobs4, g, T, st, it):
         n = len(jobs4)
+        ext = self._ext3()
+        if ext is not None:
+            with ctx.lock:
+                ctx._check(ctx.lib.sfe_icp3_compute_jobs_chain_ext(
+                    ctx.handle, _C.byref(self.params), *(ext + (
+                        _L.ptr(src, _C.c_float), len(src), _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(jobs4, _C.c_int32),
+                        _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float), _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))))
+            return
         with ctx.lock:
             ctx._check(ctx.lib.sfe_icp3_compute_jobs(ctx.handle, _C.byref(self.params), _L.ptr(src, _C.c_float), len(src),
                                                      _L.ptr(tgt, _C.c_float), len(tgt), _L.ptr(jobs4, _C.c_int32),

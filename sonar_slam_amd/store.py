@@ -468,7 +468,10 @@ class CloudStore3(object):
         clouds.  ``params``: an ``IcpParams`` or an ``icp_config.IcpChain``; what ``pcl.ICP`` refuses on N x 3 input
         (data-point filters, the MinDist / MedianDist / Bound modules, the 2-D point-to-plane form) is refused here in the
         same words; ``minimizer = 2`` (PointToPlaneErrorMinimizer {force2D: 0}) runs, pairs on one target handle sharing its
-        normals."""
+        normals.  A chain written for N x 3 clouds (``IcpChain.dims == 3``) runs whole: its reading filters once on every
+        distinct source handle of the call, its reference filters once on every distinct target handle, into context
+        scratch (the store is left as it was), its MinDist / MedianDist / Bound modules inside the loop; a job whose
+        filters leave no point reports status 7."""
         from . import pcl as _pcl
         icp = _pcl.ICP(self.ctx)
         if isinstance(params, _cfg.IcpChain):
@@ -482,6 +485,14 @@ class CloudStore3(object):
         n = len(pairs)
         g = np.ascontiguousarray(np.asarray(guesses, np.float32).reshape(n, 16))
         T, st, it = np.zeros((n, 4, 4), np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        ext = icp._ext3()
+        if ext is not None:
+            with self.ctx.lock:
+                self.ctx._check(self.ctx.lib.sfe_icp3_store_compute_chain_ext(
+                    self.ctx.handle, _C.byref(p), *(ext + (
+                        self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(g, _C.c_float), n, _L.ptr(T, _C.c_float),
+                        _L.ptr(st, _C.c_int32), _L.ptr(it, _C.c_int32)))))
+            return st, T, it
         with self.ctx.lock:
             self.ctx._check(self.ctx.lib.sfe_icp3_store_compute(
                 self.ctx.handle, _C.byref(p), self.handle, _L.ptr(pairs, _C.c_int32), _L.ptr(g, _C.c_float), n,
