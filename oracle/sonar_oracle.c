@@ -416,7 +416,10 @@ void orc_match(const float *ref, int nref, const float *in, int nin, float max_d
 }
 
 /* pcl.match with knn >= 1 (pcl.cpp:161-174; libpointmatcher KDTreeMatcher on libnabo's linear-heap tree: the knn
- * nearest, ascending; -1 / inf beyond maxDist).  Brute force: all distances, the knn smallest by (d2, index). */
+ * nearest, ascending; -1 / inf beyond maxDist).  Brute force: all distances, the knn smallest by (d2, index).
+ * A reference point at d2 = +inf is no neighbour for any max_dist, inf included: the rule of nn1 and of the device
+ * kernels (d < best from an infinite best), and -- as far as recalled, libnabo is not vendored: PARITY UNPINNED --
+ * libnabo's strict test against an infinite heap head. */
 typedef struct {
     float d;
     int id;
@@ -440,7 +443,7 @@ void orc_match_knn(const float *ref, int nref, const float *in, int nin, int knn
             volatile float dx = in[2 * i] - ref[2 * j], dy = in[2 * i + 1] - ref[2 * j + 1];
             volatile float a = dx * dx, b = dy * dy;
             const float d = a + b;
-            if (d == d) { /* a NaN distance is never a match */
+            if (d < INFINITY) { /* a NaN or infinite distance is never a match, whatever max_dist (nn1's d < best) */
                 e[m].d = d;
                 e[m].id = j;
                 ++m;

@@ -21,21 +21,25 @@ def _c3(a):
 
 def dist2(p, q):
     """squared distances of the rows of q [n x 3] from p ([3] or [n x 3]), float32, in the kernels' order"""
-    d = (p - q).astype(F)
-    a, b, c = d[..., 0] * d[..., 0], d[..., 1] * d[..., 1], d[..., 2] * d[..., 2]
-    return ((a + b).astype(F) + c).astype(F)
+    with np.errstate(over="ignore", invalid="ignore"):   # (points 3e19 apart: +inf, as in C)
+        d = (p - q).astype(F)
+        a, b, c = d[..., 0] * d[..., 0], d[..., 1] * d[..., 1], d[..., 2] * d[..., 2]
+        return ((a + b).astype(F) + c).astype(F)
 
 
 def match_knn(ref, pts, knn, max_dist):
-    """-> (ids int32 [knn x N], d2 float32 [knn x N]): ascending (d2, index), -1 / inf beyond the radius"""
+    """-> (ids int32 [knn x N], d2 float32 [knn x N]): ascending (d2, index), -1 / inf beyond the radius.  A reference
+    point at d2 = +inf is no neighbour for any max_dist, inf included (the kernels' and oracle.match's d < best from an
+    infinite best; recalled to be libnabo's strict heap test too, parity unpinned)."""
     ref, pts = _c3(ref), _c3(pts)
-    r2 = F(max_dist) * F(max_dist)                       # float * float, as sfe_match forms it
+    with np.errstate(over="ignore"):
+        r2 = F(max_dist) * F(max_dist)                   # float * float, as sfe_match forms it
     ids = np.full((knn, len(pts)), -1, np.int32)
     d2 = np.full((knn, len(pts)), np.inf, F)
     for i, p in enumerate(pts):
         d = dist2(p, ref)
         order = np.argsort(d, kind="stable")[:knn]       # stable: ties -> the lowest reference index
-        ok = d[order] <= r2                              # (NaN: never)
+        ok = (d[order] <= r2) & (d[order] < F(np.inf))   # (NaN: never; +inf: never, even with r2 = inf)
         ids[:len(order), i] = np.where(ok, order, -1)
         d2[:len(order), i] = np.where(ok, d[order], F(np.inf))
     return ids, d2
@@ -56,18 +60,20 @@ def knn_density(pts, knn):
     pts = _c3(pts)
     if knn > len(pts):
         raise RuntimeError("Requesting more points than available in cloud")
-    ids, _ = match_knn(pts, pts, knn, np.inf)            # incl. self; every neighbour exists
+    ids, _ = match_knn(pts, pts, knn, np.inf)            # incl. self; a point at d2 = +inf is no neighbour: ids -1
+    have = ids >= 0
+    real = have.sum(axis=0).astype(F)                    # the real neighbours: what the C oracle and the kernels divide by
     s = np.zeros((len(pts), 3), F)
-    for j in range(knn):                                 # one chain of additions per coordinate, in neighbour order
-        s = (s + pts[ids[j]]).astype(F)
-    mean = (s / F(knn)).astype(F)
-    rmax = np.zeros(len(pts), F)
-    for j in range(knn):
-        rmax = np.maximum(rmax, np.sqrt(dist2(pts[ids[j]], mean)).astype(F))
-    r = rmax.astype(np.float64)
-    volume = ((4. / 3.) * 3.14159265358979323846 * (r * r * r)).astype(F)
-    with np.errstate(divide="ignore"):
-        return (F(knn) / volume).astype(F)
+    with np.errstate(all="ignore"):
+        for j in range(knn):                             # one chain of additions per coordinate, in neighbour order
+            s = np.where(have[j][:, None], (s + pts[ids[j]]).astype(F), s)
+        mean = (s / real[:, None]).astype(F)
+        rmax = np.zeros(len(pts), F)
+        for j in range(knn):                             # fmax: a NaN distance never raises the maximum (r > rmax in C)
+            rmax = np.where(have[j], np.fmax(rmax, np.sqrt(dist2(pts[ids[j]], mean)).astype(F)), rmax)
+        r = rmax.astype(np.float64)
+        volume = ((4. / 3.) * 3.14159265358979323846 * (r * r * r)).astype(F)
+        return (real / volume).astype(F)
 
 
 def max_size_of(resolution):

@@ -1,0 +1,822 @@
+"""Constructed edge cases of the brute-force cloud kernels behind ``pcl.match``, ``pcl.remove_outlier``, ``pcl.knn_density``
+and the rank-counting route of ``pcl.downsample`` (csrc/sfe_icp.hip: match / match_knn / knn_density / radius_count;
+csrc/sfe_pcl3.hip: their N x 3 twins and ds3_*; csrc/sfe_map.hip: radius_count_many; csrc/sfe_downsample.hip: ds_*).
+tests/test_pcl_edges_host.py runs them through the references alone, tests/test_gpu_pcl_edges.py through the device.
+Importable without a GPU.
+
+Every case is a ``Case``: a name, one line saying what it is for, and the call's arguments.  Every constructor asserts, on the
+CPU and with the reference of its width, the property the case exists for.  ``dim`` is 2 or 3; the 3-D forms carry a z of
+their own, and ``z0`` appends a zero column to a 2-D case (the 3-D call must then give the 2-D answer).
+
+References: the C oracle (2-D) and tests/pcl3_ref.py (3-D, and 2-D clouds with z = 0).  ``model_*`` below restate the
+kernels' *structure* in numpy (2048-point tiles, a best carried across tiles, the global index tb + j, one pass per
+neighbour) with a ``variant`` switch that breaks one rule at a time: the host test shows that every such break is caught
+by a named case, and that ``variant=None`` is the reference.
+
+What the rules are where they were open:
+  * a reference point at d2 = +inf is no neighbour for any max_dist, inf included;
+  * knn_density divides by the number of real neighbours;
+  * the 2-D downsample cuts its tree at 31 levels, the oracle's recursion has no cap: ``LEVEL_CAP_CLOUD``.
+"""
+import collections
+from fractions import Fraction
+
+import numpy as np
+
+import pcl3_ref
+
+F = np.float32
+INF = F(np.inf)
+TILE = 2048                      # reference points per LDS tile (match, radius count, rank)
+LEVELS = {2: 31, 3: 21}          # DS_MAX_LEVELS / DS3_MAX_LEVELS
+U = 2.0 ** -24                   # unit roundoff of float32
+
+Case = collections.namedtuple("Case", "name why args")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, F).view(np.uint32)
+
+
+def z0(xy):
+    xy = np.ascontiguousarray(xy, F)
+    return np.ascontiguousarray(np.c_[xy, np.zeros(len(xy), F)], F)
+
+
+def up(x):
+    return np.nextafter(F(x), INF)
+
+
+def down(x):
+    return np.nextafter(F(x), -INF)
+
+
+def sq_float(m):
+    """max_dist * max_dist as sfe_match forms it: the float product of the float argument"""
+    with np.errstate(over="ignore"):
+        return F(m) * F(m)
+
+
+def sq_double(r):
+    """(float)(radius * radius) as sfe_remove_outlier forms it: the double product of the double argument, rounded"""
+    with np.errstate(over="ignore"):
+        return F(float(r) * float(r))
+
+
+def squares_differ(m):
+    return sq_float(m) != sq_double(m)
+
+
+def split_radii(n=4, lo=0.05, hi=1.5):
+    """the first n two-decimal radii whose float square and rounded double square differ (0.05, 0.1, 0.2, 0.35 ...)"""
+    out = [k / 100.0 for k in range(int(lo * 100), int(hi * 100) + 1, 5) if squares_differ(k / 100.0)]
+    assert len(out) >= n, out
+    return out[:n]
+
+
+# ---- the float rule and its fused counterfeit ------------------------------------------------------------------------------
+def dist2(p, q, fused=False):
+    """d2 = fl(fl(dx dx) + fl(dy dy)) [+ fl(dz dz)], every operation a float32 one.  fused: the contraction a compiler would
+    make of it, fma(dx, dx, fl(dy dy)) and then fma(dz, dz, .), through float64 (dx dx is exact there; the constructed
+    cases that depend on it are re-checked with exact fractions)."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        d = np.subtract(p, q, dtype=F)
+        s = np.multiply(d, d, dtype=F)
+        if not fused:
+            acc = np.add(s[..., 0], s[..., 1], dtype=F)
+            return acc if d.shape[-1] == 2 else np.add(acc, s[..., 2], dtype=F)
+        d64 = d.astype(np.float64)
+        acc = (d64[..., 0] * d64[..., 0] + s[..., 1].astype(np.float64)).astype(F)
+        return acc if d.shape[-1] == 2 else (d64[..., 2] * d64[..., 2] + acc.astype(np.float64)).astype(F)
+
+
+def fused_exact(p, q):
+    """``dist2(fused=True)`` of one pair with exact rational arithmetic (no double rounding)"""
+    d = [Fraction(float(F(a) - F(b))) for a, b in zip(p, q)]
+    acc = _round32(d[0] * d[0] + Fraction(float(F(float(d[1])) * F(float(d[1])))))
+    return acc if len(d) == 2 else _round32(d[2] * d[2] + Fraction(float(acc)))
+
+
+def _round32(x):
+    """a Fraction to the nearest float32, ties to even, without passing through float64"""
+    if x == 0:
+        return F(0)
+    lo = F(float(x))                                       # within a float64 rounding of x: the answer or a neighbour
+    cands = sorted({float(down(lo)), float(lo), float(up(lo))})
+    best = min(cands, key=lambda c: (abs(Fraction(c) - x), int(F(c).view(np.uint32)) & 1))
+    return F(best)
+
+
+# ---- numpy models of the kernels, with one rule broken at a time -----------------------------------------------------------
+MATCH_VARIANTS = ("le_update", "tile_local_index", "best_reset", "stale_tail", "lt_radius", "r2_other_precision", "fused",
+                  "knn_no_index_clause", "knn_ge_index", "inf_is_neighbour", "nan_is_zero")
+OUTLIER_VARIANTS = ("stale_tail", "lt_radius", "r2_other_precision", "fused", "count_ge", "count_no_self",
+                    "unsigned_min_points")
+DENSITY_VARIANTS = ("le_update", "knn_no_index_clause", "density_div_knn", "sqrt_approx", "inf_is_neighbour")
+DS_VARIANTS = ("rank_desc_index", "segment_wave_edge", "leaf_cut_at_tile", "nonpositive_is_identity")
+
+
+def _tiles(ref, variant):
+    """(global indices, points) per tile; stale_tail: a partial tile also scans what the previous tile left in LDS"""
+    for tb in range(0, len(ref), TILE):
+        tn = min(TILE, len(ref) - tb)
+        pts, idx = ref[tb:tb + tn], np.arange(tb, tb + tn)
+        if variant == "stale_tail" and tb > 0 and tn < TILE:
+            pts, idx = np.concatenate([pts, ref[tb - TILE + tn:tb]]), np.arange(tb, tb + TILE)
+        yield tb, idx, pts
+
+
+def model_match(ref, pts, knn, max_dist, variant=None):
+    """match_kernel / match_knn_kernel as written: neighbour jn = the lexicographic minimum of (d2, index) above neighbour
+    jn - 1, found tile by tile with a strict d < best -> (ids int32 [knn x N], d2 float32 [knn x N])"""
+    ref, pts = np.ascontiguousarray(ref, F), np.ascontiguousarray(pts, F)
+    n_in, rows = len(pts), np.arange(len(pts))
+    r2 = sq_double(max_dist) if variant == "r2_other_precision" else sq_float(max_dist)
+    ids, d2 = np.full((knn, n_in), -1, np.int32), np.full((knn, n_in), INF, F)
+    prev_d, prev_i = np.full(n_in, -1, F), np.full(n_in, -1, np.int64)
+    for jn in range(knn):
+        best, bi = np.full(n_in, INF, F), np.full(n_in, -1, np.int64)
+        far = np.full(n_in, -1, np.int64)                  # inf_is_neighbour: the first candidate at d2 = +inf
+        for tb, idx, tile in _tiles(ref, variant):
+            if variant == "best_reset":
+                best[:] = INF
+            d = dist2(pts[:, None, :], tile[None, :, :], fused=variant == "fused")
+            if variant == "nan_is_zero":                    # a comparison written so that NaN passes it
+                d = np.where(np.isnan(d), F(0), d)
+            same = d == prev_d[:, None]
+            if variant == "knn_no_index_clause":
+                after = d > prev_d[:, None]
+            elif variant == "knn_ge_index":
+                after = (d > prev_d[:, None]) | (same & (idx[None, :] >= prev_i[:, None]))
+            else:
+                after = (d > prev_d[:, None]) | (same & (idx[None, :] > prev_i[:, None]))
+            cand = np.where(after & ~np.isnan(d), d, INF)
+            if variant == "inf_is_neighbour":
+                isfar = after & (d == INF)
+                first = np.where(isfar.any(axis=1), idx[np.argmax(isfar, axis=1)], -1)
+                far = np.where((far < 0) & (first >= 0), first, far)
+            if variant == "le_update":                      # d <= best: the last point attaining the minimum wins
+                j = cand.shape[1] - 1 - np.argmin(cand[:, ::-1], axis=1)
+                upd = (cand[rows, j] <= best) & (cand[rows, j] < INF)
+            else:
+                j = np.argmin(cand, axis=1)
+                upd = cand[rows, j] < best
+            best = np.where(upd, cand[rows, j], best)
+            bi = np.where(upd, j if variant == "tile_local_index" else idx[j], bi)
+        if variant == "inf_is_neighbour":
+            bi = np.where((bi < 0) & (far >= 0), far, bi)
+        with np.errstate(invalid="ignore"):
+            miss = (bi < 0) | ~((best < r2) if variant == "lt_radius" else (best <= r2))
+        bi, best = np.where(miss, -1, bi), np.where(miss, INF, best)
+        ids[jn], d2[jn] = bi, best
+        prev_d, prev_i = np.where(bi < 0, INF, best).astype(F), bi
+    return ids, d2
+
+
+def model_outlier(pts, radius, min_points, variant=None):
+    """radius_count_kernel as written -> the keep mask"""
+    pts = np.ascontiguousarray(pts, F)
+    n = len(pts)
+    r2 = sq_float(radius) if variant == "r2_other_precision" else sq_double(radius)
+    cnt = np.zeros(n, np.int64)
+    for b in range(0, n, 512):
+        me = np.arange(b, min(b + 512, n))
+        for tb, idx, tile in _tiles(pts, variant):
+            d = dist2(pts[me][:, None, :], tile[None, :, :], fused=variant == "fused")
+            with np.errstate(invalid="ignore"):
+                near = (d < r2) if variant == "lt_radius" else (d <= r2)
+            if variant == "count_no_self":
+                near &= idx[None, :] != me[:, None]
+            cnt[me] += near.sum(axis=1)
+    if variant == "unsigned_min_points":
+        min_points = min_points & 0xFFFFFFFF
+    return (cnt >= min_points) if variant == "count_ge" else (cnt > min_points)
+
+
+def _sqrt_approx(q):
+    """a square root that is within an ulp but not correctly rounded (q * rsqrt(q) in float32)"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(q > 0, (q * (F(1) / np.sqrt(q).astype(F)).astype(F)).astype(F), np.sqrt(q).astype(F))
+
+
+def model_density(pts, knn, variant=None):
+    """sfe_knn_density as written: match_knn_kernel with r2 = inf, then knn_density_kernel"""
+    pts = np.ascontiguousarray(pts, F)
+    ids, _ = model_match(pts, pts, knn, np.inf, variant if variant in MATCH_VARIANTS else None)
+    have = ids >= 0
+    real = have.sum(axis=0).astype(F)
+    s = np.zeros(pts.shape, F)
+    with np.errstate(all="ignore"):
+        for j in range(knn):
+            s = np.where(have[j][:, None], np.add(s, pts[ids[j]], dtype=F), s)
+        mean = np.divide(s, (F(knn) if variant == "density_div_knn" else real[:, None]), dtype=F)
+        rmax = np.zeros(len(pts), F)
+        for j in range(knn):
+            q = dist2(pts[ids[j]], mean)
+            r = _sqrt_approx(q) if variant == "sqrt_approx" else np.sqrt(q).astype(F)
+            rmax = np.where(have[j], np.fmax(rmax, r), rmax)
+        r = rmax.astype(np.float64)
+        volume = ((4. / 3.) * 3.14159265358979323846 * (r * r * r)).astype(F)
+        return np.divide(F(knn) if variant == "density_div_knn" else real, volume, dtype=F)
+
+
+def ds_keys(pts, resolution):
+    """ds_bbox_kernel + ds_key_kernel: (keys uint64 [n], levels) -- every point descends `levels` levels, at most LEVELS[dim]"""
+    pts = np.ascontiguousarray(pts, F)
+    dim = pts.shape[1]
+    max_size = pcl3_ref.max_size_of(resolution)
+    mn, mx = pts.min(axis=0), pts.max(axis=0)
+    ext = np.subtract(mx, mn, dtype=F)
+    c = np.add(mn, np.multiply(ext, F(0.5), dtype=F), dtype=F)
+    r = F(ext.max() * F(0.5))
+    levels, rr = 0, r
+    while not (float(rr) * 2.0 <= float(max_size)) and levels < LEVELS[dim]:
+        rr, levels = F(rr * F(0.5)), levels + 1
+    key = np.zeros(len(pts), np.uint64)
+    c = np.broadcast_to(c, pts.shape).copy()
+    for _ in range(levels):
+        b = pts > c
+        child = np.zeros(len(pts), np.uint64)
+        for a in range(dim):
+            child |= b[:, a].astype(np.uint64) << np.uint64(a)
+        key = (key << np.uint64(dim)) | child
+        r = F(r * F(0.5))
+        c = np.add(c, np.where(b, r, -r), dtype=F)
+    return key, levels
+
+
+def model_downsample(pts, resolution, variant=None, info=None):
+    """the rank-counting chain: stable sort by (key, index), one leaf per run of equal keys, float centroid in that order, the
+    first point at the minimum float distance -> (medoids, their input indices int32)"""
+    pts = np.ascontiguousarray(pts, F)
+    if len(pts) == 0:
+        return pts.copy(), np.zeros(0, np.int32)
+    if variant == "nonpositive_is_identity" and not resolution > 0:      # what the batch entry point means by it
+        return pts.copy(), np.arange(len(pts), dtype=np.int32)
+    key, levels = ds_keys(pts, resolution)
+    i = np.arange(len(pts))
+    order = np.lexsort((-i if variant == "rank_desc_index" else i, key))
+    sk = key[order]
+    starts = np.r_[0, np.nonzero(sk[1:] != sk[:-1])[0] + 1, len(pts)]
+    if variant == "segment_wave_edge":                      # a run start on a wave's first lane (a multiple of 64) is lost
+        starts = np.array([r for r in starts if r == 0 or r == len(pts) or r % 64], np.int64)
+    if variant == "leaf_cut_at_tile":                       # a run is cut where the sorted keys cross a tile
+        starts = np.unique(np.r_[starts, np.arange(TILE, len(pts), TILE)]).astype(np.int64)
+    out = []
+    for a, b in zip(starts[:-1], starts[1:]):
+        leaf = order[a:b]
+        s = np.add.accumulate(pts[leaf], axis=0, dtype=F)[-1]
+        s = np.divide(s, F(b - a), dtype=F)
+        d = np.sqrt(dist2(pts[leaf], s)).astype(F)
+        out.append(int(leaf[int(np.argmin(d))]))
+    if info is not None:
+        info.update(levels=levels, sizes=np.diff(starts), leaves=[order[a:b] for a, b in zip(starts[:-1], starts[1:])])
+    idx = np.array(out, np.int32)
+    return pts[idx].copy(), idx
+
+
+# ---- references ------------------------------------------------------------------------------------------------------------
+def ref_match(ref, pts, knn, max_dist):
+    """the reference of the cloud's width: the C oracle for N x 2 (oracle.match for knn = 1 as well: asserted equal),
+    pcl3_ref for N x 3"""
+    ref, pts = np.ascontiguousarray(ref, F), np.ascontiguousarray(pts, F)
+    if ref.shape[1] == 3:
+        return pcl3_ref.match_knn(ref, pts, knn, max_dist)
+    import oracle
+    ids, d2 = oracle.match_knn(ref, pts, knn, max_dist)
+    if knn == 1:
+        ids1, d21 = oracle.match(ref, pts, max_dist)
+        assert np.array_equal(ids, ids1) and np.array_equal(bits(d2), bits(d21))
+    return ids, d2
+
+
+def ref_outlier(pts, radius, min_points):
+    """-> (kept rows, keep mask).  N x 2: the rows are the C oracle's, the mask pcl3_ref's on z = 0 (asserted consistent)"""
+    pts = np.ascontiguousarray(pts, F)
+    if pts.shape[1] == 3:
+        return pcl3_ref.remove_outlier(pts, radius, min_points, return_mask=True)
+    import oracle
+    rows = oracle.remove_outlier(pts, radius, min_points)
+    _, keep = pcl3_ref.remove_outlier(z0(pts), radius, min_points, return_mask=True)
+    assert np.array_equal(bits(rows), bits(pts[keep]))
+    return rows, keep
+
+
+def ref_density(pts, knn):
+    pts = np.ascontiguousarray(pts, F)
+    if pts.shape[1] == 3:
+        return pcl3_ref.knn_density(pts, knn)
+    import oracle
+    return oracle.knn_density(pts, knn)
+
+
+def ref_downsample(pts, resolution):
+    pts = np.ascontiguousarray(pts, F)
+    if pts.shape[1] == 3:
+        return pcl3_ref.downsample(pts, resolution)
+    import oracle
+    return oracle.downsample(pts, resolution, return_index=True)
+
+
+# ---- building blocks -------------------------------------------------------------------------------------------------------
+BOX = np.array([10.0, 10.0, 4.0])
+
+
+def cloud(seed, n, dim, lo=0.0, hi=1.0):
+    """n uniform points in the 10 x 10 (x 4) box scaled to [lo, hi] of it"""
+    u = np.random.default_rng(seed).uniform(lo, hi, (n, dim))
+    return np.ascontiguousarray(u * BOX[:dim], F)
+
+
+def far_site(k, dim):
+    """an empty place for constructed points: site k sits 50 m further out than the random cloud and the other sites"""
+    p = np.array([100.0 + 50.0 * k, -100.0, 7.0][:dim])
+    return p.astype(F)
+
+
+def point_at(target, site):
+    """a point q (off the site in every coordinate) whose float d2 from `site` is exactly `target`, by search: y and z
+    offsets from a list, x stepped ulp by ulp around the root of the rest.  The site's x is 0, so q's x is fine-grained."""
+    target, site = F(target), np.asarray(site, F)
+    dim = len(site)
+    assert site[0] == 0
+    scale = max(np.sqrt(float(target)), 1e-30)
+    small = [2.0 ** -k * scale for k in range(3, 24)]
+    for dz in (small[:8] if dim == 3 else [0.0]):
+        for dy in small:
+            q = (site + np.array([0.0, dy, dz][:dim], F)).astype(F)
+            rest = float(target) - float(dist2(q, site))
+            if rest <= 0:
+                continue
+            x = F(np.sqrt(rest))
+            for _ in range(16):
+                x = down(x)
+            for _ in range(33):
+                q[0] = x
+                if dist2(q, site) == target:
+                    return q.copy()
+                x = up(x)
+    raise AssertionError("no point at d2 = %r from %r" % (target, site))
+
+
+def bound_points(r2, dim):
+    """(site, queries at d2 == r2, the float below, the float above)"""
+    site = np.array([0.0, 0.0, 1.0][:dim], F)
+    qs = np.array([point_at(t, site) for t in (r2, down(r2), up(r2))], F)
+    assert [dist2(q, site) for q in qs] == [r2, down(r2), up(r2)]
+    return site, qs
+
+
+# ---- match / match_knn -----------------------------------------------------------------------------------------------------
+SIZE_PAIRS = [(1, 1), (2047, 63), (2048, 64), (2049, 255), (4096, 256), (4097, 257), (4097, 513)]
+RANDOM_RADIUS = {2: 0.35, 3: 0.7}     # (both squares differ between the two precisions)
+
+
+def match_size_cases(dim):
+    """the random part: every n_ref / n_in of the list with knn 1, 2 and 5; queries reach 1 m beyond the box, so some have
+    fewer than knn neighbours and some none"""
+    out = []
+    for n_ref, n_in in SIZE_PAIRS:
+        for knn in (1, 2, 5):
+            if knn > n_ref:
+                continue
+            ref, pts = cloud(100 + n_ref, n_ref, dim), cloud(200 + n_in, n_in, dim, -0.1, 1.1)
+            if n_ref > 1:
+                ids, _ = ref_match(ref, pts, knn, RANDOM_RADIUS[dim])
+                assert (ids[-1] == -1).any() and (ids[-1] >= 0).any() and (ids[0] >= 0).any()
+                assert n_ref < 2 * TILE or ((ids[0] >= TILE).any() and (0 <= ids[0]).any() and (ids[0] < TILE).any())
+            out.append(Case("sizes_%d_%d_knn%d" % (n_ref, n_in, knn), "n_ref / n_in at a tile / block edge, random cloud",
+                            (ref, pts, knn, RANDOM_RADIUS[dim])))
+    return out
+
+
+def _base(dim, n=4100):
+    """the filler of the constructed cases: 4100 random points (two full tiles and a partial one of 4)"""
+    return cloud(7, n, dim)
+
+
+def match_constructed_cases(dim):
+    out = []
+
+    def e(k, v):
+        x = np.zeros(dim, F)
+        x[k] = v
+        return x
+
+    # -- the nearest point at a tile edge
+    ref = _base(dim)
+    at = [0, 2047, 2048, 4096, 4099]
+    for k, i in enumerate(at):
+        ref[i] = far_site(k, dim)
+    pts = np.array([ref[i] + e(0, 0.01) + e(dim - 1, 0.02) for i in at], F)
+    for knn in (1, 2):
+        ids, d2 = ref_match(ref, pts, knn, 0.5)
+        assert ids[0].tolist() == at and (knn == 1 or (ids[1] == -1).all())       # unique: nothing else within 0.5 m
+        out.append(Case("nearest_at_tile_edges_knn%d" % knn, "the unique nearest point at index 0, 2047, 2048, 4096 and the "
+                        "last of a partial tile", (ref, pts, knn, 0.5)))
+
+    # -- ties across the boundary
+    ref = _base(dim)
+    s = [far_site(k, dim) for k in range(8)]
+    ref[2047] = ref[2048] = s[0]                                # an exact duplicate pair across the boundary
+    ref[2046], ref[2049] = s[1], s[1].copy()
+    ref[2049][0] = up(s[1][0])                                  # near-duplicates: 2049 one ulp to the right of 2046
+    ref[5] = ref[4090] = s[2]                                   # duplicates in the first and the last tile
+    ref[100], ref[3000] = s[3] + e(0, -1.0), s[3] + e(0, 1.0)   # a lattice tie: the query in the middle, d2 = 1 twice
+    pts = np.array([s[0] + e(1, 0.25),                          # -> 2047, then 2048
+                    s[1] + e(0, -0.25),                         # left of both: 2046 is nearer
+                    s[1] + e(0, 0.25),                          # right of both: 2049 is nearer, the higher index wins
+                    s[2] + e(dim - 1, 0.125),                   # -> 5, then 4090
+                    s[3]], F)                                   # -> 100, then 3000
+    for knn in (1, 2):
+        ids, d2 = ref_match(ref, pts, knn, 2.0)
+        assert ids[0].tolist() == [2047, 2046, 2049, 5, 100]
+        if knn == 2:
+            assert ids[1].tolist() == [2048, 2049, 2046, 4090, 3000]
+            assert d2[0, 0] == d2[1, 0] and d2[0, 3] == d2[1, 3] and d2[0, 4] == d2[1, 4] == 1.0
+            assert d2[0, 1] < d2[1, 1] and d2[0, 2] < d2[1, 2]
+        out.append(Case("ties_across_tiles_knn%d" % knn, "duplicates (2047, 2048) and (5, 4090), one-ulp near-duplicates in "
+                        "both orders, a lattice tie between two tiles", (ref, pts, knn, 2.0)))
+
+    # -- a run of four coincident points over the boundary; fewer than knn inside the radius; none
+    ref = _base(dim)
+    ref[2046:2050] = s[0]
+    ref[7], ref[2500] = s[1], s[1] + e(0, 0.125)
+    pts = np.array([s[0] + e(0, 0.0625), s[1] + e(0, 0.03125), s[5]], F)
+    for knn in (2, 5):
+        ids, d2 = ref_match(ref, pts, knn, 0.35)
+        assert ids[:min(knn, 4), 0].tolist() == [2046, 2047, 2048, 2049][:knn] and len(set(bits(d2[:min(knn, 4), 0]))) == 1
+        assert ids[:2, 1].tolist() == [7, 2500] and (ids[2:, 1] == -1).all() and np.isinf(d2[2:, 1]).all()
+        assert (ids[:, 2] == -1).all() and np.isinf(d2[:, 2]).all()
+        assert knn == 2 or ids[4, 0] == -1
+        out.append(Case("knn_run_and_suffix_knn%d" % knn, "four coincident points 2046..2049 in index order; a query with "
+                        "two neighbours inside the radius; a query with none", (ref, pts, knn, 0.35)))
+
+    # -- the bound: d2 == r2, one float below, one above; the point sits in the second tile
+    for m in [0.5] + split_radii(3):
+        r2 = sq_float(m)
+        site, qs = bound_points(r2, dim)
+        ref = _base(dim) + F(20.0)                              # the filler is far from the origin side
+        ref[2051] = site
+        for knn in (1, 2):
+            ids, d2 = ref_match(ref, qs, knn, m)
+            assert ids[0].tolist() == [2051, 2051, -1] and bits(d2[0])[0] == bits(r2) and d2[0, 1] == down(r2)
+            out.append(Case("bound_%g_knn%d" % (m, knn), "nearest d2 exactly r2 = fl(m * m), the float below it and the float "
+                            "above it" + ("; fl(m * m) != fl(double m * m)" if squares_differ(m) else ""), (ref, qs, knn, m)))
+
+    # -- max_dist = 0 with a coincident point, max_dist = inf
+    ref = _base(dim)
+    pts = np.array([ref[2048], ref[2048] + e(0, 1e-3), s[0], -s[0]], F)
+    for knn in (1, 2):
+        ids, d2 = ref_match(ref, pts, knn, 0.0)
+        assert ids[0].tolist() == [2048, -1, -1, -1] and d2[0, 0] == 0 and (ids[1:] == -1).all()
+        out.append(Case("max_dist_zero_knn%d" % knn, "r2 = 0 admits exactly the coincident point", (ref, pts, knn, 0.0)))
+        ids, d2 = ref_match(ref, pts, knn, np.inf)
+        assert (ids >= 0).all() and np.isfinite(d2).all() and d2[0, 2] > 1e4
+        out.append(Case("max_dist_inf_knn%d" % knn, "r2 = inf admits every finite distance", (ref, pts, knn, np.inf)))
+
+    # -- rounding: pairs where the fused d2 would pick the other candidate
+    ref, pts = fused_flip_pairs(dim)
+    ids, _ = ref_match(ref, pts, 1, 5.0)
+    ids_f, _ = model_match(ref, pts, 1, 5.0, "fused")
+    assert (ids != ids_f).sum() >= 5
+    out.append(Case("fused_flips", "two candidates per query whose order by d2 differs between the unfused and the fused float "
+                    "form", (ref, pts, 1, 5.0)))
+
+    # -- knn = n_ref
+    ref, pts = cloud(31, 37, dim), cloud(32, 70, dim, -0.1, 1.1)
+    ids, d2 = ref_match(ref, pts, 37, 8.0)
+    full = (ids >= 0).all(axis=0)
+    assert full.any() and (~full).any() and all(sorted(c) == list(range(37)) for c in ids.T[full])
+    out.append(Case("knn_is_n_ref", "every reference point is a neighbour, in (d2, index) order", (ref, pts, 37, 8.0)))
+
+    # -- non-finite input
+    nan, big = np.nan, 3e19
+    ref = np.array([[nan, nan, nan], [0, 0, 1], [1, 0, 1], [0, 1, 1], [big, 0, 1], [0, big, 1], [-big, -big, 1], [nan, 1, 1],
+                    [0.5, 0.5, nan]], F)[:, :dim]
+    pts = np.array([[0.1, 0.2, 1.5], [nan, 0, 1], [0, nan, 1], [big, 0, 1], [0.2, 0.7, 1]], F)[:, :dim]
+    if dim == 2:
+        ref[8] = (nan, 0.5)
+    for knn in (1, 4, len(ref)):
+        for m in (2.0, np.inf):
+            ids, d2 = ref_match(ref, pts, knn, m)
+            assert (ids[:, 1:3] == -1).all() and np.isinf(d2[:, 1:3]).all()             # a NaN query
+            assert not np.isin(ids, [0, 7, 8]).any()                                   # NaN reference points
+            assert ids[0, 3] == 4 and (ids[1:, 3] == -1).all()                      # the far query: its copy at d2 = 0 only
+            assert knn < 4 or (ids[:3, 0].tolist() == [1, 3, 2] and (ids[3:, 0] == -1).all())    # d2 = inf: no neighbour
+            out.append(Case("nonfinite_knn%d_%s" % (knn, "inf" if m == np.inf else "2"), "NaN queries and reference points, "
+                            "reference points at d2 = +inf, with max_dist %g" % m, (ref, pts, knn, m)))
+
+    # -- n_in = 0 (n_ref = 0 goes through the C entry point: test_gpu_pcl_edges.py)
+    out.append(Case("no_queries", "n_in = 0: two empty arrays of the right shape", (cloud(1, 10, dim), np.zeros((0, dim), F), 1,
+                                                                                   1.0)))
+    return out
+
+
+def fused_flip_pairs(dim, want=8):
+    """reference points (a_k, b_k) and queries q_k, one triple per far site, such that a_k wins by the unfused float d2 and b_k
+    wins (or ties, which would give a_k's lower index ... so: strictly wins) by the fused one, or the other way round"""
+    rng = np.random.default_rng(5)
+    ref, pts = [], []
+    k = 0
+    while len(pts) < want:
+        c = far_site(len(pts), dim).astype(np.float64)
+        q = c + rng.uniform(-1, 1, dim)
+        rad = rng.uniform(0.5, 2.0)
+        ab = []
+        for _ in range(2):
+            v = rng.normal(size=dim)
+            ab.append(q + rad * v / np.linalg.norm(v))
+        q, a, b = F(q).astype(F), np.array(ab[0], F), np.array(ab[1], F)
+        du, df = dist2(q, np.array([a, b])), dist2(q, np.array([a, b]), fused=True)
+        win_u, win_f = int(du[1] < du[0]), int(df[1] < df[0])
+        k += 1
+        assert k < 200000
+        if win_u == win_f:
+            continue
+        fe = [fused_exact(q, a), fused_exact(q, b)]
+        if fe[0] != df[0] or fe[1] != df[1]:
+            continue                                           # (double rounding in the float64 shortcut: not this one)
+        ref += [a, b]
+        pts.append(q)
+    return np.array(ref, F), np.array(pts, F)
+
+
+def match_cases(dim):
+    return match_size_cases(dim) + match_constructed_cases(dim)
+
+
+def true_nearest_bound(dim):
+    """The float rule against float64 (the random cases): with u = 2^-24 and D the true squared distance of float points,
+    dx = fl(px - tx) = (px - tx)(1 + e1); fl(dx dx) = dx^2 (1 + e2); each addition (one in 2-D, two in 3-D) one more (1 + e):
+    d2 = D (1 + t) with (1 - u)^k <= 1 + t <= (1 + u)^k, k = 2 + 1 + 1 = 4 in 2-D (the subtraction counts twice: it is
+    squared) and 5 in 3-D.  No product of these clouds under- or overflows (coordinates are multiples of 2^-24 * 16 below
+    16).  The kernel returns the point of the least float d2, so D_ret (1 - u)^k <= d2_ret <= d2_true <= D_min (1 + u)^k:
+        D_ret <= D_min ((1 + u) / (1 - u))^k,      |d2_ret - D_ret| <= ((1 + u)^k - 1) D_ret.
+    -> (the factor, the relative error of d2)"""
+    k = 4 if dim == 2 else 5
+    return ((1 + U) / (1 - U)) ** k, (1 + U) ** k - 1
+
+
+def check_against_float64(c, ids, d2):
+    """(ids, d2) of a random match case against float64 within true_nearest_bound -> the number of neighbours checked"""
+    ref, pts, knn, m = c.args
+    factor, rel = true_nearest_bound(ref.shape[1])
+    r2 = float(sq_float(m))
+    diff = pts.astype(np.float64)[:, None, :] - ref.astype(np.float64)[None, :, :]
+    D = np.sort((diff * diff).sum(axis=2), axis=1)[:, :knn].T            # [knn x N]: the true j-th smallest
+    Dm = (diff * diff).sum(axis=2)
+    have = ids >= 0
+    D_ret = np.where(have, Dm[np.arange(len(pts))[None, :], np.where(have, ids, 0)], np.inf)
+    assert (D_ret[have] <= D[have] * factor).all(), c.name
+    assert (np.abs(d2[have].astype(np.float64) - D_ret[have]) <= rel * D_ret[have]).all(), c.name
+    assert (D[~have] * (1 + rel) > r2).all(), c.name                     # a missing neighbour: truly at the radius or beyond
+    return int(have.sum())
+
+
+# ---- remove_outlier --------------------------------------------------------------------------------------------------------
+OUTLIER_SIZES = [255, 256, 257, 2047, 2048, 2049, 4097]
+
+
+def outlier_cases(dim):
+    out = []
+    for n in OUTLIER_SIZES:                                      # about four points in a radius: the filter decides both ways
+        rad = RANDOM_RADIUS[dim]
+        side = (n * np.pi * rad ** 2 / 4.0) ** 0.5 if dim == 2 else (n * 4.19 * rad ** 3 / 4.0) ** (1 / 3.0)
+        pts = np.ascontiguousarray(np.random.default_rng(300 + n).uniform(0, side, (n, dim)), F)
+        pts[n - n // 16:] = pts[:n // 16]                         # duplicates: each counts for the other
+        _, keep = ref_outlier(pts, rad, 4)
+        assert 0.2 * n < keep.sum() < 0.8 * n, keep.sum()
+        out.append(Case("sizes_%d" % n, "n at a tile / block edge, random cloud with duplicates", (pts, rad, 4)))
+
+    def lattice(n):
+        """n isolated points: a 1 m lattice, every count is 1"""
+        g = np.arange(n)
+        p = np.zeros((n, dim), F)
+        p[:, 0], p[:, 1] = g % 64, g // 64
+        return p
+
+    # -- a count of exactly min_points (dropped) and min_points + 1 (kept), the neighbours in one tile and in three
+    for name, a_idx, b_idx in (("count_exact_one_tile", [10, 11, 12, 13], [20, 21, 22, 23, 24]),
+                               ("count_exact_three_tiles", [10, 2047, 2048, 4096], [20, 2046, 2049, 4095, 4090])):
+        pts = lattice(4097)
+        sa, sb = far_site(0, dim), far_site(1, dim)
+        for k, i in enumerate(a_idx):
+            pts[i] = sa + F(0.01 * k)
+        for k, i in enumerate(b_idx):
+            pts[i] = sb + F(0.01 * k)
+        rows, keep = ref_outlier(pts, 0.35, 4)
+        assert np.nonzero(keep)[0].tolist() == sorted(b_idx) and np.array_equal(bits(rows), bits(pts[sorted(b_idx)]))
+        out.append(Case(name, "a cluster of min_points points is dropped, one of min_points + 1 kept, in input order",
+                        (pts, 0.35, 4)))
+
+    # -- a neighbour at exactly r2 and one ulp to each side; radii whose squares differ between the precisions
+    for rad in [0.5] + split_radii(3):
+        r2 = sq_double(rad)
+        pts = lattice(2100)
+        for k, t in enumerate((r2, down(r2), up(r2))):
+            site = np.array([0.0, -8.0 * (k + 1), 3.0][:dim], F)
+            q = point_at(t, site)
+            assert dist2(q, site) == t and dist2(site, q) == t
+            pts[40 + k], pts[2050 + k] = site, q
+        _, keep = ref_outlier(pts, rad, 1)
+        assert np.nonzero(keep)[0].tolist() == [40, 41, 2050, 2051]
+        if squares_differ(rad):                                 # ... and a pair at the other precision's r2: decided by it
+            other = sq_float(rad)
+            site = np.array([0.0, -40.0, 3.0][:dim], F)
+            q = point_at(max(other, r2), site)
+            pts[50], pts[2060] = site, q
+            _, keep = ref_outlier(pts, rad, 1)
+            assert bool(keep[50]) == bool(r2 > other) and keep[50] == keep[2060]
+        out.append(Case("bound_%g" % rad, "a neighbour (in the other tile) at d2 == r2 = fl(double r * r), the float below, the "
+                        "float above" + ("; and at the float square, which differs" if squares_differ(rad) else ""),
+                        (pts, rad, 1)))
+
+    # -- min_points 0, negative, >= n; a NaN point counts nobody, itself included
+    pts = cloud(41, 300, dim)
+    pts[17] = np.nan
+    for mp, kept in ((0, 299), (-1, 300), (-5, 300), (300, 0), (1000, 0)):
+        rows, keep = ref_outlier(pts, 0.5, mp)
+        assert keep.sum() == kept and bool(keep[17]) == (mp < 0)
+        out.append(Case("min_points_%d" % mp, "min_points %d keeps %d of 300 (a NaN point has count 0)" % (mp, kept),
+                        (pts, 0.5, mp)))
+
+    # -- radius 0 on a cloud with duplicates: only coincident points count
+    pts = cloud(42, 2100, dim)
+    pts[2050:2080] = pts[:30]
+    pts[100] = pts[101] = pts[2090] = pts[2099]
+    for mp, kept in ((1, 64), (2, 4), (4, 0)):
+        rows, keep = ref_outlier(pts, 0.0, mp)
+        assert keep.sum() == kept
+        out.append(Case("radius_zero_min%d" % mp, "r2 = 0: pairs and a quadruple of coincident points against min_points %d" % mp,
+                        (pts, 0.0, mp)))
+    out.append(Case("empty", "n = 0", (np.zeros((0, dim), F), 0.35, 4)))
+    return out
+
+
+def outlier_many_batches():
+    """sfe_remove_outlier_many: [(name, radius, min_points, [clouds])] -- clouds of unequal size in one launch, empty ones
+    at the front, in the middle and at the end; built from the 2-D cases of one radius / min_points"""
+    cases = outlier_cases(2)
+    e = np.zeros((0, 2), F)
+    sized = [c.args[0] for c in cases if c.args[1:] == (0.35, 4)]
+    built = [c.args[0] for c in cases if c.name.startswith(("bound_", "radius_zero_min1", "min_points_0"))]
+    assert len(sized) >= 8 and len(built) >= 5
+    out = [("many_sizes", 0.35, 4, [e] + sized[:2] + [e, e] + sized[2:] + [e])]
+    for rad, mp in ((0.35, 1), (0.0, 1), (0.5, -1)):             # the constructed clouds again, one radius per launch
+        out.append(("many_built_r%g_min%d" % (rad, mp), rad, mp, built[:3] + [e] + built[3:]))
+    return out
+
+
+# ---- knn_density -----------------------------------------------------------------------------------------------------------
+def density_cases(dim):
+    out = []
+    for n in (256, 257, 2049):
+        pts = cloud(500 + n, n, dim)
+        want = ref_density(pts, 5)
+        assert np.isfinite(want).all() and (want > 0).all()
+        out.append(Case("sizes_%d" % n, "n at a block / tile edge, random cloud", (pts, 5)))
+    pts = cloud(51, 12, dim)
+    want = ref_density(pts, 12)
+    assert len(set(bits(want))) > 1                              # the same 12 neighbours, another order: another float mean
+    out.append(Case("knn_is_n", "every point is a neighbour of every point", (pts, 12)))
+    pts = cloud(52, 300, dim)
+    pts[99], pts[10] = np.array([2.5, 3.75, 1.25], F)[:dim], np.array([7.25, 1.5, 3.5], F)[:dim]    # 5 p / 5 is exact
+    pts[100:106] = pts[99]
+    pts[290:296] = pts[10]
+    pts[200:206] = pts[199]                                      # (any float: the mean of five copies may miss it by an ulp)
+    want = ref_density(pts, 5)
+    assert np.isinf(want[[10, 99, 100, 105, 290, 295]]).all() and np.isinf(want).sum() >= 14 and (want > 0).all()
+    out.append(Case("coincident", "more coincident points than knn: r = 0, an infinite density", (pts, 5)))
+    g = np.random.default_rng(53)                                 # a 0.1 m lattice, shuffled: equal distances everywhere
+    lat = np.array([[i, j, k] for i in range(10) for j in range(10) for k in range(3)], np.float64)[:, :dim]
+    lat = np.unique(lat, axis=0)
+    pts = np.ascontiguousarray((lat * 0.1)[g.permutation(len(lat))], F)
+    ids, d2 = ref_match(pts, pts, 4, np.inf)
+    assert ((d2[1] == d2[2]) | (d2[2] == d2[3])).mean() > 0.5
+    out.append(Case("lattice_ties", "neighbours at equal distances: the index order decides the float mean's addition order",
+                    (pts, 4)))
+    big = 3e19
+    pts = np.array([[0, 0, 0], [1, 0, 0.5], [0, 1, 0.25], [big, 0, 0], [0, big, 0], [-big, -big, big]], F)[:, :dim]
+    want = ref_density(pts, 4)
+    ids, _ = ref_match(pts, pts, 4, np.inf)
+    assert (ids[3, :3] == -1).all() and (ids[1:, 3:] == -1).all() and (want[:3] > 0).all() and np.isinf(want[3:]).all()
+    out.append(Case("far_points", "points at d2 = +inf from the others are nobody's neighbour: three real neighbours near the "
+                    "origin, one (itself) far out", (pts, 4)))
+    pts = cloud(54, 400, dim)
+    assert (bits(model_density(pts, 5, "sqrt_approx")) != bits(ref_density(pts, 5))).any()
+    out.append(Case("sqrt_rounding", "rmax arguments on which a one-ulp sqrtf gives another radius", (pts, 5)))
+    return out
+
+
+# ---- the rank-counting downsample ------------------------------------------------------------------------------------------
+DS_SIZES = [255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 4097]
+SIDE = 64.0                                                       # two anchors: a 64 m box, 7 levels to 0.5 m leaves
+
+
+def anchors(dim):
+    return np.array([[0, 0, 0], [SIDE, SIDE, SIDE]], F)[:, :dim]
+
+
+def in_cells(rng, cells, sizes, dim):
+    """sizes[k] points well inside cell cells[k] of the 0.5 m grid"""
+    return np.concatenate([(np.asarray(c)[:dim] + rng.uniform(0.06, 0.94, (k, dim))) * 0.5 for c, k in zip(cells, sizes)])
+
+
+def ds_cases(dim):
+    out = []
+    rng = np.random.default_rng(9)
+    for n in DS_SIZES:                                            # leaves of 1 .. 12 points around the middle, shuffled
+        sizes = []
+        while sum(sizes) < n - 2 - n // 10:
+            sizes.append(int(min(rng.integers(1, 13), n - 2 - n // 10 - sum(sizes))))
+        side = int(np.ceil(len(sizes) ** (1.0 / dim)))
+        cells = [np.array(np.unravel_index(k, (side,) * dim)) + 20 for k in range(len(sizes))]
+        p = in_cells(rng, cells, sizes, dim)
+        p = np.concatenate([anchors(dim), p, p[:n // 10]])        # a tenth are exact duplicates: ties inside leaves
+        pts = np.ascontiguousarray(p[rng.permutation(n)], F)
+        info = {}
+        _, idx = model_downsample(pts, 0.5, info=info)
+        assert len(pts) == n and len(idx) == len(sizes) + 2 and info["levels"] == 7
+        out.append(Case("sizes_%d" % n, "n at a block / segment / tile edge; anchored 0.5 m grid, %d leaves" % len(idx),
+                        (pts, 0.5)))
+    # -- one leaf longer than a tile
+    p = np.concatenate([anchors(dim), in_cells(rng, [np.full(dim, 40)], [2049], dim)])
+    pts = np.ascontiguousarray(p[rng.permutation(len(p))], F)
+    info = {}
+    model_downsample(pts, 0.5, info=info)
+    assert sorted(info["sizes"]) == [1, 1, 2049]
+    out.append(Case("one_long_leaf", "2049 equal keys: a leaf longer than a rank tile", (pts, 0.5)))
+    # -- a leaf per point, n_seg = 1024 / 1025
+    for n_seg in (1024, 1025):
+        cells = [np.r_[k % 40 + 10, k // 40 + 10, np.full(max(dim - 2, 0), 30)] for k in range(n_seg - 2)]
+        p = np.concatenate([anchors(dim), in_cells(rng, cells, [1] * (n_seg - 2), dim)])
+        pts = np.ascontiguousarray(p[rng.permutation(n_seg)], F)
+        _, idx = model_downsample(pts, 0.5)
+        assert sorted(idx) == list(range(n_seg))
+        out.append(Case("leaf_per_point_%d" % n_seg, "n_seg = n = %d: every segment thread has one run start" % n_seg,
+                        (pts, 0.5)))
+    # -- runs of equal keys that begin in one rank tile and end in the next
+    cells = [np.r_[k % 30 + 10, k // 30 + 10, np.full(max(dim - 2, 0), 30)] for k in range(300)]
+    p = in_cells(rng, cells, [10] * 300, dim)                     # 3000 points; members of leaf k at rows k, k + 300, ...
+    p = p.reshape(300, 10, dim).transpose(1, 0, 2).reshape(3000, dim)
+    pts = np.ascontiguousarray(np.concatenate([anchors(dim), p]), F)
+    info = {}
+    model_downsample(pts, 0.5, info=info)
+    straddle = [leaf for leaf in info["leaves"] if leaf.min() < TILE <= leaf.max()]
+    assert len(straddle) == 300 and all((np.diff(leaf) > 0).all() for leaf in straddle)
+    out.append(Case("runs_straddle_tiles", "every leaf has members on both sides of input row 2048", (pts, 0.5)))
+    # -- resolution <= 0: split to the level cap; only clouds whose distinct points separate within the cap
+    for n, res in ((257, 0.0), (1025, 0.0), (300, -1.0)):
+        q = rng.integers(0, 1024, (n, dim)).astype(np.float64) / 64.0      # a 1/64 lattice in a 16 m box: 10 levels
+        if res == 0.0:
+            q[n - 40:] = q[:40]                                   # exact duplicates share a leaf at any depth
+        else:
+            q = np.unique(q, axis=0)                              # (no duplicates below zero: nothing ends the oracle's
+            q = q[rng.permutation(len(q))]                        #  recursion on two coincident points there)
+        pts = np.ascontiguousarray(q, F)
+        key, levels = ds_keys(pts, res)
+        distinct = len(np.unique(pts, axis=0))
+        assert levels == LEVELS[dim] and len(np.unique(key)) == distinct          # separates within 31 (21) levels
+        out.append(Case("split_to_cap_%d_res%g" % (len(pts), res), "resolution %g: %d levels, a leaf per distinct point"
+                        % (res, LEVELS[dim]), (pts, res)))
+    return out
+
+
+# the smallest cloud that shows the 2-D level cap: the oracle's recursion separates the two tiny points
+# (level 44 or so), a 31-level key cannot.  A recorded difference, not a defect: the host test pins both answers.
+LEVEL_CAP_CLOUD = np.array([[-10, -10], [10, 10], [1e-12, 1e-12], [2e-12, 3e-12], [5, 5], [5, 5]], F)
+LEVEL_CAP_ORACLE_IDX = [0, 2, 3, 4, 1]
+LEVEL_CAP_KERNEL_IDX = [0, 2, 4, 1]
+
+
+# ---- the cases, built once -------------------------------------------------------------------------------------------------
+KINDS = {"match": (match_cases, model_match, ref_match, MATCH_VARIANTS),
+         "outlier": (outlier_cases, model_outlier, ref_outlier, OUTLIER_VARIANTS),
+         "density": (density_cases, model_density, ref_density, DENSITY_VARIANTS),
+         "downsample": (ds_cases, model_downsample, ref_downsample, DS_VARIANTS)}
+_CACHE = {}
+
+
+def cases(kind, dim):
+    """the cases of one kind and width, in order, built (and their properties asserted) on first use"""
+    if (kind, dim) not in _CACHE:
+        _CACHE[kind, dim] = KINDS[kind][0](dim)
+        names = [c.name for c in _CACHE[kind, dim]]
+        assert len(set(names)) == len(names), names
+    return _CACHE[kind, dim]
+
+
+def case(kind, dim, name):
+    return next(c for c in cases(kind, dim) if c.name == name)
+
+
+def same(kind, got, want):
+    """bit for bit, per kind: (ids, d2) / keep mask / densities / (medoids, indices)"""
+    if kind == "match" or kind == "downsample":
+        a, b = (got[1], got[0]) if kind == "match" else got
+        c, d = (want[1], want[0]) if kind == "match" else want
+        return a.shape == c.shape and np.array_equal(bits(a), bits(c)) and np.array_equal(np.asarray(b), np.asarray(d))
+    if kind == "outlier":
+        return np.array_equal(np.asarray(got, bool), np.asarray(want, bool))
+    return np.array_equal(bits(got), bits(want))
