@@ -215,7 +215,8 @@ typedef struct sfe_icp_params {
     int use_trimmed_filter;  /* TrimmedDistOutlierFilter listed (icp.yaml:14) */
     float trim_ratio;        /*   .ratio (icp.yaml:15) */
     int minimizer;           /* 0 PointToPointErrorMinimizer (icp.yaml:20), 1 2-D PointToPlane (icp.yaml:18-19, force2D: 1;
-                              * N x 2 clouds only), 2 3-D PointToPlane (force2D: 0; N x 3 clouds only, sfe_icp3_*) */
+                              * N x 2 clouds only), 2 3-D PointToPlane (force2D: 0; N x 3 clouds only, sfe_icp3_*),
+                              * 3 3-D PointToPlane {force4DOF: 1}: yaw and translation only (N x 3 clouds only, sfe_icp3_*) */
     int max_iter;            /* CounterTransformationChecker.maxIterationCount (icp.yaml:24) */
     int use_diff_checker;    /* DifferentialTransformationChecker listed (icp.yaml:25) */
     float min_diff_rot;      /*   .minDiffRotErr (icp.yaml:26) */
@@ -300,8 +301,9 @@ int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src
 /* pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (PM::ICP::compute, pcl.cpp:198-212, is dimension-generic; the
  * reference carries such clouds as Keyframe.points3D): the chain of the shipped config/icp.yaml with its point-to-point
  * minimiser (sfe_icp_params with minimizer == 0) or with PointToPlaneErrorMinimizer {force2D: 0} (minimizer == 2, with
- * 2 <= normals_knn <= 16); minimizer == 1, the 2-D form, is SFE_ERR_ARG here (3-D clouds take the point-to-point or the 3-D
- * point-to-plane minimiser), like a job slice that is empty or outside the clouds.
+ * 2 <= normals_knn <= 16) or its 4-DoF form {force4DOF: 1} (minimizer == 3, the same normals_knn bound); minimizer == 1, the
+ * 2-D form, is SFE_ERR_ARG here (3-D clouds take the point-to-point or a 3-D point-to-plane minimiser), like a job slice
+ * that is empty or outside the clouds.  Every 2-D entry point (sfe_icp_compute*) answers minimizer 2 and 3 with SFE_ERR_ARG.
  * Host pointers, the job table of sfe_icp_compute_jobs; src / tgt packed float[n][3], guesses16 / T_out16 4 x 4 row-major
  * per job.  One workgroup per job, brute-force search (sfe_icp3.hip); jobs naming the same target slice share nothing.
  * The route record of the last 2-D call stays as it is.  Rules, restated from libpointmatcher (parity unpinned, like the
@@ -331,6 +333,16 @@ int sfe_icp_compute_jobs(sfe_ctx *ctx, const sfe_icp_params *p, const float *src
  *             t = x[3..5], R = Rodrigues' rotation by |r| about r / |r| (the identity for |r| == 0); T_step = [R t]
  *             rounded to float.  A planar target (every z = 0 cloud) has parallel normals and a rank-3 A: status 5, so
  *             z = 0 input does NOT reduce to the 2-D point-to-plane result.
+ *   minimizer 3  libpointmatcher's force4DOF: 1 -- the step has yaw and translation only (roll and pitch are never estimated:
+ *             a Pose2-plus-depth state takes them from the IMU).  Normals, match, outlier filters, e and the checkers are
+ *             minimizer 2's.  Per kept pair c = p_x n_y - p_y n_x (the third component of minimizer 2's p x n),
+ *             F = (c, n_x, n_y, n_z); the fp64 sums W += 1, A += F F^T (10 distinct entries), b -= F e: 15 sums.  W == 0:
+ *             SFE_ICP_NO_POINT.  A x = b by a 4 x 4 Cholesky under the pivot rule above, else SFE_ICP_SINGULAR (T = the
+ *             guess).  gamma = x[0], R = [[cos gamma, -sin gamma, 0], [sin gamma, cos gamma, 0], [0, 0, 1]] in fp64 (no
+ *             small-angle form), t = x[1..3]; T_step = [R t] rounded to float.  So with a guess that rotates about z only,
+ *             entries (0,2), (1,2), (2,0), (2,1) of every T are exactly 0 and (2,2) is exactly 1.  Rank: a target whose
+ *             normals all have n_z = 0 leaves t_z free, one whose normals are all +-z leaves yaw, t_x and t_y free:
+ *             status 5 for both.
  *   checkers  Counter as in 2-D.  Differential: the history holds T_iter's float rotation block and translation, the
  *             identity first (a sliding window of 64 entries); per step, in fp64 from those floats, the rotation error
  *             is 2 atan2(|vec(q_i conj(q_i-1))|, |w|) with q the quaternion of the block by Eigen's branch rule (trace
@@ -441,7 +453,7 @@ int sfe_icp3_filter_clouds_dev(sfe_ctx *ctx, const sfe_icp_dpf *stages, int n_st
 /* sfe_icp3_compute_jobs with a whole chain.  The reading stages run once on every distinct source slice of the call, the
  * reference stages once on every distinct target slice, each in the cloud's own frame before any guess is applied; ICP
  * then runs on the filtered clouds: the reference mean is the filtered target's, whether the LDS tile is resident or
- * streamed is decided by the filtered target's size, and with minimizer == 2 the normals are taken once per distinct
+ * streamed is decided by the filtered target's size, and with minimizer == 2 or 3 the normals are taken once per distinct
  * filtered target.  A job whose filtered reading or reference is empty reports SFE_ICP_DPF_EMPTY with T = the guess and 0
  * iterations; the other jobs are unaffected.
  * The modules of sfe_icp_outliers run inside the loop, on the matcher's float d2 of sfe_icp3_compute_jobs:
@@ -746,7 +758,7 @@ int sfe_cloud_store3_get_points(sfe_ctx *ctx, sfe_cloud_store3 *s, const int32_t
                                 float resolution, const int64_t *stamps, int32_t *handles_out);
 /* sfe_icp3_compute_jobs over handles: pairs = n_jobs x (source handle, target handle), guesses / results 16 floats per job.
  * The same kernel on the store's pool, no point copied: T, status and iterations are bit for bit those of the host-pointer
- * call on the same clouds.  The same parameter check (minimizer 0 or 2; with 2, pairs on one target handle share its
+ * call on the same clouds.  The same parameter check (minimizer 0, 2 or 3; with 2 or 3, pairs on one target handle share its
  * normals).  A pair that names an empty or unknown cloud is
  * refused with SFE_ERR_ARG before any launch. */
 int sfe_icp3_store_compute(sfe_ctx *ctx, const sfe_icp_params *p, sfe_cloud_store3 *s, const int32_t *pairs,

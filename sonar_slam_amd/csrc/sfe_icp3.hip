@@ -1,7 +1,8 @@
 // 3-D ICP on gfx950: pcl.ICP.compute on N x 3 clouds with 4 x 4 guesses (pcl.cpp:198-212; PM::ICP is dimension-generic),
 // the module set of the shipped config/icp.yaml -- KDTreeMatcher {knn 1}, MaxDist and TrimmedDist outlier filters,
-// PointToPointErrorMinimizer (sfe_icp_params with minimizer 0) or PointToPlaneErrorMinimizer {force2D: 0} (minimizer 2),
-// Counter and Differential transformation checkers.  A chain written for N x 3 clouds adds, in the EXT build of the job kernel,
+// PointToPointErrorMinimizer (sfe_icp_params with minimizer 0), PointToPlaneErrorMinimizer {force2D: 0} (minimizer 2) or
+// PointToPlaneErrorMinimizer {force4DOF: 1} (minimizer 3: yaw and translation only), Counter and Differential transformation
+// checkers.  A chain written for N x 3 clouds adds, in the EXT build of the job kernel,
 // the MinDist and MedianDist outlier filters and the Bound checker (sfe_icp_outliers; sfe_icp3_compute_jobs_chain_ext), and in
 // front of the launch its data-point filters (sfe_icp3_dpf.hip).
 //
@@ -12,7 +13,8 @@
 //         keep = [d2 <= MaxDist^2] * [d2 <= quantile_ratio(finite d2)]
 //         T_step = the rigid motion that minimises the kept pairs' squared distances (sfe_icp3_solve.h), rounded to float
 //                  (minimizer 2: the step of the linearised point-to-plane system, sfe_icp3_plane.h; the target's surface
-//                  normals come from normals3_kernel, which runs once per distinct target in front of the job kernel)
+//                  normals come from normals3_kernel, which runs once per distinct target in front of the job kernel;
+//                  minimizer 3: the same system restricted to (yaw, t), T_step a rotation about z and a translation)
 //         T_iter = T_step * T_iter ; Counter / Differential checkers
 //   result = translate(+mean) * (T_iter * T0)
 //
@@ -20,10 +22,10 @@
 // sits in LDS as three arrays (x, y, z: 48 KiB for 4096 points, padded with +inf) for all iterations, larger targets are
 // streamed through the same tile; a lane owns up to two source points per pass and scans the tile in index order with a strict
 // '<' (lowest index on ties); nearest distances and indices go to HBM scratch; the trimmed quantile is the radix select on the
-// float bit patterns; the 16 sums (point-to-plane: 28, accumulated in two passes over the kept pairs) are reduced in fp64 in a
-// fixed order; one lane solves and runs the checkers.
-// fp32 VALU + LDS broadcast reads, no MFMA.  LDS: 48 KiB tile + 2.1 KiB sums (point-to-plane: 3.7 KiB) + 1 KiB histogram +
-// 3 KiB history = 55 KiB, so two workgroups fit the 160 KiB of a CU where the register count allows it.
+// float bit patterns; the 16 sums (point-to-plane: 28, accumulated in two passes over the kept pairs; its 4-DoF form: 15, in
+// one pass) are reduced in fp64 in a fixed order; one lane solves and runs the checkers.
+// fp32 VALU + LDS broadcast reads, no MFMA.  LDS: 48 KiB tile + 2.1 KiB sums (point-to-plane: 3.7 KiB, 4-DoF: 2 KiB) + 1 KiB
+// histogram + 3 KiB history = 55 KiB, so two workgroups fit the 160 KiB of a CU where the register count allows it.
 #include "sfe_internal.h"
 
 #include <algorithm>
@@ -45,15 +47,17 @@
 static_assert(ICP3_TCAP % ICP3_UNR == 0, "the tile is read ICP3_UNR points at a time");
 static_assert(ICP3_NSUM == 16, "point-to-point in 3-D: W, sum p, sum q, sum q p^T");
 static_assert(ICP3P_NSUM == 28, "point-to-plane in 3-D: W, the upper triangle of sum F F^T, -sum F e");
+static_assert(ICP3P4_NSUM == 15, "4-DoF point-to-plane: W, the upper triangle of the 4 x 4 sum F F^T, -sum F e");
 static_assert(ICP3P_PIVOT_RTOL == ICP_PIVOT_RTOL, "one singularity rule for the 2-D and the 3-D point-to-plane systems");
 
-#define ICP3_POINT 0 // sfe_icp_params.minimizer of the two instantiations
+#define ICP3_POINT 0 // sfe_icp_params.minimizer of the three instantiations
 #define ICP3_PLANE 2
+#define ICP3_PLANE4 3 // point-to-plane with force4DOF: 1
 #define N3_TILE 2048 // points per LDS tile of the normals kernel (24 KiB), as P3_TILE of sfe_pcl3.hip
 
 template <int MIN>
 struct Icp3Sums {
-    static constexpr int N = MIN == ICP3_PLANE ? ICP3P_NSUM : ICP3_NSUM;
+    static constexpr int N = MIN == ICP3_PLANE ? ICP3P_NSUM : MIN == ICP3_PLANE4 ? ICP3P4_NSUM : ICP3_NSUM;
 };
 
 // What the job kernel gets by value: the chain's parameters and, in the EXT builds only, the modules sfe_icp_params has no
@@ -108,7 +112,7 @@ struct Icp3Job {
     long long nrm_off;     // offset (in points) of its target's normals (point-to-plane; jobs on one target share them)
 };
 
-template <int NS> // the minimiser's sums: 16 or 28
+template <int NS> // the minimiser's sums: 16, 28 or 15
 struct Icp3SharedT {
     float tx[ICP3_TCAP], ty[ICP3_TCAP], tz[ICP3_TCAP];
     double red[ICP_WAVES * NS + NS];
@@ -123,7 +127,10 @@ static_assert(sizeof(((Icp3SharedT<ICP3_NSUM> *)nullptr)->red) >= sizeof(double)
               "block_sum<ICP3_NSUM> needs (waves + 1) x ICP3_NSUM doubles");
 static_assert(sizeof(((Icp3SharedT<ICP3P_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3P_NSUM + ICP3P_NSUM),
               "block_sum<ICP3P_NSUM> needs (waves + 1) x ICP3P_NSUM doubles");
-static_assert(sizeof(Icp3SharedT<ICP3_NSUM>) <= 64 * 1024 && sizeof(Icp3SharedT<ICP3P_NSUM>) <= 64 * 1024,
+static_assert(sizeof(((Icp3SharedT<ICP3P4_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3P4_NSUM + ICP3P4_NSUM),
+              "block_sum<ICP3P4_NSUM> needs (waves + 1) x ICP3P4_NSUM doubles");
+static_assert(sizeof(Icp3SharedT<ICP3_NSUM>) <= 64 * 1024 && sizeof(Icp3SharedT<ICP3P_NSUM>) <= 64 * 1024 &&
+                  sizeof(Icp3SharedT<ICP3P4_NSUM>) <= 64 * 1024,
               "two workgroups per CU");
 
 // load target points [base, base + n) of the job (packed float triples), centred on the mean, into the LDS tile (+inf pad)
@@ -229,7 +236,7 @@ __device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_
 // libpointmatcher's order.  Checker state: nhist / counter / iters in the lane's registers, the history in LDS.  Not inlined:
 // the fp64 Jacobi sweeps want more registers than the scan loop, and one lane runs them once per iteration.  MIN picks the
 // minimiser's solve (point-to-plane: a system that counts as singular ends the job with SFE_ICP_SINGULAR before anything is
-// composed or counted); everything behind it is the same code for both.
+// composed or counted; the 4-DoF form likewise, by its 4 x 4 system); everything behind it is the same code for all.
 // EXT: the Bound checker in its place of the list (sfe_icp_outliers.bound_order: the rule of icp_solve_and_check,
 // sfe_icp_common.h, with icp3_bound_out for the test).
 template <int MIN, int EXT>
@@ -247,6 +254,11 @@ __device__ __noinline__ void icp3_solve_and_check(const Icp3Args<EXT> &A, const 
     double R[9], t[3];
     if constexpr (MIN == ICP3_PLANE) {
         if (icp3p_solve(acc, R, t)) {
+            status = SFE_ICP_SINGULAR;
+            return;
+        }
+    } else if constexpr (MIN == ICP3_PLANE4) {
+        if (icp3p_solve4(acc, R, t)) {
             status = SFE_ICP_SINGULAR;
             return;
         }
@@ -594,6 +606,49 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
             pass(std::integral_constant<int, 0>());
             pass(std::integral_constant<int, 1>());
             block_sum_finish<NS>(acc, S.red);
+        } else if constexpr (MIN == ICP3_PLANE4) {
+            // force4DOF: F = ((p x n)_z, n), the third component of the 6-DoF form's p x n and its n; e as there.  W, the
+            // upper triangle of the 4 x 4 F F^T (10) and b (4): 15 accumulators, one pass like point-to-point's 16.
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                acc[i] = 0;
+            for (int i = tid; i < ns; i += ICP_THREADS) {
+                const int id = nn_idx[i];
+                const float d = nn_d2[i];
+                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit) &&
+                      ext_keep(d)))
+                    continue;
+                const float *s = src + 3 * (size_t)i;
+                const float sx = s[0], sy = s[1], sz = s[2];
+                const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+                const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
+                const float *nv = nrm_all + 3 * (size_t)(J.nrm_off + id);
+                const double n0 = nv[0], n1 = nv[1], n2 = nv[2];
+                double q[3];
+                if (resident) {
+                    q[0] = S.tx[id];
+                    q[1] = S.ty[id];
+                    q[2] = S.tz[id];
+                } else {
+                    const float *t = tgt + 3 * (size_t)id;
+                    q[0] = f_add(t[0], -mx);
+                    q[1] = f_add(t[1], -my);
+                    q[2] = f_add(t[2], -mz);
+                }
+                const double F[4] = {p[0] * n1 - p[1] * n0, n0, n1, n2};
+                const double e = (n0 * (p[0] - q[0]) + n1 * (p[1] - q[1])) + n2 * (p[2] - q[2]);
+                acc[0] += 1.0;
+                int k = 1;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int c = r; c < 4; ++c)
+                        acc[k++] += F[r] * F[c];
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    acc[11 + r] -= F[r] * e;
+            }
+            block_sum<NS>(acc, S.red);
         } else {
 #pragma unroll
             for (int i = 0; i < NS; ++i)
@@ -826,10 +881,10 @@ static int icp3_normals_dev(sfe_ctx *ctx, const Nrm3Target *d_targets, const Nrm
 int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
 {
     SFE_ARG(ctx, p != nullptr);
-    if (p->minimizer != ICP3_POINT && p->minimizer != ICP3_PLANE)
+    if (p->minimizer != ICP3_POINT && p->minimizer != ICP3_PLANE && p->minimizer != ICP3_PLANE4)
         return sfe_set_err(ctx, SFE_ERR_ARG, "3-D ICP runs the point-to-point error minimiser (0) and the 3-D point-to-plane one "
-                                             "(2, force2D: 0), not minimizer = %d", p->minimizer);
-    SFE_ARG(ctx, p->minimizer != ICP3_PLANE || (p->normals_knn >= 2 && p->normals_knn <= ICP_KMAX));
+                                             "(2, force2D: 0; 3, force4DOF: 1), not minimizer = %d", p->minimizer);
+    SFE_ARG(ctx, p->minimizer == ICP3_POINT || (p->normals_knn >= 2 && p->normals_knn <= ICP_KMAX));
     SFE_ARG(ctx, p->max_iter >= 1);
     SFE_ARG(ctx, !p->use_diff_checker || (p->smooth_len >= 1 && p->smooth_len < ICP_MAX_HIST));
     SFE_ARG(ctx, !p->use_trimmed_filter || (p->trim_ratio >= 0.0f && p->trim_ratio <= 1.0f));
@@ -860,7 +915,7 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outlie
                      const float *d_tgt, const int64_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
                      int32_t *status, int32_t *iters)
 {
-    const bool plane = p->minimizer == ICP3_PLANE;
+    const bool plane = p->minimizer == ICP3_PLANE || p->minimizer == ICP3_PLANE4; // the minimisers that take normals
     const bool ext = o && (o->use_min_dist || o->use_median || o->use_bound);
     const Icp3Args<0> A0{*p};
     const Icp3Args<1> A1{*p, ext ? *o : sfe_icp_outliers{}};
@@ -911,10 +966,16 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outlie
         if (int rc = icp3_normals_dev(ctx, (const Nrm3Target *)d_tg, targets.data(), n_targets, d_tgt, (float *)(d_tg + b_tg),
                                       p->normals_knn, d_nrm))
             return rc;
-        if (int rc = ext ? icp3_launch<ICP3_PLANE, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
-                                                      (float *)d_out, d_st)
-                         : icp3_launch<ICP3_PLANE, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
-                                                      (float *)d_out, d_st))
+        if (p->minimizer == ICP3_PLANE4) {
+            if (int rc = ext ? icp3_launch<ICP3_PLANE4, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
+                                                           (float *)d_out, d_st)
+                             : icp3_launch<ICP3_PLANE4, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
+                                                           (float *)d_out, d_st))
+                return rc;
+        } else if (int rc = ext ? icp3_launch<ICP3_PLANE, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2,
+                                                             d_nn_idx, (float *)d_out, d_st)
+                                : icp3_launch<ICP3_PLANE, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2,
+                                                             d_nn_idx, (float *)d_out, d_st))
             return rc;
     } else {
         if (int rc = ext ? icp3_launch<ICP3_POINT, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, nullptr, d_nn_d2, d_nn_idx,

@@ -1,7 +1,8 @@
 // The one-lane arithmetic of the 3-D point-to-plane ICP (sfe_icp3.hip, sfe_icp_params.minimizer == 2), plain C++ in fp64 so
 // that the CPU can check it (tests/host/icp3_plane_check.cpp): the surface normal of a neighbourhood (3 x 3 symmetric
 // Jacobi, eigenvector of the smallest eigenvalue), the 6 x 6 Cholesky solve of the normal equations with the 2-D
-// minimiser's singularity rule, and Rodrigues' rotation.
+// minimiser's singularity rule, and Rodrigues' rotation; for minimizer == 3 (force4DOF: 1: yaw and translation only) the
+// 4 x 4 solve under the same rule and the rotation about z.
 #pragma once
 #include <math.h>
 
@@ -14,6 +15,7 @@
 #endif
 
 #define ICP3P_NSUM 28          // W, A = sum F F^T (21: the upper triangle row by row), b = -sum F e (6)
+#define ICP3P4_NSUM 15         // force4DOF: W, A = sum F F^T (10) and b = -sum F e (4) with F = ((p x n)_z, n)
 #define ICP3P_JACOBI_SWEEPS 12 // cyclic Jacobi sweeps over the 3 x 3 matrix, at most (quadratic convergence; it ends earlier)
 #define ICP3P_PIVOT_RTOL 1e-10 // ICP_PIVOT_RTOL of the 2-D minimiser (sfe_icp_common.h)
 
@@ -185,6 +187,95 @@ SFE_ICP3P_HD void icp3p_rodrigues(const double *r, double *R)
     R[6] = v * (kx * kz) - s * ky;
     R[7] = v * (ky * kz) + s * kx;
     R[8] = 1.0 - v * (kx * kx + ky * ky);
+}
+
+// A x = b for the symmetric 4 x 4 matrix whose upper triangle is A10 (row by row: 00 01 02 03 11 12 13 22 23 33): icp3p_chol6
+// with two rows fewer, the same singularity rule.  -> 0 and x, or 1 (singular, NaN included; x untouched).
+SFE_ICP3P_HD int icp3p_chol4(const double *A10, const double *b, double *x)
+{
+    double L[4][4];
+    {
+        int k = 0;
+        SFE_ICP3P_UNROLL
+        for (int i = 0; i < 4; ++i)
+            SFE_ICP3P_UNROLL
+            for (int j = i; j < 4; ++j) {
+                L[j][i] = A10[k]; // the lower triangle holds A, then the factor
+                ++k;
+            }
+    }
+    int singular = 0;
+    SFE_ICP3P_UNROLL
+    for (int j = 0; j < 4; ++j) {
+        const double ajj = L[j][j];
+        double piv = ajj;
+        SFE_ICP3P_UNROLL
+        for (int k = 0; k < j; ++k)
+            piv -= L[j][k] * L[j][k];
+        if (j == 0 ? !(piv > 0) : !(piv > ICP3P_PIVOT_RTOL * ajj))
+            singular = 1;
+        const double ljj = sqrt(piv);
+        L[j][j] = ljj;
+        SFE_ICP3P_UNROLL
+        for (int i = j + 1; i < 4; ++i) {
+            double s = L[i][j];
+            SFE_ICP3P_UNROLL
+            for (int k = 0; k < j; ++k)
+                s -= L[i][k] * L[j][k];
+            L[i][j] = s / ljj;
+        }
+    }
+    if (singular)
+        return 1;
+    double y[4];
+    SFE_ICP3P_UNROLL
+    for (int i = 0; i < 4; ++i) {
+        double s = b[i];
+        SFE_ICP3P_UNROLL
+        for (int k = 0; k < i; ++k)
+            s -= L[i][k] * y[k];
+        y[i] = s / L[i][i];
+    }
+    SFE_ICP3P_UNROLL
+    for (int i = 3; i >= 0; --i) {
+        double s = y[i];
+        SFE_ICP3P_UNROLL
+        for (int k = i + 1; k < 4; ++k)
+            s -= L[k][i] * x[k];
+        x[i] = s / L[i][i];
+    }
+    return 0;
+}
+
+// The rotation by gamma about the z axis (row-major), libpointmatcher's AngleAxis(gamma, UnitZ): no small-angle form; the
+// third row and column are exact, and gamma == 0 gives the identity to the bit (cos 0 = 1, sin 0 = 0).
+SFE_ICP3P_HD void icp3p_rot_z(double gamma, double *R)
+{
+    const double c = cos(gamma), s = sin(gamma);
+    R[0] = c;
+    R[1] = -s;
+    R[2] = 0.0;
+    R[3] = s;
+    R[4] = c;
+    R[5] = 0.0;
+    R[6] = 0.0;
+    R[7] = 0.0;
+    R[8] = 1.0;
+}
+
+// PointToPlaneErrorMinimizer {force4DOF: 1} from the 15 fp64 sums over the kept pairs, F = ((p x n)_z, n) (acc[0] = W > 0,
+// acc[1 .. 10] = A's upper triangle, acc[11 .. 14] = b): x = A^-1 b, R = the rotation by x[0] about z, t = x[1 .. 3].
+// -> 0, or 1 where A counts as singular.
+SFE_ICP3P_HD int icp3p_solve4(const double *acc, double *R, double *t)
+{
+    double x[4];
+    if (icp3p_chol4(acc + 1, acc + 11, x))
+        return 1;
+    icp3p_rot_z(x[0], R);
+    t[0] = x[1];
+    t[1] = x[2];
+    t[2] = x[3];
+    return 0;
 }
 
 // PointToPlaneErrorMinimizer {force2D: 0} from the 28 fp64 sums over the kept pairs (acc[0] = W > 0, acc[1 .. 21] = A's upper

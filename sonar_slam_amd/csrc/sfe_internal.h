@@ -195,7 +195,7 @@ int sfe_icp_dpf_run_host(sfe_ctx *ctx, const sfe_icp_params *p, const IcpCall &c
                          const sfe_icp_dpf *rf, int n_rf, const float *d_src, const float *d_tgt, const int32_t *jobs4,
                          const float *guesses9, int n_jobs, float *T_out9, int32_t *status, int32_t *iters);
 
-// sfe_icp3.hip: the parameter check of the 3-D ICP (minimizer 0, or 2 with its normals_knn), and one 3-D ICP call on device pools of packed
+// sfe_icp3.hip: the parameter check of the 3-D ICP (minimizer 0, or 2 / 3 with their normals_knn), and one 3-D ICP call on device pools of packed
 // float triples with a validated job table (n_jobs x (src_start, n_src, tgt_start, n_tgt) in points, every cloud non-empty
 // and inside its pool), host guesses (16 floats per job) and host results; one synchronisation.  iters may be nullptr.
 // `o` (nullable; all zero: none): the MinDist / MedianDist / Bound modules, which pick the EXT build of the job kernel.

@@ -17,7 +17,9 @@ silently ignoring a filter would change the pose):
                        (each at most once, any order; the weights are the product of the filters')
     errorMinimizer     PointToPointErrorMinimizer | PointToPlaneErrorMinimizer {force2D: 1} (the 2-D form, N x 2 clouds);
                        with ``parse_icp_chain`` also PointToPlaneErrorMinimizer {force2D: 0} or without parameters
-                       (libpointmatcher's default): the 3-D form, ``minimizer = 2``, N x 3 clouds only
+                       (libpointmatcher's default): the 3-D form, ``minimizer = 2``, N x 3 clouds only; with
+                       ``parse_icp_chain(text, dims=3)`` also {force4DOF: 1} (``force2D: 0`` may stand beside it): the 3-D
+                       form solved for yaw and translation only, ``minimizer = 3``, N x 3 clouds only
     transformationCheckers  CounterTransformationChecker {maxIterationCount},
                             DifferentialTransformationChecker {minDiffRotErr, minDiffTransErr,
                                                                smoothLength};
@@ -50,7 +52,10 @@ the fixture that would pin them):
 
 Chains for N x 3 clouds: a chain says which dimension it was written for.  ``parse_icp_chain(text, dims=3)`` (and
 ``IcpChain(..., dims=3)``) makes a 3-D chain: ``dim: 2`` (the z axis) is accepted, BoundingBox uses zMin / zMax, OctreeGrid
-is the 8-way tree of ``pcl.downsample`` on N x 3 clouds, and the Bound checker measures the 3-D rotation angle.  ``pcl.ICP``
+is the 8-way tree of ``pcl.downsample`` on N x 3 clouds, the Bound checker measures the 3-D rotation angle, and
+``PointToPlaneErrorMinimizer {force4DOF: 1}`` is read (``minimizer = 3``; a 2-D chain keeps refusing ``force4DOF``, with
+either value, wherever ``force2D: 1`` does not stand beside it -- beside ``force2D: 1`` a 2-D chain examines no other
+parameter, as before, and a 3-D chain refuses ``force4DOF: 1``).  ``pcl.ICP``
 and ``store.CloudStore3.icp`` run such a chain's filters and modules on N x 3 clouds and refuse it on N x 2 clouds; a chain
 with ``dims=2`` (the default) stays what it was, refused with filters or extra modules on N x 3 clouds.  The stage rules are
 the ones above with one more coordinate (include/sonarfe.h at ``sfe_icp3_filter_clouds_dev``).
@@ -119,9 +124,10 @@ def _positive(name, key, v):
     return v
 
 
-def _params(doc, ox=None):
+def _params(doc, ox=None, dims=2):
     """the sections other than the data-point filters -> IcpParams; ``ox`` (an IcpOutliers to fill: parse_icp_chain)
-    takes the modules of _CHAIN_ONLY and the 3-D point-to-plane minimiser, without it they are refused"""
+    takes the modules of _CHAIN_ONLY and the 3-D point-to-plane minimiser, without it they are refused; ``dims`` = 3
+    (a chain for N x 3 clouds) also takes ``force4DOF``"""
     p = dict(matcher_max_dist=float("inf"), use_max_dist_filter=0, max_dist_filter=0.0,
              use_trimmed_filter=0, trim_ratio=1.0, minimizer=0, max_iter=40, use_diff_checker=0,
              min_diff_rot=0.001, min_diff_trans=0.01, smooth_len=3, normals_knn=10)
@@ -173,11 +179,16 @@ def _params(doc, ox=None):
             p["minimizer"] = 0
         elif name == "PointToPlaneErrorMinimizer":
             if int(ep.get("force2D", 0)) == 1:
+                if dims == 3 and int(ep.get("force4DOF", 0)) == 1:
+                    raise IcpConfigError("PointToPlaneErrorMinimizer: force2D: 1 and force4DOF: 1 name two different "
+                                         "systems; give one of them")
                 p["minimizer"] = 1
             elif ox is not None and int(ep.get("force2D", 0)) == 0:
-                # force4DOF, sensorStdDev, ...: a parameter that is not restated would change the pose silently
-                _known_params(name, ep, ("force2D",))
-                p["minimizer"] = 2      # libpointmatcher's default: the 3-D normal equations (N x 3 clouds)
+                # sensorStdDev, ...: a parameter that is not restated would change the pose silently.  force4DOF is a
+                # statement about the z axis (like dim: 2 and zMin / zMax): a chain written for N x 3 clouds may make it
+                _known_params(name, ep, ("force2D", "force4DOF") if dims == 3 else ("force2D",))
+                # 2: libpointmatcher's default, the 3-D normal equations; 3: their yaw-and-translation form (N x 3 clouds)
+                p["minimizer"] = 3 if int(ep.get("force4DOF", 0)) == 1 else 2
             else:
                 raise IcpConfigError("PointToPlaneErrorMinimizer needs force2D: 1 (clouds are 2-D)")
         else:
@@ -395,7 +406,7 @@ def parse_icp_chain(text, dims=2):
             raise IcpConfigError("%s: %d stages, at most %d" % (key, len(nodes), MAX_STAGES))
         sides[key] = [_stage(*_single(node, key), dims=dims) for node in nodes]
     outliers = IcpOutliers()
-    params = _params(doc, outliers)
+    params = _params(doc, outliers, dims)
     reading, reference = sides["readingDataPointsFilters"], sides["referenceDataPointsFilters"]
     if any(isinstance(s, SurfaceNormalStage) for s in reading):
         raise IcpConfigError("SurfaceNormalDataPointsFilter in readingDataPointsFilters: only the last reference stage "
@@ -404,7 +415,7 @@ def parse_icp_chain(text, dims=2):
         if isinstance(s, SurfaceNormalStage):
             if i != len(reference) - 1:
                 raise IcpConfigError("SurfaceNormalDataPointsFilter must be the last referenceDataPointsFilters stage")
-            if params.minimizer not in (1, 2):
+            if params.minimizer not in (1, 2, 3):
                 raise IcpConfigError("SurfaceNormalDataPointsFilter is only supported in a point-to-plane chain "
                                      "(PointToPlaneErrorMinimizer), where it sets the normals")
             params.normals_knn = s.knn

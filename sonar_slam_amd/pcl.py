@@ -17,9 +17,10 @@ topRows(mat_in.cols())): an N x 3 cloud goes to HIP kernels of its own (sfe_pcl3
 coordinate, an 8-way tree for ``downsample``; brute force, quadratic in the cloud size) and comes back N' x 3; ``match``
 wants both clouds of one width (RuntimeError otherwise, like libnabo).  ``ICP.compute*`` takes N x 3 clouds with 4 x 4
 guesses too (PM::ICP::compute is dimension-generic) and returns 4 x 4 transforms: the chain of the shipped icp.yaml with
-its point-to-point minimiser or with ``PointToPlaneErrorMinimizer {force2D: 0}`` (``minimizer = 2``) on a HIP kernel of its
-own (sfe_icp3.hip, brute force); mixed widths, data-point filters, the MinDist / MedianDist / Bound modules and the 2-D
-point-to-plane form (``force2D: 1``) raise NotImplementedError on 3-D input, the 3-D form on N x 2 input.
+its point-to-point minimiser, with ``PointToPlaneErrorMinimizer {force2D: 0}`` (``minimizer = 2``) or with its yaw-and-
+translation form ``{force4DOF: 1}`` (``minimizer = 3``) on a HIP kernel of its own (sfe_icp3.hip, brute force); mixed widths,
+data-point filters, the MinDist / MedianDist / Bound modules and the 2-D point-to-plane form (``force2D: 1``) raise
+NotImplementedError on 3-D input, the 3-D forms on N x 2 input.
 
 Extension (not in the reference): ``ICP.compute_batch(source, target, guesses)`` runs the
 many-guesses-one-pair loop of SLAM.compute_icp_with_cov (slam.py:346-358) in one launch.
@@ -376,6 +377,9 @@ class ICP(object):
         if self._chain().minimizer == 2:
             raise NotImplementedError("%s: PointToPlaneErrorMinimizer {force2D: 0} on N x 2 clouds: libpointmatcher would "
                                       "run its 2-D form there; say force2D: 1 (minimizer = 1) for 2-D clouds" % what)
+        if self._chain().minimizer == 3:
+            raise NotImplementedError("%s: PointToPlaneErrorMinimizer {force4DOF: 1} on N x 2 clouds: yaw and translation "
+                                      "of a 3-D cloud have no 2-D form; say force2D: 1 (minimizer = 1) for 2-D clouds" % what)
         ch = self.chain
         if ch is not None and ch.dims == 3:
             raise NotImplementedError("%s: a chain written for N x 3 clouds (dims = 3) on N x 2 clouds: its dim: 2, zMin / "
@@ -590,7 +594,7 @@ class ICP(object):
         ``sensorStdDev``; the reference cannot run that chain (icp.yaml configures no normals) and the 2-D form
         is not defined anywhere, so a point-to-plane chain raises instead of returning a made-up matrix.  No
         caller in the reference reads either (grep)."""
-        if self._chain().minimizer in (1, 2):
+        if self._chain().minimizer in (1, 2, 3):
             raise NotImplementedError("ICP.getCovariance for a point-to-plane chain: libpointmatcher's Censi estimate "
                                       "is 3-D only and the reference never runs this chain; use "
                                       "SLAM.compute_icp_with_cov's sampled covariance (slam.py:325-387)")

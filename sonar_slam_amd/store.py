@@ -467,8 +467,8 @@ class CloudStore3(object):
         -> (status int32 [n], T [n x 4 x 4] float32, iterations int32 [n]), bit for bit ``pcl.ICP.compute_jobs`` on the same
         clouds.  ``params``: an ``IcpParams`` or an ``icp_config.IcpChain``; what ``pcl.ICP`` refuses on N x 3 input
         (data-point filters, the MinDist / MedianDist / Bound modules, the 2-D point-to-plane form) is refused here in the
-        same words; ``minimizer = 2`` (PointToPlaneErrorMinimizer {force2D: 0}) runs, pairs on one target handle sharing its
-        normals.  A chain written for N x 3 clouds (``IcpChain.dims == 3``) runs whole: its reading filters once on every
+        same words; ``minimizer = 2`` (PointToPlaneErrorMinimizer {force2D: 0}) and ``minimizer = 3`` ({force4DOF: 1}: yaw
+        and translation only) run, pairs on one target handle sharing its normals.  A chain written for N x 3 clouds (``IcpChain.dims == 3``) runs whole: its reading filters once on every
         distinct source handle of the call, its reference filters once on every distinct target handle, into context
         scratch (the store is left as it was), its MinDist / MedianDist / Bound modules inside the loop; a job whose
         filters leave no point reports status 7."""

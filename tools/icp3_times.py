@@ -11,7 +11,8 @@ point, and ``pcl.surface_normals`` alone on one target of either size (a host ca
 down) with its share of the plane time of ``compute`` and of the 30 guesses, which have one distinct target each; the normals
 of the 256 targets of ``compute_pairs`` are one launch, whose share is read from a kernel trace
 (``rocprofv3 --kernel-trace -- python tools/icp3_times.py --minimizer plane``).  ``--minimizer point`` (the default) prints
-what the tool always printed.
+what the tool always printed.  ``--minimizer 4dof`` alternates the point-to-plane minimiser with its 4-DoF form (``minimizer = 3``:
+yaw and translation only) in the same way, on the same pairs, and prints the range of every series and the ratio 4dof / plane.
 """
 import argparse
 import json
@@ -63,10 +64,13 @@ def planar(T4):
 
 
 def minimizers(ctx, a, s, t, guess, guesses, big, out):
-    """the three 3-D shapes with the point-to-plane minimiser, alone or alternated with point-to-point"""
+    """the three 3-D shapes with the point-to-plane minimiser, alone or alternated with point-to-point, or (``4dof``)
+    alternated with its 4-DoF form"""
     kinds = {"point": 0, "plane": 2}
     if a.minimizer == "plane":
         kinds.pop("point")
+    elif a.minimizer == "4dof":
+        kinds = {"plane": 2, "4dof": 3}
     icps = {}
     for k, m in kinds.items():
         icps[k] = pcl.ICP(ctx)
@@ -102,6 +106,9 @@ def minimizers(ctx, a, s, t, guess, guesses, big, out):
                             }  # (the pairs' normals run as one launch over all targets: their share is read from a kernel trace)
     if "point" in kinds:
         out["plane_over_point"] = {n: round(ms[n] / out["ms"]["point"][n], 3) for n in ms}
+    if "4dof" in kinds:
+        out["range_ms"] = {k: {n: [min(v), max(v)] for n, v in out["series"][k].items()} for k in kinds}
+        out["4dof_over_plane"] = {n: round(out["ms"]["4dof"][n] / ms[n], 3) for n in ms}
     return out
 
 
@@ -110,7 +117,7 @@ def main():
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--pairs", type=int, default=256)
     ap.add_argument("--n", type=int, default=5000)
-    ap.add_argument("--minimizer", choices=("point", "plane", "both"), default="point")
+    ap.add_argument("--minimizer", choices=("point", "plane", "both", "4dof"), default="point")
     a = ap.parse_args()
     ctx = _lib.default_context()
     icp = pcl.ICP(ctx)
