@@ -36,6 +36,7 @@
 #include <utility>
 
 #include "sfe_icp_common.h"
+#include "sfe_points3.h"
 #include "sfe_icp3_chain.h"
 #include "sfe_icp3_plane.h"
 #include "sfe_icp3_solve.h"
@@ -53,7 +54,7 @@ static_assert(ICP3P_PIVOT_RTOL == ICP_PIVOT_RTOL, "one singularity rule for the 
 #define ICP3_POINT 0 // sfe_icp_params.minimizer of the three instantiations
 #define ICP3_PLANE 2
 #define ICP3_PLANE4 3 // point-to-plane with force4DOF: 1
-#define N3_TILE 2048 // points per LDS tile of the normals kernel (24 KiB), as P3_TILE of sfe_pcl3.hip
+#define N3_TILE 2048 // points per LDS tile of the normals kernel (24 KiB), as P3_TILE of sfe_points3.h
 
 template <int MIN>
 struct Icp3Sums {
@@ -93,16 +94,11 @@ __device__ __forceinline__ void mat4_mul(const float *a, const float *b, float *
         c[i] = r[i];
 }
 
-// one row of a 4 x 4 transform on a point: ((a x + b y) + c z) + d, every product and sum rounded to float
+// one row of a 4 x 4 transform on a point: ((a x + b y) + c z) + d, every product and sum rounded to float.  Not s3_move of
+// sfe_store3.hip: that is numpy's sgemm rule with fused products, this is the ICP chain's rule (the 2-D kernel's, no fma).
 __device__ __forceinline__ float affine3(const float *row, float x, float y, float z)
 {
     return f_add(f_add(f_add(f_mul(row[0], x), f_mul(row[1], y)), f_mul(row[2], z)), row[3]);
-}
-
-__device__ __forceinline__ float dist3(float px, float py, float pz, float tx, float ty, float tz)
-{
-    const float dx = f_add(px, -tx), dy = f_add(py, -ty), dz = f_add(pz, -tz);
-    return f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
 }
 
 struct Icp3Job {
@@ -167,10 +163,10 @@ __device__ __forceinline__ void nn3_scan_tile(const Icp3Shared &S, int tn, int t
         const float4 z4 = *reinterpret_cast<const float4 *>(&S.tz[j]);
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
-            const float d0 = dist3(px[k], py[k], pz[k], x4.x, y4.x, z4.x);
-            const float d1 = dist3(px[k], py[k], pz[k], x4.y, y4.y, z4.y);
-            const float d2 = dist3(px[k], py[k], pz[k], x4.z, y4.z, z4.z);
-            const float d3 = dist3(px[k], py[k], pz[k], x4.w, y4.w, z4.w);
+            const float d0 = p3_dist2(px[k], py[k], pz[k], x4.x, y4.x, z4.x);
+            const float d1 = p3_dist2(px[k], py[k], pz[k], x4.y, y4.y, z4.y);
+            const float d2 = p3_dist2(px[k], py[k], pz[k], x4.z, y4.z, z4.z);
+            const float d3 = p3_dist2(px[k], py[k], pz[k], x4.w, y4.w, z4.w);
             if (d0 < best[k]) {
                 best[k] = d0;
                 bi[k] = tb + j;
@@ -792,7 +788,7 @@ __global__ __launch_bounds__(256) void normals3_kernel(const Nrm3Target *__restr
         __syncthreads();
         if (act) {
             for (int j = 0; j < tn; ++j) { // every lane reads the same LDS words: a broadcast
-                const float d = dist3(qx, qy, qz, s_t[3 * j], s_t[3 * j + 1], s_t[3 * j + 2]);
+                const float d = p3_dist2(qx, qy, qz, s_t[3 * j], s_t[3 * j + 1], s_t[3 * j + 2]);
                 if (d < kth) { // kth = the list's K-th distance (inf until it is full); NaN and inf: never
                     // position = number of kept entries <= d (ascending index: equal distances keep the earlier point)
                     int p = 0;

@@ -11,10 +11,10 @@
 //     is ONE pass, one workgroup per cloud, the stages evaluated together per point.  The order of the kept points comes
 //     from a ballot / popcount prefix inside each wave and a scan of the wave totals across the workgroup, carried from
 //     chunk to chunk: no atomic decides a position.
-//   * OctreeGridDataPointsFilter {samplingMethod: 3}: the multi-job downsample of the 3-D keyframe store (sfe_octree3.h:
-//     bounding box -> keys -> ranks -> segments -> medoids, one launch per step for all clouds), which is sfe_downsample3
-//     point for point; the tree is cut at 21 levels, so no cloud is ever refused.
-//   * the end: the sizes' exclusive sum and the placement back to back, the store's offsets / place kernels.
+//   * OctreeGridDataPointsFilter {samplingMethod: 3}: the multi-job downsample of sfe_octree3.hip (bounding box -> keys
+//     -> ranks -> segments -> medoids, one launch per step for all clouds), the kernels sfe_downsample3 runs with one job;
+//     the tree is cut at 21 levels, so no cloud is ever refused.
+//   * the end: the sizes' exclusive sum and the placement back to back, the same file's offsets / place kernels.
 //
 // Scratch slots 64-70, shared with the 2-D pass of sfe_icp_dpf.hip (a call is one or the other, both end synchronised).
 #include "sfe_icp3_chain.h"

@@ -1,11 +1,14 @@
-// The multi-job 3-D downsample of sfe_store3.hip (pcl.downsample / sfe_downsample3 on many clouds per launch) as two
-// enqueue-only steps, for the callers that run it: CloudStore3.get_points and the octree stage of a 3-D ICP chain
-// (sfe_icp3_dpf.hip).  The kernels are sfe_store3.hip's; this header only names what a caller hands them.
+// The 3-D octree downsample (sfe_octree3.hip: pcl.downsample on N x 3, many clouds per launch) as enqueue-only steps.  Its
+// callers: pcl.downsample on N x 3 (sfe_downsample3 in sfe_pcl3.hip, a one-job call), CloudStore3.get_points (sfe_store3.hip)
+// and the octree stage of a 3-D ICP chain (sfe_icp3_dpf.hip).  This header names what a caller hands the kernels.
 #pragma once
 #include "sfe_internal.h"
 #include "sfe_store3_slots.h"
 
-struct S3Header { // Ds3Header: a job's tree and its leaf count
+#define S3_MAX_LEVELS 21  // 3 key bits per level in a 64-bit key; a deeper tree is cut here
+#define S3_MAX_JOBS 65535 // blockIdx.y
+
+struct S3Header { // a job's tree and its leaf count
     float cx, cy, cz, radius;
     int levels;
     int n_seg;
@@ -21,11 +24,11 @@ struct S3OctreeBufs {
     int *midx;                        // [total] or nullptr: the medoids' indices in their concatenations
 };
 
-// std::to_string(float) and back (pcl.cpp:134), as sfe_downsample3 takes its resolution
+// std::to_string(float) and back (pcl.cpp:134): the leaf size the reference's octree is built with
 float sfe_s3_max_size(float resolution);
 
-// bounding box -> keys -> ranks -> segments -> medoids of the jobs d_jobs[0 .. n_jobs) (n_jobs <= 65535) over d_cat; job j
-// reads its tot points at d_jobs[j].cat, tot read ON THE DEVICE (max_tot: an upper bound known to the host, sizes the
+// bounding box -> keys -> ranks -> segments -> medoids of the jobs d_jobs[0 .. n_jobs) (n_jobs <= S3_MAX_JOBS) over d_cat; job
+// j reads its tot points at d_jobs[j].cat, tot read ON THE DEVICE (max_tot: an upper bound known to the host, sizes the
 // grids), and leaves hdr[j].n_seg medoids.  One launch per step.
 int sfe_s3_octree_enqueue(sfe_ctx *ctx, const float *d_cat, const S3Job *d_jobs, int n_jobs, int max_tot, float max_size,
                           const S3OctreeBufs &b);
@@ -34,6 +37,6 @@ int sfe_s3_octree_enqueue(sfe_ctx *ctx, const float *d_cat, const S3Job *d_jobs,
 // (all n_jobs jobs, one workgroup) ...
 int sfe_s3_offsets_enqueue(sfe_ctx *ctx, const S3Job *d_jobs, const S3Header *d_hdr, int n_jobs, int raw, int *d_cnt,
                            long long *d_off);
-// ... and the jobs' points from their `cat` in d_from to pool[top + d_off[j] ..), one behind the other (n_jobs <= 65535)
+// ... and the jobs' points from their `cat` in d_from to pool[top + d_off[j] ..), one behind the other (n_jobs <= S3_MAX_JOBS)
 int sfe_s3_place_enqueue(sfe_ctx *ctx, const float *d_from, const S3Job *d_jobs, int n_jobs, int max_tot, const int *d_cnt,
                          const long long *d_off, long long top, float *pool);

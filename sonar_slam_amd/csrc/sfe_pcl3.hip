@@ -2,44 +2,20 @@
 // (pcl.cpp:54-74, 76-88, 128-174 are dimension-generic: fromEigen labels a z row when mat.cols() == 3 and every function
 // returns topRows(mat_in.cols())).  The reference carries such clouds (Keyframe.points3D, slam_objects.py:101-106).
 //
-// These are the 3-D counterparts of match_kernel / match_knn_kernel / knn_density_kernel / radius_count_kernel
-// (sfe_icp.hip) and of the rank-counting downsample chain (sfe_downsample.hip), written as kernels of their own: the 2-D
-// kernels and their launchers are untouched.  The rules are the 2-D rules with one more coordinate:
-//   d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), no fma; a z of 0 on both sides adds +0 and leaves the 2-D value;
-//   the octree is 8-way: child bit0 = x > cx, bit1 = y > cy, bit2 = z > cz, 3 key bits per level, at most 21 levels in
-//   a 64-bit key (the 2-D chain: 2 bits, 31 levels); a deeper tree is cut at the cap.
+// match, k-NN, density and radius count are the 3-D counterparts of match_kernel / match_knn_kernel / knn_density_kernel /
+// radius_count_kernel (sfe_icp.hip), written as kernels of their own: the 2-D kernels and their launchers are untouched.
+// The rules are the 2-D rules with one more coordinate (p3_dist2 of sfe_points3.h).  downsample is a
+// one-job call of the octree chain of sfe_octree3.hip.
 // Points are packed float triples (12-byte stride, a contiguous N x 3 float32 array): no padding is asked of the caller,
 // and nothing is read as float4.  The reference cloud / the point tile goes through LDS, 2048 points (24 KiB) at a time;
 // all lanes read the same LDS word in the inner loop (a broadcast).  Every kernel is brute force and quadratic in the
-// cloud size, like its 2-D counterpart.
-#include "sfe_icp_common.h"
+// cloud size, like its 2-D counterpart.  The largest cloud is S3_MAX_POINTS: its float offsets (3 n) and [knn x n] tables
+// stay inside the kernels' int arithmetic.
+#include "sfe_octree3.h"
+#include "sfe_points3.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-
-#define P3_TILE 2048
-#define DS3_MAX_LEVELS 21
-
-struct Ds3Header {
-    float cx, cy, cz, radius;
-    int levels;
-    int n_seg;
-};
-
-__device__ __forceinline__ float dist2_3(float px, float py, float pz, float tx, float ty, float tz)
-{
-    const float dx = f_add(px, -tx), dy = f_add(py, -ty), dz = f_add(pz, -tz);
-    return f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
-}
-
-// points [tb, tb + tn) of a packed cloud -> s[0 .. 3 tn), by all 256 threads (consecutive floats: coalesced)
-__device__ __forceinline__ void p3_stage(float *s, const float *__restrict__ pts, int tb, int tn)
-{
-    const float *src = pts + 3 * (size_t)tb;
-    for (int j = threadIdx.x; j < 3 * tn; j += 256)
-        s[j] = src[j];
-}
+#include <vector>
 
 // pcl.match, knn = 1: one lane per query, the reference tiled through LDS; ties -> the lowest reference index
 __global__ __launch_bounds__(256) void match3_kernel(const float *__restrict__ ref, int nref, const float *__restrict__ in,
@@ -53,21 +29,9 @@ __global__ __launch_bounds__(256) void match3_kernel(const float *__restrict__ r
         py = in[3 * (size_t)i + 1];
         pz = in[3 * (size_t)i + 2];
     }
-    float best = INFINITY;
-    int bi = -1;
-    for (int tb = 0; tb < nref; tb += P3_TILE) {
-        const int tn = min(P3_TILE, nref - tb);
-        __syncthreads();
-        p3_stage(s_ref, ref, tb, tn);
-        __syncthreads();
-        for (int j = 0; j < tn; ++j) {
-            const float d = dist2_3(px, py, pz, s_ref[3 * j], s_ref[3 * j + 1], s_ref[3 * j + 2]);
-            if (d < best) {
-                best = d;
-                bi = tb + j;
-            }
-        }
-    }
+    float best;
+    int bi;
+    p3_nearest(s_ref, ref, nref, px, py, pz, best, bi);
     if (i < nin) {
         if (bi < 0 || !(best <= r2)) {
             bi = -1;
@@ -103,7 +67,7 @@ __global__ __launch_bounds__(256) void match_knn3_kernel(const float *__restrict
             p3_stage(s_ref, ref, tb, tn);
             __syncthreads();
             for (int j = 0; j < tn; ++j) {
-                const float d = dist2_3(px, py, pz, s_ref[3 * j], s_ref[3 * j + 1], s_ref[3 * j + 2]);
+                const float d = p3_dist2(px, py, pz, s_ref[3 * j], s_ref[3 * j + 1], s_ref[3 * j + 2]);
                 const bool after = d > prev_d || (d == prev_d && tb + j > prev_i); // NaN: never
                 if (after && d < best) { // ascending index: the first point attaining the minimum wins
                     best = d;
@@ -150,7 +114,7 @@ __global__ __launch_bounds__(256) void knn_density3_kernel(const float *__restri
         const int id = ids[(size_t)j * n + i];
         if (id >= 0) {
             const float *q = pts + 3 * (size_t)id;
-            rmax = fmaxf(rmax, sqrtf(dist2_3(q[0], q[1], q[2], mx, my, mz)));
+            rmax = fmaxf(rmax, sqrtf(p3_dist2(q[0], q[1], q[2], mx, my, mz)));
         }
     }
     const double r = (double)rmax;
@@ -177,190 +141,11 @@ __global__ __launch_bounds__(256) void radius_count3_kernel(const float *__restr
         p3_stage(s_p, pts, tb, tn);
         __syncthreads();
         for (int j = 0; j < tn; ++j)
-            cnt += dist2_3(px, py, pz, s_p[3 * j], s_p[3 * j + 1], s_p[3 * j + 2]) <= r2;
+            cnt += p3_dist2(px, py, pz, s_p[3 * j], s_p[3 * j + 1], s_p[3 * j + 2]) <= r2;
     }
     if (i < n)
         keep[i] = cnt > min_points;
 }
-
-// ---------------------------------------------------------------------------------------------
-// pcl.downsample on N x 3: the chain of sfe_downsample.hip on an 8-way tree (one cloud per call)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(1024) void ds3_bbox_kernel(const float *__restrict__ pts, int n, float max_size,
-                                                        Ds3Header *__restrict__ hdr)
-{
-    __shared__ float s_mn[3][16], s_mx[3][16];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = threadIdx.x; i < n; i += 1024) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = pts[3 * (size_t)i + a];
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_down(mn[a], d));
-            mx[a] = fmaxf(mx[a], __shfl_down(mx[a], d));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            s_mn[a][threadIdx.x >> 6] = mn[a];
-            s_mx[a][threadIdx.x >> 6] = mx[a];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float c[3], radius = 0.0f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            for (int w = 1; w < 16; ++w) {
-                mn[a] = fminf(mn[a], s_mn[a][w]);
-                mx[a] = fmaxf(mx[a], s_mx[a][w]);
-            }
-            // Octree::build: centre = min + radii*0.5, radius = max(radii)*0.5
-            const float ext = mx[a] - mn[a];
-            c[a] = mn[a] + ext * 0.5f;
-            if (a == 0 || radius < ext)
-                radius = ext;
-        }
-        radius *= 0.5f;
-        hdr->cx = c[0];
-        hdr->cy = c[1];
-        hdr->cz = c[2];
-        hdr->radius = radius;
-        int L = 0;
-        float r = radius;
-        while (!((double)r * 2.0 <= (double)max_size) && L < DS3_MAX_LEVELS) {
-            r *= 0.5f;
-            ++L;
-        }
-        hdr->levels = L;
-        hdr->n_seg = 0;
-    }
-}
-
-__global__ __launch_bounds__(256) void ds3_key_kernel(const float *__restrict__ pts, int n, const Ds3Header *__restrict__ hdr,
-                                                      unsigned long long *__restrict__ keys)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n)
-        return;
-    const float px = pts[3 * (size_t)i], py = pts[3 * (size_t)i + 1], pz = pts[3 * (size_t)i + 2];
-    float cx = hdr->cx, cy = hdr->cy, cz = hdr->cz, r = hdr->radius;
-    const int L = hdr->levels;
-    unsigned long long key = 0;
-    for (int l = 0; l < L; ++l) {
-        const unsigned bx = px > cx, by = py > cy, bz = pz > cz; // Octree::idx: bit i = pt(i) > centre(i)
-        key = (key << 3) | (bx | (by << 1) | (bz << 2));
-        const float hr = r * 0.5f;
-        cx = cx + (bx ? hr : -hr);
-        cy = cy + (by ? hr : -hr);
-        cz = cz + (bz ? hr : -hr);
-        r = hr;
-    }
-    keys[i] = key;
-}
-
-// rank of (key_i, i) among all points = position in the stable sort; scatter index and key there
-__global__ __launch_bounds__(256) void ds3_rank_kernel(const unsigned long long *__restrict__ keys, int n,
-                                                       int *__restrict__ sorted_idx,
-                                                       unsigned long long *__restrict__ sorted_key)
-{
-    __shared__ unsigned long long s_k[P3_TILE];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long ki = (i < n) ? keys[i] : 0ull;
-    int rank = 0;
-    for (int tb = 0; tb < n; tb += P3_TILE) {
-        const int tn = min(P3_TILE, n - tb);
-        __syncthreads();
-        for (int q = threadIdx.x; q < tn; q += 256)
-            s_k[q] = keys[tb + q];
-        __syncthreads();
-        for (int q = 0; q < tn; ++q) {
-            const unsigned long long kj = s_k[q];
-            rank += (kj < ki) || (kj == ki && tb + q < i);
-        }
-    }
-    if (i < n) { // (rank < n: it counts points other than i)
-        sorted_idx[rank] = i;
-        sorted_key[rank] = ki;
-    }
-}
-
-// one workgroup: the first position of every run of equal keys, listed in order, + a sentinel
-__global__ __launch_bounds__(1024) void ds3_segment_kernel(const unsigned long long *__restrict__ sorted_key, int n,
-                                                           int *__restrict__ seg_start /* [n + 1] */,
-                                                           Ds3Header *__restrict__ hdr)
-{
-    __shared__ int s_part[1024];
-    const int per = (n + 1023) / 1024;
-    const int b = (int)min((long long)threadIdx.x * per, (long long)n), e = min(b + per, n);
-    int c = 0;
-    for (int r = b; r < e; ++r)
-        c += (r == 0) || (sorted_key[r] != sorted_key[r - 1]);
-    s_part[threadIdx.x] = c;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int s = (threadIdx.x == 0) ? 0 : s_part[threadIdx.x - 1];
-    for (int r = b; r < e; ++r)
-        if ((r == 0) || (sorted_key[r] != sorted_key[r - 1]))
-            seg_start[s++] = r;
-    if (threadIdx.x == 1023) {
-        hdr->n_seg = s_part[1023];
-        seg_start[s_part[1023]] = n; // sentinel (n_seg <= n)
-    }
-}
-
-// one thread per leaf: float centroid in input order, the first point at the minimum distance from it
-__global__ __launch_bounds__(256) void ds3_medoid_kernel(const float *__restrict__ pts, const int *__restrict__ sorted_idx,
-                                                         const int *__restrict__ seg_start,
-                                                         const Ds3Header *__restrict__ hdr, float *__restrict__ out,
-                                                         int *__restrict__ out_idx)
-{
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= hdr->n_seg)
-        return;
-    const int r0 = seg_start[s], r1 = seg_start[s + 1];
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    for (int r = r0; r < r1; ++r) {
-        const float *q = pts + 3 * (size_t)sorted_idx[r];
-        sx = f_add(sx, q[0]);
-        sy = f_add(sy, q[1]);
-        sz = f_add(sz, q[2]);
-    }
-    const float cnt = (float)(r1 - r0);
-    sx = __fdiv_rn(sx, cnt);
-    sy = __fdiv_rn(sy, cnt);
-    sz = __fdiv_rn(sz, cnt);
-    float best = 3.402823466e+38f;
-    int bi = sorted_idx[r0];
-    for (int r = r0; r < r1; ++r) {
-        const int id = sorted_idx[r];
-        const float *q = pts + 3 * (size_t)id;
-        // sqrtf: the correctly rounded sequence (ds_medoid_kernel says why)
-        const float d = sqrtf(dist2_3(q[0], q[1], q[2], sx, sy, sz));
-        if (d < best) {
-            best = d;
-            bi = id;
-        }
-    }
-    const float *q = pts + 3 * (size_t)bi;
-    out[3 * (size_t)s] = q[0];
-    out[3 * (size_t)s + 1] = q[1];
-    out[3 * (size_t)s + 2] = q[2];
-    out_idx[s] = bi;
-}
-
-// the largest cloud whose float offsets (3 n) and [knn x n] tables stay inside the kernels' int arithmetic
-#define P3_MAX_POINTS (1 << 28)
 
 extern "C" {
 
@@ -375,7 +160,7 @@ int sfe_match_knn3(sfe_ctx *ctx, const float *ref, int n_ref, const float *in, i
     if (int rc = sfe_use(ctx))
         return rc;
     SFE_ARG(ctx, n_ref >= 0 && n_in >= 0 && knn >= 1 && (n_in == 0 || (in && ids && d2)) && (n_ref == 0 || ref));
-    SFE_ARG(ctx, n_ref <= P3_MAX_POINTS && n_in <= P3_MAX_POINTS);
+    SFE_ARG(ctx, n_ref <= S3_MAX_POINTS && n_in <= S3_MAX_POINTS);
     if (n_in == 0)
         return 0;
     const size_t b_ref = sizeof(float) * 3 * (size_t)n_ref, b_in = sizeof(float) * 3 * (size_t)n_in;
@@ -407,7 +192,7 @@ int sfe_knn_density3(sfe_ctx *ctx, const float *pts, int n, int knn, float *dens
 {
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, n >= 0 && n <= P3_MAX_POINTS && knn >= 1 && (n == 0 || (pts && dens_out)));
+    SFE_ARG(ctx, n >= 0 && n <= S3_MAX_POINTS && knn >= 1 && (n == 0 || (pts && dens_out)));
     if (n == 0)
         return 0;
     if (knn > n) // libnabo: "Requesting more points than available in cloud"
@@ -433,7 +218,7 @@ int sfe_remove_outlier3(sfe_ctx *ctx, const float *pts, int n, double radius, in
 {
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, n >= 0 && n <= P3_MAX_POINTS && n_out && (n == 0 || (pts && out)));
+    SFE_ARG(ctx, n >= 0 && n <= S3_MAX_POINTS && n_out && (n == 0 || (pts && out)));
     *n_out = 0;
     if (n == 0)
         return 0;
@@ -464,13 +249,12 @@ int sfe_downsample3(sfe_ctx *ctx, const float *pts, int n, float resolution, flo
 {
     if (int rc = sfe_use(ctx))
         return rc;
-    SFE_ARG(ctx, n >= 0 && n <= P3_MAX_POINTS && n_out && (n == 0 || (pts && out && out_idx)));
+    SFE_ARG(ctx, n >= 0 && n <= S3_MAX_POINTS && n_out && (n == 0 || (pts && out && out_idx)));
     *n_out = 0;
     if (n == 0)
         return 0; // pcl.cpp:130-131
-    char buf[64];
-    snprintf(buf, sizeof buf, "%f", (double)resolution); // pcl.cpp:134: std::to_string(float)
-    const float max_size = strtof(buf, nullptr);
+    // one job of the octree chain (sfe_octree3.hip): the cloud is its own concatenation
+    const float max_size = sfe_s3_max_size(resolution);
     const size_t b_pts = sizeof(float) * 3 * (size_t)n;
     float *d_pts = (float *)sfe_scratch(ctx, 0, b_pts);
     unsigned long long *d_keys = (unsigned long long *)sfe_scratch(ctx, 1, 8 * (size_t)n);
@@ -479,22 +263,18 @@ int sfe_downsample3(sfe_ctx *ctx, const float *pts, int n, float resolution, flo
     int *d_seg = (int *)sfe_scratch(ctx, 4, 4 * ((size_t)n + 1));
     float *d_out = (float *)sfe_scratch(ctx, 5, b_pts);
     int *d_oidx = (int *)sfe_scratch(ctx, 6, 4 * (size_t)n);
-    Ds3Header *d_hdr = (Ds3Header *)sfe_scratch(ctx, 7, sizeof(Ds3Header));
-    if (!d_pts || !d_keys || !d_skeys || !d_sidx || !d_seg || !d_out || !d_oidx || !d_hdr)
+    S3Header *d_hdr = (S3Header *)sfe_scratch(ctx, 7, sizeof(S3Header));
+    S3Job *d_job = (S3Job *)sfe_scratch(ctx, 8, sizeof(S3Job));
+    S3Job *h_job = (S3Job *)sfe_pinned_io(ctx, 2, sizeof(S3Job)); // (pinned and the context's: no copy from dead memory)
+    if (!d_pts || !d_keys || !d_skeys || !d_sidx || !d_seg || !d_out || !d_oidx || !d_hdr || !d_job || !h_job)
         return SFE_ERR_HIP;
+    *h_job = S3Job{0, n, 0, 0, 0};
+    SFE_HIP(ctx, hipMemcpyAsync(d_job, h_job, sizeof(S3Job), hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_pts, pts, b_pts, hipMemcpyHostToDevice, ctx->stream));
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(ds3_bbox_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const float *)d_pts, n, max_size, d_hdr);
-    hipLaunchKernelGGL(ds3_key_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)d_pts, n, (const Ds3Header *)d_hdr,
-                       d_keys);
-    hipLaunchKernelGGL(ds3_rank_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const unsigned long long *)d_keys, n, d_sidx,
-                       d_skeys);
-    hipLaunchKernelGGL(ds3_segment_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)d_skeys, n, d_seg,
-                       d_hdr);
-    hipLaunchKernelGGL(ds3_medoid_kernel, dim3(nb), dim3(256), 0, ctx->stream, (const float *)d_pts, (const int *)d_sidx,
-                       (const int *)d_seg, (const Ds3Header *)d_hdr, d_out, d_oidx);
-    SFE_LAUNCH_CHECK(ctx);
-    Ds3Header h;
+    if (int rc = sfe_s3_octree_enqueue(ctx, d_pts, d_job, 1, n, max_size,
+                                       S3OctreeBufs{d_keys, d_skeys, d_sidx, d_seg, d_hdr, d_out, d_oidx}))
+        return rc;
+    S3Header h;
     SFE_HIP(ctx, hipMemcpyAsync(&h, d_hdr, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const int m = h.n_seg;

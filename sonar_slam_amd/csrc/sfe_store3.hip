@@ -13,13 +13,10 @@
 //   table needs no device copy and nothing can turn out not to fit after the fact.  Every kernel gets the offsets it needs in
 //   a small per-call job table.  Clouds are named by handle (slot index); slots are released in stack order.
 //
-//   get_points   n_jobs targets per call, every stage ONE launch with the job in blockIdx.y (or .x for the one-workgroup
-//                stages): transform + gather -> bounding box -> keys -> ranks -> segments -> medoids -> offsets -> place.
-//                The downsample stages are the kernels of sfe_downsample3 (sfe_pcl3.hip: 8-way tree, rank-counting sort,
-//                float centroid, first point at the minimum distance) with a job table in front, expression for expression,
-//                so that a job's result is bit for bit pcl.downsample of its concatenation.  The results are placed one
-//                behind the other at the pool's fill level (the offsets kernel scans the jobs' leaf counts on the device);
-//                the host synchronises once, for the counts.
+//   get_points   n_jobs targets per call, every stage ONE launch with the job in blockIdx.y: transform + gather here, then
+//                the octree downsample, the offsets and the placement of sfe_octree3.hip (the kernels pcl.downsample on
+//                N x 3 runs, so a job's result is bit for bit pcl.downsample of its concatenation).  The results are placed
+//                one behind the other at the pool's fill level; the host synchronises once, for the counts.
 //   icp          icp3_job_kernel (sfe_icp3.hip) on the pool, its job table built from the slot table: no point is copied.
 //   overlap      one lane per moved source point, the target tiled through LDS (2048 points), integer counts.
 //
@@ -34,9 +31,9 @@
 //   fov_select        s3_fov_kernel: one lane per point, the job's frames looped; ballot + one atomic per wave for the two
 //                     counters, integer atomics into the job's histogram.
 //   compact_selected  s3_compact_kernel: one workgroup per cloud, chunks of 1024 with a running base, order kept; the sizes
-//                     go through s3_offsets_kernel and the results through the place kernels, as get_points' do.
-//   match_keys        s3_match_keys_kernel: the overlap kernel's tiling with the nearest target's index kept (strict `<` in
-//                     ascending index: ties go to the lowest index, across tile borders too) and the histogram of its key.
+//                     and the results go through the offsets and place steps, as get_points' do.
+//   match_keys        s3_match_keys_kernel: the nearest target of every moved source point (p3_nearest, the scan of
+//                     match3_kernel) and the histogram of its key.
 //   Every keyed call takes n_jobs jobs and runs one launch per stage for all of them; every call that creates slots asks
 //   Store3Slots::fits for an upper bound first.  All counts are integers: no result depends on the order of the atomics; the
 //   histogram and counter scratch is zeroed on the stream per call.
@@ -44,21 +41,14 @@
 // The transform rule is numpy's for float32 arrays (sgemm, then the broadcast addition), per output coordinate i
 //     fl( fma(p2, Hi2, fma(p1, Hi1, fl(p0 * Hi0))) + Hi3 )
 // -- the 3-term form of SFE_STORE_F32_POINTS in sfe_store.hip -- written with explicit intrinsics.
-#include "sfe_icp_common.h"
 #include "sfe_octree3.h"
-#include "sfe_store3_slots.h"
+#include "sfe_points3.h"
 
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <vector>
-
-#define S3_TILE 2048       // points per LDS tile (24 KiB), as P3_TILE of sfe_pcl3.hip
-#define S3_MAX_LEVELS 21   // DS3_MAX_LEVELS
-#define S3_MAX_JOBS 65535  // blockIdx.y
 
 struct sfe_cloud_store3 {
     sfe_ctx *ctx = nullptr;
@@ -85,13 +75,8 @@ struct S3FovJob { // one keyed cloud against frames [f0, f1)
     int pad;
 };
 
-__device__ __forceinline__ float s3_dist2(float px, float py, float pz, float tx, float ty, float tz)
-{
-    const float dx = f_add(px, -tx), dy = f_add(py, -ty), dz = f_add(pz, -tz);
-    return f_add(f_add(f_mul(dx, dx), f_mul(dy, dy)), f_mul(dz, dz));
-}
-
-// row i of the transform on a point: numpy's float32 `p.dot(R.T) + t`
+// row i of the transform on a point: numpy's float32 `p.dot(R.T) + t`.  Not affine3 of sfe_icp3.hip: numpy's sgemm fuses
+// the second and third product into the sum, the ICP kernel's rule rounds every product.
 __device__ __forceinline__ float s3_move(const float *row, float p0, float p1, float p2)
 {
     return f_add(__fmaf_rn(p2, row[2], __fmaf_rn(p1, row[1], f_mul(p0, row[0]))), row[3]);
@@ -124,215 +109,6 @@ __global__ __launch_bounds__(256) void s3_gather_kernel(const float *__restrict_
         cat_key[J.cat + i] = seg_key[J.seg0 + k];
 }
 
-// ds3_bbox_kernel per job (one workgroup each): Octree::build's centre, radius and depth
-__global__ __launch_bounds__(1024) void s3_bbox_kernel(const float *__restrict__ cat, const S3Job *__restrict__ jobs,
-                                                       float max_size, S3Header *__restrict__ hdrs)
-{
-    __shared__ float s_mn[3][16], s_mx[3][16];
-    const S3Job J = jobs[blockIdx.x];
-    const int n = J.tot;
-    const float *__restrict__ pts = cat + 3 * (size_t)J.cat;
-    S3Header *hdr = hdrs + blockIdx.x;
-    if (n == 0) { // (uniform) an empty job: no leaf
-        if (threadIdx.x == 0) {
-            hdr->cx = hdr->cy = hdr->cz = hdr->radius = 0.0f;
-            hdr->levels = 0;
-            hdr->n_seg = 0;
-        }
-        return;
-    }
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = threadIdx.x; i < n; i += 1024) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = pts[3 * (size_t)i + a];
-            mn[a] = fminf(mn[a], v);
-            mx[a] = fmaxf(mx[a], v);
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            mn[a] = fminf(mn[a], __shfl_down(mn[a], d));
-            mx[a] = fmaxf(mx[a], __shfl_down(mx[a], d));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            s_mn[a][threadIdx.x >> 6] = mn[a];
-            s_mx[a][threadIdx.x >> 6] = mx[a];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float c[3], radius = 0.0f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            for (int w = 1; w < 16; ++w) {
-                mn[a] = fminf(mn[a], s_mn[a][w]);
-                mx[a] = fmaxf(mx[a], s_mx[a][w]);
-            }
-            // Octree::build: centre = min + radii*0.5, radius = max(radii)*0.5
-            const float ext = mx[a] - mn[a];
-            c[a] = mn[a] + ext * 0.5f;
-            if (a == 0 || radius < ext)
-                radius = ext;
-        }
-        radius *= 0.5f;
-        hdr->cx = c[0];
-        hdr->cy = c[1];
-        hdr->cz = c[2];
-        hdr->radius = radius;
-        int L = 0;
-        float r = radius;
-        while (!((double)r * 2.0 <= (double)max_size) && L < S3_MAX_LEVELS) {
-            r *= 0.5f;
-            ++L;
-        }
-        hdr->levels = L;
-        hdr->n_seg = 0;
-    }
-}
-
-// ds3_key_kernel per job
-__global__ __launch_bounds__(256) void s3_key_kernel(const float *__restrict__ cat, const S3Job *__restrict__ jobs,
-                                                     const S3Header *__restrict__ hdrs, unsigned long long *__restrict__ keys)
-{
-    const S3Job J = jobs[blockIdx.y];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= J.tot)
-        return;
-    const float *q = cat + 3 * (size_t)(J.cat + i);
-    const float px = q[0], py = q[1], pz = q[2];
-    const S3Header *hdr = hdrs + blockIdx.y;
-    float cx = hdr->cx, cy = hdr->cy, cz = hdr->cz, r = hdr->radius;
-    const int L = hdr->levels;
-    unsigned long long key = 0;
-    for (int l = 0; l < L; ++l) {
-        const unsigned bx = px > cx, by = py > cy, bz = pz > cz; // Octree::idx: bit i = pt(i) > centre(i)
-        key = (key << 3) | (bx | (by << 1) | (bz << 2));
-        const float hr = r * 0.5f;
-        cx = cx + (bx ? hr : -hr);
-        cy = cy + (by ? hr : -hr);
-        cz = cz + (bz ? hr : -hr);
-        r = hr;
-    }
-    keys[J.cat + i] = key;
-}
-
-// ds3_rank_kernel per job: rank of (key_i, i) among the job's points = position in the stable sort
-__global__ __launch_bounds__(256) void s3_rank_kernel(const unsigned long long *__restrict__ keys_all,
-                                                      const S3Job *__restrict__ jobs, int *__restrict__ sorted_idx_all,
-                                                      unsigned long long *__restrict__ sorted_key_all)
-{
-    __shared__ unsigned long long s_k[S3_TILE];
-    const S3Job J = jobs[blockIdx.y];
-    const int n = J.tot;
-    if (blockIdx.x * 256 >= n) // (uniform: the whole workgroup leaves before any barrier)
-        return;
-    const unsigned long long *__restrict__ keys = keys_all + J.cat;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const unsigned long long ki = (i < n) ? keys[i] : 0ull;
-    int rank = 0;
-    for (int tb = 0; tb < n; tb += S3_TILE) {
-        const int tn = min(S3_TILE, n - tb);
-        __syncthreads();
-        for (int q = threadIdx.x; q < tn; q += 256)
-            s_k[q] = keys[tb + q];
-        __syncthreads();
-        for (int q = 0; q < tn; ++q) {
-            const unsigned long long kj = s_k[q];
-            rank += (kj < ki) || (kj == ki && tb + q < i);
-        }
-    }
-    if (i < n) { // (rank < n: it counts points other than i)
-        sorted_idx_all[J.cat + rank] = i;
-        sorted_key_all[J.cat + rank] = ki;
-    }
-}
-
-// ds3_segment_kernel per job (one workgroup each): the first position of every run of equal keys + a sentinel.  Job j's
-// list has tot + 1 entries and begins at cat + j.
-__global__ __launch_bounds__(1024) void s3_segment_kernel(const unsigned long long *__restrict__ sorted_key_all,
-                                                          const S3Job *__restrict__ jobs, int *__restrict__ seg_start_all,
-                                                          S3Header *__restrict__ hdrs)
-{
-    __shared__ int s_part[1024];
-    const S3Job J = jobs[blockIdx.x];
-    const int n = J.tot;
-    const unsigned long long *__restrict__ sorted_key = sorted_key_all + J.cat;
-    int *__restrict__ seg_start = seg_start_all + J.cat + blockIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int b = (int)min((long long)threadIdx.x * per, (long long)n), e = min(b + per, n);
-    int c = 0;
-    for (int r = b; r < e; ++r)
-        c += (r == 0) || (sorted_key[r] != sorted_key[r - 1]);
-    s_part[threadIdx.x] = c;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int s = (threadIdx.x == 0) ? 0 : s_part[threadIdx.x - 1];
-    for (int r = b; r < e; ++r)
-        if ((r == 0) || (sorted_key[r] != sorted_key[r - 1]))
-            seg_start[s++] = r;
-    if (threadIdx.x == 1023) {
-        hdrs[blockIdx.x].n_seg = s_part[1023];
-        seg_start[s_part[1023]] = n; // sentinel (n_seg <= n)
-    }
-}
-
-// ds3_medoid_kernel per job: one thread per leaf, float centroid in input order, the first point at the minimum distance;
-// IDX: the medoid's index in the job's concatenation goes to out_idx_all (the index output of sfe_downsample3)
-template <bool IDX>
-__global__ __launch_bounds__(256) void s3_medoid_kernel(const float *__restrict__ cat, const S3Job *__restrict__ jobs,
-                                                        const int *__restrict__ sorted_idx_all,
-                                                        const int *__restrict__ seg_start_all,
-                                                        const S3Header *__restrict__ hdrs, float *__restrict__ out_all,
-                                                        int *__restrict__ out_idx_all)
-{
-    const S3Job J = jobs[blockIdx.y];
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= hdrs[blockIdx.y].n_seg)
-        return;
-    const float *__restrict__ pts = cat + 3 * (size_t)J.cat;
-    const int *__restrict__ sorted_idx = sorted_idx_all + J.cat;
-    const int *__restrict__ seg_start = seg_start_all + J.cat + blockIdx.y;
-    const int r0 = seg_start[s], r1 = seg_start[s + 1];
-    float sx = 0.0f, sy = 0.0f, sz = 0.0f;
-    for (int r = r0; r < r1; ++r) {
-        const float *q = pts + 3 * (size_t)sorted_idx[r];
-        sx = f_add(sx, q[0]);
-        sy = f_add(sy, q[1]);
-        sz = f_add(sz, q[2]);
-    }
-    const float cnt = (float)(r1 - r0);
-    sx = __fdiv_rn(sx, cnt);
-    sy = __fdiv_rn(sy, cnt);
-    sz = __fdiv_rn(sz, cnt);
-    float best = 3.402823466e+38f;
-    int bi = sorted_idx[r0];
-    for (int r = r0; r < r1; ++r) {
-        const int id = sorted_idx[r];
-        const float *q = pts + 3 * (size_t)id;
-        // sqrtf: the correctly rounded sequence (ds_medoid_kernel says why)
-        const float d = sqrtf(s3_dist2(q[0], q[1], q[2], sx, sy, sz));
-        if (d < best) {
-            best = d;
-            bi = id;
-        }
-    }
-    const float *q = pts + 3 * (size_t)bi;
-    float *o = out_all + 3 * (size_t)(J.cat + s);
-    o[0] = q[0];
-    o[1] = q[1];
-    o[2] = q[2];
-    if (IDX)
-        out_idx_all[J.cat + s] = bi;
-}
-
 // the descriptor overload of the downsample: leaf s of job blockIdx.y carries the key of its medoid, picked through the
 // medoid's index in the concatenation
 __global__ __launch_bounds__(256) void s3_pick_keys_kernel(const int32_t *__restrict__ cat_key, const S3Job *__restrict__ jobs,
@@ -347,49 +123,7 @@ __global__ __launch_bounds__(256) void s3_pick_keys_kernel(const int32_t *__rest
     out_key[J.cat + s] = cat_key[J.cat + id];
 }
 
-// one workgroup: every job's output size (its leaves, or with `raw` its whole concatenation) and the exclusive sum of the
-// sizes in front of it = its place behind the pool's fill level
-__global__ __launch_bounds__(1024) void s3_offsets_kernel(const S3Job *__restrict__ jobs, const S3Header *__restrict__ hdrs,
-                                                          int n_jobs, int raw, int *__restrict__ out_cnt,
-                                                          long long *__restrict__ out_off)
-{
-    __shared__ long long s_part[1024];
-    const int per = (n_jobs + 1023) / 1024;
-    const int b = min((int)threadIdx.x * per, n_jobs), e = min(b + per, n_jobs);
-    long long c = 0;
-    for (int j = b; j < e; ++j)
-        c += raw ? jobs[j].tot : hdrs[j].n_seg;
-    s_part[threadIdx.x] = c;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const long long v = (threadIdx.x >= d) ? s_part[threadIdx.x - d] : 0;
-        __syncthreads();
-        s_part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    long long at = (threadIdx.x == 0) ? 0 : s_part[threadIdx.x - 1];
-    for (int j = b; j < e; ++j) {
-        const int cj = raw ? jobs[j].tot : hdrs[j].n_seg;
-        out_cnt[j] = cj;
-        out_off[j] = at;
-        at += cj;
-    }
-}
-
-// the jobs' results, one behind the other, into the pool at `top` (in points)
-__global__ __launch_bounds__(256) void s3_place_kernel(const float *__restrict__ from, const S3Job *__restrict__ jobs,
-                                                       const int *__restrict__ out_cnt, const long long *__restrict__ out_off,
-                                                       long long top, float *__restrict__ pool)
-{
-    const S3Job J = jobs[blockIdx.y];
-    const long long nf = 3ll * out_cnt[blockIdx.y]; // (<= 3 tot)
-    const float *__restrict__ src = from + 3 * (size_t)J.cat;
-    float *__restrict__ dst = pool + 3 * (size_t)(top + out_off[blockIdx.y]);
-    for (long long f = blockIdx.x * 256ll + threadIdx.x; f < nf; f += 256ll * gridDim.x)
-        dst[f] = src[f];
-}
-
-// ... and their keys into the key pool, at the same offsets
+// the jobs' keys into the key pool, at the offsets s3_place_kernel (sfe_octree3.hip) puts their points
 __global__ __launch_bounds__(256) void s3_place_keys_kernel(const int32_t *__restrict__ from, const S3Job *__restrict__ jobs,
                                                             const int *__restrict__ out_cnt,
                                                             const long long *__restrict__ out_off, long long top,
@@ -403,63 +137,13 @@ __global__ __launch_bounds__(256) void s3_place_keys_kernel(const int32_t *__res
         dst[i] = src[i];
 }
 
-// the downsample stages and the placement as enqueue-only steps (sfe_octree3.h): get_points below and the octree stage of a
-// 3-D ICP chain run them
-float sfe_s3_max_size(float resolution)
-{
-    char buf[64];
-    snprintf(buf, sizeof buf, "%f", (double)resolution); // pcl.cpp:134: std::to_string(float), as sfe_downsample3
-    return strtof(buf, nullptr);
-}
-
-int sfe_s3_octree_enqueue(sfe_ctx *ctx, const float *d_cat, const S3Job *d_jobs, int n_jobs, int max_tot, float max_size,
-                          const S3OctreeBufs &b)
-{
-    SFE_ARG(ctx, n_jobs >= 1 && n_jobs <= S3_MAX_JOBS && max_tot >= 0);
-    const unsigned nb = (unsigned)std::max((max_tot + 255) / 256, 1);
-    const dim3 per_point(nb, (unsigned)n_jobs), per_job((unsigned)n_jobs);
-    hipLaunchKernelGGL(s3_bbox_kernel, per_job, dim3(1024), 0, ctx->stream, d_cat, d_jobs, max_size, b.hdr);
-    hipLaunchKernelGGL(s3_key_kernel, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const S3Header *)b.hdr, b.keys);
-    hipLaunchKernelGGL(s3_rank_kernel, per_point, dim3(256), 0, ctx->stream, (const unsigned long long *)b.keys, d_jobs, b.sidx,
-                       b.skeys);
-    hipLaunchKernelGGL(s3_segment_kernel, per_job, dim3(1024), 0, ctx->stream, (const unsigned long long *)b.skeys, d_jobs, b.seg,
-                       b.hdr);
-    if (b.midx)
-        hipLaunchKernelGGL(s3_medoid_kernel<true>, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const int *)b.sidx,
-                           (const int *)b.seg, (const S3Header *)b.hdr, b.out, b.midx);
-    else
-        hipLaunchKernelGGL(s3_medoid_kernel<false>, per_point, dim3(256), 0, ctx->stream, d_cat, d_jobs, (const int *)b.sidx,
-                           (const int *)b.seg, (const S3Header *)b.hdr, b.out, (int *)nullptr);
-    SFE_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int sfe_s3_offsets_enqueue(sfe_ctx *ctx, const S3Job *d_jobs, const S3Header *d_hdr, int n_jobs, int raw, int *d_cnt,
-                           long long *d_off)
-{
-    hipLaunchKernelGGL(s3_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_jobs, d_hdr, n_jobs, raw, d_cnt, d_off);
-    SFE_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int sfe_s3_place_enqueue(sfe_ctx *ctx, const float *d_from, const S3Job *d_jobs, int n_jobs, int max_tot, const int *d_cnt,
-                         const long long *d_off, long long top, float *pool)
-{
-    SFE_ARG(ctx, n_jobs >= 1 && n_jobs <= S3_MAX_JOBS && max_tot >= 0);
-    const unsigned nb = (unsigned)std::max((max_tot + 255) / 256, 1);
-    hipLaunchKernelGGL(s3_place_kernel, dim3(std::min(3u * nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream, d_from, d_jobs,
-                       d_cnt, d_off, top, pool);
-    SFE_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // overlap: moved source points with a target point within the radius (the rules of match3_kernel)
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void s3_overlap_kernel(const float *__restrict__ pool, const S3Pair *__restrict__ pairs,
                                                          float r2, int *__restrict__ counts)
 {
-    __shared__ float s_t[3 * S3_TILE];
+    __shared__ float s_t[3 * P3_TILE];
     const S3Pair J = pairs[blockIdx.y];
     if (blockIdx.x * 256 >= J.ns) // (uniform)
         return;
@@ -474,14 +158,13 @@ __global__ __launch_bounds__(256) void s3_overlap_kernel(const float *__restrict
     }
     const float *__restrict__ tgt = pool + 3 * (size_t)J.tgt;
     bool hit = false;
-    for (int tb = 0; tb < J.nt; tb += S3_TILE) {
-        const int tn = min(S3_TILE, J.nt - tb);
+    for (int tb = 0; tb < J.nt; tb += P3_TILE) {
+        const int tn = min(P3_TILE, J.nt - tb);
         __syncthreads();
-        for (int q = threadIdx.x; q < 3 * tn; q += 256) // consecutive floats: coalesced
-            s_t[q] = tgt[3 * (size_t)tb + q];
+        p3_stage(s_t, tgt, tb, tn);
         __syncthreads();
         for (int j = 0; j < tn; ++j) // every lane reads the same LDS words: a broadcast
-            hit |= s3_dist2(px, py, pz, s_t[3 * j], s_t[3 * j + 1], s_t[3 * j + 2]) <= r2; // NaN: never
+            hit |= p3_dist2(px, py, pz, s_t[3 * j], s_t[3 * j + 1], s_t[3 * j + 2]) <= r2; // NaN: never
     }
     hit = hit && i < J.ns;
     const unsigned long long b = __ballot(hit);
@@ -597,14 +280,14 @@ __global__ __launch_bounds__(1024) void s3_compact_kernel(const float *__restric
 }
 
 // get_overlap(..., return_indices=True) and the keys of the matched targets (slam.py:977-985): every moved source point gets
-// its sfe_match3 neighbour -- the nearest target by s3_dist2, the lowest index among equal distances (the update is on strict
-// `<` in ascending index, within a tile and from tile to tile), kept iff d2 <= r2; NaN and infinite distances never win.
+// its sfe_match3 neighbour -- p3_nearest: the nearest target by p3_dist2, the lowest index among equal distances -- kept iff
+// d2 <= r2; NaN and infinite distances never win.
 // hist[key of the neighbour] += 1; the number of matches is what s3_overlap_kernel counts.
 __global__ __launch_bounds__(256) void s3_match_keys_kernel(const float *__restrict__ pool, const int32_t *__restrict__ key_pool,
                                                             const S3Pair *__restrict__ pairs, float r2, int n_keys,
                                                             int32_t *__restrict__ hist_, int32_t *__restrict__ overlap_)
 {
-    __shared__ float s_t[3 * S3_TILE];
+    __shared__ float s_t[3 * P3_TILE];
     const S3Pair J = pairs[blockIdx.y];
     if (blockIdx.x * 256 >= J.ns) // (uniform)
         return;
@@ -617,23 +300,9 @@ __global__ __launch_bounds__(256) void s3_match_keys_kernel(const float *__restr
         py = s3_move(J.H + 4, p0, p1, p2);
         pz = s3_move(J.H + 8, p0, p1, p2);
     }
-    const float *__restrict__ tgt = pool + 3 * (size_t)J.tgt;
-    float best = INFINITY;
-    int bi = -1;
-    for (int tb = 0; tb < J.nt; tb += S3_TILE) {
-        const int tn = min(S3_TILE, J.nt - tb);
-        __syncthreads();
-        for (int q = threadIdx.x; q < 3 * tn; q += 256)
-            s_t[q] = tgt[3 * (size_t)tb + q];
-        __syncthreads();
-        for (int t = 0; t < tn; ++t) {
-            const float d = s3_dist2(px, py, pz, s_t[3 * t], s_t[3 * t + 1], s_t[3 * t + 2]);
-            if (d < best) { // (NaN, +inf: never)
-                best = d;
-                bi = tb + t;
-            }
-        }
-    }
+    float best;
+    int bi;
+    p3_nearest(s_t, pool + 3 * (size_t)J.tgt, J.nt, px, py, pz, best, bi);
     const bool hit = i < J.ns && bi >= 0 && best <= r2;
     if (hit) {
         const int k = key_pool[J.tgt + bi];
@@ -1121,11 +790,11 @@ int sfe_cloud_store3_compact_selected(sfe_ctx *ctx, sfe_cloud_store3 *s, const i
     hipLaunchKernelGGL(s3_compact_kernel, dim3((unsigned)n_jobs), dim3(1024), 0, ctx->stream, (const float *)s->d_pool,
                        (const int32_t *)s->d_key, (const uint8_t *)s->d_sel, d_jobs, (const long long *)(d_tab + b_jobs), d_out,
                        d_okey, d_hdr);
-    hipLaunchKernelGGL(s3_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_jobs, (const S3Header *)d_hdr, n_jobs, 0, d_cnt,
-                       d_off);
+    if (int rc = sfe_s3_offsets_enqueue(ctx, d_jobs, d_hdr, n_jobs, 0, d_cnt, d_off))
+        return rc;
     // (the results lie within [top, top + need.points))
-    hipLaunchKernelGGL(s3_place_kernel, dim3(std::min(3u * nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream,
-                       (const float *)d_out, d_jobs, (const int *)d_cnt, (const long long *)d_off, (long long)t.top, s->d_pool);
+    if (int rc = sfe_s3_place_enqueue(ctx, d_out, d_jobs, n_jobs, max_n, d_cnt, d_off, (long long)t.top, s->d_pool))
+        return rc;
     hipLaunchKernelGGL(s3_place_keys_kernel, dim3(std::min(nb, 64u), (unsigned)n_jobs), dim3(256), 0, ctx->stream,
                        (const int32_t *)d_okey, d_jobs, (const int *)d_cnt, (const long long *)d_off, (long long)t.top, s->d_key);
     SFE_LAUNCH_CHECK(ctx);

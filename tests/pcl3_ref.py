@@ -10,7 +10,7 @@ With z = 0 on both sides the third term is +0 and every function gives what the 
 import numpy as np
 
 F = np.float32
-MAX_LEVELS = 21     # 3 key bits per level in a 64-bit path key (sfe_pcl3.hip)
+MAX_LEVELS = 21     # 3 key bits per level in a 64-bit path key (S3_MAX_LEVELS, sfe_octree3.h)
 
 
 def _c3(a):

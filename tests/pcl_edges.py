@@ -1,6 +1,6 @@
 """Constructed edge cases of the brute-force cloud kernels behind ``pcl.match``, ``pcl.remove_outlier``, ``pcl.knn_density``
 and the rank-counting route of ``pcl.downsample`` (csrc/sfe_icp.hip: match / match_knn / knn_density / radius_count;
-csrc/sfe_pcl3.hip: their N x 3 twins and ds3_*; csrc/sfe_map.hip: radius_count_many; csrc/sfe_downsample.hip: ds_*).
+csrc/sfe_pcl3.hip: their N x 3 twins; csrc/sfe_octree3.hip: s3_*, one job; csrc/sfe_map.hip: radius_count_many; csrc/sfe_downsample.hip: ds_*).
 tests/test_pcl_edges_host.py runs them through the references alone, tests/test_gpu_pcl_edges.py through the device.
 Importable without a GPU.
 
@@ -28,7 +28,7 @@ import pcl3_ref
 F = np.float32
 INF = F(np.inf)
 TILE = 2048                      # reference points per LDS tile (match, radius count, rank)
-LEVELS = {2: 31, 3: 21}          # DS_MAX_LEVELS / DS3_MAX_LEVELS
+LEVELS = {2: 31, 3: 21}          # DS_MAX_LEVELS / S3_MAX_LEVELS
 U = 2.0 ** -24                   # unit roundoff of float32
 
 Case = collections.namedtuple("Case", "name why args")

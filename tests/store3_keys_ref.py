@@ -18,7 +18,7 @@ import pcl3_ref
 import store3_ref as R
 
 F = np.float32
-TILE = 2048                                         # S3_TILE: target points per LDS tile of the matching kernels
+TILE = 2048                                         # P3_TILE: target points per LDS tile of the matching kernels
 
 
 def get_points_keys(clouds, Hs, keys, resolution):
