@@ -138,46 +138,6 @@ struct IcpShared {
     float hist_c[ICP_MAX_HIST], hist_s[ICP_MAX_HIST], hist_x[ICP_MAX_HIST], hist_y[ICP_MAX_HIST];
 };
 
-// k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns) by radix select on the float bit patterns: the loop of the
-// trimmed quantile in icp_job_kernel, for the median of its OX builds (called by the whole workgroup)
-__device__ __forceinline__ float job_select_kth(IcpShared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
-{
-    if (tid == 0) {
-        S.sel_k = k_sel;
-        S.sel_prefix = 0;
-    }
-    __syncthreads();
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256)
-            S.hist[tid] = 0;
-        __syncthreads();
-        const unsigned prefix = S.sel_prefix;
-        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (int i = tid; i < ns; i += ICP_THREADS) {
-            const float d = nn_d2[i];
-            if (d != INFINITY) {
-                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
-                if ((u & himask) == prefix)
-                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned k = S.sel_k, b = 0;
-            for (; b < 256; ++b) {
-                const unsigned h = S.hist[b];
-                if (k < h)
-                    break;
-                k -= h;
-            }
-            S.sel_k = k;
-            S.sel_prefix = prefix | (b << shift);
-        }
-        __syncthreads();
-    }
-    return __uint_as_float(S.sel_prefix);
-}
-
 template <int MINW, bool OX>
 __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_params P, int nn_variant,
                                                               const IcpJob *__restrict__ jobs,
@@ -514,7 +474,8 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
         __syncthreads();
         if (fail)
             break;
-        // ---- MedianDistOutlierFilter limit (OX builds): factor x the median, the same radix select at rank icp_median_rank ----
+        // ---- MedianDistOutlierFilter limit (OX builds): factor x the median, the radix select of the trimmed quantile above
+        // (icp_select_kth, sfe_icp_common.h) at rank icp_median_rank ----
         float med_limit = INFINITY;
         if constexpr (OX) {
             if (O.use_median) {
@@ -524,7 +485,7 @@ __global__ __launch_bounds__(ICP_THREADS, MINW) void icp_job_kernel(sfe_icp_para
                     break;
                 }
                 // (the barrier above: every wave has read the trimmed limit out of S.sel_prefix, which this select resets)
-                med_limit = f_mul(O.median_factor, job_select_kth(S, nn_d2, ns, tid, icp_median_rank(nfin)));
+                med_limit = f_mul(O.median_factor, icp_select_kth(S, nn_d2, ns, tid, icp_median_rank(nfin)));
                 __syncthreads(); // (... and the median out of it before anything else writes it)
             }
         }

@@ -118,16 +118,16 @@ struct Icp3SharedT {
     float Ti[16];
     float mean[3];
     float hist_T[ICP_MAX_HIST][12]; // rotation block (9, row-major) and translation (3) of T_iter after every step
+
+    // the dynamic LDS of a launch, so every instantiation that is launched passes the check.  (Only its 64 KiB half can
+    // fail: red is declared with the size block_sum<NS> needs, and the first half says so where it is relied on.)
+    static constexpr size_t bytes()
+    {
+        static_assert(sizeof(red) >= sizeof(double) * (ICP_WAVES + 1) * NS && sizeof(Icp3SharedT) <= 64 * 1024,
+                      "block_sum<NS> needs (waves + 1) x NS doubles; two workgroups per CU");
+        return sizeof(Icp3SharedT);
+    }
 };
-static_assert(sizeof(((Icp3SharedT<ICP3_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3_NSUM + ICP3_NSUM),
-              "block_sum<ICP3_NSUM> needs (waves + 1) x ICP3_NSUM doubles");
-static_assert(sizeof(((Icp3SharedT<ICP3P_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3P_NSUM + ICP3P_NSUM),
-              "block_sum<ICP3P_NSUM> needs (waves + 1) x ICP3P_NSUM doubles");
-static_assert(sizeof(((Icp3SharedT<ICP3P4_NSUM> *)nullptr)->red) >= sizeof(double) * (ICP_WAVES * ICP3P4_NSUM + ICP3P4_NSUM),
-              "block_sum<ICP3P4_NSUM> needs (waves + 1) x ICP3P4_NSUM doubles");
-static_assert(sizeof(Icp3SharedT<ICP3_NSUM>) <= 64 * 1024 && sizeof(Icp3SharedT<ICP3P_NSUM>) <= 64 * 1024 &&
-                  sizeof(Icp3SharedT<ICP3P4_NSUM>) <= 64 * 1024,
-              "two workgroups per CU");
 
 // load target points [base, base + n) of the job (packed float triples), centred on the mean, into the LDS tile (+inf pad)
 template <class Icp3Shared>
@@ -185,47 +185,6 @@ __device__ __forceinline__ void nn3_scan_tile(const Icp3Shared &S, int tn, int t
             }
         }
     }
-}
-
-// k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns): the radix select of job_select_kth (sfe_icp.hip) on this
-// kernel's shared block; called by the whole workgroup
-template <class Icp3Shared>
-__device__ __forceinline__ float job3_select_kth(Icp3Shared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
-{
-    if (tid == 0) {
-        S.sel_k = k_sel;
-        S.sel_prefix = 0;
-    }
-    __syncthreads();
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        if (tid < 256)
-            S.hist[tid] = 0;
-        __syncthreads();
-        const unsigned prefix = S.sel_prefix;
-        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
-        for (int i = tid; i < ns; i += ICP_THREADS) {
-            const float d = nn_d2[i];
-            if (d != INFINITY) {
-                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
-                if ((u & himask) == prefix)
-                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            unsigned k = S.sel_k, b = 0;
-            for (; b < 255; ++b) { // (b stops at 255: the shift below stays inside the word whatever the histogram holds)
-                const unsigned h = S.hist[b];
-                if (k < h)
-                    break;
-                k -= h;
-            }
-            S.sel_k = k;
-            S.sel_prefix = prefix | (b << shift);
-        }
-        __syncthreads();
-    }
-    return __uint_as_float(S.sel_prefix);
 }
 
 // One lane: solve from the reduced sums, T_iter = T_step * T_iter (to LDS), then the Counter and Differential checkers in
@@ -379,7 +338,7 @@ __device__ __forceinline__ void icp3_target_mean(const float *__restrict__ tgt, 
 
 // EXT = 1: the kernel of a chain that lists a MinDist or MedianDist outlier filter or a Bound checker (sfe_icp_outliers;
 // rules at sfe_icp3_compute_jobs_chain_ext in include/sonarfe.h).  The median is a second radix select over the same finite
-// d2; MinDist and the median limit join the keep test of both minimisers' sums; Bound runs in icp3_solve_and_check.
+// d2; MinDist and the median limit join the kernel's one keep test; Bound runs in icp3_solve_and_check.
 template <int MIN, int EXT>
 __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, const Icp3Job *__restrict__ jobs,
                                                                const float *__restrict__ src_all,
@@ -446,8 +405,17 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
 #pragma unroll
         for (int i = 0; i < 12; ++i)
             Ti[i] = S.Ti[i];
+        // the current point of source point i: T_iter * (T0 * src[i]), every row by affine3 (floats, whatever x, y, z are)
+        auto cur_point = [&](int i, auto &x, auto &y, auto &z) {
+            const float *s = src + 3 * (size_t)i;
+            const float sx = s[0], sy = s[1], sz = s[2];
+            const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
+            x = affine3(Ti, rx, ry, rz);
+            y = affine3(Ti + 4, rx, ry, rz);
+            z = affine3(Ti + 8, rx, ry, rz);
+        };
 
-        // ---- match: exact 1-NN of cur = Ti * (T0 * src) in the centred target ----
+        // ---- match: exact 1-NN of the current points in the centred target ----
         double nfin_d[1] = {0};
         for (int base = 0; base < ns; base += ICP_THREADS * ICP3_PB) {
             const int np = (ns - base > ICP_THREADS) ? ICP3_PB : 1; // uniform: queries per lane in this pass
@@ -457,14 +425,8 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
             for (int k = 0; k < ICP3_PB; ++k) {
                 const int i = base + k * ICP_THREADS + tid;
                 float x = 0, y = 0, z = 0;
-                if (k < np && i < ns) {
-                    const float *s = src + 3 * (size_t)i;
-                    const float sx = s[0], sy = s[1], sz = s[2];
-                    const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
-                    x = affine3(Ti, rx, ry, rz);
-                    y = affine3(Ti + 4, rx, ry, rz);
-                    z = affine3(Ti + 8, rx, ry, rz);
-                }
+                if (k < np && i < ns)
+                    cur_point(i, x, y, z);
                 px[k] = x;
                 py[k] = y;
                 pz[k] = z;
@@ -512,10 +474,10 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                 break;
             }
             const unsigned k_sel = (P.trim_ratio >= 1.0f) ? nfin - 1 : (unsigned)f_mul((float)nfin, P.trim_ratio);
-            limit = job3_select_kth(S, nn_d2, ns, tid, min(k_sel, nfin - 1));
+            limit = icp_select_kth(S, nn_d2, ns, tid, min(k_sel, nfin - 1));
             __syncthreads();
         }
-        // ---- MedianDistOutlierFilter limit (EXT): factor x the median, the same select at rank icp3_median_rank ----
+        // ---- MedianDistOutlierFilter limit (EXT): factor x the median, the same select at rank icp_median_rank ----
         float med_limit = INFINITY;
         if constexpr (EXT) {
             if (A.O.use_median) {
@@ -525,26 +487,51 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                     break;
                 }
                 // (the barrier above: every wave has read the trimmed limit out of S.sel_prefix, which this select resets)
-                med_limit = f_mul(A.O.median_factor, job3_select_kth(S, nn_d2, ns, tid, icp3_median_rank(nfin)));
+                med_limit = f_mul(A.O.median_factor, icp_select_kth(S, nn_d2, ns, tid, icp_median_rank(nfin)));
                 __syncthreads(); // (... and the median out of it before anything else writes it)
             }
         }
-        // a pair that MaxDist and Trimmed keep: do the EXT filters keep it too?
-        auto ext_keep = [&](float d) {
+        // the keep test of a stored pair (id, d): a target point in range that MaxDist, Trimmed and (EXT) MinDist / MedianDist keep
+        auto keep = [&](int id, float d) {
+            bool ok = id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit);
             if constexpr (EXT)
-                return icp3_ox_keep(A.O, min2, med_limit, d);
-            else
-                return true;
+                ok = ok && icp_ox_keep(A.O, min2, med_limit, d);
+            return ok;
+        };
+        // the centred target point id: out of the LDS tile where the target is resident
+        auto target_point = [&](int id, double (&q)[3]) {
+            if (resident) {
+                q[0] = S.tx[id];
+                q[1] = S.ty[id];
+                q[2] = S.tz[id];
+            } else {
+                const float *t = tgt + 3 * (size_t)id;
+                q[0] = f_add(t[0], -mx);
+                q[1] = f_add(t[1], -my);
+                q[2] = f_add(t[2], -mz);
+            }
+        };
+        // the normal of target point id, gathered from HBM (one per kept pair)
+        auto target_normal = [&](int id, double (&n)[3]) {
+            const float *nv = nrm_all + 3 * (size_t)(J.nrm_off + id);
+            n[0] = nv[0];
+            n[1] = nv[1];
+            n[2] = nv[2];
+        };
+        // point-to-plane: e = n . (p - q)
+        auto plane_err = [&](int id, const double (&n)[3], const double (&p)[3]) {
+            double q[3];
+            target_point(id, q);
+            return (n[0] * (p[0] - q[0]) + n[1] * (p[1] - q[1])) + n[2] * (p[2] - q[2]);
         };
 
         // ---- error minimiser: accumulate over kept pairs ----
         double acc[NS];
         if constexpr (MIN == ICP3_PLANE) {
-            // F = (p x n, n), e = n . (p - q): A += F F^T (upper triangle, row by row), b -= F e, W += 1; the normal of the
-            // matched target point is gathered from HBM (one per kept pair).  28 fp64 accumulators beside the pair's own
-            // values do not fit the 128 registers of a 1024-thread workgroup, so the kept pairs are walked twice: W and
-            // the rows of A that begin with p x n (16 sums), then the n n^T block and b (12 sums).  Each sum is reduced
-            // exactly as block_sum<28> would reduce it.
+            // F = (p x n, n), e = n . (p - q): A += F F^T (upper triangle, row by row), b -= F e, W += 1.  28 fp64
+            // accumulators beside the pair's own values do not fit the 128 registers of a 1024-thread workgroup, so the
+            // kept pairs are walked twice: W and the rows of A that begin with p x n (16 sums), then the n n^T block and b
+            // (12 sums).  Each sum is reduced exactly as block_sum<28> would reduce it.
             auto pass = [&](auto part) {
                 constexpr int PART = decltype(part)::value;
                 constexpr int OFF = PART ? 16 : 0, CNT = PART ? 12 : 16;
@@ -554,17 +541,13 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                     a[i] = 0;
                 for (int i = tid; i < ns; i += ICP_THREADS) {
                     const int id = nn_idx[i];
-                    const float d = nn_d2[i];
-                    if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) &&
-                          (!P.use_trimmed_filter || d <= limit) && ext_keep(d)))
+                    if (!keep(id, nn_d2[i]))
                         continue;
-                    const float *s = src + 3 * (size_t)i;
-                    const float sx = s[0], sy = s[1], sz = s[2];
-                    const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
-                    const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
-                    const float *nv = nrm_all + 3 * (size_t)(J.nrm_off + id);
-                    const double n0 = nv[0], n1 = nv[1], n2 = nv[2];
-                    const double F[6] = {p[1] * n2 - p[2] * n1, p[2] * n0 - p[0] * n2, p[0] * n1 - p[1] * n0, n0, n1, n2};
+                    double p[3], n[3];
+                    cur_point(i, p[0], p[1], p[2]);
+                    target_normal(id, n);
+                    const double F[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0],
+                                         n[0],                      n[1],                      n[2]};
                     if constexpr (PART == 0) {
                         a[0] += 1.0;
                         int k = 1;
@@ -574,18 +557,7 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                             for (int c = r; c < 6; ++c)
                                 a[k++] += F[r] * F[c];
                     } else {
-                        double q[3];
-                        if (resident) {
-                            q[0] = S.tx[id];
-                            q[1] = S.ty[id];
-                            q[2] = S.tz[id];
-                        } else {
-                            const float *t = tgt + 3 * (size_t)id;
-                            q[0] = f_add(t[0], -mx);
-                            q[1] = f_add(t[1], -my);
-                            q[2] = f_add(t[2], -mz);
-                        }
-                        const double e = (n0 * (p[0] - q[0]) + n1 * (p[1] - q[1])) + n2 * (p[2] - q[2]);
+                        const double e = plane_err(id, n, p);
                         int k = 0;
 #pragma unroll
                         for (int r = 3; r < 6; ++r)
@@ -610,29 +582,13 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                 acc[i] = 0;
             for (int i = tid; i < ns; i += ICP_THREADS) {
                 const int id = nn_idx[i];
-                const float d = nn_d2[i];
-                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit) &&
-                      ext_keep(d)))
+                if (!keep(id, nn_d2[i]))
                     continue;
-                const float *s = src + 3 * (size_t)i;
-                const float sx = s[0], sy = s[1], sz = s[2];
-                const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
-                const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
-                const float *nv = nrm_all + 3 * (size_t)(J.nrm_off + id);
-                const double n0 = nv[0], n1 = nv[1], n2 = nv[2];
-                double q[3];
-                if (resident) {
-                    q[0] = S.tx[id];
-                    q[1] = S.ty[id];
-                    q[2] = S.tz[id];
-                } else {
-                    const float *t = tgt + 3 * (size_t)id;
-                    q[0] = f_add(t[0], -mx);
-                    q[1] = f_add(t[1], -my);
-                    q[2] = f_add(t[2], -mz);
-                }
-                const double F[4] = {p[0] * n1 - p[1] * n0, n0, n1, n2};
-                const double e = (n0 * (p[0] - q[0]) + n1 * (p[1] - q[1])) + n2 * (p[2] - q[2]);
+                double p[3], n[3];
+                cur_point(i, p[0], p[1], p[2]);
+                target_normal(id, n);
+                const double F[4] = {p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2]};
+                const double e = plane_err(id, n, p);
                 acc[0] += 1.0;
                 int k = 1;
 #pragma unroll
@@ -651,25 +607,11 @@ __global__ __launch_bounds__(ICP_THREADS) void icp3_job_kernel(Icp3Args<EXT> A, 
                 acc[i] = 0;
             for (int i = tid; i < ns; i += ICP_THREADS) {
                 const int id = nn_idx[i];
-                const float d = nn_d2[i];
-                if (!(id >= 0 && id < nt && (!P.use_max_dist_filter || d <= r2_filter) && (!P.use_trimmed_filter || d <= limit) &&
-                      ext_keep(d)))
+                if (!keep(id, nn_d2[i]))
                     continue;
-                const float *s = src + 3 * (size_t)i;
-                const float sx = s[0], sy = s[1], sz = s[2];
-                const float rx = affine3(T0, sx, sy, sz), ry = affine3(T0 + 4, sx, sy, sz), rz = affine3(T0 + 8, sx, sy, sz);
-                const double p[3] = {affine3(Ti, rx, ry, rz), affine3(Ti + 4, rx, ry, rz), affine3(Ti + 8, rx, ry, rz)};
-                double q[3];
-                if (resident) {
-                    q[0] = S.tx[id];
-                    q[1] = S.ty[id];
-                    q[2] = S.tz[id];
-                } else {
-                    const float *t = tgt + 3 * (size_t)id;
-                    q[0] = f_add(t[0], -mx);
-                    q[1] = f_add(t[1], -my);
-                    q[2] = f_add(t[2], -mz);
-                }
+                double p[3], q[3];
+                cur_point(i, p[0], p[1], p[2]);
+                target_point(id, q);
                 acc[0] += 1.0;
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
@@ -888,33 +830,43 @@ int sfe_icp3_check_params(sfe_ctx *ctx, const sfe_icp_params *p)
     return 0;
 }
 
+// Enqueue icp3_job_kernel<MIN, EXT> for a staged job table.  One signature for all six, so that sfe_icp3_run_dev picks one
+// from a table: the EXT = 0 builds leave `o` alone and pass sfe_icp_params and nothing else.
+template <int MIN, int EXT>
+static int icp3_launch(sfe_ctx *ctx, const sfe_icp_params &p, const sfe_icp_outliers &o, int n_jobs, const Icp3Job *d_jobs,
+                       const float *d_src, const float *d_tgt, const float *d_g, const float *d_nrm, float *d_nn_d2,
+                       int *d_nn_idx, float *d_T, int32_t *d_st)
+{
+    using Shared = Icp3SharedT<Icp3Sums<MIN>::N>;
+    Icp3Args<EXT> A{p};
+    if constexpr (EXT)
+        A.O = o;
+    SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<MIN, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)Shared::bytes()));
+    hipLaunchKernelGGL((icp3_job_kernel<MIN, EXT>), dim3(n_jobs), dim3(ICP_THREADS), Shared::bytes(), ctx->stream, A, d_jobs,
+                       d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx, d_T, d_st, d_st + n_jobs);
+    return 0;
+}
+
 // The launch both entry points share (sfe_icp3_compute_jobs on clouds it has just copied up, sfe_icp3_store_compute on a
 // store's pool): a validated job table over two device pools, host guesses and host results.  Stages [guesses | job table
 // | target table], launches icp3_job_kernel -- for point-to-plane behind the normals of the call's distinct targets (by
 // first point and size: the 30 guesses of a compute_batch, or store pairs on one handle, take them once), in stream order
 // -- and brings [T | status | iterations] back: one copy each way, one synchronisation.  `o` (nullable; all zero: none)
 // names the modules of the EXT build; without any the launch is the plain kernel's.
-template <int MIN, int EXT>
-static int icp3_launch(sfe_ctx *ctx, const Icp3Args<EXT> &A, int n_jobs, const Icp3Job *d_jobs, const float *d_src,
-                       const float *d_tgt, const float *d_g, const float *d_nrm, float *d_nn_d2, int *d_nn_idx, float *d_T,
-                       int32_t *d_st)
-{
-    using Shared = Icp3SharedT<Icp3Sums<MIN>::N>;
-    SFE_HIP(ctx, hipFuncSetAttribute((const void *)icp3_job_kernel<MIN, EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sizeof(Shared)));
-    hipLaunchKernelGGL((icp3_job_kernel<MIN, EXT>), dim3(n_jobs), dim3(ICP_THREADS), sizeof(Shared), ctx->stream, A, d_jobs,
-                       d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx, d_T, d_st, d_st + n_jobs);
-    return 0;
-}
-
 int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outliers *o, const float *d_src,
                      const float *d_tgt, const int64_t *jobs4, const float *guesses16, int n_jobs, float *T_out16,
                      int32_t *status, int32_t *iters)
 {
     const bool plane = p->minimizer == ICP3_PLANE || p->minimizer == ICP3_PLANE4; // the minimisers that take normals
     const bool ext = o && (o->use_min_dist || o->use_median || o->use_bound);
-    const Icp3Args<0> A0{*p};
-    const Icp3Args<1> A1{*p, ext ? *o : sfe_icp_outliers{}};
+    // icp3_launch<MIN, EXT> by [minimiser][EXT].  sfe_icp3_check_params has let 0, 2 and 3 through; the row agrees with
+    // `plane` for any value (the point-to-point row is the one that takes no normals).
+    static constexpr decltype(&icp3_launch<ICP3_POINT, 0>) launch[3][2] = {
+        {icp3_launch<ICP3_POINT, 0>, icp3_launch<ICP3_POINT, 1>},
+        {icp3_launch<ICP3_PLANE, 0>, icp3_launch<ICP3_PLANE, 1>},
+        {icp3_launch<ICP3_PLANE4, 0>, icp3_launch<ICP3_PLANE4, 1>}};
+    const int min_row = p->minimizer == ICP3_PLANE ? 1 : p->minimizer == ICP3_PLANE4 ? 2 : 0;
     std::vector<Icp3Job> jobs((size_t)n_jobs);
     std::vector<Nrm3Target> targets;
     std::map<std::pair<long long, int>, long long> seen; // (first point, size) of a target -> where its normals go
@@ -951,9 +903,10 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outlie
     SFE_HIP(ctx, hipMemcpyAsync(d_g, h_in, b_g, hipMemcpyHostToDevice, ctx->stream));
     SFE_HIP(ctx, hipMemcpyAsync(d_jobs, h_in + b_g, b_jobs, hipMemcpyHostToDevice, ctx->stream));
     int32_t *d_st = (int32_t *)(d_out + b_g);
+    float *d_nrm = nullptr;
     if (plane) {
         // normals: 3 floats per point of every distinct target (HBM); [target table | means] in one slot
-        float *d_nrm = (float *)sfe_scratch(ctx, 7, sizeof(float) * 3 * (size_t)noff);
+        d_nrm = (float *)sfe_scratch(ctx, 7, sizeof(float) * 3 * (size_t)noff);
         char *d_tg = (char *)sfe_scratch(ctx, 8, b_tg + sizeof(float) * 3 * (size_t)n_targets);
         if (!d_nrm || !d_tg)
             return SFE_ERR_HIP;
@@ -962,24 +915,10 @@ int sfe_icp3_run_dev(sfe_ctx *ctx, const sfe_icp_params *p, const sfe_icp_outlie
         if (int rc = icp3_normals_dev(ctx, (const Nrm3Target *)d_tg, targets.data(), n_targets, d_tgt, (float *)(d_tg + b_tg),
                                       p->normals_knn, d_nrm))
             return rc;
-        if (p->minimizer == ICP3_PLANE4) {
-            if (int rc = ext ? icp3_launch<ICP3_PLANE4, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
-                                                           (float *)d_out, d_st)
-                             : icp3_launch<ICP3_PLANE4, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2, d_nn_idx,
-                                                           (float *)d_out, d_st))
-                return rc;
-        } else if (int rc = ext ? icp3_launch<ICP3_PLANE, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2,
-                                                             d_nn_idx, (float *)d_out, d_st)
-                                : icp3_launch<ICP3_PLANE, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2,
-                                                             d_nn_idx, (float *)d_out, d_st))
-            return rc;
-    } else {
-        if (int rc = ext ? icp3_launch<ICP3_POINT, 1>(ctx, A1, n_jobs, d_jobs, d_src, d_tgt, d_g, nullptr, d_nn_d2, d_nn_idx,
-                                                      (float *)d_out, d_st)
-                         : icp3_launch<ICP3_POINT, 0>(ctx, A0, n_jobs, d_jobs, d_src, d_tgt, d_g, nullptr, d_nn_d2, d_nn_idx,
-                                                      (float *)d_out, d_st))
-            return rc;
     }
+    if (int rc = launch[min_row][ext](ctx, *p, ext ? *o : sfe_icp_outliers{}, n_jobs, d_jobs, d_src, d_tgt, d_g, d_nrm, d_nn_d2,
+                                      d_nn_idx, (float *)d_out, d_st))
+        return rc;
     SFE_LAUNCH_CHECK(ctx);
     SFE_HIP(ctx, hipMemcpyAsync(h_out, d_out, b_out, hipMemcpyDeviceToHost, ctx->stream));
     SFE_HIP(ctx, hipStreamSynchronize(ctx->stream));

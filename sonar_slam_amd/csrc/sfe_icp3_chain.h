@@ -10,6 +10,7 @@
 
 #include "../../include/sonarfe.h"
 #include "sfe_icp3_solve.h"
+#include "sfe_icp_outlier_rules.h" // the outlier filters' keep test: icp_median_rank, icp_ox_keep (the 2-D chain's)
 
 SFE_ICP3_HD float icp3c_mul(float a, float b)
 {
@@ -77,13 +78,11 @@ inline int icp3_dpf_validate(const sfe_icp_dpf *st, int n, int *bad)
     return ICP3_DPF_OK;
 }
 
-// MedianDistOutlierFilter: rank (0-based) of the median among the nfin finite distances, the trimmed filter's quantile at 0.5
-SFE_ICP3_HD unsigned icp3_median_rank(unsigned nfin) { return (unsigned)icp3c_mul((float)nfin, 0.5f); }
-
-// kept by MinDist (d >= minDist^2, min2 = fl(minDist minDist)) and by the median filter (d <= med_limit = fl(factor median))?
+// The outlier filters' median rank and keep test under this header's names: the one pair of sfe_icp_outlier_rules.h
+SFE_ICP3_HD unsigned icp3_median_rank(unsigned nfin) { return icp_median_rank(nfin); }
 SFE_ICP3_HD bool icp3_ox_keep(const sfe_icp_outliers &O, float min2, float med_limit, float d)
 {
-    return (!O.use_min_dist || d >= min2) && (!O.use_median || d <= med_limit);
+    return icp_ox_keep(O, min2, med_limit, d);
 }
 
 // BoundTransformationChecker on T_iter (4 x 4 row-major floats), in fp64 from the float entries: the rotation is the angle

@@ -3,6 +3,7 @@
 // explicit IEEE roundings (no contraction) so both kernels and the oracle take the same decisions.
 #pragma once
 #include "sfe_internal.h"
+#include "sfe_icp_outlier_rules.h" // icp_median_rank, icp_ox_keep
 #include "sfe_wave_sum_plan.h"
 
 #ifndef ICP_THREADS
@@ -230,14 +231,48 @@ struct IcpCheck {
     int nhist, counter, iters;
 };
 
-// MedianDistOutlierFilter: rank (0-based) of the median among the nfin finite distances -- Matches::getDistsQuantile(0.5)
-// as the trimmed quantile is taken: values.size() * 0.5 in float, truncated
-__device__ __forceinline__ unsigned icp_median_rank(unsigned nfin) { return (unsigned)f_mul((float)nfin, 0.5f); }
-
-// kept by MinDist (d >= minDist^2) and by the median filter (d <= its limit)?
-__device__ __forceinline__ bool icp_ox_keep(const sfe_icp_outliers &O, float min2, float med_limit, float d)
+// k_sel-th smallest (0-based) finite distance of nn_d2[0 .. ns) by radix select on the float bit patterns, four passes of
+// eight bits over the histogram of the job's shared block (Shared: hist[256], sel_prefix, sel_k); called by the whole
+// workgroup of ICP_THREADS.  The callers keep k_sel below the number nfin >= 1 of finite distances (the trimmed rank as
+// min(k_sel, nfin - 1), the median's as nfin / 2), and only finite distances are stored and counted, so the bucket loop
+// always breaks inside the histogram; its bound matters only to a k_sel that is not below the histogram's total.
+template <class Shared>
+__device__ __forceinline__ float icp_select_kth(Shared &S, const float *nn_d2, int ns, int tid, unsigned k_sel)
 {
-    return (!O.use_min_dist || d >= min2) && (!O.use_median || d <= med_limit);
+    if (tid == 0) {
+        S.sel_k = k_sel;
+        S.sel_prefix = 0;
+    }
+    __syncthreads();
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        if (tid < 256)
+            S.hist[tid] = 0;
+        __syncthreads();
+        const unsigned prefix = S.sel_prefix;
+        const unsigned himask = (shift == 24) ? 0u : (0xFFFFFFFFu << (shift + 8));
+        for (int i = tid; i < ns; i += ICP_THREADS) {
+            const float d = nn_d2[i];
+            if (d != INFINITY) {
+                const unsigned u = __float_as_uint(d); // d >= 0: bit pattern order == value order
+                if ((u & himask) == prefix)
+                    atomicAdd(&S.hist[(u >> shift) & 255u], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned k = S.sel_k, b = 0;
+            for (; b < 255; ++b) { // (b stops at 255: the shift below stays inside the word whatever the histogram holds)
+                const unsigned h = S.hist[b];
+                if (k < h)
+                    break;
+                k -= h;
+            }
+            S.sel_k = k;
+            S.sel_prefix = prefix | (b << shift);
+        }
+        __syncthreads();
+    }
+    return __uint_as_float(S.sel_prefix);
 }
 
 // BoundTransformationChecker on T_iter: rotation acosf(T00) (NaN when |T00| > 1: never out of bounds), translation

@@ -9,6 +9,8 @@ LO-HI of the source file the tool prints, in the order of the file: its head, de
 chain of the loop's instructions) and, with --mark A-B, how many of its instructions come from lines A-B (e.g. the lines
 that maintain the runner-up distance: which of two instances of a body a loop belongs to).
 usage: tools/icp_isa_loops.py out.s LO-HI [--kernel K = 0] [--file NAME = sfe_icp_sweep_loop.hip] [--min-share S = 0.5]
+                              [--symbol PREFIX = _Z16icp_sweep_kernel]  (another file's kernel: its mangled name's beginning,
+                              e.g. --file sfe_icp3.hip --symbol _Z15icp3_job_kernelILi3ELi0E)
                               [--mark A-B] [--max-insts N --max-vector M [--unmarked-only]]
 With --max-insts / --max-vector the exit status is 1 if a listed loop (with --unmarked-only: one without marked
 instructions) is larger, or if nothing is listed."""
@@ -23,9 +25,9 @@ def span(s):
     return int(lo), int(hi)
 
 
-def loops_of(lines, which, fname):
-    """-> [dict(head, depth, insts, vector, lines Counter, chains Counter)] of the which-th icp_sweep_kernel"""
-    st = [i for i, l in enumerate(lines) if l.startswith('_Z16icp_sweep_kernel')][which]
+def loops_of(lines, which, fname, symbol='_Z16icp_sweep_kernel'):
+    """-> [dict(head, depth, insts, vector, lines Counter, chains Counter)] of the which-th kernel whose name begins with symbol"""
+    st = [i for i, l in enumerate(lines) if l.startswith(symbol)][which]
     en = [i for i, l in enumerate(lines) if i > st and l.startswith('.Lfunc_end')][0]
     files = {}                # (the file table is the translation unit's: its entries stand wherever they were first needed)
     for l in lines:
@@ -78,13 +80,14 @@ def main():
     ap.add_argument('range', type=span)
     ap.add_argument('--kernel', type=int, default=0)
     ap.add_argument('--file', default='sfe_icp_sweep_loop.hip')
+    ap.add_argument('--symbol', default='_Z16icp_sweep_kernel')
     ap.add_argument('--min-share', type=float, default=0.5)
     ap.add_argument('--mark', type=span)
     ap.add_argument('--max-insts', type=int)
     ap.add_argument('--max-vector', type=int)
     ap.add_argument('--unmarked-only', action='store_true')
     a = ap.parse_args()
-    name, loops = loops_of(open(a.asm).read().split('\n'), a.kernel, a.file)
+    name, loops = loops_of(open(a.asm).read().split('\n'), a.kernel, a.file, a.symbol)
     print(name)
     lo, hi = a.range
     shown, bad = 0, 0
